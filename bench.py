@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: Mpixels/s forward+backward at 1920x1080 / 1M triangles.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one forward + one backward of the render op (`_C.render_forward_cuda` +
@@ -20,6 +20,11 @@ Rank 0 prints ONE JSON line (contract in the task statement) with two extra obje
 `roofline` (dominant kernel, algorithmic bytes / live hipEvent duration) and
 `cpu_baseline` (the CPU oracle -- a port, the reference has no CPU path -- on a bounded
 band of the same frame, on this host's cores).
+
+--dump-outputs DIR: rank 0 writes what the last timed step returned -- the op's colour and depth of its
+band and the gradients the step hands back -- as DIR/<name>.npy (float32).  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.  Arrays too large for the 64 MB
+budget are stored as a fixed, seeded sample of their flattened elements (sorted indices; see dump_outputs).
 """
 from __future__ import annotations
 
@@ -28,6 +33,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -288,6 +294,36 @@ VALU_PEAK_GINSTR_PER_S_PER_SIMD = 1.05   # measured on this part (tools/calib/va
                                          # (one wave alone: 0.48; v_fma 0.83; DPP / v_min3 / v_bcnt 0.57; IEEE fp32 divide 0.056)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+# what a step returns: the op's six gradients (world 1, DM2_BENCH_REDUCE=op6) or the leaf gradients (N > 1 otherwise)
+STEP_OUTPUT_NAMES = {
+    6: ("dL_dverts", "dL_dverts_color", "dL_dfaces_opacity", "dL_dverts_ndc", "dL_dfaces_intense", "dL_daa_face_verts"),
+    4: ("dL_dverts", "dL_dverts_color", "dL_dfaces_opacity", "dL_dfaces_intense"),
+}
+
+
+def dump_outputs(dirname, named):
+    """Write each (name, tensor) as dirname/<name>.npy in float32, all of them within DUMP_BUDGET_BYTES.  Smallest first,
+    every array gets an equal share of what is left; one larger than its share is stored as the elements of its
+    flattened form at sorted indices drawn without replacement by a generator seeded with the name (the same shapes
+    give the same indices on every run).  -> {name: {"shape", "stored", "sampled"}} for the result line."""
+    os.makedirs(dirname, exist_ok=True)
+    left = (DUMP_BUDGET_BYTES - 4096 * len(named)) // 4          # elements; 4 KB per file for the .npy header
+    info = {}
+    order = sorted(named, key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(order):
+        a = t.detach().to(torch.float32).cpu().numpy()
+        cap = left // (len(order) - i)
+        sampled = a.size > cap
+        if sampled:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.size
+        info[name] = {"shape": list(t.shape), "stored": int(a.size), "sampled": sampled}
+    return info
+
+
 def _visible_gpus():
     """GPUs of this node as the kernel driver lists them (KFD topology nodes with SIMDs), without touching the HIP runtime;
     None when sysfs does not say (the ranks then find out themselves)."""
@@ -345,7 +381,13 @@ def main():
                     help="AA temperature of the workload (1.0 = BASELINE; 0.0 = point-sampled coverage, SURVEY 8(d) asks for both)")
     ap.add_argument("--cpu-rows", type=int, default=1088,
                     help="rows of the frame the CPU baseline renders (default: the whole 1080p frame, a few seconds on a 128-thread host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     opt = ap.parse_args()
+    if opt.steps < 1:
+        ap.error("--steps must be at least 1")
+    if opt.dump_outputs:
+        opt.dump_outputs = os.path.abspath(opt.dump_outputs)      # (the ranks of a self-launched job may start elsewhere)
     if opt.config in VIEWS or opt.config in DEPTH_COMPLEXITY:
         opt.no_cpu = True              # (the side legs -- host prep, end to end, CPU baseline -- belong to the BASELINE configs)
     global AA_TEMPERATURE
@@ -465,8 +507,9 @@ def main():
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(opt.steps + 1)]
     t0 = time.perf_counter()
     evs[0].record()
+    last = None
     for i in range(opt.steps):
-        step()
+        last = step()
         evs[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
@@ -477,6 +520,12 @@ def main():
     ms_step = dt / opt.steps * 1e3
     ev_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(opt.steps))
     ms_median = ev_ms[len(ev_ms) // 2] if ev_ms else 0.0
+    dumped = None
+    if opt.dump_outputs and rank == 0:
+        # (before any other step runs: the op may reuse its output buffers)
+        named = [("color", op.fwd[1]), ("depth", op.fwd[2])] if op.fwd is not None else []
+        named += list(zip(STEP_OUTPUT_NAMES[len(last)], last))
+        dumped = dump_outputs(opt.dump_outputs, named)
 
     # per-stage hipEvent timing of the same step (separate passes so the events do not perturb `value`)
     _C.profile_enable(True)
@@ -572,6 +621,8 @@ def main():
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": cfg, "roofline": roofline,
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": opt.dump_outputs, "arrays": dumped}
         if world == 1 and not opt.no_cpu:
             cfg["host_prep_ms_not_in_value"] = host_prep_ms(opt.config, device)
             cfg["end_to_end_ms_not_in_value"] = end_to_end_ms(opt.config, device)
