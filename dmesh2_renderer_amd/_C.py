@@ -495,7 +495,7 @@ def render_backward_cuda(*args):
             # scratch of this call: the queue of the pairs whose AA Jacobian the exact clipper has to supply -- room for one entry
             # per pair of the binning buffer's pool part (written only for the 1-5 % that are ties)
             tie_buf = None
-            if mode in (FWD_POOL, FWD_UNKNOWN) and d.aa_temperature > 0.0 and not (d.flags & DM2_FLAG_LEGACY_KERNELS):
+            if mode not in (FWD_MASKS, FWD_NONE) and d.aa_temperature > 0.0 and not (d.flags & DM2_FLAG_LEGACY_KERNELS):
                 pool_pairs = max(0, bin_buf.numel() - lib.dm2_scratch_bytes(SCRATCH_BINNING, num_rendered, _tiles(B, W, H))) // 4
                 if pool_pairs > 0:
                     tie_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_TIE_QUEUE, pool_pairs, 0))

@@ -311,8 +311,11 @@ int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward
         tie_queue = c.take<dm2::TieEntry>(0);
         tie_cap = (int64_t)((tie_bytes - c.used(tie_scratch)) / sizeof(dm2::TieEntry));
     }
-    if (forward_mode == DM2_FWD_POOL && d->aa_temperature > 0.0f && !(d->flags & DM2_FLAG_LEGACY_KERNELS)) {
-        if (bs.pool_cap <= 0) return fail("forward_mode is DM2_FWD_POOL but the binning scratch has no pool part");
+    // the routes of dm2_backward.hip's table that reach the pool kernel: told DM2_FWD_POOL, or the cascade at temperature > 0
+    const bool pool_route = d->aa_temperature > 0.0f && !(d->flags & DM2_FLAG_LEGACY_KERNELS) &&
+                            (forward_mode == DM2_FWD_POOL || forward_mode == DM2_FWD_UNKNOWN || forward_mode == DM2_FWD_POINT);
+    if (pool_route) {
+        if (forward_mode == DM2_FWD_POOL && bs.pool_cap <= 0) return fail("forward_mode is DM2_FWD_POOL but the binning scratch has no pool part");
         if (tie_cap < bs.pool_cap) return fail("tie scratch too small for the pool part of the binning scratch");
     }
     dm2::launch_render_backward(*d, is.ranges, bs.face_list, is, dL_dout_color, dL_dout_depth, dL_dverts, dL_dverts_color,

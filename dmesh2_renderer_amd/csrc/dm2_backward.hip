@@ -1,9 +1,12 @@
 // dm2_backward.hip -- visibility / colour / depth gradients of the composite
-// (BACKWARD::renderCUDA<3>, backward.cu:17-532) for gfx950.
+// (BACKWARD::renderCUDA<3>, backward.cu:17-532) for gfx950: the per-pixel walk
+// k_render_backward, and the table that picks the backward kernels of a frame
+// (launch_render_backward, at the end).
 //
-// Same tiling as the forward: one 256-thread workgroup per 16x16 tile, the
-// tile's face list walked back to front in chunks staged in LDS.  Two things
-// differ from the reference by design:
+// k_render_backward is the fallback: it runs under DM2_FLAG_LEGACY_KERNELS and
+// after a forward that left no blend masks.  Same tiling as the forward: one
+// 256-thread workgroup per 16x16 tile, the tile's face list walked back to
+// front in chunks staged in LDS.  Two things differ from the reference by design:
 //   * AA records are not stored by the forward; the overlap area and its
 //     Jacobian are recomputed here (the reference's own K=0 path,
 //     backward.cu:264-272).  Recomputed values are bit-identical to recorded
@@ -15,6 +18,7 @@
 //     chunk with (entry,component)-shaped global atomics.
 #include <hip/hip_runtime.h>
 
+#include "dm2_bwd_shared.h"
 #include "dm2_device_math.h"
 #include "dm2_stage.h"
 #include "dm2_state.h"
@@ -22,16 +26,7 @@
 namespace dm2 {
 
 constexpr int BWD_CHUNK = 128;
-constexpr int ACC_STRIDE = 32;     // floats per entry accumulator
-// accumulator slots
-constexpr int A_DV = 0;            // 9: dL/dverts of the 3 corners
-constexpr int A_DC = 9;            // 9: dL/dverts_color
-constexpr int A_DZ = 18;           // 3: dL/dverts_ndc[...,2]
-constexpr int A_OP = 21;           // dL/dfaces_opacity
-constexpr int A_IN = 22;           // dL/dfaces_intense
-constexpr int A_AA = 23;           // 6: dL/daa_face_verts
-constexpr int A_N = 29;
-constexpr int A_FLAG = 31;
+constexpr int ACC_STRIDE = 32;     // floats per entry accumulator (the M_* row of dm2_bwd_shared.h)
 
 __device__ __forceinline__ void lds_add(float* p, float v) { atomicAdd(p, v); }   // ds_add_f32, no return
 
@@ -42,9 +37,9 @@ k_render_backward(dm2_render_desc d, const uint2* __restrict__ ranges, const uin
                   float* __restrict__ dL_dfaces_opacity, float* __restrict__ dL_dverts_ndc,
                   float* __restrict__ dL_dfaces_intense, float* __restrict__ dL_daa_face_verts,
                   const uint32_t* __restrict__ skip_if_masks) {
-    // launched behind the mask-driven kernels when the caller did not know what the forward left (DM2_FWD_UNKNOWN): one of
-    // them did the work when the forward left masks
-    if (skip_if_masks && skip_if_masks[0] >= 2u) return;
+    // the last kernel of the device-side cascade (launch_render_backward): a mask-driven kernel did the work when the
+    // forward left masks of any kind
+    if (skip_if_masks && skip_if_masks[0] != 0u) return;
     __shared__ FaceRec recs[BWD_CHUNK];
     __shared__ float acc[BWD_CHUNK * ACC_STRIDE];
     __shared__ uint32_t s_max_lc;
@@ -188,103 +183,91 @@ k_render_backward(dm2_render_desc d, const uint2* __restrict__ ranges, const uin
                 const f3 dp2 = dL_diu * du2 + dL_div * dv2;
 
                 float* a = acc + j * ACC_STRIDE;
-                lds_add(a + A_DV + 0, dp0.x); lds_add(a + A_DV + 1, dp0.y); lds_add(a + A_DV + 2, dp0.z);
-                lds_add(a + A_DV + 3, dp1.x); lds_add(a + A_DV + 4, dp1.y); lds_add(a + A_DV + 5, dp1.z);
-                lds_add(a + A_DV + 6, dp2.x); lds_add(a + A_DV + 7, dp2.y); lds_add(a + A_DV + 8, dp2.z);
+                lds_add(a + M_DV + 0, dp0.x); lds_add(a + M_DV + 1, dp0.y); lds_add(a + M_DV + 2, dp0.z);
+                lds_add(a + M_DV + 3, dp1.x); lds_add(a + M_DV + 4, dp1.y); lds_add(a + M_DV + 5, dp1.z);
+                lds_add(a + M_DV + 6, dp2.x); lds_add(a + M_DV + 7, dp2.y); lds_add(a + M_DV + 8, dp2.z);
 #pragma unroll
-                for (int k = 0; k < 9; k++) lds_add(a + A_DC + k, dvc[k]);
-                lds_add(a + A_DZ + 0, dvd0); lds_add(a + A_DZ + 1, dvd1); lds_add(a + A_DZ + 2, dvd2);
-                lds_add(a + A_OP, dL_dfop);
-                lds_add(a + A_IN, dL_dfint);
+                for (int k = 0; k < 9; k++) lds_add(a + M_DC + k, dvc[k]);
+                lds_add(a + M_DZ + 0, dvd0); lds_add(a + M_DZ + 1, dvd1); lds_add(a + M_DZ + 2, dvd2);
+                lds_add(a + M_OP, dL_dfop);
+                lds_add(a + M_IN, dL_dfint);
 #pragma unroll
-                for (int k = 0; k < 6; k++) lds_add(a + A_AA + k, dL_doarea * dg[k]);
-                a[A_FLAG] = 1.0f;
+                for (int k = 0; k < 6; k++) lds_add(a + M_AA + k, dL_doarea * dg[k]);
+                a[M_FLAG] = 1.0f;
             }
         }
         __syncthreads();
 
         // flush: lane = (entry, component); 8 entries per pass
         const int comp = tid & 31;
-        if (comp < A_N) {
+        if (comp < M_N) {
             for (int e = tid >> 5; e < n; e += TILE_PIX / 32) {
                 const float* a = acc + e * ACC_STRIDE;
-                if (a[A_FLAG] == 0.f) continue;
+                if (a[M_FLAG] == 0.f) continue;
                 const FaceRec& fc = recs[e];
                 const float val = a[comp];
                 float* dst;
-                if (comp < A_DC) dst = dL_dverts + 3 * (int64_t)fc.vid[comp / 3] + (comp % 3);
-                else if (comp < A_DZ) dst = dL_dverts_color + 3 * (int64_t)fc.vid[(comp - A_DC) / 3] + ((comp - A_DC) % 3);
-                else if (comp < A_OP) dst = dL_dverts_ndc + ((int64_t)b * d.P + fc.vid[comp - A_DZ]) * 3 + 2;
-                else if (comp == A_OP) dst = dL_dfaces_opacity + fc.face_id;
-                else if (comp == A_IN) dst = dL_dfaces_intense + (int64_t)b * d.F + fc.face_id;
+                if (comp < M_DC) dst = dL_dverts + 3 * (int64_t)fc.vid[comp / 3] + (comp % 3);
+                else if (comp < M_DZ) dst = dL_dverts_color + 3 * (int64_t)fc.vid[(comp - M_DC) / 3] + ((comp - M_DC) % 3);
+                else if (comp < M_OP) dst = dL_dverts_ndc + ((int64_t)b * d.P + fc.vid[comp - M_DZ]) * 3 + 2;
+                else if (comp == M_OP) dst = dL_dfaces_opacity + fc.face_id;
+                else if (comp == M_IN) dst = dL_dfaces_intense + (int64_t)b * d.F + fc.face_id;
                 else if (d.flags & DM2_FLAG_AA_GRAD_TO_VERTS) {                  // corner -> the vertex the CCW reorder took it from
-                    const int c = (comp - A_AA) >> 1;
+                    const int c = (comp - M_AA) >> 1;
                     const bool flip = (fc.aa.zmask >> 8) & 1u;
-                    dst = dL_daa_face_verts + ((int64_t)b * d.P + fc.vid[c == 0 ? 0 : (flip ? 3 - c : c)]) * 2 + ((comp - A_AA) & 1);
+                    dst = dL_daa_face_verts + ((int64_t)b * d.P + fc.vid[c == 0 ? 0 : (flip ? 3 - c : c)]) * 2 + ((comp - M_AA) & 1);
                 }
-                else dst = dL_daa_face_verts + ((int64_t)b * d.F + fc.face_id) * 6 + (comp - A_AA);
+                else dst = dL_daa_face_verts + ((int64_t)b * d.F + fc.face_id) * 6 + (comp - M_AA);
                 atomicAdd(dst, val);
             }
         }
     }
 }
 
+// The backward kernels of a frame (fwd_mode: what the forward returned, DM2_FWD_*; "check": the kernel looks at
+// hit_valid[0] on the device and returns at once unless the forward left what it reads):
+//
+//   DM2_FLAG_LEGACY_KERNELS, or DM2_FWD_NONE        k_render_backward
+//   temperature 0,   DM2_FWD_POINT                  fast<POINT>                  (dm2_backward_fast.hip)
+//   temperature > 0, DM2_FWD_POOL                   fast<false> + k_aa_ties      (the default)
+//   temperature > 0, DM2_FWD_MASKS                  mask                         (dm2_backward_mask.hip)
+//   anything else: DM2_FWD_UNKNOWN, or a mode no    the device-side cascade --
+//   forward at this temperature returns (POINT at     temperature 0:  fast<POINT> (check) -> k_render_backward (check)
+//   temperature > 0, MASKS / POOL at temperature 0)   temperature > 0: fast<false> (check; only when the binning scratch
+//                                                     has a pool part) -> mask (check) -> k_render_backward (check)
+//
+// In the cascade exactly one kernel works for each value of hit_valid[0]: 1 (written only at temperature 0) fast<POINT>,
+// 2 mask, 3 (written only when a pool part exists, and dm2_backward then demands the tie scratch) fast<false>, 0
+// k_render_backward, which stands down on anything else.
 void launch_render_backward(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                             const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
                             float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
                             float* dL_daa_face_verts, const BinningState& bs, int fwd_mode, TieEntry* tie_queue, int64_t tie_cap,
                             hipStream_t st) {
-    const uint64_t* const hit_masks = bs.hit_masks; const uint32_t* const hit_valid = bs.hit_valid;
-    const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
-    const bool fast_only = !(d.flags & DM2_FLAG_LEGACY_KERNELS) && d.aa_temperature > 0.0f && hit_masks && hit_valid && fwd_mode == DM2_FWD_POOL &&
-                           bs.pool && bs.pool_cap > 0 && tie_queue && tie_cap > 0;
-    if (fast_only) {      // (times its two kernels as two stages)
+    const bool aa = d.aa_temperature > 0.0f;
+    auto fast = [&](bool check) {          // (times its kernels itself, unless checked: then the cascade is timed as one stage)
         launch_render_backward_fast(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color, dL_dfaces_opacity,
-                                    dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, tie_queue, tie_cap, false, st);
-        return;
-    }
+                                    dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, aa ? tie_queue : nullptr,
+                                    aa ? tie_cap : 0, check, st);
+    };
+    auto mask = [&]() {
+        launch_render_backward_mask(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color, dL_dfaces_opacity,
+                                    dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs.hit_masks, bs.hit_valid, st);
+    };
+    auto per_pixel = [&](const uint32_t* skip_if_masks) {
+        const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
+        hipLaunchKernelGGL(k_render_backward, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
+                           dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts,
+                           skip_if_masks);
+    };
+    const bool legacy = (d.flags & DM2_FLAG_LEGACY_KERNELS) != 0;
+    if (!legacy && fwd_mode == (aa ? DM2_FWD_POOL : DM2_FWD_POINT)) { fast(false); return; }
     StageTimer tm(ST_BWD, st);
-    if (!(d.flags & DM2_FLAG_LEGACY_KERNELS)) {
-        // aa_temperature == 0: no bbox test in the reference (backward.cu:241-244), every face of a tile's list meets
-        // all 256 pixels; the pair enumeration has nothing to prune there -> dm2_backward_point.hip (dense
-        // intersection test per wave, compacted hits for the gradient chain).  -DDM2_POINT_PER_PIXEL: the
-        // reference-shaped per-pixel walk below instead (A/B).
-#ifndef DM2_POINT_PER_PIXEL
-        if (!(d.aa_temperature > 0.0f)) {
-            if (fwd_mode == DM2_FWD_POINT && hit_masks && hit_valid) {
-                // the masks of this frame's dm2_forward_point.hip drive the same kernel as at temperature > 0 (coverage 1, no AA terms)
-                launch_render_backward_fast(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color, dL_dfaces_opacity,
-                                            dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, nullptr, 0, false, st);
-                return;
-            }
-            // (what the forward left is not known, or it left nothing: dm2_backward_point.hip looks at hit_valid itself and
-            // repeats the dense intersection test when the masks are not this frame's)
-            launch_render_backward_point(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color,
-                                         dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, hit_masks, hit_valid, st);
-            return;
-        }
-#endif
-        if (d.aa_temperature > 0.0f && hit_masks && hit_valid && fwd_mode != DM2_FWD_NONE) {
-            // What the forward left decides the kernel: masks + pool -> dm2_backward_fast.hip, masks -> dm2_backward_mask.hip,
-            // nothing -> the per-pixel walk.  A caller that says DM2_FWD_UNKNOWN gets all of them, each looking at hit_valid
-            // on the device (no host read-back) and all but one returning at once.
-            const bool unknown = fwd_mode == DM2_FWD_UNKNOWN;
-            const bool pool_ok = bs.pool && bs.pool_cap > 0 && tie_queue && tie_cap > 0;
-            if ((fwd_mode == DM2_FWD_POOL || unknown) && pool_ok)
-                launch_render_backward_fast(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color, dL_dfaces_opacity,
-                                            dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, tie_queue, tie_cap, unknown, st);
-            if (fwd_mode == DM2_FWD_MASKS || unknown)
-                launch_render_backward_mask(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color,
-                                            dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, hit_masks, hit_valid, st);
-            if (unknown)
-                hipLaunchKernelGGL(k_render_backward, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
-                                   dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, hit_valid);
-            return;
-        }
-    }
-    hipLaunchKernelGGL(k_render_backward, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
-                       dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts,
-                       (const uint32_t*)nullptr);
+    if (legacy || fwd_mode == DM2_FWD_NONE) { per_pixel(nullptr); return; }
+    if (aa && fwd_mode == DM2_FWD_MASKS) { mask(); return; }
+    if (!aa || bs.pool_cap > 0) fast(true);
+    if (aa) mask();
+    per_pixel(bs.hit_valid);
 }
 
 }  // namespace dm2

@@ -213,13 +213,9 @@ k_render_backward_mask(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         float i0 = 0.f, i1 = 0.f, i2 = 0.f, ratio = 0.f, alpha = 0.f;
         int code = 0;
         bool blend = false;
-#if DM2_BM_CARRY
         // carried from B2 into phase D in registers (phase C in between needs few): ray, world corners, colours, NDC z
         f3 k_ro = {0, 0, 0}, k_rd = {0, 0, 0}, k_p0 = {0, 0, 0}, k_p1 = {0, 0, 0}, k_p2 = {0, 0, 0};
-#if DM2_BM_CARRY > 1
         float k_col[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, k_dep[3] = {0, 0, 0}, k_int = 0.f, k_opa = 0.f;
-#endif
-#endif
         if (have) {
             const int lo = (int)(mk >> 9) - 1;                                    // the slot of pair tid, first pair mk & 511
             j = lo >> 2;
@@ -247,14 +243,10 @@ k_render_backward_mask(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             const f3 rd = {s_ray[q * 6 + 3], s_ray[q * 6 + 4], s_ray[q * 6 + 5]};
             const f3 p0 = {fc.v[0], fc.v[1], fc.v[2]}, p1 = {fc.v[3], fc.v[4], fc.v[5]}, p2 = {fc.v[6], fc.v[7], fc.v[8]};
             f3 tuv = {0, 0, 0};
-#if DM2_BM_CARRY
             k_ro = ro; k_rd = rd; k_p0 = p0; k_p1 = p1; k_p2 = p2;
-#if DM2_BM_CARRY > 1
 #pragma unroll
             for (int c = 0; c < 9; c++) k_col[c] = fc.col[c];
             k_dep[0] = fc.dep[0]; k_dep[1] = fc.dep[1]; k_dep[2] = fc.dep[2]; k_int = fc.intense; k_opa = fc.opacity;
-#endif
-#endif
             if (ray_tri_intersection(ro, rd, p0, p1, p2, tuv)) {
                 float iuc, ivc;
                 clamp_bary_uv(tuv.y, tuv.z, iuc, ivc, code);
@@ -356,9 +348,6 @@ k_render_backward_mask(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             seg_scan16(nact, s1, s2, s4, s8);
             const bool emit = ((l16 == 15) | (kn != jkey)) & (jkey >= 0) & (nact > 0.f);
             float* const arow = acc + j * BM_ACC;
-#if DM2_BM_CARRY < 2
-            const FaceRec& fcD = recs[j];
-#endif
             float dL_diu = 0.f, dL_div = 0.f, dL_doarea = 0.f;
             {   // group 1: vertex colours, NDC depth, intensity, opacity
                 float g1[14];
@@ -367,13 +356,8 @@ k_render_backward_mask(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 if (active) {
                     const float Tq = pr.T, dL_dalpha = pr.dL_dalpha;
                     const float qc0 = pr.c0, qc1 = pr.c1, qc2 = pr.c2, qd = pr.depth;   // dL/dcolour, dL/ddepth of the pixel
-#if DM2_BM_CARRY > 1
                     const float intense = k_int, opacity = k_opa;
                     const float* const colD = k_col; const float* const depD = k_dep;
-#else
-                    const float intense = fcD.intense, opacity = fcD.opacity;
-                    const float* const colD = fcD.col; const float* const depD = fcD.dep;
-#endif
                     const float dics[3] = {qc0 * alpha * Tq, qc1 * alpha * Tq, qc2 * alpha * Tq};
                     const float did = qd * alpha * Tq;
                     g1[12] = dL_dalpha * ratio;
@@ -425,13 +409,7 @@ k_render_backward_mask(dm2_render_desc d, const uint2* __restrict__ ranges, cons
 #pragma unroll
                 for (int c = 0; c < 9; c++) g3[c] = 0.f;
                 if (active) {
-#if DM2_BM_CARRY
                     const f3 ro = k_ro, rd = k_rd, p0 = k_p0, p1 = k_p1, p2 = k_p2;
-#else
-                    const f3 ro = {s_ray[q * 6], s_ray[q * 6 + 1], s_ray[q * 6 + 2]};
-                    const f3 rd = {s_ray[q * 6 + 3], s_ray[q * 6 + 4], s_ray[q * 6 + 5]};
-                    const f3 p0 = {fcD.v[0], fcD.v[1], fcD.v[2]}, p1 = {fcD.v[3], fcD.v[4], fcD.v[5]}, p2 = {fcD.v[6], fcD.v[7], fcD.v[8]};
-#endif
                     f3 du0, du1, du2, dv0, dv1, dv2;
                     ray_tri_intersection_grad(ro, rd, p0, p1, p2, corrected, du0, du1, du2, dv0, dv1, dv2);
                     const f3 dp0 = dL_diu * du0 + dL_div * dv0;
@@ -472,11 +450,7 @@ k_render_backward_mask(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 if (flag != 0.f) {
                     a[comp] = 0.f;                                                // ready for the next chunk
                     if (comp == 0) a[M_FLAG] = 0.f;
-#if !defined(DM2_BM_FLUSH_MODE) || DM2_BM_FLUSH_MODE == 0
                     atomicAdd(basep + (int64_t)id * mult, val);
-#else
-                    if (val == 12345.678f) basep[(int64_t)id * mult] = val;     // timing experiment only: no global traffic
-#endif
                 }
             }
         }

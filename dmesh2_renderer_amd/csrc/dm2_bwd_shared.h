@@ -1,13 +1,11 @@
-// dm2_bwd_shared.h -- constants, pair record and small helpers of the mask-driven backward kernel (dm2_backward_mask.hip).
+// dm2_bwd_shared.h -- accumulator-row layout, pair records and small helpers of the backward kernels (dm2_backward_mask.hip,
+// dm2_backward_fast.hip; dm2_backward.hip uses the row layout with its own pitch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace dm2 {
 
-#ifndef DM2_BM_CARRY
-#define DM2_BM_CARRY 2         // phase D takes ray, corners, colours, NDC z of its pair from phase B2 in registers (0: re-reads LDS; A/B at cfg4: -3.7 %)
-#endif
 #ifndef DM2_BM_ACC
 #define DM2_BM_ACC 33       // odd pitch: the emit lanes of different faces add to different LDS banks (A/B at cfg4: 32 -> 33, -0.4 %)
 #endif

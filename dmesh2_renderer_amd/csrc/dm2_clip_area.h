@@ -127,9 +127,6 @@ __device__ __forceinline__ int clip_area_classified(const AAFace& f, float pxmin
                                                     uint32_t inside, float pix_area, float& area) {
     area = 0.f;
     if (inside == 0xF) { area = pix_area; return 0; }
-#ifdef DM2_ABLATE_CLIP   // diagnostic only: price of the polygon clip
-    area = 0.5f * pix_area; return 0;
-#endif
     FanState S;
     S.fx = S.fy = S.px = S.py = 0.f; S.area = 0.f; S.cnt = 0; S.err = false;
     clip_edge_area<0>(f, pxmin, pxmax, pymin, pymax, inside, S);

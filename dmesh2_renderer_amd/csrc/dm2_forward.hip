@@ -125,13 +125,10 @@ int launch_render_forward(const dm2_render_desc& d, const uint2* ranges, const u
         // aa_temperature == 0: the reference applies no bbox test (forward.cu:314), every face of a tile's list meets
         // all 256 pixels: the per-pixel walk is the dense formulation there.  dm2_forward_point.hip is that walk with
         // one extra product: the per-(entry, wave) hit masks the backward would otherwise have to recompute.
-        // -DDM2_POINT_PER_PIXEL: the plain walk below instead (A/B).
-#ifndef DM2_POINT_PER_PIXEL
         if (hit_masks && hit_valid) {
             launch_render_forward_point(d, ranges, face_list, is, out_color, out_depth, out_tri_cnt, hit_masks, hit_valid, st);
             return DM2_FWD_POINT;
         }
-#endif
     }
     // (hit_valid was reset by the binning of this forward, dm2_binning.hip: no masks from this path)
     const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);

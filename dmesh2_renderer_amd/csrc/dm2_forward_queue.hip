@@ -259,11 +259,7 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         // pair pool: the chunk takes one slot per survivor (>= the pairs that blend) -- one atomic per chunk, issued here and
         // looked at behind B2
         uint32_t cbase = 0;
-#if defined(DM2_FQ_POOL_EXP) && DM2_FQ_POOL_EXP == 1     // timing experiment only: no allocation
-        if (pool && tid == 0) cbase = (tile * 4096u + (uint32_t)base * 16u) % (pool_cap - 600u);
-#else
         if (pool && tid == 0) cbase = atomicAdd(hit_valid + 1, (uint32_t)S);
-#endif
         // ---- phase B2: one survivor per lane ------------------------------------------------
         // Pool: a blending survivor's slot is the chunk's first slot + its rank among the chunk's blending survivors -- record
         // order is (entry, pixel) order, the order of the masks.  Without classes the lanes run in record order: a ballot per

@@ -183,7 +183,8 @@ int dm2_forward(const dm2_render_desc* d, void* face_scratch, size_t face_bytes,
  * dL_dverts_ndc (B,P,3) [only z written], dL_dfaces_intense (B,F),
  * dL_daa_face_verts (B,F,3,2).
  * forward_mode: what the forward of this frame returned (DM2_FWD_*; DM2_FWD_UNKNOWN costs a few idle launches).
- * tie_scratch: needed with DM2_FWD_POOL (and with DM2_FWD_UNKNOWN when the binning scratch has a pool part):
+ * tie_scratch: needed with DM2_FWD_POOL (and, when the binning scratch has a pool part, with DM2_FWD_UNKNOWN or
+ * DM2_FWD_POINT at aa_temperature > 0):
  * dm2_scratch_bytes(DM2_SCRATCH_TIE_QUEUE, pairs of the pool part, 0) bytes, scratch of this call only.  The binning
  * scratch is not const: the pool backward keeps its queue counters there (left as it found them). */
 int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode,

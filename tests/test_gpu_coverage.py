@@ -1,6 +1,7 @@
 """GPU cases that close the coverage holes of the round-1 review: BASELINE configs[0] at full size on the HIP path,
 the device-side fallback of the backward dispatch, the corrected-gradient flag on the device, and the one gradient
 mismatch the randomised sweep ever recorded, pinned down to a summation-order bound."""
+import contextlib
 import os
 import sys
 
@@ -89,8 +90,8 @@ def test_cfg1_full_size(kernels):
 @pytest.mark.parametrize("temp", [1.0, 0.5, 0.0])
 def test_backward_without_forward_masks(temp):
     """Forward with the per-pixel-walk kernels (no blend masks; the binning resets hit_valid), backward with the default
-    flags: dm2_backward_mask.hip / the mask path of dm2_backward_point.hip must stand down on the device and the
-    fallbacks (k_render_backward, the dense test of dm2_backward_point.hip) must produce the gradients."""
+    flags: the mask-driven kernels (dm2_backward_mask.hip, dm2_backward_fast.hip) must stand down on the device and the
+    fallback (k_render_backward) must produce the gradients."""
     C, orc = _C(), _orc()
     args = _soup(96, 80, 700, 21, temp)
     rng = np.random.RandomState(5)
@@ -300,13 +301,25 @@ def test_aa_gradient_routing_does_not_depend_on_the_forwards_flags():
 
 
 # ---- every route from a forward to its backward kernel -----------------------------------------------------------
-@pytest.mark.parametrize("route", ["pool", "masks_only", "unknown_with_pool", "unknown_masks_only", "told_wrong_object"])
+@pytest.mark.parametrize("route", ["pool", "masks_only", "unknown_with_pool", "unknown_masks_only", "told_wrong_object",
+                                   "point", "unknown_point", "mismatched"])
 def test_backward_kernel_selection(route):
     """The backward's kernel follows what the forward left (include/dm2_hip.h DM2_FWD_*): masks + pair pool -> the polygon-free
-    kernel + tie pass; masks only (the caller gave the pool no room) -> the exact-clipper mask kernel; not told -> every
-    candidate is launched and looks at the device-side word itself.  Same gradients on every route."""
+    kernel + tie pass; masks only (the caller gave the pool no room) -> the exact-clipper mask kernel; point-sampled masks
+    (temperature 0) -> the POINT instantiation of the polygon-free kernel; not told, or told a mode that no forward at this
+    temperature returns -> the candidates are launched and look at the device-side word themselves (exactly one works: a
+    wrong stand-down rule would double the gradients).  Same gradients on every route."""
+    C = _C()
+    if route == "mismatched":
+        _selection_route(1.0, "pool", told=C.FWD_POINT)
+        _selection_route(0.0, "point", told=C.FWD_POOL)
+    else:
+        _selection_route(0.0 if "point" in route else 1.0, route)
+
+
+def _selection_route(temp, route, told=None):
     C, orc = _C(), _orc()
-    args = _soup(96, 64, 500, 64, 1.0)
+    args = _soup(96, 64, 500, 64, temp)
     dargs = _dev(args)
     ref = orc.render_forward_cuda(*to_numpy_args(args))
     rng = np.random.default_rng(8)
@@ -319,18 +332,19 @@ def test_backward_kernel_selection(route):
         out = C.render_forward_cuda(*dargs)
     finally:
         C._pool_budget = budget
-    assert C.last_forward_mode() == (C.FWD_MASKS if "masks_only" in route else C.FWD_POOL)
+    want_mode = C.FWD_POINT if "point" in route else (C.FWD_MASKS if "masks_only" in route else C.FWD_POOL)
+    assert C.last_forward_mode() == want_mode
     assert np.array_equal(out[1].cpu().numpy().view(np.uint32), ref.color.view(np.uint32))
     bin_buf = out[8]
     if route.startswith("unknown") or route == "told_wrong_object":
         bin_buf = out[8].clone()                                # another tensor object: the shim's note of the mode is gone
         assert not hasattr(bin_buf, "_dm2_fwd_mode")
     tgc, tgd = torch.from_numpy(gc).cuda(), torch.from_numpy(gd).cuda()
-    g = C.render_backward_cuda(out[0], *dargs, tgc, tgd, out[7], bin_buf, out[9], out[3], out[4], out[5], out[6])
-    _check_grads([x.cpu().numpy() for x in g], gref)
     # a second backward of the same forward (retain_graph): the tie queue's counters were left as they were found
-    g2 = C.render_backward_cuda(out[0], *dargs, tgc, tgd, out[7], bin_buf, out[9], out[3], out[4], out[5], out[6])
-    _check_grads([x.cpu().numpy() for x in g2], gref)
+    for _ in range(2):
+        with (C.forward_mode(told) if told is not None else contextlib.nullcontext()):
+            g = C.render_backward_cuda(out[0], *dargs, tgc, tgd, out[7], bin_buf, out[9], out[3], out[4], out[5], out[6])
+        _check_grads([x.cpu().numpy() for x in g], gref)
 
 
 # ---- the composite kernels' block -> tile order is only an order of execution ---------------------------------------------
