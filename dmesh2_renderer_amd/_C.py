@@ -362,6 +362,12 @@ def last_forward_mode():
     return getattr(_tls, "last_fwd_mode", FWD_UNKNOWN)
 
 
+def last_pair_bound():
+    """The pair bound the plan of the calling thread's most recent render_forward_cuda counted: the (pixel, face) pairs its
+    composite may enumerate, which sized the pair pool of the binning buffer (0 when nothing was planned)."""
+    return getattr(_tls, "last_pair_bound", 0)
+
+
 def _pool_budget(N, R):
     """Pairs the shim is willing to give pool room to (4 B each in the binning buffer + 16 B each of backward scratch, 8 GB at
     the cap): a frame whose plan counts more candidate pairs than this -- hundreds of faces over every pixel of a large image,
@@ -411,6 +417,7 @@ def render_forward_cuda(*args):
             color.zero_(); depth.zero_()
             tri_cnt = torch.zeros((B, H, W), dtype=i32, device=dev)
             e = _bytes(dev, 0)
+            _tls.last_pair_bound = 0
             return 0, color, depth, oarea, tri_id, tri_cnt, doarea, e, _bytes(dev, 0), _bytes(dev, 0)
         tri_cnt = torch.empty((B, H, W), dtype=i32, device=dev)
         face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn + 1))
@@ -451,6 +458,7 @@ def render_forward_cuda(*args):
                     _bin_hint.clear()
                 _bin_hint[key] = need + need // 4
     _tls.last_fwd_mode = int(mode.value)
+    _tls.last_pair_bound = int(pairs.value)
     bin_buf._dm2_fwd_mode = int(mode.value)       # (survives only as long as this very tensor object is passed around)
     return R, color, depth, oarea, tri_id, tri_cnt, doarea, face_buf, bin_buf, img_buf
 

@@ -136,9 +136,10 @@ __device__ __forceinline__ void store_records(const FaceRec& r, bool has, unsign
 }
 
 // PACK: also write the face's packed record (dm2_stage.h) for the composite kernels -- only for faces that reach a
-// tile list.  `d` is read only then.  (A/B at cfg4: packing in a kernel of its own behind the plan's read-back, so that
-// it runs while the host sizes and enqueues the run step, costs more than it hides -- the binning part alone is bound by
-// its atomics, 0.08 ms, which here disappear behind the record traffic: 0.16 ms fused against 0.08 + 0.13 ms split.)
+// tile list.  `d` is read only then, and for the pair bound (its flags; the caller's aa_face_verts).  (A/B at cfg4:
+// packing in a kernel of its own behind the plan's read-back, so that it runs while the host sizes and enqueues the run
+// step, costs more than it hides -- the binning part alone is bound by its atomics, 0.08 ms, which here disappear behind
+// the record traffic: 0.16 ms fused against 0.08 + 0.13 ms split.)
 #ifndef DM2_PRE_WAVES
 #define DM2_PRE_WAVES 1
 #endif
@@ -242,14 +243,27 @@ k_preprocess(int B, int P, int F, uint32_t gx, uint32_t gy, uint32_t block_strid
         // Upper bound of the (pixel, face) pairs the forward composite will enumerate for this face: the patch pixels whose
         // unit square passes the clipper's bounding-box test (aa.h:96-101; dm2_pairs.h face_pixel_rect, tile by tile).  The
         // sum over the faces sizes the forward's pair pool (dm2_state.h), read back with num_rendered.
+        // The clipper's box is that of the AA corners (pack_face: aa.bb), the tiles are those of verts_image.  Tables built
+        // from verts_image have the image triangle's box.  Tables read from memory are the caller's, and their box may be
+        // larger: then the box is theirs, cut to the face's tile rectangle widened by one pixel per side (for tables of the
+        // image triangle that cut removes nothing: the bound is the same number either way).
         unsigned long long cand = 0;
         if (touched != 0) {
-            const float bx0 = fminf(fminf(i0.x, i1.x), i2.x), bx1 = fmaxf(fmaxf(i0.x, i1.x), i2.x);
-            const float by0 = fminf(fminf(i0.y, i1.y), i2.y), by1 = fmaxf(fmaxf(i0.y, i1.y), i2.y);
+            float bx0 = fminf(fminf(i0.x, i1.x), i2.x), bx1 = fmaxf(fmaxf(i0.x, i1.x), i2.x);
+            float by0 = fminf(fminf(i0.y, i1.y), i2.y), by1 = fmaxf(fmaxf(i0.y, i1.y), i2.y);
+            float tx0 = -1.0f, tx1 = 3.0e38f, ty0 = -1.0f, ty1 = 3.0e38f;
+            if (!(d.flags & DM2_FLAG_TABLES_FROM_IMAGE)) {
+                const float* av = d.aa_face_verts + idx * 6;                 // (the corners pack_face reads for this record)
+                bx0 = fminf(fminf(av[0], av[2]), av[4]); bx1 = fmaxf(fmaxf(av[0], av[2]), av[4]);
+                by0 = fminf(fminf(av[1], av[3]), av[5]); by1 = fmaxf(fmaxf(av[1], av[3]), av[5]);
+                tx0 = (float)((lo & 0xFFFFu) * TILE) - 1.0f; tx1 = (float)((hi & 0xFFFFu) * TILE);
+                ty0 = (float)((lo >> 16) * TILE) - 1.0f; ty1 = (float)((hi >> 16) * TILE);
+            }
             if (bx0 == bx0 && bx1 == bx1 && by0 == by0 && by1 == by1) {
                 const float Wm = (float)(gx * TILE), Hm = (float)(gy * TILE);          // (>= the patch: an upper bound is all that is asked)
-                const float lo_x = fminf(fmaxf(ceilf(bx0) - 1.0f - (float)pmx, 0.0f), Wm), hi_x = fminf(fmaxf(floorf(bx1) - (float)pmx, -1.0f), Wm - 1.0f);
-                const float lo_y = fminf(fmaxf(ceilf(by0) - 1.0f - (float)pmy, 0.0f), Hm), hi_y = fminf(fmaxf(floorf(by1) - (float)pmy, -1.0f), Hm - 1.0f);
+                float lo_x = fminf(fmaxf(ceilf(bx0) - 1.0f - (float)pmx, 0.0f), Wm), hi_x = fminf(fmaxf(floorf(bx1) - (float)pmx, -1.0f), Wm - 1.0f);
+                float lo_y = fminf(fmaxf(ceilf(by0) - 1.0f - (float)pmy, 0.0f), Hm), hi_y = fminf(fmaxf(floorf(by1) - (float)pmy, -1.0f), Hm - 1.0f);
+                lo_x = fmaxf(lo_x, tx0); hi_x = fminf(hi_x, tx1); lo_y = fmaxf(lo_y, ty0); hi_y = fminf(hi_y, ty1);
                 const float w = hi_x - lo_x + 1.0f, h = hi_y - lo_y + 1.0f;
                 if (w > 0.0f && h > 0.0f) cand = (unsigned long long)w * (unsigned long long)h;
             }

@@ -2,7 +2,9 @@
 """Randomised parity sweep of the HIP path against the CPU oracle (both through the reference's `_C` surface):
 random image sizes, triangle counts, depth complexity, temperature, K, cameras, patch windows and opacities.
 Forward must be bit-exact, gradients within 1e-5 relative L_inf.  `python tests/fuzz_parity.py [seconds] [seed]`.
-A development tool (needs a GPU); the fixed cases of tests/test_gpu_parity.py are the gate."""
+A development tool (needs a GPU); the fixed cases of tests/test_gpu_parity.py are the gate.
+DM2_FUZZ_TEMP0=1: temperature 0 only.  DM2_FUZZ_FROM_IMAGE=1: the AA tables built by the op from verts_image."""
+import contextlib
 import os
 import sys
 import time
@@ -13,7 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from util import capture_forward_args, rel_linf, scenes, to_numpy_args  # noqa: E402
+from util import capture_forward_args, from_image_oracle_args, rel_linf, scenes, to_numpy_args  # noqa: E402
 from dmesh2_renderer_amd import _C  # noqa: E402
 from oracle import cpu as orc  # noqa: E402
 
@@ -43,15 +45,24 @@ def one_case(seed, idx, verbose=False):
     desc = dict(W=W, H=H, F=F, dc=dc, temp=temp, K=K, cams=cams, bidx=bidx, pw=pw, ph=ph, pm=pm)
     args, _ = capture_forward_args(sc, bidx, pm, pw, ph, temp, K)
     dargs = [a.cuda() if torch.is_tensor(a) else a for a in args]
-    out = _C.render_forward_cuda(*dargs)
-    ref = orc.render_forward_cuda(*to_numpy_args(args), nthreads=orc.max_threads())
+    # DM2_FUZZ_FROM_IMAGE=1: the same sweep with the AA tables built by the plan from verts_image (placeholder tables, as
+    # bench.py runs the op); the oracle gets the tables the reference builds from verts_image
+    from_image = os.environ.get("DM2_FUZZ_FROM_IMAGE") == "1"
+    ctx = (lambda: _C.tables_from_image(True)) if from_image else contextlib.nullcontext
+    if from_image:
+        from dmesh2_renderer_amd.sharding import BandShardedOp
+        dargs = BandShardedOp(dargs, 1, 0, tables_from_image=True).args
+    with ctx():
+        out = _C.render_forward_cuda(*dargs)
+    ref = orc.render_forward_cuda(*(from_image_oracle_args(args) if from_image else to_numpy_args(args)), nthreads=orc.max_threads())
     ok = np.array_equal(out[1].cpu().numpy().view(np.uint32), ref.color.view(np.uint32)) and \
         np.array_equal(out[2].cpu().numpy().view(np.uint32), ref.depth.view(np.uint32)) and \
         np.array_equal(out[5].cpu().numpy(), ref.buf_tri_cnt) and int(out[0]) == int(ref.num_rendered)
     gc = rng.standard_normal(ref.color.shape).astype(np.float32)
     gd = rng.standard_normal(ref.depth.shape).astype(np.float32)
-    g = _C.render_backward_cuda(out[0], *dargs, torch.from_numpy(gc).cuda(), torch.from_numpy(gd).cuda(),
-                                out[7], out[8], out[9], out[3], out[4], out[5], out[6])
+    with ctx():
+        g = _C.render_backward_cuda(out[0], *dargs, torch.from_numpy(gc).cuda(), torch.from_numpy(gd).cuda(),
+                                    out[7], out[8], out[9], out[3], out[4], out[5], out[6])
     gref = orc.render_backward_cuda(ref, gc, gd, nthreads=orc.max_threads())
     worst = max(rel_linf(x.cpu().numpy(), gref[n]) for x, n in zip(g, GRAD_NAMES))
     if verbose:

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import ROOT, capture_forward_args, rel_linf, scenes, soup_args, to_numpy_args
+from util import ROOT, capture_forward_args, check_from_image, rel_linf, scenes, soup_args, to_numpy_args
 
 pytestmark = pytest.mark.gpu
 
@@ -58,14 +58,23 @@ def _soup(W, H, F, seed, temp, K=20, dc=4.0):
 
 
 # ---- BASELINE configs[0]: 256 x 256, 2 k triangles, at full size through the HIP path --------------------------
+@pytest.mark.parametrize("from_image", [False, True], ids=["tables", "from_image"])
 @pytest.mark.parametrize("kernels", ["dense", "legacy"])
-def test_cfg1_full_size(kernels):
+def test_cfg1_full_size(kernels, from_image):
     sys.path.insert(0, ROOT)
     import bench
     C, orc = _C(), _orc()
     args, dLc, dLd, (W, H, F) = bench.build_inputs("cfg1", torch.device("cuda", 0), 0, 1)
     assert (W, H, F) == (256, 256, 2000)
     flags = C.DM2_FLAG_LEGACY_KERNELS if kernels == "legacy" else 0
+    if from_image:
+        # the AA tables built by the plan from verts_image, as bench.py runs the op (tests/util.py run_from_image)
+        old = C.set_flags(flags)
+        try:
+            check_from_image(args, dLc, dLd, nthreads=orc.max_threads())
+        finally:
+            C.set_flags(old)
+        return
     cargs = [a.cpu() if torch.is_tensor(a) else a for a in args]
     ref = orc.render_forward_cuda(*to_numpy_args(cargs), nthreads=orc.max_threads())
     # forward only (configs[0] is "forward-only"), under no_grad as an inference caller would run it

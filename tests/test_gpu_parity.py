@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import ARG_NAMES, rel_linf, scenes, soup_args, to_numpy_args
+from util import ARG_NAMES, check_pool, pool_state, rel_linf, scenes, soup_args, to_numpy_args
 
 pytestmark = pytest.mark.gpu
 
@@ -44,8 +44,8 @@ def run_both(args, seed=0, backward=True):
     C, orc = _C(), _orc()
     dargs = to_dev(args)
     out = C.render_forward_cuda(*dargs)
-    ref = orc.render_forward_cuda(*to_numpy_args(args))
-    res = dict(out=out, ref=ref)
+    res = dict(out=out, pool=pool_state(out))           # (read before any backward runs)
+    ref = res["ref"] = orc.render_forward_cuda(*to_numpy_args(args))
     if backward:
         rng = np.random.RandomState(seed)
         gc = rng.randn(*ref.color.shape).astype(np.float32)
@@ -64,6 +64,7 @@ def check_forward(res, args):
     R, color, depth, oarea, tri_id, tri_cnt, doarea, face_buf, bin_buf, img_buf = out
     B, H, W = ref.depth.shape
     assert R == ref.num_rendered
+    check_pool(res.get("pool"))                         # the pair pool held every pair the composite enumerated
     assert color.shape == (B, H, W, 3) and depth.shape == (B, H, W) and tri_cnt.shape == (B, H, W)
     assert oarea.dim() == 4 and tri_id.dim() == 4 and doarea.dim() == 6
     N, Tn = B * H * W, B * ((W + 15) // 16) * ((H + 15) // 16)
@@ -270,3 +271,86 @@ def test_layers_with_an_unreachable_padded_tet():
     got = lr.generate([0], scd.verts, scd.faces, tets2, scd.face_tets, tf2, scd.faces_existence, 3)
     torch.cuda.synchronize()
     assert torch.equal(base[0], got[0]) and torch.equal(base[1], got[1])
+
+
+# ---- AA tables of the caller's own: the 21-argument boundary takes aa_face_verts as an input of its own (forward.cu:480-481) --
+CALLER_SCENES = {
+    "soup": dict(W=96, H=64, F=600, seed=15, temp=1.0, K=20),
+    "patches": dict(W=96, H=80, F=600, seed=16, temp=1.0, K=20, cams=3, batch_idx=(2, 0), patch_min=[[16, 8], [5, 3]], pw=40, ph=33),
+}
+CALLER_VARIANTS = ["scale2", "scale3", "scale0.5", "shift", "nan", "flip"]
+
+
+def caller_tables(args, variant):
+    """``args`` with aa_face_verts replaced by a variant that is not the projected triangle, and the other five tables rebuilt
+    from it as the reference's Triangles does without reordering (the variant keeps its own orientation)."""
+    orc = _orc()
+    a = list(args)
+    v = args[12].numpy().astype(np.float32)                                   # (B,F,3,2), the reordered projected triangles
+    c = (v.sum(axis=2, keepdims=True) / np.float32(3.0)).astype(np.float32)
+    if variant.startswith("scale"):                                           # about the centroid; x2 and x3: boxes beyond the tiles
+        v = c + np.float32(float(variant[5:])) * (v - c)
+    elif variant == "shift":
+        v = v + np.array([3.5, -2.25], np.float32)
+    elif variant == "nan":
+        v = v.copy()
+        v[:, ::37, 0, 0] = np.nan; v[:, 5::41, 2, :] = np.nan; v[:, 11::53] = np.nan
+    elif variant == "flip":
+        v = v[:, :, [0, 2, 1]]                                                # clockwise tables
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    B, F = v.shape[:2]
+    with np.errstate(invalid="ignore"):
+        t = orc.aa_tables(v.reshape(-1, 3, 2), np.float32, reorder=False)
+    for k, name in zip(range(12, 17), ("verts", "edges", "iszero", "recip", "normal")):
+        a[k] = torch.from_numpy(np.ascontiguousarray(t[name].reshape(B, F, 3, 2)))
+    a[17] = torch.from_numpy(np.ascontiguousarray(t["normal_c"].reshape(B, F, 3)))
+    return a
+
+
+def _caller_args(scene, variant, temp):
+    c = dict(CALLER_SCENES[scene]); c["temp"] = temp
+    return caller_tables(make_args(c), variant)
+
+
+@pytest.mark.parametrize("temp", [1.0, 0.5])
+@pytest.mark.parametrize("variant", CALLER_VARIANTS)
+@pytest.mark.parametrize("scene", list(CALLER_SCENES))
+def test_caller_tables_pool_invariant(scene, variant, temp):
+    """Forward only (no backward reads the pool): the pair pool is sized by what the composite enumerates -- the pixels of the
+    caller's AA box inside the face's tiles -- so the slots it claims stay within the pair bound and the bound within the pool,
+    and the forward matches the oracle bit for bit."""
+    args = _caller_args(scene, variant, temp)
+    res = run_both(args, backward=False)
+    check_forward(res, args)
+
+
+@pytest.mark.parametrize("temp", [1.0, 0.5, 0.0])
+@pytest.mark.parametrize("variant", CALLER_VARIANTS)
+@pytest.mark.parametrize("scene", list(CALLER_SCENES))
+def test_caller_tables_parity(scene, variant, temp):
+    """Forward bit-exact and all six gradients within 1e-5 of the oracle for AA tables that differ from verts_image: larger
+    (x2, x3: more pairs than the projected triangle has), smaller, shifted, with NaN corners, clockwise."""
+    args = _caller_args(scene, variant, temp)
+    res = run_both(args, seed=17)
+    check_forward(res, args)
+    check_backward(res)
+
+
+def test_pair_bound_same_from_image_and_materialised():
+    """On tables of the projected triangles the plan's pair bound does not depend on where the tables come from (bench cfg2)."""
+    import sys
+    from util import ROOT
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    from dmesh2_renderer_amd.sharding import BandShardedOp
+    C = _C()
+    args, _, _, _ = bench.build_inputs("cfg2", torch.device("cuda", 0), 0, 1)
+    out = C.render_forward_cuda(*args)
+    bound = C.last_pair_bound()
+    a = BandShardedOp(args, 1, 0, tables_from_image=True).args
+    with C.tables_from_image(True):
+        out2 = C.render_forward_cuda(*a)
+    torch.cuda.synchronize()
+    assert out2[0] == out[0] and bound > 0
+    assert C.last_pair_bound() == bound

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import ROOT, rel_linf, scenes, to_numpy_args
+from util import ROOT, check_from_image, rel_linf, scenes, to_numpy_args
 
 pytestmark = pytest.mark.gpu
 
@@ -100,11 +100,15 @@ def test_cfg4_backward_is_linear_in_upstream_gradient(cfg4):
         assert err <= 1e-5, (name, err)
 
 
-def test_cfg4_band_matches_oracle(cfg4):
+@pytest.mark.parametrize("from_image", [False, True], ids=["tables", "from_image"])
+def test_cfg4_band_matches_oracle(cfg4, from_image):
     from oracle import cpu as orc
     y0, rows = 512, 48
     a = _band(cfg4["args"], y0, rows)
     dLc = cfg4["dLc"][:, y0:y0 + rows].contiguous(); dLd = cfg4["dLd"][:, y0:y0 + rows].contiguous()
+    if from_image:                   # (the AA tables built by the plan from verts_image, as bench.py runs the op)
+        print("cfg4 band from_image worst rel err", check_from_image(a, dLc, dLd, nthreads=orc.max_threads()))
+        return
     out, g = _fwd_bwd(a, dLc, dLd)
     ref = orc.render_forward_cuda(*to_numpy_args(a), nthreads=orc.max_threads())
     assert out[0] == ref.num_rendered
@@ -116,14 +120,22 @@ def test_cfg4_band_matches_oracle(cfg4):
         assert rel_linf(x.cpu().numpy(), gref[name]) <= 1e-5, name
 
 
-def test_cfg5_4k_2m_faces_band_decomposition_and_oracle_band():
+@pytest.mark.parametrize("from_image", [False, True], ids=["tables", "from_image"])
+def test_cfg5_4k_2m_faces_band_decomposition_and_oracle_band(from_image):
     """BASELINE configs[4] (3840x2160, 2 M triangles; quoted on 8 GPUs, fits one): the 8-band decomposition the
     multi-GPU run uses reproduces the single-GPU frame bit for bit, the band gradients add up to the full ones, and
-    one 32-row band agrees with the oracle."""
+    one 32-row band agrees with the oracle.  from_image: the oracle band alone, with the AA tables built by the plan from
+    verts_image, as bench.py runs the op."""
     from oracle import cpu as orc
     from dmesh2_renderer_amd.sharding import all_bands
     b = _bench()
     args, dLc, dLd, (W, H, F) = b.build_inputs("cfg5", torch.device("cuda", 0), 0, 1)
+    if from_image:
+        y0, rows = 1024, 32
+        a = _band(args, y0, rows)
+        gc, gd = dLc[:, y0:y0 + rows].contiguous(), dLd[:, y0:y0 + rows].contiguous()
+        print("cfg5 band from_image worst rel err", check_from_image(a, gc, gd, nthreads=orc.max_threads()))
+        return
     out, g = _fwd_bwd(args, dLc, dLd)
     g = [x.clone() for x in g]
     assert out[0] > 3_000_000
@@ -148,11 +160,18 @@ def test_cfg5_4k_2m_faces_band_decomposition_and_oracle_band():
         assert rel_linf(x.cpu().numpy(), gref[name]) <= 1e-5, name
 
 
-def test_cfg2_full_size_against_oracle():
-    """BASELINE config 2: forward+backward 512x512, 50k triangles, AA visibility gradients on."""
+@pytest.mark.parametrize("from_image,temp", [(False, None), (True, None), (True, 0.0)], ids=["tables", "from_image", "from_image-temp0"])
+def test_cfg2_full_size_against_oracle(from_image, temp):
+    """BASELINE config 2: forward+backward 512x512, 50k triangles, AA visibility gradients on.  from_image: the AA tables
+    built by the plan from verts_image, as bench.py runs the op; also at temperature 0 (the point-sampled backward)."""
     from oracle import cpu as orc
     b = _bench()
     args, dLc, dLd, _ = b.build_inputs("cfg2", torch.device("cuda", 0), 0, 1)
+    if from_image:
+        if temp is not None:
+            args = list(args); args[11] = temp
+        print("cfg2 from_image temp", args[11], "worst rel err", check_from_image(args, dLc, dLd, nthreads=orc.max_threads()))
+        return
     out, g = _fwd_bwd(args, dLc, dLd)
     ref = orc.render_forward_cuda(*to_numpy_args(args), nthreads=orc.max_threads())
     assert out[0] == ref.num_rendered

@@ -133,3 +133,36 @@ def test_error_codes_match_reference(ge):
         assert code == 0, (i, code)
         assert abs(area - ge["area_analytic"][i]) <= 2e-6, (i, area, ge["area_analytic"][i])
         assert np.allclose(grad, ge["grad_analytic"][i], rtol=1e-5, atol=2e-6), (i, grad, ge["grad_analytic"][i])
+
+
+def test_from_image_helpers_on_two_faces():
+    """tests/util.py: the oracle tables of a from-image call, and the corner -> vertex scatter that undoes the CCW reorder,
+    on two faces over four vertices, the second one clockwise."""
+    import torch
+    from util import from_image_oracle_args, scatter_aa_grad_to_verts
+    vi = np.array([[[0.0, 0.0], [4.0, 0.0], [0.0, 3.0], [5.0, 5.0]]], np.float32)        # (B=1, P=4, 2)
+    faces = np.array([[0, 1, 2], [1, 2, 3]], np.int32)       # face 0 CCW (area +6); face 1: (4,0) (0,3) (5,5) clockwise (-11.5)
+    args = [None] * 21
+    args[5], args[9] = torch.from_numpy(faces), torch.from_numpy(vi)
+    for k in range(12, 17):
+        args[k] = torch.empty((1, 0, 3, 2))
+    args[17] = torch.empty((1, 0, 3))
+    na = from_image_oracle_args(args)
+    assert na[12].shape == (1, 2, 3, 2) and na[17].shape == (1, 2, 3) and na[14].dtype == bool
+    assert np.array_equal(na[12][0, 0], vi[0, [0, 1, 2]])
+    assert np.array_equal(na[12][0, 1], vi[0, [1, 3, 2]])                    # corners 1 and 2 swapped
+    assert np.array_equal(na[13][0, 1], vi[0, [3, 2, 1]] - vi[0, [1, 3, 2]])
+    assert na[16].shape == (1, 2, 3, 2) and np.array_equal(na[17][0, 1], (na[16][0, 1] * na[12][0, 1]).sum(-1))
+    g = np.arange(12, dtype=np.float32).reshape(1, 2, 3, 2) + 1.0
+    got = scatter_aa_grad_to_verts(g, na[12], vi, faces)
+    want = np.zeros((1, 4, 2))
+    want[0, 0] += g[0, 0, 0]; want[0, 1] += g[0, 0, 1]; want[0, 2] += g[0, 0, 2]
+    want[0, 1] += g[0, 1, 0]; want[0, 3] += g[0, 1, 1]; want[0, 2] += g[0, 1, 2]   # face 1: table corner 1 is vertex 3
+    assert got.dtype == np.float64 and np.array_equal(got, want)
+    # tables that are not reordered: corners go straight to faces[:, k]
+    plain = np.stack([vi[0, faces[0]], vi[0, faces[1]]])[None]
+    want2 = np.zeros((1, 4, 2))
+    for f in range(2):
+        for k in range(3):
+            want2[0, faces[f, k]] += g[0, f, k]
+    assert np.array_equal(scatter_aa_grad_to_verts(g, plain, vi, faces), want2)

@@ -67,3 +67,113 @@ def to_numpy_args(args):
 def rel_linf(a, b):
     a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
     return float(np.max(np.abs(a - b)) / max(float(np.max(np.abs(b))), 1e-12)) if a.size else 0.0
+
+
+def from_image_oracle_args(args):
+    """The oracle's 21 arguments for a call whose AA tables are built from ``verts_image`` (DM2_FLAG_TABLES_FROM_IMAGE): args
+    12-17 become the six tables the reference's ``Triangles`` builds from ``verts_image[:, faces]``, CCW reorder included
+    (what the op's plan builds in registers).  Whatever ``args`` holds there, placeholders or tables, is ignored."""
+    from oracle import cpu as orc
+    na = to_numpy_args(args)
+    vi, fc = na[9], na[5].astype(np.int64)
+    Bv, Fv = vi.shape[0], fc.shape[0]
+    t = orc.aa_tables(vi[:, fc.reshape(-1)].reshape(-1, 3, 2), np.float32, reorder=True)
+    for k, name in zip(range(12, 17), ("verts", "edges", "iszero", "recip", "normal")):
+        na[k] = t[name].reshape(Bv, Fv, 3, 2)
+    na[17] = t["normal_c"].reshape(Bv, Fv, 3)
+    return na
+
+
+def scatter_aa_grad_to_verts(g_aa, aa_face_verts, verts_image, faces):
+    """Per-corner gradient of the AA tables (B,F,3,2) -> per-vertex gradient of ``verts_image`` (B,P,2), summed in fp64.
+    Corner 0 is always the face's vertex 0; corners 1 and 2 are its vertices 2 and 1 where the CCW reorder swapped them,
+    which is where the table's corner 1 is not ``verts_image[faces[:, 1]]`` (the test the op's records make)."""
+    g = np.asarray(g_aa, dtype=np.float64)
+    av, vi, fc = np.asarray(aa_face_verts), np.asarray(verts_image), np.asarray(faces).astype(np.int64)
+    B, F, P = g.shape[0], g.shape[1], vi.shape[1]
+    v1 = vi[:, fc[:, 1]]                                                  # (B,F,2)
+    swap = ~((av[:, :, 1, 0] == v1[..., 0]) & (av[:, :, 1, 1] == v1[..., 1]))
+    idx = np.broadcast_to(fc, (B, F, 3)).copy()
+    idx[..., 1] = np.where(swap, fc[:, 2], fc[:, 1])
+    idx[..., 2] = np.where(swap, fc[:, 1], fc[:, 2])
+    out = np.zeros((B, P, 2), dtype=np.float64)
+    for b in range(B):
+        np.add.at(out[b], idx[b].reshape(-1), g[b].reshape(-1, 2))
+    return out
+
+
+# ---- GPU side --------------------------------------------------------------------------------------------------------------
+def pool_state(out):
+    """What the forward ``out`` (its 10-tuple) left of its pair pool, read right after it (before any backward): dict(mode,
+    claimed = pool slots its composite handed out (hit_valid[1]), bound = the plan's pair bound, cap = pool capacity of its
+    binning buffer, hit_valid), or None when the forward kept no pool (mode != DM2_FWD_POOL)."""
+    mode, bound = _C.last_forward_mode(), _C.last_pair_bound()
+    R, bin_buf = out[0], out[8]
+    if mode != _C.FWD_POOL or R <= 0:
+        return None
+    B, H, W = out[2].shape
+    Tn = _C._tiles(B, W, H)
+    lib = _C.load_library()
+    cap = max(0, bin_buf.numel() - lib.dm2_scratch_bytes(_C.SCRATCH_BINNING, R, Tn)) // 4      # (as render_backward_cuda sizes it)
+    hv = _C.debug_fetch(9, B * H * W, Tn, R, bin_buf, torch.int32, 4).cpu().numpy().view(np.uint32)
+    return dict(mode=mode, claimed=int(hv[1]), bound=int(bound), cap=int(cap), hit_valid=hv.tolist())
+
+
+def check_pool(state):
+    """The pool invariant: the slots the composite claimed never exceed the plan's pair bound, nor the bound the pool."""
+    if state is None:
+        return
+    assert state["hit_valid"][0] == 3, f"hit_valid {state['hit_valid']}: the forward reported DM2_FWD_POOL"
+    assert state["claimed"] <= state["bound"] <= state["cap"], state
+
+
+def run_from_image(args, dL_dcolor, dL_ddepth):
+    """The op as bench.py runs its default path: placeholder AA tables (BandShardedOp(.., tables_from_image=True)), forward under
+    ``tables_from_image`` + ``aa_grad_to_verts``.  Backward twice: the sixth gradient unrouted (B,F,3,2), then routed (B,P,2).
+    ``args`` on the GPU.  -> (forward 10-tuple, six gradients (numpy), routed gradient (numpy), pool_state)."""
+    from dmesh2_renderer_amd.sharding import BandShardedOp
+    a = BandShardedOp(args, 1, 0, tables_from_image=True).args
+    assert a[12].shape[1] == 0 and a[17].shape[1] == 0
+    with _C.aa_grad_to_verts(True), _C.tables_from_image(True):
+        out = _C.render_forward_cuda(*a)
+    pool = pool_state(out)
+    check_pool(pool)
+    bw = (out[0], *a, dL_dcolor, dL_ddepth, out[7], out[8], out[9], out[3], out[4], out[5], out[6])
+    with _C.tables_from_image(True):
+        g = [x.cpu().numpy() for x in _C.render_backward_cuda(*bw)]
+    with _C.aa_grad_to_verts(True), _C.tables_from_image(True):
+        routed = _C.render_backward_cuda(*bw)[5].cpu().numpy()
+    torch.cuda.synchronize()
+    return out, g, routed, pool
+
+
+GRAD_NAMES = ["verts", "verts_color", "faces_opacity", "verts_ndc", "faces_intense", "aa_face_verts"]
+
+
+def check_from_image(args, dL_dcolor, dL_ddepth, tol=1e-5, nthreads=1):
+    """run_from_image against the oracle given the tables the reference builds from verts_image: num_rendered, colour, depth,
+    tri_cnt, n_contrib bit-equal; the six gradients and the routed AA gradient (against the fp64 scatter of the oracle's) within
+    ``tol`` relative L-inf.  -> per-tensor worst relative error."""
+    from oracle import cpu as orc
+    out, g, routed, _ = run_from_image(args, dL_dcolor, dL_ddepth)
+    na = from_image_oracle_args(args)
+    ref = orc.render_forward_cuda(*na, nthreads=nthreads)
+    R = out[0]
+    assert R == ref.num_rendered
+    assert np.array_equal(out[1].cpu().numpy().view(np.uint32), ref.color.view(np.uint32))
+    assert np.array_equal(out[2].cpu().numpy().view(np.uint32), ref.depth.view(np.uint32))
+    assert np.array_equal(out[5].cpu().numpy(), ref.buf_tri_cnt)
+    B, H, W = ref.depth.shape
+    N, Tn = B * H * W, _C._tiles(B, W, H)
+    if R > 0:
+        nc = _C.debug_fetch(4, N, Tn, R, out[9], torch.int32, N).cpu().numpy().view(np.uint32)
+        flipped = int((nc != ref.n_contrib.reshape(-1)).sum())
+        assert flipped == 0, f"{flipped} pixels with a different last contributor"
+    gref = orc.render_backward_cuda(ref, dL_dcolor.cpu().numpy(), dL_ddepth.cpu().numpy(), nthreads=nthreads)
+    worst = {}
+    for name, x in zip(GRAD_NAMES, g):
+        assert x.shape == gref[name].shape, name
+        worst[name] = rel_linf(x, gref[name])
+    worst["aa_to_verts"] = rel_linf(routed, scatter_aa_grad_to_verts(gref["aa_face_verts"], na[12], na[9], na[5]))
+    assert all(v <= tol for v in worst.values()), worst
+    return worst
