@@ -10,7 +10,7 @@
 //   * owes the clipper only d(area)/d(corners), which needs no polygon (dm2_clip_fast.h: per triangle edge, the piece
 //     inside the pixel; ~350 instead of ~950 VALU instructions per pair, no 160-register working set).  Pairs whose
 //     reference polygon is not the geometric intersection (ties, 1-5 % at 1080p) are queued with their dL/d(area) and
-//     get the exact segment clipper in k_aa_ties behind this kernel.
+//     get the reference's own clipper (its fan-order Jacobian) in k_aa_ties behind this kernel.
 //
 //   per chunk (walked back to front): the masks of the next <= 32 entries, scan of their hit counts (every wave for
 //   itself, DPP), keep the leading entries whose hits fit 256 lanes (a ballot), pair lane -> (entry, pixel) through
@@ -486,8 +486,9 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     STAMP_FLUSH
 }
 
-// The ties of k_render_backward_fast: one queued (pixel, face) pair per lane, the exact segment clipper's Jacobian
-// (dm2_clip_seg.h: the reference's polygon also where it is not the geometric intersection) times the pair's dL/d(area),
+// The ties of k_render_backward_fast: one queued (pixel, face) pair per lane, the Jacobian of the reference's own clipper in its
+// fan order (tri_pix_overlap_area: its polygon also where that is not the geometric intersection, and its rounding where the
+// Jacobian is ill-conditioned -- bit-equal to the oracle, tests/test_gpu_clippers.py variant 0) times the pair's dL/d(area),
 // added to dL/d(aa_face_verts) -- or, under DM2_FLAG_AA_GRAD_TO_VERTS, to the image-space gradient of the vertex the corner
 // came from.  Grid-stride over the queue; the block that finishes last empties the queue for a second backward of the
 // same forward.
@@ -521,7 +522,7 @@ k_aa_ties(dm2_render_desc d, const uint4* __restrict__ face_recs, const TieEntry
             for (int k = 0; k < 8; k++) dst[k] = src[k];                          // the AA tables: the record's first 128 bytes
             const float pxmin = (float)(x + (uint32_t)d.patch_min[2 * b]), pymin = (float)(y + (uint32_t)d.patch_min[2 * b + 1]);
             float area;
-            seg_area_grad(f, pxmin, pxmin + 1, pymin, pymin + 1, 1.0f, area, g, false);
+            (void)tri_pix_overlap_area<true>(f, pxmin, pxmin + 1, pymin, pymin + 1, 1.0f, area, g);   // (0: the forward blended it)
 #pragma unroll
             for (int c = 0; c < 6; c++) g[c] *= e.dL_doarea;
         }

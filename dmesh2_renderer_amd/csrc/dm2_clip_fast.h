@@ -20,9 +20,11 @@
 // polygon is not the geometric intersection: a triangle corner within rounding of a pixel boundary line (its closed
 // interval tests and the end point tests then disagree about one crossing), an edge that passes within rounding of a
 // pixel corner (the corner classification, aa.h:103-149, and the crossing validity tests disagree), an "iszero" edge
-// (|e| < 1e-3, crossings with the parallel pixel lines are ignored, pyrenderer.py:14) that straddles such a line.
+// (|e| < 1e-3, crossings with the parallel pixel lines are ignored, pyrenderer.py:14) that straddles such a line -- and,
+// though the polygon is right there, a nearly axis-parallel edge (|e| < 1/64) straddling such a line, whose crossing's
+// Jacobian amplifies the rounding of the corner coordinates by 1/|e| (so that no regrouping reproduces it).
 // Those pairs are recognised by distance tests with a margin of 16-32 ulp of the image coordinate (`tie`), take no
-// gradient here and are handed to the exact segment clipper (dm2_clip_seg.h) by the caller: 1-5 % of the pairs of a
+// gradient here and are handed to the reference's own clipper (tri_pix_overlap_area, dm2_device_math.h) by the caller: 1-5 % of the pairs of a
 // 1080p frame.  tests/test_gpu_clippers.py (variant 4) holds every pair that is NOT flagged to the oracle's Jacobian
 // on the reference's vectors, on random pairs and on the exact-tie stress sets.
 #pragma once
@@ -32,7 +34,11 @@ namespace dm2 {
 
 // margin of the tie tests: 2^-19 of the larger pixel coordinate = 16..32 ulp of an image coordinate there
 constexpr float FAST_TIE_REL = 1.0f / 524288.0f;
-constexpr float FAST_TIE_ISZERO = 1.5e-3f;          // both ends of an "iszero" edge lie within 1e-3 of a line it straddles
+// an edge with a component below this (the "iszero" ones, |e| < 1e-3, among them) whose end lies within it of a pixel line of
+// that axis: the edge may straddle the line.  Above 1e-3 the reference does clip there, but its Jacobian of that crossing has
+// the factor 1/e: the rounding of the corner coordinates, ~6e-8 of the pixel, comes out as ~6e-8 / |e| of an entry and the
+// polygon-free regrouping rounds differently (8.5e-5 of max(1, largest entry) seen at |e| = 1.01e-3).  At 1/64 that is < 4e-6.
+constexpr float FAST_TIE_NEAR = 1.0f / 64.0f;
 
 template <int TI, class Face>      // Face: anything with v[6], e[6], r[6], zmask (AAFace, or the backward's shorter LDS record)
 __device__ __forceinline__ void fast_edge(const Face& f, float pxmin, float pxmax, float pymin, float pymax,
@@ -76,12 +82,13 @@ __device__ __forceinline__ void fast_edge(const Face& f, float pxmin, float pxma
     const float ax = fminf(fabsf(dxl), fabsf(dxh)), ay = fminf(fabsf(dyl), fabsf(dyh));
     const bool inx = (dxl <= delta) && (dxh >= -delta), iny = (dyl <= delta) && (dyh >= -delta);
     tie = tie || (!(ax >= delta) && iny) || (!(ay >= delta) && inx);
-    // (b) an "iszero" edge (|e| < 1e-3 on an axis: the reference ignores its crossings with the pixel lines of that axis,
-    // pyrenderer.py:14) one of whose ends is within 1.5e-3 of such a line: it may straddle it
-    const uint32_t zx = (f.zmask >> (2 * TI)) & 1u, zy = (f.zmask >> (2 * TI + 1)) & 1u;
-    if (zx | zy) {                                                     // (rare: one face in a few hundred)
+    // (b) a (nearly) axis-parallel edge, |e| < FAST_TIE_NEAR on an axis, one of whose ends is within FAST_TIE_NEAR of a pixel
+    // line of that axis: it may straddle it -- an "iszero" edge (|e| < 1e-3: the reference ignores its crossings with those
+    // lines, pyrenderer.py:14), or one whose crossing there has an ill-conditioned Jacobian (FAST_TIE_NEAR)
+    const bool nx = fabsf(ex) < FAST_TIE_NEAR, ny = fabsf(ey) < FAST_TIE_NEAR;
+    if (nx | ny) {                                                     // (rare in general position: a few faces in a thousand)
         const float bx = fminf(fabsf(pxmin - p1x), fabsf(pxmax - p1x)), by = fminf(fabsf(pymin - p1y), fabsf(pymax - p1y));
-        tie = tie || (zx && !(fminf(ax, bx) >= FAST_TIE_ISZERO)) || (zy && !(fminf(ay, by) >= FAST_TIE_ISZERO));
+        tie = tie || (nx && !(fminf(ax, bx) >= FAST_TIE_NEAR)) || (ny && !(fminf(ay, by) >= FAST_TIE_NEAR));
     }
     // (c) the edge's line within ~delta of a pixel corner: the crossings with the two pixel lines through that corner then have
     // (nearly) the same parameter.  (Whether that corner lies on the edge at all is not looked at: one pair in a thousand more.)

@@ -9,7 +9,7 @@ backward's segment formulation (variant 2; the same polynomial regrouped, see dm
 reference's fan sum over its corners, the area bit-equal as well) agrees to 2 ulp of the
 pixel area and 1e-6 absolute in the Jacobian.  All three report an error exactly where the reference raises.
 Variant 4 is the default backward's Jacobian without a polygon (dm2_clip_fast.h): every pair it does NOT hand to the
-segment formulation as a tie (code -1) is held to the oracle's Jacobian; the ties are variant 2's."""
+tie path (code -1) is held to the oracle's Jacobian; the ties get variant 0's (k_aa_ties)."""
 import os
 
 import numpy as np
@@ -225,7 +225,7 @@ def _check_fast(g, o_area, o_grad, o_code, max_tie_fraction=None, min_ok=10):
     assert err[ok].max() <= FAST_GRAD_TOL, (err[ok].max(), np.where(ok & (err > FAST_GRAD_TOL))[0][:10])
     if max_tie_fraction is not None:
         assert tie[live].mean() <= max_tie_fraction, tie[live].mean()
-    # and the ties go to the segment formulation, held to its own bar above
+    # and the ties go to the generic clipper (k_aa_ties), bit-equal to the oracle above
     return tie[live].mean(), err[ok].max()
 
 

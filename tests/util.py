@@ -148,6 +148,75 @@ def run_from_image(args, dL_dcolor, dL_ddepth):
 
 
 GRAD_NAMES = ["verts", "verts_color", "faces_opacity", "verts_ndc", "faces_intense", "aa_face_verts"]
+GRAD_TOL = 1e-5         # gradients: relative L-inf against the oracle (fp32 atomic summation order differs)
+
+
+def to_dev(args, dev="cuda"):
+    return [a.to(dev) if torch.is_tensor(a) else a for a in args]
+
+
+def run_both(args, seed=0, backward=True, nthreads=1):
+    """The HIP op and the oracle on the same 21 arguments (CPU tensors), forward and (with random output gradients drawn from
+    ``seed``) backward.  -> dict(out, pool, ref[, grads, ref_grads])."""
+    from oracle import cpu as orc
+    dargs = to_dev(args)
+    out = _C.render_forward_cuda(*dargs)
+    res = dict(out=out, pool=pool_state(out))           # (read before any backward runs)
+    ref = res["ref"] = orc.render_forward_cuda(*to_numpy_args(args), nthreads=nthreads)
+    if backward:
+        rng = np.random.RandomState(seed)
+        gc = rng.randn(*ref.color.shape).astype(np.float32)
+        gd = rng.randn(*ref.depth.shape).astype(np.float32)
+        grads = _C.render_backward_cuda(out[0], *dargs, torch.from_numpy(gc).cuda(), torch.from_numpy(gd).cuda(),
+                                       out[7], out[8], out[9], out[3], out[4], out[5], out[6])
+        res["grads"] = [g.cpu().numpy() for g in grads]
+        res["ref_grads"] = orc.render_backward_cuda(ref, gc, gd, nthreads=nthreads)
+    torch.cuda.synchronize()
+    return res
+
+
+def check_forward(res, args):
+    """Forward bit-exact against the oracle: num_rendered, the pool invariant, ranges, face_list, final_T, final_prev_T,
+    n_contrib, colour, depth, tri_cnt."""
+    out, ref = res["out"], res["ref"]
+    R, color, depth, oarea, tri_id, tri_cnt, doarea, face_buf, bin_buf, img_buf = out
+    B, H, W = ref.depth.shape
+    assert R == ref.num_rendered
+    check_pool(res.get("pool"))                         # the pair pool held every pair the composite enumerated
+    assert color.shape == (B, H, W, 3) and depth.shape == (B, H, W) and tri_cnt.shape == (B, H, W)
+    assert oarea.dim() == 4 and tri_id.dim() == 4 and doarea.dim() == 6
+    N, Tn = B * H * W, B * ((W + 15) // 16) * ((H + 15) // 16)
+    if R > 0:
+        ranges = _C.debug_fetch(0, N, Tn, R, img_buf, torch.int32, Tn * 2).cpu().numpy().view(np.uint32).reshape(Tn, 2)
+        flist = _C.debug_fetch(1, N, Tn, R, bin_buf, torch.int32, R).cpu().numpy().view(np.uint32)
+        assert np.array_equal(ranges, ref.binning.ranges)
+        assert np.array_equal(flist, ref.binning.face_list)
+        fT = _C.debug_fetch(2, N, Tn, R, img_buf, torch.float32, N).cpu().numpy()
+        fpT = _C.debug_fetch(3, N, Tn, R, img_buf, torch.float32, N).cpu().numpy()
+        nc = _C.debug_fetch(4, N, Tn, R, img_buf, torch.int32, N).cpu().numpy().view(np.uint32)
+        flipped = int((nc != ref.n_contrib).sum())
+        assert flipped == 0, f"{flipped} pixels with a different last contributor"
+        assert np.array_equal(fT.view(np.uint32), ref.final_T.view(np.uint32))
+        assert np.array_equal(fpT.view(np.uint32), ref.final_prev_T.view(np.uint32))
+    c, d = color.cpu().numpy(), depth.cpu().numpy()
+    assert np.array_equal(c.view(np.uint32), ref.color.view(np.uint32)), f"color max abs diff {np.abs(c - ref.color).max()}"
+    assert np.array_equal(d.view(np.uint32), ref.depth.view(np.uint32)), f"depth max abs diff {np.abs(d - ref.depth).max()}"
+    assert np.array_equal(tri_cnt.cpu().numpy(), ref.buf_tri_cnt)
+
+
+def check_backward(res, tol=GRAD_TOL):
+    """The six gradients within ``tol`` relative L-inf of the oracle's, the same non-finite pattern.  -> per-tensor worst."""
+    worst = {}
+    for name, g in zip(GRAD_NAMES, res["grads"]):
+        r = res["ref_grads"][name]
+        assert g.shape == r.shape, name
+        assert np.isfinite(g).all() == np.isfinite(r).all(), name
+        m = np.isfinite(r)
+        worst[name] = rel_linf(g[m], r[m])
+    assert all(v <= tol for v in worst.values()), worst
+    ndc = res["grads"][3]
+    assert not ndc[..., :2].any()                       # only the z channel receives gradient (backward.cu:516-518)
+    return worst
 
 
 def check_from_image(args, dL_dcolor, dL_ddepth, tol=1e-5, nthreads=1):
