@@ -225,19 +225,20 @@ k_render_backward(dm2_render_desc d, const uint2* __restrict__ ranges, const uin
 }
 
 // The backward kernels of a frame (fwd_mode: what the forward returned, DM2_FWD_*; "check": the kernel looks at
-// hit_valid[0] on the device and returns at once unless the forward left what it reads):
+// hit_valid[0] on the device and returns at once unless the forward left what it reads).  fast<...>: the instantiations
+// of k_render_backward_fast (dm2_backward_fast.hip) by the source of a pair's coverage:
 //
 //   DM2_FLAG_LEGACY_KERNELS, or DM2_FWD_NONE        k_render_backward
-//   temperature 0,   DM2_FWD_POINT                  fast<POINT>                  (dm2_backward_fast.hip)
-//   temperature > 0, DM2_FWD_POOL                   fast<false> + k_aa_ties      (the default)
-//   temperature > 0, DM2_FWD_MASKS                  mask                         (dm2_backward_mask.hip)
+//   temperature 0,   DM2_FWD_POINT                  fast<POINT>
+//   temperature > 0, DM2_FWD_POOL                   fast<POOL> + k_aa_ties      (the default)
+//   temperature > 0, DM2_FWD_MASKS                  fast<CLIP>
 //   anything else: DM2_FWD_UNKNOWN, or a mode no    the device-side cascade --
 //   forward at this temperature returns (POINT at     temperature 0:  fast<POINT> (check) -> k_render_backward (check)
-//   temperature > 0, MASKS / POOL at temperature 0)   temperature > 0: fast<false> (check; only when the binning scratch
-//                                                     has a pool part) -> mask (check) -> k_render_backward (check)
+//   temperature > 0, MASKS / POOL at temperature 0)   temperature > 0: fast<POOL> (check; only when the binning scratch
+//                                                     has a pool part) -> fast<CLIP> (check) -> k_render_backward (check)
 //
 // In the cascade exactly one kernel works for each value of hit_valid[0]: 1 (written only at temperature 0) fast<POINT>,
-// 2 mask, 3 (written only when a pool part exists, and dm2_backward then demands the tie scratch) fast<false>, 0
+// 2 fast<CLIP>, 3 (written only when a pool part exists, and dm2_backward then demands the tie scratch) fast<POOL>, 0
 // k_render_backward, which stands down on anything else.
 void launch_render_backward(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                             const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
@@ -245,14 +246,10 @@ void launch_render_backward(const dm2_render_desc& d, const uint2* ranges, const
                             float* dL_daa_face_verts, const BinningState& bs, int fwd_mode, TieEntry* tie_queue, int64_t tie_cap,
                             hipStream_t st) {
     const bool aa = d.aa_temperature > 0.0f;
-    auto fast = [&](bool check) {          // (times its kernels itself, unless checked: then the cascade is timed as one stage)
+    auto fast = [&](bool clip, bool check) {   // (times its kernels itself, unless checked: then the cascade is timed as one stage)
         launch_render_backward_fast(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color, dL_dfaces_opacity,
-                                    dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, aa ? tie_queue : nullptr,
+                                    dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, clip, aa ? tie_queue : nullptr,
                                     aa ? tie_cap : 0, check, st);
-    };
-    auto mask = [&]() {
-        launch_render_backward_mask(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color, dL_dfaces_opacity,
-                                    dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs.hit_masks, bs.hit_valid, st);
     };
     auto per_pixel = [&](const uint32_t* skip_if_masks) {
         const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
@@ -261,12 +258,12 @@ void launch_render_backward(const dm2_render_desc& d, const uint2* ranges, const
                            skip_if_masks);
     };
     const bool legacy = (d.flags & DM2_FLAG_LEGACY_KERNELS) != 0;
-    if (!legacy && fwd_mode == (aa ? DM2_FWD_POOL : DM2_FWD_POINT)) { fast(false); return; }
+    if (!legacy && fwd_mode == (aa ? DM2_FWD_POOL : DM2_FWD_POINT)) { fast(false, false); return; }
+    if (!legacy && aa && fwd_mode == DM2_FWD_MASKS) { fast(true, false); return; }
     StageTimer tm(ST_BWD, st);
     if (legacy || fwd_mode == DM2_FWD_NONE) { per_pixel(nullptr); return; }
-    if (aa && fwd_mode == DM2_FWD_MASKS) { mask(); return; }
-    if (!aa || bs.pool_cap > 0) fast(true);
-    if (aa) mask();
+    if (!aa || bs.pool_cap > 0) fast(false, true);
+    if (aa) fast(true, true);
     per_pixel(bs.hit_valid);
 }
 

@@ -1,30 +1,37 @@
-// dm2_backward_fast.hip -- backward composite driven by the forward's blend masks AND its pair pool (the default).
+// dm2_backward_fast.hip -- backward composite driven by the forward's blend masks (every forward that left them).
 //
 // Same results as k_render_backward (dm2_backward.hip; BACKWARD::renderCUDA<3>, backward.cu:17-532) up to fp32
-// summation order of the scattered gradients.  dm2_forward_queue.hip leaves, per list entry and wave of the tile's
-// block, the 64-bit mask of the pixels the entry blends into, and per blended pair its coverage ratio
-// (forward.cu:375-378) in a pool ordered like the masks.  With those the backward
-//   * neither enumerates nor classifies (pixel,face) pairs and never meets a clipper error path (the masks),
-//   * replays the forward's alpha TO THE BIT without clipping for an area (the pool): nothing depends on reproducing
-//     an area, nearly opaque faces included,
-//   * owes the clipper only d(area)/d(corners), which needs no polygon (dm2_clip_fast.h: per triangle edge, the piece
-//     inside the pixel; ~350 instead of ~950 VALU instructions per pair, no 160-register working set).  Pairs whose
-//     reference polygon is not the geometric intersection (ties, 1-5 % at 1080p) are queued with their dL/d(area) and
-//     get the reference's own clipper (its fan-order Jacobian) in k_aa_ties behind this kernel.
+// summation order of the scattered gradients.  The forward leaves, per list entry and wave of the tile's block, the
+// 64-bit mask of the pixels the entry blends into: the backward neither enumerates nor classifies (pixel,face) pairs,
+// never meets a clipper error path, and sizes every chunk to exactly one full round.  One kernel, three sources of a
+// pair's coverage (the template parameter):
+//   POOL   (the default) dm2_forward_queue.hip also left every blended pair's coverage ratio (forward.cu:375-378) in a
+//          pool ordered like the masks: the backward replays the forward's alpha TO THE BIT without clipping for an
+//          area -- nothing depends on reproducing one, nearly opaque faces included -- and owes the clipper only
+//          d(area)/d(corners), which needs no polygon (dm2_clip_fast.h: per triangle edge, the piece inside the pixel;
+//          ~350 instead of ~950 VALU instructions per pair, no 160-register working set).  Pairs whose reference polygon
+//          is not the geometric intersection (ties, 1-5 % at 1080p) are queued with their dL/d(area) and get the
+//          reference's own clipper (its fan-order Jacobian) in k_aa_ties behind this kernel.
+//   POINT  aa_temperature == 0 (dm2_forward_point.hip left the masks): coverage 1 for every pair, no pool, no AA terms.
+//   CLIP   masks but no pool (the plan's pair bound was over the caller's budget, or DM2_FLAG_NO_PAIR_POOL): area and
+//          Jacobian from the segment clipper (dm2_clip_seg.h, the reference's K = 0 path backward.cu:264-272).
 //
 //   per chunk (walked back to front): the masks of the next <= 32 entries, scan of their hit counts (every wave for
 //   itself, DPP), keep the leading entries whose hits fit 256 lanes (a ballot), pair lane -> (entry, pixel) through
 //   start marks and a running maximum, then
-//   B2  lane s: its (face, pixel) from the masks, its coverage from the pool; Moeller-Trumbore, clamp, alpha,
-//       interpolated colour / depth -> record in LDS
+//   B2  lane s: its (face, pixel) from the masks, its coverage; Moeller-Trumbore, clamp, alpha, interpolated colour /
+//       depth -> record in LDS
 //   C   pixel p: replay its records back to front (backward.cu:340-405)
 //   D   lane s: chain rule (backward.cu:408-488) incl. the AA Jacobian, DPP pre-reduction over the lanes of one face,
 //       ds_add_f32
 //   flush with (entry,component) global atomics.
 //
-// Memory pipeline as in dm2_backward_mask.hip (the exact-clipper variant kept for forwards without a pool): a chunk's
-// inputs -- face ids, blend masks, pool offsets, packed face records -- are requested ONE CHUNK AHEAD with LDS-direct
-// loads into the other half of double-buffered LDS arrays.
+// Memory pipeline.  A chunk's inputs -- face ids, blend masks, pool offsets, packed face records (dm2_stage.h: 256 B per
+// (view,face), two full lines) -- are requested ONE CHUNK AHEAD, right after the current chunk's cut is known, with
+// LDS-direct loads (global_load_lds_dwordx4: no staging registers) into the OTHER half of double-buffered LDS arrays: the
+// global latency is covered by phases B2, C and D of the current chunk instead of stalling the block (in-kernel stamps of
+// the round-1 kernel: 48 % of a block's time went into that stall).  The ids a record address needs are read one chunk
+// earlier still, as a window of 64 entries.
 #include <hip/hip_runtime.h>
 
 #include "dm2_bwd_shared.h"
@@ -42,18 +49,29 @@ namespace dm2 {
 #ifndef DM2_BF_CAND
 #define DM2_BF_CAND 30        // 30 candidates + 127 VGPRs: four blocks per CU (40.5 KB of LDS each).  A/B at cfg4: 32 candidates / 3 blocks 1.17 ms, 30 / 4 blocks 1.05 ms, 28 / 4 blocks 1.05 ms
 #endif
-constexpr int BM_CAND = DM2_BF_CAND;      // candidate entries per chunk
-static_assert(BM_CAND * 4 <= TILE_PIX && 2 * BM_CAND <= 64, "one scan thread per (face, wave); one id window per wave");
-constexpr int BM_SLOTS = BM_CAND * 4;
-constexpr int REC_CHUNKS = FACE_RECB_PARTS;               // 12 of the 16 sixteen-byte parts of the global record (dm2_stage.h: FaceRecB)
-constexpr int REC_PER_INSTR = 64 / REC_CHUNKS;            // records one wave instruction copies
-static_assert(8 * REC_PER_INSTR >= BM_CAND, "two LDS-direct instructions per wave fetch a chunk");
 #ifndef DM2_BF_BLOCKS
 #define DM2_BF_BLOCKS 4       // resident blocks per CU the register budget is set for (no spills at 127 VGPRs)
 #endif
-// POINT: aa_temperature == 0 (dm2_forward_point.hip left the masks): coverage 1 for every pair of the masks, no pool, no AA terms
-template <bool POINT>
-__global__ void __launch_bounds__(TILE_PIX, DM2_BF_BLOCKS)
+enum Coverage { POOL, POINT, CLIP };      // where a pair's coverage comes from (file header)
+// What the coverage sources do not share: the LDS record (and the parts of the 256-B global record it is copied from),
+// candidate entries per chunk, resident blocks per CU
+template <Coverage COV> struct BfTraits {
+    using Rec = FaceRecB;                                  // 12 of the 16 sixteen-byte parts of the global record (dm2_stage.h)
+    static constexpr int PARTS = FACE_RECB_PARTS;
+    static __device__ __forceinline__ int src_part(int rp) { return recb_src_part(rp); }
+    static constexpr int CAND = DM2_BF_CAND, BLOCKS = DM2_BF_BLOCKS;
+};
+template <> struct BfTraits<CLIP> {
+    using Rec = FaceRec;                                   // the segment clipper classifies: normals and their offsets too, 15 parts
+    static constexpr int PARTS = (int)(sizeof(FaceRec) / 16);
+    static __device__ __forceinline__ int src_part(int rp) { return rp; }
+    // A/B at cfg4 on MI355X: 4 blocks (128 VGPRs) spill 39 registers to scratch, and a scratch reload waits for every
+    // LDS-direct load issued before it: 2.08 ms; 3 blocks (no spill) 1.63 ms
+    static constexpr int CAND = 32, BLOCKS = 3;
+};
+
+template <Coverage COV>
+__global__ void __launch_bounds__(TILE_PIX, BfTraits<COV>::BLOCKS)
 k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                        ImageState is, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                        float* __restrict__ dL_dverts, float* __restrict__ dL_dverts_color,
@@ -62,9 +80,18 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                        const uint64_t* __restrict__ hit_masks, uint32_t* __restrict__ hit_valid,
                        const uint32_t* __restrict__ hit_base, const float* __restrict__ pool,
                        TieEntry* __restrict__ tie_queue, uint32_t tie_cap, bool check_mode STAMP_PARAM) {
-    if (check_mode && hit_valid[0] != (POINT ? 1u : 3u)) return;                  // (caller did not know what the forward left: not masks + pool -> another kernel runs)
+    // (the caller did not know what the forward left: hit_valid[0] 1 point-sampled masks, 2 masks only, 3 masks + pool; anything
+    // else -> another kernel runs)
+    if (check_mode && hit_valid[0] != (COV == POINT ? 1u : COV == CLIP ? 2u : 3u)) return;
+    using Rec = typename BfTraits<COV>::Rec;
+    constexpr int BM_CAND = BfTraits<COV>::CAND;                // candidate entries per chunk
+    static_assert(BM_CAND * 4 <= TILE_PIX && 2 * BM_CAND <= 64, "one scan thread per (face, wave); one id window per wave");
+    constexpr int BM_SLOTS = BM_CAND * 4;
+    constexpr int REC_CHUNKS = BfTraits<COV>::PARTS;
+    constexpr int REC_PER_INSTR = 64 / REC_CHUNKS;              // records one wave instruction copies
+    static_assert(8 * REC_PER_INSTR >= BM_CAND, "two LDS-direct instructions per wave fetch a chunk");
 
-    __shared__ FaceRecB recs2[2][BM_CAND];                     // [buffer]: this chunk's candidates / the next chunk's
+    __shared__ Rec recs2[2][BM_CAND];                          // [buffer]: this chunk's candidates / the next chunk's
     __shared__ float acc[BM_CAND * BM_ACC];
     __shared__ BfPair s_pair[TILE_PIX];
     __shared__ float s_ray[TILE_PIX * 6];
@@ -107,8 +134,8 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     // (backward.cu:171).  The next chunk's inputs go straight from global memory into the other LDS buffer
     // (global_load_lds: per-lane source address, destination = wave-uniform base + lane * size; no registers held).
     auto walk_entry = [&](int k) -> int64_t { return (int64_t)range.x + (uint32_t)(total - 1 - k); };
-    const int rl = lane / REC_CHUNKS, rp = lane - rl * REC_CHUNKS;   // record copy: 5 records x 12 parts per wave instruction
-    const int rsrc = recb_src_part(rp);
+    const int rl = lane / REC_CHUNKS, rp = lane - rl * REC_CHUNKS;   // record copy: 5 records x 12 parts (CLIP 4 x 15) per wave instruction
+    const int rsrc = BfTraits<COV>::src_part(rp);
     // request the id window [nb, nb + 64) of the walk into s_ids2[buf]
     auto request_ids = [&](int buf, int nb) {
         if (wid == 2 && nb + lane < total)
@@ -154,7 +181,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         // load issued before it -- vmcnt is in order -- and must not find this chunk's record loads in front of it)
         if (wid == 1 && (lane >> 1) < nc2)                         // lane: masks of (face lane / 2, waves 2 (lane & 1), + 1)
             glds16(hit_masks + walk_entry(nb + (lane >> 1)) * 4 + (lane & 1) * 2, &s_hit2[buf][0]);
-        if (!POINT && wid == 3 && lane < nc2) glds4(hit_base + walk_entry(nb + lane), &s_hb2[buf][0]);
+        if (COV == POOL && wid == 3 && lane < nc2) glds4(hit_base + walk_entry(nb + lane), &s_hb2[buf][0]);
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             const int r0 = (i * 4 + wid) * REC_PER_INSTR;          // this wave instruction's first record
@@ -181,7 +208,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         STAMP(1)
         const int nc = min(BM_CAND, total - base);
         // recs[j] / s_hit[j][.] = walk position base + j (requested by the previous chunk, or by the prologue)
-        FaceRecB* const recs = recs2[cur];
+        Rec* const recs = recs2[cur];
         const unsigned long long* const s_hit = s_hit2[cur];
         const uint32_t* const s_ids = s_ids2[cur];
         const uint32_t* const s_hb = s_hb2[cur];
@@ -198,7 +225,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         n = max(1, __popcll(__ballot((lane & 1) && inc <= TILE_PIX && (lane >> 1) < nc)));
         const int S = __builtin_amdgcn_readlane(inc, 2 * n - 1);
         if ((lane & 1) == (wid >> 1) && (lane >> 1) < BM_CAND) s_wbase[wid][lane >> 1] = (uint16_t)((wid & 1) ? b1 : b0);    // phase C: slot (face, this wave)
-        if (!POINT && (lane & 1) == 0 && (lane >> 1) < BM_CAND) s_efirst[wid][lane >> 1] = (uint16_t)b0;                              // B2: the face's first pair
+        if (COV == POOL && (lane & 1) == 0 && (lane >> 1) < BM_CAND) s_efirst[wid][lane >> 1] = (uint16_t)b0;                          // B2: the face's first pair
         // pair lane -> slot: every non-empty slot that starts inside this wave's 64 pair lanes leaves a mark at its first
         // pair; a running maximum spreads it (slots and their first pairs grow together); the slot that covers the wave's
         // first lane comes from a ballot
@@ -221,6 +248,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         // ---- phase B2: one blending (pixel,face) pair per lane -------------------------------
         const bool have = tid < S;
         int j = 0, q = 0;
+        float dg[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};                          // CLIP: d(area)/d(corners), carried to D
         float i0 = 0.f, i1 = 0.f, i2 = 0.f, ratio = 0.f, alpha = 0.f;
         int code = 0;
         bool blend = false;
@@ -232,13 +260,27 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             j = lo >> 2;
             q = ((lo & 3) << 6) + nth_set_bit64(s_hit[lo], tid - (int)(mk & 511u));
             // The forward blended this pair: its clip (aa.h:446-504) returned no error and a positive area, the ray met the
-            // face's plane and the coverage was not 0.  None of those decisions is taken again, and the coverage itself --
-            // hence alpha, to the bit -- comes from the forward's pool: the replay divides the running T by (1 - alpha)
-            // (backward.cu:340-348) and the background term by it once more (backward.cu:396-401), so that one ulp of alpha is
-            // ulp / (1 - alpha) of both; with the forward's own number a nearly opaque, nearly covering face is no special case.
+            // face's plane and the coverage was not 0.  None of those decisions is taken again: a pair of the masks is
+            // replayed whatever the recomputed values say (the segment formulation may round an area of 1e-9 to 0, or 1 to
+            // 1 - 1 ulp), otherwise the per-pixel replay below would lose its place in the list.
+            // The replay divides the running T by (1 - alpha) (backward.cu:340-348) and the background term by it once more
+            // (backward.cu:396-401), so that one ulp of alpha is ulp / (1 - alpha) of both.  POOL: the coverage -- hence
+            // alpha, to the bit -- is the forward's own number, and a nearly opaque, nearly covering face is no special case.
             // Pool slot: the entry's first pair + this pair's place among the entry's pairs (the pool is in mask order).
-            ratio = POINT ? 1.0f : pool[s_hb[j] + (uint32_t)(tid - (int)s_efirst[wid][j])];
-            const FaceRecB& fc = recs[j];
+            // CLIP: the segment formulation's shoelace area is good to 2 ulp of the pixel area (2.4e-7): at most 2.4e-6 of T
+            // per entry up to alpha = 0.9, but a nearly opaque, nearly covering face needs the forward's alpha to the bit
+            // (found by the randomised sweep: opacity 1, coverage 0.999998, 1.3 % error in one opacity gradient).
+            // alpha <= opacity, so faces with opacity > 0.9 get the reference's fan sum over the same corners -- the
+            // forward's area exactly (dm2_clip_seg.h); a wave without such a face skips it.
+            if constexpr (COV == CLIP) {
+                const float pxmin = (float)(uint32_t)(X0a + (q & 15)), pymin = (float)(uint32_t)(Y0a + (q >> 4));
+                float oarea;
+                seg_area_grad(recs[j].aa, pxmin, pxmin + 1, pymin, pymin + 1, pix_area, oarea, dg, recs[j].opacity > 0.9f);
+                ratio = fmaxf(oarea, 0.0f) / pix_area;
+            } else {
+                ratio = COV == POINT ? 1.0f : pool[s_hb[j] + (uint32_t)(tid - (int)s_efirst[wid][j])];
+            }
+            const Rec& fc = recs[j];
             BfPair out; out.alpha = 0.f; out.c0 = out.c1 = out.c2 = out.depth = 0.f; out.flags = 0;
             const f3 ro = {s_ray[q * 6], s_ray[q * 6 + 1], s_ray[q * 6 + 2]};
             const f3 rd = {s_ray[q * 6 + 3], s_ray[q * 6 + 4], s_ray[q * 6 + 5]};
@@ -252,6 +294,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 float iuc, ivc;
                 clamp_bary_uv(tuv.y, tuv.z, iuc, ivc, code);
                 i0 = 1 - iuc - ivc; i1 = iuc; i2 = ivc;
+                if constexpr (COV == CLIP) ratio = mix_coverage(code, ratio, temp);
                 float c0 = i0 * fc.col[0] + i1 * fc.col[3] + i2 * fc.col[6];
                 float c1 = i0 * fc.col[1] + i1 * fc.col[4] + i2 * fc.col[7];
                 float c2 = i0 * fc.col[2] + i1 * fc.col[5] + i2 * fc.col[8];
@@ -397,18 +440,27 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 }
             }
             ISA_MARK(D_group2)
-            // group 2: AA corners.  d(area)/d(corners) without a polygon (dm2_clip_fast.h); a pair it flags as a tie adds nothing
-            // here: it is queued with its dL/d(area) for the exact clipper (k_aa_ties below).  One atomic per wave with such a
-            // pair, its return value looked at behind group 3.
+            // group 2: AA corners.  POOL: d(area)/d(corners) without a polygon (dm2_clip_fast.h); a pair it flags as a tie adds
+            // nothing here: it is queued with its dL/d(area) for the exact clipper (k_aa_ties below).  One atomic per wave with
+            // such a pair, its return value looked at behind group 3.  CLIP: B2's Jacobian.
             bool tie_push = false;
             uint32_t tie_base = 0;
             unsigned long long tie_bal = 0;
-            if (!POINT) {
+            if constexpr (COV == CLIP) {
+                float g2[6];
+#pragma unroll
+                for (int c = 0; c < 6; c++) g2[c] = dL_doarea * dg[c];                   // dL_doarea is 0 on inactive lanes
+                seg_scan16_safe(g2, m1, m2, m4, m8, s1, s2, s4, s8);
+                if (emit) {
+#pragma unroll
+                    for (int c = 0; c < 6; c++) atomicAdd(arow + M_AA + c, g2[c]);
+                }
+            } else if constexpr (COV == POOL) {
                 float g2[6];
                 bool tie = false;
                 {
                     const FaceRecB& fb = recs[j];
-                    const AAFaceB fa = {fb.v2, fb.e, fb.r, fb.zmask};
+                    const AAFaceB fa = {fb.v2, fb.e, fb.r, rec_zmask(fb)};
                     const float pxmin = (float)(uint32_t)(X0a + (q & 15)), pymin = (float)(uint32_t)(Y0a + (q >> 4));
                     fast_area_grad(fa, pxmin, pxmin + 1, pymin, pymin + 1, g2, tie);
                 }
@@ -461,7 +513,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         // ---- flush: lane = (entry, component); 8 entries per pass ------------------------------
         // Branch-free: every component's destination is  base + 4 (id * mult),  id one of the record's (face_id, vid[0..2]).
         const int comp = tid & 31;
-        if (comp < (POINT ? M_AA : M_N)) {                                    // (no AA components at temperature 0)
+        if (comp < (COV == POINT ? M_AA : M_N)) {                             // (no AA components at temperature 0)
             float* const basep = s_fl_base[comp];                                 // (per-component table, filled in the prologue)
             const int entry = s_fl_sel[comp];
             const bool corner = (entry & 0x80) != 0;                              // DM2_FLAG_AA_GRAD_TO_VERTS: an AA corner on its way to its vertex
@@ -472,7 +524,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 const float flag = a[M_FLAG];                                     // (the 32 lanes of an entry sit in one wave)
                 const float val = a[comp];
                 int sel = sel0;
-                if (corner) { int m_; flush_id_and_mult(entry, recs[e].zmask, sel, m_); }      // (the record knows the reorder)
+                if (corner) { int m_; flush_id_and_mult(entry, rec_zmask(recs[e]), sel, m_); }   // (the record knows the reorder)
                 const int id = (&recs[e].face_id)[sel];
                 if (flag != 0.f) {
                     a[comp] = 0.f;                                                // ready for the next chunk
@@ -562,27 +614,24 @@ k_aa_ties(dm2_render_desc d, const uint4* __restrict__ face_recs, const TieEntry
     if (s_ticket == working - 1 && threadIdx.x == 0) { counters[2] = 0u; counters[3] = 0u; }
 }
 
-// check_mode: the caller does not know what the forward left (DM2_FWD_UNKNOWN): both kernels look at hit_valid themselves
+// clip: the forward left masks but no pool (DM2_FWD_MASKS; aa_temperature > 0).  check_mode: the caller does not know what
+// the forward left (DM2_FWD_UNKNOWN): the kernels look at hit_valid themselves
 void launch_render_backward_fast(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                                  const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
                                  float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
-                                 float* dL_daa_face_verts, const BinningState& bs, TieEntry* tie_queue, int64_t tie_cap,
+                                 float* dL_daa_face_verts, const BinningState& bs, bool clip, TieEntry* tie_queue, int64_t tie_cap,
                                  bool check_mode, hipStream_t st) {
     const uint32_t Tn = (uint32_t)(((d.W + TILE - 1) / TILE) * ((d.H + TILE - 1) / TILE) * d.B);
     const uint32_t cap = (uint32_t)(tie_cap > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : tie_cap);
-    if (!(d.aa_temperature > 0.0f)) {                      // point-sampled coverage: the masks of dm2_forward_point.hip, nothing else
-        StageTimer tm(check_mode ? -1 : ST_BWD, st);
-        hipLaunchKernelGGL(k_render_backward_fast<true>, dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
-                           dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts,
-                           bs.hit_masks, bs.hit_valid, bs.hit_base, bs.pool, tie_queue, 0u, check_mode STAMP_ARG(1));
-        return;
-    }
-    {
+    auto launch = [&](auto kernel, uint32_t kcap) {
         StageTimer tm(check_mode ? -1 : ST_BWD, st);       // (under DM2_FWD_UNKNOWN the caller times the whole cascade)
-        hipLaunchKernelGGL(k_render_backward_fast<false>, dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
+        hipLaunchKernelGGL(kernel, dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
                            dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts,
-                           bs.hit_masks, bs.hit_valid, bs.hit_base, bs.pool, tie_queue, cap, check_mode STAMP_ARG(1));
-    }
+                           bs.hit_masks, bs.hit_valid, bs.hit_base, bs.pool, tie_queue, kcap, check_mode STAMP_ARG(1));
+    };
+    if (!(d.aa_temperature > 0.0f)) { launch(k_render_backward_fast<POINT>, 0u); return; }   // point-sampled coverage: the masks of dm2_forward_point.hip, nothing else
+    if (clip) { launch(k_render_backward_fast<CLIP>, 0u); return; }
+    launch(k_render_backward_fast<POOL>, cap);
     const unsigned blocks = (unsigned)((cap + 255u) / 256u < 1024u ? (cap + 255u) / 256u : 1024u);
     StageTimer tm(check_mode ? -1 : ST_TIES, st);
     if (blocks) hipLaunchKernelGGL(k_aa_ties, dim3(blocks), dim3(256), 0, st, d, is.face_recs, tie_queue, cap, bs.hit_valid, dL_daa_face_verts, check_mode);

@@ -1,5 +1,5 @@
-// dm2_bwd_shared.h -- accumulator-row layout, pair records and small helpers of the backward kernels (dm2_backward_mask.hip,
-// dm2_backward_fast.hip; dm2_backward.hip uses the row layout with its own pitch).
+// dm2_bwd_shared.h -- accumulator-row layout, the pair record and small helpers of the backward kernels
+// (dm2_backward_fast.hip; dm2_backward.hip uses the row layout with its own pitch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,8 +14,6 @@ constexpr int BM_ACC = DM2_BM_ACC;       // pitch of an accumulator row (dwords)
 constexpr int M_DV = 0, M_DC = 9, M_DZ = 18, M_OP = 21, M_IN = 22, M_AA = 23, M_N = 29, M_FLAG = 31;
 constexpr uint32_t MB_BLEND = 1u, MB_ACTIVE = 2u;
 
-struct __attribute__((aligned(16))) BmPair { float alpha, c0, c1, c2, depth; uint32_t flags; float T, dL_dalpha; };
-static_assert(sizeof(BmPair) == 32, "BmPair");
 // dm2_backward_fast.hip: phase B2 leaves (alpha, colour, depth), phase C replaces alpha by dL/dalpha and depth by the T in
 // front of the pair and sets the flags; phase D reads the pixel's loss gradients from the per-pixel LDS rows itself
 struct __attribute__((aligned(8))) BfPair { float alpha, c0, c1, c2, depth; uint32_t flags; };

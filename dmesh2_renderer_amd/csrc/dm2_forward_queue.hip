@@ -120,7 +120,7 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     const uint2 range = ranges[tile];
     const int total = (int)(range.y - range.x);
     const uint4* const grecs = is.face_recs + (int64_t)b * d.F * FACE_REC_U4;
-    // Memory pipeline (see dm2_backward_mask.hip, dm2_stage.h): packed face records go straight from global memory into
+    // Memory pipeline (see dm2_backward_fast.hip, dm2_stage.h): packed face records go straight from global memory into
     // LDS.  Phase B2 is the last reader of a chunk's records, so the NEXT chunk's are requested into the same array right
     // behind it (its cut is known by then) and land while the pixels blend (phase C) -- no second buffer: 4 blocks per CU
     // with 52-face chunks.  The ids a record address needs are requested one phase earlier and land during B2.
@@ -346,10 +346,10 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         lds_prefetch_wait();
         __syncthreads();
         if (base + n < total) request_recs(base + n);              // B2 was the records' last reader: refill behind it
-        // what the backward needs to find its work without re-classifying (dm2_backward_mask.hip): per list entry and
+        // what the backward needs to find its work without re-classifying (dm2_backward_fast.hip): per list entry and
         // wave of the tile's block, the pixels the entry blends into
         if (hit_masks && tid < n * 4) hit_masks[((int64_t)range.x + base + (tid >> 2)) * 4 + (tid & 3)] = s_bmask[tid];
-        // ... and (dm2_backward_fast.hip) the coverage of every such pair, so that the backward neither clips for an area nor
+        // ... and (its POOL instantiation) the coverage of every such pair, so that the backward neither clips for an area nor
         // depends on reproducing it: pool slots in mask order -- entry by entry, wave by wave, pixel by pixel -- behind the
         // chunk's first slot; per entry the slot of its first pair.
         if (pool) {

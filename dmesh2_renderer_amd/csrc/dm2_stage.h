@@ -57,6 +57,9 @@ constexpr int FACE_RECB_PARTS = 12 + DM2_FACERECB_PAD;       // (the pad is copi
 __device__ __forceinline__ int recb_src_part(int rp) { return rp < 5 ? rp : (rp < 12 ? rp + 3 : 15); }
 // view of a FaceRecB's AA members under the names dm2_clip_fast.h uses
 struct AAFaceB { const float* v; const float* e; const float* r; uint32_t zmask; };
+// the edge-flag word of either LDS record (bits 0-5: the edge flags, bit 8: the CCW reorder swapped corners 1 and 2)
+__device__ __forceinline__ uint32_t rec_zmask(const FaceRec& r) { return r.aa.zmask; }
+__device__ __forceinline__ uint32_t rec_zmask(const FaceRecB& r) { return r.zmask; }
 
 // Copy the packed record of (view, face) `bf` into LDS (one lane per record: 15 loads of 16 bytes from two 128-byte
 // lines; the kernels with a prefetch pipeline copy cooperatively instead, 16 lanes per record).

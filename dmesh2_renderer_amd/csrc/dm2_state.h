@@ -185,15 +185,11 @@ void launch_prepare_faces_backward(const dm2_prep_desc& d, const float* g_ndc, c
 void launch_render_forward_queue(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                                  float* out_color, float* out_depth, int32_t* out_tri_cnt, uint64_t* hit_masks,
                                  uint32_t* hit_valid, float* pool, int64_t pool_cap, uint32_t* hit_base, bool classes, hipStream_t st);
-void launch_render_backward_mask(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
-                                 const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
-                                 float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
-                                 float* dL_daa_face_verts, const uint64_t* hit_masks, const uint32_t* hit_valid, hipStream_t st);
 void launch_render_backward_fast(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                                  const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
                                  float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
-                                 float* dL_daa_face_verts, const BinningState& bs, TieEntry* tie_queue, int64_t tie_cap,
-                                 bool check_mode, hipStream_t st);
+                                 float* dL_daa_face_verts, const BinningState& bs, bool clip, TieEntry* tie_queue,
+                                 int64_t tie_cap, bool check_mode, hipStream_t st);
 // fwd_mode: DM2_FWD_* of the forward.  The selection table is in dm2_backward.hip: a mode that matches the temperature
 // launches its kernel(s) unchecked; DM2_FWD_UNKNOWN, or a mode no forward at this temperature returns, launches a cascade
 // of candidates that look at hit_valid on the device, exactly one of which works

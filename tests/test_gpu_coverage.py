@@ -99,7 +99,7 @@ def test_cfg1_full_size(kernels, from_image):
 @pytest.mark.parametrize("temp", [1.0, 0.5, 0.0])
 def test_backward_without_forward_masks(temp):
     """Forward with the per-pixel-walk kernels (no blend masks; the binning resets hit_valid), backward with the default
-    flags: the mask-driven kernels (dm2_backward_mask.hip, dm2_backward_fast.hip) must stand down on the device and the
+    flags: the mask-driven kernels (every instantiation of dm2_backward_fast.hip) must stand down on the device and the
     fallback (k_render_backward) must produce the gradients."""
     C, orc = _C(), _orc()
     args = _soup(96, 80, 700, 21, temp)
@@ -203,18 +203,21 @@ def test_fuzz4_regression(kernels):
 def test_nearly_opaque_nearly_covering_faces(seed, idx):
     """Cases of the randomised sweep (tests/fuzz_parity.py, replayable by (seed, idx)) with faces of opacity exactly 1: a
     pixel's last contributor with alpha = 1 - 2e-6 makes the replay's T / (1 - alpha) and the background term
-    -final_T / (1 - alpha) (backward.cu:340-348, 396-401) amplify one ulp of alpha to 3 %.  The mask-driven backward
+    -final_T / (1 - alpha) (backward.cu:340-348, 396-401) amplify one ulp of alpha to 3 %.  The masks-only backward
     recomputes the coverage with its own (segment) clipper, good to 2 ulp -- it must fall back to the forward's exact clip
-    for such pairs (dm2_backward_mask.hip, alpha > 0.9).  Before that: 2.9e-3 / 1.1e-4 / 6.6e-5 on these three."""
+    for such pairs (dm2_backward_fast.hip CLIP, opacity > 0.9).  Before that: 2.9e-3 / 1.1e-4 / 6.6e-5 on these three.  The
+    default backward takes alpha from the forward's pair pool; both routes are held to it."""
     import fuzz_parity
     C = _C()
-    old = C.set_flags(0)
-    try:
-        ok, worst, desc = fuzz_parity.one_case(seed, idx)
-    finally:
-        C.set_flags(old)
-    assert ok, desc
-    assert worst <= GRAD_TOL or desc.get("accepted_as_summation_noise", False), (worst, desc)
+    for flags in (0, C.DM2_FLAG_NO_PAIR_POOL):
+        old = C.set_flags(flags)
+        try:
+            ok, worst, desc = fuzz_parity.one_case(seed, idx)
+            assert (C.last_forward_mode() == C.FWD_POOL) == (flags == 0)
+        finally:
+            C.set_flags(old)
+        assert ok, (flags, desc)
+        assert worst <= GRAD_TOL or desc.get("accepted_as_summation_noise", False), (flags, worst, desc)
 
 
 # ---- the reference's record-stack desync corner (SURVEY.md appendix A), constructed ------------------------------
@@ -314,8 +317,8 @@ def test_aa_gradient_routing_does_not_depend_on_the_forwards_flags():
                                    "point", "unknown_point", "mismatched"])
 def test_backward_kernel_selection(route):
     """The backward's kernel follows what the forward left (include/dm2_hip.h DM2_FWD_*): masks + pair pool -> the polygon-free
-    kernel + tie pass; masks only (the caller gave the pool no room) -> the exact-clipper mask kernel; point-sampled masks
-    (temperature 0) -> the POINT instantiation of the polygon-free kernel; not told, or told a mode that no forward at this
+    kernel + tie pass; masks only (the caller gave the pool no room) -> its CLIP instantiation (the segment clipper);
+    point-sampled masks (temperature 0) -> its POINT instantiation; not told, or told a mode that no forward at this
     temperature returns -> the candidates are launched and look at the device-side word themselves (exactly one works: a
     wrong stand-down rule would double the gradients).  Same gradients on every route."""
     C = _C()
