@@ -8,6 +8,10 @@ tuple returns:
     render_backward_cuda(...31 args...) -> 6-tuple    (render.cu:198-373)
     generate_render_layers_cuda(...13 args...) -> 2-tuple (render.cu:378-476)
 
+and the consumer of those layers the reference does not have (LayeredRenderer.render):
+
+    composite_layers_cuda(...10 args...) -> 4-tuple, composite_layers_backward_cuda(...13 args...) -> 4-tuple
+
 PyTorch is used only as the owner of device memory and of the current stream;
 every computation happens in the HIP library.  There is NO fallback: if the
 library is missing, or tensors are not on a ROCm device, a RuntimeError is
@@ -76,6 +80,15 @@ class LayersDesc(ctypes.Structure):
     ]
 
 
+class LayerCompositeDesc(ctypes.Structure):
+    _fields_ = [
+        ("B", _i32), ("P", _i32), ("F", _i32), ("W", _i32), ("H", _i32), ("L", _i32), ("flags", _i32),
+        ("render_layers", _vp), ("verts", _vp), ("faces", _vp), ("verts_color", _vp), ("faces_opacity", _vp),
+        ("faces_intense", _vp), ("verts_ndc", _vp), ("background", _vp), ("image_ray_o", _vp), ("image_ray_d", _vp),
+        ("ray_cam", _vp),
+    ]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "dm2_abi_version": (ctypes.c_int, []),
@@ -90,6 +103,8 @@ EXPORTS = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_plan": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _sz, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "dm2_layers_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
+    "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_prepare_faces": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp]),
     "dm2_prepare_faces_backward": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_exchange_mark": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp, _vp, _vp]),
@@ -581,6 +596,105 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
     generate_render_layers_cuda.last_debug = (R, face_buf, bin_buf, img_buf)      # kept for tests
     return layers, cnt
 
+
+def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
+                    image_ray_o, image_ray_d, keep):
+    """Checks (in the style of generate_render_layers_cuda) + the dm2_layer_composite_desc of a composite call."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(render_layers.dim() != 4, "render_layers must have dimensions (B, H, W, L)")
+    bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
+    bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
+    bad(verts_color.dim() != 2 or verts_color.size(1) != 3, "vert color must have dimensions (P, 3)")
+    bad(faces_opacity.dim() != 1 or faces_opacity.size(0) != faces.size(0), "face opacity must have dimensions (F,)")
+    bad(faces_intense.dim() != 2 or faces_intense.size(1) != faces.size(0), "faces_intense must have dimensions (B, F,)")
+    bad(verts_ndc.dim() != 3 or verts_ndc.size(2) != 3, "verts_ndc must have dimensions (B, P, 3)")
+    bad(background.dim() != 1 or background.size(0) != 3, "background must have dimensions (3,)")
+    bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
+    bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
+    dev = _require_gpu(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
+                       image_ray_o, image_ray_d)
+    f32, i32 = torch.float32, torch.int32
+    B, H, W, L = (int(x) for x in render_layers.shape)
+    P, F = verts.size(0), faces.size(0)
+    bad(tuple(verts_color.shape) != (P, 3), "verts_color must have dimensions (P, 3)")
+    bad(tuple(faces_intense.shape) != (B, F), "faces_intense must have dimensions (B, F)")
+    bad(tuple(verts_ndc.shape) != (B, P, 3), "verts_ndc must have dimensions (B, P, 3)")
+    ana = _analytic(B, dev)
+    bad(ana is None and (tuple(image_ray_o.shape) != (B, H, W, 3) or tuple(image_ray_d.shape) != (B, H, W, 3)),
+        "image_ray_o/image_ray_d must have dimensions (B, H, W, 3)")
+    ts = dict(render_layers=_c(render_layers, i32), verts=_c(verts, f32), faces=_c(faces, i32), verts_color=_c(verts_color, f32),
+              faces_opacity=_c(faces_opacity, f32), faces_intense=_c(faces_intense, f32), verts_ndc=_c(verts_ndc, f32),
+              background=_c(background, f32), image_ray_o=_c(image_ray_o, f32), image_ray_d=_c(image_ray_d, f32))
+    keep += list(ts.values())
+    d = LayerCompositeDesc()
+    d.B, d.P, d.F, d.W, d.H, d.L, d.flags = B, P, F, W, H, L, 0
+    for k, t in ts.items():
+        setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
+    if ana is not None:
+        if (ana[1], ana[2]) != (W, H):
+            raise RuntimeError("analytic_rays: the image size differs from render_layers' width / height")
+        keep.append(ana[0])
+        d.flags |= DM2_FLAG_ANALYTIC_RAYS
+        d.ray_cam = ana[0].data_ptr()
+        d.image_ray_o = d.image_ray_d = None
+    return d, dev
+
+
+def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
+                          image_ray_o, image_ray_d):
+    """Front-to-back compositing of per-pixel face layers (include/dm2_hip.h: dm2_layers_composite).
+
+    render_layers (B,H,W,L) int32 (ids outside [0, F) are skipped), verts (P,3), faces (F,3) int32, verts_color (P,3),
+    faces_opacity (F), faces_intense (B,F), verts_ndc (B,P,3), background (3), image_ray_o / image_ray_d (B,H,W,3) of the
+    full frame (placeholders under ``analytic_rays``) -> (color (B,H,W,3), depth_raw (B,H,W) NDC depth with background 1,
+    final_T (B,H,W), n_contrib (B,H,W) int32: 1 + index of the last layer that blended)."""
+    lib = load_library()
+    keep: list = []
+    d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
+                             image_ray_o, image_ray_d, keep)
+    B, H, W = d.B, d.H, d.W
+    f32 = torch.float32
+    color = torch.empty((B, H, W, 3), dtype=f32, device=dev)
+    depth = torch.empty((B, H, W), dtype=f32, device=dev)
+    final_T = torch.empty((B, H, W), dtype=f32, device=dev)
+    n_contrib = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    if B * H * W == 0:
+        return color, depth, final_T, n_contrib
+    with torch.cuda.device(dev):
+        if lib.dm2_layers_composite(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib), _stream(dev)):
+            raise _err(lib, "composite_layers_cuda")
+    return color, depth, final_T, n_contrib
+
+
+def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
+                                   image_ray_o, image_ray_d, n_contrib, dL_dcolor, dL_ddepth):
+    """Gradients of composite_layers_cuda (dm2_layers_composite_backward): dL_dcolor (B,H,W,3), dL_ddepth (B,H,W) of depth_raw,
+    n_contrib from the forward -> (dL_dverts_color (P,3), dL_dfaces_opacity (F), dL_dverts_ndc (B,P,3) [z only],
+    dL_dfaces_intense (B,F)).  Nothing reaches verts (through the barycentrics) or background."""
+    lib = load_library()
+    keep: list = []
+    d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
+                             image_ray_o, image_ray_d, keep)
+    B, P, F, H, W = d.B, d.P, d.F, d.H, d.W
+    f32 = torch.float32
+    for t, shape, nm in ((n_contrib, (B, H, W), "n_contrib"), (dL_dcolor, (B, H, W, 3), "dL_dcolor"), (dL_ddepth, (B, H, W), "dL_ddepth")):
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{nm} must have dimensions {shape}, got {tuple(t.shape)}")
+        _require_gpu(render_layers, t)
+    nc, gc, gd = _c(n_contrib, torch.int32), _c(dL_dcolor, f32), _c(dL_ddepth, f32)
+    dcolor = torch.zeros((P, 3), dtype=f32, device=dev)
+    dopacity = torch.zeros((F,), dtype=f32, device=dev)
+    dndc = torch.zeros((B, P, 3), dtype=f32, device=dev)
+    dintense = torch.zeros((B, F), dtype=f32, device=dev)
+    if B * H * W == 0:
+        return dcolor, dopacity, dndc, dintense
+    with torch.cuda.device(dev):
+        if lib.dm2_layers_composite_backward(ctypes.byref(d), _ptr(gc), _ptr(gd), _ptr(nc), _ptr(dcolor), _ptr(dopacity),
+                                             _ptr(dndc), _ptr(dintense), _stream(dev)):
+            raise _err(lib, "composite_layers_backward_cuda")
+    return dcolor, dopacity, dndc, dintense
 
 def _prep_desc(verts, faces, mv, proj, width, height, keep):
     dev = _require_gpu(verts, faces, mv, proj)

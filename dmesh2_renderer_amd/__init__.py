@@ -4,7 +4,8 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
 
 * ``RenderFunction``  (reference :11-177)  torch.autograd.Function, 21 inputs -> (color, depth)
 * ``Renderer``        (reference :179-380) nn.Module: host prep (rays, projection, AA tables) + op
-* ``LayeredRenderer`` (reference :388-451) ``generate()`` -> (render_layers, render_layers_cnt)
+* ``LayeredRenderer`` (reference :388-451) ``generate()`` -> (render_layers, render_layers_cnt), and (not in the
+  reference) ``render()``: those layers composited into (color, depth), differentiable (``LayeredCompositeFunction``)
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -22,7 +23,7 @@ import torch
 from . import _C
 from .pyrenderer import Triangles
 
-__all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "Triangles"]
+__all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "Triangles"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -291,12 +292,48 @@ class Renderer(torch.nn.Module):
         return color, depth
 
 
-class LayeredRenderer(Renderer):
-    """Reference ``LayeredRenderer`` (__init__.py:388-451): non-differentiable per-pixel face layers.
+class LayeredCompositeFunction(torch.autograd.Function):
+    """Differentiable front-to-back compositing of per-pixel face layers (``_C.composite_layers_cuda``).
 
-    Like the reference it is used through ``generate`` only.  (The reference
-    skips ``nn.Module.__init__``; here the module is initialised properly,
-    which changes nothing observable.)
+    Inputs: render_layers (B,H,W,L) int32 (ids outside [0, F) are skipped), verts (P,3), faces (F,3) int32,
+    verts_color (P,3)*, faces_opacity (F)*, faces_intense (B,F)*, verts_ndc (B,P,3)* [grad only in z], background (3),
+    image_ray_o, image_ray_d (B,H,W,3) (placeholders under ``_C.analytic_rays``).  Outputs: color (B,H,W,3) and the raw
+    NDC depth (B,H,W), background 1.  (* = receives a gradient.)
+
+    Per pixel a layer blends where the pixel's ray hits its face inside the triangle (Renderer's coverage at
+    aa_temperature 0), with the same colour, depth and alpha as Renderer.  No gradient reaches ``verts`` through the
+    barycentrics: layers from the tet walk are piecewise constant in the points, and DMesh++ holds the points fixed on
+    this path.  ``background`` gets no gradient, as in Renderer.
+    """
+
+    @staticmethod
+    def forward(ctx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
+                image_ray_o, image_ray_d):
+        ctx.analytic = getattr(_C._tls, "analytic", None)
+        color, depth, _final_T, n_contrib = _C.composite_layers_cuda(
+            render_layers, verts.detach(), faces, verts_color.detach(), faces_opacity.detach(), faces_intense.detach(),
+            verts_ndc.detach(), background, image_ray_o, image_ray_d)
+        ctx.save_for_backward(render_layers, verts.detach(), faces, verts_color.detach(), faces_opacity.detach(),
+                              faces_intense.detach(), verts_ndc.detach(), background, image_ray_o, image_ray_d, n_contrib)
+        return color, depth
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_depth):
+        (render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
+         n_contrib) = ctx.saved_tensors
+        ana = ctx.analytic
+        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))):
+            dcolor, dopacity, dndc, dintense = _C.composite_layers_backward_cuda(
+                render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
+                n_contrib, grad_color, grad_depth)
+        return None, None, None, dcolor, dopacity, dintense, dndc, None, None, None
+
+
+class LayeredRenderer(Renderer):
+    """Reference ``LayeredRenderer`` (__init__.py:388-451): non-differentiable per-pixel face layers (``generate``).
+
+    Not in the reference: ``render`` composites such layers into an image, differentiably.  (The reference skips
+    ``nn.Module.__init__``; here the module is initialised properly, which changes nothing observable.)
     """
 
     def __init__(self, mv, proj, width, height, device, fused_prep=None, analytic_rays=False):
@@ -331,3 +368,34 @@ class LayeredRenderer(Renderer):
             verts.to(f32), faces.to(i32), tets.to(i32), face_tets.to(i32), tet_faces.to(i32),
             faces_existence.to(i32), verts_ndc.to(f32), verts_image.to(f32),
             ray_o.to(f32), ray_d.to(f32), num_layers)
+
+    def render(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
+               verts_color: torch.Tensor, faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor):
+        """Composite per-pixel face layers front to back -> color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background).
+
+        render_layers (B,H,W,L) int32 over the full frame, e.g. from ``generate`` (-1 and any id outside [0, F) is skipped,
+        holes included); faces_intense (B,F) of the selected views.  A layer blends where the pixel's ray hits its face
+        inside the triangle, with Renderer's colour, depth and alpha at aa_temperature 0 (LayeredCompositeFunction).
+        Gradients reach verts_color, faces_opacity, faces_intense, and verts through the projected depth only (as in
+        Renderer); none goes through the barycentrics, in which the layers are piecewise constant.
+        """
+        mv = self.mv[batch_mvp_idx]
+        proj = self.proj[batch_mvp_idx]
+        i32, f32 = torch.int32, torch.float32
+        if getattr(self, "fused_prep", False) and verts.is_cuda:
+            from . import prep
+            verts_ndc, _ = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
+        else:
+            verts_ndc, _ = self.compute_verts_ndc_image(verts, mv, proj)
+        args = (render_layers.to(i32), verts.to(f32), faces.to(i32), verts_color.to(f32), faces_opacity.to(f32),
+                faces_intense.to(f32), verts_ndc.to(f32), background.to(f32))
+        if getattr(self, "analytic_rays", False):
+            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
+            ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
+            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
+                color, depth = LayeredCompositeFunction.apply(*args, ph, ph)
+        else:
+            ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
+            color, depth = LayeredCompositeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32))
+        # NDC z in [-1,1] (background +1) -> [0,1] with background 0, as Renderer.forward
+        return color, 1.0 - (depth + 1.0) / 2.0

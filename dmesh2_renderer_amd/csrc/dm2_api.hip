@@ -382,6 +382,48 @@ int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_t
     return 0;
 }
 
+static int check_composite_desc(const dm2_layer_composite_desc* d) {
+    if (!d) return fail("null descriptor");
+    if (d->B < 0 || d->P < 0 || d->F < 0 || d->W < 0 || d->H < 0 || d->L < 0) return fail("negative size in descriptor");
+    const int64_t gx = (d->W + dm2::TILE - 1) / dm2::TILE, gy = (d->H + dm2::TILE - 1) / dm2::TILE;
+    if (gx > 0x7FFFFFFF || gy > 0xFFFF || d->B > 65535) return fail("image too large");
+    const int64_t N = (int64_t)d->B * d->H * d->W;
+    if (N == 0) return 0;
+    if (!d->background) return fail("background must not be null");
+    if (d->L > 0 && !d->render_layers) return fail("render_layers must not be null");
+    if (d->F > 0 && (!d->faces || !d->verts || !d->verts_color || !d->faces_opacity || !d->faces_intense || !d->verts_ndc))
+        return fail("the per-face / per-vertex inputs must not be null");
+    if (d->flags & DM2_FLAG_ANALYTIC_RAYS) {
+        if (!d->ray_cam) return fail("DM2_FLAG_ANALYTIC_RAYS needs ray_cam");
+    } else if (!d->image_ray_o || !d->image_ray_d) {
+        return fail("image_ray_o / image_ray_d must not be null");
+    }
+    return 0;
+}
+
+int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
+                         int32_t* out_n_contrib, void* stream) {
+    if (check_composite_desc(d)) return 1;
+    if ((int64_t)d->B * d->H * d->W == 0) return 0;
+    if (!out_color || !out_depth || !out_n_contrib) return fail("out_color / out_depth / out_n_contrib must not be null");
+    dm2::launch_layer_composite(*d, out_color, out_depth, out_final_T, out_n_contrib, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
+                                  const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
+                                  float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream) {
+    if (check_composite_desc(d)) return 1;
+    if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0) return 0;       // nothing blends: all gradients stay zero
+    if (!dL_dout_color || !dL_dout_depth || !n_contrib) return fail("dL_dout_color / dL_dout_depth / n_contrib must not be null");
+    if (!dL_dverts_color || !dL_dfaces_opacity || !dL_dverts_ndc || !dL_dfaces_intense) return fail("gradient outputs must not be null");
+    dm2::launch_layer_composite_backward(*d, dL_dout_color, dL_dout_depth, n_contrib, dL_dverts_color, dL_dfaces_opacity,
+                                         dL_dverts_ndc, dL_dfaces_intense, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_prep_desc(const dm2_prep_desc* d) {
     if (!d) return fail("null descriptor");
     if (d->B < 0 || d->P < 0 || d->F < 0 || d->W < 0 || d->H < 0) return fail("negative size in descriptor");

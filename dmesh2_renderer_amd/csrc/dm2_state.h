@@ -211,6 +211,12 @@ hipError_t launch_exchange_unpack(int B, int P, int F, int N, int rank, const fl
 int exchange_max_ranks();
 size_t tet_scratch_bytes(int64_t T);
 // tet_scratch (tet_scratch_bytes(T)) holds the packed per-tet records of the walk; nullptr = the reference-shaped walk
+// LayeredRenderer.render (dm2_layer_composite.hip)
+void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color, float* out_depth, float* out_final_T,
+                            int32_t* out_n_contrib, hipStream_t st);
+void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const float* dL_dcolor, const float* dL_ddepth,
+                                     const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
+                                     float* dL_dverts_ndc, float* dL_dfaces_intense, hipStream_t st);
 void launch_layers(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                    LayerImageState ls, void* tet_scratch, int32_t* render_layers, int32_t* render_layers_cnt, hipStream_t st);
 

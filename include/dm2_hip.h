@@ -229,6 +229,46 @@ int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_t
                    void* tet_scratch, size_t tet_bytes,
                    int32_t* render_layers, int32_t* render_layers_cnt, void* stream);
 
+/* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
+ * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
+ *   1. skip f < 0 or f >= F (holes and out-of-range ids are allowed and never read through);
+ *   2. intersect the pixel's ray (image_ray_o / image_ray_d, or DM2_FLAG_ANALYTIC_RAYS) with verts[faces[f]]
+ *      (Moeller-Trumbore as the Renderer's kernels evaluate it); skip an edge case (zero denominator);
+ *   3. clamp the barycentrics; skip unless the clamp code is 0 (Renderer's coverage at aa_temperature 0);
+ *   4. i0 = 1-u-v, i1 = u, i2 = v; iC = (i0 c0 + i1 c1 + i2 c2) * faces_intense[b,f]; iD = i0 z0 + i1 z1 + i2 z2 with
+ *      z = verts_ndc[b,.,2]; alpha = faces_opacity[f];
+ *   5. C += iC alpha T, D += iD alpha T, T *= 1 - alpha; stop once T < 1e-4.
+ * out_color = C + T background (B,H,W,3), out_depth = D + T (B,H,W; NDC depth, background 1), out_final_T = T (B,H,W),
+ * out_n_contrib (B,H,W) int32 = 1 + the index of the last layer that blended (0: none).  out_final_T may be NULL;
+ * out_n_contrib is what the backward takes.  Bit-exact: the same fp32 operations, in the same order, as the
+ * point-sampled Renderer forward. */
+typedef struct dm2_layer_composite_desc {
+    int32_t B, P, F;
+    int32_t W, H, L;              /* full frame width/height, layers per pixel */
+    int32_t flags;                /* DM2_FLAG_ANALYTIC_RAYS */
+    const int32_t* render_layers; /* (B,H,W,L) */
+    const float* verts;           /* (P,3) */
+    const int32_t* faces;         /* (F,3) */
+    const float* verts_color;     /* (P,3) */
+    const float* faces_opacity;   /* (F) */
+    const float* faces_intense;   /* (B,F) */
+    const float* verts_ndc;       /* (B,P,3) */
+    const float* background;      /* (3) */
+    const float* image_ray_o;     /* (B,H,W,3); may be NULL with DM2_FLAG_ANALYTIC_RAYS */
+    const float* image_ray_d;     /* (B,H,W,3); may be NULL with DM2_FLAG_ANALYTIC_RAYS */
+    const float* ray_cam;         /* DM2_FLAG_ANALYTIC_RAYS: (B,32), see dm2_render_desc */
+} dm2_layer_composite_desc;
+
+int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
+                         int32_t* out_n_contrib, void* stream);
+/* Gradients of the composite w.r.t. verts_color (P,3), faces_opacity (F), verts_ndc (B,P,3; only z written) and
+ * faces_intense (B,F); the four outputs must be zero-filled by the caller.  No gradient reaches verts through the
+ * barycentrics (the layers are piecewise constant in the points) and none reaches background.  n_contrib: what the
+ * forward of the same inputs wrote.  Division-free in alpha: opacities of exactly 1.0 are fine. */
+int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
+                                  const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
+                                  float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
+
 /* Host prep of Renderer.forward / LayeredRenderer.generate, fused.
  * Replaces the ~20 torch kernels of the reference's Python host layer:
  *   compute_verts_ndc_image  dmesh2_renderer/__init__.py:239-262  (projection, |w| clamp, NDC -> image)
