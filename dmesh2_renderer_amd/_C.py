@@ -12,6 +12,9 @@ and the consumer of those layers the reference does not have (LayeredRenderer.re
 
     composite_layers_cuda(...10 args...) -> 4-tuple, composite_layers_backward_cuda(...13 args...) -> 4-tuple
 
+Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
+its gradient as the keyword ``dL_dout_alpha``.
+
 PyTorch is used only as the owner of device memory and of the current stream;
 every computation happens in the HIP library.  There is NO fallback: if the
 library is missing, or tensors are not on a ROCm device, a RuntimeError is
@@ -105,6 +108,11 @@ EXPORTS = {
     "dm2_layers_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                            _vp]),
+    "dm2_forward_alpha": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _vp]),
+    "dm2_backward_alpha": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp,
+                                          _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_prepare_faces": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp]),
     "dm2_prepare_faces_backward": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_exchange_mark": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp, _vp, _vp]),
@@ -354,6 +362,24 @@ class tables_from_image:
         _tls.tables_from_image = self.old
 
 
+class alpha_output:
+    """``with _C.alpha_output(True): _C.render_forward_cuda(...)`` -- the forward returns an 11-tuple: the reference's ten
+    outputs, then the alpha (coverage) image (B,H,W) float32 = 1 - T, the T the colour multiplied the background by (zeros
+    when nothing is rendered; dm2_forward_alpha).  Its gradient goes to ``render_backward_cuda(..., dL_dout_alpha=g)``.  Also
+    read by ``LayeredCompositeFunction``.  A side channel like ``forward_only``: the 21-argument signature stays the
+    reference's."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_tls, "alpha_output", False)
+        _tls.alpha_output = self.on
+
+    def __exit__(self, *exc):
+        _tls.alpha_output = self.old
+
+
 class forward_mode:
     """``with _C.forward_mode(mode): _C.render_backward_cuda(...)`` -- tells the backward what the forward of this frame left
     for it (FWD_NONE / FWD_MASKS / FWD_POOL, as ``_C.last_forward_mode()`` reported right after that forward), so that it
@@ -418,6 +444,7 @@ def render_forward_cuda(*args):
         d.flags |= DM2_FLAG_NO_BACKWARD
     if getattr(_tls, "aa_to_verts", False):
         d.flags |= DM2_FLAG_AA_GRAD_TO_VERTS          # the packed records note the CCW reorder for the backward
+    want_alpha = bool(getattr(_tls, "alpha_output", False))
     with torch.cuda.device(dev):
         st = _stream(dev)
         f32, i32 = torch.float32, torch.int32
@@ -433,7 +460,8 @@ def render_forward_cuda(*args):
             tri_cnt = torch.zeros((B, H, W), dtype=i32, device=dev)
             e = _bytes(dev, 0)
             _tls.last_pair_bound = 0
-            return 0, color, depth, oarea, tri_id, tri_cnt, doarea, e, _bytes(dev, 0), _bytes(dev, 0)
+            out = (0, color, depth, oarea, tri_id, tri_cnt, doarea, e, _bytes(dev, 0), _bytes(dev, 0))
+            return out + (torch.zeros((B, H, W), dtype=f32, device=dev),) if want_alpha else out
         tri_cnt = torch.empty((B, H, W), dtype=i32, device=dev)
         face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn + 1))
         img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_IMAGE, N, Tn))
@@ -472,18 +500,24 @@ def render_forward_cuda(*args):
                 if len(_bin_hint) > 64:
                     _bin_hint.clear()
                 _bin_hint[key] = need + need // 4
+        if want_alpha:
+            alpha = torch.empty((B, H, W), dtype=f32, device=dev)
+            if lib.dm2_forward_alpha(ctypes.byref(d), _ptr(img_buf), img_buf.numel(), _ptr(alpha), st):
+                raise _err(lib, "render_forward_cuda (alpha)")
     _tls.last_fwd_mode = int(mode.value)
     _tls.last_pair_bound = int(pairs.value)
     bin_buf._dm2_fwd_mode = int(mode.value)       # (survives only as long as this very tensor object is passed around)
-    return R, color, depth, oarea, tri_id, tri_cnt, doarea, face_buf, bin_buf, img_buf
+    out = (R, color, depth, oarea, tri_id, tri_cnt, doarea, face_buf, bin_buf, img_buf)
+    return out + (alpha,) if want_alpha else out
 
 
-def render_backward_cuda(*args):
+def render_backward_cuda(*args, dL_dout_alpha=None):
     """-> (dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts).
 
     The six gradients are views of ONE packed fp32 buffer (attribute
     ``_dm2_packed`` on the first tensor) so that a multi-GPU caller can sum
     them with a single RCCL all-reduce (dmesh2_renderer_amd.sharding).
+    dL_dout_alpha (B,H,W) or None: the gradient of the alpha image of ``alpha_output`` (dm2_backward_alpha).
     """
     if len(args) != 31:
         raise TypeError(f"render_backward_cuda() takes 31 positional arguments ({len(args)} given)")
@@ -511,6 +545,12 @@ def render_backward_cuda(*args):
         if tuple(dL_dcolor.shape) != (B, H, W, 3) or tuple(dL_ddepth.shape) != (B, H, W):
             raise RuntimeError("dL_dout_color / dL_dout_depth must have dimensions (B, H, W, 3) / (B, H, W)")
         dc = _c(dL_dcolor, f32); dd = _c(dL_ddepth, f32)
+        da = None
+        if dL_dout_alpha is not None:
+            if tuple(dL_dout_alpha.shape) != (B, H, W):
+                raise RuntimeError("dL_dout_alpha must have dimensions (B, H, W)")
+            _require_gpu(dL_dcolor, dL_dout_alpha)
+            da = _c(dL_dout_alpha, f32)
         mode = getattr(_tls, "fwd_mode", None)
         if mode is None:
             mode = getattr(bin_buf, "_dm2_fwd_mode", FWD_UNKNOWN)
@@ -522,11 +562,14 @@ def render_backward_cuda(*args):
                 pool_pairs = max(0, bin_buf.numel() - lib.dm2_scratch_bytes(SCRATCH_BINNING, num_rendered, _tiles(B, W, H))) // 4
                 if pool_pairs > 0:
                     tie_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_TIE_QUEUE, pool_pairs, 0))
-            if lib.dm2_backward(ctypes.byref(d), num_rendered, int(mode), _ptr(dc), _ptr(dd), _ptr(face_buf), face_buf.numel(),
-                                _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(),
-                                _ptr(tie_buf), tie_buf.numel() if tie_buf is not None else 0,
-                                _ptr(g_verts), _ptr(g_color), _ptr(g_opac),
-                                _ptr(g_ndc), _ptr(g_int), _ptr(g_aa), _stream(dev)):
+            tail = (_ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(),
+                    _ptr(tie_buf), tie_buf.numel() if tie_buf is not None else 0,
+                    _ptr(g_verts), _ptr(g_color), _ptr(g_opac), _ptr(g_ndc), _ptr(g_int), _ptr(g_aa), _stream(dev))
+            if da is None:
+                rc = lib.dm2_backward(ctypes.byref(d), num_rendered, int(mode), _ptr(dc), _ptr(dd), *tail)
+            else:
+                rc = lib.dm2_backward_alpha(ctypes.byref(d), num_rendered, int(mode), _ptr(dc), _ptr(dd), _ptr(da), *tail)
+            if rc:
                 raise _err(lib, "render_backward_cuda")
     g_verts._dm2_packed = packed
     return g_verts, g_color, g_opac, g_ndc, g_int, g_aa
@@ -669,21 +712,26 @@ def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacit
 
 
 def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
-                                   image_ray_o, image_ray_d, n_contrib, dL_dcolor, dL_ddepth):
+                                   image_ray_o, image_ray_d, n_contrib, dL_dcolor, dL_ddepth, dL_dout_alpha=None):
     """Gradients of composite_layers_cuda (dm2_layers_composite_backward): dL_dcolor (B,H,W,3), dL_ddepth (B,H,W) of depth_raw,
     n_contrib from the forward -> (dL_dverts_color (P,3), dL_dfaces_opacity (F), dL_dverts_ndc (B,P,3) [z only],
-    dL_dfaces_intense (B,F)).  Nothing reaches verts (through the barycentrics) or background."""
+    dL_dfaces_intense (B,F)).  Nothing reaches verts (through the barycentrics) or background.  dL_dout_alpha (B,H,W) or
+    None: the gradient of alpha = 1 - final_T (dm2_layers_composite_backward_alpha; it reaches dL_dfaces_opacity only)."""
     lib = load_library()
     keep: list = []
     d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                              image_ray_o, image_ray_d, keep)
     B, P, F, H, W = d.B, d.P, d.F, d.H, d.W
     f32 = torch.float32
-    for t, shape, nm in ((n_contrib, (B, H, W), "n_contrib"), (dL_dcolor, (B, H, W, 3), "dL_dcolor"), (dL_ddepth, (B, H, W), "dL_ddepth")):
+    checks = [(n_contrib, (B, H, W), "n_contrib"), (dL_dcolor, (B, H, W, 3), "dL_dcolor"), (dL_ddepth, (B, H, W), "dL_ddepth")]
+    if dL_dout_alpha is not None:
+        checks.append((dL_dout_alpha, (B, H, W), "dL_dout_alpha"))
+    for t, shape, nm in checks:
         if tuple(t.shape) != shape:
             raise RuntimeError(f"{nm} must have dimensions {shape}, got {tuple(t.shape)}")
         _require_gpu(render_layers, t)
     nc, gc, gd = _c(n_contrib, torch.int32), _c(dL_dcolor, f32), _c(dL_ddepth, f32)
+    ga = _c(dL_dout_alpha, f32) if dL_dout_alpha is not None else None
     dcolor = torch.zeros((P, 3), dtype=f32, device=dev)
     dopacity = torch.zeros((F,), dtype=f32, device=dev)
     dndc = torch.zeros((B, P, 3), dtype=f32, device=dev)
@@ -691,8 +739,13 @@ def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, fac
     if B * H * W == 0:
         return dcolor, dopacity, dndc, dintense
     with torch.cuda.device(dev):
-        if lib.dm2_layers_composite_backward(ctypes.byref(d), _ptr(gc), _ptr(gd), _ptr(nc), _ptr(dcolor), _ptr(dopacity),
-                                             _ptr(dndc), _ptr(dintense), _stream(dev)):
+        if ga is None:
+            rc = lib.dm2_layers_composite_backward(ctypes.byref(d), _ptr(gc), _ptr(gd), _ptr(nc), _ptr(dcolor), _ptr(dopacity),
+                                                   _ptr(dndc), _ptr(dintense), _stream(dev))
+        else:
+            rc = lib.dm2_layers_composite_backward_alpha(ctypes.byref(d), _ptr(gc), _ptr(gd), _ptr(ga), _ptr(nc), _ptr(dcolor),
+                                                         _ptr(dopacity), _ptr(dndc), _ptr(dintense), _stream(dev))
+        if rc:
             raise _err(lib, "composite_layers_backward_cuda")
     return dcolor, dopacity, dndc, dintense
 

@@ -45,6 +45,10 @@ class RenderFunction(torch.autograd.Function):
     aa_face_edges_iszero (bool), aa_face_edges_recip, aa_face_edges_normal
     (all (B,F,3,2)), aa_face_edges_normal_c(B,F,3), len_oarea_buffer,
     image_ray_o(B,H,W,3), image_ray_d(B,H,W,3).  (* = receives a gradient.)
+
+    Outputs: (color, depth); under ``_C.alpha_output(True)`` (color, depth, alpha) with alpha (B,H,W) = 1 - T, the share
+    of each pixel the blended faces cover.  Then an output left out of the loss costs nothing in the backward: an unused
+    alpha launches the kernels of the two-output op.
     """
 
     N_INPUTS = 21
@@ -63,6 +67,9 @@ class RenderFunction(torch.autograd.Function):
         # (input 9, verts_image) instead of as dL/d(aa_face_verts) (input 12) -- see _C.aa_grad_to_verts
         ctx.aa_to_verts = bool(getattr(_C._tls, "aa_to_verts", False))
         ctx.tables_from_image = bool(getattr(_C._tls, "tables_from_image", False))
+        ctx.alpha = bool(getattr(_C._tls, "alpha_output", False))
+        if ctx.alpha:
+            ctx.set_materialize_grads(False)        # an unused alpha arrives as None, and the backward is the two-output one
         try:
             with _C.forward_only(not any(ctx.needs_input_grad)):
                 out = _C.render_forward_cuda(*inputs)
@@ -72,17 +79,19 @@ class RenderFunction(torch.autograd.Function):
             raise
         ctx.fwd_mode = _C.last_forward_mode()       # what this forward left for its backward (masks, pair pool): picks the backward's kernel
         num_rendered, color, depth = out[0], out[1], out[2]
-        opaque = out[3:]            # 4 AA-record tensors + face/binning/image byte buffers
+        opaque = out[3:10]          # 4 AA-record tensors + face/binning/image byte buffers
         tensors_in = [x for x in inputs if torch.is_tensor(x)]
         ctx.save_for_backward(*tensors_in, *opaque)
         ctx.n_tensor_in = len(tensors_in)
         ctx.tensor_slots = [i for i, x in enumerate(inputs) if torch.is_tensor(x)]
         ctx.scalars = {i: x for i, x in enumerate(inputs) if not torch.is_tensor(x)}
         ctx.num_rendered = num_rendered
+        if ctx.alpha:
+            return color, depth, out[10]
         return color, depth
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_out_depth):
+    def backward(ctx, grad_out_color, grad_out_depth, grad_out_alpha=None):
         saved = ctx.saved_tensors
         inputs: list = [None] * RenderFunction.N_INPUTS
         for slot, t in zip(ctx.tensor_slots, saved[:ctx.n_tensor_in]):
@@ -90,13 +99,22 @@ class RenderFunction(torch.autograd.Function):
         for slot, v in ctx.scalars.items():
             inputs[slot] = v
         oarea, tri_id, tri_cnt, doarea, face_buf, binning_buf, image_buf = saved[ctx.n_tensor_in:]
+        if ctx.alpha:                               # (grads not materialised: zeros for an unused colour / depth)
+            ref = grad_out_alpha if grad_out_alpha is not None else grad_out_color if grad_out_color is not None else grad_out_depth
+            B, H, W = int(inputs[8].shape[0]), int(inputs[3]), int(inputs[2])
+            if grad_out_color is None:
+                grad_out_color = torch.zeros((B, H, W, 3), dtype=torch.float32, device=ref.device)
+            if grad_out_depth is None:
+                grad_out_depth = torch.zeros((B, H, W), dtype=torch.float32, device=ref.device)
         try:
             ana = ctx.analytic
             with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.aa_grad_to_verts(ctx.aa_to_verts), \
                     _C.forward_mode(ctx.fwd_mode), _C.tables_from_image(ctx.tables_from_image):
+                # (the keyword only when alpha is in the loss: otherwise the very call of the two-output op)
+                extra = {} if grad_out_alpha is None else {"dL_dout_alpha": grad_out_alpha}
                 grads = _C.render_backward_cuda(
                     ctx.num_rendered, *inputs, grad_out_color, grad_out_depth,
-                    face_buf, binning_buf, image_buf, oarea, tri_id, tri_cnt, doarea)
+                    face_buf, binning_buf, image_buf, oarea, tri_id, tri_cnt, doarea, **extra)
         except Exception as ex:
             print("\nAn error occured in renderer backward.")
             print(ex)
@@ -219,8 +237,18 @@ class Renderer(torch.nn.Module):
     def forward(self, batch_mvp_idx: List[int], batch_patch_min: torch.Tensor, patch_width: int,
                 patch_height: int, verts: torch.Tensor, faces: torch.Tensor, verts_color: torch.Tensor,
                 faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor,
-                aa_temperature: float = 1.0):
-        """Render ``len(batch_mvp_idx)`` patches; returns color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background)."""
+                aa_temperature: float = 1.0, return_alpha: bool = False):
+        """Render ``len(batch_mvp_idx)`` patches; returns color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background).
+
+        Not in the reference's signature: ``return_alpha=True`` returns (color, depth, alpha), alpha (B,H,W) = 1 - T, the
+        T the colour multiplied the background by -- differentiable w.r.t. faces_opacity and, through the AA coverage,
+        verts."""
+        with _C.alpha_output(return_alpha):
+            return self._forward(batch_mvp_idx, batch_patch_min, patch_width, patch_height, verts, faces, verts_color,
+                                 faces_opacity, faces_intense, background, aa_temperature)
+
+    def _forward(self, batch_mvp_idx, batch_patch_min, patch_width, patch_height, verts, faces, verts_color, faces_opacity,
+                 faces_intense, background, aa_temperature):
         B = len(batch_mvp_idx)
         F = faces.shape[0]
         mv = self.mv[batch_mvp_idx]
@@ -249,30 +277,30 @@ class Renderer(torch.nn.Module):
                 verts_ndc, verts_image = prep.project(verts.to(f32), faces.to(torch.int32), mv.to(f32), proj.to(f32), self.width, self.height)
                 ph4 = torch.empty((B, 0, 3, 2), dtype=f32, device=verts.device)
                 with _C.tables_from_image(True), _C.aa_grad_to_verts(True):
-                    color, depth = RenderFunction.apply(
+                    out = RenderFunction.apply(
                         background.to(f32), batch_patch_min.to(torch.int32), patch_width, patch_height,
                         verts.to(f32), faces.to(torch.int32), verts_color.to(f32), faces_opacity.to(f32),
                         verts_ndc, verts_image, faces_intense.to(f32), aa_temperature,
                         ph4, ph4, ph4.to(torch.bool), ph4, ph4, torch.empty((B, 0, 3), dtype=f32, device=verts.device),
                         self.aa_grad_buffer_size, ray_o.to(f32), ray_d.to(f32))
-                return color, 1.0 - (depth + 1.0) / 2.0
+                return _finish(out)
             (verts_ndc, verts_image, aa_v, aa_e, aa_z, aa_r, aa_n, aa_c) = prep.prepare(
                 verts.to(f32), faces.to(torch.int32), mv.to(f32), proj.to(f32), self.width, self.height)
             # the fused prep owns both ends of aa_face_verts: the op hands its corner gradients back per VERTEX (as the
             # gradient of verts_image) and prepare_faces_backward needs no (B,F,3,2) scatter pass (DM2_FUSED_AA_GRAD=0: the
             # reference's route through dL/d(aa_face_verts))
             with _C.aa_grad_to_verts(_FUSED_AA_GRAD and verts_image.requires_grad):
-                color, depth = RenderFunction.apply(
+                out = RenderFunction.apply(
                     background.to(f32), batch_patch_min.to(torch.int32), patch_width, patch_height,
                     verts.to(f32), faces.to(torch.int32), verts_color.to(f32), faces_opacity.to(f32),
                     verts_ndc, verts_image, faces_intense.to(f32), aa_temperature,
                     aa_v, aa_e, aa_z, aa_r, aa_n, aa_c, self.aa_grad_buffer_size, ray_o.to(f32), ray_d.to(f32))
-            return color, 1.0 - (depth + 1.0) / 2.0
+            return _finish(out)
         verts_ndc, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
 
         corners = verts_image[:, faces.flatten()].view(-1, 3, 2)             # (B*F,3,2)
         tri = Triangles(corners[:, 0], corners[:, 1], corners[:, 2])
-        color, depth = RenderFunction.apply(
+        out = RenderFunction.apply(
             background.to(f32),
             batch_patch_min.to(torch.int32), patch_width, patch_height,
             verts.to(f32), faces.to(torch.int32), verts_color.to(f32), faces_opacity.to(f32),
@@ -287,9 +315,13 @@ class Renderer(torch.nn.Module):
             self.aa_grad_buffer_size,
             ray_o.to(f32), ray_d.to(f32),
         )
-        # NDC z in [-1,1] (background +1) -> [0,1] with background 0 (reference :377-378)
-        depth = 1.0 - (depth + 1.0) / 2.0
-        return color, depth
+        return _finish(out)
+
+
+def _finish(out):
+    """RenderFunction's (color, depth[, alpha]) -> Renderer's: NDC z in [-1,1] (background +1) -> [0,1] with background 0
+    (reference :377-378)."""
+    return (out[0], 1.0 - (out[1] + 1.0) / 2.0) + tuple(out[2:])
 
 
 class LayeredCompositeFunction(torch.autograd.Function):
@@ -304,28 +336,42 @@ class LayeredCompositeFunction(torch.autograd.Function):
     aa_temperature 0), with the same colour, depth and alpha as Renderer.  No gradient reaches ``verts`` through the
     barycentrics: layers from the tet walk are piecewise constant in the points, and DMesh++ holds the points fixed on
     this path.  ``background`` gets no gradient, as in Renderer.
+
+    Under ``_C.alpha_output(True)`` a third output: alpha (B,H,W) = 1 - final_T, with a gradient w.r.t. faces_opacity; an
+    alpha left out of the loss launches the kernel of the two-output function.
     """
 
     @staticmethod
     def forward(ctx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                 image_ray_o, image_ray_d):
         ctx.analytic = getattr(_C._tls, "analytic", None)
-        color, depth, _final_T, n_contrib = _C.composite_layers_cuda(
+        ctx.alpha = bool(getattr(_C._tls, "alpha_output", False))
+        if ctx.alpha:
+            ctx.set_materialize_grads(False)
+        color, depth, final_T, n_contrib = _C.composite_layers_cuda(
             render_layers, verts.detach(), faces, verts_color.detach(), faces_opacity.detach(), faces_intense.detach(),
             verts_ndc.detach(), background, image_ray_o, image_ray_d)
         ctx.save_for_backward(render_layers, verts.detach(), faces, verts_color.detach(), faces_opacity.detach(),
                               faces_intense.detach(), verts_ndc.detach(), background, image_ray_o, image_ray_d, n_contrib)
+        if ctx.alpha:
+            return color, depth, 1.0 - final_T         # (bit-equal to the kernel's 1.f - T)
         return color, depth
 
     @staticmethod
-    def backward(ctx, grad_color, grad_depth):
+    def backward(ctx, grad_color, grad_depth, grad_alpha=None):
         (render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
          n_contrib) = ctx.saved_tensors
+        if ctx.alpha:                                  # (grads not materialised: zeros for an unused colour / depth)
+            if grad_color is None:
+                grad_color = torch.zeros(tuple(n_contrib.shape) + (3,), dtype=torch.float32, device=n_contrib.device)
+            if grad_depth is None:
+                grad_depth = torch.zeros(tuple(n_contrib.shape), dtype=torch.float32, device=n_contrib.device)
         ana = ctx.analytic
         with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))):
+            extra = {} if grad_alpha is None else {"dL_dout_alpha": grad_alpha}
             dcolor, dopacity, dndc, dintense = _C.composite_layers_backward_cuda(
                 render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
-                n_contrib, grad_color, grad_depth)
+                n_contrib, grad_color, grad_depth, **extra)
         return None, None, None, dcolor, dopacity, dintense, dndc, None, None, None
 
 
@@ -370,8 +416,10 @@ class LayeredRenderer(Renderer):
             ray_o.to(f32), ray_d.to(f32), num_layers)
 
     def render(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
-               verts_color: torch.Tensor, faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor):
-        """Composite per-pixel face layers front to back -> color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background).
+               verts_color: torch.Tensor, faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor,
+               return_alpha: bool = False):
+        """Composite per-pixel face layers front to back -> color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background); with
+        ``return_alpha=True`` also alpha (B,H,W) = 1 - T, differentiable w.r.t. faces_opacity.
 
         render_layers (B,H,W,L) int32 over the full frame, e.g. from ``generate`` (-1 and any id outside [0, F) is skipped,
         holes included); faces_intense (B,F) of the selected views.  A layer blends where the pixel's ray hits its face
@@ -392,10 +440,11 @@ class LayeredRenderer(Renderer):
         if getattr(self, "analytic_rays", False):
             cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
             ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
-            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
-                color, depth = LayeredCompositeFunction.apply(*args, ph, ph)
+            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height), _C.alpha_output(return_alpha):
+                out = LayeredCompositeFunction.apply(*args, ph, ph)
         else:
             ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
-            color, depth = LayeredCompositeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32))
+            with _C.alpha_output(return_alpha):
+                out = LayeredCompositeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32))
         # NDC z in [-1,1] (background +1) -> [0,1] with background 0, as Renderer.forward
-        return color, 1.0 - (depth + 1.0) / 2.0
+        return _finish(out)

@@ -287,11 +287,33 @@ int dm2_forward(const dm2_render_desc* d, void* face_scratch, size_t face_bytes,
                        image_scratch, image_bytes, out_color, out_depth, out_tri_cnt, stream, planned && ranges != nullptr, forward_mode);
 }
 
+int dm2_forward_alpha(const dm2_render_desc* d, const void* image_scratch, size_t image_bytes, float* out_alpha, void* stream) {
+    if (check_render_desc(d)) return 1;
+    const int64_t N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
+    if (N == 0) return 0;
+    if (!image_scratch || !out_alpha) return fail("image_scratch / out_alpha must not be null");
+    if (dm2_scratch_bytes(DM2_SCRATCH_IMAGE, N, Tn) > image_bytes) return fail("image scratch too small");
+    dm2::launch_forward_alpha(dm2::ImageState::carve(const_cast<void*>(image_scratch), N, Tn), N, out_alpha, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode, const float* dL_dout_color, const float* dL_dout_depth,
                  const void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
                  const void* image_scratch, size_t image_bytes, void* tie_scratch, size_t tie_bytes,
                  float* dL_dverts, float* dL_dverts_color, float* dL_dfaces_opacity, float* dL_dverts_ndc,
                  float* dL_dfaces_intense, float* dL_daa_face_verts, void* stream) {
+    return dm2_backward_alpha(d, num_rendered, forward_mode, dL_dout_color, dL_dout_depth, nullptr, face_scratch, face_bytes,
+                              binning_scratch, binning_bytes, image_scratch, image_bytes, tie_scratch, tie_bytes, dL_dverts,
+                              dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, stream);
+}
+
+int dm2_backward_alpha(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode, const float* dL_dout_color,
+                       const float* dL_dout_depth, const float* dL_dout_alpha,
+                       const void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                       const void* image_scratch, size_t image_bytes, void* tie_scratch, size_t tie_bytes,
+                       float* dL_dverts, float* dL_dverts_color, float* dL_dfaces_opacity, float* dL_dverts_ndc,
+                       float* dL_dfaces_intense, float* dL_daa_face_verts, void* stream) {
     if (check_render_desc(d)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int64_t N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
@@ -319,7 +341,8 @@ int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward
         if (tie_cap < bs.pool_cap) return fail("tie scratch too small for the pool part of the binning scratch");
     }
     dm2::launch_render_backward(*d, is.ranges, bs.face_list, is, dL_dout_color, dL_dout_depth, dL_dverts, dL_dverts_color,
-                                dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, forward_mode, tie_queue, tie_cap, st);
+                                dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, forward_mode, tie_queue, tie_cap,
+                                dL_dout_alpha, st);
     DM2_HIP(hipGetLastError());
     return 0;
 }
@@ -414,12 +437,19 @@ int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, fl
 int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
                                   const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
                                   float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream) {
+    return dm2_layers_composite_backward_alpha(d, dL_dout_color, dL_dout_depth, nullptr, n_contrib, dL_dverts_color,
+                                               dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, stream);
+}
+
+int dm2_layers_composite_backward_alpha(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
+                                        const float* dL_dout_alpha, const int32_t* n_contrib, float* dL_dverts_color,
+                                        float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream) {
     if (check_composite_desc(d)) return 1;
     if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0) return 0;       // nothing blends: all gradients stay zero
     if (!dL_dout_color || !dL_dout_depth || !n_contrib) return fail("dL_dout_color / dL_dout_depth / n_contrib must not be null");
     if (!dL_dverts_color || !dL_dfaces_opacity || !dL_dverts_ndc || !dL_dfaces_intense) return fail("gradient outputs must not be null");
     dm2::launch_layer_composite_backward(*d, dL_dout_color, dL_dout_depth, n_contrib, dL_dverts_color, dL_dfaces_opacity,
-                                         dL_dverts_ndc, dL_dfaces_intense, (hipStream_t)stream);
+                                         dL_dverts_ndc, dL_dfaces_intense, dL_dout_alpha, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,8 @@
 //     pixels of a tile walk the same entry in lock-step, so the 29 partials are
 //     first summed per (tile,entry) in LDS (ds_add_f32) and flushed once per
 //     chunk with (entry,component)-shaped global atomics.
+// ALPHA (the template parameter): dL_dalpha_img is the gradient of the alpha image 1 - T_final, which adds
+// g_A T_final / (1 - alpha) (a last contributor of alpha 1: g_A prev_T_final) to a pair's dL/dalpha.
 #include <hip/hip_runtime.h>
 
 #include "dm2_bwd_shared.h"
@@ -30,13 +32,14 @@ constexpr int ACC_STRIDE = 32;     // floats per entry accumulator (the M_* row 
 
 __device__ __forceinline__ void lds_add(float* p, float v) { atomicAdd(p, v); }   // ds_add_f32, no return
 
+template <bool ALPHA>
 __global__ void __launch_bounds__(TILE_PIX)
 k_render_backward(dm2_render_desc d, const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                   ImageState is, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                   float* __restrict__ dL_dverts, float* __restrict__ dL_dverts_color,
                   float* __restrict__ dL_dfaces_opacity, float* __restrict__ dL_dverts_ndc,
                   float* __restrict__ dL_dfaces_intense, float* __restrict__ dL_daa_face_verts,
-                  const uint32_t* __restrict__ skip_if_masks) {
+                  const uint32_t* __restrict__ skip_if_masks, const float* __restrict__ dL_dalpha_img) {
     // the last kernel of the device-side cascade (launch_render_backward): a mask-driven kernel did the work when the
     // forward left masks of any kind
     if (skip_if_masks && skip_if_masks[0] != 0u) return;
@@ -57,13 +60,14 @@ k_render_backward(dm2_render_desc d, const uint2* __restrict__ ranges, const uin
     f3 ro = {0, 0, 0}, rd = {0, 0, 0};
     float T_final = 0.f, prev_T_final = 0.f;
     uint32_t last_contributor = 0;
-    float dLc0 = 0.f, dLc1 = 0.f, dLc2 = 0.f, dLd = 0.f;
+    float dLc0 = 0.f, dLc1 = 0.f, dLc2 = 0.f, dLd = 0.f, dLa = 0.f;
     if (inside) {
         pixel_ray(d, b, pix, px + pmx, py + pmy, d.full_W, d.full_H, ro, rd);
         T_final = is.final_T[pix]; prev_T_final = is.final_prev_T[pix];
         last_contributor = is.n_contrib[pix];
         dLc0 = dL_dcolor[3 * pix]; dLc1 = dL_dcolor[3 * pix + 1]; dLc2 = dL_dcolor[3 * pix + 2];
         dLd = dL_ddepth[pix];
+        if constexpr (ALPHA) dLa = dL_dalpha_img[pix];
     }
     const uint32_t tile = ((uint32_t)b * gy + blockIdx.y) * gx + blockIdx.x;
     const uint2 range = ranges[tile];
@@ -149,6 +153,7 @@ k_render_backward(dm2_render_desc d, const uint2* __restrict__ ranges, const uin
                     dL_dalpha += (-T_final / (1.f - alpha)) * bg_dot;
                     dL_dalpha += (-T_final / (1.f - alpha)) * bd_dot;
                 }
+                if constexpr (ALPHA) dL_dalpha += (alpha == 1.0f ? prev_T_final : T_final / (1.f - alpha)) * dLa;
                 const float dL_dfop = dL_dalpha * ratio;
                 const float dL_dratio = (dL_dalpha * opacity) * temp;
                 const float dL_doarea = dL_dratio / pix_area;
@@ -244,18 +249,18 @@ void launch_render_backward(const dm2_render_desc& d, const uint2* ranges, const
                             const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
                             float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
                             float* dL_daa_face_verts, const BinningState& bs, int fwd_mode, TieEntry* tie_queue, int64_t tie_cap,
-                            hipStream_t st) {
+                            const float* dL_dalpha, hipStream_t st) {
     const bool aa = d.aa_temperature > 0.0f;
     auto fast = [&](bool clip, bool check) {   // (times its kernels itself, unless checked: then the cascade is timed as one stage)
         launch_render_backward_fast(d, ranges, face_list, is, dL_dcolor, dL_ddepth, dL_dverts, dL_dverts_color, dL_dfaces_opacity,
                                     dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, bs, clip, aa ? tie_queue : nullptr,
-                                    aa ? tie_cap : 0, check, st);
+                                    aa ? tie_cap : 0, check, dL_dalpha, st);
     };
     auto per_pixel = [&](const uint32_t* skip_if_masks) {
         const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
-        hipLaunchKernelGGL(k_render_backward, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
+        hipLaunchKernelGGL(dL_dalpha ? k_render_backward<true> : k_render_backward<false>, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
                            dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts,
-                           skip_if_masks);
+                           skip_if_masks, dL_dalpha);
     };
     const bool legacy = (d.flags & DM2_FLAG_LEGACY_KERNELS) != 0;
     if (!legacy && fwd_mode == (aa ? DM2_FWD_POOL : DM2_FWD_POINT)) { fast(false, false); return; }

@@ -26,6 +26,13 @@
 //       ds_add_f32
 //   flush with (entry,component) global atomics.
 //
+// ALPHA (the second template parameter; dm2_backward_alpha with a non-null dL/d(alpha image)): the alpha image 1 - T_final
+// adds g_A T_final / (1 - alpha) to a pair's dL/dalpha, g_A prev_T_final for a last contributor of alpha 1 -- the background
+// term with -g_A in the place of bg.dL/dcolour + dL/ddepth.  Folded into that term: the prologue parks T_final K and
+// prev_T_final K in the two s_pixc rows that held T_final and prev_T_final, K = bg.g_c + g_d - g_A; no LDS and no register
+// more (K == 0 zeroes the term in both branches, so the T_final == 0 test reads the product).  ALPHA = false is the kernel
+// without the alpha output, instruction for instruction.
+//
 // Memory pipeline.  A chunk's inputs -- face ids, blend masks, pool offsets, packed face records (dm2_stage.h: 256 B per
 // (view,face), two full lines) -- are requested ONE CHUNK AHEAD, right after the current chunk's cut is known, with
 // LDS-direct loads (global_load_lds_dwordx4: no staging registers) into the OTHER half of double-buffered LDS arrays: the
@@ -70,7 +77,7 @@ template <> struct BfTraits<CLIP> {
     static constexpr int CAND = 32, BLOCKS = 3;
 };
 
-template <Coverage COV>
+template <Coverage COV, bool ALPHA>
 __global__ void __launch_bounds__(TILE_PIX, BfTraits<COV>::BLOCKS)
 k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                        ImageState is, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
@@ -79,7 +86,8 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                        float* __restrict__ dL_dfaces_intense, float* __restrict__ dL_daa_face_verts,
                        const uint64_t* __restrict__ hit_masks, uint32_t* __restrict__ hit_valid,
                        const uint32_t* __restrict__ hit_base, const float* __restrict__ pool,
-                       TieEntry* __restrict__ tie_queue, uint32_t tie_cap, bool check_mode STAMP_PARAM) {
+                       TieEntry* __restrict__ tie_queue, uint32_t tie_cap, bool check_mode,
+                       const float* __restrict__ dL_dalpha STAMP_PARAM) {
     // (the caller did not know what the forward left: hit_valid[0] 1 point-sampled masks, 2 masks only, 3 masks + pool; anything
     // else -> another kernel runs)
     if (check_mode && hit_valid[0] != (COV == POINT ? 1u : COV == CLIP ? 2u : 3u)) return;
@@ -147,7 +155,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     float T = 0.f;                                                 // starts as the T in front of the pixel's last contributor
     {
     float T_final = 0.f, prev_T_final = 0.f;
-    float dLc0 = 0.f, dLc1 = 0.f, dLc2 = 0.f, dLd = 0.f;
+    float dLc0 = 0.f, dLc1 = 0.f, dLc2 = 0.f, dLd = 0.f, dLa = 0.f;
     if (inside) {
         f3 ro, rd;
         pixel_ray(d, b, pix, px + pmx, py + pmy, d.full_W, d.full_H, ro, rd);
@@ -157,10 +165,18 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         last_contributor = is.n_contrib[pix];
         dLc0 = dL_dcolor[3 * pix]; dLc1 = dL_dcolor[3 * pix + 1]; dLc2 = dL_dcolor[3 * pix + 2];
         dLd = dL_ddepth[pix];
+        if constexpr (ALPHA) dLa = dL_dalpha[pix];
     }
     // phase C is their only reader: parked in LDS, not in six registers that would be live across B2 and D
     s_pixc[0][tid] = dLc0; s_pixc[1][tid] = dLc1; s_pixc[2][tid] = dLc2; s_pixc[3][tid] = dLd;
-    s_pixc[4][tid] = T_final; s_pixc[5][tid] = prev_T_final;
+    if constexpr (ALPHA) {                                         // (file header: T_final K, prev_T_final K)
+        float bg_dot = 0.f;
+        bg_dot += d.background[0] * dLc0; bg_dot += d.background[1] * dLc1; bg_dot += d.background[2] * dLc2;
+        const float K = (bg_dot + (float)(0.0 + 1.0 * (double)dLd)) - dLa;
+        s_pixc[4][tid] = T_final * K; s_pixc[5][tid] = prev_T_final * K;
+    } else {
+        s_pixc[4][tid] = T_final; s_pixc[5][tid] = prev_T_final;
+    }
     T = prev_T_final;
     }
     if (tid < M_N) fill_flush_table(tid, b, d.P, d.F, dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense,
@@ -356,15 +372,20 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 dL_dalpha += (iD - accum_recd) * dLd;
                 dL_dalpha *= T;
                 last_alpha = a;
-                float bg_dot = 0.f;
-                bg_dot += bg0 * dLc0; bg_dot += bg1 * dLc1; bg_dot += bg2 * dLc2;
-                const float bd_dot = (float)(0.0 + 1.0 * (double)dLd);            // backward.cu:394
-                if (alpha_is_one) {
-                    dL_dalpha += (-prev_T_final) * bg_dot;
-                    dL_dalpha += (-prev_T_final) * bd_dot;
+                if constexpr (ALPHA) {                                            // T_final, prev_T_final: times K
+                    if (alpha_is_one) dL_dalpha += -prev_T_final;
+                    else dL_dalpha += (-T_final) * inv_1ma;
                 } else {
-                    dL_dalpha += (-T_final * inv_1ma) * bg_dot;
-                    dL_dalpha += (-T_final * inv_1ma) * bd_dot;
+                    float bg_dot = 0.f;
+                    bg_dot += bg0 * dLc0; bg_dot += bg1 * dLc1; bg_dot += bg2 * dLc2;
+                    const float bd_dot = (float)(0.0 + 1.0 * (double)dLd);        // backward.cu:394
+                    if (alpha_is_one) {
+                        dL_dalpha += (-prev_T_final) * bg_dot;
+                        dL_dalpha += (-prev_T_final) * bd_dot;
+                    } else {
+                        dL_dalpha += (-T_final * inv_1ma) * bg_dot;
+                        dL_dalpha += (-T_final * inv_1ma) * bd_dot;
+                    }
                 }
                 pr.depth = T; pr.alpha = dL_dalpha; pr.flags = MB_BLEND | MB_ACTIVE;   // (phase D: T, dL/dalpha in place of depth, alpha)
             }
@@ -620,18 +641,21 @@ void launch_render_backward_fast(const dm2_render_desc& d, const uint2* ranges, 
                                  const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
                                  float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
                                  float* dL_daa_face_verts, const BinningState& bs, bool clip, TieEntry* tie_queue, int64_t tie_cap,
-                                 bool check_mode, hipStream_t st) {
+                                 bool check_mode, const float* dL_dalpha, hipStream_t st) {
     const uint32_t Tn = (uint32_t)(((d.W + TILE - 1) / TILE) * ((d.H + TILE - 1) / TILE) * d.B);
     const uint32_t cap = (uint32_t)(tie_cap > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : tie_cap);
     auto launch = [&](auto kernel, uint32_t kcap) {
         StageTimer tm(check_mode ? -1 : ST_BWD, st);       // (under DM2_FWD_UNKNOWN the caller times the whole cascade)
         hipLaunchKernelGGL(kernel, dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
                            dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts,
-                           bs.hit_masks, bs.hit_valid, bs.hit_base, bs.pool, tie_queue, kcap, check_mode STAMP_ARG(1));
+                           bs.hit_masks, bs.hit_valid, bs.hit_base, bs.pool, tie_queue, kcap, check_mode, dL_dalpha STAMP_ARG(1));
     };
-    if (!(d.aa_temperature > 0.0f)) { launch(k_render_backward_fast<POINT>, 0u); return; }   // point-sampled coverage: the masks of dm2_forward_point.hip, nothing else
-    if (clip) { launch(k_render_backward_fast<CLIP>, 0u); return; }
-    launch(k_render_backward_fast<POOL>, cap);
+    const bool A = dL_dalpha != nullptr;                   // the alpha image's gradient: the ALPHA instantiations
+    if (!(d.aa_temperature > 0.0f)) {                      // point-sampled coverage: the masks of dm2_forward_point.hip, nothing else
+        launch(A ? k_render_backward_fast<POINT, true> : k_render_backward_fast<POINT, false>, 0u); return;
+    }
+    if (clip) { launch(A ? k_render_backward_fast<CLIP, true> : k_render_backward_fast<CLIP, false>, 0u); return; }
+    launch(A ? k_render_backward_fast<POOL, true> : k_render_backward_fast<POOL, false>, cap);
     const unsigned blocks = (unsigned)((cap + 255u) / 256u < 1024u ? (cap + 255u) / 256u : 1024u);
     StageTimer tm(check_mode ? -1 : ST_TIES, st);
     if (blocks) hipLaunchKernelGGL(k_aa_ties, dim3(blocks), dim3(256), 0, st, d, is.face_recs, tie_queue, cap, bs.hit_valid, dL_daa_face_verts, check_mode);

@@ -137,4 +137,18 @@ int launch_render_forward(const dm2_render_desc& d, const uint2* ranges, const u
     return DM2_FWD_NONE;
 }
 
+// The alpha image (dm2_forward_alpha): 1 - T of every pixel, the T the forward multiplied the background by.  Elementwise
+// over the N pixels of the image scratch; every forward kernel above (and dm2_forward_queue.hip, dm2_forward_point.hip)
+// writes final_T for each pixel of the image, whatever its mode.
+__global__ void __launch_bounds__(256)
+k_forward_alpha(const float* __restrict__ final_T, int64_t N, float* __restrict__ out_alpha) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < N) out_alpha[i] = 1.f - final_T[i];
+}
+
+void launch_forward_alpha(ImageState is, int64_t N, float* out_alpha, hipStream_t st) {
+    if (N <= 0) return;
+    hipLaunchKernelGGL(k_forward_alpha, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, is.final_T, N, out_alpha);
+}
+
 }  // namespace dm2

@@ -18,6 +18,9 @@
 // with T_l from a front-to-back pass.  The layers [0, n_contrib) are processed in chunks of LC_REG from the back: per chunk
 // a front pass (T at the chunk's start from the layers in front of it, then the chunk's hits kept in registers) and a back
 // pass that carries R.  L <= LC_REG is one chunk; a larger L re-intersects the layers in front of each chunk (correct, not fast).
+// ALPHA (the template parameter; dm2_layers_composite_backward_alpha): the alpha image 1 - T_final is a fourth channel of
+// colour 1 over background 0, RA_l = alpha_l + (1 - alpha_l) RA_{l+1} (RA = 0 behind the last layer), and adds
+// T_l g_A (1 - RA_{l+1}) to dL/dalpha_l -- still no division.
 //
 // Gradient scatter: a (pixel, layer) hit adds its 14 components (9 colour, 3 z, opacity, intensity) into a per-block LDS
 // table keyed by face id (open addressing); the table is flushed with one global atomic per (face or vertex row, component)
@@ -147,9 +150,10 @@ __device__ __forceinline__ void lc_global_add(const dm2_layer_composite_desc& d,
     if (g[LC_IN] != 0.0f) atomicAdd(o.dintense + (int64_t)b * d.F + f, g[LC_IN]);
 }
 
+template <bool ALPHA>
 __global__ void __launch_bounds__(TILE_PIX)
 k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
-                      const int32_t* __restrict__ n_contrib, LcGrads o) {
+                      const int32_t* __restrict__ n_contrib, LcGrads o, const float* __restrict__ dL_dalpha) {
     __shared__ int s_key[LC_SLOTS];
     __shared__ float s_acc[LC_NCOMP * LC_SLOTS];                       // component-major: [comp][slot]
     const int b = blockIdx.z;
@@ -168,6 +172,8 @@ k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_d
         const int32_t* ids = d.render_layers + pix * d.L;
         const float g0 = dL_dcolor[3 * pix], g1 = dL_dcolor[3 * pix + 1], g2 = dL_dcolor[3 * pix + 2], gd = dL_ddepth[pix];
         float R0 = d.background[0], R1 = d.background[1], R2 = d.background[2], RD = 1.0f;
+        float gA = 0.f, RA = 0.f;                                       // (ALPHA only)
+        if constexpr (ALPHA) gA = dL_dalpha[pix];
         for (int e = n; e > 0;) {
             const int s = e > LC_REG ? e - LC_REG : 0;
             float T = 1.0f;
@@ -202,6 +208,10 @@ k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_d
                     g[LC_DZ + i] = gz * w[i];
                 }
                 g[LC_OP] = Ts[j] * ((g0 * (c0 - R0) + g1 * (c1 - R1) + g2 * (c2 - R2)) + gd * (h.iD - RD));
+                if constexpr (ALPHA) {
+                    g[LC_OP] += Ts[j] * gA * (1 - RA);
+                    RA = h.alpha + (1 - h.alpha) * RA;
+                }
                 g[LC_IN] = (g0 * h.bc0 + g1 * h.bc1 + g2 * h.bc2) * aT;
                 const float om = 1 - h.alpha;
                 R0 = h.alpha * c0 + om * R0; R1 = h.alpha * c1 + om * R1; R2 = h.alpha * c2 + om * R2;
@@ -250,10 +260,13 @@ void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color,
 
 void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const float* dL_dcolor, const float* dL_ddepth,
                                      const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
-                                     float* dL_dverts_ndc, float* dL_dfaces_intense, hipStream_t st) {
+                                     float* dL_dverts_ndc, float* dL_dfaces_intense, const float* dL_dalpha, hipStream_t st) {
     const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
-    hipLaunchKernelGGL(k_layer_composite_bwd, grid, dim3(TILE_PIX), 0, st, d, dL_dcolor, dL_ddepth, n_contrib,
-                       LcGrads{dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense});
+    const LcGrads o{dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense};
+    if (dL_dalpha)
+        hipLaunchKernelGGL(k_layer_composite_bwd<true>, grid, dim3(TILE_PIX), 0, st, d, dL_dcolor, dL_ddepth, n_contrib, o, dL_dalpha);
+    else
+        hipLaunchKernelGGL(k_layer_composite_bwd<false>, grid, dim3(TILE_PIX), 0, st, d, dL_dcolor, dL_ddepth, n_contrib, o, dL_dalpha);
 }
 
 }  // namespace dm2

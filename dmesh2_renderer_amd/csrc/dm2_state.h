@@ -189,7 +189,7 @@ void launch_render_backward_fast(const dm2_render_desc& d, const uint2* ranges, 
                                  const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
                                  float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
                                  float* dL_daa_face_verts, const BinningState& bs, bool clip, TieEntry* tie_queue,
-                                 int64_t tie_cap, bool check_mode, hipStream_t st);
+                                 int64_t tie_cap, bool check_mode, const float* dL_dalpha, hipStream_t st);
 // fwd_mode: DM2_FWD_* of the forward.  The selection table is in dm2_backward.hip: a mode that matches the temperature
 // launches its kernel(s) unchecked; DM2_FWD_UNKNOWN, or a mode no forward at this temperature returns, launches a cascade
 // of candidates that look at hit_valid on the device, exactly one of which works
@@ -197,7 +197,7 @@ void launch_render_backward(const dm2_render_desc& d, const uint2* ranges, const
                             const float* dL_dcolor, const float* dL_ddepth, float* dL_dverts, float* dL_dverts_color,
                             float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense,
                             float* dL_daa_face_verts, const BinningState& bs, int fwd_mode, TieEntry* tie_queue, int64_t tie_cap,
-                            hipStream_t st);
+                            const float* dL_dalpha, hipStream_t st);
 void launch_debug_aa_overlap(int variant, int64_t n, const float* tv, const float* te, const uint8_t* tz, const float* tr,
                              const float* tn, const float* tc, const float* pixmin, float* area, float* grad, int32_t* code,
                              hipStream_t st);
@@ -216,7 +216,9 @@ void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color,
                             int32_t* out_n_contrib, hipStream_t st);
 void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const float* dL_dcolor, const float* dL_ddepth,
                                      const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
-                                     float* dL_dverts_ndc, float* dL_dfaces_intense, hipStream_t st);
+                                     float* dL_dverts_ndc, float* dL_dfaces_intense, const float* dL_dalpha, hipStream_t st);
+// out_alpha[pix] = 1 - is.final_T[pix] for the N pixels of a forward (dm2_forward_alpha)
+void launch_forward_alpha(ImageState is, int64_t N, float* out_alpha, hipStream_t st);
 void launch_layers(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                    LayerImageState ls, void* tet_scratch, int32_t* render_layers, int32_t* render_layers_cnt, hipStream_t st);
 

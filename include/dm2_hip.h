@@ -197,6 +197,24 @@ int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward
                  float* dL_dverts_ndc, float* dL_dfaces_intense, float* dL_daa_face_verts,
                  void* stream);
 
+/* The alpha (coverage) image of a forward: out_alpha (B,H,W) = 1 - T, the T the forward multiplied the background by
+ * (0 where no face blended).  image_scratch: the forward's, unmodified.  Call it behind dm2_forward / dm2_forward_run
+ * on the same stream; it reads nothing else. */
+int dm2_forward_alpha(const dm2_render_desc* d, const void* image_scratch, size_t image_bytes, float* out_alpha, void* stream);
+
+/* dm2_backward with one more upstream gradient: dL_dout_alpha (B,H,W), of the alpha image of dm2_forward_alpha.  It
+ * reaches dL_dfaces_opacity and, through the AA coverage, dL_daa_face_verts (or verts_image); nothing else.  NULL: exactly
+ * dm2_backward. */
+int dm2_backward_alpha(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode,
+                       const float* dL_dout_color, const float* dL_dout_depth, const float* dL_dout_alpha,
+                       const void* face_scratch, size_t face_bytes,
+                       void* binning_scratch, size_t binning_bytes,
+                       const void* image_scratch, size_t image_bytes,
+                       void* tie_scratch, size_t tie_bytes,
+                       float* dL_dverts, float* dL_dverts_color, float* dL_dfaces_opacity,
+                       float* dL_dverts_ndc, float* dL_dfaces_intense, float* dL_daa_face_verts,
+                       void* stream);
+
 /* LayeredRenderer (render.h:101-119). */
 typedef struct dm2_layers_desc {
     int32_t B, P, F, T;
@@ -268,6 +286,12 @@ int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, fl
 int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
                                   const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
                                   float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
+/* dm2_layers_composite_backward with one more upstream gradient: dL_dout_alpha (B,H,W), of alpha = 1 - out_final_T.  It
+ * reaches dL_dfaces_opacity only.  NULL: exactly dm2_layers_composite_backward. */
+int dm2_layers_composite_backward_alpha(const dm2_layer_composite_desc* d, const float* dL_dout_color,
+                                        const float* dL_dout_depth, const float* dL_dout_alpha,
+                                        const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
+                                        float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
 
 /* Host prep of Renderer.forward / LayeredRenderer.generate, fused.
  * Replaces the ~20 torch kernels of the reference's Python host layer:
