@@ -13,7 +13,8 @@ and the consumer of those layers the reference does not have (LayeredRenderer.re
     composite_layers_cuda(...10 args...) -> 4-tuple, composite_layers_backward_cuda(...13 args...) -> 4-tuple
 
 Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
-its gradient as the keyword ``dL_dout_alpha``.
+its gradient as the keyword ``dL_dout_alpha``.  Under ``face_weights_output`` render_forward_cuda and composite_layers_cuda
+append the per-face blend weights (B,F), behind everything else they return; they have no gradient.
 
 PyTorch is used only as the owner of device memory and of the current stream;
 every computation happens in the HIP library.  There is NO fallback: if the
@@ -111,6 +112,11 @@ EXPORTS = {
     "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                             _vp]),
     "dm2_forward_alpha": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _vp]),
+    "dm2_forward_weights": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                           ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
+    "dm2_forward_run_weights": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp,
+                                               _vp, _vp, _vp, ctypes.POINTER(_i32)]),
+    "dm2_layers_composite_weights": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_backward_alpha": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp,
                                           _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_prepare_faces": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp]),
@@ -380,6 +386,24 @@ class alpha_output:
         _tls.alpha_output = self.old
 
 
+class face_weights_output:
+    """``with _C.face_weights_output(True): _C.render_forward_cuda(...)`` -- the forward appends face_weights (B,F) float32
+    behind everything else it returns (behind alpha under ``alpha_output``): per view and face the sum, over the pixels of
+    the patch, of alpha * T of each of the face's blends -- the factor its colour gets in C += c alpha T
+    (dm2_forward_weights).  Float atomics: the last bits may vary from run to run.  No gradient.  Also read by
+    ``composite_layers_cuda`` (dm2_layers_composite_weights) and ``LayeredCompositeFunction``."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_tls, "face_weights_output", False)
+        _tls.face_weights_output = self.on
+
+    def __exit__(self, *exc):
+        _tls.face_weights_output = self.old
+
+
 class forward_mode:
     """``with _C.forward_mode(mode): _C.render_backward_cuda(...)`` -- tells the backward what the forward of this frame left
     for it (FWD_NONE / FWD_MASKS / FWD_POOL, as ``_C.last_forward_mode()`` reported right after that forward), so that it
@@ -445,9 +469,11 @@ def render_forward_cuda(*args):
     if getattr(_tls, "aa_to_verts", False):
         d.flags |= DM2_FLAG_AA_GRAD_TO_VERTS          # the packed records note the CCW reorder for the backward
     want_alpha = bool(getattr(_tls, "alpha_output", False))
+    want_weights = bool(getattr(_tls, "face_weights_output", False))
     with torch.cuda.device(dev):
         st = _stream(dev)
         f32, i32 = torch.float32, torch.int32
+        weights = torch.zeros((B, F), dtype=f32, device=dev) if want_weights else None   # (accumulated by the composite)
         color = torch.empty((B, H, W, 3), dtype=f32, device=dev)
         depth = torch.empty((B, H, W), dtype=f32, device=dev)
         oarea = torch.empty((B, H, W, 0), dtype=f32, device=dev)
@@ -461,7 +487,9 @@ def render_forward_cuda(*args):
             e = _bytes(dev, 0)
             _tls.last_pair_bound = 0
             out = (0, color, depth, oarea, tri_id, tri_cnt, doarea, e, _bytes(dev, 0), _bytes(dev, 0))
-            return out + (torch.zeros((B, H, W), dtype=f32, device=dev),) if want_alpha else out
+            if want_alpha:
+                out += (torch.zeros((B, H, W), dtype=f32, device=dev),)
+            return out + (weights,) if want_weights else out
         tri_cnt = torch.empty((B, H, W), dtype=i32, device=dev)
         face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn + 1))
         img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_IMAGE, N, Tn))
@@ -474,9 +502,13 @@ def render_forward_cuda(*args):
         if _pool_budget(N, 0) <= 0:
             d.flags |= DM2_FLAG_NO_PAIR_POOL
         bin_buf = _bytes(dev, hint)
-        rc = lib.dm2_forward(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(),
-                             _ptr(color), _ptr(depth), _ptr(tri_cnt), st, ctypes.byref(nr), ctypes.byref(longest), ctypes.byref(pairs),
-                             ctypes.byref(mode))
+        fwd_args = (ctypes.byref(d), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(),
+                    _ptr(color), _ptr(depth), _ptr(tri_cnt))
+        fwd_tail = (st, ctypes.byref(nr), ctypes.byref(longest), ctypes.byref(pairs), ctypes.byref(mode))
+        if want_weights:
+            rc = lib.dm2_forward_weights(*fwd_args, _ptr(weights), *fwd_tail)
+        else:
+            rc = lib.dm2_forward(*fwd_args, *fwd_tail)
         if rc not in (0, 2):
             raise _err(lib, "render_forward_cuda")
         R = int(nr.value)
@@ -490,9 +522,14 @@ def render_forward_cuda(*args):
             if over:
                 d.flags |= DM2_FLAG_NO_PAIR_POOL
             bin_buf = _bytes(dev, need + need // 4)
-            if lib.dm2_forward_run(ctypes.byref(d), R, int(longest.value), int(pairs.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf),
-                                   bin_buf.numel(), _ptr(img_buf), img_buf.numel(), _ptr(color), _ptr(depth), _ptr(tri_cnt), st,
-                                   ctypes.byref(mode)):
+            run_args = (ctypes.byref(d), R, int(longest.value), int(pairs.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf),
+                        bin_buf.numel(), _ptr(img_buf), img_buf.numel(), _ptr(color), _ptr(depth), _ptr(tri_cnt))
+            if want_weights:
+                weights.zero_()                       # (the over-budget case composited once already: the sums start again)
+                rc = lib.dm2_forward_run_weights(*run_args, _ptr(weights), st, ctypes.byref(mode))
+            else:
+                rc = lib.dm2_forward_run(*run_args, st, ctypes.byref(mode))
+            if rc:
                 raise _err(lib, "render_forward_cuda (run)")
         with _lock:
             hint = _bin_hint.get(key, 0)
@@ -508,7 +545,9 @@ def render_forward_cuda(*args):
     _tls.last_pair_bound = int(pairs.value)
     bin_buf._dm2_fwd_mode = int(mode.value)       # (survives only as long as this very tensor object is passed around)
     out = (R, color, depth, oarea, tri_id, tri_cnt, doarea, face_buf, bin_buf, img_buf)
-    return out + (alpha,) if want_alpha else out
+    if want_alpha:
+        out += (alpha,)
+    return out + (weights,) if want_weights else out
 
 
 def render_backward_cuda(*args, dL_dout_alpha=None):
@@ -692,7 +731,8 @@ def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacit
     render_layers (B,H,W,L) int32 (ids outside [0, F) are skipped), verts (P,3), faces (F,3) int32, verts_color (P,3),
     faces_opacity (F), faces_intense (B,F), verts_ndc (B,P,3), background (3), image_ray_o / image_ray_d (B,H,W,3) of the
     full frame (placeholders under ``analytic_rays``) -> (color (B,H,W,3), depth_raw (B,H,W) NDC depth with background 1,
-    final_T (B,H,W), n_contrib (B,H,W) int32: 1 + index of the last layer that blended)."""
+    final_T (B,H,W), n_contrib (B,H,W) int32: 1 + index of the last layer that blended); under ``face_weights_output`` a
+    fifth: face_weights (B,F), the sum of alpha * T over each face's blends (dm2_layers_composite_weights)."""
     lib = load_library()
     keep: list = []
     d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
@@ -703,12 +743,19 @@ def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacit
     depth = torch.empty((B, H, W), dtype=f32, device=dev)
     final_T = torch.empty((B, H, W), dtype=f32, device=dev)
     n_contrib = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    weights = torch.zeros((B, d.F), dtype=f32, device=dev) if getattr(_tls, "face_weights_output", False) else None
+    extra = (weights,) if weights is not None else ()
     if B * H * W == 0:
-        return color, depth, final_T, n_contrib
+        return (color, depth, final_T, n_contrib) + extra
     with torch.cuda.device(dev):
-        if lib.dm2_layers_composite(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib), _stream(dev)):
+        if weights is None:
+            rc = lib.dm2_layers_composite(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib), _stream(dev))
+        else:
+            rc = lib.dm2_layers_composite_weights(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib),
+                                                  _ptr(weights), _stream(dev))
+        if rc:
             raise _err(lib, "composite_layers_cuda")
-    return color, depth, final_T, n_contrib
+    return (color, depth, final_T, n_contrib) + extra
 
 
 def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,

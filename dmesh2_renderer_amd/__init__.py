@@ -48,7 +48,9 @@ class RenderFunction(torch.autograd.Function):
 
     Outputs: (color, depth); under ``_C.alpha_output(True)`` (color, depth, alpha) with alpha (B,H,W) = 1 - T, the share
     of each pixel the blended faces cover.  Then an output left out of the loss costs nothing in the backward: an unused
-    alpha launches the kernels of the two-output op.
+    alpha launches the kernels of the two-output op.  Under ``_C.face_weights_output(True)`` one more output at the end:
+    face_weights (B,F), the sum of alpha * T over each face's blends -- non-differentiable; the backward is the call it
+    would be without it.
     """
 
     N_INPUTS = 21
@@ -68,6 +70,7 @@ class RenderFunction(torch.autograd.Function):
         ctx.aa_to_verts = bool(getattr(_C._tls, "aa_to_verts", False))
         ctx.tables_from_image = bool(getattr(_C._tls, "tables_from_image", False))
         ctx.alpha = bool(getattr(_C._tls, "alpha_output", False))
+        ctx.weights = bool(getattr(_C._tls, "face_weights_output", False))
         if ctx.alpha:
             ctx.set_materialize_grads(False)        # an unused alpha arrives as None, and the backward is the two-output one
         try:
@@ -86,12 +89,16 @@ class RenderFunction(torch.autograd.Function):
         ctx.tensor_slots = [i for i, x in enumerate(inputs) if torch.is_tensor(x)]
         ctx.scalars = {i: x for i, x in enumerate(inputs) if not torch.is_tensor(x)}
         ctx.num_rendered = num_rendered
-        if ctx.alpha:
-            return color, depth, out[10]
-        return color, depth
+        res = (color, depth, out[10]) if ctx.alpha else (color, depth)
+        if ctx.weights:
+            ctx.mark_non_differentiable(out[-1])
+            res += (out[-1],)
+        return res
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_out_depth, grad_out_alpha=None):
+    def backward(ctx, grad_out_color, grad_out_depth, *grad_rest):
+        # grad_rest: (alpha's,) under alpha_output, then face_weights' (non-differentiable: ignored)
+        grad_out_alpha = grad_rest[0] if ctx.alpha else None
         saved = ctx.saved_tensors
         inputs: list = [None] * RenderFunction.N_INPUTS
         for slot, t in zip(ctx.tensor_slots, saved[:ctx.n_tensor_in]):
@@ -237,13 +244,16 @@ class Renderer(torch.nn.Module):
     def forward(self, batch_mvp_idx: List[int], batch_patch_min: torch.Tensor, patch_width: int,
                 patch_height: int, verts: torch.Tensor, faces: torch.Tensor, verts_color: torch.Tensor,
                 faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor,
-                aa_temperature: float = 1.0, return_alpha: bool = False):
+                aa_temperature: float = 1.0, return_alpha: bool = False, return_face_weights: bool = False):
         """Render ``len(batch_mvp_idx)`` patches; returns color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background).
 
         Not in the reference's signature: ``return_alpha=True`` returns (color, depth, alpha), alpha (B,H,W) = 1 - T, the
         T the colour multiplied the background by -- differentiable w.r.t. faces_opacity and, through the AA coverage,
-        verts."""
-        with _C.alpha_output(return_alpha):
+        verts.  ``return_face_weights=True`` appends face_weights (B,F) float32: for each view and face, the sum over the
+        patch's pixels of alpha * T of the face's blends, the factor its colour gets in C += c alpha T (sum_f equals the
+        alpha image's sum; > 0 marks the faces the view used).  Not differentiable; also under torch.no_grad().  Float
+        atomics: the last bits may vary from run to run."""
+        with _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
             return self._forward(batch_mvp_idx, batch_patch_min, patch_width, patch_height, verts, faces, verts_color,
                                  faces_opacity, faces_intense, background, aa_temperature)
 
@@ -338,7 +348,8 @@ class LayeredCompositeFunction(torch.autograd.Function):
     this path.  ``background`` gets no gradient, as in Renderer.
 
     Under ``_C.alpha_output(True)`` a third output: alpha (B,H,W) = 1 - final_T, with a gradient w.r.t. faces_opacity; an
-    alpha left out of the loss launches the kernel of the two-output function.
+    alpha left out of the loss launches the kernel of the two-output function.  Under ``_C.face_weights_output(True)`` a last
+    output: face_weights (B,F), the sum of alpha * T over each face's blends, non-differentiable.
     """
 
     @staticmethod
@@ -348,17 +359,21 @@ class LayeredCompositeFunction(torch.autograd.Function):
         ctx.alpha = bool(getattr(_C._tls, "alpha_output", False))
         if ctx.alpha:
             ctx.set_materialize_grads(False)
-        color, depth, final_T, n_contrib = _C.composite_layers_cuda(
+        out = _C.composite_layers_cuda(
             render_layers, verts.detach(), faces, verts_color.detach(), faces_opacity.detach(), faces_intense.detach(),
             verts_ndc.detach(), background, image_ray_o, image_ray_d)
+        color, depth, final_T, n_contrib = out[:4]
         ctx.save_for_backward(render_layers, verts.detach(), faces, verts_color.detach(), faces_opacity.detach(),
                               faces_intense.detach(), verts_ndc.detach(), background, image_ray_o, image_ray_d, n_contrib)
-        if ctx.alpha:
-            return color, depth, 1.0 - final_T         # (bit-equal to the kernel's 1.f - T)
-        return color, depth
+        res = (color, depth, 1.0 - final_T) if ctx.alpha else (color, depth)     # (alpha bit-equal to the kernel's 1.f - T)
+        if len(out) > 4:                               # face_weights_output: non-differentiable
+            ctx.mark_non_differentiable(out[4])
+            res += (out[4],)
+        return res
 
     @staticmethod
-    def backward(ctx, grad_color, grad_depth, grad_alpha=None):
+    def backward(ctx, grad_color, grad_depth, *grad_rest):
+        grad_alpha = grad_rest[0] if ctx.alpha else None      # (then face_weights', ignored)
         (render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
          n_contrib) = ctx.saved_tensors
         if ctx.alpha:                                  # (grads not materialised: zeros for an unused colour / depth)
@@ -417,9 +432,11 @@ class LayeredRenderer(Renderer):
 
     def render(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
                verts_color: torch.Tensor, faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor,
-               return_alpha: bool = False):
+               return_alpha: bool = False, return_face_weights: bool = False):
         """Composite per-pixel face layers front to back -> color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background); with
-        ``return_alpha=True`` also alpha (B,H,W) = 1 - T, differentiable w.r.t. faces_opacity.
+        ``return_alpha=True`` also alpha (B,H,W) = 1 - T, differentiable w.r.t. faces_opacity; with
+        ``return_face_weights=True`` last face_weights (B,F), the sum of faces_opacity * T over each face's blends (a face
+        listed twice in a pixel counts twice), not differentiable.
 
         render_layers (B,H,W,L) int32 over the full frame, e.g. from ``generate`` (-1 and any id outside [0, F) is skipped,
         holes included); faces_intense (B,F) of the selected views.  A layer blends where the pixel's ray hits its face
@@ -440,11 +457,12 @@ class LayeredRenderer(Renderer):
         if getattr(self, "analytic_rays", False):
             cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
             ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
-            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height), _C.alpha_output(return_alpha):
+            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height), _C.alpha_output(return_alpha), \
+                    _C.face_weights_output(return_face_weights):
                 out = LayeredCompositeFunction.apply(*args, ph, ph)
         else:
             ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
-            with _C.alpha_output(return_alpha):
+            with _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
                 out = LayeredCompositeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32))
         # NDC z in [-1,1] (background +1) -> [0,1] with background 0, as Renderer.forward
         return _finish(out)

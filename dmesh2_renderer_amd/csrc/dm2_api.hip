@@ -227,7 +227,8 @@ int dm2_forward_plan(const dm2_render_desc* d, void* face_scratch, size_t face_b
 
 static int forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound, void* face_scratch, size_t face_bytes,
                        void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
-                       float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream, bool ranges_cleared, int32_t* forward_mode) {
+                       float* out_color, float* out_depth, int32_t* out_tri_cnt, float* out_face_weights, void* stream,
+                       bool ranges_cleared, int32_t* forward_mode) {
     if (forward_mode) *forward_mode = DM2_FWD_NONE;
     if (check_render_desc(d)) return 1;
     hipStream_t st = (hipStream_t)stream;
@@ -252,7 +253,8 @@ static int forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t m
     // the pair pool is used when the caller appended room for every pair the plan counted (a smaller appendix is ignored)
     const bool use_pool = have_faces && pair_bound > 0 && bs.pool_cap >= pair_bound && !(d->flags & DM2_FLAG_NO_PAIR_POOL);
     const float pairs_per_entry = num_rendered > 0 ? (float)((double)pair_bound / (double)num_rendered) : 0.0f;
-    const int mode = dm2::launch_render_forward(*d, is.ranges, bs.face_list, is, out_color, out_depth, out_tri_cnt, bs, use_pool, pairs_per_entry, st);
+    const int mode = dm2::launch_render_forward(*d, is.ranges, bs.face_list, is, out_color, out_depth, out_tri_cnt, bs, use_pool, pairs_per_entry,
+                                                out_face_weights, st);
     if (forward_mode) *forward_mode = mode;
     DM2_HIP(hipGetLastError());
     return 0;
@@ -261,13 +263,29 @@ static int forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t m
 int dm2_forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound, void* face_scratch, size_t face_bytes,
                     void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
                     float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream, int32_t* forward_mode) {
+    return dm2_forward_run_weights(d, num_rendered, max_tile_entries, pair_bound, face_scratch, face_bytes, binning_scratch, binning_bytes,
+                                   image_scratch, image_bytes, out_color, out_depth, out_tri_cnt, nullptr, stream, forward_mode);
+}
+
+int dm2_forward_run_weights(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound,
+                            void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                            void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt,
+                            float* out_face_weights, void* stream, int32_t* forward_mode) {
     return forward_run(d, num_rendered, max_tile_entries, pair_bound, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch,
-                       image_bytes, out_color, out_depth, out_tri_cnt, stream, false, forward_mode);
+                       image_bytes, out_color, out_depth, out_tri_cnt, out_face_weights, stream, false, forward_mode);
 }
 
 int dm2_forward(const dm2_render_desc* d, void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
                 void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream,
                 int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound, int32_t* forward_mode) {
+    return dm2_forward_weights(d, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch, image_bytes, out_color,
+                               out_depth, out_tri_cnt, nullptr, stream, num_rendered, max_tile_entries, pair_bound, forward_mode);
+}
+
+int dm2_forward_weights(const dm2_render_desc* d, void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                        void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt,
+                        float* out_face_weights, void* stream, int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound,
+                        int32_t* forward_mode) {
     if (check_render_desc(d)) return 1;
     if (!pair_bound) return fail("pair_bound is null");
     if (forward_mode) *forward_mode = DM2_FWD_NONE;
@@ -284,7 +302,8 @@ int dm2_forward(const dm2_render_desc* d, void* face_scratch, size_t face_bytes,
     if (dm2_scratch_bytes(DM2_SCRATCH_BINNING, *num_rendered, Tn) + (wants_pool ? dm2_scratch_bytes(DM2_SCRATCH_PAIR_POOL, *pair_bound, 0) : 0) > binning_bytes)
         return 2;                                                                // plan done; allocate, then dm2_forward_run
     return forward_run(d, *num_rendered, *max_tile_entries, *pair_bound, face_scratch, face_bytes, binning_scratch, binning_bytes,
-                       image_scratch, image_bytes, out_color, out_depth, out_tri_cnt, stream, planned && ranges != nullptr, forward_mode);
+                       image_scratch, image_bytes, out_color, out_depth, out_tri_cnt, out_face_weights, stream, planned && ranges != nullptr,
+                       forward_mode);
 }
 
 int dm2_forward_alpha(const dm2_render_desc* d, const void* image_scratch, size_t image_bytes, float* out_alpha, void* stream) {
@@ -426,10 +445,15 @@ static int check_composite_desc(const dm2_layer_composite_desc* d) {
 
 int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
                          int32_t* out_n_contrib, void* stream) {
+    return dm2_layers_composite_weights(d, out_color, out_depth, out_final_T, out_n_contrib, nullptr, stream);
+}
+
+int dm2_layers_composite_weights(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
+                                 int32_t* out_n_contrib, float* out_face_weights, void* stream) {
     if (check_composite_desc(d)) return 1;
     if ((int64_t)d->B * d->H * d->W == 0) return 0;
     if (!out_color || !out_depth || !out_n_contrib) return fail("out_color / out_depth / out_n_contrib must not be null");
-    dm2::launch_layer_composite(*d, out_color, out_depth, out_final_T, out_n_contrib, (hipStream_t)stream);
+    dm2::launch_layer_composite(*d, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }

@@ -17,11 +17,15 @@ namespace dm2 {
 
 constexpr int FWD_CHUNK = 128;
 
+// WEIGHTS (dm2_forward_weights): each blend adds its alpha * T into an LDS sum per staged face (ds_add_f32); behind the next
+// barrier one lane per list entry flushes a non-zero sum to face_weights[b, face] with one global atomic.
+template <bool WEIGHTS>
 __global__ void __launch_bounds__(TILE_PIX)
 k_render_forward(dm2_render_desc d, const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                  ImageState is, float* __restrict__ out_color, float* __restrict__ out_depth,
-                 int32_t* __restrict__ out_tri_cnt) {
+                 int32_t* __restrict__ out_tri_cnt, float* __restrict__ face_weights) {
     __shared__ FaceRec recs[FWD_CHUNK];
+    __shared__ float s_w[WEIGHTS ? FWD_CHUNK : 1];
 
     const int b = blockIdx.z;
     const uint32_t gx = (d.W + TILE - 1) / TILE, gy = (d.H + TILE - 1) / TILE;
@@ -51,9 +55,23 @@ k_render_forward(dm2_render_desc d, const uint2* __restrict__ ranges, const uint
     uint32_t contributor = 0, last_contributor = 0;
     float C0 = 0.f, C1 = 0.f, C2 = 0.f, D = 0.f;
     int rec_cnt = 0;
+    // (WEIGHTS) the sums of list entries [wb, wb + wn) after a barrier behind their walk; a flushed slot is zero again
+    auto flush_weights = [&](int wb, int wn) {
+        if (tid < wn) {
+            const float w = s_w[tid];
+            if (w != 0.0f) { atomicAdd(face_weights + (int64_t)b * d.F + face_list[range.x + wb + tid], w); s_w[tid] = 0.f; }
+        }
+    };
+    if constexpr (WEIGHTS) { if (tid < FWD_CHUNK) s_w[tid] = 0.f; }   // (first read behind the loop's first barrier)
 
     for (int base = 0; base < total; base += FWD_CHUNK) {
-        if (__syncthreads_count(done) == TILE_PIX) break;          // forward.cu:258-260 (also guards LDS reuse)
+        if constexpr (WEIGHTS) {                                    // forward.cu:258-260 (also guards LDS reuse)
+            const int ndone = __syncthreads_count(done);
+            if (base > 0) flush_weights(base - FWD_CHUNK, FWD_CHUNK);  // the previous (full) chunk's sums
+            if (ndone == TILE_PIX) break;
+        } else if (__syncthreads_count(done) == TILE_PIX) {
+            break;
+        }
         const int n = min(FWD_CHUNK, total - base);
         if (tid < n) stage_face(is.face_recs, (int64_t)b * d.F + face_list[range.x + base + tid], recs[tid]);
         __syncthreads();
@@ -83,12 +101,19 @@ k_render_forward(dm2_render_desc d, const uint2* __restrict__ ranges, const uint
             const float iD = i0 * fc.dep[0] + i1 * fc.dep[1] + i2 * fc.dep[2];
             const float alpha = fc.opacity * ratio;
             const float test_T = T * (1 - alpha);
+            if constexpr (WEIGHTS) atomicAdd(&s_w[j], alpha * T);
             C0 += c0 * alpha * T; C1 += c1 * alpha * T; C2 += c2 * alpha * T;
             D += iD * alpha * T;
             pT = T; T = test_T;
             last_contributor = contributor;
             if (T < T_EPS) { done = true; break; }
         }
+    }
+    if constexpr (WEIGHTS) {
+        // the last chunk's sums: it started at a multiple of FWD_CHUNK below total, or the loop broke behind a flush that left
+        // every slot zero
+        __syncthreads();
+        if (total > 0) flush_weights((total - 1) / FWD_CHUNK * FWD_CHUNK, (total - 1) % FWD_CHUNK + 1);
     }
 
     if (inside) {
@@ -109,7 +134,7 @@ constexpr float FQ_CLASSES_FROM = 32.0f;
 
 int launch_render_forward(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                           float* out_color, float* out_depth, int32_t* out_tri_cnt, const BinningState& bs, bool use_pool,
-                          float pairs_per_entry, hipStream_t st) {
+                          float pairs_per_entry, float* face_weights, hipStream_t st) {
     uint64_t* const hit_masks = bs.hit_masks; uint32_t* const hit_valid = bs.hit_valid;
     if (!(d.flags & DM2_FLAG_LEGACY_KERNELS)) {
         if (d.aa_temperature > 0.0f) {
@@ -119,21 +144,26 @@ int launch_render_forward(const dm2_render_desc& d, const uint2* ranges, const u
             const bool pool = masks && use_pool && bs.pool && bs.pool_cap > 0;
             launch_render_forward_queue(d, ranges, face_list, is, out_color, out_depth, out_tri_cnt, masks ? hit_masks : nullptr,
                                         masks ? hit_valid : nullptr, pool ? bs.pool : nullptr, pool ? bs.pool_cap : 0, bs.hit_base,
-                                        pairs_per_entry >= FQ_CLASSES_FROM, st);
+                                        pairs_per_entry >= FQ_CLASSES_FROM, face_weights, st);
             return pool ? DM2_FWD_POOL : (masks ? DM2_FWD_MASKS : DM2_FWD_NONE);
         }
         // aa_temperature == 0: the reference applies no bbox test (forward.cu:314), every face of a tile's list meets
         // all 256 pixels: the per-pixel walk is the dense formulation there.  dm2_forward_point.hip is that walk with
         // one extra product: the per-(entry, wave) hit masks the backward would otherwise have to recompute.
         if (hit_masks && hit_valid) {
-            launch_render_forward_point(d, ranges, face_list, is, out_color, out_depth, out_tri_cnt, hit_masks, hit_valid, st);
+            launch_render_forward_point(d, ranges, face_list, is, out_color, out_depth, out_tri_cnt, hit_masks, hit_valid, face_weights, st);
             return DM2_FWD_POINT;
         }
     }
     // (hit_valid was reset by the binning of this forward, dm2_binning.hip: no masks from this path)
     const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
     StageTimer tm(ST_FWD, st);
-    hipLaunchKernelGGL(k_render_forward, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth, out_tri_cnt);
+    if (face_weights)
+        hipLaunchKernelGGL(k_render_forward<true>, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth,
+                           out_tri_cnt, face_weights);
+    else
+        hipLaunchKernelGGL(k_render_forward<false>, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth,
+                           out_tri_cnt, face_weights);
     return DM2_FWD_NONE;
 }
 

@@ -35,13 +35,19 @@ constexpr float FP_EPS = 1.0e-5f;     // relative bound of |quick dot - exact nu
 // per staged face, for rays from `ro`: A = E2 x T, Bv = T x E1, Nn = E2 x E1 and the same sums with every term's magnitude
 struct __attribute__((aligned(16))) FpQuick { float A[3], ma, Bv[3], mb, Nn[3], md; };    // m*: FP_EPS x the sums' un-cancelled magnitudes for |rd_i| <= 1
 
+// WEIGHTS (dm2_forward_weights): a wave walks one entry at a time, so the alpha * T of its blends is summed across the wave
+// and added into an LDS sum per staged face (one ds_add_f32 per wave and entry hit); behind the next barrier one lane per
+// list entry flushes a non-zero sum to face_weights[b, face] with one global atomic.
+template <bool WEIGHTS>
 __global__ void __launch_bounds__(TILE_PIX)
 k_render_forward_point(dm2_render_desc d, const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                        ImageState is, float* __restrict__ out_color, float* __restrict__ out_depth,
-                       int32_t* __restrict__ out_tri_cnt, uint64_t* __restrict__ hit_masks, uint32_t* __restrict__ hit_valid) {
+                       int32_t* __restrict__ out_tri_cnt, uint64_t* __restrict__ hit_masks, uint32_t* __restrict__ hit_valid,
+                       float* __restrict__ face_weights) {
     __shared__ FaceRec recs[FP_CHUNK];
     __shared__ FpQuick s_quick[FP_CHUNK];
     __shared__ float s_ro[3];
+    __shared__ float s_w[WEIGHTS ? FP_CHUNK : 1];
 
     const uint32_t gx = (d.W + TILE - 1) / TILE, gy = (d.H + TILE - 1) / TILE;
     uint32_t tile;
@@ -64,6 +70,7 @@ k_render_forward_point(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     const int total = (int)(range.y - range.x);
     // do all rays of the tile share their origin (pixel (0,0) of the tile is always inside the image)?
     if (tid == 0) { s_ro[0] = ro.x; s_ro[1] = ro.y; s_ro[2] = ro.z; }
+    if constexpr (WEIGHTS) { if (tid < FP_CHUNK) s_w[tid] = 0.f; }
     __syncthreads();
     const f3 ro0 = {s_ro[0], s_ro[1], s_ro[2]};
     const bool quick = __syncthreads_and(!inside || (ro.x == ro0.x && ro.y == ro0.y && ro.z == ro0.z &&
@@ -94,9 +101,22 @@ k_render_forward_point(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     float pT = 1.0f, T = 1.0f;
     uint32_t contributor = 0, last_contributor = 0;
     float C0 = 0.f, C1 = 0.f, C2 = 0.f, D = 0.f;
+    // (WEIGHTS) the sums of list entries [wb, wb + wn) after a barrier behind their walk; a flushed slot is zero again
+    auto flush_weights = [&](int wb, int wn) {
+        if (tid < wn) {
+            const float w = s_w[tid];
+            if (w != 0.0f) { atomicAdd(face_weights + (int64_t)b * d.F + face_list[range.x + wb + tid], w); s_w[tid] = 0.f; }
+        }
+    };
 
     for (int base = 0; base < total; base += FP_CHUNK) {
-        if (__syncthreads_count(done) == TILE_PIX) break;          // forward.cu:258-260 (also guards LDS reuse)
+        if constexpr (WEIGHTS) {                                    // forward.cu:258-260 (also guards LDS reuse)
+            const int ndone = __syncthreads_count(done);
+            if (base > 0) flush_weights(base - FP_CHUNK, FP_CHUNK);  // the previous (full) chunk's sums
+            if (ndone == TILE_PIX) break;
+        } else if (__syncthreads_count(done) == TILE_PIX) {
+            break;
+        }
         const int n = min(FP_CHUNK, total - base);
         if (tid < n) {
             stage_face(is.face_recs, (int64_t)b * d.F + face_list[range.x + base + tid], recs[tid]);
@@ -175,6 +195,7 @@ k_render_forward_point(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             const bool hit = !done && ok && (iuc >= 0.0f) && (ivc >= 0.0f) && (iuc + ivc <= 1.0f);
             const unsigned long long bal = __ballot(hit);
             if (lane == 0) hit_masks[((int64_t)range.x + base + j) * 4 + wid] = bal;
+            float wgt = 0.f;                                            // (WEIGHTS)
             if (hit) {
                 const float i0 = 1 - iuc - ivc, i1 = iuc, i2 = ivc;
                 float c0 = i0 * fc.col[0] + i1 * fc.col[3] + i2 * fc.col[6];
@@ -184,11 +205,19 @@ k_render_forward_point(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 const float iD = i0 * fc.dep[0] + i1 * fc.dep[1] + i2 * fc.dep[2];
                 const float alpha = fc.opacity * ratio;
                 const float test_T = T * (1 - alpha);
+                if constexpr (WEIGHTS) wgt = alpha * T;
                 C0 += c0 * alpha * T; C1 += c1 * alpha * T; C2 += c2 * alpha * T;
                 D += iD * alpha * T;
                 pT = T; T = test_T;
                 last_contributor = contributor;
                 if (T < T_EPS) done = true;
+            }
+            if constexpr (WEIGHTS) {
+                if (bal) {                                              // (wave-uniform)
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) wgt += __shfl_xor(wgt, o);
+                    if (lane == 0) atomicAdd(&s_w[j], wgt);
+                }
             }
         }
         }   // sub-chunks of 64 faces
@@ -198,6 +227,9 @@ k_render_forward_point(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     __shared__ uint32_t s_maxlc;
     __syncthreads();
     if (tid == 0) s_maxlc = 0;
+    // (WEIGHTS) the last chunk's sums: it started at a multiple of FP_CHUNK below total, or the loop broke behind a flush that
+    // left every slot zero
+    if constexpr (WEIGHTS) { if (total > 0) flush_weights((total - 1) / FP_CHUNK * FP_CHUNK, (total - 1) % FP_CHUNK + 1); }
     __syncthreads();
     { const uint32_t m = wave_inclusive_max(last_contributor); if (lane == 63 && m) atomicMax(&s_maxlc, m); }
     __syncthreads();
@@ -216,11 +248,15 @@ k_render_forward_point(dm2_render_desc d, const uint2* __restrict__ ranges, cons
 
 void launch_render_forward_point(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                                  float* out_color, float* out_depth, int32_t* out_tri_cnt, uint64_t* hit_masks,
-                                 uint32_t* hit_valid, hipStream_t st) {
+                                 uint32_t* hit_valid, float* face_weights, hipStream_t st) {
     const dim3 grid(tile_grid_blocks((uint32_t)(((d.W + TILE - 1) / TILE) * ((d.H + TILE - 1) / TILE) * d.B)));
     StageTimer tm(ST_FWD, st);
-    hipLaunchKernelGGL(k_render_forward_point, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth,
-                       out_tri_cnt, hit_masks, hit_valid);
+    if (face_weights)
+        hipLaunchKernelGGL(k_render_forward_point<true>, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth,
+                           out_tri_cnt, hit_masks, hit_valid, face_weights);
+    else
+        hipLaunchKernelGGL(k_render_forward_point<false>, grid, dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth,
+                           out_tri_cnt, hit_masks, hit_valid, face_weights);
 }
 
 }  // namespace dm2

@@ -64,13 +64,16 @@ struct __attribute__((aligned(8))) FqPair { float alpha, c0, c1, c2, depth; uint
 // (256 x 256 / 2 k faces: forward -14 %, with depth complexity 60: -17 %), costs 4 % with the 2.5-pixel triangles of the
 // 1080p / 1 M workload (a fifth of whose survivors are fully covered: one wave in eight): the launcher picks by the plan's
 // candidate pairs per list entry.
-template <bool CLASSES>
+// WEIGHTS (dm2_forward_weights): phase C adds each blend's alpha * T into an LDS sum per staged face (ds_add_f32); behind the
+// next barrier -- the next chunk's first, or the one after the loop -- one lane per list entry flushes a non-zero sum to
+// face_weights[b, face] with one global atomic.  A face is on a tile's list at most once: at most one atomic per entry.
+template <bool CLASSES, bool WEIGHTS>
 __global__ void __launch_bounds__(TILE_PIX, DM2_FQ_BLOCKS)
 k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                        ImageState is, float* __restrict__ out_color, float* __restrict__ out_depth,
                        int32_t* __restrict__ out_tri_cnt, uint64_t* __restrict__ hit_masks,
                        uint32_t* __restrict__ hit_valid, float* __restrict__ pool, uint32_t pool_cap,
-                       uint32_t* __restrict__ hit_base STAMP_PARAM) {
+                       uint32_t* __restrict__ hit_base, float* __restrict__ face_weights STAMP_PARAM) {
     __shared__ FaceRec recs[FQ_CHUNK];                   // this chunk's faces; refilled (LDS-direct) behind phase B2, its last reader
     __shared__ uint32_t s_ids[64];                       // face ids of the NEXT chunk's list entries
     __shared__ FqPair s_pair[FQ_SURVCAP];
@@ -90,6 +93,7 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     __shared__ int s_bpre[4][FQ_SURVCAP / 64];           // [wave]: set bits of s_blend in front of each word (every wave scans for itself)
     __shared__ uint32_t s_cbase;                         // pair pool: first slot of this chunk
     __shared__ uint32_t s_maxlc;
+    __shared__ float s_w[WEIGHTS ? FQ_CHUNK : 1];        // (WEIGHTS) per staged face: sum of alpha * T over its blends
 
     const uint32_t gx = (d.W + TILE - 1) / TILE, gy = (d.H + TILE - 1) / TILE;
     uint32_t tile;
@@ -101,6 +105,7 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     STAMP_DECL
     fill_inv_table(s_inv);
     s_mask[tid] = 0;
+    if constexpr (WEIGHTS) { if (tid < FQ_CHUNK) s_w[tid] = 0.f; }
     if (hit_valid && blockIdx.x == 0 && tid == 0) hit_valid[0] = pool ? 3u : 2u;   // AA blend masks (+ the pair pool) are current
     const int lx = tid & 15, ly = tid >> 4;
     const int X0 = tile_x * TILE, Y0 = tile_y * TILE;
@@ -151,12 +156,25 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     uint32_t last_contributor = 0;
     float C0 = 0.f, C1 = 0.f, C2 = 0.f, D = 0.f;
     int rec_cnt = 0;
+    // (WEIGHTS) the sums of list entries [wb, wb + n) after a barrier behind their phase C; a flushed slot is zero again
+    auto flush_weights = [&](int wb, int wn) {
+        if (tid < wn) {
+            const float w = s_w[tid];
+            if (w != 0.0f) { atomicAdd(face_weights + (int64_t)b * d.F + face_list[range.x + wb + tid], w); s_w[tid] = 0.f; }
+        }
+    };
 
     STAMP(0)
     int n = 0;
     for (int base = 0; base < total; base += n) {
         lds_prefetch_wait();                                        // this wave's part of the chunk's records has landed ...
-        if (__syncthreads_count(done) == TILE_PIX) break;          // ... everyone's; forward.cu:258-260; fences LDS reuse
+        if constexpr (WEIGHTS) {                                    // ... everyone's; forward.cu:258-260; fences LDS reuse
+            const int ndone = __syncthreads_count(done);
+            flush_weights(base - n, n);                             // the previous chunk's sums (none in front of the first)
+            if (ndone == TILE_PIX) break;
+        } else if (__syncthreads_count(done) == TILE_PIX) {
+            break;
+        }
         STAMP(1)
         // ---- phase A ----------------------------------------------------------------------
         n = min(FQ_CHUNK, total - base);
@@ -403,6 +421,7 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 if (!(pr.flags & QF_BLEND)) continue;
                 const float alpha = pr.alpha;
                 const float test_T = T * (1 - alpha);
+                if constexpr (WEIGHTS) atomicAdd(&s_w[j], alpha * T);
                 C0 += pr.c0 * alpha * T; C1 += pr.c1 * alpha * T; C2 += pr.c2 * alpha * T;
                 D += pr.depth * alpha * T;
                 pT = T; T = test_T;
@@ -416,6 +435,8 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     // the tile's largest n_contrib: where the backward's walk starts (dm2_backward_fast.hip)
     if (tid == 0) s_maxlc = 0;
     __syncthreads();
+    // (WEIGHTS) the last chunk's sums: it ended at `total`, or the loop broke behind a flush that left every slot zero
+    if constexpr (WEIGHTS) flush_weights(total - n, n);
     { const uint32_t m = wave_inclusive_max(last_contributor); if (lane == 63 && m) atomicMax(&s_maxlc, m); }
     __syncthreads();
     if (tid == 0) is.tile_max_lc[tile] = s_maxlc;
@@ -436,15 +457,20 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
 // classes: take the survivors class by class (triangles of many pixels; the caller decides from the plan's numbers)
 void launch_render_forward_queue(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                                  float* out_color, float* out_depth, int32_t* out_tri_cnt, uint64_t* hit_masks,
-                                 uint32_t* hit_valid, float* pool, int64_t pool_cap, uint32_t* hit_base, bool classes, hipStream_t st) {
+                                 uint32_t* hit_valid, float* pool, int64_t pool_cap, uint32_t* hit_base, bool classes,
+                                 float* face_weights, hipStream_t st) {
     const uint32_t Tn = (uint32_t)(((d.W + TILE - 1) / TILE) * ((d.H + TILE - 1) / TILE) * d.B);
     StageTimer tm(ST_FWD, st);
-    if (classes)
-        hipLaunchKernelGGL(k_render_forward_queue<true>, dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth,
-                           out_tri_cnt, hit_masks, hit_valid, pool, (uint32_t)pool_cap, hit_base STAMP_ARG(0));
-    else
-        hipLaunchKernelGGL(k_render_forward_queue<false>, dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, is, out_color, out_depth,
-                           out_tri_cnt, hit_masks, hit_valid, pool, (uint32_t)pool_cap, hit_base STAMP_ARG(0));
+#define DM2_FQ_LAUNCH(C, W)                                                                                                 \
+    hipLaunchKernelGGL((k_render_forward_queue<C, W>), dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, \
+                       is, out_color, out_depth, out_tri_cnt, hit_masks, hit_valid, pool, (uint32_t)pool_cap, hit_base,      \
+                       face_weights STAMP_ARG(0))
+    if (classes) {
+        if (face_weights) DM2_FQ_LAUNCH(true, true); else DM2_FQ_LAUNCH(true, false);
+    } else {
+        if (face_weights) DM2_FQ_LAUNCH(false, true); else DM2_FQ_LAUNCH(false, false);
+    }
+#undef DM2_FQ_LAUNCH
 }
 
 }  // namespace dm2

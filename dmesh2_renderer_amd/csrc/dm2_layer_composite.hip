@@ -68,14 +68,24 @@ __device__ __forceinline__ bool lc_layer(const dm2_layer_composite_desc& d, int 
     return true;
 }
 
-template <int VEC>
-__global__ void __launch_bounds__(TILE_PIX)
-k_layer_composite(dm2_layer_composite_desc d, float* __restrict__ out_color, float* __restrict__ out_depth,
-                  float* __restrict__ out_final_T, int32_t* __restrict__ out_n_contrib) {
-    const int b = blockIdx.z;
-    const int tid = threadIdx.x;
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
-    if (!((px < (uint32_t)d.W) && (py < (uint32_t)d.H))) return;
+// slot of face f in the tile's table (inserted if new), -1 when LC_PROBES probes find neither f nor a free slot
+__device__ __forceinline__ int lc_slot(int* keys, int f) {
+    const uint32_t h = ((uint32_t)f * 2654435761u) >> 23;          // 9 bits: LC_SLOTS = 512
+#pragma unroll 1
+    for (int p = 0; p < LC_PROBES; p++) {
+        const int s = (int)((h + (uint32_t)p) & (LC_SLOTS - 1));
+        const int old = atomicCAS(&keys[s], -1, f);
+        if (old == -1 || old == f) return s;
+    }
+    return -1;
+}
+
+// one pixel of k_layer_composite (WEIGHTS: its blends' alpha * T into the block's table s_key / s_w)
+template <int VEC, bool WEIGHTS>
+__device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_desc& d, int b, uint32_t px, uint32_t py,
+                                                   float* __restrict__ out_color, float* __restrict__ out_depth,
+                                                   float* __restrict__ out_final_T, int32_t* __restrict__ out_n_contrib,
+                                                   float* __restrict__ face_weights, int* s_key, float* s_w) {
     const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
     f3 ro, rd;
     pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
@@ -89,6 +99,11 @@ k_layer_composite(dm2_layer_composite_desc d, float* __restrict__ out_color, flo
         const float c0 = h.bc0 * h.intense, c1 = h.bc1 * h.intense, c2 = h.bc2 * h.intense;
         const float alpha = h.alpha;
         const float test_T = T * (1 - alpha);
+        if constexpr (WEIGHTS) {
+            const int slot = lc_slot(s_key, f);
+            if (slot >= 0) atomicAdd(&s_w[slot], alpha * T);
+            else atomicAdd(face_weights + (int64_t)b * d.F + f, alpha * T);
+        }
         C0 += c0 * alpha * T; C1 += c1 * alpha * T; C2 += c2 * alpha * T;
         D += h.iD * alpha * T;
         T = test_T;
@@ -118,24 +133,41 @@ k_layer_composite(dm2_layer_composite_desc d, float* __restrict__ out_color, flo
     if (out_n_contrib) out_n_contrib[pix] = n_contrib;
 }
 
+// WEIGHTS (dm2_layers_composite_weights): every blend adds its alpha * T into the per-block LDS table of the backward's kind
+// (keyed by face id, LC_PROBES probes, straight to global memory when no slot is free); the table is flushed with one global
+// atomic per (block, face).
+template <int VEC, bool WEIGHTS>
+__global__ void __launch_bounds__(TILE_PIX)
+k_layer_composite(dm2_layer_composite_desc d, float* __restrict__ out_color, float* __restrict__ out_depth,
+                  float* __restrict__ out_final_T, int32_t* __restrict__ out_n_contrib, float* __restrict__ face_weights) {
+    __shared__ int s_key[WEIGHTS ? LC_SLOTS : 1];
+    __shared__ float s_w[WEIGHTS ? LC_SLOTS : 1];
+    const int b = blockIdx.z;
+    const int tid = threadIdx.x;
+    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
+    const bool inside = (px < (uint32_t)d.W) && (py < (uint32_t)d.H);
+    if constexpr (WEIGHTS) {
+        for (int i = tid; i < LC_SLOTS; i += TILE_PIX) { s_key[i] = -1; s_w[i] = 0.f; }
+        __syncthreads();
+        if (inside) lc_composite_pixel<VEC, true>(d, b, px, py, out_color, out_depth, out_final_T, out_n_contrib, face_weights, s_key, s_w);
+        __syncthreads();
+        for (int i = tid; i < LC_SLOTS; i += TILE_PIX) {
+            const int f = s_key[i];
+            const float w = s_w[i];
+            if (f >= 0 && w != 0.0f) atomicAdd(face_weights + (int64_t)b * d.F + f, w);
+        }
+    } else {
+        if (!inside) return;
+        lc_composite_pixel<VEC, false>(d, b, px, py, out_color, out_depth, out_final_T, out_n_contrib, nullptr, nullptr, nullptr);
+    }
+}
+
 struct LcGrads {
     float* dcolor;      // (P,3)
     float* dopacity;    // (F)
     float* dndc;        // (B,P,3), z only
     float* dintense;    // (B,F)
 };
-
-// slot of face f in the tile's table (inserted if new), -1 when LC_PROBES probes find neither f nor a free slot
-__device__ __forceinline__ int lc_slot(int* keys, int f) {
-    const uint32_t h = ((uint32_t)f * 2654435761u) >> 23;          // 9 bits: LC_SLOTS = 512
-#pragma unroll 1
-    for (int p = 0; p < LC_PROBES; p++) {
-        const int s = (int)((h + (uint32_t)p) & (LC_SLOTS - 1));
-        const int old = atomicCAS(&keys[s], -1, f);
-        if (old == -1 || old == f) return s;
-    }
-    return -1;
-}
 
 __device__ __forceinline__ void lc_global_add(const dm2_layer_composite_desc& d, int b, int f, const float* g, const LcGrads& o) {
     const int v[3] = {d.faces[3 * (int64_t)f], d.faces[3 * (int64_t)f + 1], d.faces[3 * (int64_t)f + 2]};
@@ -246,16 +278,19 @@ k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_d
 }
 
 void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color, float* out_depth, float* out_final_T,
-                            int32_t* out_n_contrib, hipStream_t st) {
+                            int32_t* out_n_contrib, float* out_face_weights, hipStream_t st) {
     const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
     // layer ids as 16- or 8-byte vectors where L and the pointer allow it
     const uintptr_t a = (uintptr_t)d.render_layers;
-    if (d.L % 4 == 0 && a % 16 == 0)
-        hipLaunchKernelGGL(k_layer_composite<4>, grid, dim3(TILE_PIX), 0, st, d, out_color, out_depth, out_final_T, out_n_contrib);
-    else if (d.L % 2 == 0 && a % 8 == 0)
-        hipLaunchKernelGGL(k_layer_composite<2>, grid, dim3(TILE_PIX), 0, st, d, out_color, out_depth, out_final_T, out_n_contrib);
-    else
-        hipLaunchKernelGGL(k_layer_composite<1>, grid, dim3(TILE_PIX), 0, st, d, out_color, out_depth, out_final_T, out_n_contrib);
+    const int vec = (d.L % 4 == 0 && a % 16 == 0) ? 4 : (d.L % 2 == 0 && a % 8 == 0) ? 2 : 1;
+#define DM2_LC_LAUNCH(V, W) \
+    hipLaunchKernelGGL((k_layer_composite<V, W>), grid, dim3(TILE_PIX), 0, st, d, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights)
+    if (out_face_weights) {
+        if (vec == 4) DM2_LC_LAUNCH(4, true); else if (vec == 2) DM2_LC_LAUNCH(2, true); else DM2_LC_LAUNCH(1, true);
+    } else {
+        if (vec == 4) DM2_LC_LAUNCH(4, false); else if (vec == 2) DM2_LC_LAUNCH(2, false); else DM2_LC_LAUNCH(1, false);
+    }
+#undef DM2_LC_LAUNCH
 }
 
 void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const float* dL_dcolor, const float* dL_ddepth,

@@ -177,6 +177,23 @@ int dm2_forward(const dm2_render_desc* d, void* face_scratch, size_t face_bytes,
                 float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream,
                 int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound, int32_t* forward_mode);
 
+/* dm2_forward / dm2_forward_run with one more output: out_face_weights (B,F) float32, which the caller zero-fills (as the
+ * gradient outputs of dm2_backward).  The composite adds, for every blend of face f into a pixel of view b's patch,
+ * alpha * T -- the face's alpha there times the transmittance in front of it, the factor its colour gets in C += c alpha T
+ * -- to out_face_weights[b * F + f].  So sum_f out_face_weights[b, f] = sum over the patch of 1 - T_final.  Float atomics:
+ * the last bits may vary from run to run.  A caller that composites twice into the same weights (dm2_forward_run_weights
+ * after a dm2_forward_weights that returned 0) must zero them in between.  NULL: exactly dm2_forward / dm2_forward_run. */
+int dm2_forward_weights(const dm2_render_desc* d, void* face_scratch, size_t face_bytes,
+                        void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
+                        float* out_color, float* out_depth, int32_t* out_tri_cnt, float* out_face_weights, void* stream,
+                        int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound, int32_t* forward_mode);
+int dm2_forward_run_weights(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound,
+                            void* face_scratch, size_t face_bytes,
+                            void* binning_scratch, size_t binning_bytes,
+                            void* image_scratch, size_t image_bytes,
+                            float* out_color, float* out_depth, int32_t* out_tri_cnt, float* out_face_weights, void* stream,
+                            int32_t* forward_mode);
+
 /* Gradients (BACKWARD::renderCUDA backward.cu:17-532).  The six outputs must be
  * zero-filled by the caller (the reference's zeros_like, render.cu:313-318):
  * dL_dverts (P,3), dL_dverts_color (P,3), dL_dfaces_opacity (F),
@@ -279,6 +296,11 @@ typedef struct dm2_layer_composite_desc {
 
 int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
                          int32_t* out_n_contrib, void* stream);
+/* dm2_layers_composite with one more output: out_face_weights (B,F) float32, zero-filled by the caller; every blend adds
+ * alpha * T (faces_opacity[f] times the transmittance in front of the layer) to out_face_weights[b * F + f] -- a face listed
+ * twice in one pixel's layers counts twice.  Float atomics.  NULL: exactly dm2_layers_composite. */
+int dm2_layers_composite_weights(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
+                                 int32_t* out_n_contrib, float* out_face_weights, void* stream);
 /* Gradients of the composite w.r.t. verts_color (P,3), faces_opacity (F), verts_ndc (B,P,3; only z written) and
  * faces_intense (B,F); the four outputs must be zero-filled by the caller.  No gradient reaches verts through the
  * barycentrics (the layers are piecewise constant in the points) and none reaches background.  n_contrib: what the
