@@ -121,6 +121,8 @@ EXPORTS = {
                                           _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_prepare_faces": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp]),
     "dm2_prepare_faces_backward": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_prepare_faces_camera_scratch_bytes": (_sz, [_i32, _i32]),
+    "dm2_prepare_faces_backward_camera": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_exchange_mark": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dm2_exchange_pack": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_exchange_unpack": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
@@ -839,8 +841,10 @@ def prepare_faces(verts, faces, mv, proj, width, height, tables=True):
     return tuple(outs)
 
 
-def prepare_faces_backward(verts, faces, mv, proj, width, height, g_verts_ndc=None, g_verts_image=None, g_aa_face_verts=None):
-    """d(verts) (P,3) through the fused host prep (dm2_prepare_faces_backward)."""
+def prepare_faces_backward(verts, faces, mv, proj, width, height, g_verts_ndc=None, g_verts_image=None, g_aa_face_verts=None,
+                           need_verts=True, need_camera=False):
+    """d(verts) (P,3) through the fused host prep (dm2_prepare_faces_backward).  With ``need_camera=True``: (d(verts) or None
+    when ``need_verts=False``, d(mv) (B,4,4), d(proj) (B,4,4)) -- dm2_prepare_faces_backward_camera."""
     lib = load_library()
     keep = []
     d, dev = _prep_desc(verts, faces, mv, proj, width, height, keep)
@@ -853,12 +857,23 @@ def prepare_faces_backward(verts, faces, mv, proj, width, height, g_verts_ndc=No
             g = _c(g, f32)
             _require_gpu(verts, g)
         gs.append(g)
+    need_verts = bool(need_verts) or not need_camera
     scratch = torch.empty((d.B * d.P * 2,), dtype=f32, device=dev) if gs[2] is not None else None
-    out = torch.empty((d.P, 3), dtype=f32, device=dev)
+    out = torch.empty((d.P, 3), dtype=f32, device=dev) if need_verts else None
+    if not need_camera:
+        with torch.cuda.device(dev):
+            if lib.dm2_prepare_faces_backward(ctypes.byref(d), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(scratch), _ptr(out),
+                                              _stream(dev)):
+                raise _err(lib, "dm2_prepare_faces_backward")
+        return out
+    g_mv = torch.empty((d.B, 4, 4), dtype=f32, device=dev)
+    g_proj = torch.empty((d.B, 4, 4), dtype=f32, device=dev)
+    cam = _bytes(dev, lib.dm2_prepare_faces_camera_scratch_bytes(d.B, d.P))
     with torch.cuda.device(dev):
-        if lib.dm2_prepare_faces_backward(ctypes.byref(d), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(scratch), _ptr(out), _stream(dev)):
-            raise _err(lib, "dm2_prepare_faces_backward")
-    return out
+        if lib.dm2_prepare_faces_backward_camera(ctypes.byref(d), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(scratch), _ptr(out),
+                                                 _ptr(g_mv), _ptr(g_proj), _ptr(cam), _stream(dev)):
+            raise _err(lib, "dm2_prepare_faces_backward_camera")
+    return out, g_mv, g_proj
 
 
 def debug_fetch(what, count, aux, num_rendered, scratch, dtype, n):

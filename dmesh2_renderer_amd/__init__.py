@@ -140,6 +140,11 @@ class Renderer(torch.nn.Module):
     ``mv``/``proj`` are (Bcam,4,4) column-vector matrices applied as row
     vectors (``v @ mv^T @ proj^T``).  One primary ray per pixel centre is
     precomputed for every camera at construction.
+
+    Cameras that require grad get it, as in the reference: through the projection of ``verts`` (``verts_ndc``, the AA
+    corners from ``verts_image``) on every host prep -- the fused one (dm2_prepare_faces_backward_camera) and the
+    reference-shaped torch ops.  The per-pixel rays are constants: built once at construction, they get no gradient and
+    are not refreshed when ``mv`` / ``proj`` change afterwards.
     """
 
     def __init__(self, mv, proj, width, height, device, aa_grad_buffer_size=20, fused_prep=None, analytic_rays=False,
@@ -166,11 +171,14 @@ class Renderer(torch.nn.Module):
         self.num_batch = mv.shape[0]
         self.ray_o = None
         self.ray_d = None
-        if getattr(self, "analytic_rays", False):
-            self.ray_cam = torch.cat((torch.inverse(mv).reshape(-1, 16), torch.inverse(proj).reshape(-1, 16)), dim=1) \
-                .to(device=device, dtype=torch.float32).contiguous()
-        else:
-            self._init_rays()
+        # the rays are constants of the op, as in the reference (which returns no gradient for them): built without an autograd
+        # graph, so that cameras that require grad do not tie every step's backward to a graph of the constructor
+        with torch.no_grad():
+            if getattr(self, "analytic_rays", False):
+                self.ray_cam = torch.cat((torch.inverse(mv).reshape(-1, 16), torch.inverse(proj).reshape(-1, 16)), dim=1) \
+                    .to(device=device, dtype=torch.float32).contiguous()
+            else:
+                self._init_rays()
 
     # -- rays ------------------------------------------------------------------
     def _init_rays(self):
@@ -442,7 +450,8 @@ class LayeredRenderer(Renderer):
         holes included); faces_intense (B,F) of the selected views.  A layer blends where the pixel's ray hits its face
         inside the triangle, with Renderer's colour, depth and alpha at aa_temperature 0 (LayeredCompositeFunction).
         Gradients reach verts_color, faces_opacity, faces_intense, and verts through the projected depth only (as in
-        Renderer); none goes through the barycentrics, in which the layers are piecewise constant.
+        Renderer); none goes through the barycentrics, in which the layers are piecewise constant.  Cameras that require
+        grad get theirs the same way, through verts_ndc z.
         """
         mv = self.mv[batch_mvp_idx]
         proj = self.proj[batch_mvp_idx]

@@ -501,8 +501,22 @@ int dm2_prepare_faces_backward(const dm2_prep_desc* d, const float* g_verts_ndc,
                                const float* g_aa_face_verts, float* image_grad_scratch, float* g_verts, void* stream) {
     if (check_prep_desc(d)) return 1;
     if (d->P > 0 && !g_verts) return fail("g_verts must not be null");
-    if (g_aa_face_verts && d->F > 0 && d->B > 0 && d->P > 0 && !image_grad_scratch) return fail("image_grad_scratch must not be null");
-    dm2::launch_prepare_faces_backward(*d, g_verts_ndc, g_verts_image, g_aa_face_verts, image_grad_scratch, g_verts, (hipStream_t)stream);
+    return dm2_prepare_faces_backward_camera(d, g_verts_ndc, g_verts_image, g_aa_face_verts, image_grad_scratch, g_verts, nullptr,
+                                             nullptr, nullptr, stream);
+}
+
+size_t dm2_prepare_faces_camera_scratch_bytes(int32_t B, int32_t P) { return dm2::prepare_camera_scratch_bytes(B, P); }
+
+int dm2_prepare_faces_backward_camera(const dm2_prep_desc* d, const float* g_verts_ndc, const float* g_verts_image,
+                                      const float* g_aa_face_verts, float* image_grad_scratch, float* g_verts, float* g_mv,
+                                      float* g_proj, void* camera_scratch, void* stream) {
+    if (check_prep_desc(d)) return 1;
+    const bool camera = (g_mv || g_proj) && d->B > 0;
+    if (g_aa_face_verts && d->F > 0 && d->B > 0 && d->P > 0 && (g_verts || camera) && !image_grad_scratch)
+        return fail("image_grad_scratch must not be null");
+    if (camera && dm2::prepare_camera_scratch_bytes(d->B, d->P) > 0 && !camera_scratch) return fail("camera_scratch must not be null");
+    dm2::launch_prepare_faces_backward(*d, g_verts_ndc, g_verts_image, g_aa_face_verts, image_grad_scratch, g_verts, g_mv, g_proj,
+                                       (double*)camera_scratch, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }

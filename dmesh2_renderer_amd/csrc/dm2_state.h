@@ -180,8 +180,11 @@ int launch_render_forward(const dm2_render_desc& d, const uint2* ranges, const u
                           float* out_color, float* out_depth, int32_t* out_tri_cnt, const BinningState& bs, bool use_pool,
                           float pairs_per_entry, float* face_weights, hipStream_t st);
 void launch_prepare_faces(const dm2_prep_desc& d, hipStream_t st);
+// g_verts, g_mv, g_proj: each may be NULL; camera_scratch: prepare_camera_scratch_bytes(B, P) when g_mv or g_proj is not
 void launch_prepare_faces_backward(const dm2_prep_desc& d, const float* g_ndc, const float* g_image, const float* g_aa,
-                                   float* image_grad_scratch, float* g_verts, hipStream_t st);
+                                   float* image_grad_scratch, float* g_verts, float* g_mv, float* g_proj, double* camera_scratch,
+                                   hipStream_t st);
+size_t prepare_camera_scratch_bytes(int B, int P);
 void launch_render_forward_queue(const dm2_render_desc& d, const uint2* ranges, const uint32_t* face_list, ImageState is,
                                  float* out_color, float* out_depth, int32_t* out_tri_cnt, uint64_t* hit_masks,
                                  uint32_t* hit_valid, float* pool, int64_t pool_cap, uint32_t* hit_base, bool classes,

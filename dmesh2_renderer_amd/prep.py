@@ -8,8 +8,10 @@ The reference prepares the op's inputs in Python with ~20 torch kernels -- proje
 
 Results: the six tables are bit-identical to the torch twin's for the same ``verts_image``;
 ``verts_ndc`` / ``verts_image`` agree to fp32 rounding of a 4x4 product (the reference's own value
-depends on the BLAS it runs on).  Gradients reach ``verts`` through ``verts_ndc``, ``verts_image``
-and ``aa_face_verts`` exactly as in the reference, where the other five tables are constants too.
+depends on the BLAS it runs on).  Gradients reach ``verts`` and the camera matrices ``mv`` / ``proj``
+through ``verts_ndc``, ``verts_image`` and ``aa_face_verts`` as in the reference, where the other five
+tables are constants too.  The camera gradients (dm2_prepare_faces_backward_camera) are computed only
+when ``mv`` or ``proj`` requires grad; without that the backward launches the kernels it always has.
 
 Opt-in: ``Renderer(..., fused_prep=True)`` (default: the reference-shaped torch prep).
 """
@@ -41,18 +43,24 @@ class _Prepare(torch.autograd.Function):
         verts, faces, mv, proj = ctx.saved_tensors
         if g_ndc is None and g_image is None and g_aav is None:
             return None, None, None, None, None, None, None
-        g = _C.prepare_faces_backward(verts, faces, mv, proj, ctx.size[0], ctx.size[1],
-                                      g_verts_ndc=g_ndc, g_verts_image=g_image, g_aa_face_verts=g_aav)
-        return g, None, None, None, None, None, None
+        need_verts, need_mv, need_proj = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        kw = dict(g_verts_ndc=g_ndc, g_verts_image=g_image, g_aa_face_verts=g_aav)
+        if not (need_mv or need_proj):
+            g = _C.prepare_faces_backward(verts, faces, mv, proj, ctx.size[0], ctx.size[1], **kw)
+            return g, None, None, None, None, None, None
+        g, g_mv, g_proj = _C.prepare_faces_backward(verts, faces, mv, proj, ctx.size[0], ctx.size[1], need_verts=need_verts,
+                                                    need_camera=True, **kw)
+        return g, None, g_mv if need_mv else None, g_proj if need_proj else None, None, None, None
 
 
 def prepare(verts, faces, mv, proj, width, height):
     """verts (P,3) f32, faces (F,3) i32, mv/proj (B,4,4) of the selected cameras, full image size ->
     (verts_ndc, verts_image, aa_face_verts, aa_face_edges, aa_face_edges_iszero, aa_face_edges_recip,
-    aa_face_edges_normal, aa_face_edges_normal_c), differentiable w.r.t. ``verts``."""
+    aa_face_edges_normal, aa_face_edges_normal_c), differentiable w.r.t. ``verts``, ``mv`` and ``proj``."""
     return _Prepare.apply(verts, faces, mv, proj, width, height, True)
 
 
 def project(verts, faces, mv, proj, width, height):
-    """Projection only (LayeredRenderer.generate): -> (verts_ndc, verts_image)."""
+    """Projection only (LayeredRenderer.generate / render, Renderer's tables-from-image path): -> (verts_ndc, verts_image),
+    differentiable w.r.t. ``verts``, ``mv`` and ``proj``."""
     return _Prepare.apply(verts, faces, mv, proj, width, height, False)

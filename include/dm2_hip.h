@@ -347,6 +347,20 @@ int dm2_prepare_faces(const dm2_prep_desc* d, void* stream);
 int dm2_prepare_faces_backward(const dm2_prep_desc* d, const float* g_verts_ndc, const float* g_verts_image,
                                const float* g_aa_face_verts, float* image_grad_scratch, float* g_verts,
                                void* stream);
+/* dm2_prepare_faces_backward that can also return the gradients of the camera matrices: g_mv and g_proj (B,4,4) row-major,
+ * overwritten, of the projection `hom @ mv^T @ proj^T` -> |w| clamp -> NDC -> image units, i.e. per view b
+ *   g_proj[b][j][k] = sum_p gc_j t_k,   g_mv[b][j][k] = sum_p gt_j hom_k,
+ * with hom = (x, y, z, 1), t = mv_b . hom, gc the gradient of the clip point (gc[3] = 0 where the clamp fired) and
+ * gt = proj_b^T . gc.  g_verts, g_mv and g_proj may each be NULL (NULL g_verts: d(verts) is not computed; P = 0 or no
+ * upstream gradient: zeros).  camera_scratch: dm2_prepare_faces_camera_scratch_bytes(B, P) bytes of caller scratch
+ * (= B * min(ceil(P / 256), 1024) * 256), read only when g_mv or g_proj is non-NULL.  No float atomics on the camera route:
+ * two calls with the same inputs give the same bits (the aa_face_verts route feeds it through the per-vertex scatter of
+ * image_grad_scratch, whose float atomics add a vertex's corners in no fixed order).  With g_mv = g_proj = NULL this is
+ * dm2_prepare_faces_backward, to the bit. */
+size_t dm2_prepare_faces_camera_scratch_bytes(int32_t B, int32_t P);
+int dm2_prepare_faces_backward_camera(const dm2_prep_desc* d, const float* g_verts_ndc, const float* g_verts_image,
+                                      const float* g_aa_face_verts, float* image_grad_scratch, float* g_verts, float* g_mv,
+                                      float* g_proj, void* camera_scratch, void* stream);
 
 /* Device side of the sparse leaf-gradient exchange of a frame sharded by tile rows over N ranks (the
  * collectives themselves belong to the caller: dmesh2_renderer_amd/sharding.py drives torch.distributed / RCCL).  Rows are
