@@ -23,7 +23,7 @@
 // (|e| < 1e-3, crossings with the parallel pixel lines are ignored, pyrenderer.py:14) that straddles such a line -- and,
 // though the polygon is right there, a nearly axis-parallel edge (|e| < 1/64) straddling such a line, whose crossing's
 // Jacobian amplifies the rounding of the corner coordinates by 1/|e| (so that no regrouping reproduces it).
-// Those pairs are recognised by distance tests with a margin of 16-32 ulp of the image coordinate (`tie`), take no
+// Those pairs are recognised by distance tests with a margin of 16-32 ulp of the largest coordinate of the pair (`tie`), take no
 // gradient here and are handed to the reference's own clipper (tri_pix_overlap_area, dm2_device_math.h) by the caller: 1-5 % of the pairs of a
 // 1080p frame.  tests/test_gpu_clippers.py (variant 4) holds every pair that is NOT flagged to the oracle's Jacobian
 // on the reference's vectors, on random pairs and on the exact-tie stress sets.
@@ -32,7 +32,12 @@
 
 namespace dm2 {
 
-// margin of the tie tests: 2^-19 of the larger pixel coordinate = 16..32 ulp of an image coordinate there
+// margin of the tie tests: 2^-19 of the largest coordinate of the pair, the pixel's or a triangle corner's = 16..32 ulp of it.
+// The rounding the tests have to cover -- of the corner coordinates p0 + t e, of the crossing parameters (w - p0) r and of the
+// reference's corner classification through normal_c -- grows with the triangle's coordinates: a corner 1e4 .. 1e7 px off
+// screen (a face through the side of the frustum near the camera, a vertex whose |w| the projection clamped) gives O(1)
+// Jacobian errors on unflagged pairs under a margin scaled by the pixel alone (tests/test_gpu_clippers.py far pairs).  From
+// ~1e6 px on the margin exceeds a pixel: every partially covered pair of such a face goes to the exact clipper.
 constexpr float FAST_TIE_REL = 1.0f / 524288.0f;
 // an edge with a component below this (the "iszero" ones, |e| < 1e-3, among them) whose end lies within it of a pixel line of
 // that axis: the edge may straddle the line.  Above 1e-3 the reference does clip there, but its Jacobian of that crossing has
@@ -103,7 +108,8 @@ template <class Face>
 __device__ __forceinline__ void fast_area_grad(const Face& f, float pxmin, float pxmax, float pymin, float pymax, float* g, bool& tie) {
 #pragma unroll
     for (int k = 0; k < 6; k++) g[k] = 0.f;
-    const float delta = fmaxf(pxmax, pymax) * FAST_TIE_REL;
+    const float vmax = fmaxf(fmaxf(fmaxf(fabsf(f.v[0]), fabsf(f.v[1])), fmaxf(fabsf(f.v[2]), fabsf(f.v[3]))), fmaxf(fabsf(f.v[4]), fabsf(f.v[5])));
+    const float delta = fmaxf(fmaxf(pxmax, pymax), vmax) * FAST_TIE_REL;
     tie = false;
     fast_edge<0>(f, pxmin, pxmax, pymin, pymax, delta, g, tie);
     fast_edge<1>(f, pxmin, pxmax, pymin, pymax, delta, g, tie);

@@ -3,7 +3,8 @@
 random image sizes, triangle counts, depth complexity, temperature, K, cameras, patch windows and opacities.
 Forward must be bit-exact, gradients within 1e-5 relative L_inf.  `python tests/fuzz_parity.py [seconds] [seed]`.
 A development tool (needs a GPU); the fixed cases of tests/test_gpu_parity.py are the gate.
-DM2_FUZZ_TEMP0=1: temperature 0 only.  DM2_FUZZ_FROM_IMAGE=1: the AA tables built by the op from verts_image."""
+DM2_FUZZ_TEMP0=1: temperature 0 only.  DM2_FUZZ_FROM_IMAGE=1: the AA tables built by the op from verts_image.
+DM2_FUZZ_FAR=1: one to three vertices of each case moved 1e2 .. 1e7 px off screen (tests/far.py has why)."""
 import contextlib
 import os
 import sys
@@ -43,6 +44,16 @@ def one_case(seed, idx, verbose=False):
     pw, ph = int(rng.integers(1, W + 1)), int(rng.integers(1, H + 1))
     pm = [[int(rng.integers(0, W - pw + 1)), int(rng.integers(0, H - ph + 1))] for _ in bidx]
     desc = dict(W=W, H=H, F=F, dc=dc, temp=temp, K=K, cams=cams, bidx=bidx, pw=pw, ph=ph, pm=pm)
+    if os.environ.get("DM2_FUZZ_FAR") == "1":            # (without it the sweep draws and renders the scenes it always has)
+        nf = int(rng.integers(1, 4))
+        vid = rng.integers(0, sc.verts.shape[0], size=nf)
+        dist, th = 10.0 ** rng.uniform(2, 7, size=nf), rng.uniform(0, 2 * np.pi, size=nf)
+        v = sc.verts.numpy().astype(np.float64)
+        depth = scenes.CAM_DIST - v[vid, 2]                      # (the first camera's view depth)
+        v[vid, 0] += dist * np.cos(th) * 2.0 / W * depth * (W / H) * scenes.TAN_HALF_FOV
+        v[vid, 1] += dist * np.sin(th) * 2.0 / H * depth * scenes.TAN_HALF_FOV
+        sc.verts = torch.from_numpy(v.astype(np.float32))
+        desc["far"] = [float(x) for x in dist]
     args, _ = capture_forward_args(sc, bidx, pm, pw, ph, temp, K)
     dargs = [a.cuda() if torch.is_tensor(a) else a for a in args]
     # DM2_FUZZ_FROM_IMAGE=1: the same sweep with the AA tables built by the plan from verts_image (placeholder tables, as
@@ -81,15 +92,18 @@ def one_case(seed, idx, verbose=False):
         a64 = to_numpy_args(args)
         r64 = orc.render_forward_cuda(*a64, dtype=np.float64, nthreads=orc.max_threads())
         g64 = orc.render_backward_cuda(r64, gc.astype(np.float64), gd.astype(np.float64), nthreads=orc.max_threads())
-        e_hip = max(rel_linf(x.cpu().numpy(), g64[n]) for x, n in zip(g, GRAD_NAMES))
-        e_orc = max(rel_linf(gref[n], g64[n]) for n in GRAD_NAMES)
+        # per tensor: an ill-conditioned sum in one tensor (a face's opacity over thousands of pixels) must not excuse an error
+        # in another
+        e_hip_t = {n: rel_linf(x.cpu().numpy(), g64[n]) for x, n in zip(g, GRAD_NAMES)}
+        e_orc_t = {n: rel_linf(gref[n], g64[n]) for n in GRAD_NAMES}
+        e_hip, e_orc = max(e_hip_t.values()), max(e_orc_t.values())
         desc = dict(desc, vs_f32_oracle=worst, hip_vs_f64=e_hip, f32_oracle_vs_f64=e_orc, idx=idx)
         # accepted when the error is summation-order noise.  Exact criterion (small patches): per element within 1e-5 of the
         # tensor's maximum + 8 eps32 * sum over pixels of |that pixel's contribution| (tests/test_gpu_coverage.py::
         # test_fuzz4_regression derives it on the one case this sweep ever flagged); large patches: the ratio to the fp32
         # oracle's own distance from fp64.  The TRUE e_hip stays in the returned worst value either way.
-        accepted = e_hip <= max(1e-5, 32.0 * e_orc)
-        if e_hip <= 1.5 * e_orc:
+        accepted = all(e_hip_t[n] <= max(1e-5, 32.0 * e_orc_t[n]) for n in GRAD_NAMES)
+        if all(e_hip_t[n] <= max(1e-5, 1.5 * e_orc_t[n]) for n in GRAD_NAMES):
             pass                      # no farther from the fp64 result than the reference-order fp32 computation itself
         elif len(bidx) == 1 and pw * ph <= 4096:
             from test_gpu_coverage import per_pixel_terms_f64

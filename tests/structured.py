@@ -17,6 +17,7 @@ import functools
 import numpy as np
 import torch
 
+import far
 from util import capture_forward_args, scenes
 
 
@@ -119,6 +120,25 @@ def _degenerate_faces(layer, rng, n, ox, oy, w, h):
         layer.add(tri, rng.uniform(2.5, 3.2), [(0, 1, 2)])
 
 
+def _far_faces(layer, rng, n, w, h):
+    """Scene "far"'s faces: one or two corners in or next to a pixel of the frame, the others 1e2 to 1e7 px outside it in every
+    direction -- tests/far.py's constructions (wedges, slivers, long edges exactly through a pixel corner or a few ulp off it,
+    near corners on pixel lines, long nearly axis-parallel edges) around random pixels.  One in eight may cross the frame;
+    the others point out of it from near its border (at most 150 of its pixels in the face's bounding box: the pair count of
+    bbox_pairs stays small)."""
+    made = 0
+    while made < n:
+        kind = far.KINDS[made % len(far.KINDS)]
+        reach = far.REACHES[(made // len(far.KINDS)) % len(far.REACHES)]
+        pm = np.array([rng.randint(0, w), rng.randint(0, h)], np.float64)
+        tri = far.far_triangle(rng, pm, reach, kind).astype(np.float64)
+        lo = np.maximum(np.floor(tri.min(axis=0)), 0); hi = np.minimum(np.floor(tri.max(axis=0)), [w - 1, h - 1])
+        if np.prod(np.maximum(hi - lo + 1, 0)) > (w * h if made % 8 == 0 else 150):
+            continue
+        layer.add(tri, rng.uniform(2.5, 3.5), [(0, 1, 2)])
+        made += 1
+
+
 def _unproject(xy, z, W, H):
     """Image point (px, py) at view depth z -> world point, exactly as scenes.triangle_soup does (fp64, then fp32)."""
     t, aspect = scenes.TAN_HALF_FOV, W / H
@@ -149,6 +169,12 @@ def _geometry(name):
         nlat = L.n
         _iszero_faces(L, rng, 400, 3760, 2004, 48, 40)
         views, pw, ph = [(3700, 2000), (3756, 2006)], 56, 44
+    elif name == "far":
+        # faces through the frame's sides with corners 1e2 .. 1e7 px away, over a backdrop grid
+        W, H = 64, 48
+        grid(L, -1, -1, 17, 13, 4.0, 3.45)
+        nlat = L.n
+        _far_faces(L, rng, 300, W, H)
     elif name == "degenerate":
         W, H = 40, 32
         _degenerate_faces(L, rng, 500, 0, 0, W, H)
@@ -168,9 +194,10 @@ def _geometry(name):
     return dict(W=W, H=H, xy=xy, z=z, faces=faces, views=views, pw=pw or W, ph=ph or H, nlat=len(xy) if nlat is None else nlat)
 
 
-EXACT = ["grid", "subpixel", "iszero", "large", "degenerate", "coplanar"]
+EXACT = ["grid", "subpixel", "iszero", "large", "degenerate", "coplanar", "far"]
 ALL = EXACT + ["projected"]
-LATTICE = {"grid": 0.5, "subpixel": 0.25, "large": 0.5, "degenerate": 0.5, "coplanar": 0.5, "projected": 0.5}   # (None: iszero)
+LATTICE = {"grid": 0.5, "subpixel": 0.25, "large": 0.5, "degenerate": 0.5, "coplanar": 0.5, "projected": 0.5,
+           "far": 0.5}   # (None: iszero; far: its backdrop)
 
 
 def scene(name):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import far
 from util import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -222,11 +223,12 @@ def _check_fast(g, o_area, o_grad, o_code, max_tie_fraction=None, min_ok=10):
     ok = live & ~tie
     assert ok.sum() >= min_ok, ok.sum()
     err = _grad_err(grad, o_grad)
-    assert err[ok].max() <= FAST_GRAD_TOL, (err[ok].max(), np.where(ok & (err > FAST_GRAD_TOL))[0][:10])
+    worst = err[ok].max() if ok.any() else 0.0
+    assert worst <= FAST_GRAD_TOL, (worst, np.where(ok & (err > FAST_GRAD_TOL))[0][:10])
     if max_tie_fraction is not None:
         assert tie[live].mean() <= max_tie_fraction, tie[live].mean()
     # and the ties go to the generic clipper (k_aa_ties), bit-equal to the oracle above
-    return tie[live].mean(), err[ok].max()
+    return tie[live].mean(), worst
 
 
 @pytest.mark.parametrize("name", ["aa_pairs.npz", "aa_error_pairs.npz"])
@@ -274,6 +276,43 @@ def _axis_pairs(seed, n):
         tris[it] = tri
         pms[it] = np.floor(o + rng.uniform(-1, 6, 2))
     return tris, pms
+
+
+@pytest.mark.parametrize("reach", far.REACHES)
+def test_clippers_far_pairs(reach):
+    """Triangles with one or two corners ~reach px away (tests/far.py: random directions, negative coordinates, tested pixels
+    near the origin and at 1080p / 4K magnitudes), general and stress constructions: long edges exactly through a pixel corner
+    or a few ulp of the far coordinate off it, a near corner on a pixel line or 1 ulp off it, long nearly axis-parallel edges.
+    The rounding of the corner coordinates, crossing parameters and normal_c grows with the far corner here, so the tie
+    margin of the polygon-free Jacobian has to (dm2_clip_fast.h): every pair it does not flag still has the oracle's."""
+    from oracle import cpu as orc
+    tris, pms, kind = far.far_pairs(int(np.log10(reach)) * 1000 + 7, 10000, reach)
+    with np.errstate(all="ignore"):
+        t = orc.aa_tables(tris, np.float32, reorder=True)
+    g = dict(t_verts=t["verts"], t_edges=t["edges"], t_edges_iszero=t["iszero"], t_edges_recip=t["recip"],
+             t_edges_normal=t["normal"], t_edges_normal_c=t["normal_c"], pixmin=pms)
+    with np.errstate(all="ignore"):
+        o_area, o_grad, o_code = _oracle_run(g)
+    live = (o_code == 0) & (o_area != 0)
+    partial = live & (o_area < 1)
+    for k, name in enumerate(far.KINDS):            # no construction can pass empty (most exact corner crossings make the reference raise)
+        assert (partial & (kind == k)).sum() >= (15 if name == "corner" else 300), (name, (partial & (kind == k)).sum())
+    for variant in (0, 1, 2, 3):
+        area, grad, code = _device_run(g, variant)
+        assert np.array_equal(code != 0, o_code != 0), variant
+        if variant in (0, 1):
+            assert np.array_equal(area.view(np.uint32), o_area.view(np.uint32)), variant
+            if variant == 0:
+                assert np.array_equal(grad.view(np.uint32), o_grad.view(np.uint32))
+        else:
+            if variant == 3:
+                assert np.array_equal(area[live].view(np.uint32), o_area[live].view(np.uint32)), np.abs(area - o_area)[live].max()
+            assert np.abs(area - o_area).max() <= SEG_AREA_TOL, (variant, np.abs(area - o_area).max())
+            assert _grad_err(grad, o_grad)[live].max() <= SEG_GRAD_TOL, (variant, _grad_err(grad, o_grad)[live].max())
+    # (at 1e6 px and beyond the margin exceeds a pixel: every partially covered pair of such a face is a tie)
+    frac, worst = _check_fast(g, o_area, o_grad, o_code, min_ok=500 if reach <= 1e4 else 0)
+    print(f"fast Jacobian, corners ~{reach:.0e} px away: {int(partial.sum())} partially covered live pairs, ties {frac:.1%}, "
+          f"worst error of the others {worst:.2e}")
 
 
 def test_fast_jacobian_axis_parallel_and_ties():

@@ -17,6 +17,7 @@ FLOORS = {
     "large": dict(tie=0.3, iszero=10000, errors=15000),
     "degenerate": dict(tie=0.7, iszero=800, errors=4000),
     "coplanar": dict(tie=0.2, iszero=3000, errors=8000),
+    "far": dict(tie=0.09, iszero=800, errors=5000),              # (0.11 exact ties, mostly the backdrop's)
 }
 
 
@@ -55,6 +56,16 @@ def test_scene_properties(name):
         assert (e == 0).sum() >= 100 and ((e > 0) & (e < 1e-3)).sum() >= 200 and ((e >= 1e-3) & (e < 1.6e-3)).sum() >= 100
     if name == "large":
         assert vi.shape[0] == 2 and (vi[..., 0] >= 3690).all() and (vi[..., 1] >= 1990).all() and (args[1].numpy() >= [3700, 2000]).all()
+    if name == "far":
+        # corners far outside the 64 x 48 frame in every direction, the faces binned in the frame (bbox pairs), few pairs
+        W, H = g["W"], g["H"]
+        out = np.maximum(np.maximum(-vi[0, :, 0], vi[0, :, 0] - W), np.maximum(-vi[0, :, 1], vi[0, :, 1] - H))
+        assert (out > 5e3).sum() >= 150 and (out > 1e5).sum() >= 150 and (out > 5e6).sum() >= 60
+        x, y = vi[0, :, 0], vi[0, :, 1]
+        for side in (x < -1e5, x > W + 1e5, y < -1e5, y > H + 1e5):          # past every side of the frame
+            assert side.sum() >= 20
+        assert len(b) <= 150_000
+        assert len(np.unique(f[live & (out[args[5].numpy()[f]].max(axis=1) > 1e5)])) >= 100
     if name == "degenerate":
         v = args[12].numpy()
         a2 = (v[..., 1, 0] - v[..., 0, 0]) * (v[..., 2, 1] - v[..., 0, 1]) - (v[..., 2, 0] - v[..., 0, 0]) * (v[..., 1, 1] - v[..., 0, 1])
