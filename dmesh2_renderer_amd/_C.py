@@ -12,6 +12,10 @@ and the consumer of those layers the reference does not have (LayeredRenderer.re
 
     composite_layers_cuda(...10 args...) -> 4-tuple, composite_layers_backward_cuda(...13 args...) -> 4-tuple
 
+and the per-pixel nearest hits of any triangle mesh (Renderer.rasterize):
+
+    rasterize_layers_cuda(...10 args...) -> 4-tuple, rasterize_layers_backward_cuda(...7 args...) -> dL/dverts
+
 Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
 its gradient as the keyword ``dL_dout_alpha``.  Under ``face_weights_output`` render_forward_cuda and composite_layers_cuda
 append the per-face blend weights (B,F), behind everything else they return; they have no gradient.
@@ -107,6 +111,8 @@ EXPORTS = {
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_plan": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _sz, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "dm2_layers_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "dm2_rasterize_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_rasterize_backward": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -679,6 +685,123 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
             raise _err(lib, "generate_render_layers_cuda (run)")
     generate_render_layers_cuda.last_debug = (R, face_buf, bin_buf, img_buf)      # kept for tests
     return layers, cnt
+
+
+def _rasterize_desc(width, height, B, verts, faces, image_ray_o, image_ray_d, num_layers, keep, face_existence=None,
+                    verts_ndc=None, verts_image=None):
+    """Checks (in the style of generate_render_layers_cuda) + the dm2_layers_desc of a rasterize call (T = 0: no tets).
+    The backward passes no face_existence / verts_ndc / verts_image: it reads neither."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
+    bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
+    bad(face_existence is not None and (face_existence.dim() != 1 or face_existence.size(0) != faces.size(0)),
+        "face_existence must have dimensions (F,)")
+    bad(verts_ndc is not None and (verts_ndc.dim() != 3 or verts_ndc.size(2) != 3), "verts_ndc must have dimensions (B, P, 3)")
+    bad(verts_image is not None and (verts_image.dim() != 3 or verts_image.size(2) != 2), "verts_image must have dimensions (B, P, 2)")
+    bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
+    bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
+    num_layers = int(num_layers); width = int(width); height = int(height)
+    bad(num_layers < 0, "num_layers must be non-negative")
+    tensors = [t for t in (verts, faces, face_existence, verts_ndc, verts_image, image_ray_o, image_ray_d) if t is not None]
+    dev = _require_gpu(*tensors)
+    f32, i32 = torch.float32, torch.int32
+    P, F = verts.size(0), faces.size(0)
+    bad((verts_ndc is not None and tuple(verts_ndc.shape) != (B, P, 3)) or (verts_image is not None and tuple(verts_image.shape) != (B, P, 2)),
+        "verts_ndc/verts_image shape mismatch")
+    ana = _analytic(B, dev)
+    bad(ana is None and (tuple(image_ray_o.shape) != (B, height, width, 3) or tuple(image_ray_d.shape) != (B, height, width, 3)),
+        "image_ray_o/image_ray_d must have dimensions (B, H, W, 3)")
+    ts = dict(verts=_c(verts, f32), faces=_c(faces, i32), image_ray_o=_c(image_ray_o, f32), image_ray_d=_c(image_ray_d, f32))
+    for k, x, dt in (("face_existence", face_existence, i32), ("verts_ndc", verts_ndc, f32), ("verts_image", verts_image, f32)):
+        if x is not None:
+            ts[k] = _c(x, dt)
+    keep += list(ts.values())
+    d = LayersDesc()
+    d.B, d.P, d.F, d.T, d.W, d.H, d.L, d.flags = B, P, F, 0, width, height, num_layers, _flags
+    for k, t in ts.items():
+        setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
+    if ana is not None:
+        if (ana[1], ana[2]) != (width, height):
+            raise RuntimeError("analytic_rays: the image size differs from the rasterize call's width / height")
+        keep.append(ana[0])
+        d.flags |= DM2_FLAG_ANALYTIC_RAYS
+        d.ray_cam = ana[0].data_ptr()
+        d.image_ray_o = d.image_ray_d = None
+    return d, dev
+
+
+def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc, verts_image, image_ray_o, image_ray_d,
+                          num_layers):
+    """The first ``num_layers`` faces each pixel's ray hits, in (t, face id) order (include/dm2_hip.h: dm2_rasterize_run).
+
+    verts (P,3), faces (F,3) int32, face_existence (F) int32 or None (every face exists), verts_ndc (B,P,3), verts_image
+    (B,P,2) of the full frame (the plan's bins and depth cull), image_ray_o / image_ray_d (B,H,W,3) (placeholders under
+    ``analytic_rays``) -> (render_layers (B,H,W,L) int32, -1 = empty; render_layers_cnt (B,H,W) int32; bary (B,H,W,L,3) float32
+    = (1 - u - v, u, v); t (B,H,W,L) float32), -1 in every empty slot."""
+    lib = load_library()
+    keep: list = []
+    if verts_ndc is None or verts_ndc.dim() != 3 or verts_image is None:
+        raise RuntimeError("verts_ndc / verts_image must have dimensions (B, P, 3) / (B, P, 2)")
+    d, dev = _rasterize_desc(width, height, verts_ndc.size(0), verts, faces, image_ray_o, image_ray_d, num_layers, keep,
+                             face_existence=face_existence, verts_ndc=verts_ndc, verts_image=verts_image)
+    B, F, H, W, L = d.B, d.F, d.H, d.W, d.L
+    f32, i32 = torch.float32, torch.int32
+    N, Tn, BF = B * H * W, _tiles(B, W, H), B * F
+    if N == 0 or L == 0 or F == 0:
+        # nothing to walk: every slot empty (the kernels would write the same)
+        return (torch.full((B, H, W, L), -1, dtype=i32, device=dev), torch.zeros((B, H, W), dtype=i32, device=dev),
+                torch.full((B, H, W, L, 3), -1.0, dtype=f32, device=dev), torch.full((B, H, W, L), -1.0, dtype=f32, device=dev))
+    layers = torch.empty((B, H, W, L), dtype=i32, device=dev)            # (every slot written by the kernel)
+    cnt = torch.empty((B, H, W), dtype=i32, device=dev)
+    bary = torch.empty((B, H, W, L, 3), dtype=f32, device=dev)
+    t = torch.empty((B, H, W, L), dtype=f32, device=dev)
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn))
+        img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_IMAGE, N, Tn))
+        nr, longest = _i64(0), _i64(0)
+        if lib.dm2_layers_plan(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest)):
+            raise _err(lib, "rasterize_layers_cuda (plan)")
+        R = int(nr.value)
+        bin_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_BINNING, R, Tn))
+        if lib.dm2_rasterize_run(ctypes.byref(d), R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf),
+                                 bin_buf.numel(), _ptr(img_buf), img_buf.numel(), _ptr(layers), _ptr(cnt), _ptr(bary), _ptr(t), st):
+            raise _err(lib, "rasterize_layers_cuda (run)")
+    return layers, cnt, bary, t
+
+
+def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, image_ray_d, dL_dbary, dL_dt):
+    """Gradient of rasterize_layers_cuda's bary and t w.r.t. verts (dm2_rasterize_backward): render_layers (B,H,W,L) as the
+    forward returned them, the forward's verts / faces / rays, dL_dbary (B,H,W,L,3) and dL_dt (B,H,W,L), either may be None
+    -> dL_dverts (P,3).  Nothing flows through the rays or through which faces are listed."""
+    lib = load_library()
+    if render_layers.dim() != 4:
+        raise RuntimeError("render_layers must have dimensions (B, H, W, L)")
+    B, H, W, L = (int(x) for x in render_layers.shape)
+    keep: list = []
+    d, dev = _rasterize_desc(W, H, B, verts, faces, image_ray_o, image_ray_d, L, keep)
+    f32 = torch.float32
+    checks = []
+    if dL_dbary is not None:
+        checks.append((dL_dbary, (B, H, W, L, 3), "dL_dbary"))
+    if dL_dt is not None:
+        checks.append((dL_dt, (B, H, W, L), "dL_dt"))
+    for x, shape, nm in checks:
+        if tuple(x.shape) != shape:
+            raise RuntimeError(f"{nm} must have dimensions {shape}, got {tuple(x.shape)}")
+    _require_gpu(verts, render_layers, *[x for x, _, _ in checks])
+    rl = _c(render_layers, torch.int32)
+    gb = _c(dL_dbary, f32) if dL_dbary is not None else None
+    gt = _c(dL_dt, f32) if dL_dt is not None else None
+    dverts = torch.zeros((d.P, 3), dtype=f32, device=dev)
+    if B * H * W * L == 0 or d.F == 0 or (gb is None and gt is None):
+        return dverts
+    with torch.cuda.device(dev):
+        if lib.dm2_rasterize_backward(ctypes.byref(d), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts), _stream(dev)):
+            raise _err(lib, "rasterize_layers_backward_cuda")
+    return dverts
 
 
 def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,

@@ -6,6 +6,8 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
 * ``Renderer``        (reference :179-380) nn.Module: host prep (rays, projection, AA tables) + op
 * ``LayeredRenderer`` (reference :388-451) ``generate()`` -> (render_layers, render_layers_cnt), and (not in the
   reference) ``render()``: those layers composited into (color, depth), differentiable (``LayeredCompositeFunction``)
+* (not in the reference) ``Renderer.rasterize()``: the first L faces each pixel's ray hits on any triangle mesh, with
+  perspective-correct barycentrics and ray distance, differentiable w.r.t. the vertices (``RasterizeFunction``)
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -23,7 +25,7 @@ import torch
 from . import _C
 from .pyrenderer import Triangles
 
-__all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "Triangles"]
+__all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "Triangles"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -282,6 +284,39 @@ class Renderer(torch.nn.Module):
         return self._forward_with_rays(B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                                        verts_color, faces_opacity, faces_intense, background, aa_temperature)
 
+    def rasterize(self, batch_mvp_idx: Sequence[int], verts: torch.Tensor, faces: torch.Tensor, num_layers: int,
+                  faces_existence: torch.Tensor = None):
+        """The first ``num_layers`` faces each pixel's ray hits, over the full frame of every selected view (not in the
+        reference) -> render_layers (B,H,W,L) int32 face ids (-1 = empty), render_layers_cnt (B,H,W) int32, bary (B,H,W,L,3)
+        float32 = the weights of faces[f][0..2] at the hit (perspective-correct), t (B,H,W,L) float32 = the hit's distance
+        along the pixel's ray; -1 in every empty slot.
+
+        Candidates are the faces whose image bbox touches the pixel's 16x16 tile and whose NDC depth range meets [-1, 1]
+        (``faces_existence`` == 0 drops a face; None keeps all); a hit is the pixel's ray meeting the triangle (t >= 0,
+        barycentrics >= 0); hits are ordered by (t, face id).  render_layers can go straight to ``LayeredRenderer.render``.
+        bary and t are differentiable w.r.t. ``verts`` (``RasterizeFunction``); nothing flows through the rays (cameras get
+        no gradient here) or through which faces are listed.  Interpolate any per-vertex attribute in torch, e.g.
+        ``(bary[..., None] * verts_color[faces[ids.clamp(min=0)].long()]).sum(-2)``."""
+        mv = self.mv[batch_mvp_idx]
+        proj = self.proj[batch_mvp_idx]
+        i32, f32 = torch.int32, torch.float32
+        # the plan's bins and depth cull: constants of the op, like the rays
+        with torch.no_grad():
+            if getattr(self, "fused_prep", False) and verts.is_cuda:
+                from . import prep
+                verts_ndc, verts_image = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
+            else:
+                verts_ndc, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
+        fe = None if faces_existence is None else faces_existence.to(i32)
+        args = (verts.to(f32), faces.to(i32), fe, verts_ndc.to(f32), verts_image.to(f32))
+        if getattr(self, "analytic_rays", False):
+            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
+            ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
+            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
+                return RasterizeFunction.apply(*args, ph, ph, self.width, self.height, int(num_layers))
+        ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
+        return RasterizeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32), self.width, self.height, int(num_layers))
+
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
         f32 = torch.float32
@@ -396,6 +431,39 @@ class LayeredCompositeFunction(torch.autograd.Function):
                 render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
                 n_contrib, grad_color, grad_depth, **extra)
         return None, None, None, dcolor, dopacity, dintense, dndc, None, None, None
+
+
+class RasterizeFunction(torch.autograd.Function):
+    """The first L faces each pixel's ray hits (``_C.rasterize_layers_cuda``), differentiable in bary and t w.r.t. verts.
+
+    Inputs: verts (P,3)*, faces (F,3) int32, faces_existence (F) int32 or None, verts_ndc (B,P,3) and verts_image (B,P,2) (the
+    plan's bins and depth cull: no gradient), image_ray_o, image_ray_d (B,H,W,3) (placeholders under ``_C.analytic_rays``),
+    width, height, num_layers.  Outputs: render_layers (B,H,W,L) int32 and render_layers_cnt (B,H,W) int32 (not
+    differentiable), bary (B,H,W,L,3), t (B,H,W,L).  (* = receives a gradient.)
+
+    A listed hit sends (g1 - g0) du/dp + (g2 - g0) dv/dp + g_t dt/dp to its three vertices; empty slots send nothing.  When
+    neither bary nor t reaches the loss no backward kernel runs.
+    """
+
+    @staticmethod
+    def forward(ctx, verts, faces, faces_existence, verts_ndc, verts_image, image_ray_o, image_ray_d, width, height, num_layers):
+        ctx.analytic = getattr(_C._tls, "analytic", None)
+        ctx.set_materialize_grads(False)            # bary / t left out of the loss arrive as None
+        layers, cnt, bary, t = _C.rasterize_layers_cuda(width, height, verts.detach(), faces, faces_existence, verts_ndc.detach(),
+                                                        verts_image.detach(), image_ray_o, image_ray_d, num_layers)
+        ctx.mark_non_differentiable(layers, cnt)
+        ctx.save_for_backward(layers, verts.detach(), faces, image_ray_o, image_ray_d)
+        return layers, cnt, bary, t
+
+    @staticmethod
+    def backward(ctx, grad_layers, grad_cnt, grad_bary, grad_t):
+        if (grad_bary is None and grad_t is None) or not ctx.needs_input_grad[0]:
+            return (None,) * 10
+        layers, verts, faces, ray_o, ray_d = ctx.saved_tensors
+        ana = ctx.analytic
+        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))):
+            dverts = _C.rasterize_layers_backward_cuda(layers, verts, faces, ray_o, ray_d, grad_bary, grad_t)
+        return (dverts,) + (None,) * 9
 
 
 class LayeredRenderer(Renderer):

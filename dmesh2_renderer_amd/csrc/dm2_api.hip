@@ -424,6 +424,54 @@ int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_t
     return 0;
 }
 
+static int check_rasterize_inputs(const dm2_layers_desc* d) {
+    if (d->F > 0 && d->B > 0 && (!d->verts || !d->faces)) return fail("verts / faces must not be null");
+    if (!(d->flags & DM2_FLAG_ANALYTIC_RAYS) && d->B > 0 && (!d->image_ray_o || !d->image_ray_d))
+        return fail("image_ray_o / image_ray_d must not be null");
+    return 0;
+}
+
+int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries, void* face_scratch, size_t face_bytes,
+                      void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
+                      int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream) {
+    if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t BF = (int64_t)d->B * d->F, N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
+    if (N == 0) return 0;
+    if (!render_layers_cnt || (d->L > 0 && (!render_layers || !bary || !t))) return fail("rasterize outputs must not be null");
+    if (d->L == 0) {
+        DM2_HIP(hipMemsetAsync(render_layers_cnt, 0, (size_t)N * sizeof(int32_t), st));
+        return 0;
+    }
+    if (dm2_scratch_bytes(DM2_SCRATCH_LAYER_IMAGE, N, Tn) > image_bytes) return fail("image scratch too small");
+    dm2::LayerImageState ls = dm2::LayerImageState::carve(image_scratch, N, Tn);
+    dm2::FaceState fs{};
+    dm2::BinningState bs{};
+    if (BF != 0) {
+        if (dm2_scratch_bytes(DM2_SCRATCH_FACE, BF, 2 * Tn) > face_bytes) return fail("face scratch too small");
+        if (dm2_scratch_bytes(DM2_SCRATCH_BINNING, num_rendered, Tn) > binning_bytes) return fail("binning scratch too small");
+        fs = dm2::FaceState::carve(face_scratch, BF, Tn, dm2::scan_temp_bytes(BF), false);
+        bs = dm2::BinningState::carve(binning_scratch, num_rendered, dm2::sort_temp_bytes(num_rendered, Tn));
+        DM2_HIP(dm2::launch_bin_sort(d->B, d->F, d->W, d->H, num_rendered, max_tile_entries, (d->flags & DM2_FLAG_LEGACY_KERNELS) != 0,
+                                     fs.min_depths, fs, bs, ls.ranges, false, nullptr, st));
+    } else {
+        DM2_HIP(hipMemsetAsync(ls.ranges, 0, (size_t)Tn * sizeof(uint2), st));
+    }
+    dm2::launch_rasterize(*d, fs, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, st);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
+                           float* dL_dverts, void* stream) {
+    if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
+    if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0 || (!dL_dbary && !dL_dt)) return 0;   // nothing is listed or nothing flows
+    if (!render_layers || !dL_dverts) return fail("render_layers / dL_dverts must not be null");
+    dm2::launch_rasterize_backward(*d, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_composite_desc(const dm2_layer_composite_desc* d) {
     if (!d) return fail("null descriptor");
     if (d->B < 0 || d->P < 0 || d->F < 0 || d->W < 0 || d->H < 0 || d->L < 0) return fail("negative size in descriptor");

@@ -29,14 +29,13 @@
 #include <hip/hip_runtime.h>
 
 #include "dm2_device_math.h"
+#include "dm2_face_table.h"
 #include "dm2_stage.h"
 #include "dm2_state.h"
 
 namespace dm2 {
 
 constexpr int LC_REG = 8;          // layers of a chunk held in registers by the backward
-constexpr int LC_SLOTS = 512;      // LDS accumulator slots (distinct faces) per tile
-constexpr int LC_PROBES = 16;
 constexpr int LC_NCOMP = 14;       // d colour (3 vertices x 3 channels), d z (3), d opacity, d intensity
 constexpr int LC_DZ = 9, LC_OP = 12, LC_IN = 13;
 
@@ -66,18 +65,6 @@ __device__ __forceinline__ bool lc_layer(const dm2_layer_composite_desc& d, int 
     h.iD = i0 * z[3 * v0] + i1 * z[3 * v1] + i2 * z[3 * v2];
     h.alpha = d.faces_opacity[f];
     return true;
-}
-
-// slot of face f in the tile's table (inserted if new), -1 when LC_PROBES probes find neither f nor a free slot
-__device__ __forceinline__ int lc_slot(int* keys, int f) {
-    const uint32_t h = ((uint32_t)f * 2654435761u) >> 23;          // 9 bits: LC_SLOTS = 512
-#pragma unroll 1
-    for (int p = 0; p < LC_PROBES; p++) {
-        const int s = (int)((h + (uint32_t)p) & (LC_SLOTS - 1));
-        const int old = atomicCAS(&keys[s], -1, f);
-        if (old == -1 || old == f) return s;
-    }
-    return -1;
 }
 
 // one pixel of k_layer_composite (WEIGHTS: its blends' alpha * T into the block's table s_key / s_w)

@@ -1,0 +1,274 @@
+// dm2_rasterize.hip -- Renderer.rasterize: the L nearest hits of every pixel's ray on a triangle mesh (no tetrahedra):
+//   k_rasterize<KR>   per pixel the first L faces its ray hits in (t, face id) order, with barycentrics and t
+//   k_rasterize_bwd   d(bary, t)/d(verts) of the listed hits
+//
+// Contract (include/dm2_hip.h, dm2_rasterize_run): per pixel of view b the candidates are the faces of its tile's list
+// (dm2_layers_plan: the verts_image bbox touches the tile, the NDC depth cull keeps the face) whose face_existence is not 0;
+// a hit is ray_tri_intersection with t >= 0, u >= 0, v >= 0, u + v <= 1 (k_first_intersect's test); the hits are ordered by
+// ascending (t, face id) and the first L are listed with bary = (1 - u - v, u, v) and t.  -ffp-contract=off: bit-exact.
+//
+// Layout: one lane per pixel, 16 x 16 tiles, the view on blockIdx.z; list chunks staged in LDS as k_first_intersect stages
+// them, the existence filter applied (and the survivors compacted) while staging.  Each lane keeps its KR nearest hits so far
+// in registers, sorted; a new hit goes in by a fully unrolled compare-and-swap over the slots (static indices only: no
+// scratch).  KR = the smallest of 1, 2, 4, 8, 16 that holds L; L > 16 runs in passes of 16, each keeping only hits strictly
+// after the previous pass's last (t, id) -- carried in registers from pass to pass.
+//
+// Early exit (not part of the result): the tile list is sorted by min depth, so once a lane holds its slots full, a face
+// whose min depth lies beyond the largest max depth of the held faces cannot come nearer along this ray and the lane stops
+// (the K-wide form of k_first_intersect's stop, forward.cu:648-651).  Depth along a ray grows with t in front of the camera;
+// a face that crosses the camera plane has no such bound, as in the first-hit pass of generate.
+//
+// Backward: per listed slot the ray is intersected again and dL/dp_k = (g1 - g0) du/dp_k + (g2 - g0) dv/dp_k + g_t dt/dp_k,
+// in fp64 (rz_hit_grad), added into the per-block face table of dm2_face_table.h (fp64 slots), flushed as fp32 atomics.
+#include <hip/hip_runtime.h>
+
+#include "dm2_device_math.h"
+#include "dm2_face_table.h"
+#include "dm2_stage.h"
+#include "dm2_state.h"
+
+namespace dm2 {
+
+constexpr int RZ_CHUNK = TILE_PIX;  // list entries staged per round: one per lane
+constexpr int RZ_PASS = 16;         // the longest register list; L > 16 runs in passes of 16
+constexpr int RZ_NCOMP = 9;         // d verts: 3 vertices x 3 coordinates
+constexpr int RZ_NO_ID = 0x7FFFFFFF;
+
+struct __attribute__((aligned(16))) RzRec {
+    float v[9];
+    float min_d, max_d;
+    int face_id;
+};
+static_assert(sizeof(RzRec) == 48, "RzRec");
+
+// a lane's nearest hits so far, ascending (t, id); empty slots hold t = +inf, id = RZ_NO_ID, md = -inf
+template <int KR>
+struct RzList {
+    float t[KR], u[KR], v[KR], md[KR];
+    int id[KR];
+};
+
+__device__ __forceinline__ bool rz_before(float ta, int ia, float tb, int ib) { return ta < tb || (ta == tb && ia < ib); }
+
+// insert a hit into the first Lp slots (the one pushed out of slot Lp - 1 is dropped); slots Lp.. stay empty
+template <int KR>
+__device__ __forceinline__ void rz_insert(RzList<KR>& h, int Lp, float t, int id, float u, float v, float md) {
+#pragma unroll
+    for (int k = 0; k < KR; k++) {
+        const bool sw = k < Lp && rz_before(t, id, h.t[k], h.id[k]);
+        const float t0 = h.t[k], u0 = h.u[k], v0 = h.v[k], m0 = h.md[k];
+        const int i0 = h.id[k];
+        h.t[k] = sw ? t : t0; h.id[k] = sw ? id : i0; h.u[k] = sw ? u : u0; h.v[k] = sw ? v : v0; h.md[k] = sw ? md : m0;
+        t = sw ? t0 : t; id = sw ? i0 : id; u = sw ? u0 : u; v = sw ? v0 : v; md = sw ? m0 : md;
+    }
+}
+
+template <int KR>
+__global__ void __launch_bounds__(TILE_PIX)
+k_rasterize(dm2_layers_desc d, const float* __restrict__ min_depths, const float* __restrict__ max_depths,
+            const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list, int32_t* __restrict__ out_layers,
+            int32_t* __restrict__ out_cnt, float* __restrict__ out_bary, float* __restrict__ out_t) {
+    __shared__ RzRec recs[RZ_CHUNK];
+    __shared__ int s_kept[TILE_PIX / 64];
+    const int b = blockIdx.z;
+    const uint32_t gx = (d.W + TILE - 1) / TILE, gy = (d.H + TILE - 1) / TILE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
+    const bool inside = (px < (uint32_t)d.W) && (py < (uint32_t)d.H);
+    const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+    f3 ro = {0, 0, 0}, rd = {0, 0, 0};
+    if (inside) pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+    const uint32_t tile = ((uint32_t)b * gy + blockIdx.y) * gx + blockIdx.x;
+    const uint2 range = ranges[tile];
+    const int total = (int)(range.y - range.x);
+    const int L = d.L;
+    const int npass = KR < RZ_PASS ? 1 : (L + RZ_PASS - 1) / RZ_PASS;
+    bool exhausted = !inside;                 // no hit left behind the previous pass's last
+    float prev_t = 0.0f;
+    int prev_id = -1, listed = 0;
+    for (int pass = 0; pass < npass; pass++) {
+        const int Lp = min(KR, L - pass * RZ_PASS);
+        RzList<KR> h;
+#pragma unroll
+        for (int k = 0; k < KR; k++) { h.t[k] = __builtin_inff(); h.id[k] = RZ_NO_ID; h.u[k] = 0.f; h.v[k] = 0.f; h.md[k] = -__builtin_inff(); }
+        int cnt = 0;                          // hits held, <= Lp
+        float bound = -__builtin_inff();      // the largest max depth of the held hits, once cnt == Lp
+        bool done = exhausted;
+        for (int base = 0; base < total; base += RZ_CHUNK) {
+            if (__syncthreads_count(done) == TILE_PIX) break;
+            const int n = min(RZ_CHUNK, total - base);
+            int f = -1;
+            bool keep = false;
+            if (tid < n) {
+                f = (int)face_list[range.x + base + tid];
+                keep = !d.face_existence || d.face_existence[f] != 0;
+            }
+            // the chunk's existing faces, compacted in list order
+            const unsigned long long m = __ballot(keep);
+            if (lane == 0) s_kept[wave] = __popcll(m);
+            __syncthreads();
+            int before = 0, kept = 0;
+#pragma unroll
+            for (int w = 0; w < TILE_PIX / 64; w++) {
+                const int c = s_kept[w];
+                before += w < wave ? c : 0;
+                kept += c;
+            }
+            if (keep) {
+                RzRec& r = recs[before + __popcll(m & ((1ull << lane) - 1ull))];
+                r.face_id = f;
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    const int64_t vi = d.faces[3 * (int64_t)f + i];
+                    r.v[3 * i] = d.verts[3 * vi]; r.v[3 * i + 1] = d.verts[3 * vi + 1]; r.v[3 * i + 2] = d.verts[3 * vi + 2];
+                }
+                r.min_d = min_depths[(int64_t)b * d.F + f];
+                r.max_d = max_depths[(int64_t)b * d.F + f];
+            }
+            __syncthreads();
+            for (int j = 0; !done && j < kept; j++) {
+                const RzRec& r = recs[j];
+                if (cnt == Lp && r.min_d > bound) { done = true; break; }
+                f3 tuv;
+                if (!ray_tri_intersection(ro, rd, {r.v[0], r.v[1], r.v[2]}, {r.v[3], r.v[4], r.v[5]}, {r.v[6], r.v[7], r.v[8]}, tuv)) continue;
+                if (!(tuv.x >= 0.0f && tuv.y >= 0.0f && tuv.z >= 0.0f && tuv.y + tuv.z <= 1.0f)) continue;
+                if (pass > 0 && !rz_before(prev_t, prev_id, tuv.x, r.face_id)) continue;    // listed by an earlier pass
+                rz_insert<KR>(h, Lp, tuv.x, r.face_id, tuv.y, tuv.z, r.max_d);
+                cnt = min(cnt + 1, Lp);
+                if (cnt == Lp) {
+                    float mx = h.md[0];
+#pragma unroll
+                    for (int k = 1; k < KR; k++) mx = fmaxf(mx, h.md[k]);
+                    bound = mx;
+                }
+            }
+        }
+        if (inside) {
+            const int64_t o = pix * L + pass * RZ_PASS;
+#pragma unroll
+            for (int k = 0; k < KR; k++) {
+                if (k >= Lp) continue;
+                const bool hit = k < cnt;
+                out_layers[o + k] = hit ? h.id[k] : -1;
+                out_bary[3 * (o + k)] = hit ? 1.0f - h.u[k] - h.v[k] : -1.0f;
+                out_bary[3 * (o + k) + 1] = hit ? h.u[k] : -1.0f;
+                out_bary[3 * (o + k) + 2] = hit ? h.v[k] : -1.0f;
+                out_t[o + k] = hit ? h.t[k] : -1.0f;
+            }
+        }
+        listed += cnt;
+        if (cnt < Lp) exhausted = true;       // the walk saw the whole list: nothing is left for a later pass
+        prev_t = h.t[KR - 1]; prev_id = h.id[KR - 1];   // (read by a next pass only: then Lp == KR == RZ_PASS and cnt == Lp)
+    }
+    if (inside) out_cnt[pix] = listed;
+}
+
+// One listed hit's gradient, in fp64: with n = E1 x E2, q = n / (rd . n), a = (E2 x n) / |n|^2, b = (n x E1) / |n|^2 (the
+// dual basis of E1, E2 in the plane) and the barycentrics w at the hit,
+//     dt/dp_k = w_k q,   du/dp_k = -w_k (a - q (rd . a)),   dv/dp_k = -w_k (b - q (rd . b)),
+// so dL/dp_k = w_k G with G = -(gu a + gv b) + q (rd . (gu a + gv b) + gt).  The same derivative as ray_tri_intersection_grad
+// (du, its corrected dv, and its reference branch's "dv", which is dt); evaluated in fp32 that formula measured 3e-5 of the
+// largest entry from float64 on a tet lattice (faces seen at grazing angles), hence fp64 here.  false: rd . n == 0.
+__device__ __forceinline__ bool rz_hit_grad(f3 ro_f, f3 rd_f, const float* pa, const float* pb, const float* pc, float gu, float gv,
+                                            float gt, double w[3], double G[3]) {
+    const double ro[3] = {ro_f.x, ro_f.y, ro_f.z}, rd[3] = {rd_f.x, rd_f.y, rd_f.z};
+    const double p0[3] = {pa[0], pa[1], pa[2]};
+    double e1[3], e2[3], T[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) { e1[i] = (double)pb[i] - p0[i]; e2[i] = (double)pc[i] - p0[i]; T[i] = ro[i] - p0[i]; }
+    auto cross = [](const double* x, const double* y, double* o) {
+        o[0] = x[1] * y[2] - x[2] * y[1]; o[1] = x[2] * y[0] - x[0] * y[2]; o[2] = x[0] * y[1] - x[1] * y[0];
+    };
+    auto dot = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+    double n[3], a[3], b[3], X[3];
+    cross(e1, e2, n);
+    const double dn = dot(rd, n), nn = dot(n, n);
+    if (dn == 0.0 || nn == 0.0) return false;
+    const double t = -dot(T, n) / dn;
+#pragma unroll
+    for (int i = 0; i < 3; i++) X[i] = T[i] + t * rd[i];             // the hit relative to p0
+    cross(e2, n, a); cross(n, e1, b);
+#pragma unroll
+    for (int i = 0; i < 3; i++) { a[i] /= nn; b[i] /= nn; }
+    const double u = dot(X, a), v = dot(X, b);
+    w[0] = 1.0 - u - v; w[1] = u; w[2] = v;
+    double s[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) s[i] = (double)gu * a[i] + (double)gv * b[i];
+    const double k = (dot(rd, s) + (double)gt) / dn;
+#pragma unroll
+    for (int i = 0; i < 3; i++) G[i] = k * n[i] - s[i];
+    return true;
+}
+
+__global__ void __launch_bounds__(TILE_PIX)
+k_rasterize_bwd(dm2_layers_desc d, const int32_t* __restrict__ layers, const float* __restrict__ dL_dbary,
+                const float* __restrict__ dL_dt, float* __restrict__ dL_dverts) {
+    __shared__ int s_key[LC_SLOTS];
+    __shared__ double s_acc[RZ_NCOMP * LC_SLOTS];                      // component-major: [comp][slot]
+    const int b = blockIdx.z;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < LC_SLOTS; i += TILE_PIX) s_key[i] = -1;
+    for (int i = tid; i < RZ_NCOMP * LC_SLOTS; i += TILE_PIX) s_acc[i] = 0.0;
+    __syncthreads();
+
+    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
+    if ((px < (uint32_t)d.W) && (py < (uint32_t)d.H)) {
+        const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+        f3 ro, rd;
+        pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+        for (int l = 0; l < d.L; l++) {
+            const int64_t s = pix * d.L + l;
+            const int f = layers[s];
+            if ((unsigned)f >= (unsigned)d.F) continue;
+            float g0 = 0.f, g1 = 0.f, g2 = 0.f, gt = 0.f;
+            if (dL_dbary) { g0 = dL_dbary[3 * s]; g1 = dL_dbary[3 * s + 1]; g2 = dL_dbary[3 * s + 2]; }
+            if (dL_dt) gt = dL_dt[s];
+            if (g0 == 0.0f && g1 == 0.0f && g2 == 0.0f && gt == 0.0f) continue;
+            const int64_t v[3] = {d.faces[3 * (int64_t)f], d.faces[3 * (int64_t)f + 1], d.faces[3 * (int64_t)f + 2]};
+            double w[3], G[3];
+            if (!rz_hit_grad(ro, rd, d.verts + 3 * v[0], d.verts + 3 * v[1], d.verts + 3 * v[2], g1 - g0, g2 - g0, gt, w, G)) continue;
+            const int slot = lc_slot(s_key, f);
+#pragma unroll
+            for (int c = 0; c < RZ_NCOMP; c++) {
+                const double gc = w[c / 3] * G[c % 3];
+                if (gc == 0.0) continue;
+                if (slot >= 0) atomicAdd(&s_acc[c * LC_SLOTS + slot], gc);
+                else atomicAdd(dL_dverts + 3 * v[c / 3] + c % 3, (float)gc);
+            }
+        }
+    }
+    __syncthreads();
+    // flush: one global atomic per (vertex row, component) of every face the tile's pixels listed
+    for (int i = tid; i < RZ_NCOMP * LC_SLOTS; i += TILE_PIX) {
+        const int c = i / LC_SLOTS, slot = i - c * LC_SLOTS;
+        const int f = s_key[slot];
+        if (f < 0) continue;
+        const float g = (float)s_acc[i];
+        if (g == 0.0f) continue;
+        const int64_t v = d.faces[3 * (int64_t)f + c / 3];
+        atomicAdd(dL_dverts + 3 * v + c % 3, g);
+    }
+}
+
+void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
+                      int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, hipStream_t st) {
+    const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
+#define DM2_RZ_LAUNCH(KR) \
+    hipLaunchKernelGGL(k_rasterize<KR>, grid, dim3(TILE_PIX), 0, st, d, fs.min_depths, fs.max_depths, ranges, face_list, \
+                       render_layers, render_layers_cnt, bary, t)
+    if (d.L <= 1) DM2_RZ_LAUNCH(1);
+    else if (d.L <= 2) DM2_RZ_LAUNCH(2);
+    else if (d.L <= 4) DM2_RZ_LAUNCH(4);
+    else if (d.L <= 8) DM2_RZ_LAUNCH(8);
+    else DM2_RZ_LAUNCH(16);
+#undef DM2_RZ_LAUNCH
+}
+
+void launch_rasterize_backward(const dm2_layers_desc& d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
+                               float* dL_dverts, hipStream_t st) {
+    const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
+    hipLaunchKernelGGL(k_rasterize_bwd, grid, dim3(TILE_PIX), 0, st, d, render_layers, dL_dbary, dL_dt, dL_dverts);
+}
+
+}  // namespace dm2

@@ -225,6 +225,12 @@ void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const fl
 void launch_forward_alpha(ImageState is, int64_t N, float* out_alpha, hipStream_t st);
 void launch_layers(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                    LayerImageState ls, void* tet_scratch, int32_t* render_layers, int32_t* render_layers_cnt, hipStream_t st);
+// Renderer.rasterize (dm2_rasterize.hip): the first d.L hits of every pixel over the plan's tile lists (d.L >= 1); every slot
+// of every pixel is written.  The backward adds into dL_dverts; either upstream gradient may be NULL.
+void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
+                      int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, hipStream_t st);
+void launch_rasterize_backward(const dm2_layers_desc& d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
+                               float* dL_dverts, hipStream_t st);
 
 }  // namespace dm2
 

@@ -110,7 +110,7 @@ enum {
                                  LayeredRenderer; tiles = ceil(W/16) * ceil(H/16) */
     DM2_SCRATCH_IMAGE = 1,    /* count = B*H*W, aux = B*tiles      */
     DM2_SCRATCH_BINNING = 2,  /* count = num_rendered, aux = B*tiles */
-    DM2_SCRATCH_LAYER_IMAGE = 3, /* count = B*H*W, aux = B*tiles    */
+    DM2_SCRATCH_LAYER_IMAGE = 3, /* count = B*H*W, aux = B*tiles (dm2_layers_run; dm2_rasterize_run uses its tile ranges) */
     DM2_SCRATCH_LAYER_TETS = 4,  /* count = T (tets): packed per-tet records of the layer walk, 256 B each */
     DM2_SCRATCH_PAIR_POOL = 5,   /* count = pair_bound of the plan: bytes to APPEND to the binning scratch (behind its
                                     DM2_SCRATCH_BINNING bytes for the same num_rendered) for the forward's pair pool: 4 B per
@@ -263,6 +263,33 @@ int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_t
                    void* image_scratch, size_t image_bytes,
                    void* tet_scratch, size_t tet_bytes,
                    int32_t* render_layers, int32_t* render_layers_cnt, void* stream);
+
+/* Renderer.rasterize: the first L faces each pixel's ray hits, on any triangle mesh (no tetrahedra), with barycentrics and
+ * ray parameter.  Plan with dm2_layers_plan (T = 0; tets, face_tets, tet_faces unused and may be NULL) and size the face /
+ * binning / image scratch as for dm2_layers_run (the image scratch: DM2_SCRATCH_LAYER_IMAGE).  Per pixel (x, y) of view b
+ * of the full frame, with its ray (image_ray_o / image_ray_d, or DM2_FLAG_ANALYTIC_RAYS):
+ *   candidates: the faces of the pixel's tile list -- the face's verts_image bbox touches the tile and the NDC depth cull
+ *     (max_z < -1 || min_z > 1) keeps it -- minus those with face_existence[f] == 0 (face_existence NULL: none dropped);
+ *   hit: ray_tri_intersection(ro, rd, p0, p1, p2) succeeds with t >= 0, u >= 0, v >= 0, u + v <= 1 (p_k = verts[faces[f][k]]);
+ *   order: ascending (t, f); the first L hits are listed.
+ * render_layers (B,H,W,L) int32 face ids, -1 = empty (the layout of dm2_layers_run, so they can go to dm2_layers_composite);
+ * render_layers_cnt (B,H,W) int32 = hits listed (<= L); bary (B,H,W,L,3) float32 = (1 - u - v, u, v), the weights of
+ * faces[f][0..2] (perspective-correct: from the world-space ray); t (B,H,W,L) float32 = the hit's ray parameter.  Empty
+ * slots hold -1 in all three.  Every slot is written: no pre-fill.  fp32 in ray_tri_intersection's operation order, bit-exact.
+ * The kernels stop a pixel's walk over its list (ordered by min depth) once a face's min depth lies beyond the largest max
+ * depth of the L hits held: exact unless a face crosses the camera plane, as in dm2_layers_run's first-hit pass. */
+int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries,
+                      void* face_scratch, size_t face_bytes,
+                      void* binning_scratch, size_t binning_bytes,
+                      void* image_scratch, size_t image_bytes,
+                      int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream);
+/* Gradients of dm2_rasterize_run's bary and t w.r.t. verts: dL_dverts (P,3), zero-filled by the caller.  For every slot of
+ * render_layers with 0 <= f < F, upstream g = dL_dbary[slot] (3) and g_t = dL_dt[slot]:
+ *   dL/dp_k += (g1 - g0) du/dp_k + (g2 - g0) dv/dp_k + g_t dt/dp_k,   p_k = verts[faces[f][k]],
+ * at the pixel's ray.  Either upstream gradient may be NULL (zero; both NULL: nothing to do).  Nothing flows through the ray
+ * or through which faces are listed.  Float atomics: the last bits may vary from run to run. */
+int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
+                           float* dL_dverts, void* stream);
 
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
