@@ -16,6 +16,11 @@ and the per-pixel nearest hits of any triangle mesh (Renderer.rasterize):
 
     rasterize_layers_cuda(...10 args...) -> 4-tuple, rasterize_layers_backward_cuda(...7 args...) -> dL/dverts
 
+and the attribute images of such hits (Renderer.interpolate):
+
+    interpolate_cuda(render_layers, bary, attr, attr_faces) -> out,
+    interpolate_backward_cuda(...those 4..., grad_out, need_attr, need_bary) -> (dL/dattr, dL/dbary)
+
 Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
 its gradient as the keyword ``dL_dout_alpha``.  Under ``face_weights_output`` render_forward_cuda and composite_layers_cuda
 append the per-face blend weights (B,F), behind everything else they return; they have no gradient.
@@ -113,6 +118,8 @@ EXPORTS = {
     "dm2_layers_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dm2_rasterize_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dm2_rasterize_backward": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _vp, _vp, _vp, _vp]),
+    "dm2_interpolate": (ctypes.c_int, [_i32] * 8 + [_vp] * 6),
+    "dm2_interpolate_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 8),
     "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -802,6 +809,70 @@ def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, ima
         if lib.dm2_rasterize_backward(ctypes.byref(d), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts), _stream(dev)):
             raise _err(lib, "rasterize_layers_backward_cuda")
     return dverts
+
+
+def _interpolate_args(render_layers, bary, attr, attr_faces, grad_out=None):
+    """Checks of an interpolate call -> (sizes (B, H, W, L, F, N, C, view_tables), contiguous tensors, device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(render_layers.dim() != 4, "render_layers must have dimensions (B, H, W, L)")
+    B, H, W, L = (int(x) for x in render_layers.shape)
+    bad(tuple(bary.shape) != (B, H, W, L, 3), f"bary must have dimensions {(B, H, W, L, 3)}, got {tuple(bary.shape)}")
+    bad(attr.dim() not in (2, 3), "attr must have dimensions (N, C) or (B, N, C)")
+    bad(attr.dim() == 3 and attr.size(0) != B, f"attr must have dimensions (N, C) or ({B}, N, C), got {tuple(attr.shape)}")
+    bad(attr.size(-1) < 1, "attr must have at least one channel")
+    bad(attr_faces.dim() != 2 or attr_faces.size(1) != 3, "attr_faces must have dimensions (F, 3)")
+    N, C, F = int(attr.size(-2)), int(attr.size(-1)), int(attr_faces.size(0))
+    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
+        f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
+    dev = _require_gpu(*[t for t in (render_layers, bary, attr, attr_faces, grad_out) if t is not None])
+    f32, i32 = torch.float32, torch.int32
+    named = (("render_layers", render_layers, i32), ("bary", bary, f32), ("attr", attr, f32), ("attr_faces", attr_faces, i32),
+             ("grad_out", grad_out, f32))
+    ts = []
+    for name, t, dt in named:
+        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    return (B, H, W, L, F, N, C, 1 if attr.dim() == 3 else 0), ts, dev
+
+
+def interpolate_cuda(render_layers, bary, attr, attr_faces):
+    """Attribute images from per-slot face ids and barycentrics (include/dm2_hip.h: dm2_interpolate).
+
+    render_layers (B,H,W,L) int32, bary (B,H,W,L,3) float32, attr (N,C) or (B,N,C) float32, attr_faces (F,3) int32 rows of attr
+    -> out (B,H,W,L,C) float32 = (bary0 attr[v0] + bary1 attr[v1]) + bary2 attr[v2]; 0 where the id is outside [0, F) or a
+    row of attr_faces[id] outside [0, N)."""
+    lib = load_library()
+    sizes, (rl, bc, at, af, _), dev = _interpolate_args(render_layers, bary, attr, attr_faces)
+    B, H, W, L, F, N, C, _ = sizes
+    if B * H * W * L == 0 or F == 0 or N == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # every slot empty: no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if lib.dm2_interpolate(*sizes, _ptr(rl), _ptr(bc), _ptr(at), _ptr(af), _ptr(out), _stream(dev)):
+            raise _err(lib, "interpolate_cuda")
+    return out
+
+
+def interpolate_backward_cuda(render_layers, bary, attr, attr_faces, grad_out, need_attr, need_bary):
+    """Gradients of interpolate_cuda (dm2_interpolate_backward) -> (dL_dattr of attr's shape or None, dL_dbary (B,H,W,L,3) or
+    None): only what ``need_attr`` / ``need_bary`` ask for is computed."""
+    lib = load_library()
+    sizes, (rl, bc, at, af, go), dev = _interpolate_args(render_layers, bary, attr, attr_faces, grad_out)
+    B, H, W, L, F, N, C, _ = sizes
+    f32 = torch.float32
+    dattr = torch.zeros(tuple(attr.shape), dtype=f32, device=dev) if need_attr else None
+    if not (need_attr or need_bary):
+        return None, None
+    if B * H * W * L == 0 or F == 0 or N == 0:
+        return dattr, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_bary else None
+    dbary = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_bary else None
+    with torch.cuda.device(dev):
+        if lib.dm2_interpolate_backward(*sizes, _ptr(rl), _ptr(bc), _ptr(at), _ptr(af), _ptr(go), _ptr(dattr), _ptr(dbary),
+                                        _stream(dev)):
+            raise _err(lib, "interpolate_backward_cuda")
+    return dattr, dbary
 
 
 def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,

@@ -7,7 +7,9 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
 * ``LayeredRenderer`` (reference :388-451) ``generate()`` -> (render_layers, render_layers_cnt), and (not in the
   reference) ``render()``: those layers composited into (color, depth), differentiable (``LayeredCompositeFunction``)
 * (not in the reference) ``Renderer.rasterize()``: the first L faces each pixel's ray hits on any triangle mesh, with
-  perspective-correct barycentrics and ray distance, differentiable w.r.t. the vertices (``RasterizeFunction``)
+  perspective-correct barycentrics and ray distance, differentiable w.r.t. the vertices (``RasterizeFunction``), and
+  ``Renderer.interpolate()``: those hits turned into an image of any C-channel vertex attribute, differentiable w.r.t.
+  the attribute and the barycentrics (``InterpolateFunction``)
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -25,7 +27,8 @@ import torch
 from . import _C
 from .pyrenderer import Triangles
 
-__all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "Triangles"]
+__all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
+           "Triangles"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -295,8 +298,8 @@ class Renderer(torch.nn.Module):
         (``faces_existence`` == 0 drops a face; None keeps all); a hit is the pixel's ray meeting the triangle (t >= 0,
         barycentrics >= 0); hits are ordered by (t, face id).  render_layers can go straight to ``LayeredRenderer.render``.
         bary and t are differentiable w.r.t. ``verts`` (``RasterizeFunction``); nothing flows through the rays (cameras get
-        no gradient here) or through which faces are listed.  Interpolate any per-vertex attribute in torch, e.g.
-        ``(bary[..., None] * verts_color[faces[ids.clamp(min=0)].long()]).sum(-2)``."""
+        no gradient here) or through which faces are listed.  ``interpolate`` turns the ids and bary into an image of any
+        per-vertex attribute (normals, UVs, features), differentiably."""
         mv = self.mv[batch_mvp_idx]
         proj = self.proj[batch_mvp_idx]
         i32, f32 = torch.int32, torch.float32
@@ -316,6 +319,19 @@ class Renderer(torch.nn.Module):
                 return RasterizeFunction.apply(*args, ph, ph, self.width, self.height, int(num_layers))
         ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
         return RasterizeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32), self.width, self.height, int(num_layers))
+
+    def interpolate(self, render_layers: torch.Tensor, bary: torch.Tensor, attr: torch.Tensor, attr_faces: torch.Tensor):
+        """Attribute images from ``rasterize``'s hits (not in the reference): render_layers (B,H,W,L) int32 face ids (as
+        ``rasterize`` / ``generate`` return them, or hand-built), bary (B,H,W,L,3) float32 weights of attr_faces[f][0..2],
+        attr (N,C) float32 shared by the views or (B,N,C) one table per view (any C >= 1), attr_faces (F,3) int32 rows of
+        attr (the mesh's ``faces`` for per-vertex data, or a table of its own, e.g. across UV seams) -> out (B,H,W,L,C)
+        float32 = (bary0 attr[v0] + bary1 attr[v1]) + bary2 attr[v2] per slot.
+
+        A slot whose id is outside [0, F), or whose attr_faces row names a row outside [0, N), is empty: zeros out, whatever
+        its bary holds, and no gradient.  Differentiable w.r.t. ``attr`` and ``bary`` (``InterpolateFunction``); through
+        ``bary``, ``rasterize``'s backward carries the gradient on to ``verts``."""
+        i32, f32 = torch.int32, torch.float32
+        return InterpolateFunction.apply(render_layers.to(i32), bary.to(f32), attr.to(f32), attr_faces.to(i32))
 
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
@@ -464,6 +480,31 @@ class RasterizeFunction(torch.autograd.Function):
         with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))):
             dverts = _C.rasterize_layers_backward_cuda(layers, verts, faces, ray_o, ray_d, grad_bary, grad_t)
         return (dverts,) + (None,) * 9
+
+
+class InterpolateFunction(torch.autograd.Function):
+    """out = (bary0 attr[v0] + bary1 attr[v1]) + bary2 attr[v2] per slot of render_layers (``_C.interpolate_cuda``).
+
+    Inputs: render_layers (B,H,W,L) int32, bary (B,H,W,L,3)*, attr (N,C)* or (B,N,C)*, attr_faces (F,3) int32.  Output: out
+    (B,H,W,L,C).  (* = receives a gradient.)  A filled slot sends bary_k g to row v_k of attr and attr[v_k] . g to bary_k;
+    empty slots send nothing and get zero.  Only the gradients ``needs_input_grad`` asks for are computed: no attr scatter
+    when only bary requires grad, and the reverse.
+    """
+
+    @staticmethod
+    def forward(ctx, render_layers, bary, attr, attr_faces):
+        out = _C.interpolate_cuda(render_layers, bary.detach(), attr.detach(), attr_faces)
+        ctx.save_for_backward(render_layers, bary.detach(), attr.detach(), attr_faces)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_bary, need_attr = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if grad_out is None or not (need_bary or need_attr):
+            return None, None, None, None
+        render_layers, bary, attr, attr_faces = ctx.saved_tensors
+        dattr, dbary = _C.interpolate_backward_cuda(render_layers, bary, attr, attr_faces, grad_out, need_attr, need_bary)
+        return None, dbary, dattr, None
 
 
 class LayeredRenderer(Renderer):

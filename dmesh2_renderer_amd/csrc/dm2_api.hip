@@ -472,6 +472,50 @@ int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layer
     return 0;
 }
 
+static int check_interpolate_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t F, int32_t N, int32_t C, int32_t view_tables) {
+    if (B < 0 || H < 0 || W < 0 || L < 0 || F < 0 || N < 0) return fail("interpolate: negative size");
+    if (C < 1) return fail("interpolate: C must be at least 1");
+    if (view_tables && (int64_t)B * N > 0x7FFFFFFF) return fail("interpolate: B * N must be below 2^31");
+    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || B > 65535) return fail("interpolate: too many slots or views");
+    return 0;
+}
+
+int dm2_interpolate(int32_t B, int32_t H, int32_t W, int32_t L, int32_t F, int32_t N, int32_t C, int32_t view_tables,
+                    const int32_t* render_layers, const float* bary, const float* attr, const int32_t* attr_faces,
+                    float* out, void* stream) {
+    if (check_interpolate_sizes(B, H, W, L, F, N, C, view_tables)) return 1;
+    const int64_t S = (int64_t)B * H * W * L;
+    if (S == 0) return 0;
+    if (!out) return fail("interpolate: out must not be null");
+    if (F == 0 || N == 0) {                                              // every slot is empty
+        DM2_HIP(hipMemsetAsync(out, 0, (size_t)S * C * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
+    if (!render_layers || !bary || !attr || !attr_faces) return fail("interpolate: inputs must not be null");
+    dm2::launch_interpolate(B, H, W, L, F, N, C, view_tables, render_layers, bary, attr, attr_faces, out, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_interpolate_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t F, int32_t N, int32_t C, int32_t view_tables,
+                             const int32_t* render_layers, const float* bary, const float* attr, const int32_t* attr_faces,
+                             const float* dL_dout, float* dL_dattr, float* dL_dbary, void* stream) {
+    if (check_interpolate_sizes(B, H, W, L, F, N, C, view_tables)) return 1;
+    const int64_t S = (int64_t)B * H * W * L;
+    if (S == 0 || (!dL_dattr && !dL_dbary)) return 0;
+    if (F == 0 || N == 0) {                                              // every slot is empty: nothing reaches attr
+        if (dL_dbary) DM2_HIP(hipMemsetAsync(dL_dbary, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
+    if (!render_layers || !attr_faces || !dL_dout) return fail("interpolate_backward: inputs must not be null");
+    if (dL_dattr && !bary) return fail("interpolate_backward: bary must not be null");
+    if (dL_dbary && !attr) return fail("interpolate_backward: attr must not be null");
+    dm2::launch_interpolate_backward(B, H, W, L, F, N, C, view_tables, render_layers, bary, attr, attr_faces, dL_dout, dL_dattr,
+                                     dL_dbary, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_composite_desc(const dm2_layer_composite_desc* d) {
     if (!d) return fail("null descriptor");
     if (d->B < 0 || d->P < 0 || d->F < 0 || d->W < 0 || d->H < 0 || d->L < 0) return fail("negative size in descriptor");

@@ -231,6 +231,13 @@ void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2
                       int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, hipStream_t st);
 void launch_rasterize_backward(const dm2_layers_desc& d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                                float* dL_dverts, hipStream_t st);
+// Renderer.interpolate (dm2_interpolate.hip): every element of out / dL_dbary is written; the backward adds into dL_dattr;
+// either of its output pointers may be NULL.  B * H * W * L > 0 and C >= 1.
+void launch_interpolate(int B, int H, int W, int L, int F, int N, int C, int view_tables, const int32_t* render_layers,
+                        const float* bary, const float* attr, const int32_t* attr_faces, float* out, hipStream_t st);
+void launch_interpolate_backward(int B, int H, int W, int L, int F, int N, int C, int view_tables, const int32_t* render_layers,
+                                 const float* bary, const float* attr, const int32_t* attr_faces, const float* dL_dout,
+                                 float* dL_dattr, float* dL_dbary, hipStream_t st);
 
 }  // namespace dm2
 

@@ -291,6 +291,25 @@ int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t ma
 int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                            float* dL_dverts, void* stream);
 
+/* Renderer.interpolate: attribute images from face ids and barycentrics per slot (dm2_rasterize_run's, dm2_layers_run's or
+ * hand-built).  render_layers (B,H,W,L) int32, bary (B,H,W,L,3) float32, attr (N,C) float32 shared by the views
+ * (view_tables == 0) or (B,N,C), one table per view (view_tables != 0), attr_faces (F,3) int32 rows of attr, out (B,H,W,L,C).
+ * A slot s is filled when f = render_layers[s] lies in [0, F) and v_k = attr_faces[f][k], k = 0..2, all lie in [0, N):
+ *   out[s,c] = (bary[s,0] * attr[v_0,c] + bary[s,1] * attr[v_1,c]) + bary[s,2] * attr[v_2,c]
+ * in fp32, in this order, without contraction (bit-exact).  Every other slot is empty: out[s,:] = 0, and neither its bary
+ * nor any attr row is read through it.  Every element of out is written: no pre-fill.  C >= 1; B * N < 2^31. */
+int dm2_interpolate(int32_t B, int32_t H, int32_t W, int32_t L, int32_t F, int32_t N, int32_t C, int32_t view_tables,
+                    const int32_t* render_layers, const float* bary, const float* attr, const int32_t* attr_faces,
+                    float* out, void* stream);
+/* Gradients of dm2_interpolate for upstream g = dL_dout (B,H,W,L,C).  Per filled slot s:
+ *   dL_dattr[v_k,c] += bary[s,k] * g[s,c]   (the view's table when view_tables != 0); dL_dattr is zero-filled by the caller;
+ *   dL_dbary[s,k] = sum_c attr[v_k,c] * g[s,c]; 0 in an empty slot; every element is written.
+ * Either output pointer may be NULL (not wanted; its kernel is not launched).  dL_dattr is summed with float atomics: its
+ * last bits may vary from run to run; dL_dbary is a pure function of the inputs. */
+int dm2_interpolate_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t F, int32_t N, int32_t C, int32_t view_tables,
+                             const int32_t* render_layers, const float* bary, const float* attr, const int32_t* attr_faces,
+                             const float* dL_dout, float* dL_dattr, float* dL_dbary, void* stream);
+
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
  *   1. skip f < 0 or f >= F (holes and out-of-range ids are allowed and never read through);
