@@ -21,6 +21,11 @@ and the attribute images of such hits (Renderer.interpolate):
     interpolate_cuda(render_layers, bary, attr, attr_faces) -> out,
     interpolate_backward_cuda(...those 4..., grad_out, need_attr, need_bary) -> (dL/dattr, dL/dbary)
 
+and a texture sampled at such an image of UVs (Renderer.texture):
+
+    texture_cuda(uv, tex, render_layers, filter_mode, boundary_mode) -> out,
+    texture_backward_cuda(...those 5..., grad_out, need_tex, need_uv) -> (dL/dtex, dL/duv)
+
 Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
 its gradient as the keyword ``dL_dout_alpha``.  Under ``face_weights_output`` render_forward_cuda and composite_layers_cuda
 append the per-face blend weights (B,F), behind everything else they return; they have no gradient.
@@ -120,6 +125,8 @@ EXPORTS = {
     "dm2_rasterize_backward": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_interpolate": (ctypes.c_int, [_i32] * 8 + [_vp] * 6),
     "dm2_interpolate_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 8),
+    "dm2_texture": (ctypes.c_int, [_i32] * 10 + [_vp] * 5),
+    "dm2_texture_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
     "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -873,6 +880,75 @@ def interpolate_backward_cuda(render_layers, bary, attr, attr_faces, grad_out, n
                                         _stream(dev)):
             raise _err(lib, "interpolate_backward_cuda")
     return dattr, dbary
+
+
+TEX_FILTERS = {"nearest": 0, "linear": 1}        # include/dm2_hip.h DM2_TEX_FILTER_*
+TEX_BOUNDARIES = {"wrap": 0, "clamp": 1}         # DM2_TEX_BOUNDARY_*
+
+
+def _texture_args(uv, tex, render_layers, filter_mode, boundary_mode, grad_out=None):
+    """Checks of a texture call -> (sizes (B, H, W, L, Ht, Wt, C, view_textures, filter, boundary), contiguous tensors, device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
+    bad(boundary_mode not in TEX_BOUNDARIES, f"boundary_mode must be one of {sorted(TEX_BOUNDARIES)}, got {boundary_mode!r}")
+    bad(uv.dim() != 5 or uv.size(4) != 2, f"uv must have dimensions (B, H, W, L, 2), got {tuple(uv.shape)}")
+    B, H, W, L = (int(x) for x in uv.shape[:4])
+    bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
+    bad(tex.dim() == 4 and tex.size(0) != B, f"tex must have dimensions (Ht, Wt, C) or ({B}, Ht, Wt, C), got {tuple(tex.shape)}")
+    Ht, Wt, C = (int(x) for x in tex.shape[-3:])
+    bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
+    bad(C < 1, "tex must have at least one channel")
+    bad(Ht * Wt >= 2 ** 31, "tex: Ht * Wt must be below 2^31")
+    bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
+    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
+        f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
+    dev = _require_gpu(*[t for t in (uv, tex, render_layers, grad_out) if t is not None])
+    f32, i32 = torch.float32, torch.int32
+    named = (("uv", uv, f32), ("tex", tex, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
+    ts = []
+    for name, t, dt in named:
+        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    return (B, H, W, L, Ht, Wt, C, 1 if tex.dim() == 4 else 0, TEX_FILTERS[filter_mode], TEX_BOUNDARIES[boundary_mode]), ts, dev
+
+
+def texture_cuda(uv, tex, render_layers=None, filter_mode="linear", boundary_mode="wrap"):
+    """A texture sampled at per-slot UVs (include/dm2_hip.h: dm2_texture).
+
+    uv (B,H,W,L,2) float32, tex (Ht,Wt,C) or (B,Ht,Wt,C) float32 channel-last, render_layers (B,H,W,L) int32 or None
+    -> out (B,H,W,L,C) float32; 0 where the id is negative or uv is not finite (or beyond 2^24 texels)."""
+    lib = load_library()
+    sizes, (uvc, tx, rl, _), dev = _texture_args(uv, tex, render_layers, filter_mode, boundary_mode)
+    B, H, W, L, C = *sizes[:4], sizes[6]
+    if B * H * W * L == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture(*sizes, _ptr(rl), _ptr(uvc), _ptr(tx), _ptr(out), _stream(dev)):
+            raise _err(lib, "texture_cuda")
+    return out
+
+
+def texture_backward_cuda(uv, tex, render_layers, filter_mode, boundary_mode, grad_out, need_tex, need_uv):
+    """Gradients of texture_cuda (dm2_texture_backward) -> (dL_dtex of tex's shape or None, dL_duv (B,H,W,L,2) or None): only
+    what ``need_tex`` / ``need_uv`` ask for is computed."""
+    lib = load_library()
+    sizes, (uvc, tx, rl, go), dev = _texture_args(uv, tex, render_layers, filter_mode, boundary_mode, grad_out)
+    B, H, W, L = sizes[:4]
+    f32 = torch.float32
+    if not (need_tex or need_uv):
+        return None, None
+    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None
+    if B * H * W * L == 0:
+        return dtex, torch.zeros((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None
+    duv = torch.empty((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None      # (every element written)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_backward(*sizes, _ptr(rl), _ptr(uvc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(duv), _stream(dev)):
+            raise _err(lib, "texture_backward_cuda")
+    return dtex, duv
 
 
 def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,

@@ -9,7 +9,9 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
 * (not in the reference) ``Renderer.rasterize()``: the first L faces each pixel's ray hits on any triangle mesh, with
   perspective-correct barycentrics and ray distance, differentiable w.r.t. the vertices (``RasterizeFunction``), and
   ``Renderer.interpolate()``: those hits turned into an image of any C-channel vertex attribute, differentiable w.r.t.
-  the attribute and the barycentrics (``InterpolateFunction``)
+  the attribute and the barycentrics (``InterpolateFunction``), and ``Renderer.texture()``: a channel-last texture sampled
+  at such an image of UVs (bilinear or nearest, wrap or clamp), differentiable w.r.t. the texture and the UVs
+  (``TextureFunction``)
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -28,7 +30,7 @@ from . import _C
 from .pyrenderer import Triangles
 
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
-           "Triangles"]
+           "TextureFunction", "Triangles"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -333,6 +335,21 @@ class Renderer(torch.nn.Module):
         i32, f32 = torch.int32, torch.float32
         return InterpolateFunction.apply(render_layers.to(i32), bary.to(f32), attr.to(f32), attr_faces.to(i32))
 
+    def texture(self, uv: torch.Tensor, tex: torch.Tensor, render_layers: torch.Tensor = None, filter_mode: str = "linear",
+                boundary_mode: str = "wrap"):
+        """A texture sampled at ``interpolate``'s UVs (not in the reference): uv (B,H,W,L,2) float32 = (u, v), u along the
+        texture's width (what ``interpolate`` returns for a 2-channel attribute), tex (Ht,Wt,C) float32 shared by the views or
+        (B,Ht,Wt,C) one texture per view, channel-last, any C >= 1, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C)
+        float32.  Texel centres sit at ((i + 0.5) / Wt, (j + 0.5) / Ht); ``filter_mode`` "linear" (bilinear) or "nearest",
+        ``boundary_mode`` "wrap" (repeat) or "clamp".
+
+        A slot with ``render_layers`` < 0 (None: no slot, by id), or whose uv is not finite, is empty: zeros out, nothing
+        read from the texture through it, no gradient.  Differentiable w.r.t. ``tex`` and ``uv`` (``TextureFunction``); through
+        ``uv``, ``interpolate``'s and ``rasterize``'s backwards carry the gradient on to the UV table and to ``verts``."""
+        i32, f32 = torch.int32, torch.float32
+        rl = None if render_layers is None else render_layers.to(i32)
+        return TextureFunction.apply(uv.to(f32), tex.to(f32), rl, filter_mode, boundary_mode)
+
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
         f32 = torch.float32
@@ -505,6 +522,35 @@ class InterpolateFunction(torch.autograd.Function):
         render_layers, bary, attr, attr_faces = ctx.saved_tensors
         dattr, dbary = _C.interpolate_backward_cuda(render_layers, bary, attr, attr_faces, grad_out, need_attr, need_bary)
         return None, dbary, dattr, None
+
+
+class TextureFunction(torch.autograd.Function):
+    """out = the texture at each slot's uv (``_C.texture_cuda``): bilinear a + fy (b - a) over the four texels round
+    (u Wt - 0.5, v Ht - 0.5), or the nearest texel; wrap or clamp addressing.
+
+    Inputs: uv (B,H,W,L,2)*, tex (Ht,Wt,C)* or (B,Ht,Wt,C)*, render_layers (B,H,W,L) int32 or None, filter_mode, boundary_mode.
+    Output: out (B,H,W,L,C).  (* = receives a gradient.)  A non-empty slot sends w_pq g to its four texels and the texture's
+    finite differences . g to (u, v) (zeros for nearest); empty slots send nothing and get zero.  Only the gradients
+    ``needs_input_grad`` asks for are computed: no texel scatter when only uv requires grad, and the reverse.
+    """
+
+    @staticmethod
+    def forward(ctx, uv, tex, render_layers, filter_mode, boundary_mode):
+        out = _C.texture_cuda(uv.detach(), tex.detach(), render_layers, filter_mode, boundary_mode)
+        ctx.modes = (filter_mode, boundary_mode)
+        ctx.has_layers = render_layers is not None
+        ctx.save_for_backward(uv.detach(), tex.detach(), *((render_layers,) if ctx.has_layers else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_uv, need_tex = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_out is None or not (need_uv or need_tex):
+            return None, None, None, None, None
+        uv, tex = ctx.saved_tensors[:2]
+        render_layers = ctx.saved_tensors[2] if ctx.has_layers else None
+        dtex, duv = _C.texture_backward_cuda(uv, tex, render_layers, *ctx.modes, grad_out, need_tex, need_uv)
+        return duv, dtex, None, None, None
 
 
 class LayeredRenderer(Renderer):

@@ -516,6 +516,49 @@ int dm2_interpolate_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
     return 0;
 }
 
+static int check_texture_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t filter,
+                               int32_t boundary) {
+    if (B < 0 || H < 0 || W < 0 || L < 0) return fail("texture: negative size");
+    if (Ht < 1 || Wt < 1) return fail("texture: Ht and Wt must be at least 1");
+    if ((int64_t)Ht * Wt > 0x7FFFFFFF) return fail("texture: Ht * Wt must be below 2^31");
+    if (C < 1) return fail("texture: C must be at least 1");
+    if (filter != DM2_TEX_FILTER_NEAREST && filter != DM2_TEX_FILTER_LINEAR) return fail("texture: unknown filter");
+    if (boundary != DM2_TEX_BOUNDARY_WRAP && boundary != DM2_TEX_BOUNDARY_CLAMP) return fail("texture: unknown boundary");
+    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || B > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
+        return fail("texture: too many slots, rows or views");
+    return 0;
+}
+
+int dm2_texture(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex, float* out,
+                void* stream) {
+    if (check_texture_sizes(B, H, W, L, Ht, Wt, C, filter, boundary)) return 1;
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!uv || !tex || !out) return fail("texture: uv, tex and out must not be null");
+    dm2::launch_texture(B, H, W, L, Ht, Wt, C, view_textures, filter, boundary, render_layers, uv, tex, out, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                         int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex,
+                         const float* dL_dout, float* dL_dtex, float* dL_duv, void* stream) {
+    if (check_texture_sizes(B, H, W, L, Ht, Wt, C, filter, boundary)) return 1;
+    const int64_t S = (int64_t)B * H * W * L;
+    if (S == 0 || (!dL_dtex && !dL_duv)) return 0;
+    if (!uv || !dL_dout) return fail("texture_backward: uv and dL_dout must not be null");
+    if (dL_duv && filter == DM2_TEX_FILTER_NEAREST) {                     // piecewise constant in uv
+        DM2_HIP(hipMemsetAsync(dL_duv, 0, (size_t)S * 2 * sizeof(float), (hipStream_t)stream));
+        dL_duv = nullptr;
+    }
+    if (dL_duv && !tex) return fail("texture_backward: tex must not be null");
+    if (dL_dtex || dL_duv)
+        dm2::launch_texture_backward(B, H, W, L, Ht, Wt, C, view_textures, filter, boundary, render_layers, uv, tex, dL_dout,
+                                     dL_dtex, dL_duv, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_composite_desc(const dm2_layer_composite_desc* d) {
     if (!d) return fail("null descriptor");
     if (d->B < 0 || d->P < 0 || d->F < 0 || d->W < 0 || d->H < 0 || d->L < 0) return fail("negative size in descriptor");

@@ -238,6 +238,13 @@ void launch_interpolate(int B, int H, int W, int L, int F, int N, int C, int vie
 void launch_interpolate_backward(int B, int H, int W, int L, int F, int N, int C, int view_tables, const int32_t* render_layers,
                                  const float* bary, const float* attr, const int32_t* attr_faces, const float* dL_dout,
                                  float* dL_dattr, float* dL_dbary, hipStream_t st);
+// Renderer.texture (dm2_texture.hip): every element of out / dL_duv is written; the backward adds into dL_dtex; either of its
+// output pointers may be NULL (dL_duv: linear only).  B * H * W * L > 0, Ht, Wt, C >= 1; filter / boundary: DM2_TEX_*.
+void launch_texture(int B, int H, int W, int L, int Ht, int Wt, int C, int view_textures, int filter, int boundary,
+                    const int32_t* render_layers, const float* uv, const float* tex, float* out, hipStream_t st);
+void launch_texture_backward(int B, int H, int W, int L, int Ht, int Wt, int C, int view_textures, int filter, int boundary,
+                             const int32_t* render_layers, const float* uv, const float* tex, const float* dL_dout,
+                             float* dL_dtex, float* dL_duv, hipStream_t st);
 
 }  // namespace dm2
 

@@ -310,6 +310,40 @@ int dm2_interpolate_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
                              const int32_t* render_layers, const float* bary, const float* attr, const int32_t* attr_faces,
                              const float* dL_dout, float* dL_dattr, float* dL_dbary, void* stream);
 
+/* Renderer.texture: a texture sampled at per-slot UVs (dm2_interpolate's output for a 2-channel attribute, or hand-built).
+ * uv (B,H,W,L,2) float32 = (u, v), u along the texture's width; tex (Ht,Wt,C) float32 shared by the views
+ * (view_textures == 0) or (B,Ht,Wt,C), one texture per view (view_textures != 0), channel-last; render_layers (B,H,W,L) int32
+ * or NULL; out (B,H,W,L,C).  Ht, Wt, C >= 1; Ht * Wt < 2^31.  Texel centres sit at ((i + 0.5) / Wt, (j + 0.5) / Ht).  Per slot
+ * s, all fp32, separate multiplies and adds in the written order, without contraction (bit-exact):
+ *   x  = u * (float)Wt - 0.5f         y  = v * (float)Ht - 0.5f
+ *   x0 = floorf(x)   fx = x - x0       y0 = floorf(y)   fy = y - y0
+ * A slot is empty when render_layers[s] < 0 (render_layers NULL: never by id), or u or v is not finite, or |x| or |y| is not
+ * below 2^24: out[s,:] = 0, and nothing is read from tex through it.  Otherwise i0 = (int)x0, i1 = i0 + 1, j0 = (int)y0,
+ * j1 = j0 + 1, addressed per boundary mode: DM2_TEX_BOUNDARY_WRAP addr(i) = ((i % n) + n) % n, DM2_TEX_BOUNDARY_CLAMP
+ * addr(i) = min(max(i, 0), n - 1), n = Wt for columns and Ht for rows; t_pq = tex[addr(j0 + q)][addr(i0 + p)]:
+ *   DM2_TEX_FILTER_LINEAR   a = t00 + fx * (t10 - t00), b = t01 + fx * (t11 - t01), out[s,c] = a + fy * (b - a)
+ *   DM2_TEX_FILTER_NEAREST  out[s,c] = tex[addr((int)floorf(y + 0.5f))][addr((int)floorf(x + 0.5f))]
+ * Every element of out is written: no pre-fill. */
+#define DM2_TEX_FILTER_NEAREST 0
+#define DM2_TEX_FILTER_LINEAR 1
+#define DM2_TEX_BOUNDARY_WRAP 0
+#define DM2_TEX_BOUNDARY_CLAMP 1
+int dm2_texture(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex, float* out,
+                void* stream);
+/* Gradients of dm2_texture for upstream g = dL_dout (B,H,W,L,C): the derivative of the fp32 function above at its fp32 fx, fy
+ * and addresses.  Per non-empty slot s:
+ *   dL_dtex[t_pq,c] += w_pq * g[s,c], w = ((1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy)  (nearest: weight 1 on the one texel); the
+ *     view's own texture when view_textures != 0, summed over the views otherwise; two corners that address one texel (clamp
+ *     at a border, wrap at n = 1) both add; dL_dtex is zero-filled by the caller;
+ *   dL_duv[s,0] = Wt * sum_c g[s,c] * ((t10 - t00) + fy * ((t11 - t01) - (t10 - t00))),  dL_duv[s,1] = Ht * sum_c g[s,c] * (b - a)
+ *     (used as it stands where clamp has a kink); zeros for nearest and in an empty slot; every element is written.
+ * Either output pointer may be NULL (not wanted; its kernel is not launched; tex may then be NULL for dL_dtex alone).
+ * dL_dtex is summed with float atomics: its last bits may vary from run to run; dL_duv is a pure function of the inputs. */
+int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                         int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex,
+                         const float* dL_dout, float* dL_dtex, float* dL_duv, void* stream);
+
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
  *   1. skip f < 0 or f >= F (holes and out-of-range ids are allowed and never read through);
