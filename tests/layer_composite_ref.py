@@ -156,9 +156,11 @@ def grads64(fwd, faces, verts_color, faces_opacity, faces_intense, verts_ndc, ba
     return out
 
 
-def ortho_scene(B=2, H=6, W=7, L=5, F=9, seed=0, holes=True):
+def ortho_scene(B=2, H=6, W=7, L=5, F=9, seed=0, holes=True, crowded=False):
     """Orthographic rays (origin (x, y, 0), direction -z) over [0,1]^2 and F triangles at distinct depths covering parts of
-    it; layers: hand-built lists with holes, out-of-range and repeated ids."""
+    it; layers: hand-built lists with holes, out-of-range and repeated ids.  ``crowded``: every triangle's xy scaled by 5
+    about its centroid (circumradius 3), so that (nearly) every face covers the whole unit square and every listed id blends:
+    with F in the hundreds or thousands a 16 x 16 tile then blends about F (1 - exp(-256 L / F)) distinct faces."""
     rng = np.random.RandomState(seed)
     ys, xs = np.meshgrid((np.arange(H) + 0.5) / H, (np.arange(W) + 0.5) / W, indexing="ij")
     ro = np.zeros((B, H, W, 3), np.float32); ro[..., 0] = xs; ro[..., 1] = ys
@@ -171,6 +173,10 @@ def ortho_scene(B=2, H=6, W=7, L=5, F=9, seed=0, holes=True):
             ang = 2 * np.pi * k / 3 + rng.uniform(0, 1)
             verts[3 * f + k, :2] = c + 0.6 * np.array([np.cos(ang), np.sin(ang)])
         verts[3 * f:3 * f + 3, 2] = -1.0 - 0.1 * f + rng.uniform(-0.02, 0.02, 3)
+    if crowded:
+        tri = verts.reshape(F, 3, 3)                                            # (a view: the faces are vertex triples in order)
+        c = tri[:, :, :2].mean(1, keepdims=True)
+        tri[:, :, :2] = (c + 5 * (tri[:, :, :2] - c)).astype(np.float32)
     faces = np.arange(P, dtype=np.int32).reshape(F, 3)
     layers = rng.randint(0, F, (B, H, W, L)).astype(np.int32)
     if holes:
@@ -185,3 +191,55 @@ def ortho_scene(B=2, H=6, W=7, L=5, F=9, seed=0, holes=True):
                   verts_ndc=rng.uniform(-1, 1, (B, P, 3)).astype(np.float32),
                   background=np.array([0.2, 0.5, 0.9], np.float32), ray_o=ro, ray_d=rd)
     return inputs
+
+
+TILE = 16                   # the layer kernels' tile: one block, one face table
+
+
+def distinct_blended_per_tile(fwd):
+    """-> (smallest, largest) number of distinct blended faces (``fwd["blend"]``, ``fwd["fs"]``) over the 16 x 16 tiles of
+    every view: what a block of the layer kernels asks of its face table (dm2_face_table.h)."""
+    blend, fs = fwd["blend"], fwd["fs"]
+    B, H, W, _ = blend.shape
+    counts = []
+    for b in range(B):
+        for y in range(0, H, TILE):
+            for x in range(0, W, TILE):
+                m = blend[b, y:y + TILE, x:x + TILE]
+                counts.append(len(np.unique(fs[b, y:y + TILE, x:x + TILE][m])))
+    return min(counts), max(counts)
+
+
+# The crowded cases of the GPU tests (B = 2, 48 x 64: twelve tiles a view).  "overflow": every tile blends more distinct faces
+# than the table has slots; "nearly_full": fewer than it has slots but more than 0.8 of them, so that probe chains fail for
+# some faces while free slots remain and both scatter routes mix inside a tile.  opacity: uniform range of faces_opacity
+# (L = 12: small, so that lists do not end at T_EPS after a few layers).
+CROWDED = {
+    "overflow_L4": dict(F=4000, L=4, kind="overflow"),
+    "overflow_L12": dict(F=4000, L=12, kind="overflow", opacity=(0.02, 0.3)),
+    "nearly_full_L4": dict(F=600, L=4, kind="nearly_full"),
+}
+
+
+def crowded_case(name):
+    """-> (inputs of forward32, kind) of a CROWDED case: the crowded ortho_scene with, as in the hand-built lists of the GPU
+    tests, a face repeated within a pixel's list (every fifth row: slot 1 = slot 0) and opacities of exactly 1 and 0 (every
+    97th face each)."""
+    c = CROWDED[name]
+    F = c["F"]
+    sc = ortho_scene(B=2, H=48, W=64, L=c["L"], F=F, seed=0, holes=False, crowded=True)
+    if "opacity" in c:
+        sc["faces_opacity"] = np.random.RandomState(1).uniform(*c["opacity"], F).astype(np.float32)
+    sc["faces_opacity"][0::97] = 1.0
+    sc["faces_opacity"][50::97] = 0.0
+    rl = sc["render_layers"]
+    rl[:, ::5, :, 1] = rl[:, ::5, :, 0]
+    return sc, c["kind"]
+
+
+def check_crowded(kind, lo, hi, slots):
+    """The condition a crowded case relies on, on the restatement's counts alone."""
+    if kind == "overflow":
+        assert lo > slots, (lo, hi, slots)
+    else:
+        assert hi <= slots and lo > 0.8 * slots, (lo, hi, slots)

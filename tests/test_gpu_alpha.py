@@ -324,6 +324,57 @@ def test_layered_alpha_hand_built_lists(L):
     assert fwd["blend"].sum() > 100
 
 
+@pytest.mark.parametrize("name", list(lref.CROWDED))
+def test_layered_alpha_table_overflow_route(name):
+    """k_layer_composite_bwd<true> where the face table overflows or is nearly full (test_gpu_layer_composite.py's crowded
+    scenes): the alpha term goes straight to global memory in g[LC_OP]."""
+    from test_gpu_layer_composite import crowded
+    fwd = _check_layered(crowded(name, "alpha"), seed=21)
+    assert fwd["blend"].sum() > 20000 and (fwd["final_T"] == 0.0).any()
+
+
+@pytest.mark.parametrize("name", list(lref.CROWDED))
+def test_layered_color_depth_alpha_together_table_overflow_route(name):
+    """Colour, depth and alpha in one loss on the crowded scenes, so that the alpha term and the colour terms share an
+    overflowing g[LC_OP].  The zero-channel scene is the reference: its blue channel is -T, alpha = 1 + blue, so with the
+    upstream colour gradient on channels 0 and 1 only the loss is the restatement's for dL/dcolor = (g_0, g_1, g_A).  All four
+    gradients against lref.grads64 of that scene; of verts_color the channels 0 and 1 (alpha does not reach the colours: the
+    kernel's blue column is 0, the restatement's is the blue channel's own)."""
+    from test_gpu_layer_composite import crowded
+    sc = crowded(name, "colour + depth + alpha")
+    sc["verts_color"][:, 2] = 0.0
+    sc["background"][2] = -1.0
+    args = _layer_args(sc)
+    leaves = [a.clone().requires_grad_(True) if i in (3, 4, 5, 6) else a for i, a in enumerate(args)]
+    with _C.alpha_output(True):
+        color, depth, alpha = dm2.LayeredCompositeFunction.apply(*leaves)
+    fwd = lref.forward32(*[a.cpu() for a in args])
+    for got, want in ((color, fwd["color"]), (depth, fwd["depth_raw"]), (alpha, np.float32(1.0) - fwd["final_T"]),
+                      (alpha, np.float32(1.0) + fwd["color"][..., 2])):
+        assert np.array_equal(_bits(got.detach().cpu().numpy()), _bits(want))
+    gen = torch.Generator().manual_seed(22)
+    gc = torch.randn(color.shape, generator=gen); gc[..., 2] = 0.0
+    gd = torch.randn(depth.shape, generator=gen)
+    gA = torch.randn(alpha.shape, generator=gen)
+    ((gc.cuda() * color).sum() + (gd.cuda() * depth).sum() + (gA.cuda() * alpha).sum()).backward()
+    torch.cuda.synchronize()
+    gcz = gc.double().clone(); gcz[..., 2] = gA.double()
+    cargs = [a.cpu() for a in args]
+    want = lref.grads64(fwd, cargs[2], cargs[3], cargs[4], cargs[5], cargs[6], cargs[7], gcz, gd.double())
+    got = dict(verts_color=leaves[3].grad, faces_opacity=leaves[4].grad, faces_intense=leaves[5].grad, verts_ndc=leaves[6].grad)
+    got = {k: x.cpu().numpy() for k, x in got.items()}
+    assert not got["verts_color"][:, 2].any()
+    for name_, g, w in (("verts_color", got["verts_color"][:, :2], want["verts_color"][:, :2]),
+                        ("faces_opacity", got["faces_opacity"], want["faces_opacity"]),
+                        ("faces_intense", got["faces_intense"], want["faces_intense"]),
+                        ("verts_ndc", got["verts_ndc"], want["verts_ndc"])):
+        assert np.isfinite(g).all() and np.abs(w).max() > 0, name_
+        assert rel_linf(g, w) <= GRAD_TOL, (name_, rel_linf(g, w))
+    # the alpha term is in it: the opacity gradient of the same loss without alpha differs
+    no_alpha = lref.grads64(fwd, cargs[2], cargs[3], cargs[4], cargs[5], cargs[6], cargs[7], gc.double(), gd.double())
+    assert rel_linf(no_alpha["faces_opacity"], want["faces_opacity"]) > 0.01
+
+
 def test_layered_alpha_generated_layers():
     W, H, bidx = 128, 96, [1, 0]
     ts = scenes.tet_lattice(W, H, 5, seed=scenes.SEED_BASE + 87, num_cams=2).to("cuda")

@@ -387,15 +387,28 @@ def _check_layered(inp, min_nonzero):
     return fwd
 
 
-@pytest.mark.parametrize("L", [5, 12])
+@pytest.mark.parametrize("L", [5, 10, 12])
 def test_layered_hand_built_lists(L):
-    """Holes, out-of-range ids, a face repeated in a pixel's list (counted twice), opacities of exactly 0 and 1."""
+    """Holes, out-of-range ids, a face repeated in a pixel's list (counted twice), opacities of exactly 0 and 1.  L = 5, 10,
+    12: ids read one at a time, as pairs and as vectors of four (k_layer_composite<1 / 2 / 4, true>)."""
     sc = lref.ortho_scene(B=2, H=37, W=45, L=L, F=11, seed=L + 50)
     rl = sc["render_layers"]
     rl[:, ::3, :, 1] = rl[:, ::3, :, 0]
     sc["faces_opacity"][[2, 5]] = [0.0, 1.0]
     fwd = _check_layered(sc, min_nonzero=3)
     assert fwd["blend"].sum() > 100
+
+
+@pytest.mark.parametrize("name", list(lref.CROWDED))
+def test_layered_table_overflow_route(name):
+    """k_layer_composite<4, true> where the face table overflows or is nearly full (test_gpu_layer_composite.py's crowded
+    scenes): the blends that find no slot add alpha * T straight to face_weights[b, f]; B = 2, so the b * F offset counts."""
+    from test_gpu_layer_composite import crowded
+    sc = crowded(name, "face weights")
+    fwd = _check_layered(sc, min_nonzero=int(0.8 * sc["faces"].shape[0]))
+    want = layered_face_weights64(fwd, sc["faces_opacity"], sc["faces"].shape[0])
+    assert (want[0] > 0).sum() > 0.5 * want.shape[1] and (want[1] > 0).sum() > 0.5 * want.shape[1]
+    assert rel_linf(want[0], want[1]) > 0.1                                   # (the views' rows differ)
 
 
 def test_layered_cfg3_and_module():

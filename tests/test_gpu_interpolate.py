@@ -1,16 +1,13 @@
 """Renderer.interpolate / dm2_interpolate on the GPU against the contract's restatement (tests/interpolate_ref.py): the forward
 bit-equal to forward32, both gradients within GRAD_TOL of grads64; the table-overflow route of the attr scatter; ids and
 attr_faces rows out of range; needs_input_grad; the module path from rasterize to verts.grad; one full-size case."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
 import interpolate_ref as ref
 import rasterize_ref as rref
-from util import GRAD_TOL, ROOT, rel_linf, scenes
+from util import GRAD_TOL, rel_linf, scenes, table_capacity
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -118,11 +115,6 @@ def test_gradients_against_float64(name, L):
             _check_grads(rl, bary, attr, s["faces"], g, (name, L, C, per_view))
 
 
-def _table_capacity():
-    src = open(os.path.join(ROOT, "dmesh2_renderer_amd", "csrc", "dm2_face_table.h")).read()
-    return int(re.search(r"constexpr int LC_SLOTS = (\d+);", src).group(1))
-
-
 @pytest.mark.parametrize("C", [3, 16])
 def test_table_overflow_route(C):
     """Hand-built layers with more distinct faces per 16 x 16 tile than the scatter's LDS table holds: the faces that find no
@@ -131,7 +123,7 @@ def test_table_overflow_route(C):
     rl = np.random.RandomState(5).randint(0, F, shape).astype(np.int32)
     least = ref.distinct_per_tile(rl)
     print("distinct ids per tile, at least", least)
-    assert least > _table_capacity()
+    assert least > table_capacity()
     rng = np.random.RandomState(6)
     bary = rng.uniform(0, 1, shape + (3,)).astype(np.float32)
     af = rng.randint(0, N, (F, 3)).astype(np.int32)

@@ -1,12 +1,13 @@
 """LayeredRenderer.render / dm2_layers_composite on the GPU against the contract's restatement (tests/layer_composite_ref.py):
 forward bit-equal to the float32 pass, gradients within GRAD_TOL of the float64 pass; agreement with Renderer at
-aa_temperature 0 where both must agree; analytic rays; the module path with both host preps; full size."""
+aa_temperature 0 where both must agree; the face table's overflow route and a nearly full table on crowded scenes; layer lists
+at unaligned addresses; analytic rays; the module path with both host preps; full size."""
 import numpy as np
 import pytest
 import torch
 
 import layer_composite_ref as ref
-from util import GRAD_TOL, rel_linf, scenes
+from util import GRAD_TOL, rel_linf, scenes, table_capacity
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -84,6 +85,67 @@ def test_hand_built_lists(L):
     # every kind of layer occurs in the blends
     f_bl = np.where(fwd["blend"], fwd["fs"], -1)
     assert (f_bl == 5).any() and (f_bl == 2).any()
+
+
+def crowded(name, what):
+    """A crowded case of the restatement (layer_composite_ref.CROWDED) with the condition it is there for asserted on the
+    restatement's own blends, and the range printed."""
+    sc, kind = ref.crowded_case(name)
+    fwd = ref.forward32(**sc)
+    lo, hi = ref.distinct_blended_per_tile(fwd)
+    print(f"{what} {name}: {lo}..{hi} distinct blended faces per tile, table of {table_capacity()} slots")
+    ref.check_crowded(kind, lo, hi, table_capacity())
+    return sc
+
+
+@pytest.mark.parametrize("name", list(ref.CROWDED))
+def test_table_overflow_route(name):
+    """k_layer_composite_bwd<false> where lc_slot finds no slot: every face covers the frame, so a 16 x 16 tile blends more
+    distinct faces than the table holds (overflow: most hits add their 14 components straight to global memory) or nearly as
+    many (nearly full: probe chains fail for a few faces while slots remain free, both routes in one tile).  B = 2: the
+    view offsets of dndc and dintense count.  Opacities of exactly 0 and 1 and a face twice in a pixel's list, as in
+    test_hand_built_lists."""
+    sc = crowded(name, "composite")
+    fwd, want = _check_op(sc, seed=7)
+    f_bl = np.where(fwd["blend"], fwd["fs"], -1)
+    assert (fwd["final_T"] == 0.0).any() and (sc["faces_opacity"][f_bl[f_bl >= 0]] == 0.0).any()
+    assert ((f_bl[..., 0] == f_bl[..., 1]) & (f_bl[..., 0] >= 0)).any()
+    assert all(np.abs(want[k]).max() > 0 for k in GRADS)
+    assert (np.abs(want["faces_intense"][1]) > 0).sum() > 0.5 * sc["faces"].shape[0]          # (the second view's rows too)
+
+
+@pytest.mark.parametrize("L", [4, 8])
+@pytest.mark.parametrize("skip", [1, 2], ids=["4_bytes", "8_bytes"])
+def test_unaligned_layers_give_the_same_bits(L, skip):
+    """render_layers as a contiguous view that starts 4 or 8 bytes into its storage: launch_layer_composite reads the ids one
+    at a time or as 8-byte pairs instead of 16-byte vectors.  Same forward bits as the aligned call, gradients within
+    GRAD_TOL of float64, and the same once more with face weights."""
+    from face_weights_ref import layered_face_weights64
+    from test_gpu_face_weights import check_weights
+    sc = ref.ortho_scene(B=2, H=37, W=45, L=L, F=11, seed=20 + L)
+    sc["render_layers"][:, ::3, :, 1] = sc["render_layers"][:, ::3, :, 0]
+    sc["faces_opacity"][[2, 5]] = [0.0, 1.0]
+    aligned = torch.from_numpy(sc["render_layers"]).cuda()
+    store = torch.empty(aligned.numel() + 4, dtype=torch.int32, device="cuda")
+    v = store[skip:skip + aligned.numel()].view(aligned.shape)
+    v.copy_(aligned)
+    assert aligned.data_ptr() % 16 == 0
+    assert v.data_ptr() % 16 in (4, 8) and v.data_ptr() % 16 == 4 * skip and v.is_contiguous()
+    t = {k: torch.from_numpy(np.ascontiguousarray(x)).cuda() for k, x in sc.items()}
+    names = ("verts", "faces", "verts_color", "faces_opacity", "faces_intense", "verts_ndc", "background", "ray_o", "ray_d")
+    rest = [t[k] for k in names]
+    want = _C.composite_layers_cuda(aligned, *rest)
+    got = _C.composite_layers_cuda(v, *rest)
+    with _C.face_weights_output(True):
+        want_w = _C.composite_layers_cuda(aligned, *rest)
+        got_w = _C.composite_layers_cuda(v, *rest)
+    torch.cuda.synchronize()
+    assert len(got) == 4 and len(got_w) == 5
+    for i in range(4):
+        assert torch.equal(got[i], want[i]) and torch.equal(got_w[i], want[i]) and torch.equal(want_w[i], want[i]), i
+    fwd, _ = _check_op(dict(sc, render_layers=v), seed=30 + L)                 # (forward bits and the four gradients, from v)
+    assert fwd["blend"].sum() > 500
+    check_weights(got_w[4], layered_face_weights64(fwd, sc["faces_opacity"], sc["faces"].shape[0]), min_nonzero=3)
 
 
 def _sheets(W, H, n_sheets, seed):

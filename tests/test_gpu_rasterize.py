@@ -1,12 +1,12 @@
 """Renderer.rasterize / dm2_rasterize_run on the GPU against the contract's restatement (tests/rasterize_ref.py): ids, counts,
 barycentrics and t bit-equal, gradients within GRAD_TOL of float64 autograd; analytic rays; agreement with generate and,
-through LayeredRenderer.render, with Renderer at aa_temperature 0; the module path."""
+through LayeredRenderer.render, with Renderer at aa_temperature 0; the backward's face-table overflow route; the module path."""
 import numpy as np
 import pytest
 import torch
 
 import rasterize_ref as ref
-from util import GRAD_TOL, rel_linf, scenes
+from util import GRAD_TOL, rel_linf, scenes, table_capacity
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -44,9 +44,11 @@ def _scene(name):
 
 
 @pytest.mark.parametrize("name", ref.SCENES)
-@pytest.mark.parametrize("L", [0, 1, 3, 8, 16, 17, 40])
+@pytest.mark.parametrize("L", [0, 1, 2, 3, 5, 8, 12, 16, 17, 32, 33, 40])
 @pytest.mark.parametrize("exist", [False, True])
 def test_op_bit_equal_to_restatement(name, L, exist):
+    """L = 1, 2, 3, 8, 16: k_rasterize<1, 2, 4, 8, 16> with full register lists; 5 and 12: lists of 8 and 16 slots of which
+    only L are used; 17, 33: a last pass of one slot after one or two full ones; 32: a list that ends on a pass boundary."""
     s = _scene(name)
     fe = s["fe"] if exist else None
     got = _C.rasterize_layers_cuda(*_dev(s, fe), L)
@@ -55,6 +57,8 @@ def test_op_bit_equal_to_restatement(name, L, exist):
     _equal(got, want, (name, L, exist))
     if name == "soup" and L > 16:
         assert (want["cnt"] > (32 if L == 40 and not exist else 16)).any()      # (the later passes had work)
+    if name == "soup" and not exist and L in (2, 5, 12, 32, 33):
+        assert (want["cnt"] == L).any()                                         # (some pixel fills every slot)
 
 
 def test_analytic_rays_bit_equal_to_the_ray_tensor_path():
@@ -160,7 +164,7 @@ def test_composite_agrees_with_renderer_at_temperature_zero():
 
 
 @pytest.mark.parametrize("name", ["soup", "lattice"])
-@pytest.mark.parametrize("L", [4, 16, 40])
+@pytest.mark.parametrize("L", [2, 4, 16, 40])
 def test_gradients_against_float64(name, L):
     s = _scene(name)
     args = _dev(s, s["fe"])
@@ -177,6 +181,36 @@ def test_gradients_against_float64(name, L):
         assert rel_linf(got, want) <= GRAD_TOL, (name, L, g_b is None, g_t is None, rel_linf(got, want))
     if L == 40 and name == "soup":
         assert int(cnt.max()) > 16                                             # (hits from the second pass)
+
+
+@pytest.mark.parametrize("name", ["overflow_L4", "overflow_L12", "nearly_full_L4"])
+def test_backward_table_overflow_route(name):
+    """k_rasterize_bwd where lc_slot finds no slot: a hit's nine components go to global memory as per-hit float casts
+    instead of into the fp64 LDS sum.  The lists, triangles and orthographic rays of the compositor's crowded scenes
+    (layer_composite_ref.CROWDED; the backward takes any lists, it needs no forward), a few ids out of range among them:
+    every 16 x 16 tile lists more distinct faces than the table holds, or nearly as many."""
+    import layer_composite_ref as lref
+    sc, kind = lref.crowded_case(name)
+    F = sc["faces"].shape[0]
+    rl = sc["render_layers"].copy()
+    pick = np.random.RandomState(9).choice(rl.size, 600, replace=False)
+    rl.reshape(-1)[pick] = np.array([-1, F, F + 7], np.int32)[np.arange(600) % 3]
+    listed = (rl >= 0) & (rl < F)                          # (this kernel's table is keyed by every listed id in range)
+    lo, hi = lref.distinct_blended_per_tile(dict(blend=listed, fs=rl))
+    print(f"rasterize backward {name}: {lo}..{hi} distinct listed faces per tile, table of {table_capacity()} slots")
+    lref.check_crowded(kind, lo, hi, table_capacity())
+    c = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    layers, verts, faces, ro, rd = c(rl), c(sc["verts"]), c(sc["faces"]), c(sc["ray_o"]), c(sc["ray_d"])
+    gen = torch.Generator().manual_seed(10)
+    gb = torch.randn(rl.shape + (3,), generator=gen)
+    gt = torch.randn(rl.shape, generator=gen)
+    for g_b, g_t in ((gb, gt), (gb, None), (None, gt)):
+        got = _C.rasterize_layers_backward_cuda(layers, verts, faces, ro, rd, None if g_b is None else g_b.cuda(),
+                                                None if g_t is None else g_t.cuda()).cpu().numpy()
+        want = ref.grads64(sc["verts"], sc["faces"], rl, sc["ray_o"], sc["ray_d"], g_b, g_t)
+        assert np.isfinite(got).all() and np.abs(want).max() > 0
+        assert (np.abs(want).max(-1) > 0).sum() > 0.9 * want.shape[0]          # (nearly every vertex has a gradient to lose)
+        assert rel_linf(got, want) <= GRAD_TOL, (name, g_b is None, g_t is None, rel_linf(got, want))
 
 
 def test_module_path():

@@ -3,8 +3,6 @@ to forward32, both gradients within GRAD_TOL of grads64; the table-overflow rout
 (every lane on a few texels); borders; needs_input_grad; argument checks; the module path from rasterize to verts.grad; one
 full-size case."""
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +11,7 @@ import torch
 import interpolate_ref as iref
 import rasterize_ref as rref
 import texture_ref as ref
-from util import GRAD_TOL, ROOT, rel_linf, scenes
+from util import GRAD_TOL, rel_linf, scenes, table_capacity
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -158,11 +156,6 @@ def test_gradient_grid_covers_every_axis():
     assert [len(s) for s in seen] == [len(CS), 2, 2, len(LS), len(SIZES), 3]
 
 
-def _table_capacity():
-    src = open(os.path.join(ROOT, "dmesh2_renderer_amd", "csrc", "dm2_face_table.h")).read()
-    return int(re.search(r"constexpr int LC_SLOTS = (\d+);", src).group(1))
-
-
 @pytest.mark.parametrize("C", [3, 16])
 @pytest.mark.parametrize("boundary_mode", ref.BOUNDARIES)
 def test_table_overflow_route(C, boundary_mode):
@@ -173,7 +166,7 @@ def test_table_overflow_route(C, boundary_mode):
     uv = rng.uniform(0.0, 1.0, shape + (2,)).astype(np.float32)          # (beyond the border clamp would fold the samples)
     least = ref.distinct_texels_per_tile(uv, *size, None, "linear", boundary_mode)
     print("distinct texels per tile and layer, at least", least)
-    assert least > _table_capacity()
+    assert least > table_capacity()
     rl = rng.integers(-1, 6, shape).astype(np.int32)
     for per_view in (False, True):
         tex = _tex(rng, shape[0], size, C, per_view)

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import layer_composite_ref as ref
-from util import ROOT  # noqa: F401  (puts the repository on sys.path)
+from util import ROOT, table_capacity  # noqa: F401  (ROOT: puts the repository on sys.path)
 
 from dmesh2_renderer_amd import _C
 
@@ -115,6 +115,45 @@ def test_opacity_one_ends_the_list():
     g = ref.grads64(fwd, sc["faces"], sc["verts_color"], sc["faces_opacity"], sc["faces_intense"], sc["verts_ndc"],
                     sc["background"], np.ones(fwd["color"].shape), np.ones(fwd["depth_raw"].shape))
     assert all(np.isfinite(v).all() for v in g.values()) and np.abs(g["faces_opacity"]).max() > 0
+
+
+def test_default_ortho_scene_is_not_crowded():
+    """``crowded`` off leaves the scene as it was: same arrays as the crowded one but for the triangles' xy."""
+    a, b = ref.ortho_scene(seed=3, holes=False), ref.ortho_scene(seed=3, holes=False, crowded=True)
+    for k in a:
+        if k != "verts":
+            assert np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["verts"][:, 2], b["verts"][:, 2])
+    ta, tb = a["verts"].reshape(-1, 3, 3)[:, :, :2], b["verts"].reshape(-1, 3, 3)[:, :, :2]
+    assert np.allclose(tb - tb.mean(1, keepdims=True), 5 * (ta - ta.mean(1, keepdims=True)), atol=1e-5)
+    assert ref.forward32(**b)["blend"].mean() > 0.99 > ref.forward32(**a)["blend"].mean()
+
+
+@pytest.mark.parametrize("name", list(ref.CROWDED))
+def test_crowded_cases_against_the_face_table(name):
+    """The scenes the GPU tests use for the face table's overflow route (dm2_face_table.h: lc_slot returns -1) hold what
+    those tests rely on, against the LC_SLOTS the header has today: every 16 x 16 tile blends more distinct faces than the
+    table has slots (overflow), or at most that many and more than 0.8 of them (nearly full).  And on them the float32 pass
+    is the float64 one: per pixel the blend weights alpha * T sum to at most 1 and a layer's term (colour * intensity <= 1.5,
+    |z| <= 1) carries about 9 roundings of its own, 2 per layer in front of it through T and one of the running sum, hence
+    1.5 * (3 L + 12) units of 2^-24."""
+    sc, kind = ref.crowded_case(name)
+    L, F = sc["render_layers"].shape[-1], sc["faces"].shape[0]
+    fwd = ref.forward32(**sc)
+    lo, hi = ref.distinct_blended_per_tile(fwd)
+    print(f"{name}: F = {F}, L = {L}, {fwd['blend'].mean():.4f} of the slots blend, {lo}..{hi} distinct blended faces per tile, "
+          f"table of {table_capacity()}")
+    ref.check_crowded(kind, lo, hi, table_capacity())
+    assert kind in ("overflow", "nearly_full")
+    # the edits are met: opacity-1 faces ended lists, opacity-0 faces blended, a face blended twice in a pixel
+    f_bl = np.where(fwd["blend"], fwd["fs"], -1)
+    assert (fwd["final_T"] == 0.0).sum() > 100 and (sc["faces_opacity"][f_bl[f_bl >= 0]] == 0.0).sum() > 100
+    assert ((f_bl[..., 0] == f_bl[..., 1]) & (f_bl[..., 0] >= 0)).sum() > 100
+    t64 = lambda k: torch.tensor(sc[k], dtype=torch.float64)
+    c, d = ref.composite64(fwd, sc["faces"], t64("verts_color"), t64("faces_opacity"), t64("faces_intense"),
+                           t64("verts_ndc")[..., 2], sc["background"])
+    bound = 1.5 * (3 * L + 12) * 2.0 ** -24
+    assert np.abs(c.numpy() - fwd["color"]).max() <= bound and np.abs(d.numpy() - fwd["depth_raw"]).max() <= bound
 
 
 def test_composite_layers_cuda_refuses_cpu_tensors():

@@ -64,6 +64,13 @@ def to_numpy_args(args):
     return [a.detach().cpu().numpy() if torch.is_tensor(a) else a for a in args]
 
 
+def table_capacity():
+    """LC_SLOTS of the layer kernels' per-block face table, read from dm2_face_table.h."""
+    import re
+    src = open(os.path.join(ROOT, "dmesh2_renderer_amd", "csrc", "dm2_face_table.h")).read()
+    return int(re.search(r"constexpr int LC_SLOTS = (\d+);", src).group(1))
+
+
 def rel_linf(a, b):
     a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
     return float(np.max(np.abs(a - b)) / max(float(np.max(np.abs(b))), 1e-12)) if a.size else 0.0
