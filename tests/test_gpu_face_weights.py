@@ -16,6 +16,7 @@ import torch
 import layer_composite_ref as lref
 from face_weights_ref import layered_face_weights64
 from util import from_image_oracle_args, rel_linf, scenes, soup_args, to_numpy_args
+from util import spy_library as _spy_library
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -142,28 +143,6 @@ def test_weights_tables_from_image():
     with _C.aa_grad_to_verts(True), _C.tables_from_image(True), _C.face_weights_output(True):
         out = _C.render_forward_cuda(*a)
     check_weights(out[10], want)
-
-
-class _LibSpy:
-    """The library with some entry points wrapped (render_forward_cuda looks it up once per call through load_library)."""
-
-    def __init__(self, lib, **fns):
-        self._lib = lib
-        self.__dict__.update(fns)
-
-    def __getattr__(self, name):
-        return getattr(self._lib, name)
-
-
-@contextlib.contextmanager
-def _spy_library(**fns):
-    lib = _C.load_library()
-    orig = _C.load_library
-    _C.load_library = lambda: _LibSpy(lib, **fns)
-    try:
-        yield lib
-    finally:
-        _C.load_library = orig
 
 
 def test_weights_over_budget_rerun_not_doubled():

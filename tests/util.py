@@ -33,6 +33,30 @@ def patched_C(**fns):
             setattr(_C, k, v)
 
 
+class _LibSpy:
+    """The library with some entry points wrapped (render_forward_cuda looks it up once per call through load_library)."""
+
+    def __init__(self, lib, **fns):
+        self._lib = lib
+        self.__dict__.update(fns)
+
+    def __getattr__(self, name):
+        return getattr(self._lib, name)
+
+
+@contextlib.contextmanager
+def spy_library(**fns):
+    """``with spy_library(dm2_forward=f): ...`` -- the shim's calls of the named C entry points go to the given functions
+    (which call the real ones of the yielded library as they see fit); every other entry point is the library's."""
+    lib = _C.load_library()
+    orig = _C.load_library
+    _C.load_library = lambda: _LibSpy(lib, **fns)
+    try:
+        yield lib
+    finally:
+        _C.load_library = orig
+
+
 def capture_forward_args(sc, batch_idx, patch_min, pw, ph, temp=1.0, K=20, device="cpu"):
     """Run the package's host prep (Renderer.forward) and return the 21 boundary args."""
     got = {}
