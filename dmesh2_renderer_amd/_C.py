@@ -684,7 +684,9 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
         cnt = torch.zeros((B, height, width), dtype=i32, device=dev)              # render.cu:437
         layers = torch.full((B, height, width, num_layers), -1, dtype=i32, device=dev)   # render.cu:438
         N, Tn, BF = B * height * width, _tiles(B, width, height), B * F
-        if N == 0:
+        if N == 0 or F == 0 or T == 0:
+            # no pixels, no face to hit, or no tet to enter (a walk starts in a tet: without tets every first_tet is -1, and
+            # face_tets may still name tets that are not there): the filled defaults, nothing is launched
             return layers, cnt
         face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn))
         img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_IMAGE, N, Tn))
