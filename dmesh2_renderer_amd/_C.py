@@ -26,6 +26,11 @@ and a texture sampled at such an image of UVs (Renderer.texture):
     texture_cuda(uv, tex, render_layers, filter_mode, boundary_mode) -> out,
     texture_backward_cuda(...those 5..., grad_out, need_tex, need_uv) -> (dL/dtex, dL/duv)
 
+and such per-slot values blended into an image (Renderer.composite; not composite_layers_cuda, which shades by itself):
+
+    composite_cuda(values, alpha, render_layers, background) -> (out, acc, final_T, n_contrib),
+    composite_backward_cuda(...those 4..., n_contrib, grad_out, grad_acc, need_values, need_alpha) -> (dL/dvalues, dL/dalpha)
+
 Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
 its gradient as the keyword ``dL_dout_alpha``.  Under ``face_weights_output`` render_forward_cuda and composite_layers_cuda
 append the per-face blend weights (B,F), behind everything else they return; they have no gradient.
@@ -127,6 +132,8 @@ EXPORTS = {
     "dm2_interpolate_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 8),
     "dm2_texture": (ctypes.c_int, [_i32] * 10 + [_vp] * 5),
     "dm2_texture_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
+    "dm2_composite": (ctypes.c_int, [_i32] * 7 + [_vp] * 9),
+    "dm2_composite_backward": (ctypes.c_int, [_i32] * 7 + [_vp] * 10),
     "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -951,6 +958,94 @@ def texture_backward_cuda(uv, tex, render_layers, filter_mode, boundary_mode, gr
         if lib.dm2_texture_backward(*sizes, _ptr(rl), _ptr(uvc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(duv), _stream(dev)):
             raise _err(lib, "texture_backward_cuda")
     return dtex, duv
+
+
+COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1      # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*
+
+
+def _composite_args(values, alpha, render_layers, background, n_contrib=None, grad_out=None, grad_acc=None):
+    """Checks of a composite call -> (sizes (B, H, W, L, C, F, alpha_mode), contiguous tensors, device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(values.dim() != 5, f"values must have dimensions (B, H, W, L, C), got {tuple(values.shape)}")
+    B, H, W, L, C = (int(x) for x in values.shape)
+    bad(C < 1, "values must have at least one channel")
+    bad(alpha.dim() not in (1, 4), f"alpha must have dimensions {(B, H, W, L)} (per slot) or (F,) (per face), got {tuple(alpha.shape)}")
+    per_face = alpha.dim() == 1
+    bad(not per_face and tuple(alpha.shape) != (B, H, W, L),
+        f"alpha must have dimensions {(B, H, W, L)} (per slot) or (F,) (per face), got {tuple(alpha.shape)}")
+    bad(per_face and render_layers is None, "a per-face alpha (F,) needs render_layers")
+    bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
+    bad(background is not None and tuple(background.shape) != (C,),
+        f"background must have dimensions {(C,)}, got {tuple(background.shape) if background is not None else None}")
+    bad(n_contrib is not None and tuple(n_contrib.shape) != (B, H, W),
+        f"n_contrib must have dimensions {(B, H, W)}, got {tuple(n_contrib.shape) if n_contrib is not None else None}")
+    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, C),
+        f"grad_out must have dimensions {(B, H, W, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
+    bad(grad_acc is not None and tuple(grad_acc.shape) != (B, H, W),
+        f"grad_acc must have dimensions {(B, H, W)}, got {tuple(grad_acc.shape) if grad_acc is not None else None}")
+    f32, i32 = torch.float32, torch.int32
+    named = (("values", values, f32), ("alpha", alpha, f32), ("render_layers", render_layers, i32), ("background", background, f32),
+             ("n_contrib", n_contrib, i32), ("grad_out", grad_out, f32), ("grad_acc", grad_acc, f32))
+    dev = _require_gpu(*[t for _, t, _ in named if t is not None])
+    ts = []
+    for name, t, dt in named:
+        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    F = int(alpha.size(0)) if per_face else 0
+    return (B, H, W, L, C, F, COMPOSITE_ALPHA_PER_FACE if per_face else COMPOSITE_ALPHA_PER_SLOT), ts, dev
+
+
+def composite_cuda(values, alpha, render_layers=None, background=None):
+    """Per-slot values blended front to back into an image (include/dm2_hip.h: dm2_composite).
+
+    values (B,H,W,L,C) float32, alpha (B,H,W,L) float32 per slot or (F,) float32 per face (gathered by render_layers),
+    render_layers (B,H,W,L) int32 or None (per-slot alpha only), background (C,) float32 or None -> (out (B,H,W,C), acc (B,H,W)
+    = 1 - T, final_T (B,H,W), n_contrib (B,H,W) int32)."""
+    lib = load_library()
+    sizes, (vc, al, rl, bg, _, _, _), dev = _composite_args(values, alpha, render_layers, background)
+    B, H, W, L, C = sizes[:5]
+    f32 = torch.float32
+    if B * H * W == 0 or L == 0:                                           # nothing blends (T = 1): no launch
+        out = torch.zeros((B, H, W, C), dtype=f32, device=dev) if bg is None else bg.expand(B, H, W, C).contiguous()
+        return (out, torch.zeros((B, H, W), dtype=f32, device=dev), torch.ones((B, H, W), dtype=f32, device=dev),
+                torch.zeros((B, H, W), dtype=torch.int32, device=dev))
+    out = torch.empty((B, H, W, C), dtype=f32, device=dev)                 # (every element written by the kernel)
+    acc = torch.empty((B, H, W), dtype=f32, device=dev)
+    final_T = torch.empty((B, H, W), dtype=f32, device=dev)
+    n_contrib = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        if lib.dm2_composite(*sizes, _ptr(vc), _ptr(al), _ptr(rl), _ptr(bg), _ptr(out), _ptr(acc), _ptr(final_T), _ptr(n_contrib),
+                             _stream(dev)):
+            raise _err(lib, "composite_cuda")
+    return out, acc, final_T, n_contrib
+
+
+def composite_backward_cuda(values, alpha, render_layers, background, n_contrib, grad_out, grad_acc, need_values, need_alpha):
+    """Gradients of composite_cuda (dm2_composite_backward) for grad_out (B,H,W,C) and grad_acc (B,H,W), either may be None ->
+    (dL_dvalues (B,H,W,L,C) or None, dL_dalpha of alpha's shape or None): only what ``need_values`` / ``need_alpha`` ask for is
+    computed; with both upstream gradients None nothing runs and both are None."""
+    lib = load_library()
+    sizes, (vc, al, rl, bg, nc, go, ga), dev = _composite_args(values, alpha, render_layers, background, n_contrib, grad_out, grad_acc)
+    B, H, W, L, C = sizes[:5]
+    f32 = torch.float32
+    if not (need_values or need_alpha) or (go is None and ga is None):
+        return None, None
+    per_face = sizes[6] == COMPOSITE_ALPHA_PER_FACE
+    if B * H * W == 0 or L == 0:
+        return (torch.zeros((B, H, W, L, C), dtype=f32, device=dev) if need_values else None,
+                torch.zeros(tuple(alpha.shape), dtype=f32, device=dev) if need_alpha else None)
+    dvalues = torch.empty((B, H, W, L, C), dtype=f32, device=dev) if need_values else None      # (every element written)
+    dalpha = None
+    if need_alpha:                                                         # (per slot: every element written; per face: summed into)
+        dalpha = torch.zeros(tuple(alpha.shape), dtype=f32, device=dev) if per_face else torch.empty((B, H, W, L), dtype=f32, device=dev)
+    with torch.cuda.device(dev):
+        if lib.dm2_composite_backward(*sizes, _ptr(vc), _ptr(al), _ptr(rl), _ptr(bg), _ptr(nc), _ptr(go), _ptr(ga), _ptr(dvalues),
+                                      _ptr(dalpha), _stream(dev)):
+            raise _err(lib, "composite_backward_cuda")
+    return dvalues, dalpha
 
 
 def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,

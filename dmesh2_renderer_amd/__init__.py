@@ -11,7 +11,8 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   ``Renderer.interpolate()``: those hits turned into an image of any C-channel vertex attribute, differentiable w.r.t.
   the attribute and the barycentrics (``InterpolateFunction``), and ``Renderer.texture()``: a channel-last texture sampled
   at such an image of UVs (bilinear or nearest, wrap or clamp), differentiable w.r.t. the texture and the UVs
-  (``TextureFunction``)
+  (``TextureFunction``), and ``Renderer.composite()``: such per-slot values blended front to back into an image and an
+  alpha image, differentiable w.r.t. the values and the per-slot or per-face opacities (``CompositeFunction``)
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -350,6 +351,24 @@ class Renderer(torch.nn.Module):
         rl = None if render_layers is None else render_layers.to(i32)
         return TextureFunction.apply(uv.to(f32), tex.to(f32), rl, filter_mode, boundary_mode)
 
+    def composite(self, values: torch.Tensor, alpha: torch.Tensor, render_layers: torch.Tensor = None,
+                  background: torch.Tensor = None):
+        """Shaded layers blended front to back into an image (not in the reference): values (B,H,W,L,C) float32, any C >= 1
+        (what ``interpolate`` or ``texture`` return, or anything computed from them), alpha (B,H,W,L) float32, one opacity per
+        slot, or (F,) float32, one per face (``faces_opacity``; gathered as alpha[render_layers] inside the op, which then
+        needs ``render_layers``), render_layers (B,H,W,L) int32 or None, background (C,) float32 or None (no background term)
+        -> out (B,H,W,C) float32, acc (B,H,W) float32 = 1 - T (the alpha image of ``return_alpha``).
+
+        ``LayeredRenderer.render``'s blend with the colour supplied by the caller: per pixel, from T = 1, every non-empty
+        slot adds values * (a * T) and multiplies T by 1 - a, until T < 1e-4; out = the sum + T * background.  A slot with a
+        negative id (per-face alpha: an id outside [0, F)) is empty: neither its values nor its alpha are looked at.  alpha is
+        used as it stands (no clamp).  Differentiable w.r.t. ``values`` and ``alpha`` (``CompositeFunction``); ``background``
+        gets no gradient, and nothing flows through which slots are listed."""
+        i32, f32 = torch.int32, torch.float32
+        rl = None if render_layers is None else render_layers.to(i32)
+        bg = None if background is None else background.to(f32)
+        return CompositeFunction.apply(values.to(f32), alpha.to(f32), rl, bg)
+
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
         f32 = torch.float32
@@ -551,6 +570,39 @@ class TextureFunction(torch.autograd.Function):
         render_layers = ctx.saved_tensors[2] if ctx.has_layers else None
         dtex, duv = _C.texture_backward_cuda(uv, tex, render_layers, *ctx.modes, grad_out, need_tex, need_uv)
         return duv, dtex, None, None, None
+
+
+class CompositeFunction(torch.autograd.Function):
+    """out, acc = the front-to-back blend of per-slot values (``_C.composite_cuda``): O += values (a T), T *= 1 - a over the
+    non-empty slots until T < 1e-4; out = O + T background, acc = 1 - T.
+
+    Inputs: values (B,H,W,L,C)*, alpha (B,H,W,L)* per slot or (F,)* per face, render_layers (B,H,W,L) int32 or None, background
+    (C,) or None.  Outputs: out (B,H,W,C), acc (B,H,W).  (* = receives a gradient.)  A blended slot gets (a T) g for its values
+    and T (S - R) for its alpha (the back pass of include/dm2_hip.h, no division); empty slots and slots behind the stop get
+    zeros.  Output gradients are not materialised: an output left out of the loss costs nothing, and with both left out no
+    kernel runs.  Only the gradients ``needs_input_grad`` asks for are computed.
+    """
+
+    @staticmethod
+    def forward(ctx, values, alpha, render_layers, background):
+        ctx.set_materialize_grads(False)
+        out, acc, _, n_contrib = _C.composite_cuda(values.detach(), alpha.detach(), render_layers, background)
+        ctx.has = (render_layers is not None, background is not None)
+        ctx.save_for_backward(values.detach(), alpha.detach(), n_contrib, *(t for t in (render_layers, background) if t is not None))
+        return out, acc
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_acc):
+        need_values, need_alpha = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (grad_out is None and grad_acc is None) or not (need_values or need_alpha):
+            return None, None, None, None
+        values, alpha, n_contrib = ctx.saved_tensors[:3]
+        rest = list(ctx.saved_tensors[3:])
+        render_layers = rest.pop(0) if ctx.has[0] else None
+        background = rest.pop(0) if ctx.has[1] else None
+        dvalues, dalpha = _C.composite_backward_cuda(values, alpha, render_layers, background, n_contrib, grad_out, grad_acc,
+                                                     need_values, need_alpha)
+        return dvalues, dalpha, None, None
 
 
 class LayeredRenderer(Renderer):

@@ -559,6 +559,51 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
     return 0;
 }
 
+static int check_composite_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C, int32_t F, int32_t alpha_mode) {
+    if (B < 0 || H < 0 || W < 0 || L < 0 || F < 0) return fail("composite: negative size");
+    if (C < 1 || C > (1 << 20)) return fail("composite: C must lie in [1, 2^20]");
+    if (alpha_mode != DM2_COMPOSITE_ALPHA_PER_SLOT && alpha_mode != DM2_COMPOSITE_ALPHA_PER_FACE)
+        return fail("composite: unknown alpha_mode");
+    if (((int64_t)B * H * W + 255) / 256 > 0x7FFFFFFF || B > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
+        return fail("composite: too many pixels, rows or views");
+    return 0;
+}
+
+int dm2_composite(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C, int32_t F, int32_t alpha_mode, const float* values,
+                  const float* alpha, const int32_t* render_layers, const float* background, float* out, float* out_acc,
+                  float* out_final_T, int32_t* out_n_contrib, void* stream) {
+    if (check_composite_sizes(B, H, W, L, C, F, alpha_mode)) return 1;
+    if ((int64_t)B * H * W == 0) return 0;
+    if (!out) return fail("composite: out must not be null");
+    const int per_face = alpha_mode == DM2_COMPOSITE_ALPHA_PER_FACE;
+    if (L > 0) {
+        if (!values) return fail("composite: values must not be null");
+        if (per_face && !render_layers) return fail("composite: a per-face alpha needs render_layers");
+        if (!alpha && !(per_face && F == 0)) return fail("composite: alpha must not be null");
+    }
+    dm2::launch_composite(B, H, W, L, C, F, per_face, values, alpha, render_layers, background, out, out_acc, out_final_T,
+                          out_n_contrib, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_composite_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C, int32_t F, int32_t alpha_mode,
+                           const float* values, const float* alpha, const int32_t* render_layers, const float* background,
+                           const int32_t* n_contrib, const float* dL_dout, const float* dL_dacc, float* dL_dvalues,
+                           float* dL_dalpha, void* stream) {
+    if (check_composite_sizes(B, H, W, L, C, F, alpha_mode)) return 1;
+    if ((int64_t)B * H * W == 0 || L == 0 || (!dL_dvalues && !dL_dalpha) || (!dL_dout && !dL_dacc)) return 0;
+    const int per_face = alpha_mode == DM2_COMPOSITE_ALPHA_PER_FACE;
+    if (!n_contrib) return fail("composite_backward: n_contrib must not be null");
+    if (per_face && !render_layers) return fail("composite_backward: a per-face alpha needs render_layers");
+    if (!alpha && !(per_face && F == 0)) return fail("composite_backward: alpha must not be null");
+    if (dL_dalpha && dL_dout && !values) return fail("composite_backward: values must not be null");
+    dm2::launch_composite_backward(B, H, W, L, C, F, per_face, values, alpha, render_layers, background, n_contrib, dL_dout,
+                                   dL_dacc, dL_dvalues, dL_dalpha, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_composite_desc(const dm2_layer_composite_desc* d) {
     if (!d) return fail("null descriptor");
     if (d->B < 0 || d->P < 0 || d->F < 0 || d->W < 0 || d->H < 0 || d->L < 0) return fail("negative size in descriptor");

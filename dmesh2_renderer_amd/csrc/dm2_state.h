@@ -245,6 +245,15 @@ void launch_texture(int B, int H, int W, int L, int Ht, int Wt, int C, int view_
 void launch_texture_backward(int B, int H, int W, int L, int Ht, int Wt, int C, int view_textures, int filter, int boundary,
                              const int32_t* render_layers, const float* uv, const float* tex, const float* dL_dout,
                              float* dL_dtex, float* dL_duv, hipStream_t st);
+// Renderer.composite (dm2_composite.hip): every element of out / out_acc / out_final_T / out_n_contrib / dL_dvalues and of the
+// per-slot dL_dalpha is written; the backward adds into the per-face dL_dalpha (per_face != 0).  B * H * W > 0, C >= 1; NULL:
+// render_layers (per-slot alpha only), background, any output but out, either upstream gradient, either output gradient.
+void launch_composite(int B, int H, int W, int L, int C, int F, int per_face, const float* values, const float* alpha,
+                      const int32_t* render_layers, const float* background, float* out, float* out_acc, float* out_final_T,
+                      int32_t* out_n_contrib, hipStream_t st);
+void launch_composite_backward(int B, int H, int W, int L, int C, int F, int per_face, const float* values, const float* alpha,
+                               const int32_t* render_layers, const float* background, const int32_t* n_contrib,
+                               const float* dL_dout, const float* dL_dacc, float* dL_dvalues, float* dL_dalpha, hipStream_t st);
 
 }  // namespace dm2
 

@@ -344,6 +344,42 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
                          int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex,
                          const float* dL_dout, float* dL_dtex, float* dL_duv, void* stream);
 
+/* Renderer.composite: per-slot values (dm2_interpolate's or dm2_texture's output, or anything shaded from them) blended front
+ * to back into an image: LayeredRenderer.render's blend with the colour supplied by the caller.
+ * values (B,H,W,L,C) float32, C >= 1; alpha float32: (B,H,W,L), one opacity per slot (DM2_COMPOSITE_ALPHA_PER_SLOT), or (F), one
+ * per face, gathered as alpha[render_layers[s]] (DM2_COMPOSITE_ALPHA_PER_FACE); render_layers (B,H,W,L) int32, or NULL with a
+ * per-slot alpha (no slot is empty then); background (C) float32 or NULL (no background term).  A slot is empty when its id is
+ * negative or, with a per-face alpha, outside [0, F).  Per pixel, all fp32, separate multiplies and adds in the written order,
+ * without contraction (bit-exact), from T = 1, O_c = 0, n = 0, for l = 0 .. L-1:
+ *   skip an empty slot (neither its values nor its alpha take part: NaNs there are harmless);
+ *   a = the slot's alpha as it stands (no clamp; a non-finite a of a non-empty slot propagates);
+ *   w = a * T;   O_c = O_c + values[l,c] * w for every c (also when w == 0);   T = T * (1 - a);   n = l + 1;
+ *   stop once T < 1e-4 (the slots behind take no part).
+ * out[c] = O_c + T * background[c] (O_c without a background) (B,H,W,C); out_acc = 1 - T (B,H,W); out_final_T = T (B,H,W);
+ * out_n_contrib = n (B,H,W) int32: what the backward takes.  out_acc, out_final_T and out_n_contrib may each be NULL.  Every
+ * element of the outputs is written: no pre-fill.  L == 0: out = background (or 0), T = 1, n = 0; values and alpha may then be
+ * NULL. */
+#define DM2_COMPOSITE_ALPHA_PER_SLOT 0
+#define DM2_COMPOSITE_ALPHA_PER_FACE 1
+int dm2_composite(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C, int32_t F, int32_t alpha_mode, const float* values,
+                  const float* alpha, const int32_t* render_layers, const float* background, float* out, float* out_acc,
+                  float* out_final_T, int32_t* out_n_contrib, void* stream);
+/* Gradients of dm2_composite for upstream g = dL_dout (B,H,W,C) and gA = dL_dacc (B,H,W); either may be NULL (zero; both NULL:
+ * nothing runs and nothing is written).  n_contrib (B,H,W) is the forward's: slot l of a pixel blended when it is not empty and
+ * l < n_contrib.  Per pixel, over its blended slots in order, T_l the transmittance in front of slot l (no division anywhere:
+ * an alpha of exactly 1 is fine):
+ *   dL_dvalues[l,c] = (a_l * T_l) * g[c];
+ *   S_l = sum_c g[c] * values[l,c];   K = sum_c g[c] * background[c] - gA   (missing terms 0);
+ *   from the last blended slot backwards, starting at R = K:   dL/da_l = T_l * (S_l - R),   then R = a_l * S_l + (1 - a_l) * R.
+ * dL_dvalues (B,H,W,L,C): every element is written, zeros in empty slots and behind the stop.  dL_dalpha per slot (B,H,W,L):
+ * likewise, a pure function of the inputs.  dL_dalpha per face (F): dL/da_l is added to dL_dalpha[render_layers[s]] over
+ * views, pixels and slots; zero-filled by the caller; float atomics: its last bits may vary from run to run.  Either output
+ * pointer may be NULL (not wanted: no phase of the kernel runs for it).  background gets no gradient. */
+int dm2_composite_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C, int32_t F, int32_t alpha_mode,
+                           const float* values, const float* alpha, const int32_t* render_layers, const float* background,
+                           const int32_t* n_contrib, const float* dL_dout, const float* dL_dacc, float* dL_dvalues,
+                           float* dL_dalpha, void* stream);
+
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
  *   1. skip f < 0 or f >= F (holes and out-of-range ids are allowed and never read through);
