@@ -31,6 +31,11 @@ and such per-slot values blended into an image (Renderer.composite; not composit
     composite_cuda(values, alpha, render_layers, background) -> (out, acc, final_T, n_contrib),
     composite_backward_cuda(...those 4..., n_contrib, grad_out, grad_acc, need_values, need_alpha) -> (dL/dvalues, dL/dalpha)
 
+and the analytic pixel coverage of listed faces, the anti-aliasing factor of such a blend's alpha (Renderer.coverage):
+
+    coverage_cuda(render_layers, verts_image, faces, temperature) -> cov,
+    coverage_backward_cuda(...those 4..., grad_cov) -> dL/dverts_image
+
 Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
 its gradient as the keyword ``dL_dout_alpha``.  Under ``face_weights_output`` render_forward_cuda and composite_layers_cuda
 append the per-face blend weights (B,F), behind everything else they return; they have no gradient.
@@ -134,6 +139,8 @@ EXPORTS = {
     "dm2_texture_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
     "dm2_composite": (ctypes.c_int, [_i32] * 7 + [_vp] * 9),
     "dm2_composite_backward": (ctypes.c_int, [_i32] * 7 + [_vp] * 10),
+    "dm2_coverage": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float] + [_vp] * 5),
+    "dm2_coverage_backward": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float] + [_vp] * 6),
     "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1046,6 +1053,66 @@ def composite_backward_cuda(values, alpha, render_layers, background, n_contrib,
                                       _ptr(dalpha), _stream(dev)):
             raise _err(lib, "composite_backward_cuda")
     return dvalues, dalpha
+
+
+def _coverage_args(render_layers, verts_image, faces, temperature, grad_cov=None):
+    """Checks of a coverage call -> (sizes (B, H, W, L, P, F, temperature), contiguous tensors, device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+    B, H, W, L = (int(x) for x in render_layers.shape)
+    bad(verts_image.dim() != 3 or verts_image.size(0) != B or verts_image.size(2) != 2,
+        f"verts_image must have dimensions ({B}, P, 2), got {tuple(verts_image.shape)}")
+    bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
+    bad(grad_cov is not None and tuple(grad_cov.shape) != (B, H, W, L),
+        f"grad_cov must have dimensions {(B, H, W, L)}, got {tuple(grad_cov.shape) if grad_cov is not None else None}")
+    temperature = float(temperature)
+    if not (0.0 <= temperature <= 1.0):
+        raise ValueError("temperature must be in the range [0, 1]")
+    f32, i32 = torch.float32, torch.int32
+    named = (("render_layers", render_layers, i32), ("verts_image", verts_image, f32), ("faces", faces, i32), ("grad_cov", grad_cov, f32))
+    dev = _require_gpu(*[t for _, t, _ in named if t is not None])
+    ts = []
+    for name, t, dt in named:
+        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    return (B, H, W, L, int(verts_image.size(1)), int(faces.size(0)), temperature), ts, dev
+
+
+def coverage_cuda(render_layers, verts_image, faces, temperature=1.0):
+    """The analytic pixel coverage of every listed slot (include/dm2_hip.h: dm2_coverage).
+
+    render_layers (B,H,W,L) int32 face ids over the full frame, verts_image (B,P,2) float32, faces (F,3) int32, temperature in
+    [0, 1] (ValueError otherwise) -> cov (B,H,W,L) float32: 0 in an empty slot and where the triangle misses the pixel, else
+    (1 - temperature) + area * temperature."""
+    lib = load_library()
+    sizes, (rl, vi, fc, _), dev = _coverage_args(render_layers, verts_image, faces, temperature)
+    B, H, W, L = sizes[:4]
+    cov = torch.empty((B, H, W, L), dtype=torch.float32, device=dev)       # (every element written by the kernel)
+    if B * H * W * L == 0:
+        return cov
+    with torch.cuda.device(dev):
+        if lib.dm2_coverage(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev)):
+            raise _err(lib, "coverage_cuda")
+    return cov
+
+
+def coverage_backward_cuda(render_layers, verts_image, faces, temperature, grad_cov):
+    """Gradient of coverage_cuda (dm2_coverage_backward) for grad_cov (B,H,W,L) -> dL_dverts_image (B,P,2), or None where
+    nothing flows: grad_cov None or temperature == 0 (no kernel runs)."""
+    lib = load_library()
+    sizes, (rl, vi, fc, gc), dev = _coverage_args(render_layers, verts_image, faces, temperature, grad_cov)
+    if gc is None or sizes[6] == 0.0:
+        return None
+    B, H, W, L, P, F = sizes[:6]
+    dimage = torch.zeros((B, P, 2), dtype=torch.float32, device=dev)       # (summed into)
+    if B * H * W * L == 0 or P == 0 or F == 0:
+        return dimage
+    with torch.cuda.device(dev):
+        if lib.dm2_coverage_backward(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(gc), _ptr(dimage), _stream(dev)):
+            raise _err(lib, "coverage_backward_cuda")
+    return dimage
 
 
 def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,

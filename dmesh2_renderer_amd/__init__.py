@@ -12,7 +12,9 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   the attribute and the barycentrics (``InterpolateFunction``), and ``Renderer.texture()``: a channel-last texture sampled
   at such an image of UVs (bilinear or nearest, wrap or clamp), differentiable w.r.t. the texture and the UVs
   (``TextureFunction``), and ``Renderer.composite()``: such per-slot values blended front to back into an image and an
-  alpha image, differentiable w.r.t. the values and the per-slot or per-face opacities (``CompositeFunction``)
+  alpha image, differentiable w.r.t. the values and the per-slot or per-face opacities (``CompositeFunction``), and
+  ``Renderer.coverage()``: the analytic pixel coverage of the listed faces, the anti-aliasing factor of such a blend's
+  alpha, differentiable w.r.t. the vertices and the cameras (``CoverageFunction``): what moves a silhouette
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -31,7 +33,7 @@ from . import _C
 from .pyrenderer import Triangles
 
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
-           "TextureFunction", "Triangles"]
+           "TextureFunction", "CoverageFunction", "Triangles"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -369,6 +371,31 @@ class Renderer(torch.nn.Module):
         bg = None if background is None else background.to(f32)
         return CompositeFunction.apply(values.to(f32), alpha.to(f32), rl, bg)
 
+    def coverage(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
+                 temperature: float = 1.0):
+        """The analytic pixel coverage of the listed faces (not in the reference): render_layers (B,H,W,L) int32 face ids over
+        the full frame (as ``rasterize`` / ``generate`` return them, or hand-built), verts (P,3), faces (F,3), temperature in
+        [0, 1] (ValueError otherwise) -> cov (B,H,W,L) float32, ``Renderer.forward``'s coverage ratio of a hit:
+        (1 - temperature) + area * temperature, area the overlap of the projected triangle with the pixel [x, x+1] x [y, y+1].
+        ``composite(values, faces_opacity[render_layers.clamp(min=0).long()] * cov, render_layers, background)`` then blends
+        anti-aliased layers, and a mask or silhouette loss moves ``verts``.
+
+        A slot whose id is outside [0, F), or whose face names a vertex outside [0, P), is empty: cov = 0.  Where the triangle
+        misses the pixel (or the clipper reports an error) cov = 0 too; at temperature 0 cov = 1 in every non-empty slot.
+        Whether the pixel's ray hits the face is not looked at.  Differentiable w.r.t. ``verts`` and, where they require grad,
+        the cameras, through the projection (``CoverageFunction``); nothing flows through which faces are listed."""
+        if not (0.0 <= float(temperature) <= 1.0):
+            raise ValueError("temperature must be in the range [0, 1]")
+        mv = self.mv[batch_mvp_idx]
+        proj = self.proj[batch_mvp_idx]
+        i32, f32 = torch.int32, torch.float32
+        if getattr(self, "fused_prep", False) and verts.is_cuda:
+            from . import prep
+            _, verts_image = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
+        else:
+            _, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
+        return CoverageFunction.apply(render_layers.to(i32), verts_image.to(f32), faces.to(i32), float(temperature))
+
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
         f32 = torch.float32
@@ -603,6 +630,32 @@ class CompositeFunction(torch.autograd.Function):
         dvalues, dalpha = _C.composite_backward_cuda(values, alpha, render_layers, background, n_contrib, grad_out, grad_acc,
                                                      need_values, need_alpha)
         return dvalues, dalpha, None, None
+
+
+class CoverageFunction(torch.autograd.Function):
+    """cov = the analytic overlap of each listed face with its pixel, mixed with the temperature (``_C.coverage_cuda``):
+    (1 - temperature) + area * temperature; 0 in an empty slot, where the clipper errs and where the area is 0.
+
+    Inputs: render_layers (B,H,W,L) int32, verts_image (B,P,2)*, faces (F,3) int32, temperature.  Output: cov (B,H,W,L).
+    (* = receives a gradient.)  A partially covered slot sends g temperature d(area)/d(corner) to the image coordinates of its
+    face's three vertices; nothing flows through which faces are listed.  The output gradient is not materialised: with cov
+    left out of the loss, or at temperature 0, no kernel runs.
+    """
+
+    @staticmethod
+    def forward(ctx, render_layers, verts_image, faces, temperature):
+        ctx.set_materialize_grads(False)
+        cov = _C.coverage_cuda(render_layers, verts_image.detach(), faces, temperature)
+        ctx.temperature = float(temperature)
+        ctx.save_for_backward(render_layers, verts_image.detach(), faces)
+        return cov
+
+    @staticmethod
+    def backward(ctx, grad_cov):
+        if grad_cov is None or ctx.temperature == 0.0 or not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        render_layers, verts_image, faces = ctx.saved_tensors
+        return None, _C.coverage_backward_cuda(render_layers, verts_image, faces, ctx.temperature, grad_cov), None, None
 
 
 class LayeredRenderer(Renderer):

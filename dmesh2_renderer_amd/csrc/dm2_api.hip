@@ -604,6 +604,37 @@ int dm2_composite_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C
     return 0;
 }
 
+static int check_coverage_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature) {
+    if (B < 0 || H < 0 || W < 0 || L < 0 || P < 0 || F < 0) return fail("coverage: negative size");
+    if (!(temperature >= 0.0f && temperature <= 1.0f)) return fail("coverage: temperature must be in the range [0, 1]");
+    if (B > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535) return fail("coverage: too many rows or views");
+    return 0;
+}
+
+int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                 const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream) {
+    if (check_coverage_sizes(B, H, W, L, P, F, temperature)) return 1;
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!render_layers || !out_cov) return fail("coverage: render_layers and out_cov must not be null");
+    if (F > 0 && !faces) return fail("coverage: faces must not be null");
+    if (F > 0 && P > 0 && !verts_image) return fail("coverage: verts_image must not be null");
+    dm2::launch_coverage(B, H, W, L, P, F, temperature, render_layers, verts_image, faces, out_cov, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_coverage_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                          const int32_t* render_layers, const float* verts_image, const int32_t* faces, const float* dL_dcov,
+                          float* dL_dverts_image, void* stream) {
+    if (check_coverage_sizes(B, H, W, L, P, F, temperature)) return 1;
+    if ((int64_t)B * H * W * L == 0 || F == 0 || P == 0 || temperature == 0.0f || !dL_dcov || !dL_dverts_image) return 0;
+    if (!render_layers || !faces || !verts_image) return fail("coverage_backward: render_layers, faces and verts_image must not be null");
+    dm2::launch_coverage_backward(B, H, W, L, P, F, temperature, render_layers, verts_image, faces, dL_dcov, dL_dverts_image,
+                                  (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_composite_desc(const dm2_layer_composite_desc* d) {
     if (!d) return fail("null descriptor");
     if (d->B < 0 || d->P < 0 || d->F < 0 || d->W < 0 || d->H < 0 || d->L < 0) return fail("negative size in descriptor");

@@ -254,6 +254,14 @@ void launch_composite(int B, int H, int W, int L, int C, int F, int per_face, co
 void launch_composite_backward(int B, int H, int W, int L, int C, int F, int per_face, const float* values, const float* alpha,
                                const int32_t* render_layers, const float* background, const int32_t* n_contrib,
                                const float* dL_dout, const float* dL_dacc, float* dL_dvalues, float* dL_dalpha, hipStream_t st);
+// Renderer.coverage (dm2_coverage.hip): every element of out_cov is written; the backward adds into dL_dverts_image (zero-filled
+// by the caller).  B * H * W * L > 0, 0 <= temperature <= 1 (the backward: > 0); faces may be NULL when F == 0, verts_image when
+// P == 0.
+void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* render_layers,
+                     const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st);
+void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* render_layers,
+                              const float* verts_image, const int32_t* faces, const float* dL_dcov, float* dL_dverts_image,
+                              hipStream_t st);
 
 }  // namespace dm2
 

@@ -380,6 +380,27 @@ int dm2_composite_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C
                            const int32_t* n_contrib, const float* dL_dout, const float* dL_dacc, float* dL_dvalues,
                            float* dL_dalpha, void* stream);
 
+/* Renderer.coverage: the analytic pixel coverage of every listed slot, the factor that makes a face's opacity an anti-aliased
+ * alpha on the deferred path (alpha = faces_opacity[id] * cov into dm2_composite) and lets a silhouette loss reach the vertices.
+ * render_layers (B,H,W,L) int32 face ids over the full frame; verts_image (B,P,2) float32, the projected vertices in pixel
+ * units; faces (F,3) int32; 0 <= temperature <= 1.  Per slot (b, y, x, l) with id f, all fp32, without contraction:
+ *   empty slot (f outside [0, F), or faces[f] names a vertex outside [0, P)): cov = 0;
+ *   temperature == 0: cov = 1 in every other slot (no clip is evaluated);
+ *   otherwise the triangle verts_image[b, faces[f]] is CCW-reordered and its six AA tables are built as under
+ *   DM2_FLAG_TABLES_FROM_IMAGE; area = its overlap with the pixel [x, x+1] x [y, y+1] by the reference's clipper (aa.h:446-504);
+ *   a clipper error or area == 0: cov = 0 (dm2_forward skips such a face); else
+ *   cov = (float)(1.0 * (double)(1.0f - temperature) + (double)(area * temperature))   (forward.cu:375-378 for a hit).
+ * Whether the pixel's ray hits the face is not looked at.  Every element of out_cov (B,H,W,L) is written: no pre-fill. */
+int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                 const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream);
+/* Gradient of dm2_coverage for upstream dL_dcov (B,H,W,L): every slot with a non-zero cov adds
+ * dL_dcov[s] * temperature * d(area)/d(corner k) to dL_dverts_image[b, v] (B,P,2), v the face's vertex that the reorder put at
+ * corner k; the Jacobian is the reference clipper's (zero at full cover).  dL_dverts_image is zero-filled by the caller; float
+ * atomics: its last bits may vary from run to run.  temperature == 0, dL_dcov NULL or dL_dverts_image NULL: nothing runs. */
+int dm2_coverage_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                          const int32_t* render_layers, const float* verts_image, const int32_t* faces, const float* dL_dcov,
+                          float* dL_dverts_image, void* stream);
+
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
  *   1. skip f < 0 or f >= F (holes and out-of-range ids are allowed and never read through);
