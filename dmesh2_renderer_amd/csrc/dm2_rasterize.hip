@@ -4,8 +4,9 @@
 //
 // Contract (include/dm2_hip.h, dm2_rasterize_run): per pixel of view b the candidates are the faces of its tile's list
 // (dm2_layers_plan: the verts_image bbox touches the tile, the NDC depth cull keeps the face) whose face_existence is not 0;
-// a hit is ray_tri_intersection with t >= 0, u >= 0, v >= 0, u + v <= 1 (k_first_intersect's test); the hits are ordered by
-// ascending (t, face id) and the first L are listed with bary = (1 - u - v, u, v) and t.  -ffp-contract=off: bit-exact.
+// a hit is ray_tri_intersection with t >= 0, u >= 0, v >= 0, u + v <= 1 (k_first_intersect's test) on a face whose plane the
+// ray does not lie in (rz_off_plane, below); the hits are ordered by ascending (t, face id) and the first L are listed with
+// bary = (1 - u - v, u, v) and t.  -ffp-contract=off: bit-exact.
 //
 // Layout: one lane per pixel, 16 x 16 tiles, the view on blockIdx.z; list chunks staged in LDS as k_first_intersect stages
 // them, the existence filter applied (and the survivors compacted) while staging.  Each lane keeps its KR nearest hits so far
@@ -16,7 +17,9 @@
 // Early exit (not part of the result): the tile list is sorted by min depth, so once a lane holds its slots full, a face
 // whose min depth lies beyond the largest max depth of the held faces cannot come nearer along this ray and the lane stops
 // (the K-wide form of k_first_intersect's stop, forward.cu:648-651).  Depth along a ray grows with t in front of the camera;
-// a face that crosses the camera plane has no such bound, as in the first-hit pass of generate.
+// a face that crosses the camera plane has no such bound, as in the first-hit pass of generate (and the plan may not have
+// put it into the tile's list at all: its bbox is that of mirrored projections).  The stop relies on a held hit's t lying
+// in its face's depth range: rz_off_plane keeps the noise t of a ray in the face's plane out of the slots.
 //
 // Backward: per listed slot the ray is intersected again and dL/dp_k = (g1 - g0) du/dp_k + (g2 - g0) dv/dp_k + g_t dt/dp_k,
 // in fp64 (rz_hit_grad), added into the per-block face table of dm2_face_table.h (fp64 slots), flushed as fp32 atomics.
@@ -47,6 +50,18 @@ struct RzList {
     float t[KR], u[KR], v[KR], md[KR];
     int id[KR];
 };
+
+// The hit rule's second half: the ray is off the face's plane, cos^2(rd, n) > RZ_PLANE_COS2 (|cos| > 5e-4) for n = E1 x E2.
+// For a ray in the plane Moeller-Trumbore's denom = -(rd . n) is rounding noise, seldom exactly 0, and t, u, v are noise that
+// can pass the inside test at any t ("phantom hits": listed nearest, with a gradient divided by rd . n ~ 0).  Above the bound
+// denom holds its value to ~1e-7 / 5e-4 of itself.  A zero-area face (n == 0 exactly for a repeated vertex) never passes.
+// Evaluated for the few candidates that pass the inside test only.  fp32, this order, uncontracted (rasterize_ref.off_plane32).
+constexpr float RZ_PLANE_COS2 = 2.5e-7f;
+__device__ __forceinline__ bool rz_off_plane(f3 rd, f3 p0, f3 p1, f3 p2) {
+    const f3 n = cross(p1 - p0, p2 - p0);
+    const float dn = dot(rd, n);
+    return dn * dn > (RZ_PLANE_COS2 * dot(n, n)) * dot(rd, rd);
+}
 
 __device__ __forceinline__ bool rz_before(float ta, int ia, float tb, int ib) { return ta < tb || (ta == tb && ia < ib); }
 
@@ -132,6 +147,7 @@ k_rasterize(dm2_layers_desc d, const float* __restrict__ min_depths, const float
                 f3 tuv;
                 if (!ray_tri_intersection(ro, rd, {r.v[0], r.v[1], r.v[2]}, {r.v[3], r.v[4], r.v[5]}, {r.v[6], r.v[7], r.v[8]}, tuv)) continue;
                 if (!(tuv.x >= 0.0f && tuv.y >= 0.0f && tuv.z >= 0.0f && tuv.y + tuv.z <= 1.0f)) continue;
+                if (!rz_off_plane(rd, {r.v[0], r.v[1], r.v[2]}, {r.v[3], r.v[4], r.v[5]}, {r.v[6], r.v[7], r.v[8]})) continue;
                 if (pass > 0 && !rz_before(prev_t, prev_id, tuv.x, r.face_id)) continue;    // listed by an earlier pass
                 rz_insert<KR>(h, Lp, tuv.x, r.face_id, tuv.y, tuv.z, r.max_d);
                 cnt = min(cnt + 1, Lp);

@@ -155,7 +155,9 @@ def upstream(shape, seed):
 
 # ---- cases ---------------------------------------------------------------------------------------------------------------------
 SCENE_LS = {"soup": (4,), "lattice": (1, 3, 8), "degenerate": (1, 3, 8), "no_faces": (3,)}
-SCENE_CASES = [(name, L) for name in rref.SCENES for L in SCENE_LS[name]]
+SCENE_LS.update(aligned=(4,), flat=(4,), duplicates=(4,))      # tet scenes (rasterize_ref.tet_case): axis-parallel projected
+                                                                # edges and vertices on pixel centres; faces listed twice
+SCENE_CASES = [(name, L) for name in rref.SCENES + ("aligned", "flat", "duplicates") for L in SCENE_LS[name]]
 FIXTURE_CASES = [(name, key) for name in ("aa_pairs", "aa_error_pairs") for key in ("tri_in", "t_verts")]
 REWOUND = ("soup", "degenerate")     # every face of these generators projects counter-clockwise: every other one is rewound here,
                                      # so that the lists hold both orientations and the reorder's swap is exercised on them too
@@ -173,6 +175,11 @@ def scene_case(name, L):
     layers -> dict(render_layers, verts_image, faces, W, H, g,
     info {temperature: coverage32})."""
     key = ("scene", name, L)
+    if key not in _CASES and name in rref.TET_CASES:
+        s = rref.tet_case(name)
+        ras = rref.select(rref.tet_intersect(name), L)
+        _CASES[key] = _finish(dict(render_layers=ras["layers"], verts_image=s["verts_image"], faces=s["faces"], W=s["W"], H=s["H"]),
+                              sum(map(ord, name)) + L)
     if key not in _CASES:
         s = dict(rref.scene(name))
         if name in REWOUND:

@@ -61,6 +61,40 @@ def test_op_bit_equal_to_restatement(name, L, exist):
         assert (want["cnt"] == L).any()                                         # (some pixel fills every slot)
 
 
+TET_BIT = ("aligned", "holes", "inside", "flat", "duplicates", "deep", "chunk_edge", "chunk_edge3")
+DEEP_SORT_SIZE = (16, 16)        # (test_rasterize_cpu.py's: the reference is shared within one run)
+
+
+@pytest.mark.parametrize("name", TET_BIT)
+@pytest.mark.parametrize("L", [1, 4, 16, 17, 33, 40])
+@pytest.mark.parametrize("exist", [None, "fe", "fe_odd"])
+def test_op_bit_equal_on_tet_scenes(name, L, exist):
+    """The tet scenes (rasterize_ref.tet_case; what each reaches is counted in test_rasterize_cpu.py): rays in face planes,
+    through vertices and along edges (aligned: the hit rule, exact-edge hits), exact t ties that the face id decides, within
+    a pass and across the pass boundaries 15|16 and 31|32 (duplicates, flat, aligned), cameras inside the mesh (inside,
+    holes), lists of 40 staging chunks with hits for three passes (deep), a list that ends one entry into a chunk
+    (chunk_edge, chunk_edge3); existence values other than 0 / 1 (fe_odd: 2, -1, INT_MIN)."""
+    s = ref.tet_case(name)
+    want = ref.select(ref.tet_intersect(name, exist), L)
+    got = _C.rasterize_layers_cuda(*_dev(s, None if exist is None else s[exist]), L)
+    torch.cuda.synchronize()
+    _equal(got, want, (name, L, exist))
+    assert want["cnt"].sum() > 0
+
+
+def test_op_bit_equal_on_a_globally_sorted_list():
+    """deep_sort: one tile whose list is longer than TILE_SORT_MAX (the plan's global radix sort), L = 17."""
+    import tet_scenes
+    s = ref.tet_case("deep_sort", *DEEP_SORT_SIZE)
+    x = ref.tet_intersect("deep_sort", None, True, *DEEP_SORT_SIZE)
+    assert (x["cand"] >= 0).sum(1).max() > tet_scenes.thresholds()["TILE_SORT_MAX"]
+    got = _C.rasterize_layers_cuda(*_dev(s, None), 17)
+    torch.cuda.synchronize()
+    want = ref.select(x, 17)
+    _equal(got, want, "deep_sort")
+    assert (want["cnt"] == 17).any()
+
+
 def test_analytic_rays_bit_equal_to_the_ray_tensor_path():
     from oracle import cpu as orc
     W, H, bidx = 88, 60, [1, 0]
@@ -183,6 +217,29 @@ def test_gradients_against_float64(name, L):
         assert int(cnt.max()) > 16                                             # (hits from the second pass)
 
 
+@pytest.mark.parametrize("name", ["aligned", "flat", "duplicates", "inside"])
+@pytest.mark.parametrize("L", [4, 17])
+def test_gradients_against_float64_on_tet_scenes(name, L):
+    """The backward on the kernel's own lists of the tet scenes: hits on edges and vertices, faces seen at grazing angles down
+    to the hit rule's |cos| > 5e-4 (aligned), faces listed twice (duplicates), a camera inside the mesh."""
+    s = ref.tet_case(name)
+    args = _dev(s, s["fe"])
+    layers, cnt, bary, t = _C.rasterize_layers_cuda(*args, L)
+    gen = torch.Generator().manual_seed(L)
+    gb = torch.randn(bary.shape, generator=gen)
+    gt = torch.randn(t.shape, generator=gen)
+    W, H, verts, faces, _, _, _, ro, rd = args
+    for g_b, g_t in ((gb, gt), (gb, None), (None, gt)):
+        got = _C.rasterize_layers_backward_cuda(layers, verts, faces, ro, rd, None if g_b is None else g_b.cuda(),
+                                                None if g_t is None else g_t.cuda()).cpu().numpy()
+        want = ref.grads64(s["verts"], s["faces"], layers.cpu(), s["ray_o"], s["ray_d"], g_b, g_t)
+        assert np.isfinite(got).all() and np.isfinite(want).all() and np.abs(want).max() > 0
+        print(name, L, g_b is None, g_t is None, rel_linf(got, want))
+        assert rel_linf(got, want) <= GRAD_TOL, (name, L, g_b is None, g_t is None, rel_linf(got, want))
+    if L == 17 and name != "inside":
+        assert int(cnt.max()) > 16                                             # (hits from the second pass)
+
+
 @pytest.mark.parametrize("name", ["overflow_L4", "overflow_L12", "nearly_full_L4"])
 def test_backward_table_overflow_route(name):
     """k_rasterize_bwd where lc_slot finds no slot: a hit's nine components go to global memory as per-hit float casts
@@ -264,3 +321,36 @@ def test_module_path():
         assert len(calls) == 1
     finally:
         _C.rasterize_layers_backward_cuda = real_b
+
+
+def test_module_path_on_aligned():
+    """LayeredRenderer.rasterize on ``aligned`` (rays in face planes: the hit rule decides) with both host preps and with
+    analytic rays: each run equals the restatement of the very inputs its op got."""
+    import tet_scenes
+    ts, _ = tet_scenes.case("aligned")
+    W, H, bidx, L = ts.width, ts.height, [0, 1], 5
+    ts = ts.to("cuda")
+    seen = []
+    real = _C.rasterize_layers_cuda
+
+    def spy(*a):
+        out = real(*a)
+        seen.append(([x.detach().cpu().numpy() if torch.is_tensor(x) else x for x in a], out))
+        return out
+    _C.rasterize_layers_cuda = spy
+    try:
+        for kw in (dict(fused_prep=False), dict(fused_prep=True), dict(analytic_rays=True)):
+            lr = dm2.LayeredRenderer(ts.mv, ts.proj, W, H, "cuda", **kw)
+            lr.rasterize(bidx, ts.verts, ts.faces, L, faces_existence=ts.faces_existence)
+            a, out = seen[-1]
+            if kw.get("analytic_rays"):
+                from oracle import cpu as orc
+                cam = lr.ray_cam.cpu().numpy()
+                a[7], a[8] = orc.analytic_rays_from_inverse(cam[:, :16].reshape(-1, 4, 4), cam[:, 16:].reshape(-1, 4, 4), W, H)
+            x_old, x = (ref.intersect(*a[:9], rule=rule) for rule in (False, True))
+            _equal(out, ref.select(x, L), kw)
+            removed = ref.rule_removed(x_old, x)
+            print(f"aligned, {kw}: the hit rule removes {removed[0]} hits at {removed[1]} pixels")
+            assert removed[0] > 0, kw
+    finally:
+        _C.rasterize_layers_cuda = real
