@@ -308,7 +308,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             k_dep[0] = fc.dep[0]; k_dep[1] = fc.dep[1]; k_dep[2] = fc.dep[2]; k_int = fc.intense; k_opa = fc.opacity;
             if (ray_tri_intersection(ro, rd, p0, p1, p2, tuv)) {
                 float iuc, ivc;
-                clamp_bary_uv(tuv.y, tuv.z, iuc, ivc, code);
+                clamp_bary_uv_chain(tuv.y, tuv.z, iuc, ivc, code);             // (the chain: see dm2_device_math.h)
                 i0 = 1 - iuc - ivc; i1 = iuc; i2 = ivc;
                 if constexpr (COV == CLIP) ratio = mix_coverage(code, ratio, temp);
                 float c0 = i0 * fc.col[0] + i1 * fc.col[3] + i2 * fc.col[6];

@@ -61,6 +61,19 @@ __device__ __forceinline__ bool ray_tri_intersection(f3 ro, f3 rd, f3 p0, f3 p1,
     return true;
 }
 
+// The same without the early return, for callers that select on the result: tuv is written either way (inf / NaN where
+// denom == 0) and only meaningful when true comes back.
+__device__ __forceinline__ bool ray_tri_intersection_pred(f3 ro, f3 rd, f3 p0, f3 p1, f3 p2, f3& tuv) {
+    f3 T = ro - p0, E1 = p1 - p0, E2 = p2 - p0;
+    f3 P = cross(rd, E2), Q = cross(T, E1);
+    float denom = dot(P, E1);
+    float inv_denom = 1.0f / denom;
+    tuv.x = dot(Q, E2) * inv_denom;
+    tuv.y = dot(P, T) * inv_denom;
+    tuv.z = dot(Q, rd) * inv_denom;
+    return denom != 0.0f;
+}
+
 // ---- auxiliary.h:245-290.  As written the "dv" outputs are grad(t), not grad(v);
 // corrected=true computes the true grad(v) (opt-in flag DM2_FLAG_CORRECTED_DV).
 // 1 / x to <= 1 ulp without the IEEE division's ~19 instructions (v_rcp_f32 + one Newton step): for gradient terms, which owe
@@ -104,7 +117,24 @@ __device__ __forceinline__ void ray_tri_intersection_grad(f3 ro, f3 rd, f3 p0, f
 }
 
 // ---- auxiliary.h:292-329 ------------------------------------------------------
+// Region tests and results as selects (the reference's else-if chain keeps its precedence in the nested select): every lane of
+// a wave clamps a different pair, so a chain of branches ran the union of the regions under exec masks anyway.
 __device__ __forceinline__ void clamp_bary_uv(float u, float v, float& u_c, float& v_c, int& code) {
+    const bool r0 = (u >= 0.0f) & (v >= 0.0f) & (u + v <= 1.0f);
+    const bool r1 = (u <= 0.0f) & (v <= 0.0f);
+    const bool r2 = ((u >= 1.0f) & (v <= 0.0f)) | ((v >= 0.0f) & (v <= u - 1.0f));
+    const bool r3 = ((u <= 0.0f) & (v >= 1.0f)) | ((u >= 0.0f) & (v >= u + 1.0f));
+    const bool r4 = (u <= 0.0f) & (v <= 1.0f) & (v >= 0.0f);
+    const bool r5 = (u <= 1.0f) & (u >= 0.0f) & (v <= 0.0f);
+    const float ue = (1.0f + u - v) * 0.5f, ve = (1.0f - u + v) * 0.5f;
+    code = r0 ? 0 : (r1 ? 1 : (r2 ? 2 : (r3 ? 3 : (r4 ? 4 : (r5 ? 5 : 6)))));
+    u_c = r0 ? u : (r1 ? 0.0f : (r2 ? 1.0f : (r3 ? 0.0f : (r4 ? 0.0f : (r5 ? u : ue)))));
+    v_c = r0 ? v : (r1 ? 0.0f : (r2 ? 0.0f : (r3 ? 1.0f : (r4 ? v : (r5 ? 0.0f : ve)))));
+}
+
+// The reference's else-if chain as it stands, for k_render_backward_fast: that kernel sits at its 128-register ceiling and the
+// select form above costs it two spilled VGPRs (a scratch reload there waits for every LDS-direct load in flight).
+__device__ __forceinline__ void clamp_bary_uv_chain(float u, float v, float& u_c, float& v_c, int& code) {
     if (u >= 0.0f && v >= 0.0f && u + v <= 1.0f) { u_c = u; v_c = v; code = 0; }
     else if (u <= 0.0f && v <= 0.0f) { u_c = 0.0f; v_c = 0.0f; code = 1; }
     else if ((u >= 1.0f && v <= 0.0f) || (v >= 0.0f && v <= u - 1.0f)) { u_c = 1.0f; v_c = 0.0f; code = 2; }

@@ -315,42 +315,41 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             const FaceRec& fc = recs[j];
             const float pxmin = (float)(uint32_t)(X0a + (q & 15)), pxmax = pxmin + 1;
             const float pymin = (float)(uint32_t)(Y0a + (q >> 4)), pymax = pymin + 1;
-            FqPair out; out.alpha = 0.f; out.c0 = out.c1 = out.c2 = out.depth = 0.f; out.flags = 0;
+            // Straight-line from here to the stores: a lane that is not live, misses the plane or mixes to zero coverage computes
+            // on (inf / NaN included) and the selects below discard it; only the LDS stores and atomics sit under a mask.
             float oarea = 0.f;
             bool live = true;
             if (use_aa) {
                 const int err = clip_area_classified(fc.aa, pxmin, pxmax, pymin, pymax, cmask, pix_area, oarea);
-                live = !((err != 0) || (oarea == 0.0f));
-                if (live) out.flags |= QF_REC;
+                live = !((err != 0) | (oarea == 0.0f));
             }
-            if (live) {
-                float ratio = oarea / pix_area;
-                const f3 ro = {s_ray[q * 6], s_ray[q * 6 + 1], s_ray[q * 6 + 2]};
-                const f3 rd = {s_ray[q * 6 + 3], s_ray[q * 6 + 4], s_ray[q * 6 + 5]};
-                const f3 p0 = {fc.v[0], fc.v[1], fc.v[2]}, p1 = {fc.v[3], fc.v[4], fc.v[5]}, p2 = {fc.v[6], fc.v[7], fc.v[8]};
-                f3 tuv = {0, 0, 0};
-                if (ray_tri_intersection(ro, rd, p0, p1, p2, tuv)) {
-                    float iuc, ivc; int code;
-                    clamp_bary_uv(tuv.y, tuv.z, iuc, ivc, code);
-                    const float i0 = 1 - iuc - ivc, i1 = iuc, i2 = ivc;
-                    ratio = mix_coverage(code, ratio, temp);
-                    if (ratio != 0.0f) {
-                        float c0 = i0 * fc.col[0] + i1 * fc.col[3] + i2 * fc.col[6];
-                        float c1 = i0 * fc.col[1] + i1 * fc.col[4] + i2 * fc.col[7];
-                        float c2 = i0 * fc.col[2] + i1 * fc.col[5] + i2 * fc.col[8];
-                        out.c0 = c0 * fc.intense; out.c1 = c1 * fc.intense; out.c2 = c2 * fc.intense;
-                        out.depth = i0 * fc.dep[0] + i1 * fc.dep[1] + i2 * fc.dep[2];
-                        out.alpha = fc.opacity * ratio;
-                        out.flags |= QF_BLEND;
-                        pool_ratio[rnd] = ratio; blend_s = true;
-                        if (CLASSES) { pool_s[rnd] = s; if (pool) atomicOr(&s_blend[s >> 6], 1ull << (s & 63)); }
-                    }
-                }
+            float ratio = oarea / pix_area;
+            const f3 ro = {s_ray[q * 6], s_ray[q * 6 + 1], s_ray[q * 6 + 2]};
+            const f3 rd = {s_ray[q * 6 + 3], s_ray[q * 6 + 4], s_ray[q * 6 + 5]};
+            const f3 p0 = {fc.v[0], fc.v[1], fc.v[2]}, p1 = {fc.v[3], fc.v[4], fc.v[5]}, p2 = {fc.v[6], fc.v[7], fc.v[8]};
+            f3 tuv;
+            const bool hit = ray_tri_intersection_pred(ro, rd, p0, p1, p2, tuv);
+            float iuc, ivc; int code;
+            clamp_bary_uv(tuv.y, tuv.z, iuc, ivc, code);
+            const float i0 = 1 - iuc - ivc, i1 = iuc, i2 = ivc;
+            ratio = mix_coverage(code, ratio, temp);
+            blend_s = live & hit & (ratio != 0.0f);
+            const float c0 = i0 * fc.col[0] + i1 * fc.col[3] + i2 * fc.col[6];
+            const float c1 = i0 * fc.col[1] + i1 * fc.col[4] + i2 * fc.col[7];
+            const float c2 = i0 * fc.col[2] + i1 * fc.col[5] + i2 * fc.col[8];
+            FqPair out;
+            out.c0 = blend_s ? c0 * fc.intense : 0.f; out.c1 = blend_s ? c1 * fc.intense : 0.f; out.c2 = blend_s ? c2 * fc.intense : 0.f;
+            out.depth = blend_s ? i0 * fc.dep[0] + i1 * fc.dep[1] + i2 * fc.dep[2] : 0.f;
+            out.alpha = blend_s ? fc.opacity * ratio : 0.f;
+            out.flags = ((use_aa & live) ? QF_REC : 0u) | (blend_s ? QF_BLEND : 0u);
+            if (blend_s) {
+                pool_ratio[rnd] = ratio;
+                if (CLASSES) { pool_s[rnd] = s; if (pool) atomicOr(&s_blend[s >> 6], 1ull << (s & 63)); }
             }
             if (out.flags) {
                 s_pair[s] = out;
                 atomicOr(&s_mask[q], 1ull << j);
-                if (hit_masks && (out.flags & QF_BLEND)) atomicOr(&s_bmask[j * 4 + (q >> 6)], 1ull << (q & 63));
+                if (hit_masks && blend_s) atomicOr(&s_bmask[j * 4 + (q >> 6)], 1ull << (q & 63));
             }
             }
             if (!CLASSES && pool) {                                     // (block-uniform; every lane of the wave is here)
