@@ -586,6 +586,23 @@ def render_forward_cuda(*args):
     return out + (weights,) if want_weights else out
 
 
+def packed_grads(P, F, B, aa_to_verts, device):
+    """Six zero gradients in the order render_backward_cuda returns them, as views of ONE packed fp32 buffer (attribute
+    ``_dm2_packed`` on the first).  Physical order: the gradients of the LEAVES first ([dverts | dverts_color | dfaces_opacity |
+    dfaces_intense], one contiguous span for a multi-GPU caller), then the two intermediates of the host prep (dverts_ndc,
+    daa_face_verts: (B,P,2) when ``aa_to_verts``, else (B,F,3,2)).  The one statement of that layout: a rank without a band
+    (sharding.BandShardedOp) and the CPU test double build theirs here, so every rank takes the same path through the
+    collectives."""
+    sizes = [P * 3, P * 3, F, B * F, B * P * 3, B * P * 2 if aa_to_verts else B * F * 6]
+    packed = torch.zeros((sum(sizes),), dtype=torch.float32, device=device)
+    parts = torch.split(packed, sizes)
+    g_verts = parts[0].view(P, 3); g_color = parts[1].view(P, 3); g_opac = parts[2].view(F)
+    g_int = parts[3].view(B, F); g_ndc = parts[4].view(B, P, 3)
+    g_aa = parts[5].view(B, P, 2) if aa_to_verts else parts[5].view(B, F, 3, 2)
+    g_verts._dm2_packed = packed
+    return g_verts, g_color, g_opac, g_ndc, g_int, g_aa
+
+
 def render_backward_cuda(*args, dL_dout_alpha=None):
     """-> (dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts).
 
@@ -605,17 +622,10 @@ def render_backward_cuda(*args, dL_dout_alpha=None):
     d, dev, (B, P, F, W, H, K) = _make_desc(fwd_args, keep)
     _require_gpu(dL_dcolor, dL_ddepth)
     f32 = torch.float32
-    # physical order: the gradients of the LEAVES first ([dverts | dverts_color | dfaces_opacity | dfaces_intense], one
-    # contiguous span for a multi-GPU caller), then the two intermediates of the host prep (dverts_ndc, daa_face_verts)
     to_verts = bool(getattr(_tls, "aa_to_verts", False))
     if to_verts:
         d.flags |= DM2_FLAG_AA_GRAD_TO_VERTS
-    sizes = [P * 3, P * 3, F, B * F, B * P * 3, B * P * 2 if to_verts else B * F * 6]
-    packed = torch.zeros((sum(sizes),), dtype=f32, device=dev)          # render.cu:313-318 zeros_like x6
-    parts = torch.split(packed, sizes)
-    g_verts = parts[0].view(P, 3); g_color = parts[1].view(P, 3); g_opac = parts[2].view(F)
-    g_int = parts[3].view(B, F); g_ndc = parts[4].view(B, P, 3)
-    g_aa = parts[5].view(B, P, 2) if to_verts else parts[5].view(B, F, 3, 2)
+    g_verts, g_color, g_opac, g_ndc, g_int, g_aa = packed_grads(P, F, B, to_verts, dev)      # render.cu:313-318 zeros_like x6
     if F != 0 and P != 0 and num_rendered > 0 and B * H * W > 0:
         if tuple(dL_dcolor.shape) != (B, H, W, 3) or tuple(dL_ddepth.shape) != (B, H, W):
             raise RuntimeError("dL_dout_color / dL_dout_depth must have dimensions (B, H, W, 3) / (B, H, W)")
@@ -646,7 +656,6 @@ def render_backward_cuda(*args, dL_dout_alpha=None):
                 rc = lib.dm2_backward_alpha(ctypes.byref(d), num_rendered, int(mode), _ptr(dc), _ptr(dd), _ptr(da), *tail)
             if rc:
                 raise _err(lib, "render_backward_cuda")
-    g_verts._dm2_packed = packed
     return g_verts, g_color, g_opac, g_ndc, g_int, g_aa
 
 

@@ -26,7 +26,10 @@ namespace dm2 {
 constexpr int XCHG_MAX_RANKS = 64;
 
 constexpr int XCHG_THREADS = 1024;
-constexpr int XCHG_IDS_PER_WAVE = 2048;                   // a wave takes 2048 contiguous ids, 32 rounds of 64: one or two owners per wave
+constexpr int XCHG_IDS_PER_WAVE = 2048;                   // a wave takes 2048 contiguous ids, 32 rounds of 64: one or two owners per wave at
+                                                          // the sizes the exchange is for; slices shorter than that put more owners
+                                                          // into a wave, and the owner loops below take any number (a pass over the
+                                                          // wave's flags per owner: slower, not different)
 constexpr int XCHG_ROUNDS = XCHG_IDS_PER_WAVE / 64;
 constexpr int XCHG_BATCH = 8;                            // rounds whose gathers are in flight together (k_xchg_pack)
 constexpr int XCHG_IDS_PER_BLOCK = XCHG_IDS_PER_WAVE * (XCHG_THREADS / 64);    // 32768 ids per block: ~100 blocks, a couple of hundred

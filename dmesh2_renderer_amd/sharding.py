@@ -152,7 +152,9 @@ class DeviceExchange:
     kernels instead of ~15 torch ops and a sort.  ``plan`` can run right after the forward (what a rank will send only depends
     on the faces its band binned), so that the one host read-back -- the all-to-all's split sizes -- overlaps the backward;
     ``reduce`` then packs, exchanges, sums and gathers.  Row order inside a segment is arbitrary; a row has a single
-    contributor but for faces that straddle a band edge, so results match ``reduce_leaves_sparse`` to fp32 rounding."""
+    contributor but for faces that straddle a band edge, and the owner adds source by source as ``reduce_leaves_sparse`` does,
+    so the two agree bit for bit.  ``face_buf`` None: a rank without a band (``band_rows`` -> 0 rows) that sends nothing and
+    still owns its slice -- it issues the same collectives, with the same dtypes, as its peers."""
 
     def __init__(self, C, face_buf, faces, B, P, group=None):
         import torch.distributed as dist
@@ -160,7 +162,11 @@ class DeviceExchange:
         self.N = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
         self.B, self.P, self.F = int(B), int(P), int(faces.shape[0])
-        self.flags, self.counts = C.exchange_mark(face_buf, faces, self.B, self.P, self.N)
+        if face_buf is None:
+            self.flags = torch.zeros((self.F + self.P,), dtype=torch.uint8, device=faces.device)
+            self.counts = torch.zeros((self.N, 2), dtype=torch.int32, device=faces.device)
+        else:
+            self.flags, self.counts = C.exchange_mark(face_buf, faces, self.B, self.P, self.N)
         self.cnt_recv = torch.empty_like(self.counts)
         dist.all_to_all_single(self.cnt_recv, self.counts, group=group)          # what comes from where
         # ONE read-back of (what goes where, what comes from where): issued now, looked at in reduce()
@@ -253,15 +259,9 @@ class BandShardedOp:
         (B,P,2), the AA-corner gradients already scattered to the vertices (``_C.aa_grad_to_verts``)."""
         a = self.args
         if self.rows == 0:
-            P, F, B = a[4].shape[0], a[5].shape[0], a[8].shape[0]
-            dev = a[4].device
-            # (the physical order of _C.render_backward_cuda: every rank must take the same path through the collectives)
-            sizes = [P * 3, P * 3, F, B * F, B * P * 3, B * P * 2 if aa_to_verts else B * F * 6]
-            packed = torch.zeros((sum(sizes),), dtype=torch.float32, device=dev)
-            parts = torch.split(packed, sizes)
-            grads = (parts[0].view(P, 3), parts[1].view(P, 3), parts[2].view(F), parts[4].view(B, P, 3),
-                     parts[3].view(B, F), parts[5].view(B, P, 2) if aa_to_verts else parts[5].view(B, F, 3, 2))
-            grads[0]._dm2_packed = packed
+            from . import _C as product
+            # (the packed layout of _C.render_backward_cuda: every rank must take the same path through the collectives)
+            grads = product.packed_grads(a[4].shape[0], a[5].shape[0], a[8].shape[0], aa_to_verts, a[4].device)
         else:
             f = self.fwd
             if aa_to_verts:
@@ -289,11 +289,13 @@ class BandShardedOp:
 
     def plan_exchange(self, group=None):
         """Call after ``forward`` (product backend, exchange="sparse"): marks the rows this rank will send and starts the
-        read-back of the all-to-all's split sizes, so that it is over by the time the backward has run."""
+        read-back of the all-to-all's split sizes, so that it is over by the time the backward has run.  A rank without a
+        band plans too (nothing to send): the exchange's collectives are the same on every rank."""
         self._xchg = None
-        if self.fwd is not None and hasattr(self._C, "exchange_mark") and self.args[5].is_cuda:
+        if hasattr(self._C, "exchange_mark") and self.args[5].is_cuda:
             a = self.args
-            self._xchg = DeviceExchange(self._C, self.fwd[7], a[5], a[8].shape[0], a[4].shape[0], group)
+            face_buf = self.fwd[7] if self.fwd is not None else None
+            self._xchg = DeviceExchange(self._C, face_buf, a[5], a[8].shape[0], a[4].shape[0], group)
         return self._xchg
 
     def backward_leaves(self, dL_dcolor_band, dL_ddepth_band, prep_inputs, group=None, prep_backward=None, exchange="dense"):
@@ -332,7 +334,8 @@ class BandShardedOp:
         else:
             dverts += pb(verts, faces, mv, proj, width, height, g_verts_ndc=dndc, g_aa_face_verts=daa)
         if not dense:
-            if self.fwd is not None and hasattr(self._C, "exchange_mark") and faces.is_cuda and \
+            # (no test on self.fwd: a rank without a band takes the route of its peers, or their collectives do not match)
+            if hasattr(self._C, "exchange_mark") and faces.is_cuda and \
                     dist.get_backend(group) != "gloo":       # (gloo has no all-to-all on device tensors)
                 x = getattr(self, "_xchg", None) or self.plan_exchange(group)
                 self._xchg = None

@@ -14,6 +14,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from util import scenes, soup_args, to_numpy_args
+from dmesh2_renderer_amd import _C
 from dmesh2_renderer_amd.sharding import BandShardedOp, all_bands, band_rows
 
 
@@ -31,14 +32,14 @@ class OracleBackend:
         from oracle import cpu as orc
         dLc, dLd, fwd = rest[21], rest[22], rest[23]
         g = orc.render_backward_cuda(fwd, dLc.numpy(), dLd.numpy())
+        # packed in the product's physical order (_C.packed_grads: leaves first), so that the double takes the branches the
+        # product takes -- and the ones a rank without a band takes -- through the collectives
         order = ["verts", "verts_color", "faces_opacity", "verts_ndc", "faces_intense", "aa_face_verts"]
-        flat = torch.cat([torch.from_numpy(g[k]).reshape(-1) for k in order])
-        outs, off = [], 0
-        for k in order:
-            n = g[k].size
-            outs.append(flat[off:off + n].view(g[k].shape)); off += n
-        outs[0]._dm2_packed = flat
-        return tuple(outs)
+        P, F, B = g["verts"].shape[0], g["faces_opacity"].shape[0], g["faces_intense"].shape[0]
+        outs = _C.packed_grads(P, F, B, False, "cpu")
+        for o, k in zip(outs, order):
+            o.copy_(torch.from_numpy(g[k]))
+        return outs
 
 
 def oracle_prep_backward(verts, faces, mv, proj, width, height, g_verts_ndc=None, g_aa_face_verts=None):
@@ -89,10 +90,12 @@ def _worker(rank, world, port, W, H, F, seed, out_dir):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_band_sharded_render_equals_full_frame(tmp_path, world):
+@pytest.mark.parametrize("H,world", [(80, 2), (80, 3), (32, 3)], ids=["2", "3", "3-surplus"])
+def test_band_sharded_render_equals_full_frame(tmp_path, H, world):
+    """(H = 32, world 3: two tile rows for three ranks, rank 0 has no band and still takes part in every collective.)"""
     from oracle import cpu as orc
-    W, H, F, seed = 64, 80, 250, scenes.SEED_BASE + 31
+    W, F, seed = 64, 250, scenes.SEED_BASE + 31
+    assert (0 in [r for _, r in all_bands(H, world)]) == (H == 32)
     mp.spawn(_worker, args=(world, _free_port(), W, H, F, seed, str(tmp_path)), nprocs=world, join=True)
     args, sc = soup_args(W, H, F, seed)
     full = orc.render_forward_cuda(*to_numpy_args(args))
