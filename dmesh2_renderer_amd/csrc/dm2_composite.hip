@@ -18,8 +18,8 @@
 // recomputes T from the front for every chunk.
 //
 // Forward: a block takes 256 consecutive pixels.  Backward, per-slot alpha: the same.  Backward, per-face alpha: one block per
-// 16 x 16 pixel tile and view (neighbouring pixels list the same faces); dL/da_l goes into the face's slot of the per-block
-// table of dm2_face_table.h (one fp32 accumulator per slot) and the block flushes with one global atomic per face of the
+// 16 x 16 pixel tile and view (neighbouring pixels list the same faces); dL/da_l goes into the face's slot of the block's
+// FaceTable (dm2_face_table.h; one fp32 accumulator per slot) and the block flushes with one global atomic per face of the
 // tile; a face that finds no slot adds straight to global memory.
 #include <hip/hip_runtime.h>
 
@@ -181,16 +181,14 @@ k_composite_bwd(CompSizes z, const float* __restrict__ values, const float* __re
     __shared__ float s_a[CP_PIX * CP_SL], s_Tl[CP_PIX * CP_SL];              // alpha and the transmittance in front of a blended slot
     __shared__ float s_S[CP_PIX * CP_SL];                                     // S_l, then dL/da_l
     __shared__ uint32_t s_mask[CP_PIX];
-    __shared__ int s_key[FACE ? LC_SLOTS : 1];
-    __shared__ float s_facc[FACE ? LC_SLOTS : 1];
+    FaceTable<float, 1>* tab = nullptr;                                        // FACE only: otherwise none is declared
+    if constexpr (FACE) { __shared__ FaceTable<float, 1> s_tab; tab = &s_tab; }
     const int tid = threadIdx.x;
     const int L = z.L, C = z.C;
     constexpr int V = VEC4 ? 4 : 1;
     const int CV = C / V;
     const int64_t gp = cp_pixel<FACE>(z, tid);
-    if (FACE) {
-        for (int i = tid; i < LC_SLOTS; i += CP_PIX) { s_key[i] = -1; s_facc[i] = 0.0f; }
-    }
+    if constexpr (FACE) tab->clear(tid);
     const int n = gp >= 0 ? n_contrib[gp] : 0;                                 // blended: not empty and in front of slot n
     float R = 0.0f;                                                            // the back pass's carry, K at its start
     if (dL_dalpha && n > 0) {
@@ -250,10 +248,10 @@ k_composite_bwd(CompSizes z, const float* __restrict__ values, const float* __re
                     const float a = s_a[tid * CP_SL + l], S = s_S[tid * CP_SL + l];
                     d = s_Tl[tid * CP_SL + l] * (S - R);
                     R = a * S + (1.0f - a) * R;
-                    if (FACE) {
+                    if constexpr (FACE) {
                         const int f = layers[gp * L + l0 + l];
-                        const int slot = lc_slot(s_key, f);
-                        if (slot >= 0) atomicAdd(&s_facc[slot], d);
+                        const int slot = tab->slot(f);
+                        if (slot >= 0) tab->add(slot, 0, d);
                         else atomicAdd(dL_dalpha + f, d);
                     }
                 }
@@ -296,16 +294,8 @@ k_composite_bwd(CompSizes z, const float* __restrict__ values, const float* __re
         }
         __syncthreads();
     }
-    if (FACE && dL_dalpha) {
-        // flush: one global atomic per face the tile blended
-        for (int i = tid; i < LC_SLOTS; i += CP_PIX) {
-            const int f = s_key[i];
-            if (f < 0) continue;
-            const float v = s_facc[i];
-            if (v == 0.0f) continue;
-            atomicAdd(dL_dalpha + f, v);
-        }
-    }
+    // flush: one global atomic per face the tile blended
+    if constexpr (FACE) { if (dL_dalpha) tab->flush_by_slot(tid, [&](int f, int, float v) { atomicAdd(dL_dalpha + f, v); }); }
 }
 
 static CompSizes cp_sizes(int B, int H, int W, int L, int C, int F) {
@@ -343,7 +333,7 @@ void launch_composite_backward(int B, int H, int W, int L, int C, int F, int per
     hipLaunchKernelGGL((k_composite_bwd<FACE, V4>), grid, dim3(CP_PIX), 0, st, z, values, alpha, render_layers, background, \
                        n_contrib, dL_dout, dL_dacc, dL_dvalues, dL_dalpha)
     if (per_face) {
-        const dim3 grid((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
+        const dim3 grid = tile_grid(W, H, B);
         if (vec4) DM2_CP_BWD(true, true); else DM2_CP_BWD(true, false);
     } else {
         const dim3 grid((unsigned)((z.P + CP_PIX - 1) / CP_PIX));

@@ -13,9 +13,9 @@
 // list the same few faces, so the gathers (three faces entries, three float2 of verts_image per slot) hit in cache.  The
 // forward clips with the straight-line area-only clipper (dm2_clip_area.h); the backward re-clips with the reference-shaped
 // clipper and its Jacobian (tri_pix_overlap_area<true>, bit-equal to the oracle's), adds the six components into the face's
-// slot of the per-block table (dm2_face_table.h) -- stored per VERTEX of the face, the reorder already undone -- and the block
-// flushes with one global atomic per (vertex row, component) and face of the tile; a face that finds no slot adds straight to
-// global memory.
+// slot of the block's FaceTable (dm2_face_table.h) -- stored per VERTEX of the face, the reorder already undone -- and the block
+// flushes by slot, with one global atomic per (vertex row, component) and face of the tile (consecutive lanes on x and y of
+// one vertex); a face that finds no slot adds straight to global memory.
 #include <hip/hip_runtime.h>
 
 #include "dm2_clip_area.h"
@@ -83,10 +83,10 @@ template <int LVEC>
 __global__ void __launch_bounds__(TILE_PIX)
 k_coverage(CovSizes z, const int32_t* __restrict__ layers, const float* __restrict__ image, const int32_t* __restrict__ faces,
            float* __restrict__ out) {
-    const uint32_t px = blockIdx.x * TILE + (threadIdx.x & 15), py = blockIdx.y * TILE + (threadIdx.x >> 4);
-    if (px >= (uint32_t)z.W || py >= (uint32_t)z.H) return;
+    const auto [px, py, inside, pix] = tile_pixel(threadIdx.x, z.W, z.H);
+    if (!inside) return;
     const int b = blockIdx.z;
-    const int64_t s0 = (((int64_t)b * z.H + py) * z.W + px) * z.L;
+    const int64_t s0 = pix * z.L;
     const float2* im = reinterpret_cast<const float2*>(image) + (int64_t)b * z.P;
     const float pxmin = (float)px, pxmax = pxmin + 1, pymin = (float)py, pymax = pymin + 1;
     const float pix_area = 1.0f;
@@ -119,17 +119,15 @@ k_coverage(CovSizes z, const int32_t* __restrict__ layers, const float* __restri
 __global__ void __launch_bounds__(TILE_PIX)
 k_coverage_bwd(CovSizes z, const int32_t* __restrict__ layers, const float* __restrict__ image, const int32_t* __restrict__ faces,
                const float* __restrict__ g_cov, float* __restrict__ g_image) {
-    __shared__ int s_key[LC_SLOTS];
-    __shared__ float s_acc[LC_SLOTS * 6];                                  // [slot][vertex of the face][x, y]
+    __shared__ FaceTable<float, 6, LC_SLOTS + 6> tab;      // component 2 * vertex + (x, y); flush: bank = (6 c + slot) % 32
     const int tid = threadIdx.x;
-    for (int i = tid; i < LC_SLOTS; i += TILE_PIX) s_key[i] = -1;
-    for (int i = tid; i < LC_SLOTS * 6; i += TILE_PIX) s_acc[i] = 0.0f;
+    tab.clear(tid);
     __syncthreads();
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
+    const auto [px, py, inside, pix] = tile_pixel(tid, z.W, z.H);
     const int b = blockIdx.z;
     float* gi = g_image + (int64_t)b * z.P * 2;
-    if (px < (uint32_t)z.W && py < (uint32_t)z.H) {
-        const int64_t s0 = (((int64_t)b * z.H + py) * z.W + px) * z.L;
+    if (inside) {
+        const int64_t s0 = pix * z.L;
         const float2* im = reinterpret_cast<const float2*>(image) + (int64_t)b * z.P;
         const float pxmin = (float)px, pxmax = pxmin + 1, pymin = (float)py, pymax = pymin + 1;
 #pragma unroll 1
@@ -149,25 +147,20 @@ k_coverage_bwd(CovSizes z, const int32_t* __restrict__ layers, const float* __re
             // corner k of the reordered triangle is vertex k of the face, 1 and 2 exchanged where the reorder swapped
             const float d[6] = {s * J[0], s * J[1], s * (flip ? J[4] : J[2]), s * (flip ? J[5] : J[3]),
                                 s * (flip ? J[2] : J[4]), s * (flip ? J[3] : J[5])};
-            const int slot = lc_slot(s_key, f);
+            const int slot = tab.slot(f);
 #pragma unroll
             for (int j = 0; j < 6; j++) {
                 if (d[j] == 0.0f) continue;
-                if (slot >= 0) atomicAdd(&s_acc[slot * 6 + j], d[j]);
+                if (slot >= 0) tab.add(slot, j, d[j]);
                 else atomicAdd(gi + 2 * (int64_t)vid[j >> 1] + (j & 1), d[j]);
             }
         }
     }
     __syncthreads();
     // flush: one global atomic per (vertex row, component) and face of the tile (keys are listed, non-empty faces only)
-    for (int i = tid; i < LC_SLOTS * 6; i += TILE_PIX) {
-        const int f = s_key[i / 6];
-        if (f < 0) continue;
-        const float v = s_acc[i];
-        if (v == 0.0f) continue;
-        const int j = i % 6;
+    tab.flush_by_slot(tid, [&](int f, int j, float v) {
         atomicAdd(gi + 2 * (int64_t)faces[3 * (int64_t)f + (j >> 1)] + (j & 1), v);
-    }
+    });
 }
 
 static CovSizes cov_sizes(int B, int H, int W, int L, int P, int F, float temperature) {
@@ -179,7 +172,7 @@ static CovSizes cov_sizes(int B, int H, int W, int L, int P, int F, float temper
 void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* render_layers,
                      const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st) {
     const CovSizes z = cov_sizes(B, H, W, L, P, F, temperature);
-    const dim3 grid((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
+    const dim3 grid = tile_grid(W, H, B);
     const bool lvec = L % 4 == 0 && (((uintptr_t)render_layers | (uintptr_t)out_cov) & 15) == 0;
     if (lvec) hipLaunchKernelGGL(k_coverage<4>, grid, dim3(TILE_PIX), 0, st, z, render_layers, verts_image, faces, out_cov);
     else hipLaunchKernelGGL(k_coverage<1>, grid, dim3(TILE_PIX), 0, st, z, render_layers, verts_image, faces, out_cov);
@@ -189,7 +182,7 @@ void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float te
                               const float* verts_image, const int32_t* faces, const float* dL_dcov, float* dL_dverts_image,
                               hipStream_t st) {
     const CovSizes z = cov_sizes(B, H, W, L, P, F, temperature);
-    const dim3 grid((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
+    const dim3 grid = tile_grid(W, H, B);
     hipLaunchKernelGGL(k_coverage_bwd, grid, dim3(TILE_PIX), 0, st, z, render_layers, verts_image, faces, dL_dcov, dL_dverts_image);
 }
 

@@ -13,11 +13,10 @@
 // wave are contiguous, and the lanes of one slot read consecutive channels of the same three attr rows.
 //
 // attr backward: the scatter.  One block per 16 x 16 pixel tile and view (neighbouring pixels list the same faces), one lane
-// per pixel, the channels in chunks of CH.  A (slot, vertex, channel) contribution goes into the face's slot of the per-block
-// table of dm2_face_table.h (3 x CH fp32 accumulators per slot, component-major with a padded stride so that neither the
-// lanes of the accumulation nor those of the flush meet in a bank); the block then flushes with one global atomic per
-// (attr row, channel) and face of the tile, consecutive lanes on consecutive channels of one row.  A face that finds no slot
-// adds straight to global memory.  The keys stay from chunk to chunk, so a face keeps its slot.
+// per pixel, the channels in chunks of CH.  A (slot, vertex, channel) contribution goes into the face's slot of the block's
+// FaceTable (dm2_face_table.h; 3 x CH fp32 accumulators per slot, a padded stride so that neither the lanes of the accumulation
+// nor those of the flush meet in a bank), flushed by slot: consecutive lanes on consecutive channels of one attr row.  The keys
+// stay from chunk to chunk, so a face keeps its slot.
 #include <hip/hip_runtime.h>
 
 #include "dm2_device_math.h"
@@ -126,23 +125,19 @@ template <int CH>
 __global__ void __launch_bounds__(TILE_PIX)
 k_interpolate_bwd_attr(InterpSizes z, const int32_t* __restrict__ layers, const float* __restrict__ bary,
                        const int32_t* __restrict__ attr_faces, const float* __restrict__ g, float* __restrict__ dL_dattr) {
-    constexpr int NCOMP = 3 * CH;
-    __shared__ int s_key[LC_SLOTS];
-    __shared__ float s_acc[NCOMP * IP_STRIDE];                                // component-major: [k * CH + c][slot]
+    __shared__ FaceTable<float, 3 * CH, IP_STRIDE> tab;                       // component k * CH + c
     const int b = blockIdx.z, tid = threadIdx.x;
-    for (int i = tid; i < LC_SLOTS; i += TILE_PIX) s_key[i] = -1;
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
-    const bool inside = (px < (uint32_t)z.W) && (py < (uint32_t)z.H);
-    const int64_t pix = ((int64_t)b * z.H + py) * z.W + px;
+    tab.clear_keys(tid);
+    const TilePixel t = tile_pixel(tid, z.W, z.H);
     const int C = z.C, L = z.L;
     float* dst = dL_dattr + (z.view_tables ? (int64_t)b * z.N * C : 0);
     for (int c0 = 0; c0 < C; c0 += CH) {
         const int nc = min(CH, C - c0);
-        for (int i = tid; i < NCOMP * IP_STRIDE; i += TILE_PIX) s_acc[i] = 0.0f;
+        tab.clear_acc(tid);
         __syncthreads();
-        if (inside) {
+        if (t.inside) {
             for (int l = 0; l < L; l++) {
-                const int64_t s = pix * L + l;
+                const int64_t s = t.pix * L + l;
                 const int f = layers[s];
                 if ((unsigned)f >= (unsigned)z.F) continue;
                 const int r[3] = {attr_faces[3 * (int64_t)f], attr_faces[3 * (int64_t)f + 1], attr_faces[3 * (int64_t)f + 2]};
@@ -151,14 +146,14 @@ k_interpolate_bwd_attr(InterpSizes z, const int32_t* __restrict__ layers, const 
                 float gv[CH];
 #pragma unroll
                 for (int c = 0; c < CH; c++) gv[c] = c < nc ? g[s * C + c0 + c] : 0.0f;
-                const int slot = lc_slot(s_key, f);
+                const int slot = tab.slot(f);
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
 #pragma unroll
                     for (int c = 0; c < CH; c++) {
                         if (c >= nc) continue;
                         const float v = w[k] * gv[c];
-                        if (slot >= 0) atomicAdd(&s_acc[(k * CH + c) * IP_STRIDE + slot], v);
+                        if (slot >= 0) tab.add(slot, k * CH + c, v);
                         else atomicAdd(dst + (int64_t)r[k] * C + c0 + c, v);
                     }
                 }
@@ -166,15 +161,11 @@ k_interpolate_bwd_attr(InterpSizes z, const int32_t* __restrict__ layers, const 
         }
         __syncthreads();
         // flush: one global atomic per (attr row, channel) of every face the tile listed; lane -> (slot, k, c), c fastest
-        for (int i = tid; i < NCOMP * LC_SLOTS; i += TILE_PIX) {
-            const int slot = i / NCOMP, comp = i - slot * NCOMP;
+        tab.flush_by_slot(tid, [&](int f, int comp, float v) {
             const int k = comp / CH, c = comp - k * CH;
-            const int f = s_key[slot];
-            if (f < 0 || c >= nc) continue;
-            const float v = s_acc[comp * IP_STRIDE + slot];
-            if (v == 0.0f) continue;
+            if (c >= nc) return;
             atomicAdd(dst + (int64_t)attr_faces[3 * (int64_t)f + k] * C + c0 + c, v);
-        }
+        });
         __syncthreads();
     }
 }
@@ -205,7 +196,7 @@ void launch_interpolate_backward(int B, int H, int W, int L, int F, int N, int C
         else hipLaunchKernelGGL(k_interpolate_bwd_bary<false>, grid, dim3(IP_BLOCK), 0, st, z, render_layers, attr, attr_faces, dL_dout, dL_dbary);
     }
     if (dL_dattr) {
-        const dim3 grid((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
+        const dim3 grid = tile_grid(W, H, B);
 #define DM2_IP_LAUNCH(CH) \
     hipLaunchKernelGGL(k_interpolate_bwd_attr<CH>, grid, dim3(TILE_PIX), 0, st, z, render_layers, bary, attr_faces, dL_dout, dL_dattr)
         if (C == 1) DM2_IP_LAUNCH(1);

@@ -22,10 +22,8 @@
 // colour 1 over background 0, RA_l = alpha_l + (1 - alpha_l) RA_{l+1} (RA = 0 behind the last layer), and adds
 // T_l g_A (1 - RA_{l+1}) to dL/dalpha_l -- still no division.
 //
-// Gradient scatter: a (pixel, layer) hit adds its 14 components (9 colour, 3 z, opacity, intensity) into a per-block LDS
-// table keyed by face id (open addressing); the table is flushed with one global atomic per (face or vertex row, component)
-// and face of the tile (MI355X: 64 lanes adding into 64 different rows run ~17x below the chip's atomic rate).  A hit whose
-// face finds no slot within LC_PROBES probes adds straight to global memory.
+// Gradient scatter: a (pixel, layer) hit adds its 14 components (9 colour, 3 z, opacity, intensity) into the block's
+// FaceTable (dm2_face_table.h) under its face id; the flush is one global atomic per (face or vertex row, component).
 #include <hip/hip_runtime.h>
 
 #include "dm2_device_math.h"
@@ -67,12 +65,12 @@ __device__ __forceinline__ bool lc_layer(const dm2_layer_composite_desc& d, int 
     return true;
 }
 
-// one pixel of k_layer_composite (WEIGHTS: its blends' alpha * T into the block's table s_key / s_w)
+// one pixel of k_layer_composite (WEIGHTS: its blends' alpha * T into the block's table)
 template <int VEC, bool WEIGHTS>
 __device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_desc& d, int b, uint32_t px, uint32_t py,
                                                    float* __restrict__ out_color, float* __restrict__ out_depth,
                                                    float* __restrict__ out_final_T, int32_t* __restrict__ out_n_contrib,
-                                                   float* __restrict__ face_weights, int* s_key, float* s_w) {
+                                                   float* __restrict__ face_weights, FaceTable<float, 1>* tab) {
     const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
     f3 ro, rd;
     pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
@@ -87,9 +85,7 @@ __device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_des
         const float alpha = h.alpha;
         const float test_T = T * (1 - alpha);
         if constexpr (WEIGHTS) {
-            const int slot = lc_slot(s_key, f);
-            if (slot >= 0) atomicAdd(&s_w[slot], alpha * T);
-            else atomicAdd(face_weights + (int64_t)b * d.F + f, alpha * T);
+            tab->add_or(tab->slot(f), 0, alpha * T, face_weights + (int64_t)b * d.F + f);
         }
         C0 += c0 * alpha * T; C1 += c1 * alpha * T; C2 += c2 * alpha * T;
         D += h.iD * alpha * T;
@@ -120,32 +116,25 @@ __device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_des
     if (out_n_contrib) out_n_contrib[pix] = n_contrib;
 }
 
-// WEIGHTS (dm2_layers_composite_weights): every blend adds its alpha * T into the per-block LDS table of the backward's kind
-// (keyed by face id, LC_PROBES probes, straight to global memory when no slot is free); the table is flushed with one global
-// atomic per (block, face).
+// WEIGHTS (dm2_layers_composite_weights): every blend adds its alpha * T into a FaceTable of one accumulator per face, flushed
+// with one global atomic per (block, face).  Without WEIGHTS no table is declared.
 template <int VEC, bool WEIGHTS>
 __global__ void __launch_bounds__(TILE_PIX)
 k_layer_composite(dm2_layer_composite_desc d, float* __restrict__ out_color, float* __restrict__ out_depth,
                   float* __restrict__ out_final_T, int32_t* __restrict__ out_n_contrib, float* __restrict__ face_weights) {
-    __shared__ int s_key[WEIGHTS ? LC_SLOTS : 1];
-    __shared__ float s_w[WEIGHTS ? LC_SLOTS : 1];
     const int b = blockIdx.z;
     const int tid = threadIdx.x;
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
-    const bool inside = (px < (uint32_t)d.W) && (py < (uint32_t)d.H);
+    const TilePixel t = tile_pixel(tid, d.W, d.H);
     if constexpr (WEIGHTS) {
-        for (int i = tid; i < LC_SLOTS; i += TILE_PIX) { s_key[i] = -1; s_w[i] = 0.f; }
+        __shared__ FaceTable<float, 1> tab;
+        tab.clear(tid);
         __syncthreads();
-        if (inside) lc_composite_pixel<VEC, true>(d, b, px, py, out_color, out_depth, out_final_T, out_n_contrib, face_weights, s_key, s_w);
+        if (t.inside) lc_composite_pixel<VEC, true>(d, b, t.px, t.py, out_color, out_depth, out_final_T, out_n_contrib, face_weights, &tab);
         __syncthreads();
-        for (int i = tid; i < LC_SLOTS; i += TILE_PIX) {
-            const int f = s_key[i];
-            const float w = s_w[i];
-            if (f >= 0 && w != 0.0f) atomicAdd(face_weights + (int64_t)b * d.F + f, w);
-        }
+        tab.flush_by_slot(tid, [&](int f, int, float w) { atomicAdd(face_weights + (int64_t)b * d.F + f, w); });
     } else {
-        if (!inside) return;
-        lc_composite_pixel<VEC, false>(d, b, px, py, out_color, out_depth, out_final_T, out_n_contrib, nullptr, nullptr, nullptr);
+        if (!t.inside) return;
+        lc_composite_pixel<VEC, false>(d, b, t.px, t.py, out_color, out_depth, out_final_T, out_n_contrib, nullptr, nullptr);
     }
 }
 
@@ -173,17 +162,13 @@ template <bool ALPHA>
 __global__ void __launch_bounds__(TILE_PIX)
 k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                       const int32_t* __restrict__ n_contrib, LcGrads o, const float* __restrict__ dL_dalpha) {
-    __shared__ int s_key[LC_SLOTS];
-    __shared__ float s_acc[LC_NCOMP * LC_SLOTS];                       // component-major: [comp][slot]
+    __shared__ FaceTable<float, LC_NCOMP> tab;
     const int b = blockIdx.z;
     const int tid = threadIdx.x;
-    for (int i = tid; i < LC_SLOTS; i += TILE_PIX) s_key[i] = -1;
-    for (int i = tid; i < LC_NCOMP * LC_SLOTS; i += TILE_PIX) s_acc[i] = 0.0f;
+    tab.clear(tid);
     __syncthreads();
 
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
-    const bool inside = (px < (uint32_t)d.W) && (py < (uint32_t)d.H);
-    const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+    const auto [px, py, inside, pix] = tile_pixel(tid, d.W, d.H);
     const int n = inside ? min(n_contrib[pix], d.L) : 0;
     if (n > 0) {
         f3 ro, rd;
@@ -235,11 +220,11 @@ k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_d
                 const float om = 1 - h.alpha;
                 R0 = h.alpha * c0 + om * R0; R1 = h.alpha * c1 + om * R1; R2 = h.alpha * c2 + om * R2;
                 RD = h.alpha * h.iD + om * RD;
-                const int slot = lc_slot(s_key, fs[j]);
+                const int slot = tab.slot(fs[j]);
                 if (slot >= 0) {
 #pragma unroll
                     for (int c = 0; c < LC_NCOMP; c++)
-                        if (g[c] != 0.0f) atomicAdd(&s_acc[c * LC_SLOTS + slot], g[c]);
+                        if (g[c] != 0.0f) tab.add(slot, c, g[c]);
                 } else {
                     lc_global_add(d, b, fs[j], g, o);
                 }
@@ -249,24 +234,19 @@ k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_d
     }
     __syncthreads();
     // flush: one global atomic per (face or vertex row, component) of every face the tile's pixels hit
-    for (int i = tid; i < LC_NCOMP * LC_SLOTS; i += TILE_PIX) {
-        const int c = i / LC_SLOTS, slot = i - c * LC_SLOTS;
-        const int f = s_key[slot];
-        if (f < 0) continue;
-        const float g = s_acc[i];
-        if (g == 0.0f) continue;
-        if (c == LC_OP) { atomicAdd(o.dopacity + f, g); continue; }
-        if (c == LC_IN) { atomicAdd(o.dintense + (int64_t)b * d.F + f, g); continue; }
+    tab.flush_by_component(tid, [&](int f, int c, float g) {
+        if (c == LC_OP) { atomicAdd(o.dopacity + f, g); return; }
+        if (c == LC_IN) { atomicAdd(o.dintense + (int64_t)b * d.F + f, g); return; }
         const int vi = c < LC_DZ ? c / 3 : c - LC_DZ;
         const int64_t v = d.faces[3 * (int64_t)f + vi];
         if (c < LC_DZ) atomicAdd(o.dcolor + 3 * v + (c - 3 * vi), g);
         else atomicAdd(o.dndc + ((int64_t)b * d.P + v) * 3 + 2, g);
-    }
+    });
 }
 
 void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color, float* out_depth, float* out_final_T,
                             int32_t* out_n_contrib, float* out_face_weights, hipStream_t st) {
-    const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
+    const dim3 grid = tile_grid(d.W, d.H, d.B);
     // layer ids as 16- or 8-byte vectors where L and the pointer allow it
     const uintptr_t a = (uintptr_t)d.render_layers;
     const int vec = (d.L % 4 == 0 && a % 16 == 0) ? 4 : (d.L % 2 == 0 && a % 8 == 0) ? 2 : 1;
@@ -283,7 +263,7 @@ void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color,
 void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const float* dL_dcolor, const float* dL_ddepth,
                                      const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
                                      float* dL_dverts_ndc, float* dL_dfaces_intense, const float* dL_dalpha, hipStream_t st) {
-    const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
+    const dim3 grid = tile_grid(d.W, d.H, d.B);
     const LcGrads o{dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense};
     if (dL_dalpha)
         hipLaunchKernelGGL(k_layer_composite_bwd<true>, grid, dim3(TILE_PIX), 0, st, d, dL_dcolor, dL_ddepth, n_contrib, o, dL_dalpha);

@@ -22,7 +22,7 @@
 // in its face's depth range: rz_off_plane keeps the noise t of a ray in the face's plane out of the slots.
 //
 // Backward: per listed slot the ray is intersected again and dL/dp_k = (g1 - g0) du/dp_k + (g2 - g0) dv/dp_k + g_t dt/dp_k,
-// in fp64 (rz_hit_grad), added into the per-block face table of dm2_face_table.h (fp64 slots), flushed as fp32 atomics.
+// in fp64 (rz_hit_grad), added into the block's FaceTable (dm2_face_table.h; fp64 accumulators), flushed as fp32 atomics.
 #include <hip/hip_runtime.h>
 
 #include "dm2_device_math.h"
@@ -88,9 +88,7 @@ k_rasterize(dm2_layers_desc d, const float* __restrict__ min_depths, const float
     const int b = blockIdx.z;
     const uint32_t gx = (d.W + TILE - 1) / TILE, gy = (d.H + TILE - 1) / TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
-    const bool inside = (px < (uint32_t)d.W) && (py < (uint32_t)d.H);
-    const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+    const auto [px, py, inside, pix] = tile_pixel(tid, d.W, d.H);
     f3 ro = {0, 0, 0}, rd = {0, 0, 0};
     if (inside) pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
     const uint32_t tile = ((uint32_t)b * gy + blockIdx.y) * gx + blockIdx.x;
@@ -220,17 +218,14 @@ __device__ __forceinline__ bool rz_hit_grad(f3 ro_f, f3 rd_f, const float* pa, c
 __global__ void __launch_bounds__(TILE_PIX)
 k_rasterize_bwd(dm2_layers_desc d, const int32_t* __restrict__ layers, const float* __restrict__ dL_dbary,
                 const float* __restrict__ dL_dt, float* __restrict__ dL_dverts) {
-    __shared__ int s_key[LC_SLOTS];
-    __shared__ double s_acc[RZ_NCOMP * LC_SLOTS];                      // component-major: [comp][slot]
+    __shared__ FaceTable<double, RZ_NCOMP> tab;
     const int b = blockIdx.z;
     const int tid = threadIdx.x;
-    for (int i = tid; i < LC_SLOTS; i += TILE_PIX) s_key[i] = -1;
-    for (int i = tid; i < RZ_NCOMP * LC_SLOTS; i += TILE_PIX) s_acc[i] = 0.0;
+    tab.clear(tid);
     __syncthreads();
 
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
-    if ((px < (uint32_t)d.W) && (py < (uint32_t)d.H)) {
-        const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+    const auto [px, py, inside, pix] = tile_pixel(tid, d.W, d.H);
+    if (inside) {
         f3 ro, rd;
         pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
         for (int l = 0; l < d.L; l++) {
@@ -244,32 +239,29 @@ k_rasterize_bwd(dm2_layers_desc d, const int32_t* __restrict__ layers, const flo
             const int64_t v[3] = {d.faces[3 * (int64_t)f], d.faces[3 * (int64_t)f + 1], d.faces[3 * (int64_t)f + 2]};
             double w[3], G[3];
             if (!rz_hit_grad(ro, rd, d.verts + 3 * v[0], d.verts + 3 * v[1], d.verts + 3 * v[2], g1 - g0, g2 - g0, gt, w, G)) continue;
-            const int slot = lc_slot(s_key, f);
+            const int slot = tab.slot(f);
 #pragma unroll
             for (int c = 0; c < RZ_NCOMP; c++) {
                 const double gc = w[c / 3] * G[c % 3];
                 if (gc == 0.0) continue;
-                if (slot >= 0) atomicAdd(&s_acc[c * LC_SLOTS + slot], gc);
+                if (slot >= 0) tab.add(slot, c, gc);
                 else atomicAdd(dL_dverts + 3 * v[c / 3] + c % 3, (float)gc);
             }
         }
     }
     __syncthreads();
     // flush: one global atomic per (vertex row, component) of every face the tile's pixels listed
-    for (int i = tid; i < RZ_NCOMP * LC_SLOTS; i += TILE_PIX) {
-        const int c = i / LC_SLOTS, slot = i - c * LC_SLOTS;
-        const int f = s_key[slot];
-        if (f < 0) continue;
-        const float g = (float)s_acc[i];
-        if (g == 0.0f) continue;
+    tab.flush_by_component(tid, [&](int f, int c, double sum) {
+        const float g = (float)sum;
+        if (g == 0.0f) return;                                           // a sum below fp32's range
         const int64_t v = d.faces[3 * (int64_t)f + c / 3];
         atomicAdd(dL_dverts + 3 * v + c % 3, g);
-    }
+    });
 }
 
 void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                       int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, hipStream_t st) {
-    const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
+    const dim3 grid = tile_grid(d.W, d.H, d.B);
 #define DM2_RZ_LAUNCH(KR) \
     hipLaunchKernelGGL(k_rasterize<KR>, grid, dim3(TILE_PIX), 0, st, d, fs.min_depths, fs.max_depths, ranges, face_list, \
                        render_layers, render_layers_cnt, bary, t)
@@ -283,7 +275,7 @@ void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2
 
 void launch_rasterize_backward(const dm2_layers_desc& d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                                float* dL_dverts, hipStream_t st) {
-    const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
+    const dim3 grid = tile_grid(d.W, d.H, d.B);
     hipLaunchKernelGGL(k_rasterize_bwd, grid, dim3(TILE_PIX), 0, st, d, render_layers, dL_dbary, dL_dt, dL_dverts);
 }
 

@@ -18,11 +18,10 @@
 // tex backward: the scatter.  One block per 16 x 16 pixel tile and view, one lane per pixel, one layer at a time (slot l of
 // neighbouring pixels is usually one surface, so its texels are neighbours; the L slots of a pixel are unrelated texels), the
 // channels of a layer in chunks of CH.
-// A (slot, corner, channel) contribution goes into the texel's slot of the per-block table of dm2_face_table.h, keyed by the
-// texel's linear index j * Wt + i (CH fp32 accumulators per slot, channel-major with a stride that keeps the 64 lanes of the
-// flush in 64 banks); the block then flushes with one global atomic per (texel, channel) it holds, consecutive lanes on
-// consecutive channels of one texel.  A texel that finds no slot adds straight to global memory: under minification a tile
-// touches up to 1024 distinct texels per layer and this is the usual route.  The table is cleared for every layer (a table
+// A (slot, corner, channel) contribution goes into the texel's slot of the block's FaceTable (dm2_face_table.h), keyed by the
+// texel's linear index j * Wt + i (CH fp32 accumulators per slot, a stride that keeps the 64 lanes of the flush in 64 banks),
+// flushed by slot: consecutive lanes on consecutive channels of one texel.  Under minification a tile touches up to 1024
+// distinct texels per layer, and straight to global memory is then the usual route.  The table is cleared for every layer (a table
 // kept across the layers of a tile fills up with the first layers' texels and measured 1.1-2x slower); within a
 // layer the keys stay from chunk to chunk, so a texel keeps its slot.
 #include <hip/hip_runtime.h>
@@ -204,23 +203,20 @@ k_texture_bwd_tex(TexSizes z, const int32_t* __restrict__ layers, const float* _
                   float* __restrict__ dL_dtex) {
     constexpr int NTAP = FILTER == TX_LINEAR ? 4 : 1;
     constexpr int STRIDE = LC_SLOTS + (64 + CH - 1) / CH;                     // flush: bank = (c * (64 / CH) + slot) % 64
-    __shared__ int s_key[LC_SLOTS];
-    __shared__ float s_acc[CH * STRIDE];                                      // channel-major: [c][slot]
+    __shared__ FaceTable<float, CH, STRIDE> tab;
     const int b = blockIdx.z, tid = threadIdx.x;
-    const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
-    const bool inside = (px < (uint32_t)z.W) && (py < (uint32_t)z.H);
-    const int64_t pix = ((int64_t)b * z.H + py) * z.W + px;
+    const TilePixel t = tile_pixel(tid, z.W, z.H);
     const int C = z.C, L = z.L;
     float* dst = dL_dtex + (z.view_textures ? (int64_t)b * z.texels * C : 0);
     for (int l = 0; l < L; l++) {
-        const int64_t s = pix * L + l;
+        const int64_t s = t.pix * L + l;
         TexTap tap = {{0, 0, 0, 0}, 0.0f, 0.0f};
-        const bool live = inside && tx_tap<FILTER, BOUNDARY>(z, s, layers, uv, tap);
+        const bool live = t.inside && tx_tap<FILTER, BOUNDARY>(z, s, layers, uv, tap);
         const float w[4] = {(1.0f - tap.fx) * (1.0f - tap.fy), tap.fx * (1.0f - tap.fy), (1.0f - tap.fx) * tap.fy, tap.fx * tap.fy};
-        for (int i = tid; i < LC_SLOTS; i += TILE_PIX) s_key[i] = -1;
+        tab.clear_keys(tid);
         for (int c0 = 0; c0 < C; c0 += CH) {
             const int nc = min(CH, C - c0);
-            for (int i = tid; i < CH * STRIDE; i += TILE_PIX) s_acc[i] = 0.0f;
+            tab.clear_acc(tid);
             __syncthreads();
             if (live) {
                 float gv[CH];
@@ -230,26 +226,21 @@ k_texture_bwd_tex(TexSizes z, const int32_t* __restrict__ layers, const float* _
                 for (int k = 0; k < NTAP; k++) {
                     const int key = tap.idx[k];
                     const float wk = FILTER == TX_LINEAR ? w[k] : 1.0f;
-                    const int slot = lc_slot(s_key, key);
+                    const int slot = tab.slot(key);
 #pragma unroll
                     for (int c = 0; c < CH; c++) {
                         if (c >= nc) continue;
                         const float v = wk * gv[c];
-                        if (slot >= 0) atomicAdd(&s_acc[c * STRIDE + slot], v);
+                        if (slot >= 0) tab.add(slot, c, v);
                         else atomicAdd(dst + (int64_t)key * C + c0 + c, v);
                     }
                 }
             }
             __syncthreads();
             // flush: one global atomic per (texel, channel) the table holds; lane -> (slot, c), c fastest
-            for (int i = tid; i < CH * LC_SLOTS; i += TILE_PIX) {
-                const int slot = i / CH, c = i - slot * CH;
-                const int key = s_key[slot];
-                if (key < 0 || c >= nc) continue;
-                const float v = s_acc[c * STRIDE + slot];
-                if (v == 0.0f) continue;
-                atomicAdd(dst + (int64_t)key * C + c0 + c, v);
-            }
+            tab.flush_by_slot(tid, [&](int key, int c, float v) {
+                if (c < nc) atomicAdd(dst + (int64_t)key * C + c0 + c, v);
+            });
             __syncthreads();
         }
     }
@@ -301,7 +292,7 @@ void launch_texture_backward(int B, int H, int W, int L, int Ht, int Wt, int C, 
 #undef DM2_TX_UV
     }
     if (dL_dtex) {
-        const dim3 grid((W + TILE - 1) / TILE, (H + TILE - 1) / TILE, B);
+        const dim3 grid = tile_grid(W, H, B);
 #define DM2_TX_TEX_CH(F, Bd, CH) hipLaunchKernelGGL((k_texture_bwd_tex<F, Bd, CH>), grid, dim3(TILE_PIX), 0, st, z, render_layers, uv, dL_dout, dL_dtex)
 #define DM2_TX_TEX(F, Bd)                       \
     if (C == 1) DM2_TX_TEX_CH(F, Bd, 1);        \
