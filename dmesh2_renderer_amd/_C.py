@@ -117,6 +117,10 @@ class LayerCompositeDesc(ctypes.Structure):
     ]
 
 
+class Window(ctypes.Structure):
+    _fields_ = [("patch_min", _vp), ("full_W", _i32), ("full_H", _i32)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "dm2_abi_version": (ctypes.c_int, []),
@@ -133,6 +137,19 @@ EXPORTS = {
     "dm2_layers_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "dm2_rasterize_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dm2_rasterize_backward": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _vp, _vp, _vp, _vp]),
+    "dm2_layers_plan_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _sz, _vp, ctypes.POINTER(_i64),
+                                              ctypes.POINTER(_i64)]),
+    "dm2_layers_run_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz,
+                                             _vp, _sz, _vp, _vp, _vp]),
+    "dm2_rasterize_run_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp, _sz, _vp,
+                                                _sz, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_rasterize_backward_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp]),
+    "dm2_coverage_window": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 5),
+    "dm2_coverage_backward_window": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
+    "dm2_layers_composite_window": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp,
+                                                   _vp]),
+    "dm2_layers_composite_backward_window": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), ctypes.POINTER(Window), _vp, _vp, _vp,
+                                                            _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_interpolate": (ctypes.c_int, [_i32] * 8 + [_vp] * 6),
     "dm2_interpolate_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 8),
     "dm2_texture": (ctypes.c_int, [_i32] * 10 + [_vp] * 5),
@@ -367,6 +384,48 @@ class analytic_rays:
 
     def __exit__(self, *exc):
         _tls.analytic = self.old
+
+
+class window:
+    """``with _C.window(patch_min, full_width, full_height): _C.rasterize_layers_cuda(...)`` (and generate_render_layers /
+    coverage / composite_layers, and their backwards): the call works on a window of the frame.  ``patch_min`` (B,2) int32 on
+    the GPU = the (x, y) origin of each view's window in its (full_width, full_height) frame; the call's width / height, its
+    ray tensors and every (B,H,W,...) tensor are then the window's (include/dm2_hip.h: dm2_window), and the ``*_window`` entry
+    points run.  That the windows lie inside the frame is the caller's check (Renderer does it, with one read-back).  None:
+    no window, the calls as they are without one.  A side channel like ``analytic_rays``: the signatures stay as they are."""
+
+    def __init__(self, patch_min, full_width=0, full_height=0):
+        self.val = None if patch_min is None else (patch_min, int(full_width), int(full_height))
+
+    def __enter__(self):
+        self.old = getattr(_tls, "window", None)
+        _tls.window = self.val
+
+    def __exit__(self, *exc):
+        _tls.window = self.old
+
+
+def _window(B, W, H, dev, keep):
+    """The thread's window for a call of B views and a W x H window on ``dev`` -> ctypes Window, or None (no window)."""
+    w = getattr(_tls, "window", None)
+    if w is None:
+        return None
+    pm, fw, fh = w
+    if pm.dtype != torch.int32 or tuple(pm.shape) != (B, 2) or pm.device != dev:
+        raise RuntimeError(f"window: patch_min must be int32 (B, 2) on {dev}, got {pm.dtype} {tuple(pm.shape)} on {pm.device}")
+    if W > fw or H > fh:
+        raise RuntimeError(f"window: a {W} x {H} window does not fit a {fw} x {fh} frame")
+    pm = pm.contiguous()
+    keep.append(pm)
+    win = Window()
+    win.patch_min, win.full_W, win.full_H = (pm.data_ptr() if pm.numel() > 0 else None), fw, fh
+    return win
+
+
+def _frame_size(width, height):
+    """The size analytic rays must have been declared for: the frame of the thread's window, or the call's own width / height."""
+    w = getattr(_tls, "window", None)
+    return (w[1], w[2]) if w is not None else (width, height)
 
 
 class aa_grad_to_verts:
@@ -687,6 +746,8 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
     bad(tuple(tet_faces.shape) != (T, 4), "tet_faces must have dimensions (T, 4)")
     bad(tuple(verts_ndc.shape) != (B, P, 3) or tuple(verts_image.shape) != (B, P, 2), "verts_ndc/verts_image shape mismatch")
     ana = _analytic(B, dev)
+    keep: list = []
+    win = _window(B, width, height, dev, keep)           # (then width / height and the rays are the window's)
     bad(ana is None and (tuple(image_ray_o.shape) != (B, height, width, 3) or tuple(image_ray_d.shape) != (B, height, width, 3)),
         "image_ray_o/image_ray_d must have dimensions (B, H, W, 3)")
     ts = dict(verts=_c(verts, f32), faces=_c(faces, i32), tets=_c(tets, i32), face_tets=_c(face_tets, i32),
@@ -697,7 +758,7 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
     for k, t in ts.items():
         setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
     if ana is not None:
-        if (ana[1], ana[2]) != (width, height):
+        if (ana[1], ana[2]) != _frame_size(width, height):
             raise RuntimeError("analytic_rays: the image size differs from generate_render_layers_cuda's width / height")
         d.flags |= DM2_FLAG_ANALYTIC_RAYS
         d.ray_cam = ana[0].data_ptr()
@@ -714,13 +775,23 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
         face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn))
         img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_IMAGE, N, Tn))
         nr, longest = _i64(0), _i64(0)
-        if lib.dm2_layers_plan(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest)):
+        if win is None:
+            rc = lib.dm2_layers_plan(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest))
+        else:
+            rc = lib.dm2_layers_plan_window(ctypes.byref(d), ctypes.byref(win), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr),
+                                            ctypes.byref(longest))
+        if rc:
             raise _err(lib, "generate_render_layers_cuda (plan)")
         R = int(nr.value)
         bin_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_BINNING, R, Tn))
         tet_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_TETS, T, 0))
-        if lib.dm2_layers_run(ctypes.byref(d), R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(),
-                              _ptr(img_buf), img_buf.numel(), _ptr(tet_buf), tet_buf.numel(), _ptr(layers), _ptr(cnt), st):
+        run_args = (R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf),
+                    img_buf.numel(), _ptr(tet_buf), tet_buf.numel(), _ptr(layers), _ptr(cnt), st)
+        if win is None:
+            rc = lib.dm2_layers_run(ctypes.byref(d), *run_args)
+        else:
+            rc = lib.dm2_layers_run_window(ctypes.byref(d), ctypes.byref(win), *run_args)
+        if rc:
             raise _err(lib, "generate_render_layers_cuda (run)")
     generate_render_layers_cuda.last_debug = (R, face_buf, bin_buf, img_buf)      # kept for tests
     return layers, cnt
@@ -728,8 +799,9 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
 
 def _rasterize_desc(width, height, B, verts, faces, image_ray_o, image_ray_d, num_layers, keep, face_existence=None,
                     verts_ndc=None, verts_image=None):
-    """Checks (in the style of generate_render_layers_cuda) + the dm2_layers_desc of a rasterize call (T = 0: no tets).
-    The backward passes no face_existence / verts_ndc / verts_image: it reads neither."""
+    """Checks (in the style of generate_render_layers_cuda) + the dm2_layers_desc of a rasterize call (T = 0: no tets); under
+    ``window``, width / height and the rays are the window's.  The backward passes no face_existence / verts_ndc / verts_image:
+    it reads neither."""
     def bad(cond, msg):
         if cond:
             raise RuntimeError(msg)
@@ -762,7 +834,7 @@ def _rasterize_desc(width, height, B, verts, faces, image_ray_o, image_ray_d, nu
     for k, t in ts.items():
         setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
     if ana is not None:
-        if (ana[1], ana[2]) != (width, height):
+        if (ana[1], ana[2]) != _frame_size(width, height):
             raise RuntimeError("analytic_rays: the image size differs from the rasterize call's width / height")
         keep.append(ana[0])
         d.flags |= DM2_FLAG_ANALYTIC_RAYS
@@ -785,6 +857,7 @@ def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc
         raise RuntimeError("verts_ndc / verts_image must have dimensions (B, P, 3) / (B, P, 2)")
     d, dev = _rasterize_desc(width, height, verts_ndc.size(0), verts, faces, image_ray_o, image_ray_d, num_layers, keep,
                              face_existence=face_existence, verts_ndc=verts_ndc, verts_image=verts_image)
+    win = _window(d.B, d.W, d.H, dev, keep)
     B, F, H, W, L = d.B, d.F, d.H, d.W, d.L
     f32, i32 = torch.float32, torch.int32
     N, Tn, BF = B * H * W, _tiles(B, W, H), B * F
@@ -801,12 +874,22 @@ def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc
         face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn))
         img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_IMAGE, N, Tn))
         nr, longest = _i64(0), _i64(0)
-        if lib.dm2_layers_plan(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest)):
+        if win is None:
+            rc = lib.dm2_layers_plan(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest))
+        else:
+            rc = lib.dm2_layers_plan_window(ctypes.byref(d), ctypes.byref(win), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr),
+                                            ctypes.byref(longest))
+        if rc:
             raise _err(lib, "rasterize_layers_cuda (plan)")
         R = int(nr.value)
         bin_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_BINNING, R, Tn))
-        if lib.dm2_rasterize_run(ctypes.byref(d), R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf),
-                                 bin_buf.numel(), _ptr(img_buf), img_buf.numel(), _ptr(layers), _ptr(cnt), _ptr(bary), _ptr(t), st):
+        run_args = (R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf),
+                    img_buf.numel(), _ptr(layers), _ptr(cnt), _ptr(bary), _ptr(t), st)
+        if win is None:
+            rc = lib.dm2_rasterize_run(ctypes.byref(d), *run_args)
+        else:
+            rc = lib.dm2_rasterize_run_window(ctypes.byref(d), ctypes.byref(win), *run_args)
+        if rc:
             raise _err(lib, "rasterize_layers_cuda (run)")
     return layers, cnt, bary, t
 
@@ -821,6 +904,7 @@ def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, ima
     B, H, W, L = (int(x) for x in render_layers.shape)
     keep: list = []
     d, dev = _rasterize_desc(W, H, B, verts, faces, image_ray_o, image_ray_d, L, keep)
+    win = _window(B, W, H, dev, keep)
     f32 = torch.float32
     checks = []
     if dL_dbary is not None:
@@ -838,7 +922,12 @@ def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, ima
     if B * H * W * L == 0 or d.F == 0 or (gb is None and gt is None):
         return dverts
     with torch.cuda.device(dev):
-        if lib.dm2_rasterize_backward(ctypes.byref(d), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts), _stream(dev)):
+        if win is None:
+            rc = lib.dm2_rasterize_backward(ctypes.byref(d), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts), _stream(dev))
+        else:
+            rc = lib.dm2_rasterize_backward_window(ctypes.byref(d), ctypes.byref(win), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts),
+                                                   _stream(dev))
+        if rc:
             raise _err(lib, "rasterize_layers_backward_cuda")
     return dverts
 
@@ -1101,8 +1190,14 @@ def coverage_cuda(render_layers, verts_image, faces, temperature=1.0):
     cov = torch.empty((B, H, W, L), dtype=torch.float32, device=dev)       # (every element written by the kernel)
     if B * H * W * L == 0:
         return cov
+    keep: list = []
+    win = _window(B, W, H, dev, keep)                    # (then render_layers is the window's, verts_image the frame's)
     with torch.cuda.device(dev):
-        if lib.dm2_coverage(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev)):
+        if win is None:
+            rc = lib.dm2_coverage(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev))
+        else:
+            rc = lib.dm2_coverage_window(*sizes, ctypes.byref(win), _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev))
+        if rc:
             raise _err(lib, "coverage_cuda")
     return cov
 
@@ -1118,8 +1213,15 @@ def coverage_backward_cuda(render_layers, verts_image, faces, temperature, grad_
     dimage = torch.zeros((B, P, 2), dtype=torch.float32, device=dev)       # (summed into)
     if B * H * W * L == 0 or P == 0 or F == 0:
         return dimage
+    keep: list = []
+    win = _window(B, W, H, dev, keep)
     with torch.cuda.device(dev):
-        if lib.dm2_coverage_backward(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(gc), _ptr(dimage), _stream(dev)):
+        if win is None:
+            rc = lib.dm2_coverage_backward(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(gc), _ptr(dimage), _stream(dev))
+        else:
+            rc = lib.dm2_coverage_backward_window(*sizes, ctypes.byref(win), _ptr(rl), _ptr(vi), _ptr(fc), _ptr(gc), _ptr(dimage),
+                                                  _stream(dev))
+        if rc:
             raise _err(lib, "coverage_backward_cuda")
     return dimage
 
@@ -1160,7 +1262,7 @@ def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, fac
     for k, t in ts.items():
         setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
     if ana is not None:
-        if (ana[1], ana[2]) != (W, H):
+        if (ana[1], ana[2]) != _frame_size(W, H):
             raise RuntimeError("analytic_rays: the image size differs from render_layers' width / height")
         keep.append(ana[0])
         d.flags |= DM2_FLAG_ANALYTIC_RAYS
@@ -1182,6 +1284,7 @@ def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacit
     keep: list = []
     d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                              image_ray_o, image_ray_d, keep)
+    win = _window(d.B, d.W, d.H, dev, keep)              # (then render_layers and the rays are the window's)
     B, H, W = d.B, d.H, d.W
     f32 = torch.float32
     color = torch.empty((B, H, W, 3), dtype=f32, device=dev)
@@ -1193,7 +1296,10 @@ def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacit
     if B * H * W == 0:
         return (color, depth, final_T, n_contrib) + extra
     with torch.cuda.device(dev):
-        if weights is None:
+        if win is not None:
+            rc = lib.dm2_layers_composite_window(ctypes.byref(d), ctypes.byref(win), _ptr(color), _ptr(depth), _ptr(final_T),
+                                                 _ptr(n_contrib), _ptr(weights), _stream(dev))
+        elif weights is None:
             rc = lib.dm2_layers_composite(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib), _stream(dev))
         else:
             rc = lib.dm2_layers_composite_weights(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib),
@@ -1213,6 +1319,7 @@ def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, fac
     keep: list = []
     d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                              image_ray_o, image_ray_d, keep)
+    win = _window(d.B, d.W, d.H, dev, keep)              # (then render_layers and the rays are the window's)
     B, P, F, H, W = d.B, d.P, d.F, d.H, d.W
     f32 = torch.float32
     checks = [(n_contrib, (B, H, W), "n_contrib"), (dL_dcolor, (B, H, W, 3), "dL_dcolor"), (dL_ddepth, (B, H, W), "dL_ddepth")]
@@ -1231,7 +1338,10 @@ def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, fac
     if B * H * W == 0:
         return dcolor, dopacity, dndc, dintense
     with torch.cuda.device(dev):
-        if ga is None:
+        if win is not None:
+            rc = lib.dm2_layers_composite_backward_window(ctypes.byref(d), ctypes.byref(win), _ptr(gc), _ptr(gd), _ptr(ga), _ptr(nc),
+                                                          _ptr(dcolor), _ptr(dopacity), _ptr(dndc), _ptr(dintense), _stream(dev))
+        elif ga is None:
             rc = lib.dm2_layers_composite_backward(ctypes.byref(d), _ptr(gc), _ptr(gd), _ptr(nc), _ptr(dcolor), _ptr(dopacity),
                                                    _ptr(dndc), _ptr(dintense), _stream(dev))
         else:

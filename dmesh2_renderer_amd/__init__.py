@@ -24,6 +24,7 @@ raise ``RuntimeError``.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Sequence
 
@@ -43,6 +44,21 @@ _FUSED_PREP_DEFAULT = os.environ.get("DM2_FUSED_PREP", "1") != "0"
 _FUSED_AA_GRAD = os.environ.get("DM2_FUSED_AA_GRAD", "1") != "0"
 _TABLES_FROM_IMAGE = os.environ.get("DM2_TABLES_FROM_IMAGE", "1") != "0"     # fused prep: AA tables built inside the op's plan, never materialised
 _W_EPS = 1e-4   # |w| clamp of the projection, sign kept (reference __init__.py:254-255)
+
+
+class _Entered:
+    """``with _Entered(a, b):`` = ``with a, b:`` for context managers put together elsewhere (entered only here)."""
+
+    def __init__(self, *managers):
+        self.managers = managers
+
+    def __enter__(self):
+        self.stack = contextlib.ExitStack()
+        for m in self.managers:
+            self.stack.enter_context(m)
+
+    def __exit__(self, *exc):
+        return self.stack.__exit__(*exc)
 
 
 class RenderFunction(torch.autograd.Function):
@@ -226,12 +242,13 @@ class Renderer(torch.nn.Module):
             return t[idx[0]:idx[0] + len(idx)]
         return t[idx]
 
-    def select_rays(self, batch_mvp_idx, batch_patch_min, patch_width, patch_height):
-        """Rays of the (patch_height, patch_width) window at patch_min of each batch item (reference :264-302)."""
+    def select_rays(self, batch_mvp_idx, batch_patch_min, patch_width, patch_height, _origins=None):
+        """Rays of the (patch_height, patch_width) window at patch_min of each batch item (reference :264-302).
+        ``_origins``: the (B,2) origins as a list, where the caller has read them back already (``_window``)."""
         # one read-back of the (B,2) patch origins serves the reference's two bound checks (same messages) and tells whether
         # every window is the whole frame -- then the ray tensors are handed over as views, not gathered into a copy
         # (2 x 24.9 MB per camera at 1080p)
-        pm = [[int(v) for v in row] for row in batch_patch_min.tolist()]
+        pm = _origins if _origins is not None else [[int(v) for v in row] for row in batch_patch_min.tolist()]
         assert all(p[0] + patch_width <= self.width for p in pm), "Some b_patch_max_x exceed self.width"
         assert all(p[1] + patch_height <= self.height for p in pm), "Some b_patch_max_y exceed self.height"
         if patch_width == self.width and patch_height == self.height and all(p[0] == 0 and p[1] == 0 for p in pm):
@@ -244,6 +261,36 @@ class Renderer(torch.nn.Module):
         cols = px0.to(dev).view(-1, 1, 1) + torch.arange(patch_width, device=dev).view(1, 1, -1)
         cam = cams.view(-1, 1, 1)
         return self.ray_o[cam, rows, cols], self.ray_d[cam, rows, cols]
+
+    # -- windows on the deferred path ------------------------------------------------
+    def _window(self, batch_mvp_idx, patch_min, patch_width, patch_height, device):
+        """The checks of a window of rasterize / generate / coverage / render -> (patch_min as (B,2) int32 on ``device``, the
+        origins as a list): the origins are read back once, for all checks (and for ``select_rays``).  ValueError for a shape
+        other than (B,2), a negative size or a negative origin; ``select_rays``' two assertions for a window past the frame."""
+        B = len(batch_mvp_idx)
+        if patch_min.dim() != 2 or tuple(patch_min.shape) != (B, 2):
+            raise ValueError(f"patch_min must have dimensions ({B}, 2), got {tuple(patch_min.shape)}")
+        patch_width, patch_height = int(patch_width), int(patch_height)
+        if patch_width < 0 or patch_height < 0:
+            raise ValueError("patch_width and patch_height must not be negative")
+        pm = [[int(v) for v in row] for row in patch_min.tolist()]
+        if any(p[0] < 0 or p[1] < 0 for p in pm):
+            raise ValueError("patch_min must not be negative")
+        assert all(p[0] + patch_width <= self.width for p in pm), "Some b_patch_max_x exceed self.width"
+        assert all(p[1] + patch_height <= self.height for p in pm), "Some b_patch_max_y exceed self.height"
+        return patch_min.to(device=device, dtype=torch.int32).contiguous(), pm
+
+    def _window_rays(self, batch_mvp_idx, pm_dev, pm, patch_width, patch_height):
+        """(ray_o, ray_d, context) of a window call: the window's cut of the ray tensors, or placeholders under analytic rays;
+        the context carries the origins (and the cameras) to the op through ``_C``'s side channels."""
+        f32 = torch.float32
+        win = _C.window(pm_dev, self.width, self.height)
+        if getattr(self, "analytic_rays", False):
+            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
+            ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
+            return ph, ph, _Entered(win, _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height))
+        ray_o, ray_d = self.select_rays(batch_mvp_idx, pm_dev, patch_width, patch_height, _origins=pm)
+        return ray_o.to(f32).contiguous(), ray_d.to(f32).contiguous(), _Entered(win)
 
     # -- projection --------------------------------------------------------------
     def compute_verts_ndc_image(self, verts, mv, proj):
@@ -293,9 +340,10 @@ class Renderer(torch.nn.Module):
                                        verts_color, faces_opacity, faces_intense, background, aa_temperature)
 
     def rasterize(self, batch_mvp_idx: Sequence[int], verts: torch.Tensor, faces: torch.Tensor, num_layers: int,
-                  faces_existence: torch.Tensor = None):
-        """The first ``num_layers`` faces each pixel's ray hits, over the full frame of every selected view (not in the
-        reference) -> render_layers (B,H,W,L) int32 face ids (-1 = empty), render_layers_cnt (B,H,W) int32, bary (B,H,W,L,3)
+                  faces_existence: torch.Tensor = None, patch_min: torch.Tensor = None, patch_width: int = None,
+                  patch_height: int = None):
+        """The first ``num_layers`` faces each pixel's ray hits, over the full frame of every selected view or over a window of
+        it (not in the reference) -> render_layers (B,H,W,L) int32 face ids (-1 = empty), render_layers_cnt (B,H,W) int32, bary (B,H,W,L,3)
         float32 = the weights of faces[f][0..2] at the hit (perspective-correct), t (B,H,W,L) float32 = the hit's distance
         along the pixel's ray; -1 in every empty slot.
 
@@ -304,7 +352,24 @@ class Renderer(torch.nn.Module):
         barycentrics >= 0); hits are ordered by (t, face id).  render_layers can go straight to ``LayeredRenderer.render``.
         bary and t are differentiable w.r.t. ``verts`` (``RasterizeFunction``); nothing flows through the rays (cameras get
         no gradient here) or through which faces are listed.  ``interpolate`` turns the ids and bary into an image of any
-        per-vertex attribute (normals, UVs, features), differentiably."""
+        per-vertex attribute (normals, UVs, features), differentiably.
+
+        Window: ``patch_min`` (B,2) int32 (x, y) per selected view, ``patch_width``, ``patch_height`` -- ``forward``'s
+        ``batch_patch_min`` and sizes -- rasterize that window of each view only: H, W above are then patch_height, patch_width.
+        Window pixel (x, y) of view b is frame pixel (x + patch_min[b,0], y + patch_min[b,1]) and takes that pixel's ray; the
+        16x16 tiles (the candidates' bbox test) are anchored at the window's origin, as in ``forward``.  So a window equals the
+        crop of the full frame where its origin is a multiple of 16, and elsewhere may differ in hits of faces whose bbox
+        misses the pixel's tile in one of the two grids.  The window must lie inside the frame (``select_rays``' assertions;
+        ValueError for a negative origin, or for ``patch_min`` without a size); an empty window returns empty tensors and
+        launches nothing.  Without ``patch_min`` the sizes must be None as well."""
+        if patch_min is None:
+            if patch_width is not None or patch_height is not None:
+                raise ValueError("patch_width / patch_height need patch_min")
+        else:
+            if patch_width is None or patch_height is None:
+                raise ValueError("patch_min needs patch_width and patch_height")
+            return self._rasterize_window(batch_mvp_idx, verts, faces, int(num_layers), faces_existence, patch_min, int(patch_width),
+                                          int(patch_height))
         mv = self.mv[batch_mvp_idx]
         proj = self.proj[batch_mvp_idx]
         i32, f32 = torch.int32, torch.float32
@@ -324,6 +389,31 @@ class Renderer(torch.nn.Module):
                 return RasterizeFunction.apply(*args, ph, ph, self.width, self.height, int(num_layers))
         ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
         return RasterizeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32), self.width, self.height, int(num_layers))
+
+    def _project_constants(self, batch_mvp_idx, verts, faces):
+        """verts_ndc, verts_image of the selected views without a graph: the plan's bins and depth cull, constants of the op."""
+        mv = self.mv[batch_mvp_idx]
+        proj = self.proj[batch_mvp_idx]
+        i32, f32 = torch.int32, torch.float32
+        with torch.no_grad():
+            if getattr(self, "fused_prep", False) and verts.is_cuda:
+                from . import prep
+                return prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
+            return self.compute_verts_ndc_image(verts, mv, proj)
+
+    def _rasterize_window(self, batch_mvp_idx, verts, faces, num_layers, faces_existence, patch_min, pw, ph):
+        i32, f32 = torch.int32, torch.float32
+        B, L, dev = len(batch_mvp_idx), num_layers, verts.device
+        pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
+        if pw == 0 or ph == 0:
+            return (torch.empty((B, ph, pw, L), dtype=i32, device=dev), torch.empty((B, ph, pw), dtype=i32, device=dev),
+                    torch.empty((B, ph, pw, L, 3), dtype=f32, device=dev), torch.empty((B, ph, pw, L), dtype=f32, device=dev))
+        verts_ndc, verts_image = self._project_constants(batch_mvp_idx, verts, faces)
+        fe = None if faces_existence is None else faces_existence.to(i32)
+        ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
+        with ctx:
+            return RasterizeFunction.apply(verts.to(f32), faces.to(i32), fe, verts_ndc.to(f32), verts_image.to(f32), ray_o, ray_d,
+                                           pw, ph, L)
 
     def interpolate(self, render_layers: torch.Tensor, bary: torch.Tensor, attr: torch.Tensor, attr_faces: torch.Tensor):
         """Attribute images from ``rasterize``'s hits (not in the reference): render_layers (B,H,W,L) int32 face ids (as
@@ -372,7 +462,7 @@ class Renderer(torch.nn.Module):
         return CompositeFunction.apply(values.to(f32), alpha.to(f32), rl, bg)
 
     def coverage(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
-                 temperature: float = 1.0):
+                 temperature: float = 1.0, patch_min: torch.Tensor = None):
         """The analytic pixel coverage of the listed faces (not in the reference): render_layers (B,H,W,L) int32 face ids over
         the full frame (as ``rasterize`` / ``generate`` return them, or hand-built), verts (P,3), faces (F,3), temperature in
         [0, 1] (ValueError otherwise) -> cov (B,H,W,L) float32, ``Renderer.forward``'s coverage ratio of a hit:
@@ -383,9 +473,21 @@ class Renderer(torch.nn.Module):
         A slot whose id is outside [0, F), or whose face names a vertex outside [0, P), is empty: cov = 0.  Where the triangle
         misses the pixel (or the clipper reports an error) cov = 0 too; at temperature 0 cov = 1 in every non-empty slot.
         Whether the pixel's ray hits the face is not looked at.  Differentiable w.r.t. ``verts`` and, where they require grad,
-        the cameras, through the projection (``CoverageFunction``); nothing flows through which faces are listed."""
+        the cameras, through the projection (``CoverageFunction``); nothing flows through which faces are listed.
+
+        Window: with ``patch_min`` (B,2) int32 (x, y) per selected view, render_layers is a window's (as ``rasterize`` /
+        ``generate`` return it for the same ``patch_min``; its own H, W are the window's size) and the pixel of slot (b, y, x)
+        is [x + patch_min[b,0], ...+1] x [y + patch_min[b,1], ...+1] of the frame: the crop of the full-frame result.  The
+        window must lie inside the frame (``select_rays``' assertions; ValueError for a negative origin)."""
         if not (0.0 <= float(temperature) <= 1.0):
             raise ValueError("temperature must be in the range [0, 1]")
+        pm_dev = None
+        if patch_min is not None:
+            if render_layers.dim() != 4:
+                raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+            pm_dev, _ = self._window(batch_mvp_idx, patch_min, render_layers.shape[2], render_layers.shape[1], verts.device)
+            if render_layers.numel() == 0:
+                return torch.empty(tuple(render_layers.shape), dtype=torch.float32, device=verts.device)
         mv = self.mv[batch_mvp_idx]
         proj = self.proj[batch_mvp_idx]
         i32, f32 = torch.int32, torch.float32
@@ -394,7 +496,8 @@ class Renderer(torch.nn.Module):
             _, verts_image = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
         else:
             _, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
-        return CoverageFunction.apply(render_layers.to(i32), verts_image.to(f32), faces.to(i32), float(temperature))
+        with _C.window(pm_dev, self.width, self.height):
+            return CoverageFunction.apply(render_layers.to(i32), verts_image.to(f32), faces.to(i32), float(temperature))
 
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
@@ -478,6 +581,7 @@ class LayeredCompositeFunction(torch.autograd.Function):
     def forward(ctx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                 image_ray_o, image_ray_d):
         ctx.analytic = getattr(_C._tls, "analytic", None)
+        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
         ctx.alpha = bool(getattr(_C._tls, "alpha_output", False))
         if ctx.alpha:
             ctx.set_materialize_grads(False)
@@ -503,8 +607,8 @@ class LayeredCompositeFunction(torch.autograd.Function):
                 grad_color = torch.zeros(tuple(n_contrib.shape) + (3,), dtype=torch.float32, device=n_contrib.device)
             if grad_depth is None:
                 grad_depth = torch.zeros(tuple(n_contrib.shape), dtype=torch.float32, device=n_contrib.device)
-        ana = ctx.analytic
-        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))):
+        ana, win = ctx.analytic, ctx.window
+        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
             extra = {} if grad_alpha is None else {"dL_dout_alpha": grad_alpha}
             dcolor, dopacity, dndc, dintense = _C.composite_layers_backward_cuda(
                 render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
@@ -527,6 +631,7 @@ class RasterizeFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces, faces_existence, verts_ndc, verts_image, image_ray_o, image_ray_d, width, height, num_layers):
         ctx.analytic = getattr(_C._tls, "analytic", None)
+        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
         ctx.set_materialize_grads(False)            # bary / t left out of the loss arrive as None
         layers, cnt, bary, t = _C.rasterize_layers_cuda(width, height, verts.detach(), faces, faces_existence, verts_ndc.detach(),
                                                         verts_image.detach(), image_ray_o, image_ray_d, num_layers)
@@ -539,8 +644,8 @@ class RasterizeFunction(torch.autograd.Function):
         if (grad_bary is None and grad_t is None) or not ctx.needs_input_grad[0]:
             return (None,) * 10
         layers, verts, faces, ray_o, ray_d = ctx.saved_tensors
-        ana = ctx.analytic
-        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))):
+        ana, win = ctx.analytic, ctx.window
+        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
             dverts = _C.rasterize_layers_backward_cuda(layers, verts, faces, ray_o, ray_d, grad_bary, grad_t)
         return (dverts,) + (None,) * 9
 
@@ -645,6 +750,7 @@ class CoverageFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, render_layers, verts_image, faces, temperature):
         ctx.set_materialize_grads(False)
+        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
         cov = _C.coverage_cuda(render_layers, verts_image.detach(), faces, temperature)
         ctx.temperature = float(temperature)
         ctx.save_for_backward(render_layers, verts_image.detach(), faces)
@@ -655,7 +761,9 @@ class CoverageFunction(torch.autograd.Function):
         if grad_cov is None or ctx.temperature == 0.0 or not ctx.needs_input_grad[1]:
             return None, None, None, None
         render_layers, verts_image, faces = ctx.saved_tensors
-        return None, _C.coverage_backward_cuda(render_layers, verts_image, faces, ctx.temperature, grad_cov), None, None
+        win = ctx.window
+        with _C.window(*(win if win is not None else (None,))):
+            return None, _C.coverage_backward_cuda(render_layers, verts_image, faces, ctx.temperature, grad_cov), None, None
 
 
 class LayeredRenderer(Renderer):
@@ -673,8 +781,22 @@ class LayeredRenderer(Renderer):
 
     def generate(self, batch_mvp_idx: Sequence[int], verts: torch.Tensor, faces: torch.Tensor,
                  tets: torch.Tensor, face_tets: torch.Tensor, tet_faces: torch.Tensor,
-                 faces_existence: torch.Tensor, num_layers: int):
-        """-> render_layers (B,H,W,L) int32 face ids (-1 = empty), render_layers_cnt (B,H,W) int32."""
+                 faces_existence: torch.Tensor, num_layers: int, patch_min: torch.Tensor = None, patch_width: int = None,
+                 patch_height: int = None):
+        """-> render_layers (B,H,W,L) int32 face ids (-1 = empty), render_layers_cnt (B,H,W) int32.
+
+        Not in the reference: ``patch_min`` (B,2) int32 (x, y) per selected view with ``patch_width``, ``patch_height``
+        generates the layers of that window of each view only (H, W = patch_height, patch_width): window pixel (x, y) is frame
+        pixel (x + patch_min[b,0], y + patch_min[b,1]) with that pixel's ray, the first-hit pass's 16x16 tiles anchored at the
+        window's origin -- ``Renderer.rasterize``'s window rules and errors."""
+        if patch_min is None:
+            if patch_width is not None or patch_height is not None:
+                raise ValueError("patch_width / patch_height need patch_min")
+        else:
+            if patch_width is None or patch_height is None:
+                raise ValueError("patch_min needs patch_width and patch_height")
+            return self._generate_window(batch_mvp_idx, verts, faces, tets, face_tets, tet_faces, faces_existence, int(num_layers),
+                                         patch_min, int(patch_width), int(patch_height))
         mv = self.mv[batch_mvp_idx]
         proj = self.proj[batch_mvp_idx]
         i32, f32 = torch.int32, torch.float32
@@ -698,9 +820,22 @@ class LayeredRenderer(Renderer):
             faces_existence.to(i32), verts_ndc.to(f32), verts_image.to(f32),
             ray_o.to(f32), ray_d.to(f32), num_layers)
 
+    def _generate_window(self, batch_mvp_idx, verts, faces, tets, face_tets, tet_faces, faces_existence, num_layers, patch_min, pw, ph):
+        i32, f32 = torch.int32, torch.float32
+        B, dev = len(batch_mvp_idx), verts.device
+        pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
+        if pw == 0 or ph == 0:
+            return torch.empty((B, ph, pw, num_layers), dtype=i32, device=dev), torch.empty((B, ph, pw), dtype=i32, device=dev)
+        verts_ndc, verts_image = self._project_constants(batch_mvp_idx, verts, faces)
+        ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
+        with ctx:
+            return _C.generate_render_layers_cuda(
+                pw, ph, verts.to(f32), faces.to(i32), tets.to(i32), face_tets.to(i32), tet_faces.to(i32), faces_existence.to(i32),
+                verts_ndc.to(f32), verts_image.to(f32), ray_o, ray_d, num_layers)
+
     def render(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
                verts_color: torch.Tensor, faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor,
-               return_alpha: bool = False, return_face_weights: bool = False):
+               return_alpha: bool = False, return_face_weights: bool = False, patch_min: torch.Tensor = None):
         """Composite per-pixel face layers front to back -> color (B,H,W,3), depth (B,H,W) in [0,1] (0 = background); with
         ``return_alpha=True`` also alpha (B,H,W) = 1 - T, differentiable w.r.t. faces_opacity; with
         ``return_face_weights=True`` last face_weights (B,F), the sum of faces_opacity * T over each face's blends (a face
@@ -712,7 +847,16 @@ class LayeredRenderer(Renderer):
         Gradients reach verts_color, faces_opacity, faces_intense, and verts through the projected depth only (as in
         Renderer); none goes through the barycentrics, in which the layers are piecewise constant.  Cameras that require
         grad get theirs the same way, through verts_ndc z.
+
+        Window: with ``patch_min`` (B,2) int32 (x, y) per selected view, render_layers is a window's (``generate`` /
+        ``rasterize`` with the same ``patch_min``; its own H, W are the window's size), each pixel takes the ray of frame pixel
+        (x + patch_min[b,0], y + patch_min[b,1]), and the images are the window's: the crop of the full-frame result.  The
+        window must lie inside the frame (``select_rays``' assertions; ValueError for a negative origin); an empty window
+        returns empty images and launches nothing.
         """
+        if patch_min is not None:
+            return self._render_window(batch_mvp_idx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense,
+                                       background, return_alpha, return_face_weights, patch_min)
         mv = self.mv[batch_mvp_idx]
         proj = self.proj[batch_mvp_idx]
         i32, f32 = torch.int32, torch.float32
@@ -734,4 +878,32 @@ class LayeredRenderer(Renderer):
             with _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
                 out = LayeredCompositeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32))
         # NDC z in [-1,1] (background +1) -> [0,1] with background 0, as Renderer.forward
+        return _finish(out)
+
+    def _render_window(self, batch_mvp_idx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense, background,
+                       return_alpha, return_face_weights, patch_min):
+        i32, f32 = torch.int32, torch.float32
+        if render_layers.dim() != 4:
+            raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+        B, ph, pw, dev = len(batch_mvp_idx), int(render_layers.shape[1]), int(render_layers.shape[2]), verts.device
+        pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
+        if pw == 0 or ph == 0:
+            out = (torch.empty((B, ph, pw, 3), dtype=f32, device=dev), torch.empty((B, ph, pw), dtype=f32, device=dev))
+            if return_alpha:
+                out += (torch.empty((B, ph, pw), dtype=f32, device=dev),)
+            if return_face_weights:
+                out += (torch.zeros((B, faces.shape[0]), dtype=f32, device=dev),)
+            return out
+        mv = self.mv[batch_mvp_idx]
+        proj = self.proj[batch_mvp_idx]
+        if getattr(self, "fused_prep", False) and verts.is_cuda:
+            from . import prep
+            verts_ndc, _ = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
+        else:
+            verts_ndc, _ = self.compute_verts_ndc_image(verts, mv, proj)
+        ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
+        with ctx, _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
+            out = LayeredCompositeFunction.apply(render_layers.to(i32), verts.to(f32), faces.to(i32), verts_color.to(f32),
+                                                 faces_opacity.to(f32), faces_intense.to(f32), verts_ndc.to(f32), background.to(f32),
+                                                 ray_o, ray_d)
         return _finish(out)

@@ -377,9 +377,25 @@ static int check_layers_desc(const dm2_layers_desc* d) {
     return 0;
 }
 
+// The window a call works in: the caller's, or -- a null pointer -- the full frame of W x H at origin 0.  A window's origins
+// are device memory: that it lies inside the frame is the caller's check (no kernel indexes memory through an origin).
+static int resolve_window(const dm2_window* win, int W, int H, dm2_window* out) {
+    if (!win) { *out = dm2_window{nullptr, W, H}; return 0; }
+    if (win->full_W < W || win->full_H < H) return fail("window: full_W / full_H must hold the window's W / H");
+    *out = *win;
+    return 0;
+}
+
 int dm2_layers_plan(const dm2_layers_desc* d, void* face_scratch, size_t face_bytes, void* stream, int64_t* num_rendered,
                     int64_t* max_tile_entries) {
+    return dm2_layers_plan_window(d, nullptr, face_scratch, face_bytes, stream, num_rendered, max_tile_entries);
+}
+
+int dm2_layers_plan_window(const dm2_layers_desc* d, const dm2_window* win, void* face_scratch, size_t face_bytes, void* stream,
+                           int64_t* num_rendered, int64_t* max_tile_entries) {
     if (check_layers_desc(d)) return 1;
+    dm2_window w;
+    if (resolve_window(win, d->W, d->H, &w)) return 1;
     if (!num_rendered || !max_tile_entries) return fail("num_rendered / max_tile_entries is null");
     hipStream_t st = (hipStream_t)stream;
     const int64_t BF = (int64_t)d->B * d->F, Tn = tiles_of(d->B, d->W, d->H);
@@ -387,10 +403,11 @@ int dm2_layers_plan(const dm2_layers_desc* d, void* face_scratch, size_t face_by
     if (BF == 0 || Tn == 0) return 0;
     if (dm2_scratch_bytes(DM2_SCRATCH_FACE, BF, 2 * Tn) > face_bytes) return fail("face scratch too small");
     dm2::FaceState fs = dm2::FaceState::carve(face_scratch, BF, Tn, dm2::scan_temp_bytes(BF), false);
-    // patch_min = 0 (renderer.cu:557-558): a null patch_min means "all zeros"
+    // the full frame: patch_min = 0 (renderer.cu:557-558), a null patch_min means "all zeros"; a window: its origins, and the
+    // tiles of its W x H
     uint32_t* host_meta = nullptr; uint32_t seq = 0;
     if (plan_meta_prepare(&host_meta, &seq)) return 1;
-    DM2_HIP(dm2::launch_preprocess_scan(d->B, d->P, d->F, d->W, d->H, nullptr, d->faces, d->verts_ndc, d->verts_image, fs, nullptr,
+    DM2_HIP(dm2::launch_preprocess_scan(d->B, d->P, d->F, d->W, d->H, w.patch_min, d->faces, d->verts_ndc, d->verts_image, fs, nullptr,
                                         host_meta, seq, nullptr, nullptr, st));
     DM2_HIP(hipGetLastError());
     return plan_meta_wait(fs.plan_meta, st, num_rendered, max_tile_entries, nullptr);
@@ -400,7 +417,17 @@ int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_t
                    void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
                    void* tet_scratch, size_t tet_bytes,
                    int32_t* render_layers, int32_t* render_layers_cnt, void* stream) {
+    return dm2_layers_run_window(d, nullptr, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes,
+                                 image_scratch, image_bytes, tet_scratch, tet_bytes, render_layers, render_layers_cnt, stream);
+}
+
+int dm2_layers_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                          void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                          void* image_scratch, size_t image_bytes, void* tet_scratch, size_t tet_bytes,
+                          int32_t* render_layers, int32_t* render_layers_cnt, void* stream) {
     if (check_layers_desc(d)) return 1;
+    dm2_window w;
+    if (resolve_window(win, d->W, d->H, &w)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int64_t BF = (int64_t)d->B * d->F, N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
     if (N == 0) return 0;
@@ -419,7 +446,7 @@ int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_t
         DM2_HIP(hipMemsetAsync(ls.ranges, 0, (size_t)Tn * sizeof(uint2), st));
     }
     if (tet_scratch && dm2_scratch_bytes(DM2_SCRATCH_LAYER_TETS, d->T, 0) > tet_bytes) return fail("tet scratch too small");
-    dm2::launch_layers(*d, fs, ls.ranges, bs.face_list, ls, tet_scratch, render_layers, render_layers_cnt, st);
+    dm2::launch_layers(*d, w, fs, ls.ranges, bs.face_list, ls, tet_scratch, render_layers, render_layers_cnt, st);
     DM2_HIP(hipGetLastError());
     return 0;
 }
@@ -434,7 +461,17 @@ static int check_rasterize_inputs(const dm2_layers_desc* d) {
 int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries, void* face_scratch, size_t face_bytes,
                       void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
                       int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream) {
+    return dm2_rasterize_run_window(d, nullptr, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes,
+                                    image_scratch, image_bytes, render_layers, render_layers_cnt, bary, t, stream);
+}
+
+int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                             void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                             void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
+                             float* bary, float* t, void* stream) {
     if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
+    dm2_window w;
+    if (resolve_window(win, d->W, d->H, &w)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int64_t BF = (int64_t)d->B * d->F, N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
     if (N == 0) return 0;
@@ -457,17 +494,24 @@ int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t ma
     } else {
         DM2_HIP(hipMemsetAsync(ls.ranges, 0, (size_t)Tn * sizeof(uint2), st));
     }
-    dm2::launch_rasterize(*d, fs, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, st);
+    dm2::launch_rasterize(*d, w, fs, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, st);
     DM2_HIP(hipGetLastError());
     return 0;
 }
 
 int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                            float* dL_dverts, void* stream) {
+    return dm2_rasterize_backward_window(d, nullptr, render_layers, dL_dbary, dL_dt, dL_dverts, stream);
+}
+
+int dm2_rasterize_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
+                                  const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream) {
     if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
+    dm2_window w;
+    if (resolve_window(win, d->W, d->H, &w)) return 1;
     if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0 || (!dL_dbary && !dL_dt)) return 0;   // nothing is listed or nothing flows
     if (!render_layers || !dL_dverts) return fail("render_layers / dL_dverts must not be null");
-    dm2::launch_rasterize_backward(*d, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
+    dm2::launch_rasterize_backward(*d, w, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
@@ -613,12 +657,17 @@ static int check_coverage_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int3
 
 int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
                  const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream) {
+    return dm2_coverage_window(B, H, W, L, P, F, temperature, nullptr, render_layers, verts_image, faces, out_cov, stream);
+}
+
+int dm2_coverage_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature, const dm2_window* win,
+                        const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream) {
     if (check_coverage_sizes(B, H, W, L, P, F, temperature)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
     if (!render_layers || !out_cov) return fail("coverage: render_layers and out_cov must not be null");
     if (F > 0 && !faces) return fail("coverage: faces must not be null");
     if (F > 0 && P > 0 && !verts_image) return fail("coverage: verts_image must not be null");
-    dm2::launch_coverage(B, H, W, L, P, F, temperature, render_layers, verts_image, faces, out_cov, (hipStream_t)stream);
+    dm2::launch_coverage(B, H, W, L, P, F, temperature, win ? win->patch_min : nullptr, render_layers, verts_image, faces, out_cov, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
@@ -626,10 +675,17 @@ int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t 
 int dm2_coverage_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
                           const int32_t* render_layers, const float* verts_image, const int32_t* faces, const float* dL_dcov,
                           float* dL_dverts_image, void* stream) {
+    return dm2_coverage_backward_window(B, H, W, L, P, F, temperature, nullptr, render_layers, verts_image, faces, dL_dcov,
+                                        dL_dverts_image, stream);
+}
+
+int dm2_coverage_backward_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                                 const dm2_window* win, const int32_t* render_layers, const float* verts_image,
+                                 const int32_t* faces, const float* dL_dcov, float* dL_dverts_image, void* stream) {
     if (check_coverage_sizes(B, H, W, L, P, F, temperature)) return 1;
     if ((int64_t)B * H * W * L == 0 || F == 0 || P == 0 || temperature == 0.0f || !dL_dcov || !dL_dverts_image) return 0;
     if (!render_layers || !faces || !verts_image) return fail("coverage_backward: render_layers, faces and verts_image must not be null");
-    dm2::launch_coverage_backward(B, H, W, L, P, F, temperature, render_layers, verts_image, faces, dL_dcov, dL_dverts_image,
+    dm2::launch_coverage_backward(B, H, W, L, P, F, temperature, win ? win->patch_min : nullptr, render_layers, verts_image, faces, dL_dcov, dL_dverts_image,
                                   (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
@@ -661,10 +717,17 @@ int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, fl
 
 int dm2_layers_composite_weights(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
                                  int32_t* out_n_contrib, float* out_face_weights, void* stream) {
+    return dm2_layers_composite_window(d, nullptr, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights, stream);
+}
+
+int dm2_layers_composite_window(const dm2_layer_composite_desc* d, const dm2_window* win, float* out_color, float* out_depth,
+                                float* out_final_T, int32_t* out_n_contrib, float* out_face_weights, void* stream) {
     if (check_composite_desc(d)) return 1;
+    dm2_window w;
+    if (resolve_window(win, d->W, d->H, &w)) return 1;
     if ((int64_t)d->B * d->H * d->W == 0) return 0;
     if (!out_color || !out_depth || !out_n_contrib) return fail("out_color / out_depth / out_n_contrib must not be null");
-    dm2::launch_layer_composite(*d, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights, (hipStream_t)stream);
+    dm2::launch_layer_composite(*d, w, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
@@ -679,11 +742,21 @@ int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const float
 int dm2_layers_composite_backward_alpha(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
                                         const float* dL_dout_alpha, const int32_t* n_contrib, float* dL_dverts_color,
                                         float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream) {
+    return dm2_layers_composite_backward_window(d, nullptr, dL_dout_color, dL_dout_depth, dL_dout_alpha, n_contrib, dL_dverts_color,
+                                                dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, stream);
+}
+
+int dm2_layers_composite_backward_window(const dm2_layer_composite_desc* d, const dm2_window* win, const float* dL_dout_color,
+                                         const float* dL_dout_depth, const float* dL_dout_alpha, const int32_t* n_contrib,
+                                         float* dL_dverts_color, float* dL_dfaces_opacity, float* dL_dverts_ndc,
+                                         float* dL_dfaces_intense, void* stream) {
     if (check_composite_desc(d)) return 1;
+    dm2_window w;
+    if (resolve_window(win, d->W, d->H, &w)) return 1;
     if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0) return 0;       // nothing blends: all gradients stay zero
     if (!dL_dout_color || !dL_dout_depth || !n_contrib) return fail("dL_dout_color / dL_dout_depth / n_contrib must not be null");
     if (!dL_dverts_color || !dL_dfaces_opacity || !dL_dverts_ndc || !dL_dfaces_intense) return fail("gradient outputs must not be null");
-    dm2::launch_layer_composite_backward(*d, dL_dout_color, dL_dout_depth, n_contrib, dL_dverts_color, dL_dfaces_opacity,
+    dm2::launch_layer_composite_backward(*d, w, dL_dout_color, dL_dout_depth, n_contrib, dL_dverts_color, dL_dfaces_opacity,
                                          dL_dverts_ndc, dL_dfaces_intense, dL_dout_alpha, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;

@@ -81,14 +81,15 @@ __device__ __forceinline__ void cov_ids(const int32_t* __restrict__ layers, int6
 // either way (the same bits).  Every slot of every pixel of the image is written.
 template <int LVEC>
 __global__ void __launch_bounds__(TILE_PIX)
-k_coverage(CovSizes z, const int32_t* __restrict__ layers, const float* __restrict__ image, const int32_t* __restrict__ faces,
+k_coverage(CovSizes z, const int32_t* __restrict__ patch_min, const int32_t* __restrict__ layers, const float* __restrict__ image, const int32_t* __restrict__ faces,
            float* __restrict__ out) {
     const auto [px, py, inside, pix] = tile_pixel(threadIdx.x, z.W, z.H);
     if (!inside) return;
     const int b = blockIdx.z;
+    const WinOrigin org = window_origin(patch_min);       // (the pixel's square lies in the frame: verts_image's units)
     const int64_t s0 = pix * z.L;
     const float2* im = reinterpret_cast<const float2*>(image) + (int64_t)b * z.P;
-    const float pxmin = (float)px, pxmax = pxmin + 1, pymin = (float)py, pymax = pymin + 1;
+    const float pxmin = (float)(px + org.x), pxmax = pxmin + 1, pymin = (float)(py + org.y), pymax = pymin + 1;
     const float pix_area = 1.0f;
     const float temp = z.temp;
     for (int l = 0; l < z.L; l += LVEC) {
@@ -117,7 +118,7 @@ k_coverage(CovSizes z, const int32_t* __restrict__ layers, const float* __restri
 // clipper reports no error and a non-zero area, and the Jacobian is not all zero (full cover).  The ids are read one at a time:
 // the clip and its Jacobian are inlined once, and a slot's 4 bytes are nothing next to them.
 __global__ void __launch_bounds__(TILE_PIX)
-k_coverage_bwd(CovSizes z, const int32_t* __restrict__ layers, const float* __restrict__ image, const int32_t* __restrict__ faces,
+k_coverage_bwd(CovSizes z, const int32_t* __restrict__ patch_min, const int32_t* __restrict__ layers, const float* __restrict__ image, const int32_t* __restrict__ faces,
                const float* __restrict__ g_cov, float* __restrict__ g_image) {
     __shared__ FaceTable<float, 6, LC_SLOTS + 6> tab;      // component 2 * vertex + (x, y); flush: bank = (6 c + slot) % 32
     const int tid = threadIdx.x;
@@ -126,10 +127,11 @@ k_coverage_bwd(CovSizes z, const int32_t* __restrict__ layers, const float* __re
     const auto [px, py, inside, pix] = tile_pixel(tid, z.W, z.H);
     const int b = blockIdx.z;
     float* gi = g_image + (int64_t)b * z.P * 2;
+    const WinOrigin org = window_origin(patch_min);
     if (inside) {
         const int64_t s0 = pix * z.L;
         const float2* im = reinterpret_cast<const float2*>(image) + (int64_t)b * z.P;
-        const float pxmin = (float)px, pxmax = pxmin + 1, pymin = (float)py, pymax = pymin + 1;
+        const float pxmin = (float)(px + org.x), pxmax = pxmin + 1, pymin = (float)(py + org.y), pymax = pymin + 1;
 #pragma unroll 1
         for (int l = 0; l < z.L; l++) {
             const int f = layers[s0 + l];
@@ -169,21 +171,21 @@ static CovSizes cov_sizes(int B, int H, int W, int L, int P, int F, float temper
     return z;
 }
 
-void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* render_layers,
+void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
                      const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st) {
     const CovSizes z = cov_sizes(B, H, W, L, P, F, temperature);
     const dim3 grid = tile_grid(W, H, B);
     const bool lvec = L % 4 == 0 && (((uintptr_t)render_layers | (uintptr_t)out_cov) & 15) == 0;
-    if (lvec) hipLaunchKernelGGL(k_coverage<4>, grid, dim3(TILE_PIX), 0, st, z, render_layers, verts_image, faces, out_cov);
-    else hipLaunchKernelGGL(k_coverage<1>, grid, dim3(TILE_PIX), 0, st, z, render_layers, verts_image, faces, out_cov);
+    if (lvec) hipLaunchKernelGGL(k_coverage<4>, grid, dim3(TILE_PIX), 0, st, z, patch_min, render_layers, verts_image, faces, out_cov);
+    else hipLaunchKernelGGL(k_coverage<1>, grid, dim3(TILE_PIX), 0, st, z, patch_min, render_layers, verts_image, faces, out_cov);
 }
 
-void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* render_layers,
+void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
                               const float* verts_image, const int32_t* faces, const float* dL_dcov, float* dL_dverts_image,
                               hipStream_t st) {
     const CovSizes z = cov_sizes(B, H, W, L, P, F, temperature);
     const dim3 grid = tile_grid(W, H, B);
-    hipLaunchKernelGGL(k_coverage_bwd, grid, dim3(TILE_PIX), 0, st, z, render_layers, verts_image, faces, dL_dcov, dL_dverts_image);
+    hipLaunchKernelGGL(k_coverage_bwd, grid, dim3(TILE_PIX), 0, st, z, patch_min, render_layers, verts_image, faces, dL_dcov, dL_dverts_image);
 }
 
 }  // namespace dm2

@@ -29,6 +29,14 @@ __device__ __forceinline__ f3 cross(f3 a, f3 b) {
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 
+// Origin of view blockIdx.z's window in its frame (dm2_window; a null patch_min: (0, 0)).  Wave-uniform: the pointer is a kernel
+// argument and the index blockIdx.z, so the two words arrive by scalar loads, once per block.
+struct WinOrigin { uint32_t x, y; };
+__device__ __forceinline__ WinOrigin window_origin(const int32_t* __restrict__ patch_min) {
+    if (!patch_min) return {0u, 0u};
+    return {(uint32_t)patch_min[2 * blockIdx.z], (uint32_t)patch_min[2 * blockIdx.z + 1]};
+}
+
 // ---- primary ray of a pixel, computed instead of read (DM2_FLAG_ANALYTIC_RAYS).  Operation order of the reference's
 // Renderer._init_rays (__init__.py:198-237): pixel centre (x + 0.5) / W * 2 - 1 -> (ndc_x, ndc_y, -1, 1), row vector times
 // inv(proj)^T, times inv(mv)^T (4-term sums in index order: the reference leaves the order to its BLAS), NO perspective

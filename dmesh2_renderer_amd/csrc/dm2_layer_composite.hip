@@ -67,13 +67,15 @@ __device__ __forceinline__ bool lc_layer(const dm2_layer_composite_desc& d, int 
 
 // one pixel of k_layer_composite (WEIGHTS: its blends' alpha * T into the block's table)
 template <int VEC, bool WEIGHTS>
-__device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_desc& d, int b, uint32_t px, uint32_t py,
+__device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_desc& d, const dm2_window& win, int b, uint32_t px, uint32_t py,
                                                    float* __restrict__ out_color, float* __restrict__ out_depth,
                                                    float* __restrict__ out_final_T, int32_t* __restrict__ out_n_contrib,
                                                    float* __restrict__ face_weights, FaceTable<float, 1>* tab) {
     const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+    // (a window: only the analytic ray needs the origin; the ray tensors are the window's own)
+    const WinOrigin org = window_origin(win.patch_min);
     f3 ro, rd;
-    pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+    pixel_ray(d, b, pix, px + org.x, py + org.y, win.full_W, win.full_H, ro, rd);
     const int32_t* ids = d.render_layers + pix * d.L;
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, D = 0.f;
     int n_contrib = 0;
@@ -120,7 +122,7 @@ __device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_des
 // with one global atomic per (block, face).  Without WEIGHTS no table is declared.
 template <int VEC, bool WEIGHTS>
 __global__ void __launch_bounds__(TILE_PIX)
-k_layer_composite(dm2_layer_composite_desc d, float* __restrict__ out_color, float* __restrict__ out_depth,
+k_layer_composite(dm2_layer_composite_desc d, dm2_window win, float* __restrict__ out_color, float* __restrict__ out_depth,
                   float* __restrict__ out_final_T, int32_t* __restrict__ out_n_contrib, float* __restrict__ face_weights) {
     const int b = blockIdx.z;
     const int tid = threadIdx.x;
@@ -129,12 +131,12 @@ k_layer_composite(dm2_layer_composite_desc d, float* __restrict__ out_color, flo
         __shared__ FaceTable<float, 1> tab;
         tab.clear(tid);
         __syncthreads();
-        if (t.inside) lc_composite_pixel<VEC, true>(d, b, t.px, t.py, out_color, out_depth, out_final_T, out_n_contrib, face_weights, &tab);
+        if (t.inside) lc_composite_pixel<VEC, true>(d, win, b, t.px, t.py, out_color, out_depth, out_final_T, out_n_contrib, face_weights, &tab);
         __syncthreads();
         tab.flush_by_slot(tid, [&](int f, int, float w) { atomicAdd(face_weights + (int64_t)b * d.F + f, w); });
     } else {
         if (!t.inside) return;
-        lc_composite_pixel<VEC, false>(d, b, t.px, t.py, out_color, out_depth, out_final_T, out_n_contrib, nullptr, nullptr);
+        lc_composite_pixel<VEC, false>(d, win, b, t.px, t.py, out_color, out_depth, out_final_T, out_n_contrib, nullptr, nullptr);
     }
 }
 
@@ -160,7 +162,7 @@ __device__ __forceinline__ void lc_global_add(const dm2_layer_composite_desc& d,
 
 template <bool ALPHA>
 __global__ void __launch_bounds__(TILE_PIX)
-k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
+k_layer_composite_bwd(dm2_layer_composite_desc d, dm2_window win, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
                       const int32_t* __restrict__ n_contrib, LcGrads o, const float* __restrict__ dL_dalpha) {
     __shared__ FaceTable<float, LC_NCOMP> tab;
     const int b = blockIdx.z;
@@ -171,8 +173,9 @@ k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_d
     const auto [px, py, inside, pix] = tile_pixel(tid, d.W, d.H);
     const int n = inside ? min(n_contrib[pix], d.L) : 0;
     if (n > 0) {
+        const WinOrigin org = window_origin(win.patch_min);
         f3 ro, rd;
-        pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+        pixel_ray(d, b, pix, px + org.x, py + org.y, win.full_W, win.full_H, ro, rd);
         const int32_t* ids = d.render_layers + pix * d.L;
         const float g0 = dL_dcolor[3 * pix], g1 = dL_dcolor[3 * pix + 1], g2 = dL_dcolor[3 * pix + 2], gd = dL_ddepth[pix];
         float R0 = d.background[0], R1 = d.background[1], R2 = d.background[2], RD = 1.0f;
@@ -244,14 +247,14 @@ k_layer_composite_bwd(dm2_layer_composite_desc d, const float* __restrict__ dL_d
     });
 }
 
-void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color, float* out_depth, float* out_final_T,
+void launch_layer_composite(const dm2_layer_composite_desc& d, const dm2_window& win, float* out_color, float* out_depth, float* out_final_T,
                             int32_t* out_n_contrib, float* out_face_weights, hipStream_t st) {
     const dim3 grid = tile_grid(d.W, d.H, d.B);
     // layer ids as 16- or 8-byte vectors where L and the pointer allow it
     const uintptr_t a = (uintptr_t)d.render_layers;
     const int vec = (d.L % 4 == 0 && a % 16 == 0) ? 4 : (d.L % 2 == 0 && a % 8 == 0) ? 2 : 1;
 #define DM2_LC_LAUNCH(V, W) \
-    hipLaunchKernelGGL((k_layer_composite<V, W>), grid, dim3(TILE_PIX), 0, st, d, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights)
+    hipLaunchKernelGGL((k_layer_composite<V, W>), grid, dim3(TILE_PIX), 0, st, d, win, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights)
     if (out_face_weights) {
         if (vec == 4) DM2_LC_LAUNCH(4, true); else if (vec == 2) DM2_LC_LAUNCH(2, true); else DM2_LC_LAUNCH(1, true);
     } else {
@@ -260,15 +263,15 @@ void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color,
 #undef DM2_LC_LAUNCH
 }
 
-void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const float* dL_dcolor, const float* dL_ddepth,
+void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const dm2_window& win, const float* dL_dcolor, const float* dL_ddepth,
                                      const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
                                      float* dL_dverts_ndc, float* dL_dfaces_intense, const float* dL_dalpha, hipStream_t st) {
     const dim3 grid = tile_grid(d.W, d.H, d.B);
     const LcGrads o{dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense};
     if (dL_dalpha)
-        hipLaunchKernelGGL(k_layer_composite_bwd<true>, grid, dim3(TILE_PIX), 0, st, d, dL_dcolor, dL_ddepth, n_contrib, o, dL_dalpha);
+        hipLaunchKernelGGL(k_layer_composite_bwd<true>, grid, dim3(TILE_PIX), 0, st, d, win, dL_dcolor, dL_ddepth, n_contrib, o, dL_dalpha);
     else
-        hipLaunchKernelGGL(k_layer_composite_bwd<false>, grid, dim3(TILE_PIX), 0, st, d, dL_dcolor, dL_ddepth, n_contrib, o, dL_dalpha);
+        hipLaunchKernelGGL(k_layer_composite_bwd<false>, grid, dim3(TILE_PIX), 0, st, d, win, dL_dcolor, dL_ddepth, n_contrib, o, dL_dalpha);
 }
 
 }  // namespace dm2

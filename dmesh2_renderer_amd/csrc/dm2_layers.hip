@@ -8,6 +8,9 @@
 // when W or H is not a multiple of 16), the "other faces" table cannot overflow
 // (forward.cu:884-896), layer writes are bounded by L, and the tet walk is
 // capped at T+1 steps so every wave terminates.
+//
+// Window (dm2_window): d.W, d.H, the tile grid and the (B,H,W,...) arrays are the window's; the ray is the frame pixel's:
+// pixel_ray gets px + origin, py + origin and the frame's size.  A null origin is (0, 0) in d.W x d.H: the full frame.
 #include <hip/hip_runtime.h>
 
 #include "dm2_device_math.h"
@@ -48,7 +51,7 @@ __device__ __forceinline__ f3 tet_face_outward_normal(const float* verts, const 
 }
 
 __global__ void __launch_bounds__(TILE_PIX)
-k_first_intersect(dm2_layers_desc d, const float* __restrict__ min_depths, const float* __restrict__ max_depths,
+k_first_intersect(dm2_layers_desc d, dm2_window win, const float* __restrict__ min_depths, const float* __restrict__ max_depths,
                   const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                   int32_t* __restrict__ first_face, int32_t* __restrict__ first_tet) {
     __shared__ LayRec recs[LAY_CHUNK];
@@ -59,8 +62,9 @@ k_first_intersect(dm2_layers_desc d, const float* __restrict__ min_depths, const
     const bool inside = (px < (uint32_t)d.W) && (py < (uint32_t)d.H);
     const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
     f3 ro = {0, 0, 0}, rd = {0, 0, 0};
+    const WinOrigin org = window_origin(win.patch_min);
     if (inside) {
-        pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+        pixel_ray(d, b, pix, px + org.x, py + org.y, win.full_W, win.full_H, ro, rd);
     }
     const uint32_t tile = ((uint32_t)b * gy + blockIdx.y) * gx + blockIdx.x;
     const uint2 range = ranges[tile];
@@ -109,15 +113,16 @@ k_first_intersect(dm2_layers_desc d, const float* __restrict__ min_depths, const
 }
 
 __global__ void __launch_bounds__(TILE_PIX)
-k_tet_walk(dm2_layers_desc d, const int32_t* __restrict__ first_face, const int32_t* __restrict__ first_tet,
+k_tet_walk(dm2_layers_desc d, dm2_window win, const int32_t* __restrict__ first_face, const int32_t* __restrict__ first_tet,
            int32_t* __restrict__ layers, int32_t* __restrict__ layers_cnt) {
     const int b = blockIdx.z;
     const int tid = threadIdx.x;
     const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
     if (!((px < (uint32_t)d.W) && (py < (uint32_t)d.H))) return;
     const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+    const WinOrigin org = window_origin(win.patch_min);
     f3 ro, rd;
-    pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+    pixel_ray(d, b, pix, px + org.x, py + org.y, win.full_W, win.full_H, ro, rd);
     int curr_face = first_face[pix], curr_tet = first_tet[pix];
     bool done = (curr_face == -1 || curr_tet == -1);
     int ndone = 0, steps = 0;
@@ -236,15 +241,16 @@ k_pack_tets(dm2_layers_desc d, TetRec* __restrict__ out) {
 }
 
 __global__ void __launch_bounds__(TILE_PIX)
-k_tet_walk_rec(dm2_layers_desc d, const TetRec* __restrict__ trecs, const int32_t* __restrict__ first_face,
+k_tet_walk_rec(dm2_layers_desc d, dm2_window win, const TetRec* __restrict__ trecs, const int32_t* __restrict__ first_face,
                const int32_t* __restrict__ first_tet, int32_t* __restrict__ layers, int32_t* __restrict__ layers_cnt) {
     const int b = blockIdx.z;
     const int tid = threadIdx.x;
     const uint32_t px = blockIdx.x * TILE + (tid & 15), py = blockIdx.y * TILE + (tid >> 4);
     if (!((px < (uint32_t)d.W) && (py < (uint32_t)d.H))) return;
     const int64_t pix = ((int64_t)b * d.H + py) * d.W + px;
+    const WinOrigin org = window_origin(win.patch_min);
     f3 ro, rd;
-    pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+    pixel_ray(d, b, pix, px + org.x, py + org.y, win.full_W, win.full_H, ro, rd);
     int curr_face = first_face[pix], curr_tet = first_tet[pix];
     bool done = (curr_face == -1 || curr_tet == -1);
     int ndone = 0, steps = 0;
@@ -302,7 +308,7 @@ k_tet_walk_rec(dm2_layers_desc d, const TetRec* __restrict__ trecs, const int32_
     layers_cnt[pix] = ndone;
 }
 
-void launch_layers(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
+void launch_layers(const dm2_layers_desc& d, const dm2_window& win, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                    LayerImageState ls, void* tet_scratch, int32_t* render_layers, int32_t* render_layers_cnt, hipStream_t st) {
     const dim3 grid((d.W + TILE - 1) / TILE, (d.H + TILE - 1) / TILE, d.B);
     const bool recs = tet_scratch && d.T > 0 && !(d.flags & DM2_FLAG_LEGACY_KERNELS);
@@ -311,12 +317,12 @@ void launch_layers(const dm2_layers_desc& d, const FaceState& fs, const uint2* r
         trecs = reinterpret_cast<TetRec*>(((uintptr_t)tet_scratch + ALIGN - 1) & ~(uintptr_t)(ALIGN - 1));
         hipLaunchKernelGGL(k_pack_tets, dim3((d.T + 255) / 256), dim3(256), 0, st, d, trecs);
     }
-    hipLaunchKernelGGL(k_first_intersect, grid, dim3(TILE_PIX), 0, st, d, fs.min_depths, fs.max_depths, ranges, face_list,
+    hipLaunchKernelGGL(k_first_intersect, grid, dim3(TILE_PIX), 0, st, d, win, fs.min_depths, fs.max_depths, ranges, face_list,
                        ls.first_face, ls.first_tet);
     if (recs)
-        hipLaunchKernelGGL(k_tet_walk_rec, grid, dim3(TILE_PIX), 0, st, d, trecs, ls.first_face, ls.first_tet, render_layers, render_layers_cnt);
+        hipLaunchKernelGGL(k_tet_walk_rec, grid, dim3(TILE_PIX), 0, st, d, win, trecs, ls.first_face, ls.first_tet, render_layers, render_layers_cnt);
     else
-        hipLaunchKernelGGL(k_tet_walk, grid, dim3(TILE_PIX), 0, st, d, ls.first_face, ls.first_tet, render_layers, render_layers_cnt);
+        hipLaunchKernelGGL(k_tet_walk, grid, dim3(TILE_PIX), 0, st, d, win, ls.first_face, ls.first_tet, render_layers, render_layers_cnt);
 }
 
 }  // namespace dm2

@@ -8,6 +8,9 @@
 // ray does not lie in (rz_off_plane, below); the hits are ordered by ascending (t, face id) and the first L are listed with
 // bary = (1 - u - v, u, v) and t.  -ffp-contract=off: bit-exact.
 //
+// Window (dm2_window): d.W, d.H, the tile grid, the tile lists and every (B,H,W,...) array are the window's; only the ray knows
+// the frame: pixel_ray gets the absolute pixel (px + origin) and the frame's size.  A null origin is (0, 0) in d.W x d.H.
+//
 // Layout: one lane per pixel, 16 x 16 tiles, the view on blockIdx.z; list chunks staged in LDS as k_first_intersect stages
 // them, the existence filter applied (and the survivors compacted) while staging.  Each lane keeps its KR nearest hits so far
 // in registers, sorted; a new hit goes in by a fully unrolled compare-and-swap over the slots (static indices only: no
@@ -80,7 +83,7 @@ __device__ __forceinline__ void rz_insert(RzList<KR>& h, int Lp, float t, int id
 
 template <int KR>
 __global__ void __launch_bounds__(TILE_PIX)
-k_rasterize(dm2_layers_desc d, const float* __restrict__ min_depths, const float* __restrict__ max_depths,
+k_rasterize(dm2_layers_desc d, dm2_window win, const float* __restrict__ min_depths, const float* __restrict__ max_depths,
             const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list, int32_t* __restrict__ out_layers,
             int32_t* __restrict__ out_cnt, float* __restrict__ out_bary, float* __restrict__ out_t) {
     __shared__ RzRec recs[RZ_CHUNK];
@@ -90,7 +93,8 @@ k_rasterize(dm2_layers_desc d, const float* __restrict__ min_depths, const float
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const auto [px, py, inside, pix] = tile_pixel(tid, d.W, d.H);
     f3 ro = {0, 0, 0}, rd = {0, 0, 0};
-    if (inside) pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+    const WinOrigin org = window_origin(win.patch_min);
+    if (inside) pixel_ray(d, b, pix, px + org.x, py + org.y, win.full_W, win.full_H, ro, rd);
     const uint32_t tile = ((uint32_t)b * gy + blockIdx.y) * gx + blockIdx.x;
     const uint2 range = ranges[tile];
     const int total = (int)(range.y - range.x);
@@ -216,7 +220,7 @@ __device__ __forceinline__ bool rz_hit_grad(f3 ro_f, f3 rd_f, const float* pa, c
 }
 
 __global__ void __launch_bounds__(TILE_PIX)
-k_rasterize_bwd(dm2_layers_desc d, const int32_t* __restrict__ layers, const float* __restrict__ dL_dbary,
+k_rasterize_bwd(dm2_layers_desc d, dm2_window win, const int32_t* __restrict__ layers, const float* __restrict__ dL_dbary,
                 const float* __restrict__ dL_dt, float* __restrict__ dL_dverts) {
     __shared__ FaceTable<double, RZ_NCOMP> tab;
     const int b = blockIdx.z;
@@ -225,9 +229,10 @@ k_rasterize_bwd(dm2_layers_desc d, const int32_t* __restrict__ layers, const flo
     __syncthreads();
 
     const auto [px, py, inside, pix] = tile_pixel(tid, d.W, d.H);
+    const WinOrigin org = window_origin(win.patch_min);
     if (inside) {
         f3 ro, rd;
-        pixel_ray(d, b, pix, px, py, d.W, d.H, ro, rd);
+        pixel_ray(d, b, pix, px + org.x, py + org.y, win.full_W, win.full_H, ro, rd);
         for (int l = 0; l < d.L; l++) {
             const int64_t s = pix * d.L + l;
             const int f = layers[s];
@@ -259,11 +264,11 @@ k_rasterize_bwd(dm2_layers_desc d, const int32_t* __restrict__ layers, const flo
     });
 }
 
-void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
+void launch_rasterize(const dm2_layers_desc& d, const dm2_window& win, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                       int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, hipStream_t st) {
     const dim3 grid = tile_grid(d.W, d.H, d.B);
 #define DM2_RZ_LAUNCH(KR) \
-    hipLaunchKernelGGL(k_rasterize<KR>, grid, dim3(TILE_PIX), 0, st, d, fs.min_depths, fs.max_depths, ranges, face_list, \
+    hipLaunchKernelGGL(k_rasterize<KR>, grid, dim3(TILE_PIX), 0, st, d, win, fs.min_depths, fs.max_depths, ranges, face_list, \
                        render_layers, render_layers_cnt, bary, t)
     if (d.L <= 1) DM2_RZ_LAUNCH(1);
     else if (d.L <= 2) DM2_RZ_LAUNCH(2);
@@ -273,10 +278,10 @@ void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2
 #undef DM2_RZ_LAUNCH
 }
 
-void launch_rasterize_backward(const dm2_layers_desc& d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
+void launch_rasterize_backward(const dm2_layers_desc& d, const dm2_window& win, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                                float* dL_dverts, hipStream_t st) {
     const dim3 grid = tile_grid(d.W, d.H, d.B);
-    hipLaunchKernelGGL(k_rasterize_bwd, grid, dim3(TILE_PIX), 0, st, d, render_layers, dL_dbary, dL_dt, dL_dverts);
+    hipLaunchKernelGGL(k_rasterize_bwd, grid, dim3(TILE_PIX), 0, st, d, win, render_layers, dL_dbary, dL_dt, dL_dverts);
 }
 
 }  // namespace dm2

@@ -216,20 +216,21 @@ int exchange_max_ranks();
 size_t tet_scratch_bytes(int64_t T);
 // tet_scratch (tet_scratch_bytes(T)) holds the packed per-tet records of the walk; nullptr = the reference-shaped walk
 // LayeredRenderer.render (dm2_layer_composite.hip)
-void launch_layer_composite(const dm2_layer_composite_desc& d, float* out_color, float* out_depth, float* out_final_T,
+// win (here and below): the render window, dm2_hip.h dm2_window; the full frame is {nullptr, d.W, d.H}
+void launch_layer_composite(const dm2_layer_composite_desc& d, const dm2_window& win, float* out_color, float* out_depth, float* out_final_T,
                             int32_t* out_n_contrib, float* out_face_weights, hipStream_t st);
-void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const float* dL_dcolor, const float* dL_ddepth,
+void launch_layer_composite_backward(const dm2_layer_composite_desc& d, const dm2_window& win, const float* dL_dcolor, const float* dL_ddepth,
                                      const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
                                      float* dL_dverts_ndc, float* dL_dfaces_intense, const float* dL_dalpha, hipStream_t st);
 // out_alpha[pix] = 1 - is.final_T[pix] for the N pixels of a forward (dm2_forward_alpha)
 void launch_forward_alpha(ImageState is, int64_t N, float* out_alpha, hipStream_t st);
-void launch_layers(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
+void launch_layers(const dm2_layers_desc& d, const dm2_window& win, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                    LayerImageState ls, void* tet_scratch, int32_t* render_layers, int32_t* render_layers_cnt, hipStream_t st);
 // Renderer.rasterize (dm2_rasterize.hip): the first d.L hits of every pixel over the plan's tile lists (d.L >= 1); every slot
 // of every pixel is written.  The backward adds into dL_dverts; either upstream gradient may be NULL.
-void launch_rasterize(const dm2_layers_desc& d, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
+void launch_rasterize(const dm2_layers_desc& d, const dm2_window& win, const FaceState& fs, const uint2* ranges, const uint32_t* face_list,
                       int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, hipStream_t st);
-void launch_rasterize_backward(const dm2_layers_desc& d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
+void launch_rasterize_backward(const dm2_layers_desc& d, const dm2_window& win, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                                float* dL_dverts, hipStream_t st);
 // Renderer.interpolate (dm2_interpolate.hip): every element of out / dL_dbary is written; the backward adds into dL_dattr;
 // either of its output pointers may be NULL.  B * H * W * L > 0 and C >= 1.
@@ -256,10 +257,10 @@ void launch_composite_backward(int B, int H, int W, int L, int C, int F, int per
                                const float* dL_dout, const float* dL_dacc, float* dL_dvalues, float* dL_dalpha, hipStream_t st);
 // Renderer.coverage (dm2_coverage.hip): every element of out_cov is written; the backward adds into dL_dverts_image (zero-filled
 // by the caller).  B * H * W * L > 0, 0 <= temperature <= 1 (the backward: > 0); faces may be NULL when F == 0, verts_image when
-// P == 0.
-void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* render_layers,
+// P == 0.  patch_min: the origins of a window (B,2), or nullptr (the full frame).
+void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
                      const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st);
-void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* render_layers,
+void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
                               const float* verts_image, const int32_t* faces, const float* dL_dcov, float* dL_dverts_image,
                               hipStream_t st);
 

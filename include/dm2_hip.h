@@ -235,7 +235,7 @@ int dm2_backward_alpha(const dm2_render_desc* d, int64_t num_rendered, int32_t f
 /* LayeredRenderer (render.h:101-119). */
 typedef struct dm2_layers_desc {
     int32_t B, P, F, T;
-    int32_t W, H, L;              /* full frame width/height, num_layers */
+    int32_t W, H, L;              /* full frame (with a dm2_window: the window's) width/height, num_layers */
     int32_t flags;                /* DM2_FLAG_ANALYTIC_RAYS, DM2_FLAG_LEGACY_KERNELS */
     const float* verts;           /* (P,3) */
     const int32_t* faces;         /* (F,3) */
@@ -263,6 +263,32 @@ int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_t
                    void* image_scratch, size_t image_bytes,
                    void* tet_scratch, size_t tet_bytes,
                    int32_t* render_layers, int32_t* render_layers_cnt, void* stream);
+
+/* A render window on the deferred path (dm2_layers_plan / dm2_layers_run / dm2_rasterize_* / dm2_coverage* /
+ * dm2_layers_composite*): the `*_window` entry points below take one next to the op's descriptor, whose W, H (and the H, W of
+ * dm2_coverage) are then the WINDOW's size, as in dm2_render_desc, and every (B,H,W,...) array is the window's.  Pixel (x, y)
+ * of view b's window is pixel (x + patch_min[b][0], y + patch_min[b][1]) of that view's full_W x full_H frame: its ray is that
+ * frame pixel's (the ray tensors, when given, are the window's own (B,H,W,3) cut of the frame's; DM2_FLAG_ANALYTIC_RAYS
+ * evaluates the absolute pixel with full_W, full_H), its pixel square for the coverage is the frame pixel's, and the 16 x 16
+ * tile grid is anchored at the window's origin (patch_min), as dm2_forward_plan anchors it.  verts_image stays in the full
+ * frame's pixel units.  The window must lie inside the frame (the caller checks: patch_min is device memory); the views may
+ * have different origins.  patch_min NULL: every origin is (0, 0).  A NULL window pointer: the entry point without `_window`,
+ * to the bit (that entry point forwards with NULL).  Gradients add into the same outputs as without a window. */
+typedef struct dm2_window {
+    const int32_t* patch_min;     /* (B,2) int32 (x, y) per view, DEVICE memory; NULL = zeros */
+    int32_t full_W, full_H;       /* the frame the cameras' rays and verts_image belong to (Renderer.width/height) */
+} dm2_window;
+
+/* dm2_layers_plan / dm2_layers_run for a window: the faces are binned into the window's tiles (bbox of verts_image against
+ * tiles anchored at patch_min), the first-hit pass and the tet walks run over the window's pixels with the window's rays. */
+int dm2_layers_plan_window(const dm2_layers_desc* d, const dm2_window* win, void* face_scratch, size_t face_bytes,
+                           void* stream, int64_t* num_rendered, int64_t* max_tile_entries);
+int dm2_layers_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                          void* face_scratch, size_t face_bytes,
+                          void* binning_scratch, size_t binning_bytes,
+                          void* image_scratch, size_t image_bytes,
+                          void* tet_scratch, size_t tet_bytes,
+                          int32_t* render_layers, int32_t* render_layers_cnt, void* stream);
 
 /* Renderer.rasterize: the first L faces each pixel's ray hits, on any triangle mesh (no tetrahedra), with barycentrics and
  * ray parameter.  Plan with dm2_layers_plan (T = 0; tets, face_tets, tet_faces unused and may be NULL) and size the face /
@@ -301,6 +327,20 @@ int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t ma
  * or through which faces are listed.  Float atomics: the last bits may vary from run to run. */
 int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                            float* dL_dverts, void* stream);
+/* dm2_rasterize_run / dm2_rasterize_backward for a window (plan with dm2_layers_plan_window): every array is (B,H,W,...) of
+ * the window.  The candidates of a window pixel are the faces whose image bbox touches the pixel's 16 x 16 WINDOW tile (the
+ * grid anchored at patch_min) and that the depth cull keeps; the hit rule, the (t, f) order, the early exit and the -1 of
+ * empty slots are dm2_rasterize_run's, word for word, at the frame pixel's ray.  A face that reaches a pixel through its bbox
+ * alone can therefore be a candidate under one grid and not under another: a window and the crop of the full frame agree
+ * wherever the tiles coincide (origin a multiple of 16) and may differ only in hits whose bbox misses one of the two tiles.
+ * The backward intersects again with the window's rays. */
+int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                             void* face_scratch, size_t face_bytes,
+                             void* binning_scratch, size_t binning_bytes,
+                             void* image_scratch, size_t image_bytes,
+                             int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream);
+int dm2_rasterize_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
+                                  const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream);
 
 /* Renderer.interpolate: attribute images from face ids and barycentrics per slot (dm2_rasterize_run's, dm2_layers_run's or
  * hand-built).  render_layers (B,H,W,L) int32, bary (B,H,W,L,3) float32, attr (N,C) float32 shared by the views
@@ -411,6 +451,16 @@ int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t 
 int dm2_coverage_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
                           const int32_t* render_layers, const float* verts_image, const int32_t* faces, const float* dL_dcov,
                           float* dL_dverts_image, void* stream);
+/* dm2_coverage / dm2_coverage_backward for a window: render_layers, out_cov and dL_dcov are (B,H,W,L) of the window, and the
+ * pixel of slot (b, y, x, l) is [x + pmx, x + pmx + 1] x [y + pmy, y + pmy + 1] with (pmx, pmy) = patch_min[b]; verts_image
+ * stays in frame units.  Per-pixel: the result is the crop of the full-frame call on layers embedded in a frame of -1.  Only
+ * win->patch_min is read (full_W, full_H are not needed). */
+int dm2_coverage_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                        const dm2_window* win, const int32_t* render_layers, const float* verts_image, const int32_t* faces,
+                        float* out_cov, void* stream);
+int dm2_coverage_backward_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                                 const dm2_window* win, const int32_t* render_layers, const float* verts_image,
+                                 const int32_t* faces, const float* dL_dcov, float* dL_dverts_image, void* stream);
 
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
@@ -427,7 +477,7 @@ int dm2_coverage_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P,
  * point-sampled Renderer forward. */
 typedef struct dm2_layer_composite_desc {
     int32_t B, P, F;
-    int32_t W, H, L;              /* full frame width/height, layers per pixel */
+    int32_t W, H, L;              /* full frame (with a dm2_window: the window's) width/height, layers per pixel */
     int32_t flags;                /* DM2_FLAG_ANALYTIC_RAYS */
     const int32_t* render_layers; /* (B,H,W,L) */
     const float* verts;           /* (P,3) */
@@ -462,6 +512,16 @@ int dm2_layers_composite_backward_alpha(const dm2_layer_composite_desc* d, const
                                         const float* dL_dout_depth, const float* dL_dout_alpha,
                                         const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
                                         float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
+/* dm2_layers_composite_weights / dm2_layers_composite_backward_alpha for a window: d->W, d->H and every (B,H,W,...) array are
+ * the window's; a window pixel's ray is its frame pixel's (the window's cut of the ray tensors, or DM2_FLAG_ANALYTIC_RAYS at
+ * the absolute pixel with full_W, full_H -- the only place the origin is used).  out_face_weights and dL_dout_alpha may be
+ * NULL as there.  Per-pixel: the crop of the full-frame call on layers embedded in a frame of -1. */
+int dm2_layers_composite_window(const dm2_layer_composite_desc* d, const dm2_window* win, float* out_color, float* out_depth,
+                                float* out_final_T, int32_t* out_n_contrib, float* out_face_weights, void* stream);
+int dm2_layers_composite_backward_window(const dm2_layer_composite_desc* d, const dm2_window* win, const float* dL_dout_color,
+                                         const float* dL_dout_depth, const float* dL_dout_alpha,
+                                         const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
+                                         float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
 
 /* Host prep of Renderer.forward / LayeredRenderer.generate, fused.
  * Replaces the ~20 torch kernels of the reference's Python host layer:
