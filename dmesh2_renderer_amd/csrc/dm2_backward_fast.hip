@@ -21,9 +21,10 @@
 //   start marks and a running maximum, then
 //   B2  lane s: its (face, pixel) from the masks, its coverage; Moeller-Trumbore, clamp, alpha, interpolated colour /
 //       depth -> record in LDS
-//   C   pixel p: replay its records back to front (backward.cu:340-405)
-//   D   lane s: chain rule (backward.cu:408-488) incl. the AA Jacobian, DPP pre-reduction over the lanes of one face,
-//       ds_add_f32
+//   C   pixel p: replay its records back to front -- the recurrence only (the running T and the accumulated colour / depth
+//       behind a pair, backward.cu:340-372): a wave runs it until its busiest pixel is through, so nothing else lives there
+//   D   lane s: dL/dalpha from what C left in its record and the pixel's loss gradients (backward.cu:350-405), chain rule
+//       (backward.cu:408-488) incl. the AA Jacobian, DPP pre-reduction over the lanes of one face, ds_add_f32
 //   flush with (entry,component) global atomics.
 //
 // ALPHA (the second template parameter; dm2_backward_alpha with a non-null dL/d(alpha image)): the alpha image 1 - T_final
@@ -98,6 +99,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     constexpr int REC_CHUNKS = BfTraits<COV>::PARTS;
     constexpr int REC_PER_INSTR = 64 / REC_CHUNKS;              // records one wave instruction copies
     static_assert(8 * REC_PER_INSTR >= BM_CAND, "two LDS-direct instructions per wave fetch a chunk");
+    static_assert(BM_CAND <= 32, "s_mask: one bit of a 32-bit word per candidate entry");
 
     __shared__ Rec recs2[2][BM_CAND];                          // [buffer]: this chunk's candidates / the next chunk's
     __shared__ float acc[BM_CAND * BM_ACC];
@@ -108,9 +110,9 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     __shared__ uint16_t s_efirst[4][BM_CAND];                       // [wave][face]: the chunk's pairs in front of the face -- written and read by that wave
     __shared__ uint32_t s_hb2[2][BM_CAND];                     // [buffer][face]: pool slot of the entry's first blended pair
     __shared__ uint32_t s_mark[4][64];                         // [wave][pair lane]: (slot + 1) << 9 | first pair of the slot, where a slot starts
-    __shared__ unsigned long long s_mask[TILE_PIX];            // per pixel: faces of the chunk with a record for it
+    __shared__ uint32_t s_mask[TILE_PIX];                      // per pixel: faces of the chunk with a record for it
     __shared__ uint32_t s_ids2[2][64];                         // [buffer]: face ids of the walk positions [base, base + 64): one wave-wide request
-    __shared__ float s_pixc[6][TILE_PIX];                      // per pixel, read by phase C only: dL/dcolour, dL/ddepth, final T, T in front of the last contributor
+    __shared__ float s_pixc[6][TILE_PIX];                      // per pixel, read by phase D only: dL/dcolour, dL/ddepth, final T, T in front of the last contributor
     __shared__ float* s_fl_base[32];                           // flush, per component: destination of id 0 ...
     __shared__ int s_fl_sel[32];                               // ... which id of the record (face_id, vid[0..2]) | dwords per id << 2
 
@@ -167,7 +169,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         dLd = dL_ddepth[pix];
         if constexpr (ALPHA) dLa = dL_dalpha[pix];
     }
-    // phase C is their only reader: parked in LDS, not in six registers that would be live across B2 and D
+    // phase D is their only reader, through the pair's pixel: parked in LDS, not in six registers live across the chunk loop
     s_pixc[0][tid] = dLc0; s_pixc[1][tid] = dLc1; s_pixc[2][tid] = dLc2; s_pixc[3][tid] = dLd;
     if constexpr (ALPHA) {                                         // (file header: T_final K, prev_T_final K)
         float bg_dot = 0.f;
@@ -318,11 +320,14 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 out.depth = i0 * fc.dep[0] + i1 * fc.dep[1] + i2 * fc.dep[2];
                 alpha = fc.opacity * ratio;
                 out.alpha = alpha;
-                out.flags = MB_BLEND;
+                // (1 / (1 - alpha) once, to <= 1 ulp, for phase C's running T: the gradients owe the reference 1e-5, not the
+                // bits of its IEEE division.  A function of the pair alone, so it is taken here, with every lane busy; the
+                // word is phase C's to overwrite with the flags)
+                out.flags = __float_as_uint(rcp_refined(1.f - alpha));
                 blend = true;
             }
             s_pair[tid] = out;
-            if (blend) atomicOr(&s_mask[q], 1ull << j);
+            if (blend) atomicOr(&s_mask[q], 1u << j);
         }
         STAMP(5)
         __syncthreads();
@@ -337,57 +342,33 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
 
         // ---- phase C: per-pixel back-to-front replay ------------------------------------------
         {
-            unsigned long long m = s_mask[tid];
+            uint32_t m = s_mask[tid];
             s_mask[tid] = 0;
-            float dLc0 = 0.f, dLc1 = 0.f, dLc2 = 0.f, dLd = 0.f, T_final = 0.f, prev_T_final = 0.f;
-            if (m) {
-                dLc0 = s_pixc[0][tid]; dLc1 = s_pixc[1][tid]; dLc2 = s_pixc[2][tid]; dLd = s_pixc[3][tid];
-                T_final = s_pixc[4][tid]; prev_T_final = s_pixc[5][tid];
-            }
+            // Only what one record owes the next stays in this loop (a wave runs it until its busiest pixel is through, most
+            // lanes idle): the running T and the four accumulators.  The record leaves as (colour, depth) minus what the pixel
+            // accumulated behind it, and the T in front of it; its own lane makes dL/dalpha of them at the head of phase D.
             while (m) {                                                           // ascending face = back to front
-                const int jj = __ffsll((long long)m) - 1;
+                const int jj = __ffs((int)m) - 1;
                 m &= m - 1;
                 const uint32_t e = (uint32_t)(total - 1 - base - jj);            // 0-based position in the list
-                if (e >= last_contributor) continue;                              // backward.cu:219-221
                 // slot of (face jj, this pixel): hits before (jj, this wave) + hits of lower pixels of this wave
                 const int t = jj * 4 + wid;
                 BfPair& pr = s_pair[(int)s_wbase[wid][jj] + __popcll(s_hit[t] & ((1ull << lane) - 1ull))];
+                // backward.cu:219-221.  (The forward set the mask bit in its B2 without knowing that the pixel had terminated
+                // in front of the entry; the word still holds B2's float: inactive for phase D)
+                if (e >= last_contributor) { pr.flags = 0; continue; }
                 const float a = pr.alpha, iC0 = pr.c0, iC1 = pr.c1, iC2 = pr.c2, iD = pr.depth;
-                // alpha == 1 exactly (backward.cu:396) is the forward's decision too: only a pixel's LAST contributor can
-                // have it (T drops to 0 and the pixel is done), and then final_T is exactly 0
-                const bool alpha_is_one = (a == 1.0f) || (T_first_pass && T_final == 0.0f);
-                // (1 / (1 - alpha) once, to <= 1 ulp, for the running T and for the background term: the gradients owe the
-                // reference 1e-5, not the bits of its two IEEE divisions)
-                const float inv_1ma = rcp_refined(1.f - a);
+                const float inv_1ma = __uint_as_float(pr.flags);                  // B2: rcp_refined(1 - a)
                 if (!T_first_pass) T = T * inv_1ma;                               // backward.cu:340-348
-                T_first_pass = false;
-                float dL_dalpha = 0.0f;
                 accum_rec0 = last_alpha * last_c0 + (1.f - last_alpha) * accum_rec0; last_c0 = iC0;
-                dL_dalpha += (iC0 - accum_rec0) * dLc0;
                 accum_rec1 = last_alpha * last_c1 + (1.f - last_alpha) * accum_rec1; last_c1 = iC1;
-                dL_dalpha += (iC1 - accum_rec1) * dLc1;
                 accum_rec2 = last_alpha * last_c2 + (1.f - last_alpha) * accum_rec2; last_c2 = iC2;
-                dL_dalpha += (iC2 - accum_rec2) * dLc2;
                 accum_recd = last_alpha * last_depth + (1.f - last_alpha) * accum_recd; last_depth = iD;
-                dL_dalpha += (iD - accum_recd) * dLd;
-                dL_dalpha *= T;
                 last_alpha = a;
-                if constexpr (ALPHA) {                                            // T_final, prev_T_final: times K
-                    if (alpha_is_one) dL_dalpha += -prev_T_final;
-                    else dL_dalpha += (-T_final) * inv_1ma;
-                } else {
-                    float bg_dot = 0.f;
-                    bg_dot += bg0 * dLc0; bg_dot += bg1 * dLc1; bg_dot += bg2 * dLc2;
-                    const float bd_dot = (float)(0.0 + 1.0 * (double)dLd);        // backward.cu:394
-                    if (alpha_is_one) {
-                        dL_dalpha += (-prev_T_final) * bg_dot;
-                        dL_dalpha += (-prev_T_final) * bd_dot;
-                    } else {
-                        dL_dalpha += (-T_final * inv_1ma) * bg_dot;
-                        dL_dalpha += (-T_final * inv_1ma) * bd_dot;
-                    }
-                }
-                pr.depth = T; pr.alpha = dL_dalpha; pr.flags = MB_BLEND | MB_ACTIVE;   // (phase D: T, dL/dalpha in place of depth, alpha)
+                pr.c0 = iC0 - accum_rec0; pr.c1 = iC1 - accum_rec1; pr.c2 = iC2 - accum_rec2; pr.depth = iD - accum_recd;
+                pr.alpha = T;
+                pr.flags = MB_BLEND | MB_ACTIVE | (T_first_pass ? MB_FIRST : 0u);
+                T_first_pass = false;
             }
         }
         STAMP(7)
@@ -406,9 +387,45 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             const bool s4 = (l16 >= 4) & (k4 == jkey);
             const bool s8 = (l16 >= 8) & (k8 == jkey);
             const float m1 = s1 ? 1.f : 0.f, m2 = s2 ? 1.f : 0.f, m4 = s4 ? 1.f : 0.f, m8 = s8 ? 1.f : 0.f;
-            uint32_t pflags = 0; float pr_T = 0.f, pr_dL_dalpha = 0.f;
-            if (have && blend) { const BfPair& pr = s_pair[tid]; pflags = pr.flags; pr_T = pr.depth; pr_dL_dalpha = pr.alpha; }
+            // the head: what phase C left in the pair's record (dm2_bwd_shared.h) and the pixel's rows -> dL/dalpha, with the
+            // reference's operations in its order (backward.cu:350-405)
+            uint32_t pflags = 0;
+            if (have && blend) pflags = s_pair[tid].flags;
             const bool active = (pflags & MB_ACTIVE) != 0;
+            float pr_T = 0.f, pr_dL_dalpha = 0.f;
+            float qc0 = 0.f, qc1 = 0.f, qc2 = 0.f, qd = 0.f;                        // dL/dcolour, dL/ddepth of the pixel
+            if (active) {
+                const BfPair& pr = s_pair[tid];
+                qc0 = s_pixc[0][q]; qc1 = s_pixc[1][q]; qc2 = s_pixc[2][q]; qd = s_pixc[3][q];
+                const float T_final = s_pixc[4][q], prev_T_final = s_pixc[5][q];   // (ALPHA: times K, file header)
+                pr_T = pr.alpha;
+                // alpha == 1 exactly (backward.cu:396) is the forward's decision too: only a pixel's LAST contributor can
+                // have it (T drops to 0 and the pixel is done), and then final_T is exactly 0
+                const bool alpha_is_one = (alpha == 1.0f) || ((pflags & MB_FIRST) != 0 && T_final == 0.0f);
+                const float inv_1ma = rcp_refined(1.f - alpha);                     // (B2's value again: the same function of the same register)
+                float dL_dalpha = 0.0f;
+                dL_dalpha += pr.c0 * qc0;
+                dL_dalpha += pr.c1 * qc1;
+                dL_dalpha += pr.c2 * qc2;
+                dL_dalpha += pr.depth * qd;
+                dL_dalpha *= pr_T;
+                if constexpr (ALPHA) {
+                    if (alpha_is_one) dL_dalpha += -prev_T_final;
+                    else dL_dalpha += (-T_final) * inv_1ma;
+                } else {
+                    float bg_dot = 0.f;
+                    bg_dot += bg0 * qc0; bg_dot += bg1 * qc1; bg_dot += bg2 * qc2;
+                    const float bd_dot = (float)(0.0 + 1.0 * (double)qd);          // backward.cu:394
+                    if (alpha_is_one) {
+                        dL_dalpha += (-prev_T_final) * bg_dot;
+                        dL_dalpha += (-prev_T_final) * bd_dot;
+                    } else {
+                        dL_dalpha += (-T_final * inv_1ma) * bg_dot;
+                        dL_dalpha += (-T_final * inv_1ma) * bd_dot;
+                    }
+                }
+                pr_dL_dalpha = dL_dalpha;
+            }
             float nact = active ? 1.f : 0.f;
             seg_scan16(nact, s1, s2, s4, s8);
             const bool emit = ((l16 == 15) | (kn != jkey)) & (jkey >= 0) & (nact > 0.f);
@@ -421,7 +438,6 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 for (int c = 0; c < 14; c++) g1[c] = 0.f;
                 if (active) {
                     const float Tq = pr_T, dL_dalpha = pr_dL_dalpha;
-                    const float qc0 = s_pixc[0][q], qc1 = s_pixc[1][q], qc2 = s_pixc[2][q], qd = s_pixc[3][q];   // dL/dcolour, dL/ddepth of the pixel
                     const float intense = k_int, opacity = k_opa;
                     const float* const colD = k_col; const float* const depD = k_dep;
                     const float dics[3] = {qc0 * alpha * Tq, qc1 * alpha * Tq, qc2 * alpha * Tq};

@@ -12,10 +12,15 @@ namespace dm2 {
 constexpr int BM_ACC = DM2_BM_ACC;       // pitch of an accumulator row (dwords)
 // accumulator row of one list entry: d/dverts (9), d/dverts_color (9), d/dndc.z (3), d/dopacity, d/dintense, d/daa (6); flag
 constexpr int M_DV = 0, M_DC = 9, M_DZ = 18, M_OP = 21, M_IN = 22, M_AA = 23, M_N = 29, M_FLAG = 31;
-constexpr uint32_t MB_BLEND = 1u, MB_ACTIVE = 2u;
+constexpr uint32_t MB_BLEND = 1u, MB_ACTIVE = 2u, MB_FIRST = 4u;   // MB_FIRST: the first record its pixel replayed (its last contributor)
 
-// dm2_backward_fast.hip: phase B2 leaves (alpha, colour, depth), phase C replaces alpha by dL/dalpha and depth by the T in
-// front of the pair and sets the flags; phase D reads the pixel's loss gradients from the per-pixel LDS rows itself
+// dm2_backward_fast.hip, the life of a pair's record inside one chunk:
+//   B2  (alpha, colour, depth) of the pair; flags = the BITS of the float 1 / (1 - alpha) (0 for a pair that does not blend)
+//   C   the pixel that owns the record replays it: (c0, c1, c2, depth) <- (colour, depth) - what the pixel accumulated behind
+//       the pair, alpha <- the T in front of the pair, flags <- MB_BLEND | MB_ACTIVE | MB_FIRST?.  A record behind the pixel's
+//       last contributor is not replayed: flags <- 0, so that phase D never tests a bit of a float
+//   D   the pair's own lane (its alpha still in a register) turns the differences, T and the pixel's loss gradients (per-pixel
+//       LDS rows) into dL/dalpha and runs the chain rule
 struct __attribute__((aligned(8))) BfPair { float alpha, c0, c1, c2, depth; uint32_t flags; };
 static_assert(sizeof(BfPair) == 24, "BfPair");
 
