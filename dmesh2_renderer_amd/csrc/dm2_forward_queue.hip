@@ -8,6 +8,7 @@
 //       About a third of the rectangle pairs are rejected here; the survivors are
 //       compacted, in pair order, into an LDS queue (wave ballot + prefix count, every
 //       wave owns a contiguous quarter of the chunk's pairs so the order is global).
+//       A pair's face comes from start marks and a running maximum over the wave (dm2_pairs.h), as in the backward.
 //   B2  one SURVIVOR per lane: polygon clip, Moeller-Trumbore, barycentric clamp, coverage
 //       mix, interpolated colour / depth -> pair record in LDS.  All lanes carry work.
 //   C   every pixel blends its own records in list order (64-bit face mask per pixel).
@@ -76,13 +77,17 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                        uint32_t* __restrict__ hit_base, float* __restrict__ face_weights STAMP_PARAM) {
     __shared__ FaceRec recs[FQ_CHUNK];                   // this chunk's faces; refilled (LDS-direct) behind phase B2, its last reader
     __shared__ uint32_t s_ids[64];                       // face ids of the NEXT chunk's list entries
-    __shared__ FqPair s_pair[FQ_SURVCAP];
+    __shared__ __attribute__((aligned(16))) FqPair s_pair[FQ_SURVCAP];
+    // Start marks of phase B1's pair decode (pair_face_from_marks, dm2_pairs.h), one byte per pair slot, in s_pair's first
+    // bytes: s_pair is written in B2 and last read in phase C, so it is dead from the loop-top barrier to the one behind B1.
+    uint8_t* const s_mark = reinterpret_cast<uint8_t*>(s_pair);
+    static_assert(4 * FQ_QCAP <= (int)sizeof(FqPair) * FQ_SURVCAP && (4 * FQ_QCAP) % 16 == 0 && 4 * FQ_QCAP <= 64 * 16 && FQ_CHUNK < 255,
+                  "B1 reads a mark for every lane of its rounds; one wave clears them with one 16-byte store per lane");
     __shared__ float s_ray[TILE_PIX * 6];
     __shared__ int s_off[FQ_CHUNK + 1];
     __shared__ uint32_t s_rect[FQ_CHUNK];
     __shared__ int s_kb[FQ_CHUNK];                       // pair index of the face's (virtual) tile pixel (0,0): off - y0*w - x0
     __shared__ int s_wtot[4];                            // survivors per wave
-    __shared__ int s_inv[17];
     __shared__ uint16_t s_slot[FQ_PAIRCAP];              // per pair: survivors before it within its wave's range
     __shared__ uint32_t s_queue[4 * FQ_QCAP];            // survivors: q | face << 8 | corner mask << 14
     __shared__ unsigned long long s_mask[TILE_PIX];      // per pixel: faces of the chunk that left a record for it
@@ -103,7 +108,6 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     const int tile_y = (int)(tyx / gx), tile_x = (int)(tyx - (uint32_t)tile_y * gx);
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     STAMP_DECL
-    fill_inv_table(s_inv);
     s_mask[tid] = 0;
     if constexpr (WEIGHTS) { if (tid < FQ_CHUNK) s_w[tid] = 0.f; }
     if (hit_valid && blockIdx.x == 0 && tid == 0) hit_valid[0] = pool ? 3u : 2u;   // AA blend masks (+ the pair pool) are current
@@ -183,16 +187,20 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         if (tid < n) {
             uint32_t rect;
             cnt = face_pixel_rect(recs[tid].aa.bb, use_aa, X0a, Y0a, xlim, ylim, rect);
-            s_rect[tid] = rect;
+            s_rect[tid] = rect_with_inv(rect);
         }
         if (tid < FQ_CHUNK * 4) s_bmask[tid] = 0;
         if (tid < FQ_SURVCAP / 64) s_blend[tid] = 0;
         STAMP(2)
         if (wid == 0) {                                             // a chunk is at most 64 faces: all staging lanes are in wave 0
+            if (lane < 4 * FQ_QCAP / 16) reinterpret_cast<uint4*>(s_mark)[lane] = make_uint4(0u, 0u, 0u, 0u);
             const int inc = wave_inclusive_scan(cnt);
             if (tid < n) {
                 const int ex = inc - cnt;
                 s_off[tid] = ex;
+                // the face's start mark, behind this wave's own clear (LDS keeps a wave's order); a face without pairs shares
+                // its successor's offset and writes nothing; the barrier below publishes the marks
+                if (cnt > 0 && ex < FQ_PAIRCAP) s_mark[ex] = (uint8_t)(tid + 1);
                 const uint32_t r = s_rect[tid];
                 s_kb[tid] = ex - (int)((r >> 4) & 15u) * ((int)((r >> 8) & 15u) + 1) - (int)(r & 15u);
             }
@@ -213,14 +221,15 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         // planes, aa.h:493-496: area = pixel area, no clip) from its back -- phase B2 then runs whole waves of one class and the
         // waves of the second class skip the clipper altogether.  An entry carries its record index within the wave.
         int wcount = 0, wfull = 0;
+        uint32_t mcarry = pair_face_seed(s_off, n, wid * Q);       // the face that holds the wave's first pair (+ 1)
         for (int r = 0; r < Q; r += 64) {
-            const int k = wid * Q + r + lane;
+            const int k = wid * Q + r + lane;                       // < 4 * FQ_QCAP: inside the cleared marks
             bool surv = false, full = false;
             uint32_t entry = 0;
+            const int j = pair_face_from_marks(s_mark[k], mcarry);  // == find_face(s_off, n, k) for k < tot
             if (k < tot) {
-                const int j = find_face(s_off, n, k);
                 int qx, qy;
-                pair_xy(s_rect[j], k - s_off[j], s_inv, qx, qy);
+                pair_xy(s_rect[j], k - s_off[j], qx, qy);
                 uint32_t cmask = 0xF;
                 surv = true;
                 if (use_aa) {
@@ -252,7 +261,7 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         int wc1 = 0, wc2 = 0, wc3 = 0, SC = 0;                      // clip class: prefix over the waves
         if (CLASSES) { wc1 = s_wtotc[0]; wc2 = wc1 + s_wtotc[1]; wc3 = wc2 + s_wtotc[2]; SC = wc3 + s_wtotc[3]; }
         const int wf1 = wb1 - wc1, wf2 = wb2 - wc2, wf3 = wb3 - wc3;                                          // fully covered class
-        // global survivor prefix at pair k (k <= tot)
+        // global survivor prefix at pair k (k <= tot), for the wave-uniform cut below
         auto surv_before = [&](int k) -> int {
             if (k >= tot) return S;
             const int w = (k >= Q) + (k >= 2 * Q) + (k >= 3 * Q);
@@ -300,13 +309,14 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 const bool isc = t < SC;
                 const int tc = isc ? t : t - SC;
                 const int b1 = isc ? wc1 : wf1, b2 = isc ? wc2 : wf2, b3 = isc ? wc3 : wf3;
-                const int w = (tc >= b1) + (tc >= b2) + (tc >= b3);
-                const int within = tc - (w == 0 ? 0 : (w == 1 ? b1 : (w == 2 ? b2 : b3)));
+                const bool g1 = tc >= b1, g2 = tc >= b2, g3 = tc >= b3;     // (b1 <= b2 <= b3: the selects below are a prefix code)
+                const int w = (int)g1 + (int)g2 + (int)g3;
+                const int within = tc - (g3 ? b3 : (g2 ? b2 : (g1 ? b1 : 0)));
                 if (t < ST) entry = s_queue[w * FQ_QCAP + (isc ? within : FQ_QCAP - 1 - within)];
-                s = (w == 0 ? 0 : (w == 1 ? wb1 : (w == 2 ? wb2 : wb3))) + (int)((entry >> 18) & 255u);      // the survivor's record
+                s = (g3 ? wb3 : (g2 ? wb2 : (g1 ? wb1 : 0))) + (int)((entry >> 18) & 255u);                  // the survivor's record
             } else if (t < ST) {
-                const int w = (s >= wb1) + (s >= wb2) + (s >= wb3);
-                entry = s_queue[w * FQ_QCAP + (s - (w == 0 ? 0 : (w == 1 ? wb1 : (w == 2 ? wb2 : wb3))))];
+                const bool g1 = s >= wb1, g2 = s >= wb2, g3 = s >= wb3;     // (wb1 <= wb2 <= wb3)
+                entry = s_queue[((int)g1 + (int)g2 + (int)g3) * FQ_QCAP + (s - (g3 ? wb3 : (g2 ? wb2 : (g1 ? wb1 : 0))))];
             }
             bool blend_s = false;
             if (t < ST && s < S) {
@@ -414,18 +424,22 @@ k_render_forward_queue(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 const int j = __ffsll((long long)m) - 1;
                 m &= m - 1;
                 // a mask bit is only set by a record for this pixel, so its pair index follows from the row pitch
+                // (k < tot: its wave's base is a prefix code of selects on the wave-uniform bases, next to the slot's read; an
+                // LDS table of the four bases measured 0.6 % slower; then the whole record in one go)
                 const int k = s_kb[j] + ly * ((int)((s_rect[j] >> 8) & 15u) + 1) + lx;
-                const FqPair pr = s_pair[surv_before(k)];
-                if ((pr.flags & QF_REC) && rec_cnt < K) rec_cnt++;           // forward.cu:344-352
-                if (!(pr.flags & QF_BLEND)) continue;
+                const FqPair pr = s_pair[(k >= 3 * Q ? wb3 : (k >= 2 * Q ? wb2 : (k >= Q ? wb1 : 0))) + (int)s_slot[k]];
+                asm volatile("" ::: "memory");                             // the whole record is read here: no load sinks under a mask of its own
+                // straight-line: a record that does not blend leaves every accumulator as it is through the selects
+                const bool bl = (pr.flags & QF_BLEND) != 0u;
+                rec_cnt += (int)(((pr.flags & QF_REC) != 0u) & (rec_cnt < K));       // forward.cu:344-352
                 const float alpha = pr.alpha;
                 const float test_T = T * (1 - alpha);
-                if constexpr (WEIGHTS) atomicAdd(&s_w[j], alpha * T);
-                C0 += pr.c0 * alpha * T; C1 += pr.c1 * alpha * T; C2 += pr.c2 * alpha * T;
-                D += pr.depth * alpha * T;
-                pT = T; T = test_T;
-                last_contributor = (uint32_t)(base + j + 1);
-                if (T < T_EPS) done = true;
+                if constexpr (WEIGHTS) { if (bl) atomicAdd(&s_w[j], alpha * T); }
+                C0 = bl ? C0 + pr.c0 * alpha * T : C0; C1 = bl ? C1 + pr.c1 * alpha * T : C1; C2 = bl ? C2 + pr.c2 * alpha * T : C2;
+                D = bl ? D + pr.depth * alpha * T : D;
+                pT = bl ? T : pT; T = bl ? test_T : T;
+                last_contributor = bl ? (uint32_t)(base + j + 1) : last_contributor;
+                done = bl & (test_T < T_EPS);
             }
         }
         STAMP(6)

@@ -37,6 +37,7 @@ __device__ __forceinline__ bool tile_of_block(uint32_t Tn, const uint32_t* __res
 }
 
 // rect packing: x0 | y0<<4 | (w-1)<<8 | (h-1)<<12 ; count==0 faces keep rect 0 and are never looked up
+// (the forward keeps the width's reciprocal in the upper half: rect_with_inv below)
 __device__ __forceinline__ uint32_t pack_rect(int x0, int y0, int w, int h) {
     return (uint32_t)x0 | ((uint32_t)y0 << 4) | ((uint32_t)(w - 1) << 8) | ((uint32_t)(h - 1) << 12);
 }
@@ -114,17 +115,35 @@ __device__ __forceinline__ int find_face_in(const int* off, int lo, int hi, int 
 }
 __device__ __forceinline__ int find_face(const int* off, int n, int k) { return find_face_in(off, 0, n, k); }
 
-// local pair index -> (dx, dy) inside a rectangle of width w <= 16 (local < 256)
-// inv_w[w] = ceil(65536 / w), w = 1..16 (LDS table filled by fill_inv_table)
-__device__ __forceinline__ void fill_inv_table(int* inv_w) {
-    if (threadIdx.x >= 1 && threadIdx.x <= 16) inv_w[threadIdx.x] = (65536 + (int)threadIdx.x - 1) / (int)threadIdx.x;
+// Face index of the pairs of one round of 64, without a search: the scan's owner stores j + 1 at mark[off[j]] for every
+// face j that owns a pair (marks are 0 elsewhere), and lane k takes the running maximum of the marks up to pair k.
+//   find_face returns the largest j with off[j] <= k.  A face without pairs shares its offset with the face behind it, so
+//   that j always owns a pair (off[j] <= k < off[j + 1]); it is the last face that starts at or in front of k, and its
+//   mark is the largest one at or in front of k because off ascends.  The running maximum of j + 1 is therefore the same j.
+// `carry` is the maximum in front of the round: the previous round's lane 63, or for a wave's first round the seed below.
+__device__ __forceinline__ int pair_face_from_marks(uint32_t mark, uint32_t& carry) {
+    const uint32_t mk = max(wave_inclusive_max(mark), carry);
+    carry = (uint32_t)__builtin_amdgcn_readlane((int)mk, 63);
+    return (int)mk - 1;
 }
-__device__ __forceinline__ void pair_xy(uint32_t rect, int local, const int* inv_w, int& lx, int& ly) {
-    const int w = (int)((rect >> 8) & 15u) + 1;
-    const int inv = inv_w[w];                      // (local * inv) >> 16 == floor(local / w) for local < 256, w <= 16
-    const int dy = (local * inv) >> 16;
-    lx = (int)(rect & 15u) + (local - dy * w);
-    ly = (int)((rect >> 4) & 15u) + dy;
+// Seed for the round that starts at pair k0 (wave-uniform): faces with off[j] <= k0, that is find_face(off, n, k0) + 1.
+__device__ __forceinline__ uint32_t pair_face_seed(const int* off, int n, int k0) {
+    const int lane = threadIdx.x & 63;
+    return (uint32_t)__popcll(__ballot(lane < n && off[lane] <= k0));
+}
+
+// local pair index -> (dx, dy) inside a rectangle of width w <= 16 (local < 256): the rect word carries ceil(8192 / w) in
+// its upper half, and (local * inv) >> 13 == floor(local / w) for local < 256, w <= 16 (tests/test_forward_decode_cpu.py
+// holds it exhaustively; ceil(65536 / w) would not fit 16 bits for w = 1)
+__device__ __forceinline__ uint32_t rect_with_inv(uint32_t rect) {
+    const uint32_t w = ((rect >> 8) & 15u) + 1u;
+    return rect | (((8192u + w - 1u) / w) << 16);
+}
+__device__ __forceinline__ void pair_xy(uint32_t rect_inv, int local, int& lx, int& ly) {
+    const int w = (int)((rect_inv >> 8) & 15u) + 1;
+    const int dy = (local * (int)(rect_inv >> 16)) >> 13;
+    lx = (int)(rect_inv & 15u) + (local - dy * w);
+    ly = (int)((rect_inv >> 4) & 15u) + dy;
 }
 
 // pair index of pixel (lx,ly) in face rect, or -1
