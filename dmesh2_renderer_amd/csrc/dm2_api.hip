@@ -880,6 +880,7 @@ int dm2_debug_fetch(int what, int64_t count, int64_t aux, int64_t num_rendered, 
         case 7: { auto s = dm2::LayerImageState::carve(base, count, aux); src = s.ranges; bytes = (size_t)aux * 8; break; }
         case 8: { auto s = dm2::FaceState::carve(base, count, 0, dm2::scan_temp_bytes(count), false); src = s.tiles_touched; bytes = (size_t)count * 4; break; }
         case 9: { auto s = dm2::BinningState::carve(base, num_rendered, dm2::sort_temp_bytes(num_rendered, aux)); src = s.hit_valid; bytes = 4 * 4; break; }
+        case 10: { auto s = dm2::BinningState::carve(base, num_rendered, dm2::sort_temp_bytes(num_rendered, aux)); src = s.hit_valid; bytes = 8 * 4; break; }
         default: return fail("dm2_debug_fetch: unknown item");
     }
     if (!scratch && bytes) return fail("dm2_debug_fetch: null scratch");

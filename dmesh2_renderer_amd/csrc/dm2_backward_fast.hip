@@ -115,6 +115,10 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
     __shared__ float s_pixc[6][TILE_PIX];                      // per pixel, read by phase D only: dL/dcolour, dL/ddepth, final T, T in front of the last contributor
     __shared__ float* s_fl_base[32];                           // flush, per component: destination of id 0 ...
     __shared__ int s_fl_sel[32];                               // ... which id of the record (face_id, vid[0..2]) | dwords per id << 2
+    // POOL only (the other instantiations never name them): the block's ties wait here for one trip to the global queue
+    constexpr uint32_t TIE_BUF = 64, TIE_DRAIN = 32;           // entries; buffered count from which the flush phase drains
+    __shared__ TieEntry s_tie[TIE_BUF];
+    __shared__ uint32_t s_tie_n;                               // places asked for since the last drain (may pass TIE_BUF)
 
     const uint32_t gx = (d.W + TILE - 1) / TILE, gy = (d.H + TILE - 1) / TILE;
     uint32_t tile;
@@ -214,6 +218,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         lds_prefetch_wait();
     }
     for (int k = tid; k < BM_CAND * BM_ACC; k += TILE_PIX) acc[k] = 0.f;     // the flush re-zeroes what it consumes
+    if constexpr (COV == POOL) { if (tid == 0) s_tie_n = 0u; }
     __syncthreads();                                                          // chunk 0's inputs and the zeroes are everyone's
 
     STAMP(0)
@@ -478,11 +483,17 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             }
             ISA_MARK(D_group2)
             // group 2: AA corners.  POOL: d(area)/d(corners) without a polygon (dm2_clip_fast.h); a pair it flags as a tie adds
-            // nothing here: it is queued with its dL/d(area) for the exact clipper (k_aa_ties below).  One atomic per wave with
-            // such a pair, its return value looked at behind group 3.  CLIP: B2's Jacobian.
+            // nothing here: it is queued with its dL/d(area) for the exact clipper (k_aa_ties below).  One LDS atomic per wave with
+            // such a pair takes its places in the block's buffer s_tie, its return value looked at behind group 3; the flush phase
+            // moves the buffer to the global queue with one global atomic per drain.  In the tile's last chunk nothing is left to
+            // hide a drain's atomic behind (a block that waits for it there ends that much later: +2 % of the kernel where every
+            // block is resident at once, 512 x 512): there a wave takes its places in the global queue itself, and a spare lane
+            // of wave 0 those of what the buffer still holds, both waited for behind group 3.  CLIP: B2's Jacobian.
             bool tie_push = false;
             uint32_t tie_base = 0;
             unsigned long long tie_bal = 0;
+            const bool last_chunk = base + n >= total;                           // (block-uniform)
+            int tie_first = -1;
             if constexpr (COV == CLIP) {
                 float g2[6];
 #pragma unroll
@@ -506,7 +517,14 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
 #pragma unroll
                 for (int c = 0; c < 6; c++) g2[c] = use ? dL_doarea * g2[c] : 0.0f;     // (a select: a tie's or an idle lane's entries need not be finite)
                 tie_bal = __ballot(tie_push);
-                if (tie_bal && lane == (int)(__ffsll((long long)tie_bal) - 1)) tie_base = atomicAdd(hit_valid + 2, (uint32_t)__popcll(tie_bal));
+                tie_first = tie_bal ? (int)(__ffsll((long long)tie_bal) - 1) : -1;
+                if (last_chunk) {
+                    if (lane == tie_first) tie_base = atomicAdd(hit_valid + 2, (uint32_t)__popcll(tie_bal));
+                    if (wid == 0) {
+                        const uint32_t held = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_tie_n);
+                        if (held != 0u && lane == (tie_first == 0 ? 1 : 0)) tie_base = atomicAdd(hit_valid + 2, min(held, TIE_BUF));
+                    }
+                } else if (lane == tie_first) tie_base = atomicAdd(&s_tie_n, (uint32_t)__popcll(tie_bal));
                 seg_scan16_safe(g2, m1, m2, m4, m8, s1, s2, s4, s8);
                 if (emit) {
 #pragma unroll
@@ -535,17 +553,57 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                     for (int c = 0; c < 9; c++) atomicAdd(arow + M_DV + c, g3[c]);
                 }
             }
+            if constexpr (COV == POOL) {
+                if (last_chunk && wid == 0) {                                    // what the buffer still holds (fewer than TIE_DRAIN entries)
+                    const uint32_t held = min((uint32_t)__builtin_amdgcn_readfirstlane((int)s_tie_n), TIE_BUF);
+                    if (held != 0u) {
+                        const uint32_t hb = (uint32_t)__shfl((int)tie_base, tie_first == 0 ? 1 : 0);
+                        if ((uint32_t)lane < held && hb + (uint32_t)lane < tie_cap) tie_queue[hb + (uint32_t)lane] = s_tie[lane];
+                    }
+                }
+            }
             if (tie_bal) {                                                       // (wave-uniform)
-                const uint32_t tb = (uint32_t)__shfl((int)tie_base, __ffsll((long long)tie_bal) - 1);
+                const uint32_t tb = (uint32_t)__shfl((int)tie_base, tie_first);
                 const uint32_t at = tb + __builtin_amdgcn_mbcnt_hi((uint32_t)(tie_bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tie_bal, 0u));
-                if (tie_push && at < tie_cap)
-                    tie_queue[at] = tie_pack((uint32_t)recs[j].face_id, (uint32_t)b, (uint32_t)(X0 + (q & 15)), (uint32_t)(Y0 + (q >> 4)), dL_doarea);
+                const TieEntry te = tie_pack((uint32_t)recs[j].face_id, (uint32_t)b, (uint32_t)(X0 + (q & 15)), (uint32_t)(Y0 + (q >> 4)), dL_doarea);
+                if (last_chunk) { if (tie_push && at < tie_cap) tie_queue[at] = te; }
+                else if (tie_push && at < TIE_BUF) s_tie[at] = te;
+                // the buffer is full (a chunk can hold 256 ties): the wave's other ties go to the queue directly, one global atomic
+                // for them, and are counted for the tests (hit_valid[6], k_aa_ties)
+                const bool direct = tie_push && !last_chunk && at >= TIE_BUF;
+                const unsigned long long dbal = __ballot(direct);
+                if (dbal) {                                                      // (wave-uniform)
+                    const int first = __ffsll((long long)dbal) - 1;
+                    uint32_t gb = 0;
+                    if (lane == first) { gb = atomicAdd(hit_valid + 2, (uint32_t)__popcll(dbal)); atomicAdd(hit_valid + 6, (uint32_t)__popcll(dbal)); }
+                    gb = (uint32_t)__shfl((int)gb, first);
+                    const uint32_t gat = gb + __builtin_amdgcn_mbcnt_hi((uint32_t)(dbal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dbal, 0u));
+                    if (direct && gat < tie_cap) tie_queue[gat] = te;
+                }
             }
         }
         STAMP(9)
         lds_prefetch_wait();                                        // the next chunk's records, masks and ids are in LDS ...
         __syncthreads();                                            // ... for every wave once all of them are here
         STAMP(10)
+
+        // ---- the buffered ties leave once half the buffer is in use (the tile's last chunk has emptied it in phase D): one wave,
+        // one global atomic, one contiguous run of 16-byte stores (a wave's ties stay adjacent: k_aa_ties reduces over runs of a
+        // face).  This chunk's pushes are in front of the barrier above; the reset is in front of the next chunk's by the barriers
+        // behind B2 and C.
+        if constexpr (COV == POOL) {
+            if (wid == 0 && base + n < total) {
+                const uint32_t cnt = min((uint32_t)__builtin_amdgcn_readfirstlane((int)s_tie_n), TIE_BUF);
+                if (cnt >= TIE_DRAIN) {
+                    uint32_t gb = 0;
+                    if (lane == 0) gb = atomicAdd(hit_valid + 2, cnt);
+                    gb = (uint32_t)__builtin_amdgcn_readfirstlane((int)gb);
+                    if ((uint32_t)lane < cnt && gb + (uint32_t)lane < tie_cap) tie_queue[gb + (uint32_t)lane] = s_tie[lane];
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");        // (the compiler keeps the reset behind the reads)
+                    if (lane == 0) s_tie_n = 0u;
+                }
+            }
+        }
 
         // ---- flush: lane = (entry, component); 8 entries per pass ------------------------------
         // Branch-free: every component's destination is  base + 4 (id * mult),  id one of the record's (face_id, vid[0..2]).
@@ -579,17 +637,26 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
 // fan order (tri_pix_overlap_area: its polygon also where that is not the geometric intersection, and its rounding where the
 // Jacobian is ill-conditioned -- bit-equal to the oracle, tests/test_gpu_clippers.py variant 0) times the pair's dL/d(area),
 // added to dL/d(aa_face_verts) -- or, under DM2_FLAG_AA_GRAD_TO_VERTS, to the image-space gradient of the vertex the corner
-// came from.  Grid-stride over the queue; the block that finishes last empties the queue for a second backward of the
-// same forward.
+// came from.  The adds leave one face per lane group: the wave's emitting lanes, compacted by ballot rank, park their three
+// destinations and six values in LDS, then lane = (emitter, component), 8 lanes per emitter with 6 active -- a face's 24
+// contiguous bytes are one memory-side request (two where they straddle a 64-B line) instead of six wave-instructions with
+// every lane in another row.  Grid-stride over the queue; the block that finishes last empties the queue for a second backward
+// of the same forward and leaves the tests two witnesses: counters[4] the queue length, counters[5] how many of the entries the
+// main kernel wrote round its LDS buffer.
 __global__ void __launch_bounds__(256)
 k_aa_ties(dm2_render_desc d, const uint4* __restrict__ face_recs, const TieEntry* __restrict__ queue, uint32_t cap,
           uint32_t* __restrict__ counters, float* __restrict__ dL_daa_face_verts, bool check_mode) {
     if (check_mode && counters[0] != 3u) return;
     const uint32_t n = min(counters[2], cap);
+    const uint32_t went_round = counters[6];                                     // (the main kernel is through: read here, not by the last block at its end)
     // the grid is sized for a full queue; the blocks behind the queue's end leave without a ticket (1024 tickets on one
     // address are serialised by the L2 in front of the working blocks' atomics: 8 us of a 0.2-ms step at cfg 1)
     const uint32_t working = min(gridDim.x, (n + blockDim.x - 1u) / blockDim.x);
+    if (working == 0u && blockIdx.x == 0u && threadIdx.x == 0u) { counters[4] = 0u; counters[5] = 0u; }   // (no block takes a ticket)
     if (blockIdx.x >= working) return;
+    __shared__ int64_t s_dst[4][64][3];                                          // [wave][emitter][corner]: element offset of the corner's x
+    __shared__ float s_val[4][64][6];
+    const uint32_t wv = threadIdx.x >> 6;
     const bool to_verts = (d.flags & DM2_FLAG_AA_GRAD_TO_VERTS) != 0;
     // (wave-uniform trip count: the lanes of a wave reduce over runs of equal faces with DPP before the atomics -- a face's ties
     // come from neighbouring lanes of one wave of the main kernel and sit next to each other in the queue)
@@ -626,29 +693,42 @@ k_aa_ties(dm2_render_desc d, const uint4* __restrict__ face_recs, const TieEntry
 #pragma unroll
         for (int c = 0; c < 6; c++) seg_scan16(g[c], s1, s2, s4, s8);
         const bool emit = valid & last;
-        if (!emit) continue;
-        if (to_verts) {
-            const uint4 ids = src[14];                                            // vid[0..2] are dwords 56..58 of the record
-            const int vid[3] = {(int)ids.x, (int)ids.y, (int)ids.z};
-            const uint32_t zm = src[4].z;                                         // zmask: dword 18
-            const bool flip = (zm >> 8) & 1u;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                const int v = vid[c == 0 ? 0 : (flip ? 3 - c : c)];
-                float* dstp = dL_daa_face_verts + ((int64_t)b * d.P + v) * 2;
-                atomicAdd(dstp, g[2 * c]); atomicAdd(dstp + 1, g[2 * c + 1]);
+        // (every lane reaches the shared stage.  The lanes of the wave talk through their rows of s_dst / s_val with no barrier
+        // in between: the fences keep the compiler from reordering across them, the hardware runs a wave's LDS operations in order)
+        const unsigned long long ebal = __ballot(emit);
+        const uint32_t ne = (uint32_t)__popcll(ebal);
+        if (emit) {
+            const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(ebal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ebal, 0u));
+            int64_t o0 = bf * 6, o1 = bf * 6 + 2, o2 = bf * 6 + 4;
+            if (to_verts) {
+                const uint4 ids = src[14];                                        // vid[0..2] are dwords 56..58 of the record
+                const uint32_t zm = src[4].z;                                     // zmask: dword 18
+                const bool flip = (zm >> 8) & 1u;
+                const int64_t vb = (int64_t)b * d.P;
+                o0 = (vb + (int)ids.x) * 2;
+                o1 = (vb + (int)(flip ? ids.z : ids.y)) * 2;
+                o2 = (vb + (int)(flip ? ids.y : ids.z)) * 2;
             }
-        } else {
-            float* dstp = dL_daa_face_verts + bf * 6;
+            s_dst[wv][r][0] = o0; s_dst[wv][r][1] = o1; s_dst[wv][r][2] = o2;
 #pragma unroll
-            for (int c = 0; c < 6; c++) atomicAdd(dstp + c, g[c]);
+            for (int c = 0; c < 6; c++) s_val[wv][r][c] = g[c];
         }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        const uint32_t comp = lane & 7u;
+        for (uint32_t e0 = 0; e0 < ne; e0 += 8u) {                                // (wave-uniform)
+            const uint32_t em = e0 + (lane >> 3);
+            if (em < ne && comp < 6u) atomicAdd(dL_daa_face_verts + s_dst[wv][em][comp >> 1] + (comp & 1u), s_val[wv][em][comp]);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
     __shared__ uint32_t s_ticket;
     __syncthreads();
     if (threadIdx.x == 0) s_ticket = atomicAdd(counters + 3, 1u);
     __syncthreads();
-    if (s_ticket == working - 1 && threadIdx.x == 0) { counters[2] = 0u; counters[3] = 0u; }
+    if (s_ticket == working - 1 && threadIdx.x == 0) {
+        counters[4] = n; counters[5] = went_round;
+        counters[2] = 0u; counters[3] = 0u; counters[6] = 0u;
+    }
 }
 
 // clip: the forward left masks but no pool (DM2_FWD_MASKS; aa_temperature > 0).  check_mode: the caller does not know what

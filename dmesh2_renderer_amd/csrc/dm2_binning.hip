@@ -525,7 +525,7 @@ k_tile_sort(int64_t Tn, uint32_t R, const uint32_t* __restrict__ tile_start, uin
     const int tid = threadIdx.x;
     const uint32_t s0 = tile_start[t], e0 = (t + 1 < Tn) ? tile_start[t + 1] : R;
     const int n = (int)(e0 - s0);
-    if (t == 0 && tid < 4) hit_valid[tid] = 0u;    // new lists: the blend masks of an earlier forward are stale; pool and tie queue empty
+    if (t == 0 && tid < 8) hit_valid[tid] = 0u;    // new lists: the blend masks of an earlier forward are stale; pool and tie queue empty
     if (tid == 0) ranges[t] = n ? make_uint2(s0, e0) : make_uint2(0u, 0u);
     if (n == 0) return;
     uint64_t* const seg = keys + s0;
@@ -614,8 +614,8 @@ k_emit_keys(int B, int F, uint32_t gx, uint32_t gy, const float* __restrict__ ke
 __global__ void __launch_bounds__(256)
 k_tile_ranges(int64_t L, const uint64_t* __restrict__ keys, uint2* __restrict__ ranges, uint32_t* __restrict__ hit_valid) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < 8) hit_valid[idx] = 0u;   // new lists: earlier masks are stale; pool and tie queue empty
     if (idx >= L) return;
-    if (idx == 0) { hit_valid[0] = 0u; hit_valid[1] = 0u; hit_valid[2] = 0u; hit_valid[3] = 0u; }   // new lists: earlier masks are stale; pool and tie queue empty
     const uint32_t cur = (uint32_t)(keys[idx] >> 32);
     if (idx == 0) ranges[cur].x = 0;
     else {

@@ -113,7 +113,9 @@ struct BinningState {
     // 0 nothing (stale), 1 point-sampled masks, 2 AA blend masks, 3 AA blend masks + the pair pool
     uint64_t* hit_masks;          // (4 R)
     uint32_t* hit_base;           // (R)  pair pool: slot of the entry's first blended pair (its pairs follow in (wave, pixel) order)
-    uint32_t* hit_valid;          // (4)  [0] mode  [1] pool slots handed out  [2] entries in the backward's tie queue
+    uint32_t* hit_valid;          // (8)  [0] mode  [1] pool slots handed out  [2] entries in the backward's tie queue  [3] k_aa_ties' block tickets
+                                  //      witnesses of the last tie pass (tests): [4] the queue length it saw  [5] how many of those entries
+                                  //      went round the block's LDS buffer;  [6] the running count behind [5]  [7] spare
     // pair pool (the tail of the buffer, whatever the caller appended to the fixed part): the coverage ratio
     // (forward.cu:375-378) of every blended (pixel, face) pair, so that the backward neither clips for an area nor depends
     // on reproducing it (dm2_backward_fast.hip)
@@ -123,7 +125,7 @@ struct BinningState {
         s.face_list = c.take<uint32_t>(R); s.keys = c.take<uint64_t>(R);
         s.keys_unsorted = c.take<uint64_t>(R); s.face_list_unsorted = c.take<uint32_t>(R);
         s.sort_temp = c.take<char>(sort_temp_bytes); s.sort_temp_bytes = sort_temp_bytes;
-        s.hit_masks = c.take<uint64_t>(4 * R); s.hit_base = c.take<uint32_t>(R); s.hit_valid = c.take<uint32_t>(4);
+        s.hit_masks = c.take<uint64_t>(4 * R); s.hit_base = c.take<uint32_t>(R); s.hit_valid = c.take<uint32_t>(8);
         const size_t fixed = c.used(base) + ALIGN;
         if (total) *total = fixed;
         s.pool = c.take<float>(0);

@@ -596,7 +596,9 @@ int dm2_exchange_unpack(int32_t B, int32_t P, int32_t F, int32_t N, int32_t rank
  * 1 face_list (num_rendered u32, from binning scratch), 2 final_T, 3 final_prev_T
  * (N f32), 4 n_contrib (N u32), 5 first_face, 6 first_tet (N i32, layer image scratch),
  * 8 tiles_touched (count = B*F u32, from face scratch; aux = the aux of dm2_scratch_bytes),
- * 9 hit_valid (4 u32 from binning scratch: [0] what the forward left, [1] pair-pool slots it claimed, [2] tie-queue entries). */
+ * 9 hit_valid (4 u32 from binning scratch: [0] what the forward left, [1] pair-pool slots it claimed, [2] tie-queue entries),
+ * 10 hit_valid, all 8 u32: behind the four of item 9, [4] the tie-queue length the last tie pass saw and [5] how many of those
+ * entries the backward wrote straight to the queue, round its per-block buffer (the destination of item 9 holds 4 words only). */
 int dm2_debug_fetch(int what, int64_t count, int64_t aux, int64_t num_rendered,
                     const void* scratch, size_t scratch_bytes, void* dst, void* stream);
 
