@@ -113,9 +113,25 @@ def backward(mod, fwd, dL_dcolor, dL_ddepth):
     """The reference's backward on its own forward's buffers -> the six gradients (numpy), in util.GRAD_NAMES order."""
     import torch
     o = fwd.out
-    g = mod.render_backward_cuda(o[0], *fwd.dargs, dL_dcolor, dL_ddepth, o[7], o[8], o[9], o[3], o[4], o[5], o[6])
+    g = mod.render_backward_cuda(o[0], *fwd.dargs, dL_dcolor, dL_ddepth, o[7], o[8], o[9], o[3], o[4], _with_slack(o[5]), o[6])
     torch.cuda.synchronize()
     return [x.cpu().numpy() for x in g]
+
+
+def _with_slack(tri_cnt):
+    """``tri_cnt`` (B, H, W) as a view of a larger allocation.  The reference's backward reads oarea_buffer_tri_cnt[b][y][x]
+    from EVERY thread of a 16 x 16 tile before it looks whether the thread has a pixel (backward.cu:156): where H or W is no
+    multiple of 16 the threads right of the patch read other pixels' counts and those below the last view's patch read up to
+    (H16 - H) * W + (W16 - W) entries past the end of the tensor.  The value is never used (such a thread is ``done``), so the
+    gradients are defined, but the load itself must stay inside memory the process owns: the view's storage has that many
+    zero entries behind it."""
+    import torch
+    B, H, W = tri_cnt.shape
+    n = B * H * W
+    slack = (-(-H // 16) * 16 - H) * W + (-(-W // 16) * 16 - W)
+    buf = torch.zeros(n + slack, dtype=tri_cnt.dtype, device=tri_cnt.device)
+    buf[:n] = tri_cnt.reshape(-1)
+    return buf[:n].view(B, H, W)
 
 
 def generate_layers(mod, dargs):
@@ -150,8 +166,78 @@ def races_in_binning(faces, verts_ndc, verts_image, patch_min, W, H):
     return dropped & ((hi - lo) > 0).all(-1)
 
 
+TILE_LIMIT = 2.0 ** 31 - 128.0            # the largest float32 below 2^31: up to it (and down to its negative) float -> int is defined
+
+
+def undefined_tile_rects(verts_ndc, verts_image, patch_min):
+    """None, or why the reference's binning defines nothing for these arguments.  Both of its kernels compute a face's tile
+    rectangle as (int)floorf((coordinate - patch_min) / 16) (auxiliary.h:75-82); the conversion is only defined for a finite
+    quotient inside int's range.  The depth key and the z test read verts_ndc z, which must be finite to order anything."""
+    ndc, img = np.asarray(verts_ndc, np.float32), np.asarray(verts_image, np.float32)
+    if not np.isfinite(ndc[..., 2]).all():
+        return "verts_ndc holds a non-finite z"
+    if not np.isfinite(img).all():
+        return "verts_image holds a non-finite coordinate"
+    with np.errstate(all="ignore"):
+        q = (img - np.asarray(patch_min, np.float32)[:, None, :]) / np.float32(16.0)
+    if img.size and float(np.abs(q).max()) > TILE_LIMIT:
+        return "a tile coordinate of verts_image lies outside int's range"
+    return None
+
+
 def _defined(faces, verts_ndc, verts_image, patch_min, W, H):
     t = [x.detach().cpu().numpy() if hasattr(x, "detach") else x for x in (faces, verts_ndc, verts_image, patch_min)]
+    why = undefined_tile_rects(t[1], t[2], t[3])
+    if why:
+        raise ValueError("the reference's binning is not defined here: " + why)
     n = int(races_in_binning(*t, W, H).sum())
     if n:
         raise ValueError(f"the reference's binning races over {n} faces of this scene (dropped by the z test, with a tile rectangle)")
+
+
+# ---- acceptance of gradients -----------------------------------------------------------------------------------------------
+def accept_gradients(ref, others, f64, tol):
+    """Hold ``others`` = {who: {tensor: array}} to the reference's gradients ``ref`` = {tensor: array}, tensor by tensor.
+
+    A tensor passes where every one of ``others`` lies within ``tol`` (relative L-inf of the tensor's maximum) of the reference.
+    The reference sums with float atomics in no fixed order, so where a tensor misses that, ``f64()`` -> {tensor: float64
+    array} is computed (once) and the REFERENCE is measured against it: if the reference itself lies farther than ``tol``
+    from float64, the bound becomes twice the reference's own distance (two independent fp32 summation orders may each be as
+    far off as the reference is) and everyone is measured against float64; if the reference is within ``tol`` of float64
+    there is no relief.  The widened bound never comes from ``others``.
+
+    -> (figures {tensor: dict(vs_ref {who: e}[, ref_vs_f64, bound, vs_f64 {who: e}])}, widened [tensor], failures [(tensor,
+    who, figure, bound)])."""
+    from util import rel_linf
+    figures, widened, failures = {}, [], []
+    g64 = None
+    for nm, r in ref.items():
+        d = {who: rel_linf(o[nm], r) for who, o in others.items()}
+        fig = figures[nm] = dict(vs_ref=d)
+        if max(d.values()) <= tol:
+            continue
+        if g64 is None:
+            g64 = f64()
+        e_ref = fig["ref_vs_f64"] = rel_linf(r, g64[nm])
+        if e_ref > tol:
+            bound = fig["bound"] = 2.0 * e_ref
+            e = fig["vs_f64"] = {who: rel_linf(o[nm], g64[nm]) for who, o in others.items()}
+            widened.append(nm)
+            failures += [(nm, who, v, bound) for who, v in e.items() if v > bound]
+        else:
+            failures += [(nm, who, v, tol) for who, v in d.items() if v > tol]
+    return figures, widened, failures
+
+
+def describe(figures):
+    """One line per call: each tensor's worst figure against the reference, and what a widened tensor was measured with."""
+    out = []
+    for nm, f in figures.items():
+        s = f"{nm} " + "/".join(f"{v:.2e}" for v in f["vs_ref"].values())
+        if "ref_vs_f64" in f:
+            s += f" [reference vs float64 {f['ref_vs_f64']:.2e}"
+            if "bound" in f:
+                s += f", WIDENED to {f['bound']:.2e}, vs float64 " + "/".join(f"{v:.2e}" for v in f["vs_f64"].values())
+            s += "]"
+        out.append(s)
+    return ", ".join(out)

@@ -222,17 +222,10 @@ def test_nearly_opaque_nearly_covering_faces(seed, idx):
 
 # ---- the reference's record-stack desync corner, constructed ------------------------------
 def _desync_args(K):
-    """A scene in which every seventh face has a degenerate WORLD triangle (p1 == p0: the ray test's denominator is exactly 0,
-    auxiliary.h:232) under unchanged image-space tables: such a face overlaps its pixels (the forward takes an AA record for
-    it, forward.cu:344-352) but never blends.  Where it is the last face of a pixel's list, the reference's backward finds
-    its record on top of the stack, does not pop it (the entry lies behind the last contributor, backward.cu:219-221) and so
-    never reaches the records of the faces that did blend: that pixel's gradients are lost (with K > 0 only)."""
-    args = list(_soup(64, 48, 300, 61, 1.0, K=K))
-    verts = args[4].clone()
-    for f in range(0, 300, 7):
-        verts[3 * f + 1] = verts[3 * f]
-    args[4] = verts
-    return args
+    """tests/desync_scene.py: every seventh face of a 300-face soup has a degenerate WORLD triangle; the comparison with the
+    reference's own kernels (tests/test_gpu_reference_edges.py) runs on the same arguments."""
+    from desync_scene import desync_args
+    return desync_args(K)
 
 
 def test_record_stack_desync_corner_size_of_the_deviation():

@@ -98,7 +98,7 @@ SCENES = {
     "far": _far,
     "empty": _empty,
 }
-BACKWARD_SCENES = ("soup_t0", "soup_t1", "soup_k2", "ties", "two_views")
+BACKWARD_SCENES = ("soup_t0", "soup_t05", "soup_t1", "soup_k2", "ties", "two_views")
 
 
 @functools.lru_cache(maxsize=None)
