@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import ROOT, capture_forward_args, check_from_image, rel_linf, scenes, soup_args, to_numpy_args
+from util import ROOT, capture_forward_args, check_from_image, per_pixel_terms_f64, rel_linf, scenes, soup_args, to_numpy_args
 
 pytestmark = pytest.mark.gpu
 
@@ -145,23 +145,6 @@ def _fuzz4_case():
     pm, pw, ph = g["pm"].tolist(), int(g["pw"]), int(g["ph"])
     args, _ = capture_forward_args(sc, [0], pm, pw, ph, float(g["temp"]), int(g["K"]))
     return args, g["gc"], g["gd"], pm, pw, ph
-
-
-def per_pixel_terms_f64(args, gc, gd, pm, pw, ph):
-    """Per gradient tensor: sum over the patch's pixels of |that pixel's contribution|, from the fp64 oracle run on
-    1 x 1 patches -- the quantity an fp32 sum's rounding error scales with, whatever its order."""
-    orc = _orc()
-    a = to_numpy_args(args)
-    sabs = None
-    for y in range(ph):
-        for x in range(pw):
-            b = list(a)
-            b[1] = np.array([[pm[0][0] + x, pm[0][1] + y]], np.int32); b[2] = 1; b[3] = 1
-            b[19] = np.ascontiguousarray(a[19][:, y:y + 1, x:x + 1]); b[20] = np.ascontiguousarray(a[20][:, y:y + 1, x:x + 1])
-            r = orc.render_forward_cuda(*b, dtype=np.float64)
-            gg = orc.render_backward_cuda(r, gc[:, y:y + 1, x:x + 1].astype(np.float64), gd[:, y:y + 1, x:x + 1].astype(np.float64))
-            sabs = {n: np.abs(gg[n]) for n in GRAD_NAMES} if sabs is None else {n: sabs[n] + np.abs(gg[n]) for n in GRAD_NAMES}
-    return sabs
 
 
 @pytest.mark.parametrize("kernels", ["legacy", "dense"])

@@ -277,3 +277,32 @@ def check_from_image(args, dL_dcolor, dL_ddepth, tol=1e-5, nthreads=1):
     worst["aa_to_verts"] = rel_linf(routed, scatter_aa_grad_to_verts(gref["aa_face_verts"], na[12], na[9], na[5]))
     assert all(v <= tol for v in worst.values()), worst
     return worst
+
+
+def per_pixel_terms_f64(args, gc, gd, pm, pw, ph):
+    """Per gradient tensor: sum over the patch's pixels of |that pixel's contribution|, from the fp64 oracle run on
+    1 x 1 patches -- the quantity an fp32 sum's rounding error scales with, whatever its order.
+    (One view, the sum over the whole patch: what test_fuzz4_regression needs, kept as it was.  tests/upstream.py PixelTerms keeps
+    the same terms per pixel and per output, sparse, so that many supports can be summed from one pass; it imports this module,
+    so this function cannot be built on it.)"""
+    from oracle import cpu as orc
+    a = to_numpy_args(args)
+    sabs = None
+    for y in range(ph):
+        for x in range(pw):
+            b = list(a)
+            b[1] = np.array([[pm[0][0] + x, pm[0][1] + y]], np.int32); b[2] = 1; b[3] = 1
+            b[19] = np.ascontiguousarray(a[19][:, y:y + 1, x:x + 1]); b[20] = np.ascontiguousarray(a[20][:, y:y + 1, x:x + 1])
+            r = orc.render_forward_cuda(*b, dtype=np.float64)
+            gg = orc.render_backward_cuda(r, gc[:, y:y + 1, x:x + 1].astype(np.float64), gd[:, y:y + 1, x:x + 1].astype(np.float64))
+            sabs = {n: np.abs(gg[n]) for n in GRAD_NAMES} if sabs is None else {n: sabs[n] + np.abs(gg[n]) for n in GRAD_NAMES}
+    return sabs
+
+
+EPS32 = 2.0 ** -24
+
+
+def summation_bound(gmax, sabs):
+    """The per-element acceptance test_gpu_coverage.py::test_fuzz4_regression derives: GRAD_TOL of the tensor's maximum plus
+    8 eps32 times the sum of the absolute per-pixel terms (what any fp32 summation order is good to)."""
+    return GRAD_TOL * gmax + 8.0 * EPS32 * sabs
