@@ -59,6 +59,55 @@ def opaque_scene(frame, temp=1.0):
     return make_args(tris, opac, W, H, temp, seed=41), dict(tile=_tile_of(frame))
 
 
+# the threshold scene: the opaque scene's faces; 0..4 transparent, 5 and 6 take T to T_EPS exactly, 7..14 behind them
+TH_A, TH_B = N_FRONT + 2, N_FRONT + 3
+THRESHOLD_STEPS = (0, -1, 1)
+
+
+def threshold_scene(frame, step=0, temp=1.0):
+    """Pixels whose transmittance lands on T_EPS exactly (tests/test_gpu_composite.py::test_the_stop_is_strictly_below_T_EPS):
+    1 - a = 8192 T_EPS and 1 - b = 2^-13 are exact in float32 and so is their product, and where the two large faces TH_A, TH_B
+    cover a pixel fully their alphas are their opacities a and b to the bit.  T < T_EPS is false there: the face behind them
+    still blends (T <= T_EPS would end the pixel one face early).  ``step``: 1 - a that many ulps away from 8192 T_EPS (-1:
+    T one ulp below T_EPS, the pixel ends at TH_B; +1: it goes on)."""
+    W, H, ox, oy = FRAMES[frame]
+    f32 = np.float32
+    x = f32(T_EPS) * f32(8192)
+    if step:
+        x = np.nextafter(x, f32(0) if step < 0 else f32(1))
+    a, b = f32(1) - x, f32(1) - f32(2.0 ** -13)
+    assert f32(1) - a == x
+    assert (x * (f32(1) - b) == f32(T_EPS)) == (step == 0)
+    rng = np.random.default_rng(17)
+    tris = [_snap(np.array([(0.8, 0.7), (3.4, 0.9), (1.0, 3.3)]) + rng.uniform(-0.1, 0.1, (3, 2))) for _ in range(N_FRONT)]
+    tris.append(_snap([(0.5, 0.5), (7.5, 0.6), (0.6, 7.5)]))
+    tris.append(_snap([(2.2, 1.3), (3.8, 1.4), (2.5, 2.7)]))
+    tris += [_snap(np.array([(-0.7, -0.6), (11.5, -0.5), (-0.6, 11.4)]) + rng.uniform(-0.3, 0.3, (3, 2))) for _ in range(N_BEHIND)]
+    tris = [t + np.array([ox, oy], dtype=np.float64) for t in tris]          # (the opaque scene's faces, draw for draw)
+    opac = rng.uniform(0.2, 0.4, len(tris)).astype(f32)
+    opac[:TH_A] = 0.0                                                        # in front: alpha 0, T stays exactly 1
+    opac[TH_A], opac[TH_B] = a, b
+    return make_args(tris, opac, W, H, temp, seed=43), dict(tile=_tile_of(frame), step=step)
+
+
+def present_threshold(args, ref, info):
+    """-> the pixels of the tile that TH_A, TH_B and the face behind them cover fully: T behind TH_B is (1 - a)(1 - b) there,
+    and n_contrib says on which side of the stop that fell."""
+    W, H, nc, fT, fpT, lens = _state(args, ref)
+    tris = _tris(args)
+    tm = _tile_mask(info["tile"], W, H)
+    full = _fully_inside(tris[TH_A], W, H) & _fully_inside(tris[TH_B], W, H) & _fully_inside(tris[TH_B + 1], W, H) & tm
+    assert full.sum() >= 6, int(full.sum())
+    op = args[7].numpy()
+    T2 = (np.float32(1) - op[TH_A]) * (np.float32(1) - op[TH_B])
+    if info["step"] < 0:
+        assert T2 < np.float32(T_EPS) and (nc[full] == TH_B + 1).all() and (fT[full] == T2).all()
+    else:
+        assert (T2 == np.float32(T_EPS)) == (info["step"] == 0) and T2 >= np.float32(T_EPS)
+        assert (nc[full] > TH_B + 1).all() and (fpT[full] <= T2).all()      # the stop did not fire at T == T_EPS
+    return full
+
+
 def _tile_of(frame):
     W, H, ox, oy = FRAMES[frame]
     return (oy // 16) * ((W + 15) // 16) + ox // 16

@@ -48,3 +48,23 @@ def test_scene_holds_its_case_and_oracle_repeats(scene, frame, temp):
     for name in GRAD_NAMES:
         assert np.abs(g1[name]).max() > 0 or name == "aa_face_verts" and temp == 0.0, name
         assert rel_linf(g2[name], g1[name]) <= GRAD_TOL, name
+
+
+THRESHOLD_REACH = {"16x16": 45, "40x24": 43}          # pixels whose T behind TH_B is (1 - a)(1 - b), as counted here
+
+
+@pytest.mark.parametrize("temp", [1.0, 0.0])
+@pytest.mark.parametrize("frame", list(brs.FRAMES))
+def test_threshold_scene_lands_on_T_EPS(frame, temp):
+    """From the fp32 oracle alone: on the pixels the two threshold faces and the face behind them cover fully, the transmittance
+    behind the second is T_EPS to the bit (step 0: the pixel goes on, n_contrib beyond that face), one ulp below (-1: the pixel
+    ends there, final_T is that T) or above (+1); a floor of a third of the pixels counted when the scene was built."""
+    orc = _orc()
+    for step in brs.THRESHOLD_STEPS:
+        args, info = brs.threshold_scene(frame, step, temp)
+        ref = orc.render_forward_cuda(*to_numpy_args(args))
+        full = brs.present_threshold(args, ref, info)
+        print(f"threshold {frame} temp {temp} step {step}: {int(full.sum())} pixels, n_contrib {sorted(set(ref.n_contrib.reshape(full.shape)[full].tolist()))}")
+        assert full.sum() >= max(THRESHOLD_REACH[frame] // 3, 6), int(full.sum())
+        if step == 0:                                  # the other side of the comparison would have ended these pixels at TH_B
+            assert (ref.n_contrib.reshape(full.shape)[full] != brs.TH_B + 1).all()

@@ -39,6 +39,8 @@ def _flags(f):
 def _build(scene, frame, temp):
     if scene == "opaque":
         return brs.opaque_scene(frame, temp)
+    if scene.startswith("threshold"):
+        return brs.threshold_scene(frame, int(scene[9:]), temp)
     return brs.stack_scene(frame, int(scene[5:]), temp)
 
 
@@ -48,6 +50,8 @@ def _k_zero_pixels(scene, args, ref, info):
     if scene == "opaque":
         fronted, alone, _ = brs.present_opaque(args, ref, info)
         picks = [np.argwhere(fronted)[0], np.argwhere(alone)[0]]
+    elif scene.startswith("threshold"):
+        picks = [np.argwhere(brs.present_threshold(args, ref, info))[0]]
     else:
         picks = [np.argwhere(brs.present_stack(args, ref, info))[0]]
     for y, x in picks:
@@ -164,3 +168,20 @@ def test_records_behind_a_last_contributor_stay_out(frame, source, alpha):
                        ("verts", np.s_[3 * h:3 * h + 3]), ("aa_face_verts", np.s_[:, h])):
         assert not np.asarray(want[name])[rows].any() and not grads[name][rows].any(), name
     assert np.abs(grads["faces_opacity"][h + 1:]).min() > 0                     # the faces behind it, seen by the neighbours
+
+
+@_cases
+def test_the_stop_is_strictly_below_T_EPS(frame, source, alpha):
+    """Pixels whose transmittance behind two faces is T_EPS to the bit, one ulp below it and one above (brs.threshold_scene):
+    the forward's state bit for bit (n_contrib: T < T_EPS, not <=, ends a pixel -- a pixel that stopped one face early keeps
+    its colour to 1e-4 and its gradients within GRAD_TOL of nothing, so only the integer state shows it) and every gradient.
+    Found by the mutation audit: no scene of the render op reached the equality."""
+    for step in brs.THRESHOLD_STEPS:
+        args, info, ref, _, _ = _run(f"threshold{step}", frame, source, alpha)
+        full = brs.present_threshold(args, ref, info)
+        if alpha:                                      # (_run's alpha branch compares colour only: the integer state here)
+            dargs = to_dev(args)
+            with _C.alpha_output(True):
+                out = _C.render_forward_cuda(*dargs)
+            check_forward(dict(out=out[:10], ref=ref), args)
+        assert full.sum() >= 6

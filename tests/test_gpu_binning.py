@@ -110,3 +110,33 @@ def test_small_and_large_faces_share_tiles():
     for legacy in (False, True):
         R, ranges, flist = _lists(args, legacy)
         assert R == R_ref and np.array_equal(ranges, ranges_ref) and np.array_equal(flist, flist_ref), legacy
+
+
+def plane_scene():
+    """A soup whose every third face lies in the far plane (NDC z = 1.0 at its three corners, exactly), every third in the near
+    plane (-1.0) -> (args, per-face label: 1 far, -1 near, 0 as drawn).  The reference culls max z < -1 or min z > 1
+    (forward.cu:71): those faces are listed, and with the far plane's depth key all of the first kind tie."""
+    args = list(_scene(64, 48, 300, 5, 6.0))
+    F = args[5].shape[0]
+    label = np.zeros(F, np.int64); label[0::3] = 1; label[1::3] = -1
+    ndc = args[8].clone()
+    faces = args[5].long()
+    for lab, z in ((1, 1.0), (-1, -1.0)):
+        ndc[:, faces[torch.from_numpy(label == lab)].reshape(-1), 2] = z
+    args[8] = ndc
+    return args, label
+
+
+def test_faces_in_the_near_and_the_far_plane_are_listed():
+    """The depth cull at its two bounds (found by the mutation audit, DESIGN.md section 2: no render scene had a face in the far
+    plane, and only the layer generator's scenes one in the near plane): lists, ranges and the rendered images as the oracle's,
+    on the per-tile sort and the radix route."""
+    from util import check_forward, run_both
+    args, label = plane_scene()
+    R_ref, ranges_ref, flist_ref = _oracle_lists(args)
+    listed = np.zeros(label.size, bool); listed[flist_ref] = True
+    assert listed[label == 1].sum() >= 30 and listed[label == -1].sum() >= 30
+    for legacy in (False, True):
+        R, ranges, flist = _lists(args, legacy)
+        assert R == R_ref and np.array_equal(ranges, ranges_ref) and np.array_equal(flist, flist_ref), legacy
+    check_forward(run_both(args, backward=False), args)

@@ -149,6 +149,121 @@ def _dense_reference(ctx, alpha):
     return _DENSE[key]
 
 
+# ---- material axes (upstream.material_args): factors a one-camera soup multiplies by 1 or 0 ------------------------------------
+_MATERIAL = {}
+MATERIAL_CASES = [(s, t, r) for s, t in U.MATERIAL_SCENES for r in (("point",) if t == 0.0 else tuple(x for x in ROUTES if x != "point"))]
+
+
+class _Material:
+    """A scene under upstream.material_args with both oracles' forwards and the float64 gradients under the scene's dense
+    upstream gradient, with and without the alpha image's; computed once and shared by the routes."""
+
+    def __init__(self, scene, temp):
+        from oracle import cpu as orc
+        from util import to_numpy_args
+        self.args = U.material_args(scene, temp)
+        self.na = to_numpy_args(self.args)
+        self.nt = min(orc.max_threads(), 16)
+        self.r32 = orc.render_forward_cuda(*self.na, nthreads=self.nt)
+        r64 = orc.render_forward_cuda(*self.na, dtype=np.float64, nthreads=self.nt)
+        assert np.array_equal(self.r32.n_contrib, r64.n_contrib)                   # (the two oracles take the same branches here)
+        B, H, W = self.r32.depth.shape
+        self.gc, self.gd, self.gA = U.dense_upstream(scene, B, H, W, alpha=True)
+        self.g64 = orc.render_backward_cuda(r64, self.gc.astype(np.float64), self.gd.astype(np.float64), nthreads=self.nt)
+        z64 = orc.render_forward_cuda(*U.zero_channel_np(self.na), dtype=np.float64, nthreads=self.nt)
+        cz = np.zeros(self.gc.shape); cz[..., 2] = self.gA
+        a64 = orc.render_backward_cuda(z64, cz, np.zeros(self.gd.shape), nthreads=self.nt)
+        self.g64_alpha = {n: self.g64[n] + (0.0 if n == "verts_color" else a64[n]) for n in GRAD_NAMES}
+
+
+@pytest.mark.parametrize("scene,temp,route", MATERIAL_CASES, ids=[f"{s}-{'own' if t is None else t}-{r}" for s, t, r in MATERIAL_CASES])
+def test_material_axes(scene, temp, route):
+    """A background with a negative and a > 1 component, signed colours, intensities per (view, face) with exact zeros and exact
+    0 and 1 opacities on the ragged 50 x 37 (temperature 0.5, and 0: the point route) and the two-view patch, on every backward
+    route: the forward bit for bit against the fp32 oracle, the six gradients at GRAD_TOL against the float64 oracle.
+    tests/test_upstream_cpu.py counts what these scenes reach: pixels that end on an alpha-1 contributor, blended faces of
+    intensity 0.  Found by the mutation audit: with intensity 1 and a grey or zero background, a swapped
+    background channel on the alpha route, a dropped intensity factor and the opaque last contributor's depth term went unseen."""
+    from util import check_forward, pool_state
+    key = (scene, temp)
+    if key not in _MATERIAL:
+        _MATERIAL[key] = _Material(scene, temp)
+    m = _MATERIAL[key]
+    dargs = to_dev(m.args)
+    if route == "from_image":
+        from dmesh2_renderer_amd.sharding import BandShardedOp
+        na = from_image_oracle_args(m.args)
+        for k in range(12, 18):
+            assert np.array_equal(np.asarray(na[k]), np.asarray(m.na[k]), equal_nan=True), k
+        dargs = BandShardedOp(dargs, 1, 0, tables_from_image=True).args
+    with _route(route):
+        out = _C.render_forward_cuda(*dargs)
+    want = {"legacy": _C.FWD_NONE, "point": _C.FWD_POINT, "masks_only": _C.FWD_MASKS}.get(route, _C.FWD_POOL)
+    assert _C.last_forward_mode() == want, (route, _C.last_forward_mode())
+    check_forward(dict(out=out[:10], ref=m.r32, pool=pool_state(out[:10])), m.args)
+    alpha = route == "alpha"
+    g = _backward(route, dargs, out, m.gc, m.gd, m.gA if alpha else None)
+    gref = dict(m.g64_alpha if alpha else m.g64)
+    if route == "from_image":
+        want_aa = U.routed(gref["aa_face_verts"], m.na)
+        assert g[5].shape == want_aa.shape
+        assert rel_linf(g[5], want_aa) <= GRAD_TOL, rel_linf(g[5], want_aa)
+        g[5] = gref["aa_face_verts"]
+    worst = check_backward(dict(grads=g, ref_grads=gref))
+    print(f"materials {scene} {temp} {route}: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+
+
+_VANISHING = {}
+
+
+@pytest.mark.parametrize("route", [r for r in ROUTES if r != "point"])
+def test_vanishing_temperature(route):
+    """aa_temperature = 2^-149 on the ragged 50 x 37: where the ray misses the face, coverage * temperature is 2^-149 for a pair
+    that covers more than half its pixel and rounds to exactly 0 for the others, and a pair of zero coverage does not blend
+    (forward.cu:379): a quarter of the pixels end on another face than under any usable temperature (counted in
+    tests/test_upstream_cpu.py), which only n_contrib and the masks show -- such a pair's alpha is 0.  Forward and integer state
+    bit for bit; gradients at GRAD_TOL against the fp32 oracle (the float64 oracle does not round those products to 0: it
+    blends other pairs and is no reference here) WITHOUT a record buffer: a pair of zero mixed coverage behind a pixel's last
+    contributor has a record the reference's backward never pops, the record-stack desync corner (SURVEY.md appendix A,
+    tests/desync_scene.py), where this library's gradients are those of len_oarea_buffer = 0 by design.  Found by the
+    mutation audit."""
+    from oracle import cpu as orc
+    from util import check_forward, pool_state, to_numpy_args
+    if not _VANISHING:
+        args = U.scene_args("ragged", U.VANISHING_TEMPERATURE)
+        na = to_numpy_args(args)
+        r32 = orc.render_forward_cuda(*na)
+        B, H, W = r32.depth.shape
+        gc, gd, gA = U.dense_upstream("ragged", B, H, W, alpha=True)
+        n0 = list(na); n0[18] = 0
+        r0 = orc.render_forward_cuda(*n0)
+        assert np.array_equal(r0.color, r32.color) and np.array_equal(r0.n_contrib, r32.n_contrib)
+        g = orc.render_backward_cuda(r0, gc, gd)
+        cz = np.zeros_like(gc); cz[..., 2] = gA
+        a = orc.render_backward_cuda(orc.render_forward_cuda(*U.zero_channel_np(n0)), cz, np.zeros_like(gd))
+        ga = {n: (g[n] if n == "verts_color" else (g[n].astype(np.float64) + a[n]).astype(np.float32)) for n in GRAD_NAMES}
+        _VANISHING.update(args=args, na=na, r32=r32, gc=gc, gd=gd, gA=gA, g=g, ga=ga)
+    v = _VANISHING
+    assert 0.0 < v["na"][11] < 1e-44
+    dargs = to_dev(v["args"])
+    if route == "from_image":
+        from dmesh2_renderer_amd.sharding import BandShardedOp
+        dargs = BandShardedOp(dargs, 1, 0, tables_from_image=True).args
+    with _route(route):
+        out = _C.render_forward_cuda(*dargs)
+    want = {"legacy": _C.FWD_NONE, "masks_only": _C.FWD_MASKS}.get(route, _C.FWD_POOL)
+    assert _C.last_forward_mode() == want, (route, _C.last_forward_mode())
+    check_forward(dict(out=out[:10], ref=v["r32"], pool=pool_state(out[:10])), v["args"])
+    alpha = route == "alpha"
+    g = _backward(route, dargs, out, v["gc"], v["gd"], v["gA"] if alpha else None)
+    gref = dict(v["ga"] if alpha else v["g"])
+    if route == "from_image":
+        want_aa = U.routed(gref["aa_face_verts"], v["na"])
+        assert g[5].shape == want_aa.shape and rel_linf(g[5], want_aa) <= GRAD_TOL
+        g[5] = gref["aa_face_verts"]
+    print(f"vanishing temperature {route}:", check_backward(dict(grads=g, ref_grads=gref)))
+
+
 # ---- the deferred ops: each module's own float64 reference and tolerance, under the slot families -------------------------------
 def _cu(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()

@@ -257,3 +257,19 @@ def test_layers_oracle_on_lattice():
                 assert best == ff[0, y, x]
                 checked += 1
     assert checked > 10
+
+
+def test_plane_scene_has_faces_in_both_planes_of_the_depth_cull():
+    """tests/test_gpu_binning.py plane_scene, from the oracle alone: the faces whose three corners have NDC z = 1.0 (-1.0)
+    exactly and that the oracle lists in some tile -- what `min z > 1` (`max z < -1`) keeps and `>=` (`<=`) would cull; a floor
+    of a third of the counts."""
+    import numpy as np
+    from test_gpu_binning import _oracle_lists, plane_scene
+    args, label = plane_scene()
+    z = args[8].numpy()[0, args[5].numpy().astype(np.int64), 2]                  # (F, 3)
+    assert (z[label == 1] == 1.0).all() and (z[label == -1] == -1.0).all()
+    R, ranges, flist = _oracle_lists(args)
+    listed = np.zeros(label.size, bool); listed[flist] = True
+    far, near = int(listed[label == 1].sum()), int(listed[label == -1].sum())
+    print(f"plane scene: {far} faces in the far plane and {near} in the near plane are listed, {R} entries")
+    assert far >= 100 // 3 and near >= 100 // 3 and listed[label == 0].any()

@@ -174,3 +174,59 @@ def test_replay_support_holds_a_pixel_whose_records_span_chunks(family):
     ref = ctx.reference(family)
     deep = ctx.weight > CAND
     assert (deep & ref["mask"]).any(), (family, ctx.window, int(deep.sum()))
+
+
+# ---- what the material axes are for (upstream.material_args; tests/test_gpu_sparse_upstream.py test_material_axes) --------------
+#                 (scene, temp): pixels ending on an alpha-1 contributor, (pixel, face) blends of intensity 0 -- as counted here
+MATERIAL_REACH = {("ragged", None): (692, 29), ("ragged", 0.0): (996, 29), ("two_views", None): (962, 35)}
+
+
+@pytest.mark.parametrize("scene,temp", U.MATERIAL_SCENES, ids=[f"{s}-{'own' if t is None else t}" for s, t in U.MATERIAL_SCENES])
+def test_material_axes_reach_what_they_are_for(scene, temp):
+    """From the fp32 oracle alone: the pixels whose last contributor has alpha exactly 1 (final_T == 0: the backward's
+    alpha_is_one arm, -prev_T_final times the background terms), the faces of intensity exactly 0 whose intensity gradient is
+    not zero (they blend: the factor the colour gradients carry and the intensity gradient does not), opacity gradients of
+    opacity-0 faces (alpha 0 pairs do not blend and yet have a gradient), a background no channel swap leaves alone; a floor of
+    a third of each count.  And the fp32 oracle stays within GRAD_TOL of the float64 one, the GPU test's acceptance."""
+    from oracle import cpu as orc
+    from util import GRAD_TOL, rel_linf, to_numpy_args
+    na = to_numpy_args(U.material_args(scene, temp))
+    r32 = orc.render_forward_cuda(*na, nthreads=4)
+    r64 = orc.render_forward_cuda(*na, dtype=np.float64, nthreads=4)
+    B, H, W = r32.depth.shape
+    gc, gd, _ = U.dense_upstream(scene, B, H, W)
+    g32 = orc.render_backward_cuda(r32, gc, gd, nthreads=4)
+    g64 = orc.render_backward_cuda(r64, gc.astype(np.float64), gd.astype(np.float64), nthreads=4)
+    for n in GRAD_NAMES:
+        assert rel_linf(g32[n], g64[n]) <= GRAD_TOL / 2, n
+    nc, fT = r32.n_contrib.reshape(-1), r32.final_T.reshape(-1)
+    opaque_last = int(((nc > 0) & (fT == 0.0)).sum())
+    dark = int(((na[10] == 0.0) & (g32["faces_intense"] != 0.0)).sum())
+    clear = int(((na[7] == 0.0) & (g32["faces_opacity"] != 0.0)).sum())
+    opaque = int(((na[7] == 1.0) & (g32["faces_opacity"] != 0.0)).sum())
+    print(f"materials {scene} {temp}: {opaque_last} of {nc.size} pixels end on an alpha-1 contributor, {dark} (view, face) of "
+          f"intensity 0 blend, {clear} faces of opacity 0 and {opaque} of opacity 1 have an opacity gradient")
+    want = MATERIAL_REACH[(scene, temp)]
+    assert opaque_last >= want[0] // 3, opaque_last
+    assert dark >= max(want[1] // 3, 1) and clear >= 1 and opaque >= 1, (dark, clear, opaque)
+    bg = na[0]
+    assert bg.min() < 0 and bg.max() > 1 and len(set(bg.tolist())) == 3 and (np.abs(na[6]).max() <= 1) and (na[6] < 0).any()
+
+
+VANISHING_REACH = 520          # pixels of the ragged scene that end on another face than under a usable temperature, as counted here
+
+
+def test_vanishing_temperature_reaches_pairs_of_zero_coverage():
+    """From the fp32 oracle alone: under aa_temperature = 2^-149 the pixels whose last contributor differs from the one under
+    2^-100 (where no product rounds to 0) -- pixels that own a pair whose mixed coverage is exactly 0 behind their last
+    blending one; a floor of a third of the count.  The records are the same (a pair of zero mixed coverage still has an area)."""
+    from oracle import cpu as orc
+    from util import to_numpy_args
+    a = to_numpy_args(U.scene_args("ragged", U.VANISHING_TEMPERATURE))
+    b = to_numpy_args(U.scene_args("ragged", float(np.float32(2.0 ** -100))))
+    assert 0.0 < a[11] < 1e-44 and np.float32(a[11]) * np.float32(0.5) == 0 and np.float32(a[11]) * np.float32(0.75) != 0
+    ra, rb = orc.render_forward_cuda(*a), orc.render_forward_cuda(*b)
+    moved = int((ra.n_contrib != rb.n_contrib).sum())
+    print(f"vanishing temperature: {moved} of {ra.n_contrib.size} pixels end on another face")
+    assert moved >= VANISHING_REACH // 3 and (ra.n_contrib <= rb.n_contrib).all()
+    assert np.array_equal(ra.buf_tri_cnt, rb.buf_tri_cnt)

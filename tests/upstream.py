@@ -77,6 +77,36 @@ def scene_args(name, temp=None, window=(0, 0)):
     return args
 
 
+# ---- material axes ------------------------------------------------------------------------------------------------------------
+# Every one-camera soup has faces_intense == 1 and background == 0 exactly, opacities in [0.2, 0.9] and colours in [0, 1]: whole
+# factors of the backward are multiplied by 1 or 0 there.  The materials below go on the existing scenes' geometry.
+MATERIAL_BACKGROUND = (-0.3, 1.7, 0.4)     # non-zero, no two components equal, one negative, one above 1
+MATERIAL_SCENES = (("ragged", None), ("ragged", 0.0), ("two_views", None))     # (scene, temperature: None = the scene's own)
+
+
+def material_args(name, temp=None, seed=0):
+    """scene_args(name, temp) with materials a one-camera soup never has: MATERIAL_BACKGROUND, signed vertex colours, opacities
+    drawn from [0.2, 0.9] with exact 0 (one face in seven) and exact 1 (one in five), intensities per (view, face) from [0, 2]
+    with exact zeros (one in seven).  The geometry, and with it every list, pair and tie, is the scene's own."""
+    args = scene_args(name, temp)
+    rng = np.random.default_rng(4000 + seed)
+    P, F, B = args[6].shape[0], args[5].shape[0], args[10].shape[0]
+    args[0] = torch.tensor(MATERIAL_BACKGROUND, dtype=torch.float32)
+    args[6] = torch.from_numpy(rng.uniform(-1.0, 1.0, (P, 3)).astype(np.float32))
+    op, u = rng.uniform(0.2, 0.9, F), rng.random(F)
+    op[u < 1.0 / 7.0] = 0.0; op[u > 0.8] = 1.0
+    args[7] = torch.from_numpy(op.astype(np.float32))
+    it = rng.uniform(0.0, 2.0, (B, F))
+    it[rng.random((B, F)) < 1.0 / 7.0] = 0.0
+    args[10] = torch.from_numpy(it.astype(np.float32))
+    return args
+
+
+# The smallest positive float32: a legal aa_temperature under which coverage * temperature rounds to 0 for every pair that covers
+# at most half its pixel -- the forward's `ratio != 0` test, which no usable temperature reaches (a live pair has an area > 0).
+VANISHING_TEMPERATURE = float(np.float32(2.0 ** -149))
+
+
 # (soup: the Jacobian of one sliver face, 218, is where the fp32 oracle comes nearest to the bound from the fp64 one, and under
 # most seeds passes it in some family -- 1.0013 of it under seed 1000, up to 3.0 under others -- through rounding inside that
 # single pair: the reference itself would not stay inside the criterion on such an input.  Under 3002 it stays at 0.89)
