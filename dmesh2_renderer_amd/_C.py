@@ -15,6 +15,7 @@ and the consumer of those layers the reference does not have (LayeredRenderer.re
 and the per-pixel nearest hits of any triangle mesh (Renderer.rasterize):
 
     rasterize_layers_cuda(...10 args...) -> 4-tuple, rasterize_layers_backward_cuda(...7 args...) -> dL/dverts
+    (both with ``overlap=True``: the faces that overlap the pixel's square, a 5-tuple with the ``inside`` mask)
 
 and the attribute images of such hits (Renderer.interpolate):
 
@@ -144,7 +145,11 @@ EXPORTS = {
     "dm2_rasterize_run_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp, _sz, _vp,
                                                 _sz, _vp, _vp, _vp, _vp, _vp]),
     "dm2_rasterize_backward_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp]),
+    "dm2_rasterize_overlap_run_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp,
+                                                        _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_rasterize_overlap_backward_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp]),
     "dm2_coverage_window": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 5),
+    "dm2_coverage_window_inside": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
     "dm2_coverage_backward_window": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
     "dm2_layers_composite_window": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp,
                                                    _vp]),
@@ -844,13 +849,16 @@ def _rasterize_desc(width, height, B, verts, faces, image_ray_o, image_ray_d, nu
 
 
 def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc, verts_image, image_ray_o, image_ray_d,
-                          num_layers):
+                          num_layers, overlap=False):
     """The first ``num_layers`` faces each pixel's ray hits, in (t, face id) order (include/dm2_hip.h: dm2_rasterize_run).
 
     verts (P,3), faces (F,3) int32, face_existence (F) int32 or None (every face exists), verts_ndc (B,P,3), verts_image
     (B,P,2) of the full frame (the plan's bins and depth cull), image_ray_o / image_ray_d (B,H,W,3) (placeholders under
     ``analytic_rays``) -> (render_layers (B,H,W,L) int32, -1 = empty; render_layers_cnt (B,H,W) int32; bary (B,H,W,L,3) float32
-    = (1 - u - v, u, v); t (B,H,W,L) float32), -1 in every empty slot."""
+    = (1 - u - v, u, v); t (B,H,W,L) float32), -1 in every empty slot.
+
+    ``overlap=True`` (dm2_rasterize_overlap_run_window): the faces that overlap the pixel's square and whose plane the ray meets
+    in front, with clamped barycentrics -> the same four and inside (B,H,W,L) bool, true where the ray hits the face itself."""
     lib = load_library()
     keep: list = []
     if verts_ndc is None or verts_ndc.dim() != 3 or verts_image is None:
@@ -863,9 +871,11 @@ def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc
     N, Tn, BF = B * H * W, _tiles(B, W, H), B * F
     if N == 0 or L == 0 or F == 0:
         # nothing to walk: every slot empty (the kernels would write the same)
-        return (torch.full((B, H, W, L), -1, dtype=i32, device=dev), torch.zeros((B, H, W), dtype=i32, device=dev),
-                torch.full((B, H, W, L, 3), -1.0, dtype=f32, device=dev), torch.full((B, H, W, L), -1.0, dtype=f32, device=dev))
+        out = (torch.full((B, H, W, L), -1, dtype=i32, device=dev), torch.zeros((B, H, W), dtype=i32, device=dev),
+               torch.full((B, H, W, L, 3), -1.0, dtype=f32, device=dev), torch.full((B, H, W, L), -1.0, dtype=f32, device=dev))
+        return out + (torch.zeros((B, H, W, L), dtype=torch.bool, device=dev),) if overlap else out
     layers = torch.empty((B, H, W, L), dtype=i32, device=dev)            # (every slot written by the kernel)
+    inside = torch.empty((B, H, W, L), dtype=torch.uint8, device=dev) if overlap else None
     cnt = torch.empty((B, H, W), dtype=i32, device=dev)
     bary = torch.empty((B, H, W, L, 3), dtype=f32, device=dev)
     t = torch.empty((B, H, W, L), dtype=f32, device=dev)
@@ -885,19 +895,25 @@ def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc
         bin_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_BINNING, R, Tn))
         run_args = (R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf),
                     img_buf.numel(), _ptr(layers), _ptr(cnt), _ptr(bary), _ptr(t), st)
-        if win is None:
+        if overlap:
+            rc = lib.dm2_rasterize_overlap_run_window(ctypes.byref(d), None if win is None else ctypes.byref(win), *run_args[:-1],
+                                                      _ptr(inside), st)
+        elif win is None:
             rc = lib.dm2_rasterize_run(ctypes.byref(d), *run_args)
         else:
             rc = lib.dm2_rasterize_run_window(ctypes.byref(d), ctypes.byref(win), *run_args)
         if rc:
             raise _err(lib, "rasterize_layers_cuda (run)")
+    if overlap:
+        return layers, cnt, bary, t, inside.view(torch.bool)       # (the kernel writes 0 or 1)
     return layers, cnt, bary, t
 
 
-def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, image_ray_d, dL_dbary, dL_dt):
+def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, image_ray_d, dL_dbary, dL_dt, overlap=False):
     """Gradient of rasterize_layers_cuda's bary and t w.r.t. verts (dm2_rasterize_backward): render_layers (B,H,W,L) as the
     forward returned them, the forward's verts / faces / rays, dL_dbary (B,H,W,L,3) and dL_dt (B,H,W,L), either may be None
-    -> dL_dverts (P,3).  Nothing flows through the rays or through which faces are listed."""
+    -> dL_dverts (P,3).  Nothing flows through the rays or through which faces are listed.  ``overlap=True``: the lists are the
+    overlap mode's (dm2_rasterize_overlap_backward_window: the clamp is recomputed and chained through)."""
     lib = load_library()
     if render_layers.dim() != 4:
         raise RuntimeError("render_layers must have dimensions (B, H, W, L)")
@@ -922,7 +938,10 @@ def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, ima
     if B * H * W * L == 0 or d.F == 0 or (gb is None and gt is None):
         return dverts
     with torch.cuda.device(dev):
-        if win is None:
+        if overlap:
+            rc = lib.dm2_rasterize_overlap_backward_window(ctypes.byref(d), None if win is None else ctypes.byref(win), _ptr(rl), _ptr(gb),
+                                                           _ptr(gt), _ptr(dverts), _stream(dev))
+        elif win is None:
             rc = lib.dm2_rasterize_backward(ctypes.byref(d), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts), _stream(dev))
         else:
             rc = lib.dm2_rasterize_backward_window(ctypes.byref(d), ctypes.byref(win), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts),
@@ -1153,6 +1172,16 @@ def composite_backward_cuda(values, alpha, render_layers, background, n_contrib,
     return dvalues, dalpha
 
 
+def _coverage_inside(inside, render_layers):
+    """The ``inside`` mask of a coverage call (bool or integer, the shape of render_layers) as contiguous uint8, 1 where set."""
+    if tuple(inside.shape) != tuple(render_layers.shape):
+        raise RuntimeError(f"inside must have dimensions {tuple(render_layers.shape)}, got {tuple(inside.shape)}")
+    if inside.dtype.is_floating_point or inside.dtype.is_complex:
+        raise RuntimeError(f"inside: expected a bool or integer dtype, got {inside.dtype}")
+    _require_gpu(inside, render_layers)
+    return (inside != 0).to(torch.uint8).contiguous()
+
+
 def _coverage_args(render_layers, verts_image, faces, temperature, grad_cov=None):
     """Checks of a coverage call -> (sizes (B, H, W, L, P, F, temperature), contiguous tensors, device)."""
     def bad(cond, msg):
@@ -1178,14 +1207,16 @@ def _coverage_args(render_layers, verts_image, faces, temperature, grad_cov=None
     return (B, H, W, L, int(verts_image.size(1)), int(faces.size(0)), temperature), ts, dev
 
 
-def coverage_cuda(render_layers, verts_image, faces, temperature=1.0):
+def coverage_cuda(render_layers, verts_image, faces, temperature=1.0, inside=None):
     """The analytic pixel coverage of every listed slot (include/dm2_hip.h: dm2_coverage).
 
     render_layers (B,H,W,L) int32 face ids over the full frame, verts_image (B,P,2) float32, faces (F,3) int32, temperature in
     [0, 1] (ValueError otherwise) -> cov (B,H,W,L) float32: 0 in an empty slot and where the triangle misses the pixel, else
-    (1 - temperature) + area * temperature."""
+    (1 - temperature) + area * temperature.  ``inside`` (B,H,W,L) bool or integer (``rasterize(overlap=True)``'s): a non-empty
+    slot where it is 0 gets area * temperature instead (dm2_coverage_window_inside)."""
     lib = load_library()
     sizes, (rl, vi, fc, _), dev = _coverage_args(render_layers, verts_image, faces, temperature)
+    ins = None if inside is None else _coverage_inside(inside, render_layers)
     B, H, W, L = sizes[:4]
     cov = torch.empty((B, H, W, L), dtype=torch.float32, device=dev)       # (every element written by the kernel)
     if B * H * W * L == 0:
@@ -1193,7 +1224,10 @@ def coverage_cuda(render_layers, verts_image, faces, temperature=1.0):
     keep: list = []
     win = _window(B, W, H, dev, keep)                    # (then render_layers is the window's, verts_image the frame's)
     with torch.cuda.device(dev):
-        if win is None:
+        if ins is not None:
+            rc = lib.dm2_coverage_window_inside(*sizes, None if win is None else ctypes.byref(win), _ptr(rl), _ptr(ins), _ptr(vi), _ptr(fc),
+                                                _ptr(cov), _stream(dev))
+        elif win is None:
             rc = lib.dm2_coverage(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev))
         else:
             rc = lib.dm2_coverage_window(*sizes, ctypes.byref(win), _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev))

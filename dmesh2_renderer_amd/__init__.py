@@ -14,7 +14,9 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   (``TextureFunction``), and ``Renderer.composite()``: such per-slot values blended front to back into an image and an
   alpha image, differentiable w.r.t. the values and the per-slot or per-face opacities (``CompositeFunction``), and
   ``Renderer.coverage()``: the analytic pixel coverage of the listed faces, the anti-aliasing factor of such a blend's
-  alpha, differentiable w.r.t. the vertices and the cameras (``CoverageFunction``): what moves a silhouette
+  alpha, differentiable w.r.t. the vertices and the cameras (``CoverageFunction``): what moves a silhouette; with
+  ``rasterize(overlap=True)`` (``RasterizeOverlapFunction``) and ``coverage(inside=...)`` the lists also name the faces that
+  only graze a pixel, and that pipeline reproduces ``Renderer.forward``'s images, silhouettes included
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -34,7 +36,7 @@ from . import _C
 from .pyrenderer import Triangles
 
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
-           "TextureFunction", "CoverageFunction", "Triangles"]
+           "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -341,7 +343,7 @@ class Renderer(torch.nn.Module):
 
     def rasterize(self, batch_mvp_idx: Sequence[int], verts: torch.Tensor, faces: torch.Tensor, num_layers: int,
                   faces_existence: torch.Tensor = None, patch_min: torch.Tensor = None, patch_width: int = None,
-                  patch_height: int = None):
+                  patch_height: int = None, overlap: bool = False):
         """The first ``num_layers`` faces each pixel's ray hits, over the full frame of every selected view or over a window of
         it (not in the reference) -> render_layers (B,H,W,L) int32 face ids (-1 = empty), render_layers_cnt (B,H,W) int32, bary (B,H,W,L,3)
         float32 = the weights of faces[f][0..2] at the hit (perspective-correct), t (B,H,W,L) float32 = the hit's distance
@@ -361,7 +363,18 @@ class Renderer(torch.nn.Module):
         crop of the full frame where its origin is a multiple of 16, and elsewhere may differ in hits of faces whose bbox
         misses the pixel's tile in one of the two grids.  The window must lie inside the frame (``select_rays``' assertions;
         ValueError for a negative origin, or for ``patch_min`` without a size); an empty window returns empty tensors and
-        launches nothing.  Without ``patch_min`` the sizes must be None as well."""
+        launches nothing.  Without ``patch_min`` the sizes must be None as well.
+
+        ``overlap=True`` -> (render_layers, render_layers_cnt, bary, t, inside): the faces ``forward`` blends at a temperature
+        > 0, so that the deferred path draws a silhouette as ``forward`` does.  Of the same candidates a face is listed where
+        its projected triangle overlaps the pixel's square [X, X+1] x [Y, Y+1] (frame coordinates) with non-zero area by
+        ``coverage``'s clipper, the ray meets its plane (not in the plane itself) and the slot's t >= 0.  bary is the ray's
+        barycentrics clamped onto the triangle (``clamp_bary_uv``), inside (B,H,W,L) bool tells the slots where the ray hits
+        the face itself (nothing was clamped): those are exactly the standard mode's hits, t included.  Elsewhere t is the ray
+        parameter of the clamped point's projection onto the ray, continuous across the triangle's edge.  Order (t, face
+        id); empty slots hold -1, and False in inside.  Hand ``inside`` to ``coverage`` so that a grazing face mixes as it
+        does in ``forward``.  Differentiable in bary and t w.r.t. ``verts`` through the clamp (``RasterizeOverlapFunction``)."""
+        fn = RasterizeOverlapFunction if overlap else RasterizeFunction
         if patch_min is None:
             if patch_width is not None or patch_height is not None:
                 raise ValueError("patch_width / patch_height need patch_min")
@@ -369,7 +382,7 @@ class Renderer(torch.nn.Module):
             if patch_width is None or patch_height is None:
                 raise ValueError("patch_min needs patch_width and patch_height")
             return self._rasterize_window(batch_mvp_idx, verts, faces, int(num_layers), faces_existence, patch_min, int(patch_width),
-                                          int(patch_height))
+                                          int(patch_height), fn)
         mv = self.mv[batch_mvp_idx]
         proj = self.proj[batch_mvp_idx]
         i32, f32 = torch.int32, torch.float32
@@ -386,9 +399,9 @@ class Renderer(torch.nn.Module):
             cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
             ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
             with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
-                return RasterizeFunction.apply(*args, ph, ph, self.width, self.height, int(num_layers))
+                return fn.apply(*args, ph, ph, self.width, self.height, int(num_layers))
         ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
-        return RasterizeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32), self.width, self.height, int(num_layers))
+        return fn.apply(*args, ray_o.to(f32), ray_d.to(f32), self.width, self.height, int(num_layers))
 
     def _project_constants(self, batch_mvp_idx, verts, faces):
         """verts_ndc, verts_image of the selected views without a graph: the plan's bins and depth cull, constants of the op."""
@@ -401,19 +414,21 @@ class Renderer(torch.nn.Module):
                 return prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
             return self.compute_verts_ndc_image(verts, mv, proj)
 
-    def _rasterize_window(self, batch_mvp_idx, verts, faces, num_layers, faces_existence, patch_min, pw, ph):
+    def _rasterize_window(self, batch_mvp_idx, verts, faces, num_layers, faces_existence, patch_min, pw, ph, fn):
         i32, f32 = torch.int32, torch.float32
         B, L, dev = len(batch_mvp_idx), num_layers, verts.device
         pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
         if pw == 0 or ph == 0:
-            return (torch.empty((B, ph, pw, L), dtype=i32, device=dev), torch.empty((B, ph, pw), dtype=i32, device=dev),
-                    torch.empty((B, ph, pw, L, 3), dtype=f32, device=dev), torch.empty((B, ph, pw, L), dtype=f32, device=dev))
+            out = (torch.empty((B, ph, pw, L), dtype=i32, device=dev), torch.empty((B, ph, pw), dtype=i32, device=dev),
+                   torch.empty((B, ph, pw, L, 3), dtype=f32, device=dev), torch.empty((B, ph, pw, L), dtype=f32, device=dev))
+            if fn is RasterizeOverlapFunction:
+                out += (torch.empty((B, ph, pw, L), dtype=torch.bool, device=dev),)
+            return out
         verts_ndc, verts_image = self._project_constants(batch_mvp_idx, verts, faces)
         fe = None if faces_existence is None else faces_existence.to(i32)
         ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
         with ctx:
-            return RasterizeFunction.apply(verts.to(f32), faces.to(i32), fe, verts_ndc.to(f32), verts_image.to(f32), ray_o, ray_d,
-                                           pw, ph, L)
+            return fn.apply(verts.to(f32), faces.to(i32), fe, verts_ndc.to(f32), verts_image.to(f32), ray_o, ray_d, pw, ph, L)
 
     def interpolate(self, render_layers: torch.Tensor, bary: torch.Tensor, attr: torch.Tensor, attr_faces: torch.Tensor):
         """Attribute images from ``rasterize``'s hits (not in the reference): render_layers (B,H,W,L) int32 face ids (as
@@ -462,7 +477,7 @@ class Renderer(torch.nn.Module):
         return CompositeFunction.apply(values.to(f32), alpha.to(f32), rl, bg)
 
     def coverage(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
-                 temperature: float = 1.0, patch_min: torch.Tensor = None):
+                 temperature: float = 1.0, patch_min: torch.Tensor = None, inside: torch.Tensor = None):
         """The analytic pixel coverage of the listed faces (not in the reference): render_layers (B,H,W,L) int32 face ids over
         the full frame (as ``rasterize`` / ``generate`` return them, or hand-built), verts (P,3), faces (F,3), temperature in
         [0, 1] (ValueError otherwise) -> cov (B,H,W,L) float32, ``Renderer.forward``'s coverage ratio of a hit:
@@ -478,9 +493,15 @@ class Renderer(torch.nn.Module):
         Window: with ``patch_min`` (B,2) int32 (x, y) per selected view, render_layers is a window's (as ``rasterize`` /
         ``generate`` return it for the same ``patch_min``; its own H, W are the window's size) and the pixel of slot (b, y, x)
         is [x + patch_min[b,0], ...+1] x [y + patch_min[b,1], ...+1] of the frame: the crop of the full-frame result.  The
-        window must lie inside the frame (``select_rays``' assertions; ValueError for a negative origin)."""
+        window must lie inside the frame (``select_rays``' assertions; ValueError for a negative origin).
+
+        ``inside`` (B,H,W,L) bool or integer, ``rasterize(overlap=True)``'s: a non-empty slot where it is 0 lists a face that
+        only grazes the pixel and mixes as ``forward`` mixes such a face, cov = area * temperature (0 at temperature 0);
+        where it is not 0, and without ``inside``, cov is as above.  The gradient is the same either way."""
         if not (0.0 <= float(temperature) <= 1.0):
             raise ValueError("temperature must be in the range [0, 1]")
+        if inside is not None and tuple(inside.shape) != tuple(render_layers.shape):
+            raise ValueError(f"inside must have dimensions {tuple(render_layers.shape)}, got {tuple(inside.shape)}")
         pm_dev = None
         if patch_min is not None:
             if render_layers.dim() != 4:
@@ -497,7 +518,7 @@ class Renderer(torch.nn.Module):
         else:
             _, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
         with _C.window(pm_dev, self.width, self.height):
-            return CoverageFunction.apply(render_layers.to(i32), verts_image.to(f32), faces.to(i32), float(temperature))
+            return CoverageFunction.apply(render_layers.to(i32), verts_image.to(f32), faces.to(i32), float(temperature), inside)
 
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
@@ -650,6 +671,37 @@ class RasterizeFunction(torch.autograd.Function):
         return (dverts,) + (None,) * 9
 
 
+class RasterizeOverlapFunction(torch.autograd.Function):
+    """``Renderer.rasterize(overlap=True)``: the first L faces that overlap each pixel's square and whose plane the ray meets in
+    front (``_C.rasterize_layers_cuda(..., overlap=True)``), differentiable in bary and t w.r.t. verts.
+
+    Inputs: RasterizeFunction's.  Outputs: render_layers, render_layers_cnt, bary (B,H,W,L,3) = the clamped barycentrics, t
+    (B,H,W,L), inside (B,H,W,L) bool (not differentiable, like the ids).  The backward recomputes each slot's clamp code and
+    chains dL/dbary through ``clamp_bary_uv_grad`` and dL/dt through the hit's t (inside) or the projection formula (elsewhere).
+    """
+
+    @staticmethod
+    def forward(ctx, verts, faces, faces_existence, verts_ndc, verts_image, image_ray_o, image_ray_d, width, height, num_layers):
+        ctx.analytic = getattr(_C._tls, "analytic", None)
+        ctx.window = getattr(_C._tls, "window", None)
+        ctx.set_materialize_grads(False)
+        layers, cnt, bary, t, inside = _C.rasterize_layers_cuda(width, height, verts.detach(), faces, faces_existence, verts_ndc.detach(),
+                                                                verts_image.detach(), image_ray_o, image_ray_d, num_layers, overlap=True)
+        ctx.mark_non_differentiable(layers, cnt, inside)
+        ctx.save_for_backward(layers, verts.detach(), faces, image_ray_o, image_ray_d)
+        return layers, cnt, bary, t, inside
+
+    @staticmethod
+    def backward(ctx, grad_layers, grad_cnt, grad_bary, grad_t, grad_inside):
+        if (grad_bary is None and grad_t is None) or not ctx.needs_input_grad[0]:
+            return (None,) * 10
+        layers, verts, faces, ray_o, ray_d = ctx.saved_tensors
+        ana, win = ctx.analytic, ctx.window
+        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
+            dverts = _C.rasterize_layers_backward_cuda(layers, verts, faces, ray_o, ray_d, grad_bary, grad_t, overlap=True)
+        return (dverts,) + (None,) * 9
+
+
 class InterpolateFunction(torch.autograd.Function):
     """out = (bary0 attr[v0] + bary1 attr[v1]) + bary2 attr[v2] per slot of render_layers (``_C.interpolate_cuda``).
 
@@ -741,17 +793,18 @@ class CoverageFunction(torch.autograd.Function):
     """cov = the analytic overlap of each listed face with its pixel, mixed with the temperature (``_C.coverage_cuda``):
     (1 - temperature) + area * temperature; 0 in an empty slot, where the clipper errs and where the area is 0.
 
-    Inputs: render_layers (B,H,W,L) int32, verts_image (B,P,2)*, faces (F,3) int32, temperature.  Output: cov (B,H,W,L).
+    Inputs: render_layers (B,H,W,L) int32, verts_image (B,P,2)*, faces (F,3) int32, temperature, inside (B,H,W,L) bool or integer
+    or None (a slot where it is 0 mixes as area * temperature; the gradient does not need it).  Output: cov (B,H,W,L).
     (* = receives a gradient.)  A partially covered slot sends g temperature d(area)/d(corner) to the image coordinates of its
     face's three vertices; nothing flows through which faces are listed.  The output gradient is not materialised: with cov
     left out of the loss, or at temperature 0, no kernel runs.
     """
 
     @staticmethod
-    def forward(ctx, render_layers, verts_image, faces, temperature):
+    def forward(ctx, render_layers, verts_image, faces, temperature, inside=None):
         ctx.set_materialize_grads(False)
         ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
-        cov = _C.coverage_cuda(render_layers, verts_image.detach(), faces, temperature)
+        cov = _C.coverage_cuda(render_layers, verts_image.detach(), faces, temperature, inside)
         ctx.temperature = float(temperature)
         ctx.save_for_backward(render_layers, verts_image.detach(), faces)
         return cov
@@ -759,11 +812,11 @@ class CoverageFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_cov):
         if grad_cov is None or ctx.temperature == 0.0 or not ctx.needs_input_grad[1]:
-            return None, None, None, None
+            return None, None, None, None, None
         render_layers, verts_image, faces = ctx.saved_tensors
         win = ctx.window
         with _C.window(*(win if win is not None else (None,))):
-            return None, _C.coverage_backward_cuda(render_layers, verts_image, faces, ctx.temperature, grad_cov), None, None
+            return None, _C.coverage_backward_cuda(render_layers, verts_image, faces, ctx.temperature, grad_cov), None, None, None
 
 
 class LayeredRenderer(Renderer):

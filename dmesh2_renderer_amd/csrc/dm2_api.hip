@@ -465,10 +465,12 @@ int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t ma
                                     image_scratch, image_bytes, render_layers, render_layers_cnt, bary, t, stream);
 }
 
-int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                             void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                             void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
-                             float* bary, float* t, void* stream) {
+// dm2_rasterize_run_window (overlap == false: `inside` is not looked at) and dm2_rasterize_overlap_run_window: the same plan,
+// scratch and tile lists; only the kernel over the lists differs.
+static int rasterize_run(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                         void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                         void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
+                         float* bary, float* t, bool overlap, uint8_t* inside, void* stream) {
     if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
     dm2_window w;
     if (resolve_window(win, d->W, d->H, &w)) return 1;
@@ -476,6 +478,8 @@ int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, in
     const int64_t BF = (int64_t)d->B * d->F, N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
     if (N == 0) return 0;
     if (!render_layers_cnt || (d->L > 0 && (!render_layers || !bary || !t))) return fail("rasterize outputs must not be null");
+    if (overlap && d->L > 0 && !inside) return fail("rasterize (overlap): inside must not be null");
+    if (overlap && d->L > 0 && d->F > 0 && !d->verts_image) return fail("rasterize (overlap): verts_image must not be null");
     if (d->L == 0) {
         DM2_HIP(hipMemsetAsync(render_layers_cnt, 0, (size_t)N * sizeof(int32_t), st));
         return 0;
@@ -494,9 +498,26 @@ int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, in
     } else {
         DM2_HIP(hipMemsetAsync(ls.ranges, 0, (size_t)Tn * sizeof(uint2), st));
     }
-    dm2::launch_rasterize(*d, w, fs, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, st);
+    if (overlap) dm2::launch_rasterize_overlap(*d, w, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, inside, st);
+    else dm2::launch_rasterize(*d, w, fs, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, st);
     DM2_HIP(hipGetLastError());
     return 0;
+}
+
+int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                             void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                             void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
+                             float* bary, float* t, void* stream) {
+    return rasterize_run(d, win, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch,
+                         image_bytes, render_layers, render_layers_cnt, bary, t, false, nullptr, stream);
+}
+
+int dm2_rasterize_overlap_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                                     void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                                     void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
+                                     float* bary, float* t, uint8_t* inside, void* stream) {
+    return rasterize_run(d, win, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch,
+                         image_bytes, render_layers, render_layers_cnt, bary, t, true, inside, stream);
 }
 
 int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
@@ -512,6 +533,18 @@ int dm2_rasterize_backward_window(const dm2_layers_desc* d, const dm2_window* wi
     if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0 || (!dL_dbary && !dL_dt)) return 0;   // nothing is listed or nothing flows
     if (!render_layers || !dL_dverts) return fail("render_layers / dL_dverts must not be null");
     dm2::launch_rasterize_backward(*d, w, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_rasterize_overlap_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
+                                          const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream) {
+    if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
+    dm2_window w;
+    if (resolve_window(win, d->W, d->H, &w)) return 1;
+    if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0 || (!dL_dbary && !dL_dt)) return 0;   // nothing is listed or nothing flows
+    if (!render_layers || !dL_dverts) return fail("render_layers / dL_dverts must not be null");
+    dm2::launch_rasterize_overlap_backward(*d, w, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
@@ -662,12 +695,19 @@ int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t 
 
 int dm2_coverage_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature, const dm2_window* win,
                         const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream) {
+    return dm2_coverage_window_inside(B, H, W, L, P, F, temperature, win, render_layers, nullptr, verts_image, faces, out_cov, stream);
+}
+
+int dm2_coverage_window_inside(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature, const dm2_window* win,
+                               const int32_t* render_layers, const uint8_t* inside, const float* verts_image, const int32_t* faces,
+                               float* out_cov, void* stream) {
     if (check_coverage_sizes(B, H, W, L, P, F, temperature)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
     if (!render_layers || !out_cov) return fail("coverage: render_layers and out_cov must not be null");
     if (F > 0 && !faces) return fail("coverage: faces must not be null");
     if (F > 0 && P > 0 && !verts_image) return fail("coverage: verts_image must not be null");
-    dm2::launch_coverage(B, H, W, L, P, F, temperature, win ? win->patch_min : nullptr, render_layers, verts_image, faces, out_cov, (hipStream_t)stream);
+    dm2::launch_coverage(B, H, W, L, P, F, temperature, win ? win->patch_min : nullptr, render_layers, inside, verts_image, faces, out_cov,
+                         (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }

@@ -1,7 +1,9 @@
 // dm2_coverage.hip -- Renderer.coverage: the analytic triangle-pixel overlap of every listed slot, the factor that turns a
 // face's opacity into an anti-aliased alpha on the deferred path (rasterize -> interpolate -> texture -> composite):
-//   k_coverage       cov[s] = mix_coverage(0, area(tri(f), pixel), temperature), 0 in an empty slot, where the clipper errs and
-//                    where area == 0 (Renderer.forward skips such a face, forward.cu:337)
+//   k_coverage       cov[s] = mix_coverage(code, area(tri(f), pixel), temperature), 0 in an empty slot, where the clipper errs and
+//                    where area == 0 (Renderer.forward skips such a face, forward.cu:337); code = 0 (a hit), or -- with the
+//                    `inside` mask of rasterize's overlap mode -- 1 where inside[s] == 0: area * temperature, forward's mix of
+//                    a face that only grazes the pixel (forward.cu:379-381)
 //   k_coverage_bwd   dL/dverts_image[b, v_k] += g_cov[s] * temperature * d(area)/d(corner k), the CCW reorder undone
 //
 // Contract (include/dm2_hip.h, dm2_coverage).  The triangle is verts_image[b, faces[f]]; its six AA tables are built in
@@ -19,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dm2_clip_area.h"
+#include "dm2_cov_tables.h"
 #include "dm2_device_math.h"
 #include "dm2_face_table.h"
 #include "dm2_state.h"
@@ -37,33 +40,20 @@ __device__ __forceinline__ bool cov_face(const CovSizes& z, int f, const int32_t
     return (unsigned)vid[0] < (unsigned)z.P && (unsigned)vid[1] < (unsigned)z.P && (unsigned)vid[2] < (unsigned)z.P;
 }
 
-// The AA tables of the face with vertices vid in view `im`, as pack_face builds them from verts_image (dm2_stage.h).
-// Returns whether the CCW reorder swapped corners 1 and 2.
-__device__ __forceinline__ bool cov_tables(const float2* __restrict__ im, const int vid[3], AAFace& a) {
-    const float2 p0 = im[vid[0]], p1 = im[vid[1]], p2 = im[vid[2]];
-    const float area2 = 0.5f * ((p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y));
-    const bool flip = area2 < 0.0f;                               // clockwise: corners 1 and 2 swap (pyrenderer.py:521-535)
-    const float2 q[3] = {p0, flip ? p2 : p1, flip ? p1 : p2};
-    uint32_t zm = 0;
+// Clamp codes (0: the ray hits the face, 1: it does not) of slots s .. s + LVEC - 1 from the `inside` bytes; !MASK: hits.
+// LVEC = 4: the four bytes are one aligned word.
+template <int LVEC, bool MASK>
+__device__ __forceinline__ void cov_codes(const uint8_t* __restrict__ in_mask, int64_t s, int code[LVEC]) {
 #pragma unroll
-    for (int i = 0; i < 3; i++) {
-        const float2 sv = q[i], ev = q[(i + 1) % 3];
-        const float ex = ev.x - sv.x, ey = ev.y - sv.y;
-        const float nx = -ey, ny = ex;
-        a.v[2 * i] = sv.x; a.v[2 * i + 1] = sv.y;
-        a.e[2 * i] = ex; a.e[2 * i + 1] = ey;
-        a.r[2 * i] = 1.0f / ex; a.r[2 * i + 1] = 1.0f / ey;
-        a.n[2 * i] = nx; a.n[2 * i + 1] = ny;
-        a.c[i] = nx * sv.x + ny * sv.y;
-        zm |= (fabsf(ex) < 1e-3f ? 1u : 0u) << (2 * i);
-        zm |= (fabsf(ey) < 1e-3f ? 1u : 0u) << (2 * i + 1);
+    for (int k = 0; k < LVEC; k++) code[k] = 0;
+    if (!MASK) return;
+    if (LVEC == 4) {
+        const uint32_t q = *reinterpret_cast<const uint32_t*>(in_mask + s);
+#pragma unroll
+        for (int k = 0; k < LVEC; k++) code[k] = ((q >> (8 * k)) & 0xFFu) == 0u ? 1 : 0;
+    } else {
+        code[0] = in_mask[s] == 0 ? 1 : 0;
     }
-    a.zmask = zm;
-    a.bb[0] = fminf(fminf(a.v[0], a.v[2]), a.v[4]);
-    a.bb[1] = fmaxf(fmaxf(a.v[0], a.v[2]), a.v[4]);
-    a.bb[2] = fminf(fminf(a.v[1], a.v[3]), a.v[5]);
-    a.bb[3] = fmaxf(fmaxf(a.v[1], a.v[3]), a.v[5]);
-    return flip;
 }
 
 // ids of slots s .. s + LVEC - 1 (LVEC = 4: L is a multiple of 4 and the array is 16-byte aligned)
@@ -77,12 +67,14 @@ __device__ __forceinline__ void cov_ids(const int32_t* __restrict__ layers, int6
     }
 }
 
-// LVEC = 4: render_layers and out are 16-byte aligned and L is a multiple of 4; every slot goes through the same operations
-// either way (the same bits).  Every slot of every pixel of the image is written.
-template <int LVEC>
+// LVEC = 4: render_layers and out are 16-byte aligned (in_mask, when given, 4-byte aligned) and L is a multiple of 4; every
+// slot goes through the same operations either way (the same bits).  Every slot of every pixel of the image is written.
+// MASK: in_mask is given.  A template parameter, not a test of the pointer: the code array costs the kernel 6 to 8 VGPRs and a
+// wave per SIMD, which the call without a mask does not pay (!MASK compiles to the registers of the kernel before the mask).
+template <int LVEC, bool MASK>
 __global__ void __launch_bounds__(TILE_PIX)
-k_coverage(CovSizes z, const int32_t* __restrict__ patch_min, const int32_t* __restrict__ layers, const float* __restrict__ image, const int32_t* __restrict__ faces,
-           float* __restrict__ out) {
+k_coverage(CovSizes z, const int32_t* __restrict__ patch_min, const int32_t* __restrict__ layers, const uint8_t* __restrict__ in_mask, const float* __restrict__ image,
+           const int32_t* __restrict__ faces, float* __restrict__ out) {
     const auto [px, py, inside, pix] = tile_pixel(threadIdx.x, z.W, z.H);
     if (!inside) return;
     const int b = blockIdx.z;
@@ -93,21 +85,22 @@ k_coverage(CovSizes z, const int32_t* __restrict__ patch_min, const int32_t* __r
     const float pix_area = 1.0f;
     const float temp = z.temp;
     for (int l = 0; l < z.L; l += LVEC) {
-        int id[LVEC];
+        int id[LVEC], code[LVEC];
         float c[LVEC];
         cov_ids<LVEC>(layers, s0 + l, id);
+        cov_codes<LVEC, MASK>(in_mask, s0 + l, code);
 #pragma unroll
         for (int k = 0; k < LVEC; k++) {
             c[k] = 0.0f;
             int vid[3];
             if (!cov_face(z, id[k], faces, vid)) continue;
-            if (temp == 0.0f) { c[k] = 1.0f; continue; }                 // no clip is evaluated
+            if (temp == 0.0f) { c[k] = code[k] == 0 ? 1.0f : 0.0f; continue; }   // no clip is evaluated
             AAFace a;
             cov_tables(im, vid, a);
             float area;
             const int err = tri_pix_overlap_area_only(a, pxmin, pxmax, pymin, pymax, pix_area, area);
             if (err != 0 || area == 0.0f) continue;
-            c[k] = mix_coverage(0, area / pix_area, temp);               // forward.cu:375-378, the slot taken as a hit
+            c[k] = mix_coverage(code[k], area / pix_area, temp);         // forward.cu:375-381; no mask: the slot taken as a hit
         }
         if (LVEC == 4) *reinterpret_cast<float4*>(out + s0 + l) = make_float4(c[0], c[1 % LVEC], c[2 % LVEC], c[3 % LVEC]);
         else out[s0 + l] = c[0];
@@ -172,12 +165,17 @@ static CovSizes cov_sizes(int B, int H, int W, int L, int P, int F, float temper
 }
 
 void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
-                     const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st) {
+                     const uint8_t* inside, const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st) {
     const CovSizes z = cov_sizes(B, H, W, L, P, F, temperature);
     const dim3 grid = tile_grid(W, H, B);
-    const bool lvec = L % 4 == 0 && (((uintptr_t)render_layers | (uintptr_t)out_cov) & 15) == 0;
-    if (lvec) hipLaunchKernelGGL(k_coverage<4>, grid, dim3(TILE_PIX), 0, st, z, patch_min, render_layers, verts_image, faces, out_cov);
-    else hipLaunchKernelGGL(k_coverage<1>, grid, dim3(TILE_PIX), 0, st, z, patch_min, render_layers, verts_image, faces, out_cov);
+    const bool lvec = L % 4 == 0 && (((uintptr_t)render_layers | (uintptr_t)out_cov) & 15) == 0 && ((uintptr_t)inside & 3) == 0;
+#define DM2_COV_LAUNCH(LVEC, MASK) \
+    hipLaunchKernelGGL((k_coverage<LVEC, MASK>), grid, dim3(TILE_PIX), 0, st, z, patch_min, render_layers, inside, verts_image, faces, out_cov)
+    if (lvec && inside) DM2_COV_LAUNCH(4, true);
+    else if (lvec) DM2_COV_LAUNCH(4, false);
+    else if (inside) DM2_COV_LAUNCH(1, true);
+    else DM2_COV_LAUNCH(1, false);
+#undef DM2_COV_LAUNCH
 }
 
 void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,

@@ -234,6 +234,12 @@ void launch_rasterize(const dm2_layers_desc& d, const dm2_window& win, const Fac
                       int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, hipStream_t st);
 void launch_rasterize_backward(const dm2_layers_desc& d, const dm2_window& win, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
                                float* dL_dverts, hipStream_t st);
+// Renderer.rasterize(overlap=True): the first d.L faces that overlap the pixel's square (d.verts_image) and whose plane the ray
+// meets in front, with clamped barycentrics and the inside byte per slot; the backward re-clamps and adds into dL_dverts.
+void launch_rasterize_overlap(const dm2_layers_desc& d, const dm2_window& win, const uint2* ranges, const uint32_t* face_list,
+                              int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, uint8_t* inside, hipStream_t st);
+void launch_rasterize_overlap_backward(const dm2_layers_desc& d, const dm2_window& win, const int32_t* render_layers, const float* dL_dbary,
+                                       const float* dL_dt, float* dL_dverts, hipStream_t st);
 // Renderer.interpolate (dm2_interpolate.hip): every element of out / dL_dbary is written; the backward adds into dL_dattr;
 // either of its output pointers may be NULL.  B * H * W * L > 0 and C >= 1.
 void launch_interpolate(int B, int H, int W, int L, int F, int N, int C, int view_tables, const int32_t* render_layers,
@@ -259,9 +265,10 @@ void launch_composite_backward(int B, int H, int W, int L, int C, int F, int per
                                const float* dL_dout, const float* dL_dacc, float* dL_dvalues, float* dL_dalpha, hipStream_t st);
 // Renderer.coverage (dm2_coverage.hip): every element of out_cov is written; the backward adds into dL_dverts_image (zero-filled
 // by the caller).  B * H * W * L > 0, 0 <= temperature <= 1 (the backward: > 0); faces may be NULL when F == 0, verts_image when
-// P == 0.  patch_min: the origins of a window (B,2), or nullptr (the full frame).
+// P == 0.  patch_min: the origins of a window (B,2), or nullptr (the full frame).  inside: rasterize's overlap-mode bytes
+// (B,H,W,L), or nullptr (every slot a hit).
 void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
-                     const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st);
+                     const uint8_t* inside, const float* verts_image, const int32_t* faces, float* out_cov, hipStream_t st);
 void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
                               const float* verts_image, const int32_t* faces, const float* dL_dcov, float* dL_dverts_image,
                               hipStream_t st);

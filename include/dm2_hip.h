@@ -341,6 +341,39 @@ int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, in
                              int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream);
 int dm2_rasterize_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
                                   const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream);
+/* Renderer.rasterize(overlap=True): the faces that overlap a pixel's SQUARE, not only those its centre ray hits -- the faces
+ * dm2_forward blends at a temperature > 0 (forward.cu:325-381), so that the deferred path draws a silhouette as it does.  Plan,
+ * scratch, candidates (tile list, existence filter) and window rules are dm2_rasterize_run_window's (win NULL: the full frame);
+ * d->verts_image must be given.  A candidate f is listed at pixel (x, y) of view b iff
+ *   (a) it overlaps the pixel: for the triangle verts_image[b, faces[f]], CCW-reordered, its tables built as under
+ *       DM2_FLAG_TABLES_FROM_IMAGE, and the square [X, X+1] x [Y, Y+1], (X, Y) = (x, y) + patch_min[b], the clipper of dm2_coverage
+ *       reports no error and area != 0 (so dm2_coverage of a listed slot is never 0 because the face misses the pixel);
+ *   (b) ray_tri_intersection succeeds and the ray is off the face's plane (dm2_rasterize_run's rule);
+ *   (c) the slot's t (below) is >= 0.
+ * Per listed slot, with (u, v) the intersection's and (uc, vc, code) = clamp_bary_uv(u, v) (auxiliary.h:292-329):
+ *   bary = (1 - uc - vc, uc, vc);   inside = (code == 0), one byte, 1 or 0;
+ *   t = the intersection's t when code == 0 (exactly dm2_rasterize_run's value), otherwise the ray parameter of the clamped
+ *       point's projection onto the ray, in fp32 in this order, without contraction (dot = (x x + y y) + z z):
+ *         b0 = (1 - uc) - vc;  d_k = dot(p_k - ro, rd);  t = ((b0 * d0 + uc * d1) + vc * d2) / dot(rd, rd)
+ *       (continuous across the triangle's edge, where the clamped point is the hit).
+ * Order: ascending (t, f); the first L are listed; empty slots hold -1 in render_layers, bary and t and 0 in inside.  A slot
+ * with inside == 1 is exactly a hit of dm2_rasterize_run: restricted to those slots, in order, the outputs are that call's
+ * wherever neither list is truncated.  The walk over a pixel's list is exhaustive (no depth-bound stop: an off-triangle
+ * slot's t is not a point of the ray on the face).  inside (B,H,W,L) uint8; every slot of every output is written. */
+int dm2_rasterize_overlap_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                                     void* face_scratch, size_t face_bytes,
+                                     void* binning_scratch, size_t binning_bytes,
+                                     void* image_scratch, size_t image_bytes,
+                                     int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, uint8_t* inside,
+                                     void* stream);
+/* Gradients of dm2_rasterize_overlap_run_window's bary and t w.r.t. verts, added into dL_dverts (P,3).  Per slot with
+ * 0 <= f < F the intersection and its clamp code are recomputed in fp32 as the forward computed them; with the code held fixed
+ * dL/d(uc, vc) = (g1 - g0, g2 - g0) (+ g_t dt/d(uc, vc) where code != 0) goes through clamp_bary_uv_grad(code) to (u, v) and
+ * on to the vertices as in dm2_rasterize_backward; g_t goes through the intersection's t (code 0) or through the projection
+ * formula, its dependence on bary included.  Nothing flows through the rays, the listing decision or inside.  Either upstream
+ * gradient may be NULL.  Float atomics. */
+int dm2_rasterize_overlap_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
+                                          const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream);
 
 /* Renderer.interpolate: attribute images from face ids and barycentrics per slot (dm2_rasterize_run's, dm2_layers_run's or
  * hand-built).  render_layers (B,H,W,L) int32, bary (B,H,W,L,3) float32, attr (N,C) float32 shared by the views
@@ -461,6 +494,14 @@ int dm2_coverage_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, i
 int dm2_coverage_backward_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
                                  const dm2_window* win, const int32_t* render_layers, const float* verts_image,
                                  const int32_t* faces, const float* dL_dcov, float* dL_dverts_image, void* stream);
+/* dm2_coverage_window with the inside bytes (B,H,W,L) of dm2_rasterize_overlap_run_window (win NULL: the full frame; inside
+ * NULL: dm2_coverage_window, to the bit).  A non-empty slot with inside == 0 mixes as a face that only grazes the pixel
+ * (forward.cu:379-381): cov = (float)(0.0 * (double)(1.0f - temperature) + (double)(area * temperature)) = area * temperature,
+ * and cov = 0 at temperature 0; a slot with inside != 0 is dm2_coverage's.  The gradient is dm2_coverage_backward_window's
+ * either way (dL_dcov * temperature * d(area)/d(corner)): the mask is not needed there. */
+int dm2_coverage_window_inside(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
+                               const dm2_window* win, const int32_t* render_layers, const uint8_t* inside,
+                               const float* verts_image, const int32_t* faces, float* out_cov, void* stream);
 
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
