@@ -27,6 +27,13 @@ and a texture sampled at such an image of UVs (Renderer.texture):
     texture_cuda(uv, tex, render_layers, filter_mode, boundary_mode) -> out,
     texture_backward_cuda(...those 5..., grad_out, need_tex, need_uv) -> (dL/dtex, dL/duv)
 
+and its mip-mapped filter (Renderer.bary_derivatives, Renderer.texture_mipmaps, texture's "linear-mipmap-linear"):
+
+    bary_derivatives_cuda(render_layers, verts, faces, ray_cam) -> (dbary_dx, dbary_dy),
+    texture_mipmaps_cuda(tex, max_mip_level) -> mip,  texture_mipmaps_backward_cuda(tex, max_mip_level, grad_mip) -> dL/dtex,
+    texture_mip_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level) -> out,
+    texture_mip_backward_cuda(...those 7..., grad_out, need_tex, need_mip, need_uv) -> (dL/dtex, dL/dmip, dL/duv)
+
 and such per-slot values blended into an image (Renderer.composite; not composite_layers_cuda, which shades by itself):
 
     composite_cuda(values, alpha, render_layers, background) -> (out, acc, final_T, n_contrib),
@@ -159,6 +166,11 @@ EXPORTS = {
     "dm2_interpolate_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 8),
     "dm2_texture": (ctypes.c_int, [_i32] * 10 + [_vp] * 5),
     "dm2_texture_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
+    "dm2_bary_derivatives_window": (ctypes.c_int, [_i32] * 6 + [ctypes.POINTER(Window)] + [_vp] * 7),
+    "dm2_texture_mipmaps": (ctypes.c_int, [_i32] * 5 + [_vp] * 3),
+    "dm2_texture_mipmaps_backward": (ctypes.c_int, [_i32] * 5 + [_vp] * 3),
+    "dm2_texture_mip": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
+    "dm2_texture_mip_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 10),
     "dm2_composite": (ctypes.c_int, [_i32] * 7 + [_vp] * 9),
     "dm2_composite_backward": (ctypes.c_int, [_i32] * 7 + [_vp] * 10),
     "dm2_coverage": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float] + [_vp] * 5),
@@ -1084,7 +1096,172 @@ def texture_backward_cuda(uv, tex, render_layers, filter_mode, boundary_mode, gr
     return dtex, duv
 
 
-COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1      # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*
+def bary_derivatives_cuda(render_layers, verts, faces, ray_cam):
+    """The footprint of a pixel on each listed face (include/dm2_hip.h: dm2_bary_derivatives_window).
+
+    render_layers (B,H,W,L) int32, verts (P,3) float32, faces (F,3) int32, ray_cam (B,32) float32 = inv(mv) then inv(proj) of
+    each view -> (dbary_dx, dbary_dy), each (B,H,W,L,3) float32: the derivatives of (1 - u - v, u, v) with respect to the
+    pixel's x and y.  Under ``_C.window`` render_layers is a window's and the frame is the window's; otherwise the frame is
+    (W, H).  Zeros in an empty slot (id outside [0, F) or a vertex outside [0, P)) and where the ray lies in the face's plane."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    lib = load_library()
+    bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+    B, H, W, L = (int(x) for x in render_layers.shape)
+    bad(verts.dim() != 2 or verts.size(1) != 3, f"verts must have dimensions (P, 3), got {tuple(verts.shape)}")
+    bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
+    bad(tuple(ray_cam.shape) != (B, 32), f"ray_cam must have dimensions ({B}, 32), got {tuple(ray_cam.shape)}")
+    f32, i32 = torch.float32, torch.int32
+    named = (("render_layers", render_layers, i32), ("verts", verts, f32), ("faces", faces, i32), ("ray_cam", ray_cam, f32))
+    dev = _require_gpu(*[t for _, t, _ in named])
+    ts = []
+    for name, t, dt in named:
+        bad(t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype}")
+        ts.append(t.contiguous())
+    rl, vs, fc, cam = ts
+    dx = torch.empty((B, H, W, L, 3), dtype=f32, device=dev)               # (every element written by the kernel)
+    dy = torch.empty((B, H, W, L, 3), dtype=f32, device=dev)
+    if B * H * W * L == 0:
+        return dx, dy                                                      # no launch
+    keep: list = []
+    win = _window(B, W, H, dev, keep)
+    with torch.cuda.device(dev):
+        if lib.dm2_bary_derivatives_window(B, H, W, L, int(verts.size(0)), int(faces.size(0)), None if win is None else ctypes.byref(win),
+                                           _ptr(rl), _ptr(vs), _ptr(fc), _ptr(cam), _ptr(dx), _ptr(dy), _stream(dev)):
+            raise _err(lib, "bary_derivatives_cuda")
+    return dx, dy
+
+
+def mip_layout(Ht, Wt, max_mip_level=None):
+    """The mip chain of an (Ht, Wt) texture (include/dm2_hip.h: dm2_texture_mipmaps) -> (nlev, [(H_k, W_k, offset_k) for k = 0 ..
+    nlev-1], T): level k+1 exists while both extents of level k are even and k < max_mip_level; offset_k = the first texel of
+    level k >= 1 in the packed chain (level 0 is the texture itself: offset 0 by convention), T = the chain's texels."""
+    if max_mip_level is not None and int(max_mip_level) < 0:
+        raise ValueError("max_mip_level must not be negative")
+    h, w, off, levels = int(Ht), int(Wt), 0, [(int(Ht), int(Wt), 0)]
+    while h >= 1 and w >= 1 and h % 2 == 0 and w % 2 == 0 and (max_mip_level is None or len(levels) - 1 < int(max_mip_level)):
+        h, w = h // 2, w // 2
+        levels.append((h, w, off))
+        off += h * w
+    return len(levels), levels, off
+
+
+def _max_level_code(max_mip_level):
+    return -1 if max_mip_level is None else min(int(max_mip_level), 64)
+
+
+def _mipmap_args(tex, max_mip_level, grad_mip=None):
+    """Checks of a mip chain call -> (sizes (NB, Ht, Wt, C, max level code), T, contiguous tensors, device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
+    Ht, Wt, C = (int(x) for x in tex.shape[-3:])
+    bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
+    bad(C < 1, "tex must have at least one channel")
+    _, _, T = mip_layout(Ht, Wt, max_mip_level)
+    bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
+    NB = int(tex.size(0)) if tex.dim() == 4 else 1
+    shape = ((NB,) if tex.dim() == 4 else ()) + (T, C)
+    bad(grad_mip is not None and tuple(grad_mip.shape) != shape,
+        f"grad_mip must have dimensions {shape}, got {tuple(grad_mip.shape) if grad_mip is not None else None}")
+    dev = _require_gpu(*[t for t in (tex, grad_mip) if t is not None])
+    ts = []
+    for name, t in (("tex", tex), ("grad_mip", grad_mip)):
+        bad(t is not None and t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    return (NB, Ht, Wt, C, _max_level_code(max_mip_level)), shape, ts, dev
+
+
+def texture_mipmaps_cuda(tex, max_mip_level=None):
+    """The mip chain of a texture (include/dm2_hip.h: dm2_texture_mipmaps): tex (Ht,Wt,C) or (B,Ht,Wt,C) float32 -> mip (T,C)
+    or (B,T,C) float32, levels 1 .. nlev-1 concatenated (``mip_layout``); T = 0 (and no launch) when no level can be built."""
+    lib = load_library()
+    sizes, shape, (tx, _), dev = _mipmap_args(tex, max_mip_level)
+    mip = torch.empty(shape, dtype=torch.float32, device=dev)               # (every element written by the kernels)
+    if mip.numel() == 0:
+        return mip
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mipmaps(*sizes, _ptr(tx), _ptr(mip), _stream(dev)):
+            raise _err(lib, "texture_mipmaps_cuda")
+    return mip
+
+
+def texture_mipmaps_backward_cuda(tex, max_mip_level, grad_mip):
+    """Gradient of texture_mipmaps_cuda (dm2_texture_mipmaps_backward) for grad_mip of mip's shape -> dL_dtex of tex's shape
+    (only tex's shape is looked at).  A gather: deterministic."""
+    lib = load_library()
+    sizes, shape, (tx, gm), dev = _mipmap_args(tex, max_mip_level, grad_mip)
+    if gm.numel() == 0:
+        return torch.zeros(tuple(tex.shape), dtype=torch.float32, device=dev)
+    dtex = torch.empty(tuple(tex.shape), dtype=torch.float32, device=dev)  # (every element written)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mipmaps_backward(*sizes, _ptr(gm), _ptr(dtex), _stream(dev)):
+            raise _err(lib, "texture_mipmaps_backward_cuda")
+    return dtex
+
+
+def _texture_mip_args(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out=None):
+    """Checks of a trilinear texture call -> (sizes (B, H, W, L, Ht, Wt, C, view_textures, boundary, max level code),
+    contiguous tensors (uv, uv_da, tex, mip, render_layers, grad_out), device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    sizes, (uvc, tx, rl, go), dev = _texture_args(uv, tex, render_layers, "linear", boundary_mode, grad_out)
+    B, H, W, L, Ht, Wt, C, per_view = sizes[:8]
+    bad(tuple(uv_da.shape) != (B, H, W, L, 4), f"uv_da must have dimensions {(B, H, W, L, 4)}, got {tuple(uv_da.shape)}")
+    _, _, T = mip_layout(Ht, Wt, max_mip_level)
+    bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
+    shape = ((B,) if per_view else ()) + (T, C)
+    bad(tuple(mip.shape) != shape,
+        f"mip must have dimensions {shape} for tex {tuple(tex.shape)} and max_mip_level {max_mip_level}, got {tuple(mip.shape)}")
+    _require_gpu(uv, uv_da, mip)
+    for name, t in (("uv_da", uv_da), ("mip", mip)):
+        bad(t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype}")
+    return sizes[:8] + (sizes[9], _max_level_code(max_mip_level)), (uvc, uv_da.contiguous(), tx, mip.contiguous(), rl, go), dev
+
+
+def texture_mip_cuda(uv, uv_da, tex, mip, render_layers=None, boundary_mode="wrap", max_mip_level=None):
+    """Trilinear sampling of a texture and its mip chain (include/dm2_hip.h: dm2_texture_mip).
+
+    uv (B,H,W,L,2), uv_da (B,H,W,L,4) = (du/dX, dv/dX, du/dY, dv/dY), tex (Ht,Wt,C) or (B,Ht,Wt,C), mip = texture_mipmaps_cuda's
+    chain of tex under the same max_mip_level, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is
+    negative or uv / uv_da is not finite."""
+    lib = load_library()
+    sizes, (uvc, da, tx, mp, rl, _), dev = _texture_mip_args(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level)
+    B, H, W, L, C = *sizes[:4], sizes[6]
+    if B * H * W * L == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mip(*sizes, _ptr(rl), _ptr(uvc), _ptr(da), _ptr(tx), _ptr(mp), _ptr(out), _stream(dev)):
+            raise _err(lib, "texture_mip_cuda")
+    return out
+
+
+def texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out, need_tex, need_mip, need_uv):
+    """Gradients of texture_mip_cuda (dm2_texture_mip_backward) -> (dL_dtex of tex's shape, dL_dmip of mip's shape, dL_duv
+    (B,H,W,L,2)), each None unless its ``need_*`` asks for it; uv_da gets none (the level of detail is a constant of the op)."""
+    lib = load_library()
+    sizes, (uvc, da, tx, mp, rl, go), dev = _texture_mip_args(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out)
+    B, H, W, L = sizes[:4]
+    f32 = torch.float32
+    if not (need_tex or need_mip or need_uv):
+        return None, None, None
+    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None      # (summed into)
+    dmip = torch.zeros(tuple(mip.shape), dtype=f32, device=dev) if need_mip else None
+    if B * H * W * L == 0:
+        return dtex, dmip, torch.zeros((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None
+    duv = torch.empty((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None        # (every element written)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mip_backward(*sizes, _ptr(rl), _ptr(uvc), _ptr(da), _ptr(tx), _ptr(mp), _ptr(go), _ptr(dtex), _ptr(dmip),
+                                        _ptr(duv), _stream(dev)):
+            raise _err(lib, "texture_mip_backward_cuda")
+    return dtex, dmip, duv
+
+
+COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1     # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*
 
 
 def _composite_args(values, alpha, render_layers, background, n_contrib=None, grad_out=None, grad_acc=None):

@@ -16,7 +16,10 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   ``Renderer.coverage()``: the analytic pixel coverage of the listed faces, the anti-aliasing factor of such a blend's
   alpha, differentiable w.r.t. the vertices and the cameras (``CoverageFunction``): what moves a silhouette; with
   ``rasterize(overlap=True)`` (``RasterizeOverlapFunction``) and ``coverage(inside=...)`` the lists also name the faces that
-  only graze a pixel, and that pipeline reproduces ``Renderer.forward``'s images, silhouettes included
+  only graze a pixel, and that pipeline reproduces ``Renderer.forward``'s images, silhouettes included; and mip-mapped
+  filtering for ``texture`` (``filter_mode="linear-mipmap-linear"``, ``TextureMipFunction``) with the two ops that feed it:
+  ``Renderer.bary_derivatives()``, the pixel's footprint on each listed face (``BaryDerivativesFunction``, a constant of
+  the pipeline), and ``Renderer.texture_mipmaps()``, the chain of 2 x 2 means (``MipmapFunction``)
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -36,7 +39,8 @@ from . import _C
 from .pyrenderer import Triangles
 
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
-           "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction"]
+           "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction", "BaryDerivativesFunction",
+           "MipmapFunction", "TextureMipFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -444,19 +448,89 @@ class Renderer(torch.nn.Module):
         return InterpolateFunction.apply(render_layers.to(i32), bary.to(f32), attr.to(f32), attr_faces.to(i32))
 
     def texture(self, uv: torch.Tensor, tex: torch.Tensor, render_layers: torch.Tensor = None, filter_mode: str = "linear",
-                boundary_mode: str = "wrap"):
+                boundary_mode: str = "wrap", uv_da: torch.Tensor = None, mip: torch.Tensor = None, max_mip_level: int = None):
         """A texture sampled at ``interpolate``'s UVs (not in the reference): uv (B,H,W,L,2) float32 = (u, v), u along the
         texture's width (what ``interpolate`` returns for a 2-channel attribute), tex (Ht,Wt,C) float32 shared by the views or
         (B,Ht,Wt,C) one texture per view, channel-last, any C >= 1, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C)
-        float32.  Texel centres sit at ((i + 0.5) / Wt, (j + 0.5) / Ht); ``filter_mode`` "linear" (bilinear) or "nearest",
-        ``boundary_mode`` "wrap" (repeat) or "clamp".
+        float32.  Texel centres sit at ((i + 0.5) / Wt, (j + 0.5) / Ht); ``filter_mode`` "linear" (bilinear), "nearest" or
+        "linear-mipmap-linear" (trilinear, below), ``boundary_mode`` "wrap" (repeat) or "clamp".
 
         A slot with ``render_layers`` < 0 (None: no slot, by id), or whose uv is not finite, is empty: zeros out, nothing
         read from the texture through it, no gradient.  Differentiable w.r.t. ``tex`` and ``uv`` (``TextureFunction``); through
-        ``uv``, ``interpolate``'s and ``rasterize``'s backwards carry the gradient on to the UV table and to ``verts``."""
+        ``uv``, ``interpolate``'s and ``rasterize``'s backwards carry the gradient on to the UV table and to ``verts``.
+
+        ``filter_mode="linear-mipmap-linear"`` needs ``uv_da`` (B,H,W,L,4) float32 = (du/dX, dv/dX, du/dY, dv/dY), the UV
+        footprint of each slot's pixel: ``torch.cat([interpolate(render_layers, dbary_dx, uv_table, uv_faces),
+        interpolate(render_layers, dbary_dy, uv_table, uv_faces)], -1)`` of ``bary_derivatives``' outputs.  With r2 = the larger
+        squared length of the two footprint vectors in texels, the level of detail is 0.5 log2(r2) with the mantissa taken
+        linearly (0 where r2 <= 1: at most 0.043 levels below the exact logarithm, include/dm2_hip.h), and the slot blends the
+        bilinear samples of the two levels of ``texture_mipmaps``' chain round it; at or below level 0 the result is
+        "linear"'s, to the bit, beyond the last level the last level's.  ``mip``: that chain for ``tex`` and ``max_mip_level``
+        (RuntimeError where its shape does not match them); None builds it here, so that the texture's gradient flows through
+        ``MipmapFunction``.  A slot whose ``uv_da`` is not finite is empty as well.  Differentiable w.r.t. ``tex``, ``mip`` and
+        ``uv`` (``TextureMipFunction``); ``uv_da`` gets no gradient: the level of detail is a constant of the op.  ValueError
+        for the mode without ``uv_da``, and for ``uv_da`` or ``mip`` with another mode."""
         i32, f32 = torch.int32, torch.float32
         rl = None if render_layers is None else render_layers.to(i32)
+        if filter_mode == "linear-mipmap-linear":
+            if uv_da is None:
+                raise ValueError('filter_mode "linear-mipmap-linear" needs uv_da')
+            tex = tex.to(f32)
+            if mip is None:
+                mip = MipmapFunction.apply(tex, max_mip_level)
+            return TextureMipFunction.apply(uv.to(f32), uv_da.to(f32), tex, mip.to(f32), rl, boundary_mode, max_mip_level)
+        if uv_da is not None or mip is not None:
+            raise ValueError('uv_da and mip belong to filter_mode "linear-mipmap-linear"')
         return TextureFunction.apply(uv.to(f32), tex.to(f32), rl, filter_mode, boundary_mode)
+
+    def texture_mipmaps(self, tex: torch.Tensor, max_mip_level: int = None):
+        """The mip chain of a texture (not in the reference): tex (Ht,Wt,C) float32 or (B,Ht,Wt,C) -> mip (T,C) or (B,T,C)
+        float32.  Level 0 is ``tex`` itself and is not copied; level k+1 exists while both extents of level k are even and
+        k < ``max_mip_level`` (None: no limit), has half the extents, and each of its texels is the mean of its 2 x 2 parents,
+        ((p00 + p10) + (p01 + p11)) * 0.25.  ``mip`` holds levels 1 .. nlev-1 one after the other, each (H_k, W_k, C)
+        row-major (``_C.mip_layout``); T = 0 when no level can be built (an odd extent).  Differentiable w.r.t. ``tex``
+        (``MipmapFunction``): the backward is a gather, deterministic."""
+        return MipmapFunction.apply(tex.to(torch.float32), max_mip_level)
+
+    def bary_derivatives(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
+                         patch_min: torch.Tensor = None):
+        """The footprint of a pixel on each listed face (not in the reference): render_layers (B,H,W,L) int32 face ids (as
+        ``rasterize`` returns them, or hand-built), verts (P,3), faces (F,3) -> (dbary_dx, dbary_dy), each (B,H,W,L,3)
+        float32: the derivatives of the slot's perspective-correct barycentrics (``rasterize``'s bary, unclamped) with respect
+        to the pixel's x and y position in pixels.  Each goes into ``interpolate`` as its ``bary``: ``interpolate`` is linear
+        in ``bary``, so ``interpolate(render_layers, dbary_dx, uv_table, uv_faces)`` is (du/dX, dv/dX).
+
+        Computed from the cameras' inv(mv), inv(proj) (the block ``Renderer(analytic_rays=True)`` keeps; a Renderer with ray
+        tensors builds the selected views' rows here) and the vertices: neither the ray tensors nor ``bary`` are read.  A slot
+        whose id is outside [0, F), or whose face names a vertex outside [0, P), is empty: zeros; zeros too where the ray
+        lies in the face's plane.  Not differentiable (``BaryDerivativesFunction`` marks both outputs so): the footprint is
+        a constant of the pipeline, as nothing flows through which faces are listed.
+
+        Window: with ``patch_min`` (B,2) int32, render_layers is a window's and slot (b, y, x) is frame pixel
+        (x + patch_min[b,0], y + patch_min[b,1]): the crop of the full-frame result.  Checks and errors are ``coverage``'s; an
+        empty window launches nothing."""
+        i32, f32 = torch.int32, torch.float32
+        if render_layers.dim() != 4:
+            raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+        pm_dev = None
+        if patch_min is not None:
+            pm_dev, _ = self._window(batch_mvp_idx, patch_min, render_layers.shape[2], render_layers.shape[1], verts.device)
+        elif tuple(render_layers.shape[1:3]) != (self.height, self.width):
+            raise ValueError(f"render_layers must cover the {self.width} x {self.height} frame (or come with patch_min), "
+                             f"got {tuple(render_layers.shape)}")
+        if render_layers.numel() == 0:
+            z = torch.empty(tuple(render_layers.shape) + (3,), dtype=f32, device=verts.device)
+            return z, z.clone()
+        with torch.no_grad():
+            if getattr(self, "analytic_rays", False):
+                cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
+                cam = self.ray_cam[cams]
+            else:
+                idx = list(batch_mvp_idx)
+                cam = torch.cat((torch.inverse(self.mv[idx]).reshape(-1, 16), torch.inverse(self.proj[idx]).reshape(-1, 16)), dim=1)
+            cam = cam.to(device=verts.device, dtype=f32).contiguous()
+        with _C.window(pm_dev, self.width, self.height):
+            return BaryDerivativesFunction.apply(render_layers.to(i32), verts.to(f32), faces.to(i32), cam)
 
     def composite(self, values: torch.Tensor, alpha: torch.Tensor, render_layers: torch.Tensor = None,
                   background: torch.Tensor = None):
@@ -754,6 +828,77 @@ class TextureFunction(torch.autograd.Function):
         render_layers = ctx.saved_tensors[2] if ctx.has_layers else None
         dtex, duv = _C.texture_backward_cuda(uv, tex, render_layers, *ctx.modes, grad_out, need_tex, need_uv)
         return duv, dtex, None, None, None
+
+
+class BaryDerivativesFunction(torch.autograd.Function):
+    """(dbary_dx, dbary_dy) = the derivatives of each listed slot's barycentrics with respect to the pixel position
+    (``_C.bary_derivatives_cuda``).
+
+    Inputs: render_layers (B,H,W,L) int32, verts (P,3), faces (F,3) int32, ray_cam (B,32) = inv(mv), inv(proj) per view.  Outputs:
+    two (B,H,W,L,3) tensors, both marked non-differentiable: the footprint is a constant of the pipeline (nothing flows to
+    ``verts`` through it, as nothing flows through which faces are listed)."""
+
+    @staticmethod
+    def forward(ctx, render_layers, verts, faces, ray_cam):
+        dx, dy = _C.bary_derivatives_cuda(render_layers, verts.detach(), faces, ray_cam.detach())
+        ctx.mark_non_differentiable(dx, dy)
+        return dx, dy
+
+    @staticmethod
+    def backward(ctx, grad_dx, grad_dy):
+        return None, None, None, None
+
+
+class MipmapFunction(torch.autograd.Function):
+    """mip = the chain of 2 x 2 means of a texture (``_C.texture_mipmaps_cuda``).
+
+    Inputs: tex (Ht,Wt,C)* or (B,Ht,Wt,C)*, max_mip_level (int or None).  Output: mip (T,C) or (B,T,C), levels 1 .. nlev-1.
+    (* = receives a gradient.)  Every texel of dL/dtex is the sum over the levels of 0.25^k times the gradient of the level-k
+    texel above it: a gather, deterministic."""
+
+    @staticmethod
+    def forward(ctx, tex, max_mip_level):
+        ctx.max_mip_level = max_mip_level
+        ctx.save_for_backward(tex.detach())
+        return _C.texture_mipmaps_cuda(tex.detach(), max_mip_level)
+
+    @staticmethod
+    def backward(ctx, grad_mip):
+        if grad_mip is None or not ctx.needs_input_grad[0]:
+            return None, None
+        (tex,) = ctx.saved_tensors
+        return _C.texture_mipmaps_backward_cuda(tex, ctx.max_mip_level, grad_mip), None
+
+
+class TextureMipFunction(torch.autograd.Function):
+    """out = the trilinear sample of a texture and its mip chain at each slot's uv (``_C.texture_mip_cuda``): the bilinear
+    samples c_j, c_{j+1} of the two levels round the slot's level of detail, c_j + f (c_{j+1} - c_j); one level at or below
+    level 0 and beyond the last.
+
+    Inputs: uv (B,H,W,L,2)*, uv_da (B,H,W,L,4), tex (Ht,Wt,C)* or (B,Ht,Wt,C)*, mip (T,C)* or (B,T,C)*, render_layers (B,H,W,L)
+    int32 or None, boundary_mode, max_mip_level.  Output: out (B,H,W,L,C).  (* = receives a gradient.)  A non-empty slot sends
+    (1 - f) w_pq g and f w_pq g to the texels of its two levels (level 0's in tex, the others in mip) and the blend of the two
+    levels' finite differences . g to (u, v); uv_da gets none: the level of detail is a constant of the op.  Only the gradients
+    ``needs_input_grad`` asks for are computed."""
+
+    @staticmethod
+    def forward(ctx, uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level):
+        out = _C.texture_mip_cuda(uv.detach(), uv_da.detach(), tex.detach(), mip.detach(), render_layers, boundary_mode, max_mip_level)
+        ctx.modes = (boundary_mode, max_mip_level)
+        ctx.has_layers = render_layers is not None
+        ctx.save_for_backward(uv.detach(), uv_da.detach(), tex.detach(), mip.detach(), *((render_layers,) if ctx.has_layers else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_uv, need_tex, need_mip = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if grad_out is None or not (need_uv or need_tex or need_mip):
+            return (None,) * 7
+        uv, uv_da, tex, mip = ctx.saved_tensors[:4]
+        render_layers = ctx.saved_tensors[4] if ctx.has_layers else None
+        dtex, dmip, duv = _C.texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, *ctx.modes, grad_out, need_tex, need_mip,
+                                                       need_uv)
+        return duv, None, dtex, dmip, None, None, None
 
 
 class CompositeFunction(torch.autograd.Function):

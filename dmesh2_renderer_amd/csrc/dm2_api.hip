@@ -636,6 +636,102 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
     return 0;
 }
 
+int dm2_bary_derivatives_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, const dm2_window* win,
+                                const int32_t* render_layers, const float* verts, const int32_t* faces, const float* ray_cam,
+                                float* dbary_dx, float* dbary_dy, void* stream) {
+    if (B < 0 || H < 0 || W < 0 || L < 0 || P < 0 || F < 0) return fail("bary_derivatives: negative size");
+    const int64_t per_view = (int64_t)H * W * L;
+    if (B > 65535 || (per_view + 255) / 256 > 0x7FFFFFFF) return fail("bary_derivatives: too many slots or views");
+    if (win && (win->full_W < W || win->full_H < H)) return fail("bary_derivatives: the window is larger than its frame");
+    const int64_t S = (int64_t)B * per_view;
+    if (S == 0) return 0;
+    if (!dbary_dx || !dbary_dy) return fail("bary_derivatives: the outputs must not be null");
+    if (F == 0 || P == 0) {                                              // every slot is empty
+        DM2_HIP(hipMemsetAsync(dbary_dx, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
+        DM2_HIP(hipMemsetAsync(dbary_dy, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
+    if (!render_layers || !verts || !faces || !ray_cam) return fail("bary_derivatives: inputs must not be null");
+    dm2::launch_bary_derivatives(B, H, W, L, P, F, win ? win->full_W : W, win ? win->full_H : H, win ? win->patch_min : nullptr,
+                                 render_layers, verts, faces, ray_cam, dbary_dx, dbary_dy, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+// the chain of (Ht, Wt, C) under max_mip_level: sizes that the kernels' 32-bit texel indices and launch grids hold
+static int check_mip_sizes(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, int64_t* T) {
+    if (NB < 0 || NB > 65535) return fail("texture_mip: the number of textures must lie in [0, 65535]");
+    if (Ht < 1 || Wt < 1) return fail("texture_mip: Ht and Wt must be at least 1");
+    if (C < 1) return fail("texture_mip: C must be at least 1");
+    dm2::mip_levels(Ht, Wt, max_mip_level, T);
+    if ((int64_t)Ht * Wt + *T > 0x7FFFFFFF) return fail("texture_mip: the texels of all levels must number below 2^31");
+    if (((int64_t)Ht * Wt * C + 255) / 256 > 0x7FFFFFFF) return fail("texture_mip: texture too large");
+    return 0;
+}
+
+int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* tex, float* mip,
+                        void* stream) {
+    int64_t T;
+    if (check_mip_sizes(NB, Ht, Wt, C, max_mip_level, &T)) return 1;
+    if (NB == 0 || T == 0) return 0;
+    if (!tex || !mip) return fail("texture_mipmaps: tex and mip must not be null");
+    dm2::launch_texture_mipmaps(NB, Ht, Wt, C, max_mip_level, tex, mip, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_texture_mipmaps_backward(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* dL_dmip,
+                                 float* dL_dtex, void* stream) {
+    int64_t T;
+    if (check_mip_sizes(NB, Ht, Wt, C, max_mip_level, &T)) return 1;
+    if (NB == 0) return 0;
+    if (!dL_dtex) return fail("texture_mipmaps_backward: dL_dtex must not be null");
+    if (T == 0) {                                                        // no level depends on tex
+        DM2_HIP(hipMemsetAsync(dL_dtex, 0, (size_t)NB * Ht * Wt * C * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
+    if (!dL_dmip) return fail("texture_mipmaps_backward: dL_dmip must not be null");
+    dm2::launch_texture_mipmaps_backward(NB, Ht, Wt, C, max_mip_level, dL_dmip, dL_dtex, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+static int check_texture_mip_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t boundary,
+                                   int32_t max_mip_level, int64_t* T) {
+    if (check_texture_sizes(B, H, W, L, Ht, Wt, C, DM2_TEX_FILTER_LINEAR, boundary)) return 1;
+    return check_mip_sizes(B, Ht, Wt, C, max_mip_level, T);
+}
+
+int dm2_texture_mip(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                    int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv, const float* uv_da,
+                    const float* tex, const float* mip, float* out, void* stream) {
+    int64_t T;
+    if (check_texture_mip_sizes(B, H, W, L, Ht, Wt, C, boundary, max_mip_level, &T)) return 1;
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!uv || !uv_da || !tex || !out) return fail("texture_mip: uv, uv_da, tex and out must not be null");
+    if (T > 0 && !mip) return fail("texture_mip: mip must not be null");
+    dm2::launch_texture_mip(B, H, W, L, Ht, Wt, C, view_textures, boundary, max_mip_level, render_layers, uv, uv_da, tex, mip, out,
+                            (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_texture_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                             int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv,
+                             const float* uv_da, const float* tex, const float* mip, const float* dL_dout, float* dL_dtex,
+                             float* dL_dmip, float* dL_duv, void* stream) {
+    int64_t T;
+    if (check_texture_mip_sizes(B, H, W, L, Ht, Wt, C, boundary, max_mip_level, &T)) return 1;
+    if (T == 0) dL_dmip = nullptr;                                       // an empty chain: nothing to add into
+    if ((int64_t)B * H * W * L == 0 || (!dL_dtex && !dL_dmip && !dL_duv)) return 0;
+    if (!uv || !uv_da || !dL_dout) return fail("texture_mip_backward: uv, uv_da and dL_dout must not be null");
+    if (dL_duv && (!tex || (T > 0 && !mip))) return fail("texture_mip_backward: tex and mip must not be null");
+    dm2::launch_texture_mip_backward(B, H, W, L, Ht, Wt, C, view_textures, boundary, max_mip_level, render_layers, uv, uv_da, tex,
+                                     mip, dL_dout, dL_dtex, dL_dmip, dL_duv, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_composite_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C, int32_t F, int32_t alpha_mode) {
     if (B < 0 || H < 0 || W < 0 || L < 0 || F < 0) return fail("composite: negative size");
     if (C < 1 || C > (1 << 20)) return fail("composite: C must lie in [1, 2^20]");

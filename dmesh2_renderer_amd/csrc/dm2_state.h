@@ -272,6 +272,25 @@ void launch_coverage(int B, int H, int W, int L, int P, int F, float temperature
 void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float temperature, const int32_t* patch_min, const int32_t* render_layers,
                               const float* verts_image, const int32_t* faces, const float* dL_dcov, float* dL_dverts_image,
                               hipStream_t st);
+// Renderer.bary_derivatives (dm2_bary_derivatives.hip): every element of both outputs is written.  B * H * W * L > 0; H, W: the
+// arrays' own extents, full_W, full_H: the frame of the cameras; patch_min as for launch_coverage; ray_cam (B,32).
+void launch_bary_derivatives(int B, int H, int W, int L, int P, int F, int full_W, int full_H, const int32_t* patch_min,
+                             const int32_t* render_layers, const float* verts, const int32_t* faces, const float* ray_cam,
+                             float* dbary_dx, float* dbary_dy, hipStream_t st);
+// Renderer.texture_mipmaps / texture(filter_mode="linear-mipmap-linear") (dm2_texture_mip.hip).  mip_levels: 1 + the levels
+// built for (Ht, Wt) under max_level (< 0: no limit), *T the chain's texels.  NB textures (1 shared, B per view); every element
+// of mip / dL_dtex (mipmaps), out / dL_duv (sampling) is written; the sampling's backward adds into dL_dtex and dL_dmip; any of
+// its three output pointers may be NULL.  mip may be NULL when the chain is empty.
+int mip_levels(int Ht, int Wt, int max_level, int64_t* T);
+void launch_texture_mipmaps(int NB, int Ht, int Wt, int C, int max_level, const float* tex, float* mip, hipStream_t st);
+void launch_texture_mipmaps_backward(int NB, int Ht, int Wt, int C, int max_level, const float* dL_dmip, float* dL_dtex, hipStream_t st);
+void launch_texture_mip(int B, int H, int W, int L, int Ht, int Wt, int C, int view_textures, int boundary, int max_level,
+                        const int32_t* render_layers, const float* uv, const float* uv_da, const float* tex, const float* mip,
+                        float* out, hipStream_t st);
+void launch_texture_mip_backward(int B, int H, int W, int L, int Ht, int Wt, int C, int view_textures, int boundary, int max_level,
+                                 const int32_t* render_layers, const float* uv, const float* uv_da, const float* tex,
+                                 const float* mip, const float* dL_dout, float* dL_dtex, float* dL_dmip, float* dL_duv,
+                                 hipStream_t st);
 
 }  // namespace dm2
 

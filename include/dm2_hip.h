@@ -428,6 +428,80 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
                          int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex,
                          const float* dL_dout, float* dL_dtex, float* dL_duv, void* stream);
 
+/* Renderer.bary_derivatives: the footprint of a pixel on each listed face.  render_layers (B,H,W,L) int32, verts (P,3) float32,
+ * faces (F,3) int32, ray_cam (B,32) float32 = inv(mv) (16, row-major) then inv(proj) (16) of each view, the camera block of
+ * DM2_FLAG_ANALYTIC_RAYS; dbary_dx, dbary_dy (B,H,W,L,3) float32 = the derivatives of the slot's perspective-correct barycentrics
+ * (1 - u - v, u, v) (dm2_rasterize_run's bary, unclamped) with respect to the pixel's x and y position in pixels.  The layout is
+ * dm2_interpolate's bary: dm2_interpolate is linear in bary, so interpolating with dbary_dx gives d(attribute)/dX.
+ * The unnormalised ray direction is affine in the pixel position, and u, v do not change when it is scaled.  Per slot of
+ * view b at window pixel (x, y), frame pixel (X, Y) = (x, y) + patch_min[b] (win NULL: the full frame, full_W = W, full_H = H),
+ * imv = ray_cam[b], ipr = ray_cam[b] + 16, all fp32, separate multiplies and adds in the written order, without contraction, dot =
+ * (x x + y y) + z z, cross as in ray_tri_intersection (bit-exact):
+ *   h    = (((X + 0.5f) / full_W * 2.0f) - 1.0f, ((Y + 0.5f) / full_H * 2.0f) - 1.0f, -1.0f, 1.0f)
+ *   v_j  = ((h0 * ipr[4j] + h1 * ipr[4j+1]) + h2 * ipr[4j+2]) + h3 * ipr[4j+3],   j = 0..3
+ *   w_k  = ((v0 * imv[4k] + v1 * imv[4k+1]) + v2 * imv[4k+2]) + v3 * imv[4k+3],   k = 0..2
+ *   ro   = (imv[3], imv[7], imv[11]),   D = w - ro                          (analytic_ray's direction before it is normalised)
+ *   gX_k = (2.0f / full_W) * (((imv[4k] * ipr[0] + imv[4k+1] * ipr[4]) + imv[4k+2] * ipr[8]) + imv[4k+3] * ipr[12])     (= dD/dX)
+ *   gY_k = (2.0f / full_H) * (((imv[4k] * ipr[1] + imv[4k+1] * ipr[5]) + imv[4k+2] * ipr[9]) + imv[4k+3] * ipr[13])     (= dD/dY)
+ *   T = ro - p0, E1 = p1 - p0, E2 = p2 - p0 (p_k = verts[faces[f][k]]),  a = cross(E2, T), b = cross(T, E1), c = cross(E2, E1)
+ *   Dc = dot(D, c),  r = 1.0f / Dc (the one reciprocal),  u = dot(D, a) * r,  v = dot(D, b) * r
+ *   du = (dot(gX, a) - u * dot(gX, c)) * r,  dv = (dot(gX, b) - v * dot(gX, c)) * r,  dbary_dx[s] = (-(du + dv), du, dv)
+ * and dbary_dy likewise with gY.  A slot is empty when its id is outside [0, F) or its face names a vertex outside [0, P); an
+ * empty slot and a slot with Dc == 0 give zeros.  The kernel reads neither ray tensors nor bary.  Every element of both
+ * outputs is written.  No backward: the footprint is a constant of the pipeline. */
+int dm2_bary_derivatives_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F,
+                                const dm2_window* win /* NULL: full frame */, const int32_t* render_layers, const float* verts,
+                                const int32_t* faces, const float* ray_cam, float* dbary_dx, float* dbary_dy, void* stream);
+
+/* Renderer.texture_mipmaps: the mip chain of NB textures tex (NB,Ht,Wt,C) float32 (NB = 1: a shared texture).  Level 0 is tex
+ * itself and is not copied.  Level k+1 exists while both extents of level k are even and k < max_mip_level (max_mip_level < 0: no
+ * limit); its extents are (H_k / 2, W_k / 2) and each texel is, in fp32 in this order,
+ *   ((p00 + p10) + (p01 + p11)) * 0.25f,   p_pq = level_k[2j + q][2i + p]
+ * nlev = 1 + the levels built (2048 x 2048: 12; 16 x 8: 4, ending at 2 x 1; 6 x 10: 2; 5 x 7: 1).  mip (NB,T,C): levels
+ * 1 .. nlev-1 concatenated per texture, each (H_k, W_k, C) row-major; T = their texels (0 when nlev == 1: nothing runs).
+ * Ht * Wt + T < 2^31.  Bit-exact; every element of mip is written. */
+int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* tex, float* mip,
+                        void* stream);
+/* Gradient of dm2_texture_mipmaps for upstream dL_dmip (NB,T,C): every texel of dL_dtex (NB,Ht,Wt,C) is written as
+ *   sum_{k = 1 .. nlev-1} 0.25^k * dL_dmip_k[j >> k][i >> k]      (acc = acc + w_k * g_k, k ascending)
+ * a gather: no atomics, a pure function of the inputs (zeros when nlev == 1). */
+int dm2_texture_mipmaps_backward(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* dL_dmip,
+                                 float* dL_dtex, void* stream);
+
+/* Renderer.texture(filter_mode="linear-mipmap-linear"): trilinear sampling.  uv, tex, render_layers, out, view_textures and
+ * boundary as for dm2_texture; uv_da (B,H,W,L,4) float32 = (du/dX, dv/dX, du/dY, dv/dY), the UV footprint of the slot's pixel
+ * (dm2_interpolate of dm2_bary_derivatives_window's outputs); mip: dm2_texture_mipmaps' chain of tex under the same
+ * max_mip_level, (T,C) or, with view_textures, (B,T,C) (may be NULL when T == 0).  Per slot s, all fp32 in the written order:
+ *   empty: the slot is empty by dm2_texture's rules evaluated at level 0, or any of its four uv_da is not finite:
+ *     out[s,:] = 0, nothing is read from tex or mip through it, no gradient;
+ *   footprint: ax = dudX * (float)Wt, bx = dvdX * (float)Ht, sx = ax * ax + bx * bx; sy likewise from (dudY, dvdY); r2 = max(sx, sy);
+ *   level of detail: r2 <= 1: lod = 0; otherwise r2 = m * 2^e with m in [1, 2) read from the float's bits (e = the biased
+ *     exponent - 127, m = the mantissa bits under exponent 0; r2 = infinity: e = 128, m = 1) and
+ *         lod = 0.5f * ((float)e + (m - 1.0f))
+ *     log2 with the mantissa taken linearly: no transcendental, so the forward is a pure function of IEEE operations.  lod never
+ *     exceeds 0.5 log2(r2) and falls short of it by at most 0.5 (log2(1 / ln 2) - (1 / ln 2 - 1)) = 0.04304 levels;
+ *   blend: lod <= 0: level 0 alone (bit-equal to DM2_TEX_FILTER_LINEAR); lod >= nlev - 1: the last level alone; otherwise
+ *     j = (int)floorf(lod), f = lod - (float)j, out[s,c] = c_j + f * (c_{j+1} - c_j)
+ *     c_k = dm2_texture's linear sample of level k: taps from x_k = u * (float)W_k - 0.5f, y_k = v * (float)H_k - 0.5f, the
+ *     boundary mode's addressing with that level's extents, a + fy * (b - a).
+ * Every element of out is written. */
+int dm2_texture_mip(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                    int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv, const float* uv_da,
+                    const float* tex, const float* mip, float* out, void* stream);
+/* Gradients of dm2_texture_mip for upstream g = dL_dout (B,H,W,L,C): the derivative of the fp32 function above at its own lod, j,
+ * f, fractions and addresses.  The level of detail is a constant of the op: uv_da gets no gradient.  Per non-empty slot, with
+ * (m_j, m_{j+1}) = (1 - f, f) (one level: weight 1 on it):
+ *   dL_dtex / dL_dmip[t_pq of level k, c] += m_k * w_pq * g[s,c], w as in dm2_texture_backward: level 0's texels in dL_dtex
+ *     (tex's shape), the others in dL_dmip (mip's shape); both zero-filled by the caller; float atomics;
+ *   dL_duv[s] = m_j * duv_j + m_{j+1} * duv_{j+1},  duv_k = dm2_texture_backward's dL_duv of level k with its own W_k, H_k
+ *     factors; zeros in an empty slot; every element is written; a pure function of the inputs.
+ * Any of the three output pointers may be NULL (not wanted; a kernel none of whose outputs is wanted is not launched; tex and
+ * mip may be NULL when dL_duv is). */
+int dm2_texture_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
+                             int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv,
+                             const float* uv_da, const float* tex, const float* mip, const float* dL_dout, float* dL_dtex,
+                             float* dL_dmip, float* dL_duv, void* stream);
+
 /* Renderer.composite: per-slot values (dm2_interpolate's or dm2_texture's output, or anything shaded from them) blended front
  * to back into an image: LayeredRenderer.render's blend with the colour supplied by the caller.
  * values (B,H,W,L,C) float32, C >= 1; alpha float32: (B,H,W,L), one opacity per slot (DM2_COMPOSITE_ALPHA_PER_SLOT), or (F), one

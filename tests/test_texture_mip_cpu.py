@@ -1,0 +1,186 @@
+"""The restatement of the mip chain and of trilinear sampling (tests/texture_mip_ref.py), without a GPU: the level of detail
+against the exact logarithm, level 0 against texture_ref, the chain's layout and adjoint, grads64 against finite differences,
+what the inputs of the GPU tests reach, and what the feature is for (a minified checkerboard)."""
+import numpy as np
+import pytest
+
+import texture_mip_ref as mref
+import texture_ref as tref
+
+from dmesh2_renderer_amd import _C
+
+f32 = np.float32
+SHAPE = (2, 20, 24, 3)
+TEXTURES = ((16, 8), (8, 8), (6, 10), (5, 7))            # (Ht, Wt): nlev 4, 4, 2, 1
+
+
+def test_layout():
+    for (Ht, Wt, mx), (nlev, T) in {(2048, 2048, None): (12, (4 ** 11 - 1) // 3), (16, 8, None): (4, 32 + 8 + 2), (6, 10, None): (2, 15),
+                                    (5, 7, None): (1, 0), (16, 8, 1): (2, 32), (16, 8, 0): (1, 0)}.items():
+        n, levels, t = mref.layout(Ht, Wt, mx)
+        assert (n, t) == (nlev, T), (Ht, Wt, mx, n, t)
+        assert (n, levels, t) == _C.mip_layout(Ht, Wt, mx)
+        off = 0
+        for k in range(1, n):
+            assert levels[k] == (Ht >> k, Wt >> k, off)
+            off += levels[k][0] * levels[k][1]
+    assert mref.layout(16, 8)[1][-1][:2] == (2, 1)
+    with pytest.raises(ValueError):
+        _C.mip_layout(8, 8, -1)
+
+
+def test_lod_against_the_exact_logarithm():
+    """lod = 0.5 (e + (m - 1)) never exceeds 0.5 log2(r2) and falls short of it by at most 0.04304 levels: e + (m - 1) and
+    m - 1 are exact in float32, the sum and the halving round once, so lod carries at most half an ulp of itself."""
+    rng = np.random.RandomState(3)
+    s = (2.0 ** rng.uniform(0.0, 20.0, 200_000)).astype(f32)
+    da = np.stack([s, np.zeros_like(s), np.zeros_like(s), np.zeros_like(s)], -1)
+    lod, r2 = mref.lod32(da, 1, 1)
+    keep = r2 > 1
+    exact = 0.5 * np.log2(r2[keep].astype(np.float64))
+    err = exact - lod[keep].astype(np.float64)
+    print("lod shortfall: min", err.min(), "max", err.max())
+    assert (err >= -lod[keep] * 2.0 ** -24).all() and err.max() <= 0.0431
+    assert err.max() > 0.0429 and abs(mref.LOD_SHORTFALL - 0.04304) < 1e-5     # (the bound is reached)
+    # the other axis, the larger of the two, and r2 <= 1
+    assert mref.lod32(np.array([[0.1, 0.2, 3.0, 4.0]], f32), 1, 1)[0][0] == f32(0.5) * (f32(4) + (f32(25.0 / 16) - f32(1)))
+    assert mref.lod32(np.array([[0.5, 0.5, 0.25, 0.1]], f32), 1, 1)[0][0] == 0 and mref.lod32(np.array([[1, 0, 0, 0]], f32), 1, 1)[0][0] == 0
+    assert mref.lod32(np.array([[1e30, 0, 0, 0]], f32), 1, 1)[0][0] == 64.0    # r2 = infinity: e = 128, m = 1
+
+
+@pytest.mark.parametrize("size", TEXTURES)
+def test_inputs_reach_every_branch(size):
+    uv, da, rl = mref.case(SHAPE, *size, seed=11)
+    r = mref.reach(uv, da, *size, rl)
+    print(size, r)
+    nlev = mref.layout(*size)[0]
+    assert r["magnified"] > 0 and r["empty_id"] > 0 and r["empty_uv"] > 0 and r["empty_da"] > 0
+    assert len(r["pairs"]) == nlev - 1 and all(n > 0 for n in r["pairs"])
+    assert r["beyond"] > 0                                                  # (one level: every minified slot)
+    r1 = mref.reach(uv, da, 16, 8, rl, max_mip_level=1)
+    assert len(r1["pairs"]) == 1 and r1["pairs"][0] > 0 and r1["beyond"] > 0
+
+
+@pytest.mark.parametrize("boundary_mode", mref.BOUNDARIES)
+def test_level_zero_is_the_linear_filter(boundary_mode):
+    """Where lod <= 0 the result is texture_ref.forward32(..., "linear")'s, to the bit."""
+    rng = np.random.default_rng(5)
+    for size in TEXTURES:
+        uv, da, rl = mref.case(SHAPE, *size, seed=12)
+        tex = rng.standard_normal(size + (3,), dtype=f32)
+        mip = mref.mipmaps(tex)
+        st = mref.stage(uv, da, *size, rl)
+        low = ~st["empty"] & (st["lod"] <= 0)
+        assert low.sum() > 50
+        got = mref.forward32(uv, da, tex, mip, rl, boundary_mode)
+        want = tref.forward32(uv, tex, rl, "linear", boundary_mode)
+        assert np.array_equal(got[low].view(np.uint32), want[low].view(np.uint32))
+        assert not got[st["empty"]].any()
+        two = st["two"]
+        if two.any():
+            assert (got[two] != want[two]).any()
+
+
+def test_constant_texture_gives_the_constant_at_every_lod():
+    for size in TEXTURES:
+        uv, da, rl = mref.case(SHAPE, *size, seed=13)
+        tex = np.full((2,) + size + (2,), f32(0.7))
+        tex[1] = f32(-3.25)
+        mip = mref.mipmaps(tex)
+        assert mip.shape == (2, mref.layout(*size)[2], 2) and (mip[0] == f32(0.7)).all() and (mip[1] == f32(-3.25)).all()
+        out = mref.forward32(uv, da, tex, mip, rl, "wrap")
+        live = ~mref.stage(uv, da, *size, rl)["empty"]
+        assert (out[0][live[0]] == f32(0.7)).all() and (out[1][live[1]] == f32(-3.25)).all() and not out[~live].any()
+
+
+def test_chain_against_its_definition_and_adjoint():
+    rng = np.random.default_rng(6)
+    tex = rng.standard_normal((2, 16, 8, 3), dtype=f32)
+    mip = mref.mipmaps(tex)
+    l1, l2 = mref.level(tex, mip, 1), mref.level(tex, mip, 2)
+    for (b, j, i, c) in ((0, 0, 0, 0), (1, 7, 3, 2), (0, 3, 1, 1)):
+        want = ((tex[b, 2 * j, 2 * i, c] + tex[b, 2 * j, 2 * i + 1, c]) + (tex[b, 2 * j + 1, 2 * i, c] + tex[b, 2 * j + 1, 2 * i + 1, c])) * f32(0.25)
+        assert l1[b, j, i, c] == want
+    assert l2[1, 3, 1, 0] == ((l1[1, 6, 2, 0] + l1[1, 6, 3, 0]) + (l1[1, 7, 2, 0] + l1[1, 7, 3, 0])) * f32(0.25)
+    assert np.array_equal(mref.mipmaps(tex, 1), mip[:, :32]) and mref.mipmaps(tex, 0).shape == (2, 0, 3)
+    # the backward against the float64 sum: <g, mipmaps(t)> = <backward(g), t> for the linear map in float64, and texel by texel
+    g = rng.standard_normal(mip.shape)
+    t64 = rng.standard_normal(tex.shape)
+    back = mref.mipmaps_backward64(tex.shape, None, g)
+    lhs, rhs = (g * mref.mipmaps(t64, dtype=np.float64)).sum(), (back * t64).sum()
+    assert abs(lhs - rhs) <= 1e-12 * np.abs(g).sum()
+    _, levels, _ = mref.layout(16, 8)
+    j, i = 13, 6
+    want = sum(0.25 ** k * g[1, levels[k][2] + (j >> k) * levels[k][1] + (i >> k), 2] for k in range(1, 4))
+    assert abs(back[1, j, i, 2] - want) < 1e-15
+
+
+@pytest.mark.parametrize("per_view", [False, True])
+@pytest.mark.parametrize("boundary_mode", mref.BOUNDARIES)
+def test_grads64_against_finite_differences(boundary_mode, per_view):
+    """grads64 is the derivative of the float32 function at its own float32 stage.  In (tex, mip) that function is linear: a
+    directional difference of forward64 with the float32 fractions is exact up to float64 rounding.  In u (and v) it is piecewise
+    linear, so a central difference of step 1e-6 of forward64 with exact fractions is exact where no tap's fraction lies within
+    1e-3 of a texel's border (the kinks are left out) -- but its fractions differ from the float32 stage's by up to 2^-20 (half
+    an ulp of |x| < 32), and du/dx is linear in fy with a slope of the size of du/dx itself: 2^-18 of the largest gradient."""
+    size, C = (16, 8), 3
+    rng = np.random.default_rng(7)
+    uv, da, rl = mref.case(SHAPE, *size, seed=14)
+    tex = rng.standard_normal(((2,) if per_view else ()) + size + (C,), dtype=f32)
+    mip = mref.mipmaps(tex)
+    g = rng.standard_normal(SHAPE + (C,), dtype=f32)
+    dtex, dmip, duv = mref.grads64(uv, da, tex, mip, rl, boundary_mode, None, g)
+    st = mref.stage(uv, da, *size, rl)
+    assert dtex.shape == tex.shape and dmip.shape == mip.shape and np.abs(dtex).max() > 0 and np.abs(dmip).max() > 0
+    assert not duv[st["empty"]].any()
+    # (tex, mip): a random direction
+    dt, dm = rng.standard_normal(tex.shape), rng.standard_normal(mip.shape)
+    uv64 = np.where(st["empty"][..., None], 0.0, uv.astype(np.float64))
+    base = mref.forward64(uv, da, tex, mip, rl, boundary_mode, st=st, stage_dtype=f32)
+    moved = mref.forward64(uv, da, tex.astype(np.float64) + dt, mip.astype(np.float64) + dm, rl, boundary_mode, st=st, stage_dtype=f32)
+    lhs, rhs = (g * (moved - base)).sum(), (dtex * dt).sum() + (dmip * dm).sum()
+    assert abs(lhs - rhs) <= 1e-10 * (np.abs(dtex * dt).sum() + np.abs(dmip * dm).sum()), (lhs, rhs)
+    # uv: central differences per slot (the slots are independent)
+    h, margin = 1e-6, 1e-3
+    away = ~st["empty"]
+    for k in range(st["nlev"]):
+        Hk, Wk = size[0] >> k, size[1] >> k
+        used = (st["j"] == k) | (st["two"] & (st["j"] + 1 == k))
+        x, y = uv64[..., 0] * Wk - 0.5, uv64[..., 1] * Hk - 0.5
+        fx, fy = x - np.floor(x), y - np.floor(y)
+        near = (np.minimum(fx, 1 - fx) < margin) | (np.minimum(fy, 1 - fy) < margin)
+        away &= ~(used & near)
+    assert away.sum() > 0.9 * (~st["empty"]).sum()
+    for axis in range(2):
+        e = np.zeros(2); e[axis] = h
+        fd = (g * (mref.forward64(uv64 + e, da, tex, mip, rl, boundary_mode, st=st)
+                   - mref.forward64(uv64 - e, da, tex, mip, rl, boundary_mode, st=st))).sum(-1) / (2 * h)
+        err = np.abs(fd - duv[..., axis])[away]
+        scale = np.abs(duv[..., axis][away]).max()
+        assert scale > 0 and err.max() <= 2.0 ** -18 * scale, (axis, err.max(), scale)
+
+
+def test_minified_checkerboard_is_grey():
+    """What the feature is for: a 64 x 64 checkerboard of period two texels seen at about 8 texels per pixel.  Level 1 is exactly
+    0.5 everywhere, so every slot with lod >= 1 returns exactly 0.5; the bilinear filter on the same input returns whatever
+    four texels the sample falls between."""
+    n = 64
+    jj, ii = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    tex = ((ii + jj) % 2).astype(f32)[..., None]
+    mip = mref.mipmaps(tex)
+    assert (mip == f32(0.5)).all() and mip.shape == ((4 ** 6 - 1) // 3, 1)
+    rng = np.random.RandomState(8)
+    shape = (1, 16, 16, 1)
+    ys, xs = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
+    step = 8.0 / n                                                           # 8 texels per pixel
+    uv = np.stack([xs * step, ys * step], -1).reshape(shape + (2,)) + rng.uniform(0, step, shape + (2,))   # jittered offsets
+    uv = uv.astype(f32)
+    da = np.broadcast_to(np.array([step, 0, 0, step], f32), shape + (4,)).copy()
+    da *= rng.uniform(0.8, 1.25, shape + (1,)).astype(f32)
+    st = mref.stage(uv, da, n, n)
+    assert (st["lod"] >= 1).all() and not st["empty"].any()
+    out = mref.forward32(uv, da, tex, mip)
+    assert (out == f32(0.5)).all()
+    lin = tref.forward32(uv, tex, None, "linear", "wrap")
+    print("bilinear on the minified checkerboard spans", float(lin.min()), float(lin.max()))
+    assert lin.max() - lin.min() > 0.5
