@@ -1,6 +1,8 @@
 """Renderer.texture_mipmaps and texture(filter_mode="linear-mipmap-linear") on the GPU against the restatement
 (tests/texture_mip_ref.py): the chain and the trilinear forward bit-equal, every gradient within GRAD_TOL of float64; what
-needs_input_grad launches; unaligned tensors; argument checks; the module path from rasterize to verts.grad."""
+needs_input_grad launches; unaligned tensors; argument checks; the module path from rasterize to verts.grad.  Then off the
+beaten path: a channel and layer grid, the scatter table's overflow route and its opposite (every lane on a few keys), the
+branch points of the level of detail, the addressing's edges at every level, images smaller than a tile, max_mip_level."""
 import itertools
 
 import numpy as np
@@ -12,7 +14,8 @@ import composite_ref as cref
 import interpolate_ref as iref
 import rasterize_ref as rref
 import texture_mip_ref as mref
-from util import GRAD_TOL, rel_linf, scenes
+import texture_ref as tref
+from util import GRAD_TOL, rel_linf, scenes, table_capacity
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -36,6 +39,15 @@ def _cu(a):
 
 def _np(t):
     return None if t is None else t.detach().cpu().numpy()
+
+
+def _shifted(a):
+    """``a`` on the GPU as a view that starts 4 bytes into its storage: the four-channel reads do not apply."""
+    buf = torch.zeros(a.size + 1, dtype=torch.float32, device="cuda")
+    buf[1:] = _cu(a).reshape(-1)
+    v = buf[1:].view(a.shape)
+    assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+    return v
 
 
 def inputs(size):
@@ -213,20 +225,13 @@ def test_unaligned_tensors_give_the_same_bits(C):
     tex = rng.standard_normal((2,) + size + (C,), dtype=np.float32)
     mip = mref.mipmaps(tex)
     g = rng.standard_normal(SHAPE + (C,), dtype=np.float32)
-
-    def shifted(a):
-        buf = torch.zeros(a.size + 1, dtype=torch.float32, device="cuda")
-        buf[1:] = _cu(a).reshape(-1)
-        v = buf[1:].view(a.shape)
-        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
-        return v
     head, tail = (_cu(uv), _cu(da)), (_cu(rl), "wrap", None)
     out_a = _C.texture_mip_cuda(*head, _cu(tex), _cu(mip), *tail)
-    for t, m in ((shifted(tex), _cu(mip)), (_cu(tex), shifted(mip)), (shifted(tex), shifted(mip))):
+    for t, m in ((_shifted(tex), _cu(mip)), (_cu(tex), _shifted(mip)), (_shifted(tex), _shifted(mip))):
         assert torch.equal(_C.texture_mip_cuda(*head, t, m, *tail), out_a)
     assert np.array_equal(_bits(_np(out_a)), _bits(mref.forward32(uv, da, tex, mip, rl, "wrap")))
     ga = _C.texture_mip_backward_cuda(*head, _cu(tex), _cu(mip), *tail, _cu(g), True, True, True)
-    gu = _C.texture_mip_backward_cuda(*head, shifted(tex), shifted(mip), *tail, shifted(g), True, True, True)
+    gu = _C.texture_mip_backward_cuda(*head, _shifted(tex), _shifted(mip), *tail, _shifted(g), True, True, True)
     assert torch.equal(ga[2], gu[2])
     want = mref.grads64(uv, da, tex, mip, rl, "wrap", None, g)
     for a, u, w in zip(ga, gu, want):
@@ -359,3 +364,240 @@ def test_module_path_end_to_end():
     print("end to end: tex.grad", et, "uv table grad", ea, "verts.grad", ev)
     assert np.abs(wt).max() > 0 and np.abs(wtab).max() > 0 and np.abs(wv).max() > 0
     assert et <= GRAD_TOL and ea <= GRAD_TOL and ev <= GRAD_TOL
+
+
+# ---- off the beaten path: the input sets of texture_mip_ref beyond ``case``, each held to its condition by its twin in
+# tests/test_texture_mip_cpu.py ----
+
+GRID_CS = (2, 5, 7, 12, 16, 20, 33)                      # CH = 2; a chunk's tail; CV = 3, 4, 5 on the vector path, 33 on the scalar one
+GRID_LS = (1, 3, 8)
+GRID_TEXTURES = ((16, 8), (32, 32), (6, 10))
+
+
+def _check(uv, da, tex, mip, rl, boundary_mode, mx, g, what, zero=""):
+    """The forward bit-equal to forward32 and, with ``g``, dL/dtex, dL/dmip and dL/duv within GRAD_TOL of grads64 -> (out, (dt, dm,
+    du), (wt, wm, wu)).  ``zero``: the gradients ("t", "m", "u") that are all zeros in the reference by construction and must be
+    exactly zero; every other is non-zero in the reference."""
+    args = (_cu(uv), _cu(da), _cu(tex), _cu(mip), _cu(rl), boundary_mode, mx)
+    out = _np(_C.texture_mip_cuda(*args))
+    want = mref.forward32(uv, da, tex, mip, rl, boundary_mode, mx)
+    assert out.shape == want.shape and out.dtype == np.float32, what
+    assert np.array_equal(_bits(out), _bits(want)), (what, int((_bits(out) != _bits(want)).sum()))
+    if g is None:
+        return out, None, None
+    got = tuple(_np(x) for x in _C.texture_mip_backward_cuda(*args, _cu(g), True, True, True))
+    ref = mref.grads64(uv, da, tex, mip, rl, boundary_mode, mx, g)
+    errs = [rel_linf(a, b) for a, b in zip(got, ref)]
+    print(what, "dtex", errs[0], "dmip", errs[1], "duv", errs[2])
+    for name, a, b, e in zip("tmu", got, ref, errs):
+        assert a.shape == b.shape and np.isfinite(a).all(), (what, name)
+        if name in zero or not b.size:
+            assert not b.any() and not a.any(), (what, name)
+        else:
+            assert np.abs(b).max() > 0 and e <= GRAD_TOL, (what, name, e)
+    assert not got[2][mref.stage(uv, da, tex.shape[-3], tex.shape[-2], rl, mx)["empty"]].any(), what
+    return out, got, ref
+
+
+def _grid(k):
+    return GRID_CS[k // 2], bool(k % 2), GRID_LS[k % 3], GRID_TEXTURES[(k // 3) % 3]
+
+
+@pytest.mark.parametrize("k", range(2 * len(GRID_CS)))
+def test_channel_and_layer_grid(k):
+    """A thinned grid, both boundary modes at each point: every C, L, texture size and sharing appears."""
+    C, per_view, L, size = _grid(k)
+    shape = SHAPE[:3] + (L,)
+    uv, da, rl = mref.case(shape, *size, seed=11)
+    rng = np.random.default_rng(300 + k)
+    tex = rng.standard_normal(((2,) if per_view else ()) + size + (C,), dtype=np.float32)
+    mip = mref.mipmaps(tex)
+    g = rng.standard_normal(shape + (C,), dtype=np.float32)
+    for boundary_mode in mref.BOUNDARIES:
+        _check(uv, da, tex, mip, rl, boundary_mode, None, g, (k, C, per_view, L, size, boundary_mode))
+
+
+def test_grid_covers_every_axis():
+    seen = [set() for _ in range(4)]
+    for k in range(2 * len(GRID_CS)):
+        for s, v in zip(seen, _grid(k)):
+            s.add(v)
+    assert [len(s) for s in seen] == [len(GRID_CS), 2, len(GRID_LS), len(GRID_TEXTURES)]
+
+
+@pytest.mark.parametrize("boundary_mode", mref.BOUNDARIES)
+def test_forward_with_more_channels_than_lanes(boundary_mode):
+    """C = 260: 65 groups of four per slot on the vector path, and (unaligned) 260 single channels on the scalar one, more than
+    the block has lanes: the sweep's slot stays and its channel moves on by 256."""
+    shape, size, C = (1, 4, 5, 2), (16, 8), 260
+    uv, da, rl = mref.case(shape, *size, seed=17)
+    rng = np.random.default_rng(43)
+    tex = rng.standard_normal(size + (C,), dtype=np.float32)
+    mip = mref.mipmaps(tex)
+    out, _, _ = _check(uv, da, tex, mip, rl, boundary_mode, None, None, ("C = 260", boundary_mode))
+    slow = _C.texture_mip_cuda(_cu(uv), _cu(da), _shifted(tex), _shifted(mip), _cu(rl), boundary_mode, None)
+    assert np.array_equal(_bits(_np(slow)), _bits(out))
+
+
+@pytest.mark.parametrize("per_view", [False, True])
+@pytest.mark.parametrize("C", [3, 16])
+def test_table_overflow_route(C, per_view):
+    """A 512^2 texture under random uv and footprints of half a texel to eleven: every tile addresses several times the keys the
+    scatter's table holds (asserted), in both destination tensors; what finds no slot adds straight to dL/dtex or dL/dmip.
+    Asked for alone, each of the two is what it is when both are asked for, up to the order of the atomics."""
+    uv, da, rl = mref.overflow_case()
+    size, shape = mref.OVERFLOW_SIZE, mref.OVERFLOW_SHAPE
+    rng = np.random.default_rng(44 + C)
+    tex = rng.standard_normal(((2,) if per_view else ()) + size + (C,), dtype=np.float32)
+    mip = mref.mipmaps(tex)
+    g = rng.standard_normal(shape + (C,), dtype=np.float32)
+    for layers, boundary_mode in ((None, "wrap"), (rl, "clamp")):
+        least = mref.distinct_keys_per_tile(uv, da, *size, layers, boundary_mode)
+        print("distinct keys per tile and layer, at least", least)
+        assert least > table_capacity()
+        what = ("overflow", C, per_view, layers is not None, boundary_mode)
+        _, (dt, dm, du), (wt, wm, wu) = _check(uv, da, tex, mip, layers, boundary_mode, None, g, what)
+        args = (_cu(uv), _cu(da), _cu(tex), _cu(mip), _cu(layers), boundary_mode, None, _cu(g))
+        t_only = _C.texture_mip_backward_cuda(*args, True, False, False)
+        m_only = _C.texture_mip_backward_cuda(*args, False, True, False)
+        assert t_only[1] is None and t_only[2] is None and m_only[0] is None and m_only[2] is None
+        et, em = rel_linf(_np(t_only[0]), wt), rel_linf(_np(m_only[1]), wm)
+        ett, emm = rel_linf(_np(t_only[0]), dt), rel_linf(_np(m_only[1]), dm)
+        print(what, "tex alone", et, "against both", ett, "mip alone", em, "against both", emm)
+        assert et <= GRAD_TOL and em <= GRAD_TOL and ett <= GRAD_TOL and emm <= GRAD_TOL, (what, et, em, ett, emm)
+
+
+@pytest.mark.parametrize("C", [1, 3, 16])
+def test_magnified_every_lane_on_a_few_keys(C):
+    """Every slot magnified into one corner of an (8, 8) texture: at most 16 keys per tile (asserted), all of level 0."""
+    uv, da = mref.hot_case_magnified()
+    assert 0 < mref.distinct_keys_per_tile(uv, da, 8, 8, worst=max) <= 16
+    rng = np.random.default_rng(45)
+    for per_view in (False, True):
+        tex = rng.standard_normal(((2,) if per_view else ()) + (8, 8, C), dtype=np.float32)
+        g = rng.standard_normal(mref.HOT_SHAPE + (C,), dtype=np.float32)
+        _check(uv, da, tex, mref.mipmaps(tex), None, "wrap", None, g, ("magnified", C, per_view), zero="m")
+
+
+@pytest.mark.parametrize("C", [1, 3, 16])
+@pytest.mark.parametrize("size", [(8, 8), (16, 8)])
+def test_every_tap_on_the_top_level(size, C):
+    """Every slot far beyond the last level (one in eight by r2 = inf): all 28000 slots' taps on the top level's one or two
+    texels (asserted), nothing for the texture itself."""
+    uv, da = mref.hot_case_beyond(*size)
+    st = mref.stage(uv, da, *size)
+    assert not st["empty"].any() and not st["two"].any() and (st["j"] == st["nlev"] - 1).all() and (st["lod"] == 64).any()
+    rng = np.random.default_rng(46)
+    for per_view, boundary_mode in ((False, "wrap"), (True, "clamp")):
+        assert mref.distinct_keys_per_tile(uv, da, *size, None, boundary_mode, worst=max) == size[0] // 8
+        tex = rng.standard_normal(((2,) if per_view else ()) + size + (C,), dtype=np.float32)
+        g = rng.standard_normal(mref.HOT_SHAPE + (C,), dtype=np.float32)
+        _, (dt, dm, du), _ = _check(uv, da, tex, mref.mipmaps(tex), None, boundary_mode, None, g, ("beyond", size, C, per_view, boundary_mode),
+                                    zero="t" if size == (16, 8) else "tu")       # (one texel: no derivative in uv)
+        top = mref.layout(*size)[1][-1][2]
+        assert not dm[..., :top, :].any() and dm[..., top:, :].all()
+
+
+@pytest.mark.parametrize("boundary_mode", mref.BOUNDARIES)
+@pytest.mark.parametrize("size,mx", mref.EDGE_TEXTURES)
+def test_level_of_detail_edges(size, mx, boundary_mode):
+    """texture_mip_ref.lod_edge_footprints: r2 and lod on every branch point and on the floats next to it.  On top of the
+    restatement: lod <= 0 gives filter_mode="linear"'s bits; an integer lod between the ends gives the bits of level j alone,
+    and the level above receives exactly nothing from those slots."""
+    C = 3
+    uv, da = mref.lod_edge_case(*size, mx)
+    rng = np.random.default_rng(47)
+    tex = rng.standard_normal((2,) + size + (C,), dtype=np.float32)
+    mip = mref.mipmaps(tex, mx)
+    shape = (2,) + mref.EDGE_SHAPE[1:]
+    uv, da = np.concatenate([uv, uv]), np.concatenate([da, da])               # (per-view textures: the table under both)
+    g = rng.standard_normal(shape + (C,), dtype=np.float32)
+    what = ("lod edges", size, mx, boundary_mode)
+    out, _, _ = _check(uv, da, tex, mip, None, boundary_mode, mx, g, what)
+    st = mref.stage(uv, da, *size, None, mx)
+    low = st["lod"] <= 0
+    lin = _np(_C.texture_cuda(_cu(uv), _cu(tex), None, "linear", boundary_mode))
+    assert low.sum() >= 20 and np.array_equal(_bits(out[low]), _bits(lin[low])), what
+    _, levels, _ = mref.layout(*size, mx)
+    for k in range(1, st["nlev"] - 1):
+        whole = st["two"] & (st["f"] == 0) & (st["j"] == k)
+        assert whole.sum() >= 4, (what, k)
+        alone = tref.forward32(uv, mref.level(tex, mip, k, mx), None, "linear", boundary_mode)
+        assert np.array_equal(_bits(out[whole]), _bits(alone[whole])), (what, k)
+        gk = np.where(whole[..., None], g, np.float32(0))
+        dt, dm, du = (_np(x) for x in _C.texture_mip_backward_cuda(_cu(uv), _cu(da), _cu(tex), _cu(mip), None, boundary_mode, mx, _cu(gk),
+                                                                   True, True, True))
+        wt, wm, wu = mref.grads64(uv, da, tex, mip, None, boundary_mode, mx, gk)
+        h, w, off = levels[k]
+        assert np.abs(wm[:, off:off + h * w]).max() > 0 and not wm[:, off + h * w:].any() and not wm[:, :off].any() and not wt.any()
+        assert not dm[:, off + h * w:].any() and not dm[:, :off].any() and not dt.any(), (what, k)
+        assert rel_linf(dm, wm) <= GRAD_TOL and rel_linf(du, wu) <= GRAD_TOL, (what, k)
+
+
+@pytest.mark.parametrize("boundary_mode", mref.BOUNDARIES)
+@pytest.mark.parametrize("scale", mref.LATTICE_SCALES)
+def test_addressing_edges_at_every_level(scale, boundary_mode):
+    """uv on the lattice of 32nds from -40/32 to 72/32: texel centres and borders of every level of (16, 8), exactly 0 and 1,
+    negative remainders at the levels one texel wide; one footprint per case, so that every level and every pair is the one
+    sampled in turn.  Ten slots sit on the range rule: x = 2^24 - 2 (the largest a slot can have) and -(2^24 - 2) are live,
+    |x| = 2^24 is empty."""
+    size, C = mref.LATTICE_SIZE, 5
+    uv, da = mref.lattice_case(scale)
+    uv, live = mref.range_case(uv)
+    rng = np.random.default_rng(48)
+    tex = rng.standard_normal(size + (C,), dtype=np.float32)
+    tex[3, 2, :] = -0.0
+    g = rng.standard_normal(mref.LATTICE_SHAPE + (C,), dtype=np.float32)
+    out, (dt, dm, du), _ = _check(uv, da, tex, mref.mipmaps(tex), None, boundary_mode, None, g, ("lattice", scale, boundary_mode),
+                                  zero="m" if scale == mref.LATTICE_SCALES[0] else "t" if scale >= 2 else "")
+    for row in (0, 1):
+        o, d = out[0, row, :5].reshape(10, C), du[0, row, :5].reshape(10, 2)
+        assert not o[~live].any() and not d[~live].any() and np.abs(o[live]).max(-1).all()
+
+
+@pytest.mark.parametrize("scale", mref.LATTICE_SCALES)
+def test_every_sample_beyond_the_border_under_clamp(scale):
+    """The lattice outside (0, 1) on both axes under clamp: the four taps of every level are one corner texel, dL/duv is exactly
+    zero, and only the corners of the sampled levels receive a gradient."""
+    size, C = mref.LATTICE_SIZE, 5
+    uv, da = mref.lattice_case(scale, outside=True)
+    rng = np.random.default_rng(49)
+    tex = rng.standard_normal(size + (C,), dtype=np.float32)
+    g = rng.standard_normal(mref.LATTICE_SHAPE + (C,), dtype=np.float32)
+    st = mref.stage(uv, da, *size)
+    _, (dt, dm, du), _ = _check(uv, da, tex, mref.mipmaps(tex), None, "clamp", None, g, ("outside", scale),
+                                zero="mu" if scale == mref.LATTICE_SCALES[0] else "tu" if scale >= 2 else "u")
+    rows = np.concatenate([dt.reshape(-1, C), dm])
+    corners = np.zeros(len(rows), bool)
+    for k, (h, w, off) in enumerate(mref.layout(*size)[1]):
+        if ((st["j"] == k) | (st["two"] & (st["j"] + 1 == k))).any():
+            corners[(0 if k == 0 else size[0] * size[1] + off) + np.array([0, w - 1, (h - 1) * w, h * w - 1])] = True
+    assert corners.sum() in (2, 4, 6, 8) and not rows[~corners].any() and rows[corners].all()
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 1), (2, 5, 3, 8)])
+def test_images_smaller_than_a_tile(shape):
+    size, C = (16, 8), 3
+    uv, da, rl = mref.case(shape, *size, seed=17)
+    rng = np.random.default_rng(50)
+    tex = rng.standard_normal((shape[0],) + size + (C,), dtype=np.float32)
+    g = rng.standard_normal(shape + (C,), dtype=np.float32)
+    single = int(np.prod(shape)) == 1                                        # one slot, magnified or not: one of the two tensors
+    st = mref.stage(uv, da, *size, rl)
+    assert not st["empty"].all()
+    zero = "" if not single else "t" if st["j"].max() > 0 else "m" if not st["two"].any() else ""
+    for boundary_mode in mref.BOUNDARIES:
+        _check(uv, da, tex, mref.mipmaps(tex), rl, boundary_mode, None, g, ("small", shape, boundary_mode), zero=zero)
+
+
+@pytest.mark.parametrize("mx", [0, 1, 2])
+def test_max_mip_level_reaches_the_backward(mx):
+    size, C = (16, 8), 5
+    uv, da, rl = inputs(size)
+    rng = np.random.default_rng(51 + mx)
+    for per_view, boundary_mode in ((False, "wrap"), (True, "clamp")):
+        tex = rng.standard_normal(((2,) if per_view else ()) + size + (C,), dtype=np.float32)
+        mip = mref.mipmaps(tex, mx)
+        assert mip.shape[-2] == (0, 32, 40)[mx]
+        g = rng.standard_normal(SHAPE + (C,), dtype=np.float32)
+        _check(uv, da, tex, mip, rl, boundary_mode, mx, g, ("max_mip_level", mx, per_view, boundary_mode))

@@ -141,6 +141,14 @@ def forward64(uv, uv_da, tex, mip, render_layers=None, boundary_mode="wrap", max
                    np.asarray(mip, np.float64), render_layers, boundary_mode, max_mip_level, np.float64, st, stage_dtype)
 
 
+def footprints(rng, shape, Ht, Wt, lo, hi):
+    """uv_da with the footprint's length along X and along Y 2^U(lo, hi) texels, at a random angle each."""
+    texels = 2.0 ** rng.uniform(lo, hi, shape + (2,))
+    ang = rng.uniform(0, 2 * np.pi, shape + (2,))
+    return np.stack([texels[..., 0] * np.cos(ang[..., 0]) / Wt, texels[..., 0] * np.sin(ang[..., 0]) / Ht,
+                     texels[..., 1] * np.cos(ang[..., 1]) / Wt, texels[..., 1] * np.sin(ang[..., 1]) / Ht], -1).astype(f32)
+
+
 def case(shape, Ht, Wt, seed, max_mip_level=None):
     """Inputs that reach every branch at this texture size -> (uv (B,H,W,L,2), uv_da (B,H,W,L,4), render_layers (B,H,W,L)):
     uv in [-0.5, 1.5]^2 (both borders), footprints from a quarter of a texel (magnified) to four times the coarsest level's
@@ -149,10 +157,7 @@ def case(shape, Ht, Wt, seed, max_mip_level=None):
     rng = np.random.RandomState(seed)
     nlev, _, _ = layout(Ht, Wt, max_mip_level)
     uv = rng.uniform(-0.5, 1.5, shape + (2,)).astype(f32)
-    texels = 2.0 ** rng.uniform(-2.0, nlev + 1.0, shape + (2,))             # the footprint's length along X and along Y, in texels
-    ang = rng.uniform(0, 2 * np.pi, shape + (2,))
-    da = np.stack([texels[..., 0] * np.cos(ang[..., 0]) / Wt, texels[..., 0] * np.sin(ang[..., 0]) / Ht,
-                   texels[..., 1] * np.cos(ang[..., 1]) / Wt, texels[..., 1] * np.sin(ang[..., 1]) / Ht], -1).astype(f32)
+    da = footprints(rng, shape, Ht, Wt, -2.0, nlev + 1.0)
     rl = np.where(rng.uniform(size=shape) < 1 / 16, -1, rng.randint(0, 50, shape)).astype(np.int32)
     bad = rng.uniform(size=shape)
     uv[bad < 1 / 32, 0] = np.nan
@@ -175,6 +180,168 @@ def reach(uv, uv_da, Ht, Wt, render_layers=None, max_mip_level=None):
                 pairs=[int((st["two"] & (st["j"] == k)).sum()) for k in range(nlev - 1)],
                 beyond=int((live & ~st["two"] & (st["lod"] >= nlev - 1) & (st["lod"] > 0)).sum()),
                 empty_id=int(by_id.sum()), empty_uv=int((by_uv & ~by_id).sum()), empty_da=int((by_da & ~by_id & ~by_uv).sum()))
+
+
+def keys(uv, uv_da, Ht, Wt, render_layers=None, boundary_mode="wrap", max_mip_level=None):
+    """(B,H,W,L,8) int64: each slot's taps in the kernel's single key space (level 0: j * Wt + i, level k >= 1: Ht * Wt +
+    offset_k + j * W_k + i), the first level's four, then the second's; -1 in an empty slot and, where the slot samples one level,
+    in the second four."""
+    st = stage(uv, uv_da, Ht, Wt, render_layers, max_mip_level)
+    _, levels, _ = layout(Ht, Wt, max_mip_level)
+    rl = _ids(st)
+    out = np.full(st["j"].shape + (8,), -1, np.int64)
+    for k, (h, w, off) in enumerate(levels):
+        first, second = ~st["empty"] & (st["j"] == k), st["two"] & (st["j"] + 1 == k)
+        if not (first.any() or second.any()):
+            continue
+        idx = tref.stage(uv, h, w, rl, "linear", boundary_mode)["idx"] + (0 if k == 0 else Ht * Wt + off)
+        out[..., :4] = np.where(first[..., None], idx, out[..., :4])
+        out[..., 4:] = np.where(second[..., None], idx, out[..., 4:])
+    return out
+
+
+def distinct_keys_per_tile(uv, uv_da, Ht, Wt, render_layers=None, boundary_mode="wrap", max_mip_level=None, tile=16, worst=min):
+    """The smallest (``worst=max``: the largest) number of distinct keys the slots of one layer address, over the tile x tile
+    pixel tiles of every view and over the layers (texture_ref.distinct_texels_per_tile on ``keys``)."""
+    ks = keys(uv, uv_da, Ht, Wt, render_layers, boundary_mode, max_mip_level)
+    B, H, W, L = ks.shape[:4]
+    best = None
+    for b in range(B):
+        for y in range(0, H, tile):
+            for x in range(0, W, tile):
+                for l in range(L):
+                    k = np.unique(ks[b, y:y + tile, x:x + tile, l])
+                    n = int((k >= 0).sum())
+                    best = n if best is None else worst(best, n)
+    return best
+
+
+def _step(a, n):
+    """float32 ``a`` moved n floats up (n < 0: down)."""
+    a = f32(a)
+    for _ in range(abs(n)):
+        a = np.nextafter(a, f32(np.inf) if n > 0 else f32(-np.inf))
+    return a
+
+
+def lod_edge_footprints(Ht, Wt, max_mip_level=None):
+    """(N,4) float32 uv_da rows on and next to every branch point of the level of detail, by lod32's own arithmetic.  For every
+    k in 0 .. nlev: r2 = 4^k exactly (lod = k), on the X axis (2^k / Wt in du/dX) and on the Y axis (2^k / Ht in dv/dY); and,
+    searched among the neighbouring floats of that component with a second component of about 2^k 2^-12 or 2^k 2^-11.5 texels
+    (whose square is one float of 4^k below it, and one above it), the rows with the nearest r2 below and above 4^k and with the
+    nearest lod below and above k.  Then: zeros, +-0 mixes, a denormal, 1e30 (r2 = inf, lod = 64), 3e38 on two components, the Y
+    axis the larger and the reverse, negative components."""
+    nlev, _, _ = layout(Ht, Wt, max_mip_level)
+    rows = []
+    for k in range(nlev + 1):
+        s = 2.0 ** k
+        rows += [[f32(s / Wt), 0, 0, 0], [0, 0, 0, f32(s / Ht)]]
+        cand = []
+        for i in range(-4, 5):
+            a = _step(s / Wt, i)
+            for b0 in (0.0, s * 2.0 ** -12 / Ht, s * 2.0 ** -11.5 / Ht):
+                for n in ((0,) if b0 == 0.0 else (-1, 0, 1)):
+                    cand.append([a, _step(b0, n), 0, 0])
+        cand = np.array(cand, f32)
+        lod, r2 = lod32(cand, Ht, Wt)
+        if k == 0:
+            lod = np.where(r2 < 1, f32(-1), lod)              # (below r2 = 1 every lod is 0: rank those rows by r2 alone)
+        exact = cand[r2 == f32(4.0 ** k)]
+        assert len(exact), (Ht, Wt, k)
+        for val, ref in ((r2, f32(4.0 ** k)), (lod, f32(k))):
+            lo, hi = val < ref, val > ref
+            if lo.any():
+                rows.append(cand[lo][np.argmax(val[lo])])
+            if hi.any():
+                rows.append(cand[hi][np.argmin(val[hi])])
+    z, n0 = f32(0.0), f32(-0.0)
+    rows += [[z, z, z, z], [z, n0, z, n0], [n0, z, n0, z], [n0, n0, n0, n0], [1e-45, 0, 0, -1e-45], [1e30, 0, 0, 0], [0, 0, 0, -1e30],
+             [3e38, 3e38, 0, 0], [0, 0, -3e38, 3e38], [1.0 / Wt, 0, 0, 3.0 / Ht], [3.0 / Wt, 0, 0, 1.0 / Ht],
+             [-2.0 / Wt, -1.0 / Ht, 0.5 / Wt, -0.25 / Ht], [-0.25 / Wt, 0.5 / Ht, -3.0 / Wt, -2.0 / Ht]]
+    table = np.array(rows, f32)
+    _, first = np.unique(table.view(np.uint32), axis=0, return_index=True)              # by bits: -0.0 is not 0.0
+    return table[np.sort(first)]
+
+
+# ---- the input sets of the GPU tests beyond ``case`` (tests/test_texture_mip_cpu.py holds each to the condition it is for) ----
+
+OVERFLOW_SHAPE, OVERFLOW_SIZE = (2, 32, 48, 2), (512, 512)
+HOT_SHAPE = (2, 50, 70, 4)
+EDGE_SHAPE = (1, 16, 16, 2)
+EDGE_TEXTURES = (((16, 8), None), ((8, 8), None), ((6, 10), None), ((16, 8), 1))        # (Ht, Wt), max_mip_level
+LATTICE_SHAPE, LATTICE_SIZE = (1, 33, 47, 2), (16, 8)
+LATTICE_SCALES = (0.5, 1.0, 2.0, 4.0, 16.0)        # uv_da = (s / Wt, s / Ht, 0, 0): r2 = 2 s^2, lod = 0, 0.5, 1.5, 2.5 and 4.5 (beyond)
+
+
+def overflow_case():
+    """Random uv in [0, 1)^2 on a 512^2 texture, footprints of 2^U(-1, 3.5) texels: every tile addresses several times the
+    keys the scatter's table holds, over levels 0 .. 5 -> (uv, uv_da, render_layers with -1 in one slot of seven)."""
+    rng = np.random.RandomState(51)
+    uv = rng.uniform(0.0, 1.0, OVERFLOW_SHAPE + (2,)).astype(f32)
+    da = footprints(rng, OVERFLOW_SHAPE, *OVERFLOW_SIZE, -1.0, 3.5)
+    return uv, da, rng.randint(-1, 6, OVERFLOW_SHAPE).astype(np.int32)
+
+
+def hot_case_magnified():
+    """Every slot magnified into one corner of an (8, 8) texture: a tile's lanes share a handful of level-0 keys."""
+    rng = np.random.RandomState(52)
+    uv = rng.uniform(0.32, 0.48, HOT_SHAPE + (2,)).astype(f32)
+    return uv, footprints(rng, HOT_SHAPE, 8, 8, -4.0, -0.5)
+
+
+def hot_case_beyond(Ht, Wt):
+    """Every footprint at least four times the coarsest level's texel, one slot in eight at 1e30 (r2 = inf): every tap of every
+    slot on the top level's texels."""
+    rng = np.random.RandomState(53)
+    nlev, _, _ = layout(Ht, Wt)
+    uv = rng.uniform(-0.5, 1.5, HOT_SHAPE + (2,)).astype(f32)
+    da = footprints(rng, HOT_SHAPE, Ht, Wt, nlev + 1.0, nlev + 6.0)
+    huge = rng.uniform(size=HOT_SHAPE) < 1 / 8
+    da[huge] = 0
+    da[huge, rng.randint(0, 4, int(huge.sum()))] = 1e30
+    return uv, da
+
+
+def lod_edge_case(Ht, Wt, max_mip_level=None):
+    """``lod_edge_footprints`` tiled over EDGE_SHAPE, uv random in [-0.5, 1.5]^2."""
+    rng = np.random.RandomState(54 + Ht + Wt)
+    table = lod_edge_footprints(Ht, Wt, max_mip_level)
+    n = int(np.prod(EDGE_SHAPE))
+    assert len(table) <= n // 4
+    da = table[np.arange(n) % len(table)].reshape(EDGE_SHAPE + (4,))
+    return rng.uniform(-0.5, 1.5, EDGE_SHAPE + (2,)).astype(f32), np.ascontiguousarray(da)
+
+
+def lattice_case(scale, outside=False):
+    """uv from the lattice {k / 32 : k = -40 .. 72} on both axes (``outside``: k <= 0 or k >= 32 only: under clamp every tap of
+    every level beyond the border), one footprint for all slots: uv_da = (scale / Wt, scale / Ht, 0, 0)."""
+    rng = np.random.RandomState(55)
+    ks = np.arange(-40, 73)
+    if outside:
+        ks = ks[(ks <= 0) | (ks >= 32)]
+    uv = (ks[rng.randint(0, len(ks), LATTICE_SHAPE + (2,))] / 32.0).astype(f32)
+    Ht, Wt = LATTICE_SIZE
+    da = np.broadcast_to(np.array([scale / Wt, scale / Ht, 0, 0], f32), LATTICE_SHAPE + (4,)).copy()
+    return uv, da
+
+
+# u (v) at which level 0's x = u * Wt - 0.5 (y) meets the range rule on LATTICE_SIZE.  Between 2^23 and 2^24 the product p is a
+# whole number and p - 0.5 a tie that rounds to the even neighbour, so x = 2^24 - 1 cannot come out: p = 2^24 - 1 gives 2^24 - 2,
+# the largest x a slot can have, and its negation gives -2^24.  (value, live)
+RANGE_EDGES = ((2.0 ** 24 - 1, True), (2.0 ** 24, False), (-(2.0 ** 24 - 1), False), (-(2.0 ** 24), False), (-(2.0 ** 24 - 2), True))
+
+
+def range_case(uv):
+    """``uv`` with the RANGE_EDGES products on u in the first ten slots of row 0 and on v in those of row 1 (both layers of five
+    pixels each) -> (uv, live (10,) bool in slot order)."""
+    uv = uv.copy()
+    Ht, Wt = LATTICE_SIZE
+    live = []
+    for n, (p, ok) in enumerate(RANGE_EDGES * 2):
+        uv[0, 0, n // 2, n % 2, 0] = f32(p / Wt)
+        uv[0, 1, n // 2, n % 2, 1] = f32(p / Ht)
+        live.append(ok)
+    return uv, np.array(live)
 
 
 def grads64(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, g):
