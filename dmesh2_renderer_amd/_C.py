@@ -27,6 +27,11 @@ and a texture sampled at such an image of UVs (Renderer.texture):
     texture_cuda(uv, tex, render_layers, filter_mode, boundary_mode) -> out,
     texture_backward_cuda(...those 5..., grad_out, need_tex, need_uv) -> (dL/dtex, dL/duv)
 
+and a cube map looked up by such an image of directions (Renderer.texture's boundary_mode="cube"):
+
+    texture_cube_cuda(dirs, tex, render_layers, filter_mode) -> out,
+    texture_cube_backward_cuda(...those 4..., grad_out, need_tex, need_dirs) -> (dL/dtex, dL/ddirs)
+
 and its mip-mapped filter (Renderer.bary_derivatives, Renderer.texture_mipmaps, texture's "linear-mipmap-linear"):
 
     bary_derivatives_cuda(render_layers, verts, faces, ray_cam) -> (dbary_dx, dbary_dy),
@@ -166,6 +171,8 @@ EXPORTS = {
     "dm2_interpolate_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 8),
     "dm2_texture": (ctypes.c_int, [_i32] * 10 + [_vp] * 5),
     "dm2_texture_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
+    "dm2_texture_cube": (ctypes.c_int, [_i32] * 8 + [_vp] * 5),
+    "dm2_texture_cube_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 7),
     "dm2_bary_derivatives_window": (ctypes.c_int, [_i32] * 6 + [ctypes.POINTER(Window)] + [_vp] * 7),
     "dm2_texture_mipmaps": (ctypes.c_int, [_i32] * 5 + [_vp] * 3),
     "dm2_texture_mipmaps_backward": (ctypes.c_int, [_i32] * 5 + [_vp] * 3),
@@ -1094,6 +1101,73 @@ def texture_backward_cuda(uv, tex, render_layers, filter_mode, boundary_mode, gr
         if lib.dm2_texture_backward(*sizes, _ptr(rl), _ptr(uvc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(duv), _stream(dev)):
             raise _err(lib, "texture_backward_cuda")
     return dtex, duv
+
+
+def _texture_cube_args(dirs, tex, render_layers, filter_mode, grad_out=None):
+    """Checks of a cube-map call -> (sizes (B, H, W, L, N, C, view_textures, filter), contiguous tensors, device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
+    bad(dirs.dim() != 5 or dirs.size(4) != 3, f"dirs must have dimensions (B, H, W, L, 3), got {tuple(dirs.shape)}")
+    B, H, W, L = (int(x) for x in dirs.shape[:4])
+    bad(tex.dim() not in (4, 5), "tex must have dimensions (6, N, N, C) or (B, 6, N, N, C)")
+    bad(tex.dim() == 5 and tex.size(0) != B, f"tex must have dimensions (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
+    six, Nr, N, C = (int(x) for x in tex.shape[-4:])
+    bad(six != 6, f"tex must have six faces, (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
+    bad(Nr != N, f"tex must have square faces, got {tuple(tex.shape)}")
+    bad(N < 1, "tex must have at least one row and one column per face")
+    bad(C < 1, "tex must have at least one channel")
+    bad(6 * N * N >= 2 ** 31, "tex: 6 * N * N must be below 2^31")
+    bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
+    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
+        f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
+    dev = _require_gpu(*[t for t in (dirs, tex, render_layers, grad_out) if t is not None])
+    f32, i32 = torch.float32, torch.int32
+    named = (("dirs", dirs, f32), ("tex", tex, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
+    ts = []
+    for name, t, dt in named:
+        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    return (B, H, W, L, N, C, 1 if tex.dim() == 5 else 0, TEX_FILTERS[filter_mode]), ts, dev
+
+
+def texture_cube_cuda(dirs, tex, render_layers=None, filter_mode="linear"):
+    """A cube map looked up by per-slot directions (include/dm2_hip.h: dm2_texture_cube).
+
+    dirs (B,H,W,L,3) float32 of any non-zero length, tex (6,N,N,C) or (B,6,N,N,C) float32 channel-last (+x, -x, +y, -y, +z,
+    -z), render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is negative or the direction is
+    not finite or all zero."""
+    lib = load_library()
+    sizes, (dc, tx, rl, _), dev = _texture_cube_args(dirs, tex, render_layers, filter_mode)
+    B, H, W, L, C = *sizes[:4], sizes[5]
+    if B * H * W * L == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_cube(*sizes, _ptr(rl), _ptr(dc), _ptr(tx), _ptr(out), _stream(dev)):
+            raise _err(lib, "texture_cube_cuda")
+    return out
+
+
+def texture_cube_backward_cuda(dirs, tex, render_layers, filter_mode, grad_out, need_tex, need_dirs):
+    """Gradients of texture_cube_cuda (dm2_texture_cube_backward) -> (dL_dtex of tex's shape or None, dL_ddirs (B,H,W,L,3) or
+    None): only what ``need_tex`` / ``need_dirs`` ask for is computed."""
+    lib = load_library()
+    sizes, (dc, tx, rl, go), dev = _texture_cube_args(dirs, tex, render_layers, filter_mode, grad_out)
+    B, H, W, L = sizes[:4]
+    f32 = torch.float32
+    if not (need_tex or need_dirs):
+        return None, None
+    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None
+    if B * H * W * L == 0:
+        return dtex, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_dirs else None
+    ddir = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_dirs else None     # (every element written)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(dc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(ddir), _stream(dev)):
+            raise _err(lib, "texture_cube_backward_cuda")
+    return dtex, ddir
 
 
 def bary_derivatives_cuda(render_layers, verts, faces, ray_cam):

@@ -19,7 +19,8 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   only graze a pixel, and that pipeline reproduces ``Renderer.forward``'s images, silhouettes included; and mip-mapped
   filtering for ``texture`` (``filter_mode="linear-mipmap-linear"``, ``TextureMipFunction``) with the two ops that feed it:
   ``Renderer.bary_derivatives()``, the pixel's footprint on each listed face (``BaryDerivativesFunction``, a constant of
-  the pipeline), and ``Renderer.texture_mipmaps()``, the chain of 2 x 2 means (``MipmapFunction``)
+  the pipeline), and ``Renderer.texture_mipmaps()``, the chain of 2 x 2 means (``MipmapFunction``); and cube-map lookup by
+  direction for ``texture`` (``boundary_mode="cube"``, ``TextureCubeFunction``): filtered across the cube's edges and corners
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -40,7 +41,7 @@ from .pyrenderer import Triangles
 
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
            "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction", "BaryDerivativesFunction",
-           "MipmapFunction", "TextureMipFunction"]
+           "MipmapFunction", "TextureMipFunction", "TextureCubeFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -469,9 +470,24 @@ class Renderer(torch.nn.Module):
         (RuntimeError where its shape does not match them); None builds it here, so that the texture's gradient flows through
         ``MipmapFunction``.  A slot whose ``uv_da`` is not finite is empty as well.  Differentiable w.r.t. ``tex``, ``mip`` and
         ``uv`` (``TextureMipFunction``); ``uv_da`` gets no gradient: the level of detail is a constant of the op.  ValueError
-        for the mode without ``uv_da``, and for ``uv_da`` or ``mip`` with another mode."""
+        for the mode without ``uv_da``, and for ``uv_da`` or ``mip`` with another mode.
+
+        ``boundary_mode="cube"`` looks a cube map up by direction: ``uv`` is then (B,H,W,L,3) float32, a direction per slot
+        of any non-zero length (``interpolate``'s output for per-vertex normals, normalised or not; a reflected view vector),
+        ``tex`` (6,N,N,C) shared by the views or (B,6,N,N,C), square faces in the order +x, -x, +y, -y, +z, -z with OpenGL's
+        face coordinates (nvdiffrast's layout).  The component of largest magnitude picks the face (x before y before z on
+        ties); ``filter_mode`` "linear" takes its taps beyond a face's border from the adjacent face, and at a cube corner,
+        where one of the four taps does not exist, blends the other three with their weights renormalised, so the lookup is
+        continuous over the whole sphere; "nearest" takes the face's nearest texel.  A slot with a negative id, a non-finite
+        component or an all-zero direction is empty.  Differentiable w.r.t. ``tex`` and the direction
+        (``TextureCubeFunction``); the direction's gradient is orthogonal to it.  ValueError naming ``boundary_mode`` for
+        "linear-mipmap-linear", ``uv_da``, ``mip`` or ``max_mip_level`` with "cube": cube mip chains are not built."""
         i32, f32 = torch.int32, torch.float32
         rl = None if render_layers is None else render_layers.to(i32)
+        if boundary_mode == "cube":
+            if filter_mode == "linear-mipmap-linear" or uv_da is not None or mip is not None or max_mip_level is not None:
+                raise ValueError('boundary_mode "cube" takes filter_mode "linear" or "nearest" and no uv_da, mip or max_mip_level')
+            return TextureCubeFunction.apply(uv.to(f32), tex.to(f32), rl, filter_mode)
         if filter_mode == "linear-mipmap-linear":
             if uv_da is None:
                 raise ValueError('filter_mode "linear-mipmap-linear" needs uv_da')
@@ -828,6 +844,35 @@ class TextureFunction(torch.autograd.Function):
         render_layers = ctx.saved_tensors[2] if ctx.has_layers else None
         dtex, duv = _C.texture_backward_cuda(uv, tex, render_layers, *ctx.modes, grad_out, need_tex, need_uv)
         return duv, dtex, None, None, None
+
+
+class TextureCubeFunction(torch.autograd.Function):
+    """out = the cube map in each slot's direction (``_C.texture_cube_cuda``): the major axis picks the face, bilinear over four
+    taps that continue onto the adjacent face across an edge (three renormalised taps at a cube corner), or the nearest texel.
+
+    Inputs: dirs (B,H,W,L,3)*, tex (6,N,N,C)* or (B,6,N,N,C)*, render_layers (B,H,W,L) int32 or None, filter_mode.
+    Output: out (B,H,W,L,C).  (* = receives a gradient.)  A non-empty slot sends w_k g to its texels and, through the face
+    coordinates sc / ma and tc / ma, a gradient orthogonal to the direction (zeros for nearest); empty slots send nothing and
+    get zero.  Only the gradients ``needs_input_grad`` asks for are computed.
+    """
+
+    @staticmethod
+    def forward(ctx, dirs, tex, render_layers, filter_mode):
+        out = _C.texture_cube_cuda(dirs.detach(), tex.detach(), render_layers, filter_mode)
+        ctx.filter_mode = filter_mode
+        ctx.has_layers = render_layers is not None
+        ctx.save_for_backward(dirs.detach(), tex.detach(), *((render_layers,) if ctx.has_layers else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_dirs, need_tex = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_out is None or not (need_dirs or need_tex):
+            return None, None, None, None
+        dirs, tex = ctx.saved_tensors[:2]
+        render_layers = ctx.saved_tensors[2] if ctx.has_layers else None
+        dtex, ddir = _C.texture_cube_backward_cuda(dirs, tex, render_layers, ctx.filter_mode, grad_out, need_tex, need_dirs)
+        return ddir, dtex, None, None
 
 
 class BaryDerivativesFunction(torch.autograd.Function):

@@ -636,6 +636,46 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
     return 0;
 }
 
+static int check_texture_cube_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t filter) {
+    if (B < 0 || H < 0 || W < 0 || L < 0) return fail("texture_cube: negative size");
+    if (N < 1) return fail("texture_cube: N must be at least 1");
+    if ((int64_t)6 * N * N > 0x7FFFFFFF) return fail("texture_cube: 6 * N * N must be below 2^31");
+    if (C < 1) return fail("texture_cube: C must be at least 1");
+    if (filter != DM2_TEX_FILTER_NEAREST && filter != DM2_TEX_FILTER_LINEAR) return fail("texture_cube: unknown filter");
+    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || B > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
+        return fail("texture_cube: too many slots, rows or views");
+    return 0;
+}
+
+int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                     const int32_t* render_layers, const float* dirs, const float* tex, float* out, void* stream) {
+    if (check_texture_cube_sizes(B, H, W, L, N, C, filter)) return 1;
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!dirs || !tex || !out) return fail("texture_cube: dirs, tex and out must not be null");
+    dm2::launch_texture_cube(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, out, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
+                              int32_t filter, const int32_t* render_layers, const float* dirs, const float* tex,
+                              const float* dL_dout, float* dL_dtex, float* dL_ddir, void* stream) {
+    if (check_texture_cube_sizes(B, H, W, L, N, C, filter)) return 1;
+    const int64_t S = (int64_t)B * H * W * L;
+    if (S == 0 || (!dL_dtex && !dL_ddir)) return 0;
+    if (!dirs || !dL_dout) return fail("texture_cube_backward: dirs and dL_dout must not be null");
+    if (dL_ddir && filter == DM2_TEX_FILTER_NEAREST) {                    // piecewise constant in the direction
+        DM2_HIP(hipMemsetAsync(dL_ddir, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
+        dL_ddir = nullptr;
+    }
+    if (dL_ddir && !tex) return fail("texture_cube_backward: tex must not be null");
+    if (dL_dtex || dL_ddir)
+        dm2::launch_texture_cube_backward(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, dL_dout, dL_dtex,
+                                          dL_ddir, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 int dm2_bary_derivatives_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, const dm2_window* win,
                                 const int32_t* render_layers, const float* verts, const int32_t* faces, const float* ray_cam,
                                 float* dbary_dx, float* dbary_dy, void* stream) {

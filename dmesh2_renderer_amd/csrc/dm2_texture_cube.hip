@@ -1,0 +1,409 @@
+// dm2_texture_cube.hip -- Renderer.texture(boundary_mode="cube"): a channel-last cube map (6, N, N, C) looked up by a direction
+// per slot s = (b, y, x, l):
+//   k_texture_cube          out[s, c] = a + fy (b - a) over four taps that may lie on the adjacent face; three taps with their
+//                           weights renormalised at a cube corner; nearest: one texel
+//   k_texture_cube_bwd_dir  dL/ddir[s] through fx, fy -> s, t -> sc / ma, tc / ma (zeros for nearest: the entry point fills them)
+//   k_texture_cube_bwd_tex  dL/dtex[t_k, c] += w_k g[s, c]
+//
+// Contract (include/dm2_hip.h, dm2_texture_cube): the major axis picks the face, (sc, tc, ma) by the OpenGL table,
+// s = 0.5 (sc / ma + 1), x = s N - 0.5 in [-0.5, N - 0.5], x0 = floor(x), fx = x - x0 (y alike); a slot is empty when its id is
+// negative, a component of the direction is not finite, or all three are zero: zeros out, nothing read from tex through it,
+// no gradient.  -ffp-contract=off: the forward is a pure function of the written operation order.
+//
+// The kernels have the shapes of dm2_texture.hip's, for the reasons given there: the forward stages one slot per lane in LDS
+// (four flat texel indices face N N + j N + i, the fractions, the missing tap of a corner) and sweeps the block's 256 * C
+// outputs with consecutive lanes on consecutive floats; the direction backward is one lane per slot; the texel scatter is one
+// block per 16 x 16 pixel tile and view, one layer at a time, through the block's FaceTable keyed by the flat texel index.
+// What is new is cube_tap(): the face selection, the seam rule for a tap beyond one border (CUBE_SEAM, a constant table read
+// only by the lanes that have such a tap) and the corner flag; everything after it sees four addresses and two fractions, as
+// the 2D op does.  The file is self-contained: dm2_texture.hip stays as it is.
+#include <hip/hip_runtime.h>
+
+#include "dm2_device_math.h"
+#include "dm2_face_table.h"
+#include "dm2_state.h"
+
+namespace dm2 {
+
+constexpr int CB_BLOCK = 256;             // slots per block of the flat kernels
+constexpr int CB_CH = 4;                  // the longest channel chunk of the tex backward
+constexpr int CB_NEAREST = 0, CB_LINEAR = 1;      // DM2_TEX_FILTER_*
+
+// borders of a face: 0: i < 0 (s = 0), 1: i >= N (s = 1), 2: j < 0 (t = 0), 3: j >= N (t = 1).
+// CUBE_SEAM[face][border] = {the face across that border, which of ITS borders the shared edge is, 1 when the position along
+// the edge runs the other way there}; faces +x, -x, +y, -y, +z, -z.  (tests/texture_cube_ref.py derives it from the geometry.)
+__device__ __constant__ signed char CUBE_SEAM[6][4][3] = {
+    {{4, 1, 0}, {5, 0, 0}, {2, 1, 1}, {3, 1, 0}},
+    {{5, 1, 0}, {4, 0, 0}, {2, 0, 0}, {3, 0, 1}},
+    {{1, 2, 0}, {0, 2, 1}, {5, 2, 1}, {4, 2, 0}},
+    {{1, 3, 1}, {0, 3, 0}, {4, 3, 0}, {5, 3, 1}},
+    {{1, 1, 0}, {0, 0, 0}, {2, 3, 0}, {3, 2, 0}},
+    {{0, 1, 0}, {1, 0, 0}, {2, 2, 1}, {3, 3, 1}},
+};
+
+struct CubeSizes {
+    int64_t S;        // B * H * W * L slots
+    int64_t per_view; // slots per view (H * W * L)
+    int64_t texels;   // 6 * N * N (< 2^31)
+    int B, H, W, L, N, C;
+    int view_textures; // tex is (B, 6, N, N, C): texel t of view b is texel b * 6 * N * N + t
+};
+
+// one slot's sample: flat texel indices of the taps (t00, t10, t01, t11; nearest: idx[0] alone), the fractions, and the tap
+// that does not exist at a cube corner (-1: all four exist; its idx is idx of an existing tap and is never used)
+struct CubeTap {
+    int idx[4];
+    float fx, fy;
+    int miss;
+};
+
+// the face and its coordinates; false = empty slot
+struct CubeFace {
+    int face;
+    float sc, tc, ma;
+};
+
+__device__ __forceinline__ bool cube_face(const CubeSizes& z, int64_t s, const int32_t* __restrict__ layers,
+                                          const float* __restrict__ dirs, CubeFace& f) {
+    if (layers && layers[s] < 0) return false;
+    const float x = dirs[3 * s], y = dirs[3 * s + 1], zz = dirs[3 * s + 2];
+    const float ax = fabsf(x), ay = fabsf(y), az = fabsf(zz);
+    if (!(ax < INFINITY) || !(ay < INFINITY) || !(az < INFINITY)) return false;      // NaN and infinities
+    if (ax == 0.0f && ay == 0.0f && az == 0.0f) return false;
+    if (ax >= ay && ax >= az) {
+        const int neg = x < 0.0f;                                          // (the major component is not zero here)
+        f.face = neg; f.ma = ax; f.sc = neg ? zz : -zz; f.tc = -y;
+    } else if (ay >= az) {
+        const int neg = y < 0.0f;
+        f.face = 2 + neg; f.ma = ay; f.sc = x; f.tc = neg ? -zz : zz;
+    } else {
+        const int neg = zz < 0.0f;
+        f.face = 4 + neg; f.ma = az; f.sc = neg ? -x : x; f.tc = -y;
+    }
+    return true;
+}
+
+// flat index of tap (i, j) of ``face`` after the seam rule; -1: beyond two borders (a cube corner)
+__device__ __forceinline__ int cube_texel(int N, int face, int i, int j) {
+    const bool ox = (unsigned)i >= (unsigned)N, oy = (unsigned)j >= (unsigned)N;
+    if (ox || oy) {
+        if (ox && oy) return -1;
+        const int e = ox ? (i < 0 ? 0 : 1) : (j < 0 ? 2 : 3);
+        const int k = ox ? j : i;
+        const signed char* row = CUBE_SEAM[face][e];
+        const int ne = row[1];
+        const int kk = row[2] ? N - 1 - k : k;
+        face = row[0];
+        i = ne == 0 ? 0 : (ne == 1 ? N - 1 : kk);
+        j = ne == 2 ? 0 : (ne == 3 ? N - 1 : kk);
+    }
+    return (face * N + j) * N + i;
+}
+
+// false = empty slot (nothing of ``tap`` or ``f`` is to be used)
+template <int FILTER>
+__device__ __forceinline__ bool cube_tap(const CubeSizes& z, int64_t s, const int32_t* __restrict__ layers,
+                                         const float* __restrict__ dirs, CubeTap& tap, CubeFace& f) {
+    if (!cube_face(z, s, layers, dirs, f)) return false;
+    const int N = z.N;
+    const float sn = 0.5f * (f.sc / f.ma + 1.0f), tn = 0.5f * (f.tc / f.ma + 1.0f);
+    const float x = sn * (float)N - 0.5f, y = tn * (float)N - 0.5f;
+    tap.miss = -1;
+    if (FILTER == CB_NEAREST) {
+        const int i = min(max((int)floorf(x + 0.5f), 0), N - 1), j = min(max((int)floorf(y + 0.5f), 0), N - 1);
+        tap.idx[0] = (f.face * N + j) * N + i;
+        tap.idx[1] = tap.idx[2] = tap.idx[3] = tap.idx[0];
+        tap.fx = tap.fy = 0.0f;
+        return true;
+    }
+    const float x0 = floorf(x), y0 = floorf(y);
+    tap.fx = x - x0; tap.fy = y - y0;
+    // |sc / ma| <= 1 puts x0 in [-1, N - 1] by itself; the clamp keeps every address inside the cube whatever the division gave
+    const int i0 = min(max((int)x0, -1), N - 1), j0 = min(max((int)y0, -1), N - 1);
+    const int t0 = cube_texel(N, f.face, i0, j0), t1 = cube_texel(N, f.face, i0 + 1, j0);
+    const int t2 = cube_texel(N, f.face, i0, j0 + 1), t3 = cube_texel(N, f.face, i0 + 1, j0 + 1);
+    // at most one tap is missing (x0 in [-1, N - 1]); of each row of taps one is inside the face's columns
+    tap.miss = t0 < 0 ? 0 : (t1 < 0 ? 1 : (t2 < 0 ? 2 : (t3 < 0 ? 3 : -1)));
+    tap.idx[0] = t0 < 0 ? t3 : t0; tap.idx[1] = t1 < 0 ? t2 : t1; tap.idx[2] = t2 < 0 ? t1 : t2; tap.idx[3] = t3 < 0 ? t0 : t3;
+    return true;
+}
+
+__device__ __forceinline__ float cb_bilinear(float t00, float t10, float t01, float t11, float fx, float fy) {
+    const float a = t00 + fx * (t10 - t00), b = t01 + fx * (t11 - t01);
+    return a + fy * (b - a);
+}
+
+// the weights of a corner sample: w_miss = 0, W their sum in the written order
+struct CornerW { float w0, w1, w2, w3, W; };
+__device__ __forceinline__ CornerW cb_corner_w(float fx, float fy, int miss) {
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    CornerW c;
+    c.w0 = miss == 0 ? 0.0f : gx * gy; c.w1 = miss == 1 ? 0.0f : fx * gy;
+    c.w2 = miss == 2 ? 0.0f : gx * fy; c.w3 = miss == 3 ? 0.0f : fx * fy;
+    c.W = ((c.w0 + c.w1) + c.w2) + c.w3;
+    return c;
+}
+
+// (t_miss = 0: what was loaded for the missing tap is not used)
+__device__ __forceinline__ float cb_corner(float t0, float t1, float t2, float t3, const CornerW& c, int miss) {
+    t0 = miss == 0 ? 0.0f : t0; t1 = miss == 1 ? 0.0f : t1; t2 = miss == 2 ? 0.0f : t2; t3 = miss == 3 ? 0.0f : t3;
+    return (((c.w0 * t0 + c.w1 * t1) + c.w2 * t2) + c.w3 * t3) / c.W;
+}
+
+// VEC4: C is a multiple of 4 and tex / out are 16-byte aligned, so a lane takes four channels at a time; every channel goes
+// through the same operations either way (the same bits).
+template <int FILTER, bool VEC4>
+__global__ void __launch_bounds__(CB_BLOCK)
+k_texture_cube(CubeSizes z, const int32_t* __restrict__ layers, const float* __restrict__ dirs, const float* __restrict__ tex,
+               float* __restrict__ out) {
+    constexpr int NIDX = FILTER == CB_LINEAR ? 4 : 1;
+    __shared__ int s_idx[NIDX][CB_BLOCK];                                     // idx[0] < 0: empty slot
+    __shared__ float s_fx[CB_BLOCK], s_fy[CB_BLOCK];
+    __shared__ int s_view[CB_BLOCK];                                          // view * 8 + (miss + 1)
+    const int tid = threadIdx.x;
+    const int64_t s0 = (int64_t)blockIdx.x * CB_BLOCK;
+    const int nslots = (int)min((int64_t)CB_BLOCK, z.S - s0);
+    if (tid < nslots) {
+        const int64_t s = s0 + tid;
+        CubeTap tap;
+        CubeFace f;
+        const bool ok = cube_tap<FILTER>(z, s, layers, dirs, tap, f);
+#pragma unroll
+        for (int k = 0; k < NIDX; k++) s_idx[k][tid] = ok ? tap.idx[k] : -1;
+        s_fx[tid] = ok ? tap.fx : 0.0f; s_fy[tid] = ok ? tap.fy : 0.0f;
+        s_view[tid] = (z.view_textures ? (int)(s / z.per_view) : 0) * 8 + (ok ? tap.miss + 1 : 0);
+    }
+    __syncthreads();
+    constexpr int V = VEC4 ? 4 : 1;
+    const int C = z.C, CV = C / V, total = nslots * CV;                      // lane -> (slot, group of V channels), group fastest
+    const int dq = CB_BLOCK / CV, dr = CB_BLOCK - dq * CV;                    // the step of (slot, group) per sweep
+    int slot = tid / CV, c = tid - slot * CV;
+    float* o = out + s0 * C;
+    for (int e = tid; e < total; e += CB_BLOCK) {
+        const int i00 = s_idx[0][slot];
+        float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};                                // (the scalar path uses r[0] alone)
+        if (i00 >= 0) {
+            const int vm = s_view[slot];
+            const float* base = tex + (int64_t)(vm >> 3) * z.texels * C + (int64_t)c * V;
+            if (FILTER == CB_NEAREST) {
+                if (VEC4) {
+                    const float4 t = *reinterpret_cast<const float4*>(base + (int64_t)i00 * C);
+                    r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
+                } else {
+                    r[0] = base[(int64_t)i00 * C];
+                }
+            } else {
+                const float fx = s_fx[slot], fy = s_fy[slot];
+                const int miss = (vm & 7) - 1;
+                const float* p00 = base + (int64_t)i00 * C;
+                const float* p10 = base + (int64_t)s_idx[NIDX > 1 ? 1 : 0][slot] * C;
+                const float* p01 = base + (int64_t)s_idx[NIDX > 1 ? 2 : 0][slot] * C;
+                const float* p11 = base + (int64_t)s_idx[NIDX > 1 ? 3 : 0][slot] * C;
+                if (VEC4) {
+                    const float4 t00 = *reinterpret_cast<const float4*>(p00), t10 = *reinterpret_cast<const float4*>(p10);
+                    const float4 t01 = *reinterpret_cast<const float4*>(p01), t11 = *reinterpret_cast<const float4*>(p11);
+                    if (miss < 0) {
+                        r[0] = cb_bilinear(t00.x, t10.x, t01.x, t11.x, fx, fy);
+                        r[1] = cb_bilinear(t00.y, t10.y, t01.y, t11.y, fx, fy);
+                        r[2] = cb_bilinear(t00.z, t10.z, t01.z, t11.z, fx, fy);
+                        r[3] = cb_bilinear(t00.w, t10.w, t01.w, t11.w, fx, fy);
+                    } else {
+                        const CornerW cw = cb_corner_w(fx, fy, miss);
+                        r[0] = cb_corner(t00.x, t10.x, t01.x, t11.x, cw, miss);
+                        r[1] = cb_corner(t00.y, t10.y, t01.y, t11.y, cw, miss);
+                        r[2] = cb_corner(t00.z, t10.z, t01.z, t11.z, cw, miss);
+                        r[3] = cb_corner(t00.w, t10.w, t01.w, t11.w, cw, miss);
+                    }
+                } else {
+                    if (miss < 0) r[0] = cb_bilinear(*p00, *p10, *p01, *p11, fx, fy);
+                    else r[0] = cb_corner(*p00, *p10, *p01, *p11, cb_corner_w(fx, fy, miss), miss);
+                }
+            }
+        }
+        if (VEC4) reinterpret_cast<float4*>(o)[e] = make_float4(r[0], r[1], r[2], r[3]);
+        else o[e] = r[0];
+        slot += dq; c += dr;
+        if (c >= CV) { c -= CV; slot++; }
+    }
+}
+
+// one channel's terms of d out / d fx . g and d out / d fy . g with all four taps
+__device__ __forceinline__ void cb_dir_term(float t00, float t10, float t01, float t11, float g, float fx, float fy, float& su, float& sv) {
+    const float d0 = t10 - t00, d1 = t11 - t01;
+    const float a = t00 + fx * d0, b = t01 + fx * d1;
+    su += g * (d0 + fy * (d1 - d0));
+    sv += g * (b - a);
+}
+
+// ... and at a corner: out = sum_k w_k t_k / W, d out / d fx = sum_k (dw_k / dfx) (t_k - out) / W (the 1 / W is applied to the sums)
+struct CornerD { float x0, x1, x2, x3, y0, y1, y2, y3; };
+__device__ __forceinline__ void cb_dir_term_corner(float t0, float t1, float t2, float t3, float g, const CornerW& cw, const CornerD& d,
+                                                   int miss, float& su, float& sv) {
+    const float o = cb_corner(t0, t1, t2, t3, cw, miss);
+    const float r0 = t0 - o, r1 = t1 - o, r2 = t2 - o, r3 = t3 - o;       // (a missing tap's d is 0)
+    su += g * (((d.x0 * r0 + d.x1 * r1) + d.x2 * r2) + d.x3 * r3);
+    sv += g * (((d.y0 * r0 + d.y1 * r1) + d.y2 * r2) + d.y3 * r3);
+}
+
+// (linear only: the entry point zero-fills dL_ddir for nearest.)  VEC4 as in k_texture_cube: the sums run over the channels in
+// the same order either way.
+template <bool VEC4>
+__global__ void __launch_bounds__(CB_BLOCK)
+k_texture_cube_bwd_dir(CubeSizes z, const int32_t* __restrict__ layers, const float* __restrict__ dirs, const float* __restrict__ tex,
+                       const float* __restrict__ g, float* __restrict__ dL_ddir) {
+    const int64_t s = (int64_t)blockIdx.x * CB_BLOCK + threadIdx.x;
+    if (s >= z.S) return;
+    CubeTap tap;
+    CubeFace f;
+    float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+    if (cube_tap<CB_LINEAR>(z, s, layers, dirs, tap, f)) {
+        const int C = z.C, miss = tap.miss;
+        const float* base = tex + (z.view_textures ? (s / z.per_view) * z.texels * C : 0);
+        const float* p00 = base + (int64_t)tap.idx[0] * C;
+        const float* p10 = base + (int64_t)tap.idx[1] * C;
+        const float* p01 = base + (int64_t)tap.idx[2] * C;
+        const float* p11 = base + (int64_t)tap.idx[3] * C;
+        const float* gs = g + s * C;
+        const float fx = tap.fx, fy = tap.fy;
+        float su = 0.0f, sv = 0.0f;
+        if (miss < 0) {
+            if (VEC4) {
+                for (int c = 0; c < C; c += 4) {
+                    const float4 t00 = *reinterpret_cast<const float4*>(p00 + c), t10 = *reinterpret_cast<const float4*>(p10 + c);
+                    const float4 t01 = *reinterpret_cast<const float4*>(p01 + c), t11 = *reinterpret_cast<const float4*>(p11 + c);
+                    const float4 gv = *reinterpret_cast<const float4*>(gs + c);
+                    cb_dir_term(t00.x, t10.x, t01.x, t11.x, gv.x, fx, fy, su, sv);
+                    cb_dir_term(t00.y, t10.y, t01.y, t11.y, gv.y, fx, fy, su, sv);
+                    cb_dir_term(t00.z, t10.z, t01.z, t11.z, gv.z, fx, fy, su, sv);
+                    cb_dir_term(t00.w, t10.w, t01.w, t11.w, gv.w, fx, fy, su, sv);
+                }
+            } else {
+                for (int c = 0; c < C; c++) cb_dir_term(p00[c], p10[c], p01[c], p11[c], gs[c], fx, fy, su, sv);
+            }
+        } else {
+            const CornerW cw = cb_corner_w(fx, fy, miss);
+            const float gx = 1.0f - fx, gy = 1.0f - fy;
+            CornerD d;
+            d.x0 = miss == 0 ? 0.0f : -gy; d.x1 = miss == 1 ? 0.0f : gy; d.x2 = miss == 2 ? 0.0f : -fy; d.x3 = miss == 3 ? 0.0f : fy;
+            d.y0 = miss == 0 ? 0.0f : -gx; d.y1 = miss == 1 ? 0.0f : -fx; d.y2 = miss == 2 ? 0.0f : gx; d.y3 = miss == 3 ? 0.0f : fx;
+            // (the scalar loop on both paths: corners are a few slots of a frame, and the order of the sum is the same)
+            for (int c = 0; c < C; c++) cb_dir_term_corner(p00[c], p10[c], p01[c], p11[c], gs[c], cw, d, miss, su, sv);
+            su = su / cw.W; sv = sv / cw.W;
+        }
+        // x = s N - 0.5, s = 0.5 (u + 1), u = sc / ma
+        const float A = 0.5f * (float)z.N * su, Bq = 0.5f * (float)z.N * sv;
+        const float inv = 1.0f / f.ma;
+        const float dsc = A * inv, dtc = Bq * inv, dma = -((A * f.sc + Bq * f.tc) * inv) * inv;
+        const int neg = f.face & 1;
+        const float dmaj = neg ? -dma : dma;
+        if (f.face < 2) { dx = dmaj; dy = -dtc; dz = neg ? dsc : -dsc; }
+        else if (f.face < 4) { dx = dsc; dy = dmaj; dz = neg ? -dtc : dtc; }
+        else { dx = neg ? -dsc : dsc; dy = -dtc; dz = dmaj; }
+    }
+    dL_ddir[3 * s] = dx; dL_ddir[3 * s + 1] = dy; dL_ddir[3 * s + 2] = dz;
+}
+
+template <int FILTER, int CH>
+__global__ void __launch_bounds__(TILE_PIX)
+k_texture_cube_bwd_tex(CubeSizes z, const int32_t* __restrict__ layers, const float* __restrict__ dirs, const float* __restrict__ g,
+                       float* __restrict__ dL_dtex) {
+    constexpr int NTAP = FILTER == CB_LINEAR ? 4 : 1;
+    constexpr int STRIDE = LC_SLOTS + (64 + CH - 1) / CH;                     // flush: bank = (c * (64 / CH) + slot) % 64
+    __shared__ FaceTable<float, CH, STRIDE> tab;
+    const int b = blockIdx.z, tid = threadIdx.x;
+    const TilePixel t = tile_pixel(tid, z.W, z.H);
+    const int C = z.C, L = z.L;
+    float* dst = dL_dtex + (z.view_textures ? (int64_t)b * z.texels * C : 0);
+    for (int l = 0; l < L; l++) {
+        const int64_t s = t.pix * L + l;
+        CubeTap tap = {{0, 0, 0, 0}, 0.0f, 0.0f, -1};
+        CubeFace f;
+        const bool live = t.inside && cube_tap<FILTER>(z, s, layers, dirs, tap, f);
+        float w[4] = {(1.0f - tap.fx) * (1.0f - tap.fy), tap.fx * (1.0f - tap.fy), (1.0f - tap.fx) * tap.fy, tap.fx * tap.fy};
+        if (tap.miss >= 0) {                                                  // a corner: the three weights over their sum
+            const CornerW cw = cb_corner_w(tap.fx, tap.fy, tap.miss);
+            w[0] = cw.w0 / cw.W; w[1] = cw.w1 / cw.W; w[2] = cw.w2 / cw.W; w[3] = cw.w3 / cw.W;
+        }
+        tab.clear_keys(tid);
+        for (int c0 = 0; c0 < C; c0 += CH) {
+            const int nc = min(CH, C - c0);
+            tab.clear_acc(tid);
+            __syncthreads();
+            if (live) {
+                float gv[CH];
+#pragma unroll
+                for (int c = 0; c < CH; c++) gv[c] = c < nc ? g[s * C + c0 + c] : 0.0f;
+#pragma unroll
+                for (int k = 0; k < NTAP; k++) {
+                    if (k == tap.miss) continue;                              // (no texel: its idx is another tap's)
+                    const int key = tap.idx[k];
+                    const float wk = FILTER == CB_LINEAR ? w[k] : 1.0f;
+                    const int slot = tab.slot(key);
+#pragma unroll
+                    for (int c = 0; c < CH; c++) {
+                        if (c >= nc) continue;
+                        const float v = wk * gv[c];
+                        if (slot >= 0) tab.add(slot, c, v);
+                        else atomicAdd(dst + (int64_t)key * C + c0 + c, v);
+                    }
+                }
+            }
+            __syncthreads();
+            // flush: one global atomic per (texel, channel) the table holds; lane -> (slot, c), c fastest
+            tab.flush_by_slot(tid, [&](int key, int c, float v) {
+                if (c < nc) atomicAdd(dst + (int64_t)key * C + c0 + c, v);
+            });
+            __syncthreads();
+        }
+    }
+}
+
+static CubeSizes cb_sizes(int B, int H, int W, int L, int N, int C, int view_textures) {
+    CubeSizes z;
+    z.per_view = (int64_t)H * W * L;
+    z.S = (int64_t)B * z.per_view;
+    z.texels = (int64_t)6 * N * N;
+    z.B = B; z.H = H; z.W = W; z.L = L; z.N = N; z.C = C; z.view_textures = view_textures;
+    return z;
+}
+
+static bool cb_aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+
+void launch_texture_cube(int B, int H, int W, int L, int N, int C, int view_textures, int filter, const int32_t* render_layers,
+                         const float* dirs, const float* tex, float* out, hipStream_t st) {
+    const CubeSizes z = cb_sizes(B, H, W, L, N, C, view_textures);
+    const dim3 grid((unsigned)((z.S + CB_BLOCK - 1) / CB_BLOCK));
+    const bool vec4 = C % 4 == 0 && cb_aligned16(tex, out);
+#define DM2_CB_FWD(F)                                                                                                        \
+    if (vec4) hipLaunchKernelGGL((k_texture_cube<F, true>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, out);  \
+    else hipLaunchKernelGGL((k_texture_cube<F, false>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, out)
+    if (filter == CB_LINEAR) { DM2_CB_FWD(CB_LINEAR); } else { DM2_CB_FWD(CB_NEAREST); }
+#undef DM2_CB_FWD
+}
+
+void launch_texture_cube_backward(int B, int H, int W, int L, int N, int C, int view_textures, int filter,
+                                  const int32_t* render_layers, const float* dirs, const float* tex, const float* dL_dout,
+                                  float* dL_dtex, float* dL_ddir, hipStream_t st) {
+    const CubeSizes z = cb_sizes(B, H, W, L, N, C, view_textures);
+    if (dL_ddir) {
+        const dim3 grid((unsigned)((z.S + CB_BLOCK - 1) / CB_BLOCK));       // (linear: the entry point zero-fills for nearest)
+        if (C % 4 == 0 && cb_aligned16(tex, dL_dout))
+            hipLaunchKernelGGL((k_texture_cube_bwd_dir<true>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, dL_dout, dL_ddir);
+        else
+            hipLaunchKernelGGL((k_texture_cube_bwd_dir<false>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, dL_dout, dL_ddir);
+    }
+    if (dL_dtex) {
+        const dim3 grid = tile_grid(W, H, B);
+#define DM2_CB_TEX_CH(F, CH) hipLaunchKernelGGL((k_texture_cube_bwd_tex<F, CH>), grid, dim3(TILE_PIX), 0, st, z, render_layers, dirs, dL_dout, dL_dtex)
+#define DM2_CB_TEX(F)                       \
+    if (C == 1) DM2_CB_TEX_CH(F, 1);        \
+    else if (C == 2) DM2_CB_TEX_CH(F, 2);   \
+    else if (C == 3) DM2_CB_TEX_CH(F, 3);   \
+    else DM2_CB_TEX_CH(F, CB_CH)
+        if (filter == CB_LINEAR) { DM2_CB_TEX(CB_LINEAR); } else { DM2_CB_TEX(CB_NEAREST); }
+#undef DM2_CB_TEX
+#undef DM2_CB_TEX_CH
+    }
+}
+
+}  // namespace dm2

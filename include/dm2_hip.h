@@ -428,6 +428,54 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
                          int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex,
                          const float* dL_dout, float* dL_dtex, float* dL_duv, void* stream);
 
+/* Renderer.texture(boundary_mode="cube"): a cube map looked up by a direction per slot.  dirs (B,H,W,L,3) float32, any
+ * non-zero length (dm2_interpolate's output for a 3-channel attribute such as a normal, or hand-built); tex (6,N,N,C) float32
+ * shared by the views (view_textures == 0) or (B,6,N,N,C), one cube per view, channel-last, faces in the order +x, -x, +y, -y,
+ * +z, -z; render_layers (B,H,W,L) int32 or NULL; out (B,H,W,L,C).  N, C >= 1; 6 * N * N < 2^31.  filter: DM2_TEX_FILTER_*.
+ * A slot is empty when render_layers[s] < 0 (render_layers NULL: never by id), or a component of the direction is not finite,
+ * or all three are zero: out[s,:] = 0, and nothing is read from tex through it.  Otherwise, per slot s with direction
+ * (x, y, z), all fp32, separate multiplies and adds in the written order, without contraction (bit-exact):
+ *   ax = |x|, ay = |y|, az = |z|;  the major axis is x if ax >= ay && ax >= az, else y if ay >= az, else z;
+ *   face = 2 * axis + (1 if the major component is negative);  ma = |major component|;  (sc, tc) by the OpenGL table:
+ *     +x: (-z, -y)   -x: (+z, -y)   +y: (+x, +z)   -y: (+x, -z)   +z: (+x, -y)   -z: (-x, -y)
+ *   sn = 0.5f * (sc / ma + 1.0f)       tn = 0.5f * (tc / ma + 1.0f)
+ *   X  = sn * (float)N - 0.5f          Y  = tn * (float)N - 0.5f              (both in [-0.5, N - 0.5])
+ *   X0 = floorf(X)   fx = X - X0       Y0 = floorf(Y)   fy = Y - Y0
+ *   DM2_TEX_FILTER_NEAREST  out[s,c] = tex[face][clamp((int)floorf(Y + 0.5f))][clamp((int)floorf(X + 0.5f))],
+ *     clamp(i) = min(max(i, 0), N - 1)
+ *   DM2_TEX_FILTER_LINEAR   taps (i0 + p, j0 + q), i0 = (int)X0, j0 = (int)Y0, tap k = p + 2 q, t_k its texel:
+ *     a tap inside the face is tex[face][j][i];
+ *     a tap outside on exactly one axis lies beyond border e of the face (0: i < 0, 1: i >= N, 2: j < 0, 3: j >= N) at position
+ *       k' = j (borders 0, 1) or i (borders 2, 3) along it, and is the texel of the face across that edge, in that face's
+ *       column or row along the shared edge, at the same position along the edge: with (nf, ne, rev) = SEAM[face][e] and
+ *       k'' = rev ? N - 1 - k' : k', tex[nf][k''][0] for ne == 0, tex[nf][k''][N - 1] for ne == 1, tex[nf][0][k''] for ne == 2,
+ *       tex[nf][N - 1][k''] for ne == 3;  SEAM[6][4] =
+ *         +x: {+z,1,0} {-z,0,0} {+y,1,1} {-y,1,0}     -x: {-z,1,0} {+z,0,0} {+y,0,0} {-y,0,1}
+ *         +y: {-x,2,0} {+x,2,1} {-z,2,1} {+z,2,0}     -y: {-x,3,1} {+x,3,0} {+z,3,0} {-z,3,1}
+ *         +z: {-x,1,0} {+x,0,0} {+y,3,0} {-y,2,0}     -z: {+x,1,0} {-x,0,0} {+y,2,1} {-y,3,1}
+ *     a tap outside on both axes (a cube corner) does not exist; at most one tap of a sample is such a tap.
+ *     With all four taps: a = t0 + fx * (t1 - t0), b = t2 + fx * (t3 - t2), out[s,c] = a + fy * (b - a)   (dm2_texture's blend).
+ *     With tap m missing: gx = 1.0f - fx, gy = 1.0f - fy, w = (gx * gy, fx * gy, gx * fy, fx * fy) with w_m = 0 and t_m = 0,
+ *       W = ((w0 + w1) + w2) + w3   (>= 0.75: the missing weight is at most 0.25),
+ *       out[s,c] = (((w0 * t0 + w1 * t1) + w2 * t2) + w3 * t3) / W.
+ * Every element of out is written: no pre-fill. */
+int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                     const int32_t* render_layers, const float* dirs, const float* tex, float* out, void* stream);
+/* Gradients of dm2_texture_cube for upstream g = dL_dout (B,H,W,L,C): the derivative of the fp32 function above at its fp32
+ * fractions, faces and addresses.  Per non-empty slot s:
+ *   dL_dtex[t_k,c] += w_k * g[s,c], w = ((1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy), at a corner w_k / W over the three taps that
+ *     exist (nearest: weight 1 on the one texel); the view's own cube when view_textures != 0, summed over the views otherwise;
+ *     two taps that address one texel (N = 1) both add; dL_dtex is zero-filled by the caller;
+ *   dL_ddir[s] goes through fx, fy (d out / d fx = (t1 - t0) + fy * ((t3 - t2) - (t1 - t0)), d out / d fy = b - a; at a
+ *     corner sum_k (dw_k / dfx) * (t_k - out) / W and alike for fy), then X = sn * N - 0.5, sn = 0.5 * (u + 1), u = sc / ma
+ *     (d/dsc = 1 / ma, d/dma = -sc / ma^2), tn alike, and the signs of the table; it is orthogonal to the direction (the lookup
+ *     does not depend on the length); zeros for nearest and in an empty slot; every element is written.
+ * Either output pointer may be NULL (not wanted; its kernel is not launched; tex may then be NULL for dL_dtex alone).
+ * dL_dtex is summed with float atomics: its last bits may vary from run to run; dL_ddir is a pure function of the inputs. */
+int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
+                              int32_t filter, const int32_t* render_layers, const float* dirs, const float* tex,
+                              const float* dL_dout, float* dL_dtex, float* dL_ddir, void* stream);
+
 /* Renderer.bary_derivatives: the footprint of a pixel on each listed face.  render_layers (B,H,W,L) int32, verts (P,3) float32,
  * faces (F,3) int32, ray_cam (B,32) float32 = inv(mv) (16, row-major) then inv(proj) (16) of each view, the camera block of
  * DM2_FLAG_ANALYTIC_RAYS; dbary_dx, dbary_dy (B,H,W,L,3) float32 = the derivatives of the slot's perspective-correct barycentrics
