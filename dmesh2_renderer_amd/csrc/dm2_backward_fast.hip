@@ -24,7 +24,14 @@
 //   C   pixel p: replay its records back to front -- the recurrence only (the running T and the accumulated colour / depth
 //       behind a pair, backward.cu:340-372): a wave runs it until its busiest pixel is through, so nothing else lives there
 //   D   lane s: dL/dalpha from what C left in its record and the pixel's loss gradients (backward.cu:350-405), chain rule
-//       (backward.cu:408-488) incl. the AA Jacobian, DPP pre-reduction over the lanes of one face, ds_add_f32
+//       (backward.cu:408-488) incl. the AA Jacobian, DPP reduction over the lanes of one face -- a run of the wave, across its
+//       16-lane rows (dm2_dpp.h) -- and ONE emitting lane per face and wave: an LDS float add costs ~3 LDS cycles per active
+//       lane, whatever its banks (profiles/lds_atomic_calibration.jsonl), so what counts is the number of emit lanes.  A face
+//       whose pairs lie inside one wave's lanes has one emit in the whole block and stores its 29 sums into its zeroed row
+//       (ds_write_b32: 4 cycles an instruction); only a face that crosses into a neighbouring wave adds (ds_add_f32).  That is
+//       the WIDE instantiation.  Frames of large faces (>= 3 tiles a face) have few emit lanes either way and
+//       only pay its extra steps: they get the instantiation with runs inside the 16-lane rows, per-lane masks and adds
+//       (third template parameter; launch_render_backward_fast picks it from the tiles a face touches)
 //   flush with (entry,component) global atomics.
 //
 // ALPHA (the second template parameter; dm2_backward_alpha with a non-null dL/d(alpha image)): the alpha image 1 - T_final
@@ -60,6 +67,9 @@ namespace dm2 {
 #ifndef DM2_BF_BLOCKS
 #define DM2_BF_BLOCKS 4       // resident blocks per CU the register budget is set for (no spills at 127 VGPRs)
 #endif
+#ifndef DM2_BF_STORE_OWNED
+#define DM2_BF_STORE_OWNED 1  // phase D: a face with one emitting lane in the block stores its sums, ds_write_b32 for ds_add_f32 (0: every emit adds; the A/B's other side)
+#endif
 enum Coverage { POOL, POINT, CLIP };      // where a pair's coverage comes from (file header)
 // What the coverage sources do not share: the LDS record (and the parts of the 256-B global record it is copied from),
 // candidate entries per chunk, resident blocks per CU
@@ -78,7 +88,10 @@ template <> struct BfTraits<CLIP> {
     static constexpr int CAND = 32, BLOCKS = 3;
 };
 
-template <Coverage COV, bool ALPHA>
+// WIDE: phase D's route (file header).  true: runs across the wave's rows, one emit per face and wave, owned rows stored;
+// false: runs inside the 16-lane rows with per-lane masks, one emit per face and row, every emit adds.
+constexpr int64_t ROW_ROUTE_TILES_PER_FACE = 3;      // list entries per (view, face) from which the default backward takes the row route
+template <Coverage COV, bool ALPHA, bool WIDE>
 __global__ void __launch_bounds__(TILE_PIX, BfTraits<COV>::BLOCKS)
 k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, const uint32_t* __restrict__ face_list,
                        ImageState is, const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
@@ -253,6 +266,19 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         // pair; a running maximum spreads it (slots and their first pairs grow together); the slot that covers the wave's
         // first lane comes from a ballot
         const int lo_pair = wid * 64;
+        // Phase D: a face emits once per wave, so a face whose pairs all lie inside this wave's 64 lanes has ONE emitting lane in
+        // the whole block and may store its sums into its (zeroed) accumulator row; only the face that crosses into the wave
+        // before (pairs on both sides of lane lo_pair) and the one that crosses into the wave behind must add.  Lane 2j + 1 of
+        // the scan holds the end of face j, its left neighbour the face's first pair.
+        int jx_lo = -1, jx_hi = -1;
+        if (DM2_BF_STORE_OWNED && WIDE) {
+            const int f0 = dpp_shr_i<1>(b0);
+            const bool kept = (lane & 1) && (lane >> 1) < n;
+            const unsigned long long xl = __ballot(kept && f0 < lo_pair && inc > lo_pair);
+            const unsigned long long xh = __ballot(kept && f0 < lo_pair + 64 && inc > lo_pair + 64);
+            if (xl) jx_lo = (__ffsll((long long)xl) - 1) >> 1;
+            if (xh) jx_hi = (__ffsll((long long)xh) - 1) >> 1;
+        }
         // (the lanes of the wave talk to each other through this row with no barrier in between: the fence below keeps the
         // compiler from forwarding this thread's own stores to its load; the hardware runs a wave's LDS operations in order)
         uint32_t* const mark_row = s_mark[wid];
@@ -385,13 +411,29 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             const int jkey = have ? j : -1;
             const int l16 = tid & 15;
             // NB: every DPP read must execute with all lanes enabled, hence the unconditional reads and `&`, `|`.
-            const int k1 = dpp_shr_i<1>(jkey), k2 = dpp_shr_i<2>(jkey), k4 = dpp_shr_i<4>(jkey), k8 = dpp_shr_i<8>(jkey);
-            const int kn = dpp_shl_i<1>(jkey);
-            const bool s1 = (l16 >= 1) & (k1 == jkey);
-            const bool s2 = (l16 >= 2) & (k2 == jkey);
-            const bool s4 = (l16 >= 4) & (k4 == jkey);
-            const bool s8 = (l16 >= 8) & (k8 == jkey);
-            const float m1 = s1 ? 1.f : 0.f, m2 = s2 ? 1.f : 0.f, m4 = s4 ? 1.f : 0.f, m8 = s8 ? 1.f : 0.f;
+            // The lanes of one face are a run of the wave, across its 16-lane rows: `cont`, the ballot of "the lane before has my
+            // face", is all the segmented scans below and the choice of the run's one emitting lane need (dm2_dpp.h).
+            // Row-wise route: runs inside the 16-lane rows, per-lane predicates and multipliers, one emit per face and row.
+            const int k1 = dpp_shr_i<1>(jkey);
+            unsigned long long cont = 0ull;
+            bool s1 = false, s2 = false, s4 = false, s8 = false, row_last = false;
+            float m1 = 0.f, m2 = 0.f, m4 = 0.f, m8 = 0.f;
+            if constexpr (WIDE) {
+                const int kb15 = __builtin_amdgcn_update_dpp(0, jkey, 0x142, 0xA, 0xF, false);   // rows 1, 3: the key of lane 15 / 47
+                const int kb31 = __builtin_amdgcn_update_dpp(0, jkey, 0x143, 0xC, 0xF, false);   // rows 2, 3: the key of lane 31
+                const int kprev = l16 ? k1 : ((lane & 16) ? kb15 : kb31);
+                cont = __ballot((lane > 0) & (kprev == jkey));
+            } else {
+                const int k2 = dpp_shr_i<2>(jkey), k4 = dpp_shr_i<4>(jkey), k8 = dpp_shr_i<8>(jkey);
+                const int kn = dpp_shl_i<1>(jkey);
+                s1 = (l16 >= 1) & (k1 == jkey); s2 = (l16 >= 2) & (k2 == jkey); s4 = (l16 >= 4) & (k4 == jkey); s8 = (l16 >= 8) & (k8 == jkey);
+                m1 = s1 ? 1.f : 0.f; m2 = s2 ? 1.f : 0.f; m4 = s4 ? 1.f : 0.f; m8 = s8 ? 1.f : 0.f;
+                row_last = (l16 == 15) | (kn != jkey);
+            }
+            auto run_sums = [&](auto& g) {
+                if constexpr (WIDE) seg_scan64_safe(g, cont, lane);
+                else seg_scan16_safe(g, m1, m2, m4, m8, s1, s2, s4, s8);
+            };
             // the head: what phase C left in the pair's record (dm2_bwd_shared.h) and the pixel's rows -> dL/dalpha, with the
             // reference's operations in its order (backward.cu:350-405)
             uint32_t pflags = 0;
@@ -432,8 +474,13 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 pr_dL_dalpha = dL_dalpha;
             }
             float nact = active ? 1.f : 0.f;
-            seg_scan16(nact, s1, s2, s4, s8);
-            const bool emit = ((l16 == 15) | (kn != jkey)) & (jkey >= 0) & (nact > 0.f);
+            if constexpr (WIDE) seg_scan64_finite(nact, seg_steps(cont));
+            else seg_scan16(nact, s1, s2, s4, s8);
+            const bool emit = (WIDE ? run_last_lane(cont, lane) : row_last) & (jkey >= 0) & (nact > 0.f);   // one emit per face and wave (row)
+            // (the face that crosses into a neighbouring wave shares its row with that wave's emit: it adds; every other face owns
+            // its row, zeroed by the last flush, and stores -- scan above)
+            const bool crosses = !(WIDE && DM2_BF_STORE_OWNED) | (jkey == jx_lo) | (jkey == jx_hi);
+            const bool emit_add = emit & crosses, emit_own = emit & !crosses;
             float* const arow = acc + j * BM_ACC;
             float dL_diu = 0.f, dL_div = 0.f, dL_doarea = 0.f;
             ISA_MARK(D_group1)
@@ -472,12 +519,19 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                     dL_diu = dL_di0 * di0_diu + dL_di1 * di1_diu + dL_di2 * di2_diu;
                     dL_div = dL_di0 * di0_div + dL_di1 * di1_div + dL_di2 * di2_div;
                 }
-                seg_scan16_safe(g1, m1, m2, m4, m8, s1, s2, s4, s8);
-                if (emit) {
+                run_sums(g1);
+                if (emit_add) {
 #pragma unroll
                     for (int c = 0; c < 12; c++) atomicAdd(arow + M_DC + c, g1[c]);      // M_DC..+8 and M_DZ..+2 are contiguous
                     atomicAdd(arow + M_OP, g1[12]);
                     atomicAdd(arow + M_IN, g1[13]);
+                    arow[M_FLAG] = 1.0f;
+                }
+                if (WIDE && DM2_BF_STORE_OWNED && emit_own) {
+#pragma unroll
+                    for (int c = 0; c < 12; c++) arow[M_DC + c] = g1[c];
+                    arow[M_OP] = g1[12];
+                    arow[M_IN] = g1[13];
                     arow[M_FLAG] = 1.0f;
                 }
             }
@@ -498,10 +552,14 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 float g2[6];
 #pragma unroll
                 for (int c = 0; c < 6; c++) g2[c] = dL_doarea * dg[c];                   // dL_doarea is 0 on inactive lanes
-                seg_scan16_safe(g2, m1, m2, m4, m8, s1, s2, s4, s8);
-                if (emit) {
+                run_sums(g2);
+                if (emit_add) {
 #pragma unroll
                     for (int c = 0; c < 6; c++) atomicAdd(arow + M_AA + c, g2[c]);
+                }
+                if (WIDE && DM2_BF_STORE_OWNED && emit_own) {
+#pragma unroll
+                    for (int c = 0; c < 6; c++) arow[M_AA + c] = g2[c];
                 }
             } else if constexpr (COV == POOL) {
                 float g2[6];
@@ -525,10 +583,14 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                         if (held != 0u && lane == (tie_first == 0 ? 1 : 0)) tie_base = atomicAdd(hit_valid + 2, min(held, TIE_BUF));
                     }
                 } else if (lane == tie_first) tie_base = atomicAdd(&s_tie_n, (uint32_t)__popcll(tie_bal));
-                seg_scan16_safe(g2, m1, m2, m4, m8, s1, s2, s4, s8);
-                if (emit) {
+                run_sums(g2);
+                if (emit_add) {
 #pragma unroll
                     for (int c = 0; c < 6; c++) atomicAdd(arow + M_AA + c, g2[c]);
+                }
+                if (WIDE && DM2_BF_STORE_OWNED && emit_own) {
+#pragma unroll
+                    for (int c = 0; c < 6; c++) arow[M_AA + c] = g2[c];
                 }
             }
             ISA_MARK(D_group3)
@@ -547,10 +609,14 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                     g3[3] = dp1.x; g3[4] = dp1.y; g3[5] = dp1.z;
                     g3[6] = dp2.x; g3[7] = dp2.y; g3[8] = dp2.z;
                 }
-                seg_scan16_safe(g3, m1, m2, m4, m8, s1, s2, s4, s8);
-                if (emit) {
+                run_sums(g3);
+                if (emit_add) {
 #pragma unroll
                     for (int c = 0; c < 9; c++) atomicAdd(arow + M_DV + c, g3[c]);
+                }
+                if (WIDE && DM2_BF_STORE_OWNED && emit_own) {
+#pragma unroll
+                    for (int c = 0; c < 9; c++) arow[M_DV + c] = g3[c];
                 }
             }
             if constexpr (COV == POOL) {
@@ -741,17 +807,29 @@ void launch_render_backward_fast(const dm2_render_desc& d, const uint2* ranges, 
     const uint32_t Tn = (uint32_t)(((d.W + TILE - 1) / TILE) * ((d.H + TILE - 1) / TILE) * d.B);
     const uint32_t cap = (uint32_t)(tie_cap > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : tie_cap);
     auto launch = [&](auto kernel, uint32_t kcap) {
-        StageTimer tm(check_mode ? -1 : ST_BWD, st);       // (under DM2_FWD_UNKNOWN the caller times the whole cascade)
         hipLaunchKernelGGL(kernel, dim3(tile_grid_blocks(Tn)), dim3(TILE_PIX), 0, st, d, ranges, face_list, is, dL_dcolor, dL_ddepth,
                            dL_dverts, dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts,
                            bs.hit_masks, bs.hit_valid, bs.hit_base, bs.pool, tie_queue, kcap, check_mode, dL_dalpha STAMP_ARG(1));
     };
     const bool A = dL_dalpha != nullptr;                   // the alpha image's gradient: the ALPHA instantiations
+    {
+    StageTimer tm(check_mode ? -1 : ST_BWD, st);           // (under DM2_FWD_UNKNOWN the caller times the whole cascade)
     if (!(d.aa_temperature > 0.0f)) {                      // point-sampled coverage: the masks of dm2_forward_point.hip, nothing else
-        launch(A ? k_render_backward_fast<POINT, true> : k_render_backward_fast<POINT, false>, 0u); return;
+        launch(A ? k_render_backward_fast<POINT, true, true> : k_render_backward_fast<POINT, false, true>, 0u); return;
     }
-    if (clip) { launch(A ? k_render_backward_fast<CLIP, true> : k_render_backward_fast<CLIP, false>, 0u); return; }
-    launch(A ? k_render_backward_fast<POOL, true> : k_render_backward_fast<POOL, false>, cap);
+    if (clip) { launch(A ? k_render_backward_fast<CLIP, true, true> : k_render_backward_fast<CLIP, false, true>, 0u); return; }
+    // The default route: phase D's two routes are two instantiations, and which one pays is a property of the frame's faces.
+    // 2.5-px triangles (~9 emit lanes a wave with row-wise emits): WIDE, backward -11 %.  130-px faces: few emit lanes either
+    // way, and WIDE's extra steps cost them 8-9 % of the backward.  The launcher's measure of a face's size is the number of
+    // tiles it touches, list entries per (view, face): 3.9 at cfg 1 and at depth complexity 60, 1.6-2.0 at cfg 2, 4 and 5
+    // (faces outside the patch only lower it).  The list's length, to 64 entries, is the distance between the first two parts
+    // of the binning scratch (dm2_backward is not told the plan's figures).  A second launch that stands down on the device
+    // was measured instead: its empty blocks cost cfg 1 as much as the wrong route.
+    const int64_t entries = ((const char*)bs.keys - (const char*)bs.face_list) / 4 - 63;     // (the carve's 256-B granule: never more than there are)
+    const bool large_faces = entries >= ROW_ROUTE_TILES_PER_FACE * (int64_t)d.B * (int64_t)d.F;
+    if (large_faces) launch(A ? k_render_backward_fast<POOL, true, false> : k_render_backward_fast<POOL, false, false>, cap);
+    else launch(A ? k_render_backward_fast<POOL, true, true> : k_render_backward_fast<POOL, false, true>, cap);
+    }
     const unsigned blocks = (unsigned)((cap + 255u) / 256u < 1024u ? (cap + 255u) / 256u : 1024u);
     StageTimer tm(check_mode ? -1 : ST_TIES, st);
     if (blocks) hipLaunchKernelGGL(k_aa_ties, dim3(blocks), dim3(256), 0, st, d, is.face_recs, tie_queue, cap, bs.hit_valid, dL_daa_face_verts, check_mode);
