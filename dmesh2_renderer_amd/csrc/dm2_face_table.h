@@ -1,6 +1,6 @@
 // dm2_face_table.h -- FaceTable: the per-block LDS table of the scatter kernels, one lane per pixel of a 16 x 16 tile
-// (k_layer_composite<WEIGHTS>, k_layer_composite_bwd, k_rasterize_bwd, k_interpolate_bwd_attr, k_texture_bwd_tex,
-// k_texture_cube_bwd_tex, k_composite_bwd<FACE>, k_coverage_bwd).  DESIGN.md 8, "The face table".
+// (k_layer_composite<WEIGHTS>, k_layer_composite_bwd, k_rasterize_bwd, k_interpolate_bwd_attr, k_texture_bwd_tex, k_composite_bwd<FACE>, k_coverage_bwd, and through
+// dm2_tex_core.h's tex_scatter_layer k_texture_mip_bwd_tex, k_texture_cube_bwd_tex).  DESIGN.md 8, "The face table".
 //
 // Neighbouring pixels list the same faces (or texels).  A (pixel, key) contribution adds its components into the key's slot,
 // and the block then flushes with one global atomic per (key, component) of the tile rather than one per (pixel, key,

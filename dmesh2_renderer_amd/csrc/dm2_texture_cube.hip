@@ -16,18 +16,16 @@
 // block per 16 x 16 pixel tile and view, one layer at a time, through the block's FaceTable keyed by the flat texel index.
 // What is new is cube_tap(): the face selection, the seam rule for a tap beyond one border (CUBE_SEAM, a constant table read
 // only by the lanes that have such a tap) and the corner flag; everything after it sees four addresses and two fractions, as
-// the 2D op does.  The file is self-contained: dm2_texture.hip stays as it is.
+// the 2D op does, and takes them through the same code: the blend, the uv terms, the sweep and the scatter are
+// dm2_tex_core.h's.  The corner sample (three taps, renormalised weights) and its gradient stay here.
 #include <hip/hip_runtime.h>
 
 #include "dm2_device_math.h"
 #include "dm2_face_table.h"
 #include "dm2_state.h"
+#include "dm2_tex_core.h"
 
 namespace dm2 {
-
-constexpr int CB_BLOCK = 256;             // slots per block of the flat kernels
-constexpr int CB_CH = 4;                  // the longest channel chunk of the tex backward
-constexpr int CB_NEAREST = 0, CB_LINEAR = 1;      // DM2_TEX_FILTER_*
 
 // borders of a face: 0: i < 0 (s = 0), 1: i >= N (s = 1), 2: j < 0 (t = 0), 3: j >= N (t = 1).
 // CUBE_SEAM[face][border] = {the face across that border, which of ITS borders the shared edge is, 1 when the position along
@@ -109,7 +107,7 @@ __device__ __forceinline__ bool cube_tap(const CubeSizes& z, int64_t s, const in
     const float sn = 0.5f * (f.sc / f.ma + 1.0f), tn = 0.5f * (f.tc / f.ma + 1.0f);
     const float x = sn * (float)N - 0.5f, y = tn * (float)N - 0.5f;
     tap.miss = -1;
-    if (FILTER == CB_NEAREST) {
+    if (FILTER == TEX_NEAREST) {
         const int i = min(max((int)floorf(x + 0.5f), 0), N - 1), j = min(max((int)floorf(y + 0.5f), 0), N - 1);
         tap.idx[0] = (f.face * N + j) * N + i;
         tap.idx[1] = tap.idx[2] = tap.idx[3] = tap.idx[0];
@@ -126,11 +124,6 @@ __device__ __forceinline__ bool cube_tap(const CubeSizes& z, int64_t s, const in
     tap.miss = t0 < 0 ? 0 : (t1 < 0 ? 1 : (t2 < 0 ? 2 : (t3 < 0 ? 3 : -1)));
     tap.idx[0] = t0 < 0 ? t3 : t0; tap.idx[1] = t1 < 0 ? t2 : t1; tap.idx[2] = t2 < 0 ? t1 : t2; tap.idx[3] = t3 < 0 ? t0 : t3;
     return true;
-}
-
-__device__ __forceinline__ float cb_bilinear(float t00, float t10, float t01, float t11, float fx, float fy) {
-    const float a = t00 + fx * (t10 - t00), b = t01 + fx * (t11 - t01);
-    return a + fy * (b - a);
 }
 
 // the weights of a corner sample: w_miss = 0, W their sum in the written order
@@ -150,19 +143,17 @@ __device__ __forceinline__ float cb_corner(float t0, float t1, float t2, float t
     return (((c.w0 * t0 + c.w1 * t1) + c.w2 * t2) + c.w3 * t3) / c.W;
 }
 
-// VEC4: C is a multiple of 4 and tex / out are 16-byte aligned, so a lane takes four channels at a time; every channel goes
-// through the same operations either way (the same bits).
 template <int FILTER, bool VEC4>
-__global__ void __launch_bounds__(CB_BLOCK)
+__global__ void __launch_bounds__(TEX_BLOCK)
 k_texture_cube(CubeSizes z, const int32_t* __restrict__ layers, const float* __restrict__ dirs, const float* __restrict__ tex,
                float* __restrict__ out) {
-    constexpr int NIDX = FILTER == CB_LINEAR ? 4 : 1;
-    __shared__ int s_idx[NIDX][CB_BLOCK];                                     // idx[0] < 0: empty slot
-    __shared__ float s_fx[CB_BLOCK], s_fy[CB_BLOCK];
-    __shared__ int s_view[CB_BLOCK];                                          // view * 8 + (miss + 1)
+    constexpr int NIDX = FILTER == TEX_LINEAR ? 4 : 1;
+    __shared__ int s_idx[NIDX][TEX_BLOCK];                                     // idx[0] < 0: empty slot
+    __shared__ float s_fx[TEX_BLOCK], s_fy[TEX_BLOCK];
+    __shared__ int s_view[TEX_BLOCK];                                          // view * 8 + (miss + 1)
     const int tid = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * CB_BLOCK;
-    const int nslots = (int)min((int64_t)CB_BLOCK, z.S - s0);
+    const int64_t s0 = (int64_t)blockIdx.x * TEX_BLOCK;
+    const int nslots = (int)min((int64_t)TEX_BLOCK, z.S - s0);
     if (tid < nslots) {
         const int64_t s = s0 + tid;
         CubeTap tap;
@@ -174,68 +165,30 @@ k_texture_cube(CubeSizes z, const int32_t* __restrict__ layers, const float* __r
         s_view[tid] = (z.view_textures ? (int)(s / z.per_view) : 0) * 8 + (ok ? tap.miss + 1 : 0);
     }
     __syncthreads();
-    constexpr int V = VEC4 ? 4 : 1;
-    const int C = z.C, CV = C / V, total = nslots * CV;                      // lane -> (slot, group of V channels), group fastest
-    const int dq = CB_BLOCK / CV, dr = CB_BLOCK - dq * CV;                    // the step of (slot, group) per sweep
-    int slot = tid / CV, c = tid - slot * CV;
-    float* o = out + s0 * C;
-    for (int e = tid; e < total; e += CB_BLOCK) {
-        const int i00 = s_idx[0][slot];
-        float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};                                // (the scalar path uses r[0] alone)
-        if (i00 >= 0) {
-            const int vm = s_view[slot];
-            const float* base = tex + (int64_t)(vm >> 3) * z.texels * C + (int64_t)c * V;
-            if (FILTER == CB_NEAREST) {
-                if (VEC4) {
-                    const float4 t = *reinterpret_cast<const float4*>(base + (int64_t)i00 * C);
-                    r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
-                } else {
-                    r[0] = base[(int64_t)i00 * C];
-                }
-            } else {
-                const float fx = s_fx[slot], fy = s_fy[slot];
-                const int miss = (vm & 7) - 1;
-                const float* p00 = base + (int64_t)i00 * C;
-                const float* p10 = base + (int64_t)s_idx[NIDX > 1 ? 1 : 0][slot] * C;
-                const float* p01 = base + (int64_t)s_idx[NIDX > 1 ? 2 : 0][slot] * C;
-                const float* p11 = base + (int64_t)s_idx[NIDX > 1 ? 3 : 0][slot] * C;
-                if (VEC4) {
-                    const float4 t00 = *reinterpret_cast<const float4*>(p00), t10 = *reinterpret_cast<const float4*>(p10);
-                    const float4 t01 = *reinterpret_cast<const float4*>(p01), t11 = *reinterpret_cast<const float4*>(p11);
-                    if (miss < 0) {
-                        r[0] = cb_bilinear(t00.x, t10.x, t01.x, t11.x, fx, fy);
-                        r[1] = cb_bilinear(t00.y, t10.y, t01.y, t11.y, fx, fy);
-                        r[2] = cb_bilinear(t00.z, t10.z, t01.z, t11.z, fx, fy);
-                        r[3] = cb_bilinear(t00.w, t10.w, t01.w, t11.w, fx, fy);
-                    } else {
-                        const CornerW cw = cb_corner_w(fx, fy, miss);
-                        r[0] = cb_corner(t00.x, t10.x, t01.x, t11.x, cw, miss);
-                        r[1] = cb_corner(t00.y, t10.y, t01.y, t11.y, cw, miss);
-                        r[2] = cb_corner(t00.z, t10.z, t01.z, t11.z, cw, miss);
-                        r[3] = cb_corner(t00.w, t10.w, t01.w, t11.w, cw, miss);
-                    }
-                } else {
-                    if (miss < 0) r[0] = cb_bilinear(*p00, *p10, *p01, *p11, fx, fy);
-                    else r[0] = cb_corner(*p00, *p10, *p01, *p11, cb_corner_w(fx, fy, miss), miss);
-                }
-            }
+    const int C = z.C;
+    tex_sweep<VEC4>(tid, nslots, C, s_idx[0], out, s0, [&](int slot, int i00, int c) -> TexQuad {
+        const int vm = s_view[slot];
+        const float* base = tex + (int64_t)(vm >> 3) * z.texels * C + (int64_t)c * (VEC4 ? 4 : 1);
+        if (FILTER == TEX_NEAREST) return tex_load_row<VEC4>(base + (int64_t)i00 * C);
+        const float fx = s_fx[slot], fy = s_fy[slot];
+        const int miss = (vm & 7) - 1;
+        const float* p00 = base + (int64_t)i00 * C;
+        const float* p10 = base + (int64_t)s_idx[NIDX > 1 ? 1 : 0][slot] * C;
+        const float* p01 = base + (int64_t)s_idx[NIDX > 1 ? 2 : 0][slot] * C;
+        const float* p11 = base + (int64_t)s_idx[NIDX > 1 ? 3 : 0][slot] * C;
+        if (!VEC4) {
+            if (miss < 0) return tex_sample_rows<false>(p00, p10, p01, p11, fx, fy);
+            return {cb_corner(*p00, *p10, *p01, *p11, cb_corner_w(fx, fy, miss), miss), 0.0f, 0.0f, 0.0f};
         }
-        if (VEC4) reinterpret_cast<float4*>(o)[e] = make_float4(r[0], r[1], r[2], r[3]);
-        else o[e] = r[0];
-        slot += dq; c += dr;
-        if (c >= CV) { c -= CV; slot++; }
-    }
+        const TexQuad t00 = tex_load_row<VEC4>(p00), t10 = tex_load_row<VEC4>(p10), t01 = tex_load_row<VEC4>(p01), t11 = tex_load_row<VEC4>(p11);
+        if (miss < 0) return tex_blend_rows<VEC4>(t00, t10, t01, t11, fx, fy);
+        const CornerW cw = cb_corner_w(fx, fy, miss);
+        return {cb_corner(t00.x, t10.x, t01.x, t11.x, cw, miss), cb_corner(t00.y, t10.y, t01.y, t11.y, cw, miss),
+                cb_corner(t00.z, t10.z, t01.z, t11.z, cw, miss), cb_corner(t00.w, t10.w, t01.w, t11.w, cw, miss)};
+    });
 }
 
-// one channel's terms of d out / d fx . g and d out / d fy . g with all four taps
-__device__ __forceinline__ void cb_dir_term(float t00, float t10, float t01, float t11, float g, float fx, float fy, float& su, float& sv) {
-    const float d0 = t10 - t00, d1 = t11 - t01;
-    const float a = t00 + fx * d0, b = t01 + fx * d1;
-    su += g * (d0 + fy * (d1 - d0));
-    sv += g * (b - a);
-}
-
-// ... and at a corner: out = sum_k w_k t_k / W, d out / d fx = sum_k (dw_k / dfx) (t_k - out) / W (the 1 / W is applied to the sums)
+// the uv terms (tex_uv_term) at a corner: out = sum_k w_k t_k / W, d out / d fx = sum_k (dw_k / dfx) (t_k - out) / W (the 1 / W is applied to the sums)
 struct CornerD { float x0, x1, x2, x3, y0, y1, y2, y3; };
 __device__ __forceinline__ void cb_dir_term_corner(float t0, float t1, float t2, float t3, float g, const CornerW& cw, const CornerD& d,
                                                    int miss, float& su, float& sv) {
@@ -248,15 +201,15 @@ __device__ __forceinline__ void cb_dir_term_corner(float t0, float t1, float t2,
 // (linear only: the entry point zero-fills dL_ddir for nearest.)  VEC4 as in k_texture_cube: the sums run over the channels in
 // the same order either way.
 template <bool VEC4>
-__global__ void __launch_bounds__(CB_BLOCK)
+__global__ void __launch_bounds__(TEX_BLOCK)
 k_texture_cube_bwd_dir(CubeSizes z, const int32_t* __restrict__ layers, const float* __restrict__ dirs, const float* __restrict__ tex,
                        const float* __restrict__ g, float* __restrict__ dL_ddir) {
-    const int64_t s = (int64_t)blockIdx.x * CB_BLOCK + threadIdx.x;
+    const int64_t s = (int64_t)blockIdx.x * TEX_BLOCK + threadIdx.x;
     if (s >= z.S) return;
     CubeTap tap;
     CubeFace f;
     float dx = 0.0f, dy = 0.0f, dz = 0.0f;
-    if (cube_tap<CB_LINEAR>(z, s, layers, dirs, tap, f)) {
+    if (cube_tap<TEX_LINEAR>(z, s, layers, dirs, tap, f)) {
         const int C = z.C, miss = tap.miss;
         const float* base = tex + (z.view_textures ? (s / z.per_view) * z.texels * C : 0);
         const float* p00 = base + (int64_t)tap.idx[0] * C;
@@ -272,13 +225,13 @@ k_texture_cube_bwd_dir(CubeSizes z, const int32_t* __restrict__ layers, const fl
                     const float4 t00 = *reinterpret_cast<const float4*>(p00 + c), t10 = *reinterpret_cast<const float4*>(p10 + c);
                     const float4 t01 = *reinterpret_cast<const float4*>(p01 + c), t11 = *reinterpret_cast<const float4*>(p11 + c);
                     const float4 gv = *reinterpret_cast<const float4*>(gs + c);
-                    cb_dir_term(t00.x, t10.x, t01.x, t11.x, gv.x, fx, fy, su, sv);
-                    cb_dir_term(t00.y, t10.y, t01.y, t11.y, gv.y, fx, fy, su, sv);
-                    cb_dir_term(t00.z, t10.z, t01.z, t11.z, gv.z, fx, fy, su, sv);
-                    cb_dir_term(t00.w, t10.w, t01.w, t11.w, gv.w, fx, fy, su, sv);
+                    tex_uv_term(t00.x, t10.x, t01.x, t11.x, gv.x, fx, fy, su, sv);
+                    tex_uv_term(t00.y, t10.y, t01.y, t11.y, gv.y, fx, fy, su, sv);
+                    tex_uv_term(t00.z, t10.z, t01.z, t11.z, gv.z, fx, fy, su, sv);
+                    tex_uv_term(t00.w, t10.w, t01.w, t11.w, gv.w, fx, fy, su, sv);
                 }
             } else {
-                for (int c = 0; c < C; c++) cb_dir_term(p00[c], p10[c], p01[c], p11[c], gs[c], fx, fy, su, sv);
+                for (int c = 0; c < C; c++) tex_uv_term(p00[c], p10[c], p01[c], p11[c], gs[c], fx, fy, su, sv);
             }
         } else {
             const CornerW cw = cb_corner_w(fx, fy, miss);
@@ -307,9 +260,8 @@ template <int FILTER, int CH>
 __global__ void __launch_bounds__(TILE_PIX)
 k_texture_cube_bwd_tex(CubeSizes z, const int32_t* __restrict__ layers, const float* __restrict__ dirs, const float* __restrict__ g,
                        float* __restrict__ dL_dtex) {
-    constexpr int NTAP = FILTER == CB_LINEAR ? 4 : 1;
-    constexpr int STRIDE = LC_SLOTS + (64 + CH - 1) / CH;                     // flush: bank = (c * (64 / CH) + slot) % 64
-    __shared__ FaceTable<float, CH, STRIDE> tab;
+    constexpr int NTAP = FILTER == TEX_LINEAR ? 4 : 1;
+    __shared__ TexTable<CH> tab;
     const int b = blockIdx.z, tid = threadIdx.x;
     const TilePixel t = tile_pixel(tid, z.W, z.H);
     const int C = z.C, L = z.L;
@@ -324,60 +276,28 @@ k_texture_cube_bwd_tex(CubeSizes z, const int32_t* __restrict__ layers, const fl
             const CornerW cw = cb_corner_w(tap.fx, tap.fy, tap.miss);
             w[0] = cw.w0 / cw.W; w[1] = cw.w1 / cw.W; w[2] = cw.w2 / cw.W; w[3] = cw.w3 / cw.W;
         }
-        tab.clear_keys(tid);
-        for (int c0 = 0; c0 < C; c0 += CH) {
-            const int nc = min(CH, C - c0);
-            tab.clear_acc(tid);
-            __syncthreads();
-            if (live) {
-                float gv[CH];
-#pragma unroll
-                for (int c = 0; c < CH; c++) gv[c] = c < nc ? g[s * C + c0 + c] : 0.0f;
-#pragma unroll
-                for (int k = 0; k < NTAP; k++) {
-                    if (k == tap.miss) continue;                              // (no texel: its idx is another tap's)
-                    const int key = tap.idx[k];
-                    const float wk = FILTER == CB_LINEAR ? w[k] : 1.0f;
-                    const int slot = tab.slot(key);
-#pragma unroll
-                    for (int c = 0; c < CH; c++) {
-                        if (c >= nc) continue;
-                        const float v = wk * gv[c];
-                        if (slot >= 0) tab.add(slot, c, v);
-                        else atomicAdd(dst + (int64_t)key * C + c0 + c, v);
-                    }
-                }
-            }
-            __syncthreads();
-            // flush: one global atomic per (texel, channel) the table holds; lane -> (slot, c), c fastest
-            tab.flush_by_slot(tid, [&](int key, int c, float v) {
-                if (c < nc) atomicAdd(dst + (int64_t)key * C + c0 + c, v);
-            });
-            __syncthreads();
-        }
+        const float one[1] = {1.0f};
+        tex_scatter_layer<CH, NTAP, false>(tab, tid, live, tap.idx, FILTER == TEX_LINEAR ? w : one, NTAP, tap.miss, g, s, C,
+                                           [&](int key) { return dst + (int64_t)key * C; });    // (miss: no texel, its idx is another tap's)
     }
 }
 
 static CubeSizes cb_sizes(int B, int H, int W, int L, int N, int C, int view_textures) {
     CubeSizes z;
-    z.per_view = (int64_t)H * W * L;
-    z.S = (int64_t)B * z.per_view;
+    tex_common_sizes(z, B, H, W, L, C, view_textures);
     z.texels = (int64_t)6 * N * N;
-    z.B = B; z.H = H; z.W = W; z.L = L; z.N = N; z.C = C; z.view_textures = view_textures;
+    z.N = N;
     return z;
 }
-
-static bool cb_aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
 void launch_texture_cube(int B, int H, int W, int L, int N, int C, int view_textures, int filter, const int32_t* render_layers,
                          const float* dirs, const float* tex, float* out, hipStream_t st) {
     const CubeSizes z = cb_sizes(B, H, W, L, N, C, view_textures);
-    const dim3 grid((unsigned)((z.S + CB_BLOCK - 1) / CB_BLOCK));
-    const bool vec4 = C % 4 == 0 && cb_aligned16(tex, out);
-#define DM2_CB_FWD(F)                                                                                                        \
-    if (vec4) hipLaunchKernelGGL((k_texture_cube<F, true>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, out);  \
-    else hipLaunchKernelGGL((k_texture_cube<F, false>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, out)
-    if (filter == CB_LINEAR) { DM2_CB_FWD(CB_LINEAR); } else { DM2_CB_FWD(CB_NEAREST); }
+    const dim3 grid = tex_flat_grid(z.S);
+    const bool vec4 = C % 4 == 0 && tex_aligned16(tex, out);
+#define DM2_CB_FWD(F, V4) hipLaunchKernelGGL((k_texture_cube<F, V4>), grid, dim3(TEX_BLOCK), 0, st, z, render_layers, dirs, tex, out)
+    if (filter == TEX_LINEAR) { if (vec4) DM2_CB_FWD(TEX_LINEAR, true); else DM2_CB_FWD(TEX_LINEAR, false); }
+    else { if (vec4) DM2_CB_FWD(TEX_NEAREST, true); else DM2_CB_FWD(TEX_NEAREST, false); }
 #undef DM2_CB_FWD
 }
 
@@ -386,23 +306,17 @@ void launch_texture_cube_backward(int B, int H, int W, int L, int N, int C, int 
                                   float* dL_dtex, float* dL_ddir, hipStream_t st) {
     const CubeSizes z = cb_sizes(B, H, W, L, N, C, view_textures);
     if (dL_ddir) {
-        const dim3 grid((unsigned)((z.S + CB_BLOCK - 1) / CB_BLOCK));       // (linear: the entry point zero-fills for nearest)
-        if (C % 4 == 0 && cb_aligned16(tex, dL_dout))
-            hipLaunchKernelGGL((k_texture_cube_bwd_dir<true>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, dL_dout, dL_ddir);
+        const dim3 grid = tex_flat_grid(z.S);                               // (linear: the entry point zero-fills for nearest)
+        if (C % 4 == 0 && tex_aligned16(tex, dL_dout))
+            hipLaunchKernelGGL((k_texture_cube_bwd_dir<true>), grid, dim3(TEX_BLOCK), 0, st, z, render_layers, dirs, tex, dL_dout, dL_ddir);
         else
-            hipLaunchKernelGGL((k_texture_cube_bwd_dir<false>), grid, dim3(CB_BLOCK), 0, st, z, render_layers, dirs, tex, dL_dout, dL_ddir);
+            hipLaunchKernelGGL((k_texture_cube_bwd_dir<false>), grid, dim3(TEX_BLOCK), 0, st, z, render_layers, dirs, tex, dL_dout, dL_ddir);
     }
     if (dL_dtex) {
         const dim3 grid = tile_grid(W, H, B);
-#define DM2_CB_TEX_CH(F, CH) hipLaunchKernelGGL((k_texture_cube_bwd_tex<F, CH>), grid, dim3(TILE_PIX), 0, st, z, render_layers, dirs, dL_dout, dL_dtex)
-#define DM2_CB_TEX(F)                       \
-    if (C == 1) DM2_CB_TEX_CH(F, 1);        \
-    else if (C == 2) DM2_CB_TEX_CH(F, 2);   \
-    else if (C == 3) DM2_CB_TEX_CH(F, 3);   \
-    else DM2_CB_TEX_CH(F, CB_CH)
-        if (filter == CB_LINEAR) { DM2_CB_TEX(CB_LINEAR); } else { DM2_CB_TEX(CB_NEAREST); }
+#define DM2_CB_TEX(F, CH) hipLaunchKernelGGL((k_texture_cube_bwd_tex<F, CH>), grid, dim3(TILE_PIX), 0, st, z, render_layers, dirs, dL_dout, dL_dtex)
+        if (filter == TEX_LINEAR) DM2_TEX_CHUNK(C, DM2_CB_TEX, TEX_LINEAR); else DM2_TEX_CHUNK(C, DM2_CB_TEX, TEX_NEAREST);
 #undef DM2_CB_TEX
-#undef DM2_CB_TEX_CH
     }
 }
 

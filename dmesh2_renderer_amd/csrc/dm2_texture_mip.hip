@@ -8,8 +8,8 @@
 //
 // Contract: include/dm2_hip.h, dm2_texture_mipmaps / dm2_texture_mip.  The level of detail comes from the float's bits (log2
 // with the mantissa taken linearly: no transcendental), so the forward is a pure function of IEEE operations.
-// -ffp-contract=off: the written operation order is the result.  The sampling of one level is dm2_texture's (tx_tap /
-// tx_bilinear of dm2_texture.hip, restated here: that file's kernels stay as they are).
+// -ffp-contract=off: the written operation order is the result.  The sampling of one level is dm2_texture's: both take it from
+// dm2_tex_core.h (the taps and fractions of one level, the blend, the uv terms, the sweep, the scatter).
 //
 // A texel of any level has one index in a single space: level 0's j * Wt + i first, then the packed chain (texels + off_k +
 // j * W_k + i).  The forward stages those indices, the scatter keys its LDS table by them.
@@ -17,20 +17,18 @@
 // Forward: the kernel of dm2_texture.hip with twice the taps: flat slots, 256 per block, each lane stages its slot's eight
 // indices, the fractions of the two levels and f in LDS, then the block sweeps its 256 * C outputs with consecutive lanes on
 // consecutive channels (four per lane on the vector path).
-// tex backward: k_texture_bwd_tex's tile scatter (one block per 16 x 16 tile and view, one layer at a time, channel chunks of
-// CH, the FaceTable cleared per layer) with up to eight (texel, weight) pairs per slot.
+// tex backward: k_texture_bwd_tex's tile scatter (tex_scatter_layer: one block per 16 x 16 tile and view, one layer at a time,
+// channel chunks of CH, the FaceTable cleared per layer) with up to eight (texel, weight) pairs per slot; the two gradient
+// tensors, either of which may be absent, are behind the one key space.
 #include <hip/hip_runtime.h>
 
 #include "dm2_device_math.h"
 #include "dm2_face_table.h"
 #include "dm2_state.h"
+#include "dm2_tex_core.h"
 
 namespace dm2 {
 
-constexpr int TM_BLOCK = 256;
-constexpr int TM_CH = 4;
-constexpr int TM_WRAP = 0, TM_CLAMP = 1;              // DM2_TEX_BOUNDARY_*
-constexpr float TM_RANGE = 16777216.0f;               // 2^24, as dm2_texture
 constexpr int TM_MAX_LEVELS = 16;                     // Ht * Wt < 2^31 with both extents even at every step: at most 16 levels
 
 struct MipSizes {
@@ -57,25 +55,12 @@ __device__ __forceinline__ void tm_offsets(const MipSizes& z, int* s_off, int ti
     }
 }
 
-template <int BOUNDARY>
-__device__ __forceinline__ int tm_addr(int i, int n) {
-    if (BOUNDARY == TM_CLAMP) return min(max(i, 0), n - 1);
-    const int r = i % n;
-    return r < 0 ? r + n : r;
-}
-
 // level k's taps at (u, v): dm2_texture's linear stage with that level's extents (W_k = Wt >> k: every step halved an even extent)
 template <int BOUNDARY>
 __device__ __forceinline__ void tm_level(const MipSizes& z, const int* s_off, int k, float u, float v, int (&idx)[4], float& fx, float& fy) {
     const int Wk = z.Wt >> k, Hk = z.Ht >> k;
     const float x = u * (float)Wk - 0.5f, y = v * (float)Hk - 0.5f;
-    const float x0 = floorf(x), y0 = floorf(y);
-    fx = x - x0; fy = y - y0;
-    const int i0 = (int)x0, j0 = (int)y0;
-    const int base = k == 0 ? 0 : (int)z.texels + s_off[k];
-    const int a0 = tm_addr<BOUNDARY>(i0, Wk), a1 = tm_addr<BOUNDARY>(i0 + 1, Wk);
-    const int r0 = base + tm_addr<BOUNDARY>(j0, Hk) * Wk, r1 = base + tm_addr<BOUNDARY>(j0 + 1, Hk) * Wk;
-    idx[0] = r0 + a0; idx[1] = r0 + a1; idx[2] = r1 + a0; idx[3] = r1 + a1;
+    tex_linear_taps<BOUNDARY>(Wk, Hk, k == 0 ? 0 : (int)z.texels + s_off[k], x, y, idx, fx, fy);
 }
 
 __device__ __forceinline__ bool tm_finite(float a) { return fabsf(a) < __builtin_inff(); }
@@ -87,7 +72,7 @@ __device__ __forceinline__ bool tm_tap(const MipSizes& z, const int* s_off, int6
     if (layers && layers[s] < 0) return false;
     const float u = uv[2 * s], v = uv[2 * s + 1];
     const float x = u * (float)z.Wt - 0.5f, y = v * (float)z.Ht - 0.5f;
-    if (!(fabsf(x) < TM_RANGE) || !(fabsf(y) < TM_RANGE)) return false;          // level 0's rule: NaN and infinities included
+    if (!(fabsf(x) < TEX_RANGE) || !(fabsf(y) < TEX_RANGE)) return false;          // level 0's rule: NaN and infinities included
     const float dudx = uv_da[4 * s], dvdx = uv_da[4 * s + 1], dudy = uv_da[4 * s + 2], dvdy = uv_da[4 * s + 3];
     if (!(tm_finite(dudx) && tm_finite(dvdx) && tm_finite(dudy) && tm_finite(dvdy))) return false;
     const float ax = dudx * (float)z.Wt, bx = dvdx * (float)z.Ht, sx = ax * ax + bx * bx;
@@ -116,11 +101,6 @@ __device__ __forceinline__ bool tm_tap(const MipSizes& z, const int* s_off, int6
     return true;
 }
 
-__device__ __forceinline__ float tm_bilinear(float t00, float t10, float t01, float t11, float fx, float fy) {
-    const float a = t00 + fx * (t10 - t00), b = t01 + fx * (t11 - t01);
-    return a + fy * (b - a);
-}
-
 // the row of single-space texel ``key``: level 0 in tex, the rest in the chain (texv, mipv: the view's own where per view)
 __device__ __forceinline__ const float* tm_row(const MipSizes& z, const float* texv, const float* mipv, int key) {
     return key < (int)z.texels ? texv + (int64_t)key * z.C : mipv + ((int64_t)key - z.texels) * z.C;
@@ -129,34 +109,23 @@ __device__ __forceinline__ const float* tm_row(const MipSizes& z, const float* t
 template <bool VEC4>
 __device__ __forceinline__ void tm_sample(const MipSizes& z, const float* texv, const float* mipv, int i00, int i10, int i01, int i11,
                                           int c, float fx, float fy, float (&r)[4]) {
-    const float* p00 = tm_row(z, texv, mipv, i00) + c;
-    const float* p10 = tm_row(z, texv, mipv, i10) + c;
-    const float* p01 = tm_row(z, texv, mipv, i01) + c;
-    const float* p11 = tm_row(z, texv, mipv, i11) + c;
-    if (VEC4) {
-        const float4 t00 = *reinterpret_cast<const float4*>(p00), t10 = *reinterpret_cast<const float4*>(p10);
-        const float4 t01 = *reinterpret_cast<const float4*>(p01), t11 = *reinterpret_cast<const float4*>(p11);
-        r[0] = tm_bilinear(t00.x, t10.x, t01.x, t11.x, fx, fy);
-        r[1] = tm_bilinear(t00.y, t10.y, t01.y, t11.y, fx, fy);
-        r[2] = tm_bilinear(t00.z, t10.z, t01.z, t11.z, fx, fy);
-        r[3] = tm_bilinear(t00.w, t10.w, t01.w, t11.w, fx, fy);
-    } else {
-        r[0] = tm_bilinear(*p00, *p10, *p01, *p11, fx, fy);
-    }
+    const TexQuad q = tex_sample_rows<VEC4>(tm_row(z, texv, mipv, i00) + c, tm_row(z, texv, mipv, i10) + c, tm_row(z, texv, mipv, i01) + c,
+                                            tm_row(z, texv, mipv, i11) + c, fx, fy);
+    r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
 }
 
 // VEC4: C is a multiple of 4 and tex / mip / out are 16-byte aligned; every channel goes through the same operations either way.
 template <int BOUNDARY, bool VEC4>
-__global__ void __launch_bounds__(TM_BLOCK)
+__global__ void __launch_bounds__(TEX_BLOCK)
 k_texture_mip(MipSizes z, const int32_t* __restrict__ layers, const float* __restrict__ uv, const float* __restrict__ uv_da,
               const float* __restrict__ tex, const float* __restrict__ mip, float* __restrict__ out) {
-    __shared__ int s_idx[8][TM_BLOCK];                                        // s_idx[0] < 0: empty slot
-    __shared__ float s_fx[2][TM_BLOCK], s_fy[2][TM_BLOCK], s_f[TM_BLOCK];
-    __shared__ int s_view[TM_BLOCK];
+    __shared__ int s_idx[8][TEX_BLOCK];                                        // s_idx[0] < 0: empty slot
+    __shared__ float s_fx[2][TEX_BLOCK], s_fy[2][TEX_BLOCK], s_f[TEX_BLOCK];
+    __shared__ int s_view[TEX_BLOCK];
     __shared__ int s_off[TM_MAX_LEVELS];
     const int tid = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * TM_BLOCK;
-    const int nslots = (int)min((int64_t)TM_BLOCK, z.S - s0);
+    const int64_t s0 = (int64_t)blockIdx.x * TEX_BLOCK;
+    const int nslots = (int)min((int64_t)TEX_BLOCK, z.S - s0);
     tm_offsets(z, s_off, tid);
     __syncthreads();
     if (tid < nslots) {
@@ -173,12 +142,13 @@ k_texture_mip(MipSizes z, const int32_t* __restrict__ layers, const float* __res
         s_view[tid] = z.view_textures ? (int)(s / z.per_view) : 0;
     }
     __syncthreads();
+    // (tex_sweep's loop, written out: through tex_sweep the two view offsets compile to other instructions than they were)
     constexpr int V = VEC4 ? 4 : 1;
     const int C = z.C, CV = C / V, total = nslots * CV;                      // lane -> (slot, group of V channels), group fastest
-    const int dq = TM_BLOCK / CV, dr = TM_BLOCK - dq * CV;
+    const int dq = TEX_BLOCK / CV, dr = TEX_BLOCK - dq * CV;
     int slot = tid / CV, c = tid - slot * CV;
     float* o = out + s0 * C;
-    for (int e = tid; e < total; e += TM_BLOCK) {
+    for (int e = tid; e < total; e += TEX_BLOCK) {
         const int i00 = s_idx[0][slot];
         float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (i00 >= 0) {
@@ -209,24 +179,18 @@ __device__ __forceinline__ void tm_uv_level(const MipSizes& z, const float* texv
     const float* p01 = tm_row(z, texv, mipv, idx[2]);
     const float* p11 = tm_row(z, texv, mipv, idx[3]);
     su = 0.0f; sv = 0.0f;
-    for (int c = 0; c < z.C; c++) {
-        const float t00 = p00[c], t10 = p10[c], t01 = p01[c], t11 = p11[c], g = gs[c];
-        const float d0 = t10 - t00, d1 = t11 - t01;
-        const float a = t00 + fx * d0, b = t01 + fx * d1;
-        su += g * (d0 + fy * (d1 - d0));
-        sv += g * (b - a);
-    }
+    for (int c = 0; c < z.C; c++) tex_uv_term(p00[c], p10[c], p01[c], p11[c], gs[c], fx, fy, su, sv);
 }
 
 template <int BOUNDARY>
-__global__ void __launch_bounds__(TM_BLOCK)
+__global__ void __launch_bounds__(TEX_BLOCK)
 k_texture_mip_bwd_uv(MipSizes z, const int32_t* __restrict__ layers, const float* __restrict__ uv, const float* __restrict__ uv_da,
                      const float* __restrict__ tex, const float* __restrict__ mip, const float* __restrict__ g,
                      float* __restrict__ dL_duv) {
     __shared__ int s_off[TM_MAX_LEVELS];
     tm_offsets(z, s_off, threadIdx.x);
     __syncthreads();
-    const int64_t s = (int64_t)blockIdx.x * TM_BLOCK + threadIdx.x;
+    const int64_t s = (int64_t)blockIdx.x * TEX_BLOCK + threadIdx.x;
     if (s >= z.S) return;
     MipTap tap;
     float du = 0.0f, dv = 0.0f;
@@ -256,8 +220,7 @@ template <int BOUNDARY, int CH>
 __global__ void __launch_bounds__(TILE_PIX)
 k_texture_mip_bwd_tex(MipSizes z, const int32_t* __restrict__ layers, const float* __restrict__ uv, const float* __restrict__ uv_da,
                       const float* __restrict__ g, float* __restrict__ dL_dtex, float* __restrict__ dL_dmip) {
-    constexpr int STRIDE = LC_SLOTS + (64 + CH - 1) / CH;                     // flush: bank = (c * (64 / CH) + slot) % 64
-    __shared__ FaceTable<float, CH, STRIDE> tab;
+    __shared__ TexTable<CH> tab;
     __shared__ int s_off[TM_MAX_LEVELS];
     const int b = blockIdx.z, tid = threadIdx.x;
     const TilePixel t = tile_pixel(tid, z.W, z.H);
@@ -286,48 +249,16 @@ k_texture_mip_bwd_tex(MipSizes z, const int32_t* __restrict__ layers, const floa
             w[lv][0] = wl[lv] * ((1.0f - fx) * (1.0f - fy)); w[lv][1] = wl[lv] * (fx * (1.0f - fy));
             w[lv][2] = wl[lv] * ((1.0f - fx) * fy); w[lv][3] = wl[lv] * (fx * fy);
         }
-        tab.clear_keys(tid);
-        for (int c0 = 0; c0 < C; c0 += CH) {
-            const int nc = min(CH, C - c0);
-            tab.clear_acc(tid);
-            __syncthreads();
-            if (live) {
-                float gv[CH];
-#pragma unroll
-                for (int c = 0; c < CH; c++) gv[c] = c < nc ? g[s * C + c0 + c] : 0.0f;
-#pragma unroll
-                for (int lv = 0; lv < 2; lv++) {
-                    if (lv == 1 && !two) continue;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const int key = tap.idx[lv][k];
-                        float* dst = row(key);
-                        if (!dst) continue;
-                        const int slot = tab.slot(key);
-#pragma unroll
-                        for (int c = 0; c < CH; c++) {
-                            if (c >= nc) continue;
-                            const float v = w[lv][k] * gv[c];
-                            if (slot >= 0) tab.add(slot, c, v);
-                            else atomicAdd(dst + c0 + c, v);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            tab.flush_by_slot(tid, [&](int key, int c, float v) {
-                if (c < nc) atomicAdd(row(key) + c0 + c, v);                   // (a held key's gradient is wanted: see above)
-            });
-            __syncthreads();
-        }
+        // (the eight pairs as flat lists: tap.idx and w are [2][4], level j's four first)
+        tex_scatter_layer<CH, 8, true>(tab, tid, live, &tap.idx[0][0], &w[0][0], two ? 8 : 4, -1, g, s, C, row);
     }
 }
 
 // level k+1 from level k of every texture: lane -> (texel, channel), channel fastest; the view on blockIdx.y
-__global__ void __launch_bounds__(TM_BLOCK)
+__global__ void __launch_bounds__(TEX_BLOCK)
 k_mip_level(int64_t n /* H1 * W1 * C */, int W1, int C, const float* __restrict__ src, int64_t src_stride, float* __restrict__ dst,
             int64_t dst_stride) {
-    const int64_t e = (int64_t)blockIdx.x * TM_BLOCK + threadIdx.x;
+    const int64_t e = (int64_t)blockIdx.x * TEX_BLOCK + threadIdx.x;
     if (e >= n) return;
     const int64_t t = e / C;
     const int c = (int)(e - t * C);
@@ -339,10 +270,10 @@ k_mip_level(int64_t n /* H1 * W1 * C */, int W1, int C, const float* __restrict_
 }
 
 // lane -> (texel of level 0, channel); acc = acc + 0.25^k g_k over the levels in order
-__global__ void __launch_bounds__(TM_BLOCK)
+__global__ void __launch_bounds__(TEX_BLOCK)
 k_mip_backward(int64_t n /* Ht * Wt * C */, int Ht, int Wt, int C, int nlev, int64_t T, const float* __restrict__ dL_dmip,
                float* __restrict__ dL_dtex) {
-    const int64_t e = (int64_t)blockIdx.x * TM_BLOCK + threadIdx.x;
+    const int64_t e = (int64_t)blockIdx.x * TEX_BLOCK + threadIdx.x;
     if (e >= n) return;
     const int64_t t = e / C;
     const int c = (int)(e - t * C);
@@ -374,11 +305,10 @@ int mip_levels(int Ht, int Wt, int max_level, int64_t* T) {
 
 static MipSizes tm_sizes(int B, int H, int W, int L, int Ht, int Wt, int C, int view_textures, int max_level) {
     MipSizes z;
-    z.per_view = (int64_t)H * W * L;
-    z.S = (int64_t)B * z.per_view;
+    tex_common_sizes(z, B, H, W, L, C, view_textures);
     z.texels = (int64_t)Ht * Wt;
     z.nlev = mip_levels(Ht, Wt, max_level, &z.T);
-    z.B = B; z.H = H; z.W = W; z.L = L; z.Ht = Ht; z.Wt = Wt; z.C = C; z.view_textures = view_textures;
+    z.Ht = Ht; z.Wt = Wt;
     return z;
 }
 
@@ -391,8 +321,7 @@ void launch_texture_mipmaps(int NB, int Ht, int Wt, int C, int max_level, const 
         const int W1 = Wt >> k, H1 = Ht >> k;
         const int64_t n = (int64_t)H1 * W1 * C;
         float* dst = mip + off * C;
-        const dim3 grid((unsigned)((n + TM_BLOCK - 1) / TM_BLOCK), (unsigned)NB);
-        hipLaunchKernelGGL(k_mip_level, grid, dim3(TM_BLOCK), 0, st, n, W1, C, src, src_stride, dst, T * C);
+        hipLaunchKernelGGL(k_mip_level, tex_flat_grid(n, NB), dim3(TEX_BLOCK), 0, st, n, W1, C, src, src_stride, dst, T * C);
         src = dst; src_stride = T * C;
         off += (int64_t)H1 * W1;
     }
@@ -402,21 +331,18 @@ void launch_texture_mipmaps_backward(int NB, int Ht, int Wt, int C, int max_leve
     int64_t T;
     const int nlev = mip_levels(Ht, Wt, max_level, &T);
     const int64_t n = (int64_t)Ht * Wt * C;
-    const dim3 grid((unsigned)((n + TM_BLOCK - 1) / TM_BLOCK), (unsigned)NB);
-    hipLaunchKernelGGL(k_mip_backward, grid, dim3(TM_BLOCK), 0, st, n, Ht, Wt, C, nlev, T, dL_dmip, dL_dtex);
+    hipLaunchKernelGGL(k_mip_backward, tex_flat_grid(n, NB), dim3(TEX_BLOCK), 0, st, n, Ht, Wt, C, nlev, T, dL_dmip, dL_dtex);
 }
-
-static bool tm_aligned16(const void* a, const void* b, const void* c) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0; }
 
 void launch_texture_mip(int B, int H, int W, int L, int Ht, int Wt, int C, int view_textures, int boundary, int max_level,
                         const int32_t* render_layers, const float* uv, const float* uv_da, const float* tex, const float* mip,
                         float* out, hipStream_t st) {
     const MipSizes z = tm_sizes(B, H, W, L, Ht, Wt, C, view_textures, max_level);
-    const dim3 grid((unsigned)((z.S + TM_BLOCK - 1) / TM_BLOCK));
-    const bool vec4 = C % 4 == 0 && tm_aligned16(tex, out, mip);
-#define DM2_TM_FWD(Bd, V4) hipLaunchKernelGGL((k_texture_mip<Bd, V4>), grid, dim3(TM_BLOCK), 0, st, z, render_layers, uv, uv_da, tex, mip, out)
-    if (boundary == TM_WRAP) { if (vec4) DM2_TM_FWD(TM_WRAP, true); else DM2_TM_FWD(TM_WRAP, false); }
-    else { if (vec4) DM2_TM_FWD(TM_CLAMP, true); else DM2_TM_FWD(TM_CLAMP, false); }
+    const dim3 grid = tex_flat_grid(z.S);
+    const bool vec4 = C % 4 == 0 && tex_aligned16(tex, out, mip);
+#define DM2_TM_FWD(Bd, V4) hipLaunchKernelGGL((k_texture_mip<Bd, V4>), grid, dim3(TEX_BLOCK), 0, st, z, render_layers, uv, uv_da, tex, mip, out)
+    if (boundary == TEX_WRAP) { if (vec4) DM2_TM_FWD(TEX_WRAP, true); else DM2_TM_FWD(TEX_WRAP, false); }
+    else { if (vec4) DM2_TM_FWD(TEX_CLAMP, true); else DM2_TM_FWD(TEX_CLAMP, false); }
 #undef DM2_TM_FWD
 }
 
@@ -426,22 +352,16 @@ void launch_texture_mip_backward(int B, int H, int W, int L, int Ht, int Wt, int
                                  hipStream_t st) {
     const MipSizes z = tm_sizes(B, H, W, L, Ht, Wt, C, view_textures, max_level);
     if (dL_duv) {
-        const dim3 grid((unsigned)((z.S + TM_BLOCK - 1) / TM_BLOCK));
-#define DM2_TM_UV(Bd) hipLaunchKernelGGL((k_texture_mip_bwd_uv<Bd>), grid, dim3(TM_BLOCK), 0, st, z, render_layers, uv, uv_da, tex, mip, dL_dout, dL_duv)
-        if (boundary == TM_WRAP) DM2_TM_UV(TM_WRAP); else DM2_TM_UV(TM_CLAMP);
+        const dim3 grid = tex_flat_grid(z.S);
+#define DM2_TM_UV(Bd) hipLaunchKernelGGL((k_texture_mip_bwd_uv<Bd>), grid, dim3(TEX_BLOCK), 0, st, z, render_layers, uv, uv_da, tex, mip, dL_dout, dL_duv)
+        if (boundary == TEX_WRAP) DM2_TM_UV(TEX_WRAP); else DM2_TM_UV(TEX_CLAMP);
 #undef DM2_TM_UV
     }
     if (dL_dtex || dL_dmip) {
         const dim3 grid = tile_grid(W, H, B);
-#define DM2_TM_TEX_CH(Bd, CH) hipLaunchKernelGGL((k_texture_mip_bwd_tex<Bd, CH>), grid, dim3(TILE_PIX), 0, st, z, render_layers, uv, uv_da, dL_dout, dL_dtex, dL_dmip)
-#define DM2_TM_TEX(Bd)                      \
-    if (C == 1) DM2_TM_TEX_CH(Bd, 1);       \
-    else if (C == 2) DM2_TM_TEX_CH(Bd, 2);  \
-    else if (C == 3) DM2_TM_TEX_CH(Bd, 3);  \
-    else DM2_TM_TEX_CH(Bd, TM_CH)
-        if (boundary == TM_WRAP) { DM2_TM_TEX(TM_WRAP); } else { DM2_TM_TEX(TM_CLAMP); }
+#define DM2_TM_TEX(Bd, CH) hipLaunchKernelGGL((k_texture_mip_bwd_tex<Bd, CH>), grid, dim3(TILE_PIX), 0, st, z, render_layers, uv, uv_da, dL_dout, dL_dtex, dL_dmip)
+        if (boundary == TEX_WRAP) DM2_TEX_CHUNK(C, DM2_TM_TEX, TEX_WRAP); else DM2_TEX_CHUNK(C, DM2_TM_TEX, TEX_CLAMP);
 #undef DM2_TM_TEX
-#undef DM2_TM_TEX_CH
     }
 }
 

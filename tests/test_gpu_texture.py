@@ -156,6 +156,24 @@ def test_gradient_grid_covers_every_axis():
     assert [len(s) for s in seen] == [len(CS), 2, 2, len(LS), len(SIZES), 3]
 
 
+@pytest.mark.parametrize("C", ref.INST_CS)
+def test_every_instantiation_once(C):
+    """Both filters x both boundary modes x shared and per-view textures at this C on texture_ref.instantiation_case() (the
+    gradient grid above is thinned: C and the boundary mode move together there): every instantiation of the three kernels that
+    C selects, at the smallest shape with two views, partial tiles, two layers and empty slots in every tile."""
+    uv, rl = ref.instantiation_case()
+    bad = ref.empty(uv, 5, 3, rl)
+    rng = np.random.default_rng(700 + C)
+    g = rng.standard_normal(uv.shape[:4] + (C,), dtype=np.float32)
+    for per_view in (False, True):
+        tex = _tex(rng, uv.shape[0], (5, 3), C, per_view)
+        for filter_mode, boundary_mode in MODES:
+            what = ("instantiation", C, per_view, filter_mode, boundary_mode)
+            out = _check_forward(uv, tex, rl, filter_mode, boundary_mode, what)
+            assert (out[bad] == 0).all(), what
+            _check_grads(uv, tex, rl, filter_mode, boundary_mode, g, what)
+
+
 @pytest.mark.parametrize("C", [3, 16])
 @pytest.mark.parametrize("boundary_mode", ref.BOUNDARIES)
 def test_table_overflow_route(C, boundary_mode):

@@ -10,6 +10,7 @@ import torch
 
 import rasterize_ref as rref
 import texture_cube_ref as ref
+import texture_ref as ref2d
 import upstream as U
 from util import GRAD_TOL, rel_linf, scenes, summation_bound, table_capacity
 
@@ -203,6 +204,25 @@ def test_gradients_against_float64(k):
     for filter_mode in ref.FILTERS:
         _check_forward(d, tex, rl, filter_mode, (k, filter_mode))
         _check_grads(d, tex, rl, filter_mode, g, GRAD_GRID[k] + (filter_mode,))
+
+
+@pytest.mark.parametrize("C", ref2d.INST_CS)
+def test_every_instantiation_once(C):
+    """Both filters x N = 2 and 5 x shared and per-view cubes at this C on texture_cube_ref.instantiation_case() (the gradient
+    grid above is thinned): every instantiation of the three kernels that C selects, at the smallest shape with two views,
+    partial tiles, two layers, empty slots in every tile, seam taps across every border and corner samples."""
+    rng = np.random.default_rng(900 + C)
+    for N in ref.INST_NS:
+        d, rl = ref.instantiation_case(N)
+        bad = ref.empty(d, rl)
+        g = rng.standard_normal(d.shape[:4] + (C,), dtype=np.float32)
+        for per_view in (False, True):
+            tex = _tex(rng, d.shape[0], N, C, per_view)
+            for filter_mode in ref.FILTERS:
+                what = ("instantiation", C, N, per_view, filter_mode)
+                out = _check_forward(d, tex, rl, filter_mode, what)
+                assert (out[bad] == 0).all(), what
+                _check_grads(d, tex, rl, filter_mode, g, what)
 
 
 SPARSE = [("lattice", 4, 5, True), ("seams", 1, 2, False), ("random", 4, 64, False)]

@@ -417,6 +417,31 @@ def test_channel_and_layer_grid(k):
         _check(uv, da, tex, mip, rl, boundary_mode, None, g, (k, C, per_view, L, size, boundary_mode))
 
 
+@pytest.mark.parametrize("C", tref.INST_CS)
+def test_every_instantiation_once(C):
+    """Both boundary modes x shared and per-view textures at this C on texture_mip_ref.instantiation_case(), with dL/dtex
+    alone, dL/dmip alone and both wanted: every instantiation of the sampling kernels that C selects, and both outcomes of the
+    scatter's absent-destination skip, at the smallest shape with two views, partial tiles, two layers and empty slots in
+    every tile."""
+    uv, da, rl = mref.instantiation_case()
+    size = mref.INST_TEXTURE
+    bad = mref.stage(uv, da, *size, rl)["empty"]
+    rng = np.random.default_rng(800 + C)
+    g = rng.standard_normal(uv.shape[:4] + (C,), dtype=np.float32)
+    for per_view in (False, True):
+        tex = rng.standard_normal(((2,) if per_view else ()) + size + (C,), dtype=np.float32)
+        mip = mref.mipmaps(tex)
+        for boundary_mode in mref.BOUNDARIES:
+            what = ("instantiation", C, per_view, boundary_mode)
+            out, got, want = _check(uv, da, tex, mip, rl, boundary_mode, None, g, what)
+            assert (out[bad] == 0).all(), what
+            args = (_cu(uv), _cu(da), _cu(tex), _cu(mip), _cu(rl), boundary_mode, None, _cu(g))
+            dt, dm, du = _C.texture_mip_backward_cuda(*args, True, False, False)
+            assert dm is None and du is None and rel_linf(_np(dt), want[0]) <= GRAD_TOL, what
+            dt, dm, du = _C.texture_mip_backward_cuda(*args, False, True, False)
+            assert dt is None and du is None and rel_linf(_np(dm), want[1]) <= GRAD_TOL, what
+
+
 def test_grid_covers_every_axis():
     seen = [set() for _ in range(4)]
     for k in range(2 * len(GRID_CS)):

@@ -262,3 +262,18 @@ def test_distinct_texels_per_tile():
     assert ref.distinct_texels_per_tile(uv[:, :, :, :1], 32, 32, None, "linear", "clamp") == 256      # (the last tile: i0 + 1 clamps; the first holds 17 x 17)
     rl = np.full((1, 32, 32, 2), -1, np.int32)
     assert ref.distinct_texels_per_tile(uv, 32, 32, rl) == 0
+
+
+def test_instantiation_inputs_are_what_they_are_for():
+    """The inputs of test_gpu_texture.py's test_every_instantiation_once: every tile has live and empty slots in both layers,
+    empty by a negative id and by a NaN or infinite uv, and the live uv lie on both sides of both borders."""
+    uv, rl = ref.instantiation_case()
+    assert uv.shape == ref.INST_SHAPE + (2,) and rl.shape == ref.INST_SHAPE
+    e = ref.empty(uv, 5, 3, rl)
+    assert ref.tiles_have_live_and_empty(e)
+    assert 0.15 < (rl < 0).mean() < 0.35
+    bad = ~np.isfinite(uv).all(-1)
+    assert bad.sum() == 6 and (rl[bad] >= 0).all() and e[bad].all() and np.isnan(uv).any() and np.isinf(uv).any()
+    assert np.array_equal(e, (rl < 0) | bad)
+    live = uv[~e]
+    assert (live < 0).any(0).all() and (live > 1).any(0).all() and ((live > 0) & (live < 1)).any(0).all()

@@ -316,3 +316,22 @@ def test_distinct_texels_per_tile():
     assert ref.distinct_texels_per_tile(d[:, :, :, 1:], 8, None, "nearest") == 1
     assert ref.distinct_texels_per_tile(d[:, :, :, :1], 1024, None, "linear") > 900
     assert ref.distinct_texels_per_tile(d, 8, np.full((1, 32, 32, 2), -1, np.int32)) == 0
+
+
+@pytest.mark.parametrize("N", ref.INST_NS)
+def test_instantiation_inputs_are_what_they_are_for(N):
+    """The inputs of test_gpu_texture_cube.py's test_every_instantiation_once: every tile has live and empty slots in both
+    layers; a seam-crossing sample across each of the 24 (face, border) pairs; corner samples (a missing tap)."""
+    d, rl = ref.instantiation_case(N)
+    st = ref.stage(d, N, rl, "linear")
+    live = ~st["empty"]
+    assert ref2d.tiles_have_live_and_empty(st["empty"])
+    bad = ~np.isfinite(d).all(-1)
+    assert bad.sum() == 6 and np.array_equal(st["empty"], (rl < 0) | bad)
+    borders = (st["i0"] == -1, st["i0"] == N - 1, st["j0"] == -1, st["j0"] == N - 1)
+    for f in range(6):
+        for k, b in enumerate(borders):
+            assert (live & (st["face"] == f) & b & st["seam"].any(-1)).any(), (N, "face", f, "border", k)
+    corners = int((live & (st["miss"] >= 0)).sum())
+    print("N", N, "seam samples", int((live & st["seam"].any(-1)).sum()), "corner samples", corners)
+    assert corners >= 8 and set(np.unique(st["miss"][live]).tolist()) == {-1, 0, 1, 2, 3}

@@ -381,3 +381,22 @@ def test_lattice_inputs_sit_on_centres_and_borders():
     s = tref.stage(uvr, Ht, Wt, None, "linear", "wrap")
     assert s["x"][0, 0, 0, 0] == f32(2.0 ** 24 - 2) and s["y"][0, 1, 0, 0] == f32(2.0 ** 24 - 2)     # the largest a slot can have
     assert e.sum() == 2 * (~live).sum()
+
+
+def test_instantiation_inputs_are_what_they_are_for():
+    """The inputs of test_gpu_texture_mip.py's test_every_instantiation_once: every tile has live and empty slots in both
+    layers, slots in each of the three level-of-detail cases, and taps in both destination tensors (tex and the chain)."""
+    uv, da, rl = mref.instantiation_case()
+    Ht, Wt = mref.INST_TEXTURE
+    st = mref.stage(uv, da, Ht, Wt, rl)
+    assert st["nlev"] == 3 and tref.tiles_have_live_and_empty(st["empty"])
+    live = ~st["empty"]
+    low, high = live & (st["lod"] <= 0), live & (st["lod"] >= st["nlev"] - 1)
+    print("lod <= 0:", int(low.sum()), "two levels:", int(st["two"].sum()), "top level:", int(high.sum()))
+    assert min(low.sum(), st["two"].sum(), high.sum()) >= 20 and low.sum() + st["two"].sum() + high.sum() == live.sum()
+    assert set(np.unique(st["j"][st["two"]])) == {0, 1}                                # both pairs of levels blend
+    bad_uv, bad_da = ~np.isfinite(uv).all(-1), ~np.isfinite(da).all(-1)
+    assert bad_uv.sum() == 6 and bad_da.sum() == 4 and np.array_equal(st["empty"], (rl < 0) | bad_uv | bad_da)
+    for boundary_mode in mref.BOUNDARIES:
+        k = mref.keys(uv, da, Ht, Wt, rl, boundary_mode)
+        assert ((k >= 0) & (k < Ht * Wt)).any() and (k >= Ht * Wt).any()

@@ -23,6 +23,8 @@ tests/test_texture_cube_cpu.py compares the two.
 """
 import numpy as np
 
+import texture_ref as tref
+
 f32 = np.float32
 FILTERS = ("nearest", "linear")
 
@@ -317,3 +319,20 @@ def distinct_texels_per_tile(dirs, N, render_layers=None, filter_mode="linear", 
                     n = int((k >= 0).sum())
                     best = n if best is None else worst(best, n)
     return best
+
+
+INST_NS = (2, 5)
+
+
+def instantiation_case(N, seed=0):
+    """The "every instantiation once" inputs (texture_ref.INST_SHAPE, texture_ref.instantiation_ids) for an N x N cube ->
+    (dirs (B,H,W,L,3) float32, render_layers): random directions, half of them replaced by near_seams' (aimed at the edges and
+    corners of every face), a few NaN / infinite components."""
+    rl = tref.instantiation_ids(seed)
+    rng = np.random.default_rng(seed + 4 + N)
+    d = rng.standard_normal((rl.size, 3))
+    aimed = near_seams(rng, rl.size // 4, N)
+    d[rng.choice(rl.size, len(aimed), replace=False)] = aimed
+    d = d.reshape(tref.INST_SHAPE + (3,)).astype(f32)
+    tref.spoil(d, rl, seed)
+    return d, rl

@@ -370,3 +370,19 @@ def grads64(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, g)
             h, w, off = levels[k]
             dmip[..., off:off + h * w, :] += dk.reshape(mip.shape[:-2] + (h * w, C))
     return dtex, dmip, duv
+
+
+INST_TEXTURE = (8, 4)                     # (Ht, Wt): three levels
+
+
+def instantiation_case(seed=0):
+    """The "every instantiation once" inputs (texture_ref.INST_SHAPE, texture_ref.instantiation_ids) for INST_TEXTURE ->
+    (uv, uv_da, render_layers): uv in [-0.5, 1.5]^2, footprints from a quarter of a texel to four times the coarsest level's
+    texel, so that lod <= 0, between two levels, and at or above the top level all occur; a few NaN / infinite uv and uv_da."""
+    rl = tref.instantiation_ids(seed)
+    rng = np.random.default_rng(seed + 3)
+    uv = rng.uniform(-0.5, 1.5, tref.INST_SHAPE + (2,)).astype(f32)
+    da = footprints(rng, tref.INST_SHAPE, *INST_TEXTURE, -2.0, 4.0)
+    tref.spoil(uv, rl, seed)
+    tref.spoil(da, rl, seed + 10, n=4)
+    return uv, da, rl

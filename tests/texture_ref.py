@@ -143,3 +143,47 @@ def distinct_texels_per_tile(uv, Ht, Wt, render_layers=None, filter_mode="linear
                     n = int((k >= 0).sum())
                     best = n if best is None else worst(best, n)
     return best
+
+
+# ---- "every instantiation once": the smallest inputs at which each loop of the kernels still has two iterations and each guard
+# both outcomes (two views, four 16 x 16 tiles per view of which three are partial, two layers), shared by the three texture ops
+INST_SHAPE = (2, 17, 17, 2)               # B, H, W, L
+INST_CS = (1, 2, 3, 4, 5, 8)              # the scatter's chunk 1, 2, 3; 4 exact; 4 with a tail chunk; two float4 groups
+
+
+def instantiation_ids(seed=0):
+    """render_layers (B,H,W,L) int32: about a quarter negative; at the one-pixel corner tile view 0 is live and view 1 empty."""
+    rng = np.random.default_rng(seed)
+    rl = np.where(rng.uniform(size=INST_SHAPE) < 0.25, -1, rng.integers(0, 9, INST_SHAPE)).astype(np.int32)
+    rl[0, 16, 16], rl[1, 16, 16] = 3, -1
+    return rl
+
+
+def spoil(coords, rl, seed=0, n=6):
+    """NaN, +inf and -inf into one component of ``n`` live slots' coordinates (not the corner pixel's) -> the spoilt slots."""
+    rng = np.random.default_rng(seed + 1)
+    live = np.argwhere((rl >= 0) & ~((np.arange(17)[:, None] == 16) & (np.arange(17)[None, :] == 16))[None, :, :, None])
+    pick = live[rng.choice(len(live), n, replace=False)]
+    for k, p in enumerate(pick):
+        coords[tuple(p) + (k % coords.shape[-1],)] = (np.nan, np.inf, -np.inf)[k % 3]
+    return pick
+
+
+def instantiation_case(seed=0):
+    """-> (uv (B,H,W,L,2) uniform in [-0.5, 1.5]^2 with a few NaN and infinite entries, render_layers)."""
+    rl = instantiation_ids(seed)
+    uv = np.random.default_rng(seed + 2).uniform(-0.5, 1.5, INST_SHAPE + (2,)).astype(f32)
+    spoil(uv, rl, seed)
+    return uv, rl
+
+
+def tiles_have_live_and_empty(empty, tile=16):
+    """Every tile of every layer holds live and empty slots: in each view where the tile has more than one pixel, and over the
+    views where it is a single pixel (one slot per view and layer cannot be both)."""
+    B, H, W, L = empty.shape
+    for y, x, l in ((y, x, l) for y in range(0, H, tile) for x in range(0, W, tile) for l in range(L)):
+        t = empty[:, y:y + tile, x:x + tile, l]
+        groups = [t] if t[0].size == 1 else list(t)
+        if not all(g.any() and not g.all() for g in groups):
+            return False
+    return True
