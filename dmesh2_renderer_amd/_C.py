@@ -49,6 +49,13 @@ and the analytic pixel coverage of listed faces, the anti-aliasing factor of suc
     coverage_cuda(render_layers, verts_image, faces, temperature) -> cov,
     coverage_backward_cuda(...those 4..., grad_cov) -> dL/dverts_image
 
+and what feeds a cube-map lookup (Renderer.vertex_normals, Renderer.shading_vectors):
+
+    vertex_normals_cuda(verts, faces, offsets, corners, normalize) -> (normals, len),
+    vertex_normals_backward_cuda(...those 5..., normals, len, grad_normals) -> dL/dverts,
+    shading_vectors_cuda(render_layers, t, normals, image_ray_o, image_ray_d) -> (position, view[, normal, reflection]),
+    shading_vectors_backward_cuda(...those 5..., g_position, g_normal, g_reflection, need_t, need_normals) -> (dL/dt, dL/dnormals)
+
 Under the ``alpha_output`` side channel render_forward_cuda appends the alpha (coverage) image; the two backwards take
 its gradient as the keyword ``dL_dout_alpha``.  Under ``face_weights_output`` render_forward_cuda and composite_layers_cuda
 append the per-face blend weights (B,F), behind everything else they return; they have no gradient.
@@ -173,6 +180,11 @@ EXPORTS = {
     "dm2_texture_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
     "dm2_texture_cube": (ctypes.c_int, [_i32] * 8 + [_vp] * 5),
     "dm2_texture_cube_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 7),
+    "dm2_vertex_normals_scratch_bytes": (_sz, [_i32] * 3),
+    "dm2_vertex_normals": (ctypes.c_int, [_i32] * 3 + [_vp] * 5 + [_sz] + [_vp] * 3),
+    "dm2_vertex_normals_backward": (ctypes.c_int, [_i32] * 3 + [_vp] * 8 + [_sz] + [_vp] * 2),
+    "dm2_shading_vectors_window": (ctypes.c_int, [_i32] * 5 + [ctypes.POINTER(Window)] + [_vp] * 11),
+    "dm2_shading_vectors_backward_window": (ctypes.c_int, [_i32] * 5 + [ctypes.POINTER(Window)] + [_vp] * 12),
     "dm2_bary_derivatives_window": (ctypes.c_int, [_i32] * 6 + [ctypes.POINTER(Window)] + [_vp] * 7),
     "dm2_texture_mipmaps": (ctypes.c_int, [_i32] * 5 + [_vp] * 3),
     "dm2_texture_mipmaps_backward": (ctypes.c_int, [_i32] * 5 + [_vp] * 3),
@@ -1168,6 +1180,154 @@ def texture_cube_backward_cuda(dirs, tex, render_layers, filter_mode, grad_out, 
         if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(dc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(ddir), _stream(dev)):
             raise _err(lib, "texture_cube_backward_cuda")
     return dtex, ddir
+
+
+def _vertex_normals_args(verts, faces, offsets, corners, normals=None, lens=None, grad_normals=None):
+    """Checks of a vertex-normals call -> ((P, F), contiguous tensors, device)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(verts.dim() != 2 or verts.size(1) != 3, f"verts must have dimensions (P, 3), got {tuple(verts.shape)}")
+    bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
+    P, F = int(verts.size(0)), int(faces.size(0))
+    bad(3 * F >= 2 ** 31, "faces: 3 * F must be below 2^31")
+    bad(tuple(offsets.shape) != (P + 1,), f"offsets must have dimensions ({P + 1},), got {tuple(offsets.shape)}")
+    bad(tuple(corners.shape) != (3 * F,), f"corners must have dimensions ({3 * F},), got {tuple(corners.shape)}")
+    for name, t, shape in (("normals", normals, (P, 3)), ("len", lens, (P,)), ("grad_normals", grad_normals, (P, 3))):
+        bad(t is not None and tuple(t.shape) != shape, f"{name} must have dimensions {shape}, got {tuple(t.shape) if t is not None else None}")
+    f32, i32 = torch.float32, torch.int32
+    named = (("verts", verts, f32), ("faces", faces, i32), ("offsets", offsets, i32), ("corners", corners, i32),
+             ("normals", normals, f32), ("len", lens, f32), ("grad_normals", grad_normals, f32))
+    dev = _require_gpu(*[t for _, t, _ in named if t is not None])
+    ts = []
+    for name, t, dt in named:
+        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    return (P, F), ts, dev
+
+
+def vertex_normals_cuda(verts, faces, offsets, corners, normalize=True):
+    """Area-weighted vertex normals without atomics (include/dm2_hip.h: dm2_vertex_normals).
+
+    verts (P,3) float32, faces (F,3) int32, (offsets (P+1,), corners (3F,)) int32 = ``Renderer.vertex_adjacency(faces, P)`` ->
+    (normals (P,3) float32, len (P,) float32 = the length of each vertex's summed face normals, what the backward takes)."""
+    lib = load_library()
+    (P, F), (vc, fc, of, co, _, _, _), dev = _vertex_normals_args(verts, faces, offsets, corners)
+    f32 = torch.float32
+    normals = torch.empty((P, 3), dtype=f32, device=dev)                      # (every element written by the kernel)
+    lens = torch.empty((P,), dtype=f32, device=dev)
+    if P == 0:
+        return normals, lens
+    nbytes = lib.dm2_vertex_normals_scratch_bytes(P, F, 0)
+    scratch = _bytes(dev, nbytes)
+    with torch.cuda.device(dev):
+        if lib.dm2_vertex_normals(P, F, 1 if normalize else 0, _ptr(vc), _ptr(fc), _ptr(of), _ptr(co), _ptr(scratch), nbytes,
+                                  _ptr(normals), _ptr(lens), _stream(dev)):
+            raise _err(lib, "vertex_normals_cuda")
+    return normals, lens
+
+
+def vertex_normals_backward_cuda(verts, faces, offsets, corners, normalize, normals, lens, grad_normals):
+    """Gradient of vertex_normals_cuda (dm2_vertex_normals_backward) for grad_normals (P,3) -> dL_dverts (P,3); ``normals`` and
+    ``lens`` are the forward's (``lens`` decides which vertices are zero; the normal itself is evaluated again in double from
+    ``verts``).  No atomics: the same bits on every call."""
+    lib = load_library()
+    (P, F), (vc, fc, of, co, nr, ln, gn), dev = _vertex_normals_args(verts, faces, offsets, corners, normals, lens, grad_normals)
+    dverts = torch.empty((P, 3), dtype=torch.float32, device=dev)               # (every element written by the kernel)
+    if P == 0:
+        return dverts
+    nbytes = lib.dm2_vertex_normals_scratch_bytes(P, F, 1)
+    scratch = _bytes(dev, nbytes)
+    with torch.cuda.device(dev):
+        if lib.dm2_vertex_normals_backward(P, F, 1 if normalize else 0, _ptr(vc), _ptr(fc), _ptr(of), _ptr(co), _ptr(nr), _ptr(ln),
+                                           _ptr(gn), _ptr(scratch), nbytes, _ptr(dverts), _stream(dev)):
+            raise _err(lib, "vertex_normals_backward_cuda")
+    return dverts
+
+
+def _shading_args(render_layers, t, normals, image_ray_o, image_ray_d, grads=()):
+    """Checks of a shading-vectors call -> ((B, H, W, L, flags), contiguous tensors, device, keep-alive list, window)."""
+    def bad(cond, msg):
+        if cond:
+            raise RuntimeError(msg)
+    bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+    B, H, W, L = (int(x) for x in render_layers.shape)
+    bad(tuple(t.shape) != (B, H, W, L), f"t must have dimensions {(B, H, W, L)}, got {tuple(t.shape)}")
+    bad(normals is not None and tuple(normals.shape) != (B, H, W, L, 3),
+        f"normals must have dimensions {(B, H, W, L, 3)}, got {tuple(normals.shape) if normals is not None else None}")
+    for name, g in grads:
+        bad(g is not None and tuple(g.shape) != (B, H, W, L, 3),
+            f"{name} must have dimensions {(B, H, W, L, 3)}, got {tuple(g.shape) if g is not None else None}")
+    f32, i32 = torch.float32, torch.int32
+    named = (("render_layers", render_layers, i32), ("t", t, f32), ("normals", normals, f32), ("image_ray_o", image_ray_o, f32),
+             ("image_ray_d", image_ray_d, f32)) + tuple((name, g, f32) for name, g in grads)
+    dev = _require_gpu(*[x for _, x, _ in named if x is not None])
+    ana = _analytic(B, dev)
+    bad(ana is None and (tuple(image_ray_o.shape) != (B, H, W, 3) or tuple(image_ray_d.shape) != (B, H, W, 3)),
+        f"image_ray_o/image_ray_d must have dimensions {(B, H, W, 3)}")
+    ts = []
+    for name, x, dt in named:
+        bad(x is not None and x.dtype != dt, f"{name}: expected dtype {dt}, got {x.dtype if x is not None else None}")
+        ts.append(None if x is None else x.contiguous())
+    keep: list = []
+    flags = 0
+    if ana is not None:
+        if (ana[1], ana[2]) != _frame_size(W, H):
+            raise RuntimeError("analytic_rays: the image size differs from render_layers' width / height")
+        flags = DM2_FLAG_ANALYTIC_RAYS
+        ts[3] = ts[4] = None
+    ts.append(None if ana is None else ana[0])
+    win = _window(B, W, H, dev, keep)
+    return (B, H, W, L, flags), ts, dev, keep, win
+
+
+def shading_vectors_cuda(render_layers, t, normals, image_ray_o, image_ray_d):
+    """Per-slot shading vectors (include/dm2_hip.h: dm2_shading_vectors_window).
+
+    render_layers (B,H,W,L) int32, t (B,H,W,L) float32, normals (B,H,W,L,3) float32 or None, image_ray_o / image_ray_d
+    (B,H,W,3) float32 (placeholders under ``analytic_rays``; under ``window`` the window's cut) -> (position, view) or
+    (position, view, normal, reflection), each (B,H,W,L,3) float32; zeros in an empty slot (a negative id or a t that is not
+    finite)."""
+    lib = load_library()
+    sizes, (rl, tt, nr, ro, rd, cam), dev, keep, win = _shading_args(render_layers, t, normals, image_ray_o, image_ray_d)
+    B, H, W, L = sizes[:4]
+    n_out = 2 if nr is None else 4
+    outs = tuple(torch.empty((B, H, W, L, 3), dtype=torch.float32, device=dev) for _ in range(n_out))   # (every element written)
+    if B * H * W * L == 0:
+        return outs
+    with torch.cuda.device(dev):
+        if lib.dm2_shading_vectors_window(*sizes, None if win is None else ctypes.byref(win), _ptr(rl), _ptr(tt), _ptr(nr), _ptr(ro),
+                                          _ptr(rd), _ptr(cam), *(_ptr(o) for o in outs), *((None, None) if nr is None else ()),
+                                          _stream(dev)):
+            raise _err(lib, "shading_vectors_cuda")
+    return outs
+
+
+def shading_vectors_backward_cuda(render_layers, t, normals, image_ray_o, image_ray_d, g_position, g_normal, g_reflection, need_t,
+                                  need_normals):
+    """Gradients of shading_vectors_cuda (dm2_shading_vectors_backward_window): upstream gradients (B,H,W,L,3) or None ->
+    (dL_dt (B,H,W,L) or None, dL_dnormals (B,H,W,L,3) or None): only what ``need_t`` / ``need_normals`` ask for, and only where
+    an upstream gradient reaches it (t: g_position; normals: g_normal or g_reflection), is computed; otherwise None."""
+    lib = load_library()
+    grads = (("g_position", g_position), ("g_normal", g_normal), ("g_reflection", g_reflection))
+    sizes, (rl, tt, nr, ro, rd, gp, gn, gr, cam), dev, keep, win = _shading_args(render_layers, t, normals, image_ray_o, image_ray_d,
+                                                                                  grads)
+    B, H, W, L = sizes[:4]
+    need_t = bool(need_t) and gp is not None
+    need_normals = bool(need_normals) and nr is not None and (gn is not None or gr is not None)
+    if not (need_t or need_normals):
+        return None, None
+    f32 = torch.float32
+    dt = torch.empty((B, H, W, L), dtype=f32, device=dev) if need_t else None                 # (every element written)
+    dn = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_normals else None
+    if B * H * W * L == 0:
+        return dt, dn
+    with torch.cuda.device(dev):
+        if lib.dm2_shading_vectors_backward_window(*sizes, None if win is None else ctypes.byref(win), _ptr(rl), _ptr(tt), _ptr(nr),
+                                                   _ptr(ro), _ptr(rd), _ptr(cam), _ptr(gp), _ptr(gn), _ptr(gr), _ptr(dt), _ptr(dn),
+                                                   _stream(dev)):
+            raise _err(lib, "shading_vectors_backward_cuda")
+    return dt, dn
 
 
 def bary_derivatives_cuda(render_layers, verts, faces, ray_cam):

@@ -20,7 +20,11 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   filtering for ``texture`` (``filter_mode="linear-mipmap-linear"``, ``TextureMipFunction``) with the two ops that feed it:
   ``Renderer.bary_derivatives()``, the pixel's footprint on each listed face (``BaryDerivativesFunction``, a constant of
   the pipeline), and ``Renderer.texture_mipmaps()``, the chain of 2 x 2 means (``MipmapFunction``); and cube-map lookup by
-  direction for ``texture`` (``boundary_mode="cube"``, ``TextureCubeFunction``): filtered across the cube's edges and corners
+  direction for ``texture`` (``boundary_mode="cube"``, ``TextureCubeFunction``): filtered across the cube's edges and corners;
+  and what produces those directions: ``Renderer.vertex_normals()``, smooth normals that carry a gradient to the vertices
+  without float atomics (``VertexNormalsFunction``, over ``Renderer.vertex_adjacency()``'s index), and
+  ``Renderer.shading_vectors()``, per-slot position, view, unit normal and reflection vectors from the pixel's own ray
+  (``ShadingVectorsFunction``)
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -41,7 +45,7 @@ from .pyrenderer import Triangles
 
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
            "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction", "BaryDerivativesFunction",
-           "MipmapFunction", "TextureMipFunction", "TextureCubeFunction"]
+           "MipmapFunction", "TextureMipFunction", "TextureCubeFunction", "VertexNormalsFunction", "ShadingVectorsFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -610,6 +614,90 @@ class Renderer(torch.nn.Module):
         with _C.window(pm_dev, self.width, self.height):
             return CoverageFunction.apply(render_layers.to(i32), verts_image.to(f32), faces.to(i32), float(temperature), inside)
 
+    @staticmethod
+    def vertex_adjacency(faces: torch.Tensor, num_verts: int):
+        """The inverted index from vertices to face corners (not in the reference): faces (F,3) of any integer dtype, on the
+        GPU or the CPU -> (offsets (P+1,) int32, corners (3F,) int32) on ``faces``' device, P = ``num_verts``.  A face is valid
+        when its three ids lie in [0, P).  ``corners`` holds the corner numbers 3 f + k ordered by (vertex id, corner number)
+        ascending, the corners of invalid faces at the end; vertex p owns ``corners[offsets[p]:offsets[p+1]]`` and
+        ``offsets[P]`` is the number of valid corners.  A pure function of ``faces``, without a host read-back: build it once per
+        topology and hand the pair to ``vertex_normals`` (nothing is cached behind the caller's back).  3 F must be below 2^31."""
+        if faces.dim() != 2 or faces.size(1) != 3:
+            raise ValueError(f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
+        if faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool:
+            raise ValueError(f"faces: expected an integer dtype, got {faces.dtype}")
+        P, F = int(num_verts), int(faces.size(0))
+        if P < 0:
+            raise ValueError("num_verts must not be negative")
+        if 3 * F >= 2 ** 31:
+            raise ValueError("faces: 3 * F must be below 2^31")
+        with torch.no_grad():
+            ids = faces.long()
+            valid = ((ids >= 0) & (ids < P)).all(dim=1, keepdim=True)
+            key = torch.where(valid, ids, torch.full_like(ids, P)).reshape(-1)          # (3F,): the corner's vertex, P if invalid
+            skey, order = torch.sort(key, stable=True)                                   # ties keep the corner numbers ascending
+            offsets = torch.searchsorted(skey, torch.arange(P + 1, device=faces.device, dtype=torch.long))
+        return offsets.to(torch.int32), order.to(torch.int32)
+
+    def vertex_normals(self, verts: torch.Tensor, faces: torch.Tensor, adjacency=None, normalize: bool = True):
+        """Smooth vertex normals (not in the reference): verts (P,3), faces (F,3) -> normals (P,3) float32 = the sum of the
+        vertex's face normals (p1 - p0) x (p2 - p0), unnormalised and so weighted by area, divided by its length
+        (``normalize=False``: the sum itself).  A vertex without faces, or whose sum is zero or not finite, gets zeros; a face
+        that names a vertex outside [0, P) contributes to none.  ``adjacency``: ``vertex_adjacency(faces, P)``, built once per
+        topology; None builds it inside the call.  ``interpolate(render_layers, bary, normals, faces)`` turns the result into a
+        normal image.
+
+        Differentiable w.r.t. ``verts`` (``VertexNormalsFunction``); faces and the index are constants.  Forward and backward
+        are a store pass over the faces and a gather pass over the vertices in the index's fixed order: no float atomics, and
+        two calls give the same bits.  The summation order is (face id, corner) ascending per vertex."""
+        i32, f32 = torch.int32, torch.float32
+        if adjacency is None:
+            adjacency = Renderer.vertex_adjacency(faces, verts.shape[0])
+        offsets, corners = adjacency
+        return VertexNormalsFunction.apply(verts.to(f32), faces.to(i32), offsets, corners, bool(normalize))
+
+    def shading_vectors(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, t: torch.Tensor,
+                        normals: torch.Tensor = None, patch_min: torch.Tensor = None):
+        """The vectors a shader needs per slot (not in the reference): render_layers (B,H,W,L) int32 and t (B,H,W,L) as
+        ``rasterize`` returns them, normals (B,H,W,L,3) of any length (``interpolate``'s output for ``vertex_normals``) or None
+        -> (position, view), or with ``normals`` (position, view, normal, reflection), each (B,H,W,L,3) float32.  With (ro, rd)
+        the ray of the slot's pixel, the one ``rasterize`` used (the ray tensors, or the computed ray of
+        ``Renderer(analytic_rays=True)``): position = ro + t rd, the hit in world space; view = -rd, from the surface to the
+        eye; normal = normals / |normals|; reflection = 2 (normal . view) normal - view, the mirror direction of the view about
+        the normal, the same for n and -n: what ``texture(..., boundary_mode="cube")`` looks an environment map up by.
+
+        A slot with a negative id or a t that is not finite is empty: zeros in every output, no gradient.  Where the normal is
+        zero or not finite, normal and reflection are zero and ``normals`` gets no gradient.  Differentiable w.r.t. ``t``
+        (through position) and ``normals`` (``ShadingVectorsFunction``; the normal's gradient is orthogonal to it); view is a
+        constant, and nothing flows to the cameras.
+
+        Window: with ``patch_min`` (B,2) int32, render_layers is a window's and slot (b, y, x) is frame pixel
+        (x + patch_min[b,0], y + patch_min[b,1]): the crop of the full-frame result.  Checks and errors are ``coverage``'s; an
+        empty window launches nothing."""
+        i32, f32 = torch.int32, torch.float32
+        if render_layers.dim() != 4:
+            raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+        B, ph, pw, L = (int(x) for x in render_layers.shape)
+        dev = render_layers.device
+        nrm = None if normals is None else normals.to(f32)
+        if patch_min is not None:
+            pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
+            if render_layers.numel() == 0:
+                return tuple(torch.empty((B, ph, pw, L, 3), dtype=f32, device=dev) for _ in range(2 if normals is None else 4))
+            ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
+            with ctx:
+                return ShadingVectorsFunction.apply(render_layers.to(i32), t.to(f32), nrm, ray_o, ray_d)
+        if (ph, pw) != (self.height, self.width):
+            raise ValueError(f"render_layers must cover the {self.width} x {self.height} frame (or come with patch_min), "
+                             f"got {tuple(render_layers.shape)}")
+        if getattr(self, "analytic_rays", False):
+            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
+            hold = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
+            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
+                return ShadingVectorsFunction.apply(render_layers.to(i32), t.to(f32), nrm, hold, hold)
+        ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
+        return ShadingVectorsFunction.apply(render_layers.to(i32), t.to(f32), nrm, ray_o.to(f32), ray_d.to(f32))
+
     def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
         f32 = torch.float32
@@ -1007,6 +1095,70 @@ class CoverageFunction(torch.autograd.Function):
         win = ctx.window
         with _C.window(*(win if win is not None else (None,))):
             return None, _C.coverage_backward_cuda(render_layers, verts_image, faces, ctx.temperature, grad_cov), None, None, None
+
+
+class VertexNormalsFunction(torch.autograd.Function):
+    """normals = the area-weighted sum of each vertex's face normals, normalised or not (``_C.vertex_normals_cuda``).
+
+    Inputs: verts (P,3)*, faces (F,3) int32, offsets (P+1,) int32, corners (3F,) int32 (``Renderer.vertex_adjacency``),
+    normalize.  Output: normals (P,3).  (* = receives a gradient.)  The backward is a store pass over the faces and a gather
+    pass over the vertices through the same index: no float atomics, the same bits on every call.  The output gradient is not
+    materialised: with the normals left out of the loss, or ``verts`` not requiring a gradient, no kernel runs.
+    """
+
+    @staticmethod
+    def forward(ctx, verts, faces, offsets, corners, normalize):
+        ctx.set_materialize_grads(False)
+        normals, lens = _C.vertex_normals_cuda(verts.detach(), faces, offsets, corners, normalize)
+        ctx.normalize = bool(normalize)
+        ctx.save_for_backward(verts.detach(), faces, offsets, corners, normals, lens)
+        return normals
+
+    @staticmethod
+    def backward(ctx, grad_normals):
+        if grad_normals is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        verts, faces, offsets, corners, normals, lens = ctx.saved_tensors
+        return _C.vertex_normals_backward_cuda(verts, faces, offsets, corners, ctx.normalize, normals, lens, grad_normals), None, None, \
+            None, None
+
+
+class ShadingVectorsFunction(torch.autograd.Function):
+    """(position, view[, normal, reflection]) per slot from rasterize's t, the pixel's ray and interpolate's normal
+    (``_C.shading_vectors_cuda``): position = ro + t rd, view = -rd, normal = n / |n|, reflection = 2 (normal . view) normal - view.
+
+    Inputs: render_layers (B,H,W,L) int32, t (B,H,W,L)*, normals (B,H,W,L,3)* or None, image_ray_o, image_ray_d (B,H,W,3)
+    (placeholders under ``_C.analytic_rays``; under ``_C.window`` the window's cut).  Outputs: two or four (B,H,W,L,3) tensors.
+    (* = receives a gradient.)  ``view`` is marked non-differentiable and nothing flows to the rays.  Output gradients are not
+    materialised: an output left out of the loss costs nothing, and only the gradients ``needs_input_grad`` asks for are
+    computed; where none is, no kernel runs.
+    """
+
+    @staticmethod
+    def forward(ctx, render_layers, t, normals, image_ray_o, image_ray_d):
+        ctx.set_materialize_grads(False)
+        ctx.analytic = getattr(_C._tls, "analytic", None)
+        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
+        ctx.has_normals = normals is not None
+        outs = _C.shading_vectors_cuda(render_layers, t.detach(), None if normals is None else normals.detach(), image_ray_o,
+                                       image_ray_d)
+        ctx.save_for_backward(render_layers, t.detach(), image_ray_o, image_ray_d, *((normals.detach(),) if ctx.has_normals else ()))
+        ctx.mark_non_differentiable(outs[1])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_position, g_view, g_normal=None, g_reflection=None):
+        need_t = ctx.needs_input_grad[1] and g_position is not None
+        need_n = ctx.has_normals and ctx.needs_input_grad[2] and (g_normal is not None or g_reflection is not None)
+        if not (need_t or need_n):
+            return None, None, None, None, None
+        render_layers, t, ray_o, ray_d = ctx.saved_tensors[:4]
+        normals = ctx.saved_tensors[4] if ctx.has_normals else None
+        ana, win = ctx.analytic, ctx.window
+        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
+            dt, dn = _C.shading_vectors_backward_cuda(render_layers, t, normals, ray_o, ray_d, g_position, g_normal, g_reflection,
+                                                      need_t, need_n)
+        return None, dt, dn, None, None
 
 
 class LayeredRenderer(Renderer):

@@ -698,6 +698,93 @@ int dm2_bary_derivatives_window(int32_t B, int32_t H, int32_t W, int32_t L, int3
     return 0;
 }
 
+static int check_vertex_normals(int32_t P, int32_t F, const void* scratch, size_t scratch_bytes, int backward) {
+    if (P < 0 || F < 0) return fail("vertex_normals: negative size");
+    if ((int64_t)3 * F > 0x7FFFFFFF) return fail("vertex_normals: 3 * F must be below 2^31");
+    if (P == 0) return 0;
+    const size_t need = dm2::vertex_normals_scratch_bytes(P, F, backward);
+    if (F > 0 && (!scratch || scratch_bytes < need)) return fail("vertex_normals: scratch is smaller than dm2_vertex_normals_scratch_bytes");
+    if ((uintptr_t)scratch % 16) return fail("vertex_normals: scratch must be 16-byte aligned");
+    return 0;
+}
+
+size_t dm2_vertex_normals_scratch_bytes(int32_t P, int32_t F, int32_t backward) {
+    if (P < 0 || F < 0) return 0;
+    return dm2::vertex_normals_scratch_bytes(P, F, backward);
+}
+
+int dm2_vertex_normals(int32_t P, int32_t F, int32_t normalize, const float* verts, const int32_t* faces, const int32_t* offsets,
+                       const int32_t* corners, void* scratch, size_t scratch_bytes, float* out_normals, float* out_len, void* stream) {
+    if (check_vertex_normals(P, F, scratch, scratch_bytes, 0)) return 1;
+    if (P == 0) return 0;
+    if (!out_normals) return fail("vertex_normals: out_normals must not be null");
+    if (!offsets) return fail("vertex_normals: offsets must not be null");
+    if (F > 0 && (!verts || !faces || !corners)) return fail("vertex_normals: verts, faces and corners must not be null");
+    dm2::launch_vertex_normals(P, F, normalize, verts, faces, offsets, corners, scratch, out_normals, out_len, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_vertex_normals_backward(int32_t P, int32_t F, int32_t normalize, const float* verts, const int32_t* faces,
+                                const int32_t* offsets, const int32_t* corners, const float* normals, const float* len,
+                                const float* dL_dnormals, void* scratch, size_t scratch_bytes, float* dL_dverts, void* stream) {
+    if (check_vertex_normals(P, F, scratch, scratch_bytes, 1)) return 1;
+    if (P == 0 || !dL_dverts || !dL_dnormals) return 0;
+    if (!offsets) return fail("vertex_normals_backward: offsets must not be null");
+    if (F > 0 && (!verts || !faces || !corners)) return fail("vertex_normals_backward: verts, faces and corners must not be null");
+    if (F > 0 && normalize && (!normals || !len)) return fail("vertex_normals_backward: normals and len must not be null");
+    dm2::launch_vertex_normals_backward(P, F, normalize, verts, faces, offsets, corners, normals, len, dL_dnormals, scratch, dL_dverts,
+                                        (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+static int check_shading(int32_t B, int32_t H, int32_t W, int32_t L, int32_t flags, const dm2_window* win, const int32_t* render_layers,
+                         const float* t, const float* image_ray_o, const float* image_ray_d, const float* ray_cam) {
+    if (B < 0 || H < 0 || W < 0 || L < 0) return fail("shading_vectors: negative size");
+    const int64_t per_view = (int64_t)H * W * L;
+    if (B > 65535 || (per_view + 255) / 256 > 0x7FFFFFFF) return fail("shading_vectors: too many slots or views");
+    if (flags & ~DM2_FLAG_ANALYTIC_RAYS) return fail("shading_vectors: unknown flag");
+    if (win && (win->full_W < W || win->full_H < H)) return fail("shading_vectors: the window is larger than its frame");
+    if ((int64_t)B * per_view == 0) return 0;
+    if (!render_layers || !t) return fail("shading_vectors: render_layers and t must not be null");
+    if (flags & DM2_FLAG_ANALYTIC_RAYS) {
+        if (!ray_cam) return fail("shading_vectors: ray_cam must not be null");
+    } else if (!image_ray_o || !image_ray_d) {
+        return fail("shading_vectors: image_ray_o and image_ray_d must not be null");
+    }
+    return 0;
+}
+
+int dm2_shading_vectors_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t flags, const dm2_window* win,
+                               const int32_t* render_layers, const float* t, const float* normals, const float* image_ray_o,
+                               const float* image_ray_d, const float* ray_cam, float* out_position, float* out_view, float* out_normal,
+                               float* out_reflection, void* stream) {
+    if (check_shading(B, H, W, L, flags, win, render_layers, t, image_ray_o, image_ray_d, ray_cam)) return 1;
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!out_position || !out_view) return fail("shading_vectors: out_position and out_view must not be null");
+    if (normals && (!out_normal || !out_reflection)) return fail("shading_vectors: out_normal and out_reflection must not be null");
+    dm2::launch_shading_vectors(B, H, W, L, flags, win ? win->full_W : W, win ? win->full_H : H, win ? win->patch_min : nullptr,
+                                render_layers, t, normals, image_ray_o, image_ray_d, ray_cam, out_position, out_view, out_normal,
+                                out_reflection, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_shading_vectors_backward_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t flags, const dm2_window* win,
+                                        const int32_t* render_layers, const float* t, const float* normals, const float* image_ray_o,
+                                        const float* image_ray_d, const float* ray_cam, const float* g_position, const float* g_normal,
+                                        const float* g_reflection, float* dL_dt, float* dL_dnormals, void* stream) {
+    if (check_shading(B, H, W, L, flags, win, render_layers, t, image_ray_o, image_ray_d, ray_cam)) return 1;
+    if ((int64_t)B * H * W * L == 0 || (!dL_dt && !dL_dnormals)) return 0;
+    if (dL_dnormals && !normals) return fail("shading_vectors_backward: normals must not be null");
+    dm2::launch_shading_vectors_backward(B, H, W, L, flags, win ? win->full_W : W, win ? win->full_H : H,
+                                         win ? win->patch_min : nullptr, render_layers, t, normals, image_ray_o, image_ray_d, ray_cam,
+                                         g_position, g_normal, g_reflection, dL_dt, dL_dnormals, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 // the chain of (Ht, Wt, C) under max_mip_level: sizes that the kernels' 32-bit texel indices and launch grids hold
 static int check_mip_sizes(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, int64_t* T) {
     if (NB < 0 || NB > 65535) return fail("texture_mip: the number of textures must lie in [0, 65535]");

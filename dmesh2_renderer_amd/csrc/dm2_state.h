@@ -284,6 +284,24 @@ void launch_coverage_backward(int B, int H, int W, int L, int P, int F, float te
 void launch_bary_derivatives(int B, int H, int W, int L, int P, int F, int full_W, int full_H, const int32_t* patch_min,
                              const int32_t* render_layers, const float* verts, const int32_t* faces, const float* ray_cam,
                              float* dbary_dx, float* dbary_dy, hipStream_t st);
+// Renderer.vertex_normals (dm2_normals.hip): every element of out_normals / out_len / dL_dverts is written.  P > 0; scratch:
+// vertex_normals_scratch_bytes(P, F, backward) bytes, 16-byte aligned (forward: F rows of 16 bytes; backward: P + 3 F rows).
+size_t vertex_normals_scratch_bytes(int P, int F, int backward);
+void launch_vertex_normals(int P, int F, int normalize, const float* verts, const int32_t* faces, const int32_t* offsets,
+                           const int32_t* corners, void* scratch, float* out_normals, float* out_len, hipStream_t st);
+void launch_vertex_normals_backward(int P, int F, int normalize, const float* verts, const int32_t* faces, const int32_t* offsets,
+                                    const int32_t* corners, const float* normals, const float* lens, const float* dL_dnormals,
+                                    void* scratch, float* dL_dverts, hipStream_t st);
+// Renderer.shading_vectors (dm2_shading.hip): every element of every non-NULL output is written.  B * H * W * L > 0; H, W, full_W,
+// full_H and patch_min as for launch_bary_derivatives; the rays as in dm2_layers_desc (flags: DM2_FLAG_ANALYTIC_RAYS).
+void launch_shading_vectors(int B, int H, int W, int L, int flags, int full_W, int full_H, const int32_t* patch_min,
+                            const int32_t* render_layers, const float* t, const float* normals, const float* image_ray_o,
+                            const float* image_ray_d, const float* ray_cam, float* out_position, float* out_view, float* out_normal,
+                            float* out_reflection, hipStream_t st);
+void launch_shading_vectors_backward(int B, int H, int W, int L, int flags, int full_W, int full_H, const int32_t* patch_min,
+                                     const int32_t* render_layers, const float* t, const float* normals, const float* image_ray_o,
+                                     const float* image_ray_d, const float* ray_cam, const float* g_position, const float* g_normal,
+                                     const float* g_reflection, float* dL_dt, float* dL_dnormals, hipStream_t st);
 // Renderer.texture_mipmaps / texture(filter_mode="linear-mipmap-linear") (dm2_texture_mip.hip).  mip_levels: 1 + the levels
 // built for (Ht, Wt) under max_level (< 0: no limit), *T the chain's texels.  NB textures (1 shared, B per view); every element
 // of mip / dL_dtex (mipmaps), out / dL_duv (sampling) is written; the sampling's backward adds into dL_dtex and dL_dmip; any of

@@ -625,6 +625,69 @@ int dm2_coverage_window_inside(int32_t B, int32_t H, int32_t W, int32_t L, int32
                                const dm2_window* win, const int32_t* render_layers, const uint8_t* inside,
                                const float* verts_image, const int32_t* faces, float* out_cov, void* stream);
 
+/* Renderer.vertex_normals: area-weighted smooth vertex normals of a triangle mesh, differentiable w.r.t. the vertices, without
+ * float atomics.  verts (P,3) float32, faces (F,3) int32, 3 F < 2^31.  A face is valid when its three ids lie in [0, P).
+ * The inverted index (Renderer.vertex_adjacency builds it; a pure function of faces): corners (3F) int32 holds the corner
+ * numbers 3 f + k ordered by (vertex id, corner number) ascending, the corners of invalid faces at the end; offsets (P+1) int32:
+ * vertex p owns corners[offsets[p] .. offsets[p+1]), offsets[P] = the number of valid corners.  (Offsets are clamped to
+ * [0, 3F] and an entry of corners outside [0, 3F) is passed over: an index not built that way cannot address out of bounds.)
+ * All fp32, separate multiplies and adds in the written order, without contraction:
+ *   face normal (valid faces): e1 = p1 - p0, e2 = p2 - p0, N = e1 x e2 = (e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z,
+ *     e1.x * e2.y - e1.y * e2.x), not normalised: it weights by area;
+ *   vertex sum: s_p = (((0 + N_c0) + N_c1) + ...) over the vertex's corners in corners' order (N_c = N of face c / 3); a face
+ *     that names a vertex twice contributes its (zero) N once per corner; an invalid face contributes to no vertex;
+ *   len = sqrtf((s.x * s.x + s.y * s.y) + s.z * s.z);
+ *   normalize != 0: out = s / len per component where len > 0 and finite, zeros elsewhere (isolated vertices, exact
+ *     cancellation, overflow, NaN); normalize == 0: out = s.
+ * Every element of out_normals (P,3) and, when not NULL, out_len (P) = len is written (the backward takes both).  scratch:
+ * dm2_vertex_normals_scratch_bytes(P, F, 0) = 16 F bytes, 16-byte aligned, of this call only (the face normals in 16-byte rows).
+ * The gradient (faces and the index are constants), for upstream g = dL_dnormals (P,3):
+ *   d_p = (g_p - n_p (n_p . g_p)) / len_p where the forward's len (the argument len) is > 0 and finite, else zeros;
+ *     normalize == 0: d_p = g_p.  n_p and len_p of this line are not the forward's fp32 values: the backward evaluates edges,
+ *     cross products, the vertex sum (in corners' order) and the length again in double and rounds d_p to fp32, because the
+ *     fp32 normal of a face whose edges meet at a small angle a is good to u / sin(a) only and d would inherit that error
+ *     whole.  The arguments normals and len stand in where the double sum has no direction although len says there is one;
+ *   per valid face (fp32 again): D = (d_v0 + d_v1) + d_v2, c1 = e2 x D, c2 = D x e1, c0 = -(c1 + c2);
+ *   dL_dverts[p] = (((0 + c_k0) + c_k1) + ...) over its corners in corners' order; every element of dL_dverts (P,3) is written.
+ * scratch: dm2_vertex_normals_scratch_bytes(P, F, 1) = 16 (P + 3 F) bytes (d, then the corner terms; the double face normals,
+ * 32 F bytes, use the corner terms' place before those are written).  No float atomics either
+ * way: two calls with the same inputs give the same bits.  dL_dnormals or dL_dverts NULL: nothing runs.  normals / len may be
+ * NULL when normalize == 0. */
+size_t dm2_vertex_normals_scratch_bytes(int32_t P, int32_t F, int32_t backward);
+int dm2_vertex_normals(int32_t P, int32_t F, int32_t normalize, const float* verts, const int32_t* faces, const int32_t* offsets,
+                       const int32_t* corners, void* scratch, size_t scratch_bytes, float* out_normals, float* out_len, void* stream);
+int dm2_vertex_normals_backward(int32_t P, int32_t F, int32_t normalize, const float* verts, const int32_t* faces,
+                                const int32_t* offsets, const int32_t* corners, const float* normals, const float* len,
+                                const float* dL_dnormals, void* scratch, size_t scratch_bytes, float* dL_dverts, void* stream);
+
+/* Renderer.shading_vectors: per slot s = (b, y, x, l) the vectors a shader needs, from dm2_rasterize_run's t, the pixel's own
+ * ray and (optionally) dm2_interpolate's normal.  render_layers (B,H,W,L) int32, t (B,H,W,L) float32, normals (B,H,W,L,3)
+ * float32 of any length or NULL.  The ray (ro, rd) of the slot's pixel is the one the rasterizer used: image_ray_o / image_ray_d
+ * (B,H,W,3), or with flags = DM2_FLAG_ANALYTIC_RAYS the ray computed from ray_cam (B,32) (dm2_render_desc) for a W x H image.
+ * win: the arrays are a window's (dm2_window: the ray tensors the window's own cut, the analytic ray that of frame pixel
+ * (x + patch_min[b][0], y + patch_min[b][1]) in full_W x full_H); NULL: the full frame.  All fp32 in the written order,
+ * without contraction:
+ *   empty slot (id < 0, or t not finite): every output is zero and no gradient flows;
+ *   position = ro + t * rd per component (one multiply, one add);   view = -rd;
+ *   nl = sqrtf((n.x * n.x + n.y * n.y) + n.z * n.z); where nl is not finite (a component that is not finite makes it so) or
+ *     nl == 0: normal = reflection = 0 and normals gets no gradient (position and view are written all the same); otherwise
+ *   normal = n / nl;   c = (normal.x * view.x + normal.y * view.y) + normal.z * view.z;
+ *   reflection = (2.0f * c) * normal - view   (the same bits for n and -n).
+ * out_position, out_view and, with normals, out_normal, out_reflection, each (B,H,W,L,3): every element is written.
+ * Gradients, for upstream g_position, g_normal, g_reflection (each (B,H,W,L,3) or NULL = zero; view has none):
+ *   dL_dt[s] = (g_position.x * rd.x + g_position.y * rd.y) + g_position.z * rd.z;
+ *   G = g_normal + 2 c g_reflection + 2 (g_reflection . normal) view,  dL_dnormals[s] = (G - normal (normal . G)) / nl:
+ *   orthogonal to n.  Nothing flows to the cameras or through the rays.  dL_dt (B,H,W,L) / dL_dnormals (B,H,W,L,3): NULL = not
+ *   wanted; every element of the others is written, zeros in empty slots; no atomics.  Both NULL: nothing runs. */
+int dm2_shading_vectors_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t flags, const dm2_window* win,
+                               const int32_t* render_layers, const float* t, const float* normals, const float* image_ray_o,
+                               const float* image_ray_d, const float* ray_cam, float* out_position, float* out_view, float* out_normal,
+                               float* out_reflection, void* stream);
+int dm2_shading_vectors_backward_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t flags, const dm2_window* win,
+                                        const int32_t* render_layers, const float* t, const float* normals, const float* image_ray_o,
+                                        const float* image_ray_d, const float* ray_cam, const float* g_position, const float* g_normal,
+                                        const float* g_reflection, float* dL_dt, float* dL_dnormals, void* stream);
+
 /* Differentiable compositing of caller-supplied face layers (LayeredRenderer.render).
  * Per pixel of view b, with T = 1, C = D = 0, for l = 0..L-1 and f = render_layers[b,y,x,l]:
  *   1. skip f < 0 or f >= F (holes and out-of-range ids are allowed and never read through);
