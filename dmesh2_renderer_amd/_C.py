@@ -88,7 +88,7 @@ DM2_FLAG_NO_PAIR_POOL = 64
 SCRATCH_FACE, SCRATCH_IMAGE, SCRATCH_BINNING, SCRATCH_LAYER_IMAGE, SCRATCH_LAYER_TETS, SCRATCH_PAIR_POOL, SCRATCH_TIE_QUEUE = range(7)
 # what a forward left for its backward (include/dm2_hip.h DM2_FWD_*)
 FWD_UNKNOWN, FWD_NONE, FWD_MASKS, FWD_POOL, FWD_POINT = 0, 1, 2, 3, 4
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # opt-in flags applied to every call (tests use this for the corrected-gradient mode)
 _flags = 0
@@ -147,33 +147,20 @@ EXPORTS = {
     "dm2_last_error": (ctypes.c_char_p, []),
     "dm2_scratch_bytes": (_sz, [ctypes.c_int, _i64, _i64]),
     "dm2_forward_plan": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
-    "dm2_forward_run": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp,
+    "dm2_forward_run": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                                        ctypes.POINTER(_i32)]),
-    "dm2_forward": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp,
+    "dm2_forward": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
                                    ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
-    "dm2_backward": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
+    "dm2_forward_alpha": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _vp]),
+    "dm2_backward": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dm2_layers_plan": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _sz, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
-    "dm2_layers_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
-    "dm2_rasterize_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "dm2_rasterize_backward": (ctypes.c_int, [ctypes.POINTER(LayersDesc), _vp, _vp, _vp, _vp, _vp]),
-    "dm2_layers_plan_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _sz, _vp, ctypes.POINTER(_i64),
-                                              ctypes.POINTER(_i64)]),
-    "dm2_layers_run_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz,
-                                             _vp, _sz, _vp, _vp, _vp]),
-    "dm2_rasterize_run_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp, _sz, _vp,
-                                                _sz, _vp, _vp, _vp, _vp, _vp]),
-    "dm2_rasterize_backward_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp]),
-    "dm2_rasterize_overlap_run_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp,
-                                                        _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dm2_rasterize_overlap_backward_window": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp]),
-    "dm2_coverage_window": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 5),
-    "dm2_coverage_window_inside": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
-    "dm2_coverage_backward_window": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
-    "dm2_layers_composite_window": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp,
-                                                   _vp]),
-    "dm2_layers_composite_backward_window": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), ctypes.POINTER(Window), _vp, _vp, _vp,
-                                                            _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_layers_plan": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _sz, _vp, ctypes.POINTER(_i64),
+                                       ctypes.POINTER(_i64)]),
+    "dm2_layers_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz,
+                                      _vp, _sz, _vp, _vp, _vp]),
+    "dm2_rasterize_run": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz,
+                                         _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "dm2_rasterize_backward": (ctypes.c_int, [ctypes.POINTER(LayersDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _i32, _vp]),
     "dm2_interpolate": (ctypes.c_int, [_i32] * 8 + [_vp] * 6),
     "dm2_interpolate_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 8),
     "dm2_texture": (ctypes.c_int, [_i32] * 10 + [_vp] * 5),
@@ -192,20 +179,11 @@ EXPORTS = {
     "dm2_texture_mip_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 10),
     "dm2_composite": (ctypes.c_int, [_i32] * 7 + [_vp] * 9),
     "dm2_composite_backward": (ctypes.c_int, [_i32] * 7 + [_vp] * 10),
-    "dm2_coverage": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float] + [_vp] * 5),
-    "dm2_coverage_backward": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float] + [_vp] * 6),
-    "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp]),
-    "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dm2_layers_composite_backward_alpha": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                            _vp]),
-    "dm2_forward_alpha": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _vp]),
-    "dm2_forward_weights": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
-                                           ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
-    "dm2_forward_run_weights": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i64, _i64, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp,
-                                               _vp, _vp, _vp, ctypes.POINTER(_i32)]),
-    "dm2_layers_composite_weights": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
-    "dm2_backward_alpha": (ctypes.c_int, [ctypes.POINTER(RenderDesc), _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp,
-                                          _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_coverage": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
+    "dm2_coverage_backward": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
+    "dm2_layers_composite": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dm2_layers_composite_backward": (ctypes.c_int, [ctypes.POINTER(LayerCompositeDesc), ctypes.POINTER(Window), _vp, _vp, _vp, _vp,
+                                                     _vp, _vp, _vp, _vp, _vp]),
     "dm2_prepare_faces": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp]),
     "dm2_prepare_faces_backward": (ctypes.c_int, [ctypes.POINTER(PrepDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dm2_prepare_faces_camera_scratch_bytes": (_sz, [_i32, _i32]),
@@ -270,6 +248,11 @@ def _err(lib, what):
     return RuntimeError(f"{what}: {msg.decode() if msg else 'unknown error'}")
 
 
+def _bad(cond, msg):
+    if cond:
+        raise RuntimeError(msg)
+
+
 def _require_gpu(*tensors):
     for t in tensors:
         if not t.is_cuda:
@@ -304,26 +287,23 @@ def _bytes(dev, n):
 def _check_render_shapes(background, patch_min, verts, faces, verts_color, faces_opacity, verts_ndc, verts_image,
                          faces_intense, aa_v, aa_e, aa_z, aa_r, aa_n, aa_c, ray_o, ray_d, temp, K):
     # messages of render.cu:62-118
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(background.dim() != 1 or background.size(0) != 3, "background must have dimensions (3,)")
-    bad(patch_min.dim() != 2 or patch_min.size(1) != 2, "patch_min must have dimensions (B, 2)")
-    bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
-    bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
-    bad(verts_color.dim() != 2 or verts_color.size(1) != 3, "vert color must have dimensions (P, 3)")
-    bad(faces_opacity.dim() != 1 or faces_opacity.size(0) != faces.size(0), "face opacity must have dimensions (F,)")
-    bad(verts_ndc.dim() != 3 or verts_ndc.size(2) != 3, "verts_ndc must have dimensions (B, P, 3)")
-    bad(verts_image.dim() != 3 or verts_image.size(2) != 2, "verts_image must have dimensions (B, P, 2)")
-    bad(faces_intense.dim() != 2 or faces_intense.size(1) != faces.size(0), "faces_intense must have dimensions (B, F,)")
+    _bad(background.dim() != 1 or background.size(0) != 3, "background must have dimensions (3,)")
+    _bad(patch_min.dim() != 2 or patch_min.size(1) != 2, "patch_min must have dimensions (B, 2)")
+    _bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
+    _bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
+    _bad(verts_color.dim() != 2 or verts_color.size(1) != 3, "vert color must have dimensions (P, 3)")
+    _bad(faces_opacity.dim() != 1 or faces_opacity.size(0) != faces.size(0), "face opacity must have dimensions (F,)")
+    _bad(verts_ndc.dim() != 3 or verts_ndc.size(2) != 3, "verts_ndc must have dimensions (B, P, 3)")
+    _bad(verts_image.dim() != 3 or verts_image.size(2) != 2, "verts_image must have dimensions (B, P, 2)")
+    _bad(faces_intense.dim() != 2 or faces_intense.size(1) != faces.size(0), "faces_intense must have dimensions (B, F,)")
     for t, nm in ((aa_v, "aa_face_verts"), (aa_e, "aa_face_edges"), (aa_z, "aa_face_edges_iszero"),
                   (aa_r, "aa_face_edges_recip"), (aa_n, "aa_face_edges_normal")):
-        bad(t.dim() != 4 or t.size(2) != 3 or t.size(3) != 2, f"{nm} must have dimensions (B, F, 3, 2)")
-    bad(aa_c.dim() != 3 or aa_c.size(2) != 3, "aa_face_edges_normal_c must have dimensions (B, F, 3)")
-    bad(ray_o.dim() != 4 or ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
-    bad(ray_d.dim() != 4 or ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
-    bad(temp < 0 or temp > 1, "aa_temperature must be in the range [0, 1]")
-    bad(K < 0, "len_oarea_buffer must be non-negative")
+        _bad(t.dim() != 4 or t.size(2) != 3 or t.size(3) != 2, f"{nm} must have dimensions (B, F, 3, 2)")
+    _bad(aa_c.dim() != 3 or aa_c.size(2) != 3, "aa_face_edges_normal_c must have dimensions (B, F, 3)")
+    _bad(ray_o.dim() != 4 or ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
+    _bad(ray_d.dim() != 4 or ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
+    _bad(temp < 0 or temp > 1, "aa_temperature must be in the range [0, 1]")
+    _bad(K < 0, "len_oarea_buffer must be non-negative")
 
 
 def _make_desc(args, keep):
@@ -387,58 +367,53 @@ def _tiles(B, W, H):
 _tls = threading.local()
 
 
-class forward_only:
+class _SideChannel:
+    """Base of the side channels below: a per-thread value that the ``*_cuda`` calls read from ``_tls`` (attribute ``_slot``,
+    ``_off`` outside every block).  Entering sets it, leaving restores what was there before, so blocks nest."""
+    _slot, _off = "", False
+
+    def __init__(self, on=True):
+        self.val = bool(on)
+
+    def __enter__(self):
+        self.old = getattr(_tls, self._slot, self._off)
+        setattr(_tls, self._slot, self.val)
+
+    def __exit__(self, *exc):
+        setattr(_tls, self._slot, self.old)
+
+
+class forward_only(_SideChannel):
     """``with _C.forward_only(True): _C.render_forward_cuda(...)`` -- no backward will follow this forward (RenderFunction
     sets it when no input requires a gradient, e.g. under ``torch.no_grad()``): the blend masks a backward would use are
     not written.  A side channel on purpose: the function keeps the reference's exact 21-argument signature."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_tls, "forward_only", False)
-        _tls.forward_only = self.on
-
-    def __exit__(self, *exc):
-        _tls.forward_only = self.old
+    _slot = "forward_only"
 
 
-class analytic_rays:
+class analytic_rays(_SideChannel):
     """``with _C.analytic_rays(ray_cam, width, height): _C.render_forward_cuda(...)`` (and the matching backward /
     generate_render_layers call): the primary rays are computed per pixel from ``ray_cam`` (B,32) float32 = inv(mv) then
     inv(proj) of each rendered view, row-major, for an image of (width, height) -- the operation order of the reference's
     ``Renderer._init_rays`` -- and the ``image_ray_o`` / ``image_ray_d`` arguments are placeholders of shape (B,0,0,3)
     that are never read.  A side channel like ``forward_only``: the 21 / 31 / 13-argument
     signatures stay the reference's."""
+    _slot, _off = "analytic", None
 
     def __init__(self, ray_cam, width, height):
         self.val = None if ray_cam is None else (ray_cam, int(width), int(height))
 
-    def __enter__(self):
-        self.old = getattr(_tls, "analytic", None)
-        _tls.analytic = self.val
 
-    def __exit__(self, *exc):
-        _tls.analytic = self.old
-
-
-class window:
+class window(_SideChannel):
     """``with _C.window(patch_min, full_width, full_height): _C.rasterize_layers_cuda(...)`` (and generate_render_layers /
     coverage / composite_layers, and their backwards): the call works on a window of the frame.  ``patch_min`` (B,2) int32 on
     the GPU = the (x, y) origin of each view's window in its (full_width, full_height) frame; the call's width / height, its
-    ray tensors and every (B,H,W,...) tensor are then the window's (include/dm2_hip.h: dm2_window), and the ``*_window`` entry
-    points run.  That the windows lie inside the frame is the caller's check (Renderer does it, with one read-back).  None:
+    ray tensors and every (B,H,W,...) tensor are then the window's (include/dm2_hip.h: dm2_window), which the entry
+    points are handed.  That the windows lie inside the frame is the caller's check (Renderer does it, with one read-back).  None:
     no window, the calls as they are without one.  A side channel like ``analytic_rays``: the signatures stay as they are."""
+    _slot, _off = "window", None
 
     def __init__(self, patch_min, full_width=0, full_height=0):
         self.val = None if patch_min is None else (patch_min, int(full_width), int(full_height))
-
-    def __enter__(self):
-        self.old = getattr(_tls, "window", None)
-        _tls.window = self.val
-
-    def __exit__(self, *exc):
-        _tls.window = self.old
 
 
 def _window(B, W, H, dev, keep):
@@ -458,99 +433,62 @@ def _window(B, W, H, dev, keep):
     return win
 
 
+def _win(win):
+    """``_window``'s result as the ``const dm2_window*`` argument: NULL without a window."""
+    return None if win is None else ctypes.byref(win)
+
+
 def _frame_size(width, height):
     """The size analytic rays must have been declared for: the frame of the thread's window, or the call's own width / height."""
     w = getattr(_tls, "window", None)
     return (w[1], w[2]) if w is not None else (width, height)
 
 
-class aa_grad_to_verts:
+class aa_grad_to_verts(_SideChannel):
     """``with _C.aa_grad_to_verts(True): _C.render_backward_cuda(...)`` -- the sixth gradient is not dL/d(aa_face_verts)
     (B,F,3,2) but that gradient already scattered to the vertices the corners belong to, (B,P,2): the gradient of
     ``verts_image`` through the reordered copy (DM2_FLAG_AA_GRAD_TO_VERTS).  For a caller that owns the host prep as well
     (Renderer with the fused prep).  A side channel like ``forward_only``: the 31-argument signature stays the reference's."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_tls, "aa_to_verts", False)
-        _tls.aa_to_verts = self.on
-
-    def __exit__(self, *exc):
-        _tls.aa_to_verts = self.old
+    _slot = "aa_to_verts"
 
 
-class tables_from_image:
+class tables_from_image(_SideChannel):
     """``with _C.tables_from_image(True): _C.render_forward_cuda(...)`` (and the matching backward): the six ``aa_*`` arguments
     are placeholders (any tensors of the right rank, e.g. ``(B, 0, 3, 2)``) that are never read -- the plan builds the tables
     per (view, face) from ``verts_image[faces]`` in registers, exactly as ``Triangles`` would (DM2_FLAG_TABLES_FROM_IMAGE).  For a
     caller that owns the host prep (Renderer with the fused prep); the AA-corner gradients then come back per vertex
     (``aa_grad_to_verts``).  A side channel like ``forward_only``: the 21 / 31-argument signatures stay the reference's."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_tls, "tables_from_image", False)
-        _tls.tables_from_image = self.on
-
-    def __exit__(self, *exc):
-        _tls.tables_from_image = self.old
+    _slot = "tables_from_image"
 
 
-class alpha_output:
+class alpha_output(_SideChannel):
     """``with _C.alpha_output(True): _C.render_forward_cuda(...)`` -- the forward returns an 11-tuple: the reference's ten
     outputs, then the alpha (coverage) image (B,H,W) float32 = 1 - T, the T the colour multiplied the background by (zeros
     when nothing is rendered; dm2_forward_alpha).  Its gradient goes to ``render_backward_cuda(..., dL_dout_alpha=g)``.  Also
     read by ``LayeredCompositeFunction``.  A side channel like ``forward_only``: the 21-argument signature stays the
     reference's."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_tls, "alpha_output", False)
-        _tls.alpha_output = self.on
-
-    def __exit__(self, *exc):
-        _tls.alpha_output = self.old
+    _slot = "alpha_output"
 
 
-class face_weights_output:
+class face_weights_output(_SideChannel):
     """``with _C.face_weights_output(True): _C.render_forward_cuda(...)`` -- the forward appends face_weights (B,F) float32
     behind everything else it returns (behind alpha under ``alpha_output``): per view and face the sum, over the pixels of
     the patch, of alpha * T of each of the face's blends -- the factor its colour gets in C += c alpha T
-    (dm2_forward_weights).  Float atomics: the last bits may vary from run to run.  No gradient.  Also read by
-    ``composite_layers_cuda`` (dm2_layers_composite_weights) and ``LayeredCompositeFunction``."""
-
-    def __init__(self, on=True):
-        self.on = bool(on)
-
-    def __enter__(self):
-        self.old = getattr(_tls, "face_weights_output", False)
-        _tls.face_weights_output = self.on
-
-    def __exit__(self, *exc):
-        _tls.face_weights_output = self.old
+    (dm2_forward's out_face_weights).  Float atomics: the last bits may vary from run to run.  No gradient.  Also read by
+    ``composite_layers_cuda`` (dm2_layers_composite's out_face_weights) and ``LayeredCompositeFunction``."""
+    _slot = "face_weights_output"
 
 
-class forward_mode:
+class forward_mode(_SideChannel):
     """``with _C.forward_mode(mode): _C.render_backward_cuda(...)`` -- tells the backward what the forward of this frame left
     for it (FWD_NONE / FWD_MASKS / FWD_POOL, as ``_C.last_forward_mode()`` reported right after that forward), so that it
     launches exactly one composite kernel.  Without it the binning buffer's own note is used when the very tensor object the
     forward returned comes back; otherwise (FWD_UNKNOWN) every candidate kernel is launched and all but one return at once.
     A side channel like ``forward_only``: the 31-argument signature stays the reference's."""
+    _slot, _off = "fwd_mode", None
 
     def __init__(self, mode):
-        self.mode = mode
-
-    def __enter__(self):
-        self.old = getattr(_tls, "fwd_mode", None)
-        _tls.fwd_mode = self.mode
-
-    def __exit__(self, *exc):
-        _tls.fwd_mode = self.old
+        self.val = mode
 
 
 def last_forward_mode():
@@ -579,6 +517,32 @@ def _analytic(B, dev):
     if cam.dtype != torch.float32 or tuple(cam.shape) != (B, 32) or cam.device != dev:
         raise RuntimeError(f"analytic_rays: ray_cam must be float32 (B, 32) on {dev}, got {cam.dtype} {tuple(cam.shape)} on {cam.device}")
     return cam.contiguous(), w, h
+
+
+def _analytic_onto(d, ana, width, height, keep, mismatch):
+    """Analytic rays (``_analytic``'s result, or None: nothing happens) onto a layers / composite descriptor of a
+    width x height call: the flag, the cameras, no ray tensors.  ``mismatch``: the caller's words for a frame size that
+    differs from the one the rays were declared for."""
+    if ana is None:
+        return
+    _bad((ana[1], ana[2]) != _frame_size(width, height), mismatch)
+    keep.append(ana[0])
+    d.flags |= DM2_FLAG_ANALYTIC_RAYS
+    d.ray_cam = ana[0].data_ptr()
+    d.image_ray_o = d.image_ray_d = None
+
+
+def _layers_plan(lib, d, win, dev, st, what):
+    """The plan step of a dm2_layers_desc (generate, rasterize): face and image scratch, dm2_layers_plan, then the binning
+    scratch its count asks for -> (num_rendered, longest tile list, face_buf, bin_buf, img_buf)."""
+    N, Tn = d.B * d.H * d.W, _tiles(d.B, d.W, d.H)
+    face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, d.B * d.F, 2 * Tn))
+    img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_IMAGE, N, Tn))
+    nr, longest = _i64(0), _i64(0)
+    if lib.dm2_layers_plan(ctypes.byref(d), _win(win), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest)):
+        raise _err(lib, f"{what} (plan)")
+    R = int(nr.value)
+    return R, int(longest.value), face_buf, _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_BINNING, R, Tn)), img_buf
 
 
 def render_forward_cuda(*args):
@@ -633,13 +597,9 @@ def render_forward_cuda(*args):
         if _pool_budget(N, 0) <= 0:
             d.flags |= DM2_FLAG_NO_PAIR_POOL
         bin_buf = _bytes(dev, hint)
-        fwd_args = (ctypes.byref(d), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(),
-                    _ptr(color), _ptr(depth), _ptr(tri_cnt))
-        fwd_tail = (st, ctypes.byref(nr), ctypes.byref(longest), ctypes.byref(pairs), ctypes.byref(mode))
-        if want_weights:
-            rc = lib.dm2_forward_weights(*fwd_args, _ptr(weights), *fwd_tail)
-        else:
-            rc = lib.dm2_forward(*fwd_args, *fwd_tail)
+        rc = lib.dm2_forward(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf),
+                             img_buf.numel(), _ptr(color), _ptr(depth), _ptr(tri_cnt), _ptr(weights), st, ctypes.byref(nr),
+                             ctypes.byref(longest), ctypes.byref(pairs), ctypes.byref(mode))
         if rc not in (0, 2):
             raise _err(lib, "render_forward_cuda")
         R = int(nr.value)
@@ -653,14 +613,11 @@ def render_forward_cuda(*args):
             if over:
                 d.flags |= DM2_FLAG_NO_PAIR_POOL
             bin_buf = _bytes(dev, need + need // 4)
-            run_args = (ctypes.byref(d), R, int(longest.value), int(pairs.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf),
-                        bin_buf.numel(), _ptr(img_buf), img_buf.numel(), _ptr(color), _ptr(depth), _ptr(tri_cnt))
             if want_weights:
                 weights.zero_()                       # (the over-budget case composited once already: the sums start again)
-                rc = lib.dm2_forward_run_weights(*run_args, _ptr(weights), st, ctypes.byref(mode))
-            else:
-                rc = lib.dm2_forward_run(*run_args, st, ctypes.byref(mode))
-            if rc:
+            if lib.dm2_forward_run(ctypes.byref(d), R, int(longest.value), int(pairs.value), _ptr(face_buf), face_buf.numel(),
+                                   _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(), _ptr(color), _ptr(depth),
+                                   _ptr(tri_cnt), _ptr(weights), st, ctypes.byref(mode)):
                 raise _err(lib, "render_forward_cuda (run)")
         with _lock:
             hint = _bin_hint.get(key, 0)
@@ -704,7 +661,7 @@ def render_backward_cuda(*args, dL_dout_alpha=None):
     The six gradients are views of ONE packed fp32 buffer (attribute
     ``_dm2_packed`` on the first tensor) so that a multi-GPU caller can sum
     them with a single RCCL all-reduce (dmesh2_renderer_amd.sharding).
-    dL_dout_alpha (B,H,W) or None: the gradient of the alpha image of ``alpha_output`` (dm2_backward_alpha).
+    dL_dout_alpha (B,H,W) or None: the gradient of the alpha image of ``alpha_output`` (dm2_backward's dL_dout_alpha).
     """
     if len(args) != 31:
         raise TypeError(f"render_backward_cuda() takes 31 positional arguments ({len(args)} given)")
@@ -742,14 +699,10 @@ def render_backward_cuda(*args, dL_dout_alpha=None):
                 pool_pairs = max(0, bin_buf.numel() - lib.dm2_scratch_bytes(SCRATCH_BINNING, num_rendered, _tiles(B, W, H))) // 4
                 if pool_pairs > 0:
                     tie_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_TIE_QUEUE, pool_pairs, 0))
-            tail = (_ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(),
-                    _ptr(tie_buf), tie_buf.numel() if tie_buf is not None else 0,
-                    _ptr(g_verts), _ptr(g_color), _ptr(g_opac), _ptr(g_ndc), _ptr(g_int), _ptr(g_aa), _stream(dev))
-            if da is None:
-                rc = lib.dm2_backward(ctypes.byref(d), num_rendered, int(mode), _ptr(dc), _ptr(dd), *tail)
-            else:
-                rc = lib.dm2_backward_alpha(ctypes.byref(d), num_rendered, int(mode), _ptr(dc), _ptr(dd), _ptr(da), *tail)
-            if rc:
+            if lib.dm2_backward(ctypes.byref(d), num_rendered, int(mode), _ptr(dc), _ptr(dd), _ptr(da),
+                                _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf), img_buf.numel(),
+                                _ptr(tie_buf), tie_buf.numel() if tie_buf is not None else 0,
+                                _ptr(g_verts), _ptr(g_color), _ptr(g_opac), _ptr(g_ndc), _ptr(g_int), _ptr(g_aa), _stream(dev)):
                 raise _err(lib, "render_backward_cuda")
     return g_verts, g_color, g_opac, g_ndc, g_int, g_aa
 
@@ -758,33 +711,29 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
                                 verts_ndc, verts_image, image_ray_o, image_ray_d, num_layers):
     """-> (render_layers (B,H,W,L) int32, -1 = empty; render_layers_cnt (B,H,W) int32)."""
     lib = load_library()
-
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
     # messages of render.cu:397-429
-    bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
-    bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
-    bad(tets.dim() != 2 or tets.size(1) != 4, "tets must have dimensions (T, 4)")
-    bad(face_tets.dim() != 2 or face_tets.size(1) != 2, "face_tets must have dimensions (F, 2)")
-    bad(tet_faces.dim() != 2 or tet_faces.size(1) != 4, "tet_faces must have dimensions (T, 4)")
-    bad(face_existence.dim() != 1 or face_existence.size(0) != faces.size(0), "face_existence must have dimensions (F,)")
-    bad(verts_ndc.dim() != 3 or verts_ndc.size(2) != 3, "verts_ndc must have dimensions (B, P, 3)")
-    bad(verts_image.dim() != 3 or verts_image.size(2) != 2, "verts_image must have dimensions (B, P, 2)")
-    bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
-    bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
+    _bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
+    _bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
+    _bad(tets.dim() != 2 or tets.size(1) != 4, "tets must have dimensions (T, 4)")
+    _bad(face_tets.dim() != 2 or face_tets.size(1) != 2, "face_tets must have dimensions (F, 2)")
+    _bad(tet_faces.dim() != 2 or tet_faces.size(1) != 4, "tet_faces must have dimensions (T, 4)")
+    _bad(face_existence.dim() != 1 or face_existence.size(0) != faces.size(0), "face_existence must have dimensions (F,)")
+    _bad(verts_ndc.dim() != 3 or verts_ndc.size(2) != 3, "verts_ndc must have dimensions (B, P, 3)")
+    _bad(verts_image.dim() != 3 or verts_image.size(2) != 2, "verts_image must have dimensions (B, P, 2)")
+    _bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
+    _bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
     num_layers = int(num_layers); width = int(width); height = int(height)
-    bad(num_layers < 0, "num_layers must be non-negative")
+    _bad(num_layers < 0, "num_layers must be non-negative")
     dev = _require_gpu(verts, faces, tets, face_tets, tet_faces, face_existence, verts_ndc, verts_image, image_ray_o, image_ray_d)
     f32, i32 = torch.float32, torch.int32
     B, P, F, T = verts_ndc.size(0), verts.size(0), faces.size(0), tets.size(0)
-    bad(tuple(face_tets.shape) != (F, 2), "face_tets must have dimensions (F, 2)")
-    bad(tuple(tet_faces.shape) != (T, 4), "tet_faces must have dimensions (T, 4)")
-    bad(tuple(verts_ndc.shape) != (B, P, 3) or tuple(verts_image.shape) != (B, P, 2), "verts_ndc/verts_image shape mismatch")
+    _bad(tuple(face_tets.shape) != (F, 2), "face_tets must have dimensions (F, 2)")
+    _bad(tuple(tet_faces.shape) != (T, 4), "tet_faces must have dimensions (T, 4)")
+    _bad(tuple(verts_ndc.shape) != (B, P, 3) or tuple(verts_image.shape) != (B, P, 2), "verts_ndc/verts_image shape mismatch")
     ana = _analytic(B, dev)
     keep: list = []
     win = _window(B, width, height, dev, keep)           # (then width / height and the rays are the window's)
-    bad(ana is None and (tuple(image_ray_o.shape) != (B, height, width, 3) or tuple(image_ray_d.shape) != (B, height, width, 3)),
+    _bad(ana is None and (tuple(image_ray_o.shape) != (B, height, width, 3) or tuple(image_ray_d.shape) != (B, height, width, 3)),
         "image_ray_o/image_ray_d must have dimensions (B, H, W, 3)")
     ts = dict(verts=_c(verts, f32), faces=_c(faces, i32), tets=_c(tets, i32), face_tets=_c(face_tets, i32),
               tet_faces=_c(tet_faces, i32), face_existence=_c(face_existence, i32), verts_ndc=_c(verts_ndc, f32),
@@ -793,41 +742,19 @@ def generate_render_layers_cuda(width, height, verts, faces, tets, face_tets, te
     d.B, d.P, d.F, d.T, d.W, d.H, d.L, d.flags = B, P, F, T, width, height, num_layers, _flags
     for k, t in ts.items():
         setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
-    if ana is not None:
-        if (ana[1], ana[2]) != _frame_size(width, height):
-            raise RuntimeError("analytic_rays: the image size differs from generate_render_layers_cuda's width / height")
-        d.flags |= DM2_FLAG_ANALYTIC_RAYS
-        d.ray_cam = ana[0].data_ptr()
-        d.image_ray_o = d.image_ray_d = None
+    _analytic_onto(d, ana, width, height, keep, "analytic_rays: the image size differs from generate_render_layers_cuda's width / height")
     with torch.cuda.device(dev):
         st = _stream(dev)
         cnt = torch.zeros((B, height, width), dtype=i32, device=dev)              # render.cu:437
         layers = torch.full((B, height, width, num_layers), -1, dtype=i32, device=dev)   # render.cu:438
-        N, Tn, BF = B * height * width, _tiles(B, width, height), B * F
-        if N == 0 or F == 0 or T == 0:
+        if B * height * width == 0 or F == 0 or T == 0:
             # no pixels, no face to hit, or no tet to enter (a walk starts in a tet: without tets every first_tet is -1, and
             # face_tets may still name tets that are not there): the filled defaults, nothing is launched
             return layers, cnt
-        face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn))
-        img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_IMAGE, N, Tn))
-        nr, longest = _i64(0), _i64(0)
-        if win is None:
-            rc = lib.dm2_layers_plan(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest))
-        else:
-            rc = lib.dm2_layers_plan_window(ctypes.byref(d), ctypes.byref(win), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr),
-                                            ctypes.byref(longest))
-        if rc:
-            raise _err(lib, "generate_render_layers_cuda (plan)")
-        R = int(nr.value)
-        bin_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_BINNING, R, Tn))
+        R, longest, face_buf, bin_buf, img_buf = _layers_plan(lib, d, win, dev, st, "generate_render_layers_cuda")
         tet_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_TETS, T, 0))
-        run_args = (R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf),
-                    img_buf.numel(), _ptr(tet_buf), tet_buf.numel(), _ptr(layers), _ptr(cnt), st)
-        if win is None:
-            rc = lib.dm2_layers_run(ctypes.byref(d), *run_args)
-        else:
-            rc = lib.dm2_layers_run_window(ctypes.byref(d), ctypes.byref(win), *run_args)
-        if rc:
+        if lib.dm2_layers_run(ctypes.byref(d), _win(win), R, longest, _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(),
+                              _ptr(img_buf), img_buf.numel(), _ptr(tet_buf), tet_buf.numel(), _ptr(layers), _ptr(cnt), st):
             raise _err(lib, "generate_render_layers_cuda (run)")
     generate_render_layers_cuda.last_debug = (R, face_buf, bin_buf, img_buf)      # kept for tests
     return layers, cnt
@@ -838,27 +765,24 @@ def _rasterize_desc(width, height, B, verts, faces, image_ray_o, image_ray_d, nu
     """Checks (in the style of generate_render_layers_cuda) + the dm2_layers_desc of a rasterize call (T = 0: no tets); under
     ``window``, width / height and the rays are the window's.  The backward passes no face_existence / verts_ndc / verts_image:
     it reads neither."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
-    bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
-    bad(face_existence is not None and (face_existence.dim() != 1 or face_existence.size(0) != faces.size(0)),
+    _bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
+    _bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
+    _bad(face_existence is not None and (face_existence.dim() != 1 or face_existence.size(0) != faces.size(0)),
         "face_existence must have dimensions (F,)")
-    bad(verts_ndc is not None and (verts_ndc.dim() != 3 or verts_ndc.size(2) != 3), "verts_ndc must have dimensions (B, P, 3)")
-    bad(verts_image is not None and (verts_image.dim() != 3 or verts_image.size(2) != 2), "verts_image must have dimensions (B, P, 2)")
-    bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
-    bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
+    _bad(verts_ndc is not None and (verts_ndc.dim() != 3 or verts_ndc.size(2) != 3), "verts_ndc must have dimensions (B, P, 3)")
+    _bad(verts_image is not None and (verts_image.dim() != 3 or verts_image.size(2) != 2), "verts_image must have dimensions (B, P, 2)")
+    _bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
+    _bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
     num_layers = int(num_layers); width = int(width); height = int(height)
-    bad(num_layers < 0, "num_layers must be non-negative")
+    _bad(num_layers < 0, "num_layers must be non-negative")
     tensors = [t for t in (verts, faces, face_existence, verts_ndc, verts_image, image_ray_o, image_ray_d) if t is not None]
     dev = _require_gpu(*tensors)
     f32, i32 = torch.float32, torch.int32
     P, F = verts.size(0), faces.size(0)
-    bad((verts_ndc is not None and tuple(verts_ndc.shape) != (B, P, 3)) or (verts_image is not None and tuple(verts_image.shape) != (B, P, 2)),
+    _bad((verts_ndc is not None and tuple(verts_ndc.shape) != (B, P, 3)) or (verts_image is not None and tuple(verts_image.shape) != (B, P, 2)),
         "verts_ndc/verts_image shape mismatch")
     ana = _analytic(B, dev)
-    bad(ana is None and (tuple(image_ray_o.shape) != (B, height, width, 3) or tuple(image_ray_d.shape) != (B, height, width, 3)),
+    _bad(ana is None and (tuple(image_ray_o.shape) != (B, height, width, 3) or tuple(image_ray_d.shape) != (B, height, width, 3)),
         "image_ray_o/image_ray_d must have dimensions (B, H, W, 3)")
     ts = dict(verts=_c(verts, f32), faces=_c(faces, i32), image_ray_o=_c(image_ray_o, f32), image_ray_d=_c(image_ray_d, f32))
     for k, x, dt in (("face_existence", face_existence, i32), ("verts_ndc", verts_ndc, f32), ("verts_image", verts_image, f32)):
@@ -869,13 +793,7 @@ def _rasterize_desc(width, height, B, verts, faces, image_ray_o, image_ray_d, nu
     d.B, d.P, d.F, d.T, d.W, d.H, d.L, d.flags = B, P, F, 0, width, height, num_layers, _flags
     for k, t in ts.items():
         setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
-    if ana is not None:
-        if (ana[1], ana[2]) != _frame_size(width, height):
-            raise RuntimeError("analytic_rays: the image size differs from the rasterize call's width / height")
-        keep.append(ana[0])
-        d.flags |= DM2_FLAG_ANALYTIC_RAYS
-        d.ray_cam = ana[0].data_ptr()
-        d.image_ray_o = d.image_ray_d = None
+    _analytic_onto(d, ana, width, height, keep, "analytic_rays: the image size differs from the rasterize call's width / height")
     return d, dev
 
 
@@ -888,7 +806,7 @@ def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc
     ``analytic_rays``) -> (render_layers (B,H,W,L) int32, -1 = empty; render_layers_cnt (B,H,W) int32; bary (B,H,W,L,3) float32
     = (1 - u - v, u, v); t (B,H,W,L) float32), -1 in every empty slot.
 
-    ``overlap=True`` (dm2_rasterize_overlap_run_window): the faces that overlap the pixel's square and whose plane the ray meets
+    ``overlap=True`` (dm2_rasterize_run's overlap mode): the faces that overlap the pixel's square and whose plane the ray meets
     in front, with clamped barycentrics -> the same four and inside (B,H,W,L) bool, true where the ray hits the face itself."""
     lib = load_library()
     keep: list = []
@@ -899,8 +817,7 @@ def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc
     win = _window(d.B, d.W, d.H, dev, keep)
     B, F, H, W, L = d.B, d.F, d.H, d.W, d.L
     f32, i32 = torch.float32, torch.int32
-    N, Tn, BF = B * H * W, _tiles(B, W, H), B * F
-    if N == 0 or L == 0 or F == 0:
+    if B * H * W == 0 or L == 0 or F == 0:
         # nothing to walk: every slot empty (the kernels would write the same)
         out = (torch.full((B, H, W, L), -1, dtype=i32, device=dev), torch.zeros((B, H, W), dtype=i32, device=dev),
                torch.full((B, H, W, L, 3), -1.0, dtype=f32, device=dev), torch.full((B, H, W, L), -1.0, dtype=f32, device=dev))
@@ -912,28 +829,10 @@ def rasterize_layers_cuda(width, height, verts, faces, face_existence, verts_ndc
     t = torch.empty((B, H, W, L), dtype=f32, device=dev)
     with torch.cuda.device(dev):
         st = _stream(dev)
-        face_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_FACE, BF, 2 * Tn))
-        img_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_LAYER_IMAGE, N, Tn))
-        nr, longest = _i64(0), _i64(0)
-        if win is None:
-            rc = lib.dm2_layers_plan(ctypes.byref(d), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr), ctypes.byref(longest))
-        else:
-            rc = lib.dm2_layers_plan_window(ctypes.byref(d), ctypes.byref(win), _ptr(face_buf), face_buf.numel(), st, ctypes.byref(nr),
-                                            ctypes.byref(longest))
-        if rc:
-            raise _err(lib, "rasterize_layers_cuda (plan)")
-        R = int(nr.value)
-        bin_buf = _bytes(dev, lib.dm2_scratch_bytes(SCRATCH_BINNING, R, Tn))
-        run_args = (R, int(longest.value), _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(), _ptr(img_buf),
-                    img_buf.numel(), _ptr(layers), _ptr(cnt), _ptr(bary), _ptr(t), st)
-        if overlap:
-            rc = lib.dm2_rasterize_overlap_run_window(ctypes.byref(d), None if win is None else ctypes.byref(win), *run_args[:-1],
-                                                      _ptr(inside), st)
-        elif win is None:
-            rc = lib.dm2_rasterize_run(ctypes.byref(d), *run_args)
-        else:
-            rc = lib.dm2_rasterize_run_window(ctypes.byref(d), ctypes.byref(win), *run_args)
-        if rc:
+        R, longest, face_buf, bin_buf, img_buf = _layers_plan(lib, d, win, dev, st, "rasterize_layers_cuda")
+        if lib.dm2_rasterize_run(ctypes.byref(d), _win(win), R, longest, _ptr(face_buf), face_buf.numel(), _ptr(bin_buf), bin_buf.numel(),
+                                 _ptr(img_buf), img_buf.numel(), _ptr(layers), _ptr(cnt), _ptr(bary), _ptr(t), 1 if overlap else 0,
+                                 _ptr(inside), st):
             raise _err(lib, "rasterize_layers_cuda (run)")
     if overlap:
         return layers, cnt, bary, t, inside.view(torch.bool)       # (the kernel writes 0 or 1)
@@ -944,7 +843,7 @@ def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, ima
     """Gradient of rasterize_layers_cuda's bary and t w.r.t. verts (dm2_rasterize_backward): render_layers (B,H,W,L) as the
     forward returned them, the forward's verts / faces / rays, dL_dbary (B,H,W,L,3) and dL_dt (B,H,W,L), either may be None
     -> dL_dverts (P,3).  Nothing flows through the rays or through which faces are listed.  ``overlap=True``: the lists are the
-    overlap mode's (dm2_rasterize_overlap_backward_window: the clamp is recomputed and chained through)."""
+    overlap mode's (dm2_rasterize_backward with overlap set: the clamp is recomputed and chained through)."""
     lib = load_library()
     if render_layers.dim() != 4:
         raise RuntimeError("render_layers must have dimensions (B, H, W, L)")
@@ -969,33 +868,23 @@ def rasterize_layers_backward_cuda(render_layers, verts, faces, image_ray_o, ima
     if B * H * W * L == 0 or d.F == 0 or (gb is None and gt is None):
         return dverts
     with torch.cuda.device(dev):
-        if overlap:
-            rc = lib.dm2_rasterize_overlap_backward_window(ctypes.byref(d), None if win is None else ctypes.byref(win), _ptr(rl), _ptr(gb),
-                                                           _ptr(gt), _ptr(dverts), _stream(dev))
-        elif win is None:
-            rc = lib.dm2_rasterize_backward(ctypes.byref(d), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts), _stream(dev))
-        else:
-            rc = lib.dm2_rasterize_backward_window(ctypes.byref(d), ctypes.byref(win), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts),
-                                                   _stream(dev))
-        if rc:
+        if lib.dm2_rasterize_backward(ctypes.byref(d), _win(win), _ptr(rl), _ptr(gb), _ptr(gt), _ptr(dverts), 1 if overlap else 0,
+                                      _stream(dev)):
             raise _err(lib, "rasterize_layers_backward_cuda")
     return dverts
 
 
 def _interpolate_args(render_layers, bary, attr, attr_faces, grad_out=None):
     """Checks of an interpolate call -> (sizes (B, H, W, L, F, N, C, view_tables), contiguous tensors, device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(render_layers.dim() != 4, "render_layers must have dimensions (B, H, W, L)")
+    _bad(render_layers.dim() != 4, "render_layers must have dimensions (B, H, W, L)")
     B, H, W, L = (int(x) for x in render_layers.shape)
-    bad(tuple(bary.shape) != (B, H, W, L, 3), f"bary must have dimensions {(B, H, W, L, 3)}, got {tuple(bary.shape)}")
-    bad(attr.dim() not in (2, 3), "attr must have dimensions (N, C) or (B, N, C)")
-    bad(attr.dim() == 3 and attr.size(0) != B, f"attr must have dimensions (N, C) or ({B}, N, C), got {tuple(attr.shape)}")
-    bad(attr.size(-1) < 1, "attr must have at least one channel")
-    bad(attr_faces.dim() != 2 or attr_faces.size(1) != 3, "attr_faces must have dimensions (F, 3)")
+    _bad(tuple(bary.shape) != (B, H, W, L, 3), f"bary must have dimensions {(B, H, W, L, 3)}, got {tuple(bary.shape)}")
+    _bad(attr.dim() not in (2, 3), "attr must have dimensions (N, C) or (B, N, C)")
+    _bad(attr.dim() == 3 and attr.size(0) != B, f"attr must have dimensions (N, C) or ({B}, N, C), got {tuple(attr.shape)}")
+    _bad(attr.size(-1) < 1, "attr must have at least one channel")
+    _bad(attr_faces.dim() != 2 or attr_faces.size(1) != 3, "attr_faces must have dimensions (F, 3)")
     N, C, F = int(attr.size(-2)), int(attr.size(-1)), int(attr_faces.size(0))
-    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
+    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
         f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
     dev = _require_gpu(*[t for t in (render_layers, bary, attr, attr_faces, grad_out) if t is not None])
     f32, i32 = torch.float32, torch.int32
@@ -1003,7 +892,7 @@ def _interpolate_args(render_layers, bary, attr, attr_faces, grad_out=None):
              ("grad_out", grad_out, f32))
     ts = []
     for name, t, dt in named:
-        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
         ts.append(None if t is None else t.contiguous())
     return (B, H, W, L, F, N, C, 1 if attr.dim() == 3 else 0), ts, dev
 
@@ -1052,29 +941,26 @@ TEX_BOUNDARIES = {"wrap": 0, "clamp": 1}         # DM2_TEX_BOUNDARY_*
 
 def _texture_args(uv, tex, render_layers, filter_mode, boundary_mode, grad_out=None):
     """Checks of a texture call -> (sizes (B, H, W, L, Ht, Wt, C, view_textures, filter, boundary), contiguous tensors, device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
-    bad(boundary_mode not in TEX_BOUNDARIES, f"boundary_mode must be one of {sorted(TEX_BOUNDARIES)}, got {boundary_mode!r}")
-    bad(uv.dim() != 5 or uv.size(4) != 2, f"uv must have dimensions (B, H, W, L, 2), got {tuple(uv.shape)}")
+    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
+    _bad(boundary_mode not in TEX_BOUNDARIES, f"boundary_mode must be one of {sorted(TEX_BOUNDARIES)}, got {boundary_mode!r}")
+    _bad(uv.dim() != 5 or uv.size(4) != 2, f"uv must have dimensions (B, H, W, L, 2), got {tuple(uv.shape)}")
     B, H, W, L = (int(x) for x in uv.shape[:4])
-    bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
-    bad(tex.dim() == 4 and tex.size(0) != B, f"tex must have dimensions (Ht, Wt, C) or ({B}, Ht, Wt, C), got {tuple(tex.shape)}")
+    _bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
+    _bad(tex.dim() == 4 and tex.size(0) != B, f"tex must have dimensions (Ht, Wt, C) or ({B}, Ht, Wt, C), got {tuple(tex.shape)}")
     Ht, Wt, C = (int(x) for x in tex.shape[-3:])
-    bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
-    bad(C < 1, "tex must have at least one channel")
-    bad(Ht * Wt >= 2 ** 31, "tex: Ht * Wt must be below 2^31")
-    bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+    _bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
+    _bad(C < 1, "tex must have at least one channel")
+    _bad(Ht * Wt >= 2 ** 31, "tex: Ht * Wt must be below 2^31")
+    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
         f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
-    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
+    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
         f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
     dev = _require_gpu(*[t for t in (uv, tex, render_layers, grad_out) if t is not None])
     f32, i32 = torch.float32, torch.int32
     named = (("uv", uv, f32), ("tex", tex, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
     ts = []
     for name, t, dt in named:
-        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
         ts.append(None if t is None else t.contiguous())
     return (B, H, W, L, Ht, Wt, C, 1 if tex.dim() == 4 else 0, TEX_FILTERS[filter_mode], TEX_BOUNDARIES[boundary_mode]), ts, dev
 
@@ -1117,30 +1003,27 @@ def texture_backward_cuda(uv, tex, render_layers, filter_mode, boundary_mode, gr
 
 def _texture_cube_args(dirs, tex, render_layers, filter_mode, grad_out=None):
     """Checks of a cube-map call -> (sizes (B, H, W, L, N, C, view_textures, filter), contiguous tensors, device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
-    bad(dirs.dim() != 5 or dirs.size(4) != 3, f"dirs must have dimensions (B, H, W, L, 3), got {tuple(dirs.shape)}")
+    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
+    _bad(dirs.dim() != 5 or dirs.size(4) != 3, f"dirs must have dimensions (B, H, W, L, 3), got {tuple(dirs.shape)}")
     B, H, W, L = (int(x) for x in dirs.shape[:4])
-    bad(tex.dim() not in (4, 5), "tex must have dimensions (6, N, N, C) or (B, 6, N, N, C)")
-    bad(tex.dim() == 5 and tex.size(0) != B, f"tex must have dimensions (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
+    _bad(tex.dim() not in (4, 5), "tex must have dimensions (6, N, N, C) or (B, 6, N, N, C)")
+    _bad(tex.dim() == 5 and tex.size(0) != B, f"tex must have dimensions (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
     six, Nr, N, C = (int(x) for x in tex.shape[-4:])
-    bad(six != 6, f"tex must have six faces, (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
-    bad(Nr != N, f"tex must have square faces, got {tuple(tex.shape)}")
-    bad(N < 1, "tex must have at least one row and one column per face")
-    bad(C < 1, "tex must have at least one channel")
-    bad(6 * N * N >= 2 ** 31, "tex: 6 * N * N must be below 2^31")
-    bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+    _bad(six != 6, f"tex must have six faces, (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
+    _bad(Nr != N, f"tex must have square faces, got {tuple(tex.shape)}")
+    _bad(N < 1, "tex must have at least one row and one column per face")
+    _bad(C < 1, "tex must have at least one channel")
+    _bad(6 * N * N >= 2 ** 31, "tex: 6 * N * N must be below 2^31")
+    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
         f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
-    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
+    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
         f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
     dev = _require_gpu(*[t for t in (dirs, tex, render_layers, grad_out) if t is not None])
     f32, i32 = torch.float32, torch.int32
     named = (("dirs", dirs, f32), ("tex", tex, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
     ts = []
     for name, t, dt in named:
-        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
         ts.append(None if t is None else t.contiguous())
     return (B, H, W, L, N, C, 1 if tex.dim() == 5 else 0, TEX_FILTERS[filter_mode]), ts, dev
 
@@ -1184,24 +1067,21 @@ def texture_cube_backward_cuda(dirs, tex, render_layers, filter_mode, grad_out, 
 
 def _vertex_normals_args(verts, faces, offsets, corners, normals=None, lens=None, grad_normals=None):
     """Checks of a vertex-normals call -> ((P, F), contiguous tensors, device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(verts.dim() != 2 or verts.size(1) != 3, f"verts must have dimensions (P, 3), got {tuple(verts.shape)}")
-    bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
+    _bad(verts.dim() != 2 or verts.size(1) != 3, f"verts must have dimensions (P, 3), got {tuple(verts.shape)}")
+    _bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
     P, F = int(verts.size(0)), int(faces.size(0))
-    bad(3 * F >= 2 ** 31, "faces: 3 * F must be below 2^31")
-    bad(tuple(offsets.shape) != (P + 1,), f"offsets must have dimensions ({P + 1},), got {tuple(offsets.shape)}")
-    bad(tuple(corners.shape) != (3 * F,), f"corners must have dimensions ({3 * F},), got {tuple(corners.shape)}")
+    _bad(3 * F >= 2 ** 31, "faces: 3 * F must be below 2^31")
+    _bad(tuple(offsets.shape) != (P + 1,), f"offsets must have dimensions ({P + 1},), got {tuple(offsets.shape)}")
+    _bad(tuple(corners.shape) != (3 * F,), f"corners must have dimensions ({3 * F},), got {tuple(corners.shape)}")
     for name, t, shape in (("normals", normals, (P, 3)), ("len", lens, (P,)), ("grad_normals", grad_normals, (P, 3))):
-        bad(t is not None and tuple(t.shape) != shape, f"{name} must have dimensions {shape}, got {tuple(t.shape) if t is not None else None}")
+        _bad(t is not None and tuple(t.shape) != shape, f"{name} must have dimensions {shape}, got {tuple(t.shape) if t is not None else None}")
     f32, i32 = torch.float32, torch.int32
     named = (("verts", verts, f32), ("faces", faces, i32), ("offsets", offsets, i32), ("corners", corners, i32),
              ("normals", normals, f32), ("len", lens, f32), ("grad_normals", grad_normals, f32))
     dev = _require_gpu(*[t for _, t, _ in named if t is not None])
     ts = []
     for name, t, dt in named:
-        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
         ts.append(None if t is None else t.contiguous())
     return (P, F), ts, dev
 
@@ -1247,27 +1127,24 @@ def vertex_normals_backward_cuda(verts, faces, offsets, corners, normalize, norm
 
 def _shading_args(render_layers, t, normals, image_ray_o, image_ray_d, grads=()):
     """Checks of a shading-vectors call -> ((B, H, W, L, flags), contiguous tensors, device, keep-alive list, window)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+    _bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
     B, H, W, L = (int(x) for x in render_layers.shape)
-    bad(tuple(t.shape) != (B, H, W, L), f"t must have dimensions {(B, H, W, L)}, got {tuple(t.shape)}")
-    bad(normals is not None and tuple(normals.shape) != (B, H, W, L, 3),
+    _bad(tuple(t.shape) != (B, H, W, L), f"t must have dimensions {(B, H, W, L)}, got {tuple(t.shape)}")
+    _bad(normals is not None and tuple(normals.shape) != (B, H, W, L, 3),
         f"normals must have dimensions {(B, H, W, L, 3)}, got {tuple(normals.shape) if normals is not None else None}")
     for name, g in grads:
-        bad(g is not None and tuple(g.shape) != (B, H, W, L, 3),
+        _bad(g is not None and tuple(g.shape) != (B, H, W, L, 3),
             f"{name} must have dimensions {(B, H, W, L, 3)}, got {tuple(g.shape) if g is not None else None}")
     f32, i32 = torch.float32, torch.int32
     named = (("render_layers", render_layers, i32), ("t", t, f32), ("normals", normals, f32), ("image_ray_o", image_ray_o, f32),
              ("image_ray_d", image_ray_d, f32)) + tuple((name, g, f32) for name, g in grads)
     dev = _require_gpu(*[x for _, x, _ in named if x is not None])
     ana = _analytic(B, dev)
-    bad(ana is None and (tuple(image_ray_o.shape) != (B, H, W, 3) or tuple(image_ray_d.shape) != (B, H, W, 3)),
+    _bad(ana is None and (tuple(image_ray_o.shape) != (B, H, W, 3) or tuple(image_ray_d.shape) != (B, H, W, 3)),
         f"image_ray_o/image_ray_d must have dimensions {(B, H, W, 3)}")
     ts = []
     for name, x, dt in named:
-        bad(x is not None and x.dtype != dt, f"{name}: expected dtype {dt}, got {x.dtype if x is not None else None}")
+        _bad(x is not None and x.dtype != dt, f"{name}: expected dtype {dt}, got {x.dtype if x is not None else None}")
         ts.append(None if x is None else x.contiguous())
     keep: list = []
     flags = 0
@@ -1296,7 +1173,7 @@ def shading_vectors_cuda(render_layers, t, normals, image_ray_o, image_ray_d):
     if B * H * W * L == 0:
         return outs
     with torch.cuda.device(dev):
-        if lib.dm2_shading_vectors_window(*sizes, None if win is None else ctypes.byref(win), _ptr(rl), _ptr(tt), _ptr(nr), _ptr(ro),
+        if lib.dm2_shading_vectors_window(*sizes, _win(win), _ptr(rl), _ptr(tt), _ptr(nr), _ptr(ro),
                                           _ptr(rd), _ptr(cam), *(_ptr(o) for o in outs), *((None, None) if nr is None else ()),
                                           _stream(dev)):
             raise _err(lib, "shading_vectors_cuda")
@@ -1323,7 +1200,7 @@ def shading_vectors_backward_cuda(render_layers, t, normals, image_ray_o, image_
     if B * H * W * L == 0:
         return dt, dn
     with torch.cuda.device(dev):
-        if lib.dm2_shading_vectors_backward_window(*sizes, None if win is None else ctypes.byref(win), _ptr(rl), _ptr(tt), _ptr(nr),
+        if lib.dm2_shading_vectors_backward_window(*sizes, _win(win), _ptr(rl), _ptr(tt), _ptr(nr),
                                                    _ptr(ro), _ptr(rd), _ptr(cam), _ptr(gp), _ptr(gn), _ptr(gr), _ptr(dt), _ptr(dn),
                                                    _stream(dev)):
             raise _err(lib, "shading_vectors_backward_cuda")
@@ -1337,21 +1214,18 @@ def bary_derivatives_cuda(render_layers, verts, faces, ray_cam):
     each view -> (dbary_dx, dbary_dy), each (B,H,W,L,3) float32: the derivatives of (1 - u - v, u, v) with respect to the
     pixel's x and y.  Under ``_C.window`` render_layers is a window's and the frame is the window's; otherwise the frame is
     (W, H).  Zeros in an empty slot (id outside [0, F) or a vertex outside [0, P)) and where the ray lies in the face's plane."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
     lib = load_library()
-    bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+    _bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
     B, H, W, L = (int(x) for x in render_layers.shape)
-    bad(verts.dim() != 2 or verts.size(1) != 3, f"verts must have dimensions (P, 3), got {tuple(verts.shape)}")
-    bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
-    bad(tuple(ray_cam.shape) != (B, 32), f"ray_cam must have dimensions ({B}, 32), got {tuple(ray_cam.shape)}")
+    _bad(verts.dim() != 2 or verts.size(1) != 3, f"verts must have dimensions (P, 3), got {tuple(verts.shape)}")
+    _bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
+    _bad(tuple(ray_cam.shape) != (B, 32), f"ray_cam must have dimensions ({B}, 32), got {tuple(ray_cam.shape)}")
     f32, i32 = torch.float32, torch.int32
     named = (("render_layers", render_layers, i32), ("verts", verts, f32), ("faces", faces, i32), ("ray_cam", ray_cam, f32))
     dev = _require_gpu(*[t for _, t, _ in named])
     ts = []
     for name, t, dt in named:
-        bad(t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype}")
+        _bad(t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype}")
         ts.append(t.contiguous())
     rl, vs, fc, cam = ts
     dx = torch.empty((B, H, W, L, 3), dtype=f32, device=dev)               # (every element written by the kernel)
@@ -1361,7 +1235,7 @@ def bary_derivatives_cuda(render_layers, verts, faces, ray_cam):
     keep: list = []
     win = _window(B, W, H, dev, keep)
     with torch.cuda.device(dev):
-        if lib.dm2_bary_derivatives_window(B, H, W, L, int(verts.size(0)), int(faces.size(0)), None if win is None else ctypes.byref(win),
+        if lib.dm2_bary_derivatives_window(B, H, W, L, int(verts.size(0)), int(faces.size(0)), _win(win),
                                            _ptr(rl), _ptr(vs), _ptr(fc), _ptr(cam), _ptr(dx), _ptr(dy), _stream(dev)):
             raise _err(lib, "bary_derivatives_cuda")
     return dx, dy
@@ -1387,23 +1261,20 @@ def _max_level_code(max_mip_level):
 
 def _mipmap_args(tex, max_mip_level, grad_mip=None):
     """Checks of a mip chain call -> (sizes (NB, Ht, Wt, C, max level code), T, contiguous tensors, device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
+    _bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
     Ht, Wt, C = (int(x) for x in tex.shape[-3:])
-    bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
-    bad(C < 1, "tex must have at least one channel")
+    _bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
+    _bad(C < 1, "tex must have at least one channel")
     _, _, T = mip_layout(Ht, Wt, max_mip_level)
-    bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
+    _bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
     NB = int(tex.size(0)) if tex.dim() == 4 else 1
     shape = ((NB,) if tex.dim() == 4 else ()) + (T, C)
-    bad(grad_mip is not None and tuple(grad_mip.shape) != shape,
+    _bad(grad_mip is not None and tuple(grad_mip.shape) != shape,
         f"grad_mip must have dimensions {shape}, got {tuple(grad_mip.shape) if grad_mip is not None else None}")
     dev = _require_gpu(*[t for t in (tex, grad_mip) if t is not None])
     ts = []
     for name, t in (("tex", tex), ("grad_mip", grad_mip)):
-        bad(t is not None and t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype if t is not None else None}")
+        _bad(t is not None and t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype if t is not None else None}")
         ts.append(None if t is None else t.contiguous())
     return (NB, Ht, Wt, C, _max_level_code(max_mip_level)), shape, ts, dev
 
@@ -1439,20 +1310,17 @@ def texture_mipmaps_backward_cuda(tex, max_mip_level, grad_mip):
 def _texture_mip_args(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out=None):
     """Checks of a trilinear texture call -> (sizes (B, H, W, L, Ht, Wt, C, view_textures, boundary, max level code),
     contiguous tensors (uv, uv_da, tex, mip, render_layers, grad_out), device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
     sizes, (uvc, tx, rl, go), dev = _texture_args(uv, tex, render_layers, "linear", boundary_mode, grad_out)
     B, H, W, L, Ht, Wt, C, per_view = sizes[:8]
-    bad(tuple(uv_da.shape) != (B, H, W, L, 4), f"uv_da must have dimensions {(B, H, W, L, 4)}, got {tuple(uv_da.shape)}")
+    _bad(tuple(uv_da.shape) != (B, H, W, L, 4), f"uv_da must have dimensions {(B, H, W, L, 4)}, got {tuple(uv_da.shape)}")
     _, _, T = mip_layout(Ht, Wt, max_mip_level)
-    bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
+    _bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
     shape = ((B,) if per_view else ()) + (T, C)
-    bad(tuple(mip.shape) != shape,
+    _bad(tuple(mip.shape) != shape,
         f"mip must have dimensions {shape} for tex {tuple(tex.shape)} and max_mip_level {max_mip_level}, got {tuple(mip.shape)}")
     _require_gpu(uv, uv_da, mip)
     for name, t in (("uv_da", uv_da), ("mip", mip)):
-        bad(t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype}")
+        _bad(t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype}")
     return sizes[:8] + (sizes[9], _max_level_code(max_mip_level)), (uvc, uv_da.contiguous(), tx, mip.contiguous(), rl, go), dev
 
 
@@ -1500,26 +1368,23 @@ COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1     # include/dm2_hip.
 
 def _composite_args(values, alpha, render_layers, background, n_contrib=None, grad_out=None, grad_acc=None):
     """Checks of a composite call -> (sizes (B, H, W, L, C, F, alpha_mode), contiguous tensors, device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(values.dim() != 5, f"values must have dimensions (B, H, W, L, C), got {tuple(values.shape)}")
+    _bad(values.dim() != 5, f"values must have dimensions (B, H, W, L, C), got {tuple(values.shape)}")
     B, H, W, L, C = (int(x) for x in values.shape)
-    bad(C < 1, "values must have at least one channel")
-    bad(alpha.dim() not in (1, 4), f"alpha must have dimensions {(B, H, W, L)} (per slot) or (F,) (per face), got {tuple(alpha.shape)}")
+    _bad(C < 1, "values must have at least one channel")
+    _bad(alpha.dim() not in (1, 4), f"alpha must have dimensions {(B, H, W, L)} (per slot) or (F,) (per face), got {tuple(alpha.shape)}")
     per_face = alpha.dim() == 1
-    bad(not per_face and tuple(alpha.shape) != (B, H, W, L),
+    _bad(not per_face and tuple(alpha.shape) != (B, H, W, L),
         f"alpha must have dimensions {(B, H, W, L)} (per slot) or (F,) (per face), got {tuple(alpha.shape)}")
-    bad(per_face and render_layers is None, "a per-face alpha (F,) needs render_layers")
-    bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+    _bad(per_face and render_layers is None, "a per-face alpha (F,) needs render_layers")
+    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
         f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
-    bad(background is not None and tuple(background.shape) != (C,),
+    _bad(background is not None and tuple(background.shape) != (C,),
         f"background must have dimensions {(C,)}, got {tuple(background.shape) if background is not None else None}")
-    bad(n_contrib is not None and tuple(n_contrib.shape) != (B, H, W),
+    _bad(n_contrib is not None and tuple(n_contrib.shape) != (B, H, W),
         f"n_contrib must have dimensions {(B, H, W)}, got {tuple(n_contrib.shape) if n_contrib is not None else None}")
-    bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, C),
+    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, C),
         f"grad_out must have dimensions {(B, H, W, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
-    bad(grad_acc is not None and tuple(grad_acc.shape) != (B, H, W),
+    _bad(grad_acc is not None and tuple(grad_acc.shape) != (B, H, W),
         f"grad_acc must have dimensions {(B, H, W)}, got {tuple(grad_acc.shape) if grad_acc is not None else None}")
     f32, i32 = torch.float32, torch.int32
     named = (("values", values, f32), ("alpha", alpha, f32), ("render_layers", render_layers, i32), ("background", background, f32),
@@ -1527,7 +1392,7 @@ def _composite_args(values, alpha, render_layers, background, n_contrib=None, gr
     dev = _require_gpu(*[t for _, t, _ in named if t is not None])
     ts = []
     for name, t, dt in named:
-        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
         ts.append(None if t is None else t.contiguous())
     F = int(alpha.size(0)) if per_face else 0
     return (B, H, W, L, C, F, COMPOSITE_ALPHA_PER_FACE if per_face else COMPOSITE_ALPHA_PER_SLOT), ts, dev
@@ -1595,15 +1460,12 @@ def _coverage_inside(inside, render_layers):
 
 def _coverage_args(render_layers, verts_image, faces, temperature, grad_cov=None):
     """Checks of a coverage call -> (sizes (B, H, W, L, P, F, temperature), contiguous tensors, device)."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+    _bad(render_layers.dim() != 4, f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
     B, H, W, L = (int(x) for x in render_layers.shape)
-    bad(verts_image.dim() != 3 or verts_image.size(0) != B or verts_image.size(2) != 2,
+    _bad(verts_image.dim() != 3 or verts_image.size(0) != B or verts_image.size(2) != 2,
         f"verts_image must have dimensions ({B}, P, 2), got {tuple(verts_image.shape)}")
-    bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
-    bad(grad_cov is not None and tuple(grad_cov.shape) != (B, H, W, L),
+    _bad(faces.dim() != 2 or faces.size(1) != 3, f"faces must have dimensions (F, 3), got {tuple(faces.shape)}")
+    _bad(grad_cov is not None and tuple(grad_cov.shape) != (B, H, W, L),
         f"grad_cov must have dimensions {(B, H, W, L)}, got {tuple(grad_cov.shape) if grad_cov is not None else None}")
     temperature = float(temperature)
     if not (0.0 <= temperature <= 1.0):
@@ -1613,7 +1475,7 @@ def _coverage_args(render_layers, verts_image, faces, temperature, grad_cov=None
     dev = _require_gpu(*[t for _, t, _ in named if t is not None])
     ts = []
     for name, t, dt in named:
-        bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
         ts.append(None if t is None else t.contiguous())
     return (B, H, W, L, int(verts_image.size(1)), int(faces.size(0)), temperature), ts, dev
 
@@ -1624,7 +1486,7 @@ def coverage_cuda(render_layers, verts_image, faces, temperature=1.0, inside=Non
     render_layers (B,H,W,L) int32 face ids over the full frame, verts_image (B,P,2) float32, faces (F,3) int32, temperature in
     [0, 1] (ValueError otherwise) -> cov (B,H,W,L) float32: 0 in an empty slot and where the triangle misses the pixel, else
     (1 - temperature) + area * temperature.  ``inside`` (B,H,W,L) bool or integer (``rasterize(overlap=True)``'s): a non-empty
-    slot where it is 0 gets area * temperature instead (dm2_coverage_window_inside)."""
+    slot where it is 0 gets area * temperature instead (dm2_coverage's inside)."""
     lib = load_library()
     sizes, (rl, vi, fc, _), dev = _coverage_args(render_layers, verts_image, faces, temperature)
     ins = None if inside is None else _coverage_inside(inside, render_layers)
@@ -1635,14 +1497,7 @@ def coverage_cuda(render_layers, verts_image, faces, temperature=1.0, inside=Non
     keep: list = []
     win = _window(B, W, H, dev, keep)                    # (then render_layers is the window's, verts_image the frame's)
     with torch.cuda.device(dev):
-        if ins is not None:
-            rc = lib.dm2_coverage_window_inside(*sizes, None if win is None else ctypes.byref(win), _ptr(rl), _ptr(ins), _ptr(vi), _ptr(fc),
-                                                _ptr(cov), _stream(dev))
-        elif win is None:
-            rc = lib.dm2_coverage(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev))
-        else:
-            rc = lib.dm2_coverage_window(*sizes, ctypes.byref(win), _ptr(rl), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev))
-        if rc:
+        if lib.dm2_coverage(*sizes, _win(win), _ptr(rl), _ptr(ins), _ptr(vi), _ptr(fc), _ptr(cov), _stream(dev)):
             raise _err(lib, "coverage_cuda")
     return cov
 
@@ -1661,12 +1516,7 @@ def coverage_backward_cuda(render_layers, verts_image, faces, temperature, grad_
     keep: list = []
     win = _window(B, W, H, dev, keep)
     with torch.cuda.device(dev):
-        if win is None:
-            rc = lib.dm2_coverage_backward(*sizes, _ptr(rl), _ptr(vi), _ptr(fc), _ptr(gc), _ptr(dimage), _stream(dev))
-        else:
-            rc = lib.dm2_coverage_backward_window(*sizes, ctypes.byref(win), _ptr(rl), _ptr(vi), _ptr(fc), _ptr(gc), _ptr(dimage),
-                                                  _stream(dev))
-        if rc:
+        if lib.dm2_coverage_backward(*sizes, _win(win), _ptr(rl), _ptr(vi), _ptr(fc), _ptr(gc), _ptr(dimage), _stream(dev)):
             raise _err(lib, "coverage_backward_cuda")
     return dimage
 
@@ -1674,29 +1524,26 @@ def coverage_backward_cuda(render_layers, verts_image, faces, temperature, grad_
 def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                     image_ray_o, image_ray_d, keep):
     """Checks (in the style of generate_render_layers_cuda) + the dm2_layer_composite_desc of a composite call."""
-    def bad(cond, msg):
-        if cond:
-            raise RuntimeError(msg)
-    bad(render_layers.dim() != 4, "render_layers must have dimensions (B, H, W, L)")
-    bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
-    bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
-    bad(verts_color.dim() != 2 or verts_color.size(1) != 3, "vert color must have dimensions (P, 3)")
-    bad(faces_opacity.dim() != 1 or faces_opacity.size(0) != faces.size(0), "face opacity must have dimensions (F,)")
-    bad(faces_intense.dim() != 2 or faces_intense.size(1) != faces.size(0), "faces_intense must have dimensions (B, F,)")
-    bad(verts_ndc.dim() != 3 or verts_ndc.size(2) != 3, "verts_ndc must have dimensions (B, P, 3)")
-    bad(background.dim() != 1 or background.size(0) != 3, "background must have dimensions (3,)")
-    bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
-    bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
+    _bad(render_layers.dim() != 4, "render_layers must have dimensions (B, H, W, L)")
+    _bad(verts.dim() != 2 or verts.size(1) != 3, "verts must have dimensions (P, 3)")
+    _bad(faces.dim() != 2 or faces.size(1) != 3, "faces must have dimensions (F, 3)")
+    _bad(verts_color.dim() != 2 or verts_color.size(1) != 3, "vert color must have dimensions (P, 3)")
+    _bad(faces_opacity.dim() != 1 or faces_opacity.size(0) != faces.size(0), "face opacity must have dimensions (F,)")
+    _bad(faces_intense.dim() != 2 or faces_intense.size(1) != faces.size(0), "faces_intense must have dimensions (B, F,)")
+    _bad(verts_ndc.dim() != 3 or verts_ndc.size(2) != 3, "verts_ndc must have dimensions (B, P, 3)")
+    _bad(background.dim() != 1 or background.size(0) != 3, "background must have dimensions (3,)")
+    _bad(image_ray_o.dim() != 4 or image_ray_o.size(3) != 3, "image_ray_o must have dimensions (B, H, W, 3)")
+    _bad(image_ray_d.dim() != 4 or image_ray_d.size(3) != 3, "image_ray_d must have dimensions (B, H, W, 3)")
     dev = _require_gpu(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                        image_ray_o, image_ray_d)
     f32, i32 = torch.float32, torch.int32
     B, H, W, L = (int(x) for x in render_layers.shape)
     P, F = verts.size(0), faces.size(0)
-    bad(tuple(verts_color.shape) != (P, 3), "verts_color must have dimensions (P, 3)")
-    bad(tuple(faces_intense.shape) != (B, F), "faces_intense must have dimensions (B, F)")
-    bad(tuple(verts_ndc.shape) != (B, P, 3), "verts_ndc must have dimensions (B, P, 3)")
+    _bad(tuple(verts_color.shape) != (P, 3), "verts_color must have dimensions (P, 3)")
+    _bad(tuple(faces_intense.shape) != (B, F), "faces_intense must have dimensions (B, F)")
+    _bad(tuple(verts_ndc.shape) != (B, P, 3), "verts_ndc must have dimensions (B, P, 3)")
     ana = _analytic(B, dev)
-    bad(ana is None and (tuple(image_ray_o.shape) != (B, H, W, 3) or tuple(image_ray_d.shape) != (B, H, W, 3)),
+    _bad(ana is None and (tuple(image_ray_o.shape) != (B, H, W, 3) or tuple(image_ray_d.shape) != (B, H, W, 3)),
         "image_ray_o/image_ray_d must have dimensions (B, H, W, 3)")
     ts = dict(render_layers=_c(render_layers, i32), verts=_c(verts, f32), faces=_c(faces, i32), verts_color=_c(verts_color, f32),
               faces_opacity=_c(faces_opacity, f32), faces_intense=_c(faces_intense, f32), verts_ndc=_c(verts_ndc, f32),
@@ -1706,13 +1553,7 @@ def _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, fac
     d.B, d.P, d.F, d.W, d.H, d.L, d.flags = B, P, F, W, H, L, 0
     for k, t in ts.items():
         setattr(d, k, t.data_ptr() if t.numel() > 0 else None)
-    if ana is not None:
-        if (ana[1], ana[2]) != _frame_size(W, H):
-            raise RuntimeError("analytic_rays: the image size differs from render_layers' width / height")
-        keep.append(ana[0])
-        d.flags |= DM2_FLAG_ANALYTIC_RAYS
-        d.ray_cam = ana[0].data_ptr()
-        d.image_ray_o = d.image_ray_d = None
+    _analytic_onto(d, ana, W, H, keep, "analytic_rays: the image size differs from render_layers' width / height")
     return d, dev
 
 
@@ -1724,7 +1565,7 @@ def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacit
     faces_opacity (F), faces_intense (B,F), verts_ndc (B,P,3), background (3), image_ray_o / image_ray_d (B,H,W,3) of the
     full frame (placeholders under ``analytic_rays``) -> (color (B,H,W,3), depth_raw (B,H,W) NDC depth with background 1,
     final_T (B,H,W), n_contrib (B,H,W) int32: 1 + index of the last layer that blended); under ``face_weights_output`` a
-    fifth: face_weights (B,F), the sum of alpha * T over each face's blends (dm2_layers_composite_weights)."""
+    fifth: face_weights (B,F), the sum of alpha * T over each face's blends (dm2_layers_composite's out_face_weights)."""
     lib = load_library()
     keep: list = []
     d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
@@ -1741,15 +1582,8 @@ def composite_layers_cuda(render_layers, verts, faces, verts_color, faces_opacit
     if B * H * W == 0:
         return (color, depth, final_T, n_contrib) + extra
     with torch.cuda.device(dev):
-        if win is not None:
-            rc = lib.dm2_layers_composite_window(ctypes.byref(d), ctypes.byref(win), _ptr(color), _ptr(depth), _ptr(final_T),
-                                                 _ptr(n_contrib), _ptr(weights), _stream(dev))
-        elif weights is None:
-            rc = lib.dm2_layers_composite(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib), _stream(dev))
-        else:
-            rc = lib.dm2_layers_composite_weights(ctypes.byref(d), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib),
-                                                  _ptr(weights), _stream(dev))
-        if rc:
+        if lib.dm2_layers_composite(ctypes.byref(d), _win(win), _ptr(color), _ptr(depth), _ptr(final_T), _ptr(n_contrib),
+                                    _ptr(weights), _stream(dev)):
             raise _err(lib, "composite_layers_cuda")
     return (color, depth, final_T, n_contrib) + extra
 
@@ -1759,7 +1593,7 @@ def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, fac
     """Gradients of composite_layers_cuda (dm2_layers_composite_backward): dL_dcolor (B,H,W,3), dL_ddepth (B,H,W) of depth_raw,
     n_contrib from the forward -> (dL_dverts_color (P,3), dL_dfaces_opacity (F), dL_dverts_ndc (B,P,3) [z only],
     dL_dfaces_intense (B,F)).  Nothing reaches verts (through the barycentrics) or background.  dL_dout_alpha (B,H,W) or
-    None: the gradient of alpha = 1 - final_T (dm2_layers_composite_backward_alpha; it reaches dL_dfaces_opacity only)."""
+    None: the gradient of alpha = 1 - final_T (it reaches dL_dfaces_opacity only)."""
     lib = load_library()
     keep: list = []
     d, dev = _composite_desc(render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
@@ -1783,16 +1617,8 @@ def composite_layers_backward_cuda(render_layers, verts, faces, verts_color, fac
     if B * H * W == 0:
         return dcolor, dopacity, dndc, dintense
     with torch.cuda.device(dev):
-        if win is not None:
-            rc = lib.dm2_layers_composite_backward_window(ctypes.byref(d), ctypes.byref(win), _ptr(gc), _ptr(gd), _ptr(ga), _ptr(nc),
-                                                          _ptr(dcolor), _ptr(dopacity), _ptr(dndc), _ptr(dintense), _stream(dev))
-        elif ga is None:
-            rc = lib.dm2_layers_composite_backward(ctypes.byref(d), _ptr(gc), _ptr(gd), _ptr(nc), _ptr(dcolor), _ptr(dopacity),
-                                                   _ptr(dndc), _ptr(dintense), _stream(dev))
-        else:
-            rc = lib.dm2_layers_composite_backward_alpha(ctypes.byref(d), _ptr(gc), _ptr(gd), _ptr(ga), _ptr(nc), _ptr(dcolor),
-                                                         _ptr(dopacity), _ptr(dndc), _ptr(dintense), _stream(dev))
-        if rc:
+        if lib.dm2_layers_composite_backward(ctypes.byref(d), _win(win), _ptr(gc), _ptr(gd), _ptr(ga), _ptr(nc), _ptr(dcolor),
+                                             _ptr(dopacity), _ptr(dndc), _ptr(dintense), _stream(dev)):
             raise _err(lib, "composite_layers_backward_cuda")
     return dcolor, dopacity, dndc, dintense
 

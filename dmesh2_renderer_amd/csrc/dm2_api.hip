@@ -260,32 +260,18 @@ static int forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t m
     return 0;
 }
 
-int dm2_forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound, void* face_scratch, size_t face_bytes,
-                    void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
-                    float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream, int32_t* forward_mode) {
-    return dm2_forward_run_weights(d, num_rendered, max_tile_entries, pair_bound, face_scratch, face_bytes, binning_scratch, binning_bytes,
-                                   image_scratch, image_bytes, out_color, out_depth, out_tri_cnt, nullptr, stream, forward_mode);
-}
-
-int dm2_forward_run_weights(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound,
-                            void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                            void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt,
-                            float* out_face_weights, void* stream, int32_t* forward_mode) {
+int dm2_forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound,
+                    void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                    void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt,
+                    float* out_face_weights, void* stream, int32_t* forward_mode) {
     return forward_run(d, num_rendered, max_tile_entries, pair_bound, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch,
                        image_bytes, out_color, out_depth, out_tri_cnt, out_face_weights, stream, false, forward_mode);
 }
 
 int dm2_forward(const dm2_render_desc* d, void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream,
-                int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound, int32_t* forward_mode) {
-    return dm2_forward_weights(d, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch, image_bytes, out_color,
-                               out_depth, out_tri_cnt, nullptr, stream, num_rendered, max_tile_entries, pair_bound, forward_mode);
-}
-
-int dm2_forward_weights(const dm2_render_desc* d, void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                        void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt,
-                        float* out_face_weights, void* stream, int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound,
-                        int32_t* forward_mode) {
+                void* image_scratch, size_t image_bytes, float* out_color, float* out_depth, int32_t* out_tri_cnt,
+                float* out_face_weights, void* stream, int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound,
+                int32_t* forward_mode) {
     if (check_render_desc(d)) return 1;
     if (!pair_bound) return fail("pair_bound is null");
     if (forward_mode) *forward_mode = DM2_FWD_NONE;
@@ -317,22 +303,12 @@ int dm2_forward_alpha(const dm2_render_desc* d, const void* image_scratch, size_
     return 0;
 }
 
-int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode, const float* dL_dout_color, const float* dL_dout_depth,
+int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode, const float* dL_dout_color,
+                 const float* dL_dout_depth, const float* dL_dout_alpha,
                  const void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
                  const void* image_scratch, size_t image_bytes, void* tie_scratch, size_t tie_bytes,
                  float* dL_dverts, float* dL_dverts_color, float* dL_dfaces_opacity, float* dL_dverts_ndc,
                  float* dL_dfaces_intense, float* dL_daa_face_verts, void* stream) {
-    return dm2_backward_alpha(d, num_rendered, forward_mode, dL_dout_color, dL_dout_depth, nullptr, face_scratch, face_bytes,
-                              binning_scratch, binning_bytes, image_scratch, image_bytes, tie_scratch, tie_bytes, dL_dverts,
-                              dL_dverts_color, dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, dL_daa_face_verts, stream);
-}
-
-int dm2_backward_alpha(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode, const float* dL_dout_color,
-                       const float* dL_dout_depth, const float* dL_dout_alpha,
-                       const void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                       const void* image_scratch, size_t image_bytes, void* tie_scratch, size_t tie_bytes,
-                       float* dL_dverts, float* dL_dverts_color, float* dL_dfaces_opacity, float* dL_dverts_ndc,
-                       float* dL_dfaces_intense, float* dL_daa_face_verts, void* stream) {
     if (check_render_desc(d)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int64_t N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
@@ -386,13 +362,8 @@ static int resolve_window(const dm2_window* win, int W, int H, dm2_window* out) 
     return 0;
 }
 
-int dm2_layers_plan(const dm2_layers_desc* d, void* face_scratch, size_t face_bytes, void* stream, int64_t* num_rendered,
-                    int64_t* max_tile_entries) {
-    return dm2_layers_plan_window(d, nullptr, face_scratch, face_bytes, stream, num_rendered, max_tile_entries);
-}
-
-int dm2_layers_plan_window(const dm2_layers_desc* d, const dm2_window* win, void* face_scratch, size_t face_bytes, void* stream,
-                           int64_t* num_rendered, int64_t* max_tile_entries) {
+int dm2_layers_plan(const dm2_layers_desc* d, const dm2_window* win, void* face_scratch, size_t face_bytes, void* stream,
+                    int64_t* num_rendered, int64_t* max_tile_entries) {
     if (check_layers_desc(d)) return 1;
     dm2_window w;
     if (resolve_window(win, d->W, d->H, &w)) return 1;
@@ -413,38 +384,41 @@ int dm2_layers_plan_window(const dm2_layers_desc* d, const dm2_window* win, void
     return plan_meta_wait(fs.plan_meta, st, num_rendered, max_tile_entries, nullptr);
 }
 
-int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries, void* face_scratch, size_t face_bytes,
-                   void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
-                   void* tet_scratch, size_t tet_bytes,
-                   int32_t* render_layers, int32_t* render_layers_cnt, void* stream) {
-    return dm2_layers_run_window(d, nullptr, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes,
-                                 image_scratch, image_bytes, tet_scratch, tet_bytes, render_layers, render_layers_cnt, stream);
+// The binning step of dm2_layers_run and dm2_rasterize_run: the tile lists of a dm2_layers_plan, ordered by min depth, and their
+// ranges (all empty without faces, where nothing was planned).
+static int layers_bin_sort(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries, void* face_scratch,
+                           size_t face_bytes, void* binning_scratch, size_t binning_bytes, uint2* ranges, dm2::FaceState* fs,
+                           dm2::BinningState* bs, hipStream_t st) {
+    const int64_t BF = (int64_t)d->B * d->F, Tn = tiles_of(d->B, d->W, d->H);
+    if (BF != 0) {
+        if (dm2_scratch_bytes(DM2_SCRATCH_FACE, BF, 2 * Tn) > face_bytes) return fail("face scratch too small");
+        if (dm2_scratch_bytes(DM2_SCRATCH_BINNING, num_rendered, Tn) > binning_bytes) return fail("binning scratch too small");
+        *fs = dm2::FaceState::carve(face_scratch, BF, Tn, dm2::scan_temp_bytes(BF), false);
+        *bs = dm2::BinningState::carve(binning_scratch, num_rendered, dm2::sort_temp_bytes(num_rendered, Tn));
+        DM2_HIP(dm2::launch_bin_sort(d->B, d->F, d->W, d->H, num_rendered, max_tile_entries, (d->flags & DM2_FLAG_LEGACY_KERNELS) != 0,
+                                     fs->min_depths, *fs, *bs, ranges, false, nullptr, st));   // renderer.cu:603
+    } else {
+        DM2_HIP(hipMemsetAsync(ranges, 0, (size_t)Tn * sizeof(uint2), st));
+    }
+    return 0;
 }
 
-int dm2_layers_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                          void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                          void* image_scratch, size_t image_bytes, void* tet_scratch, size_t tet_bytes,
-                          int32_t* render_layers, int32_t* render_layers_cnt, void* stream) {
+int dm2_layers_run(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                   void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                   void* image_scratch, size_t image_bytes, void* tet_scratch, size_t tet_bytes,
+                   int32_t* render_layers, int32_t* render_layers_cnt, void* stream) {
     if (check_layers_desc(d)) return 1;
     dm2_window w;
     if (resolve_window(win, d->W, d->H, &w)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t BF = (int64_t)d->B * d->F, N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
+    const int64_t N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
     if (N == 0) return 0;
     if (dm2_scratch_bytes(DM2_SCRATCH_LAYER_IMAGE, N, Tn) > image_bytes) return fail("image scratch too small");
     dm2::LayerImageState ls = dm2::LayerImageState::carve(image_scratch, N, Tn);
     dm2::FaceState fs{};
     dm2::BinningState bs{};
-    if (BF != 0) {
-        if (dm2_scratch_bytes(DM2_SCRATCH_FACE, BF, 2 * Tn) > face_bytes) return fail("face scratch too small");
-        if (dm2_scratch_bytes(DM2_SCRATCH_BINNING, num_rendered, Tn) > binning_bytes) return fail("binning scratch too small");
-        fs = dm2::FaceState::carve(face_scratch, BF, Tn, dm2::scan_temp_bytes(BF), false);
-        bs = dm2::BinningState::carve(binning_scratch, num_rendered, dm2::sort_temp_bytes(num_rendered, Tn));
-        DM2_HIP(dm2::launch_bin_sort(d->B, d->F, d->W, d->H, num_rendered, max_tile_entries, (d->flags & DM2_FLAG_LEGACY_KERNELS) != 0,
-                                     fs.min_depths, fs, bs, ls.ranges, false, nullptr, st));   // renderer.cu:603
-    } else {
-        DM2_HIP(hipMemsetAsync(ls.ranges, 0, (size_t)Tn * sizeof(uint2), st));
-    }
+    if (layers_bin_sort(d, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes, ls.ranges, &fs, &bs, st))
+        return 1;
     if (tet_scratch && dm2_scratch_bytes(DM2_SCRATCH_LAYER_TETS, d->T, 0) > tet_bytes) return fail("tet scratch too small");
     dm2::launch_layers(*d, w, fs, ls.ranges, bs.face_list, ls, tet_scratch, render_layers, render_layers_cnt, st);
     DM2_HIP(hipGetLastError());
@@ -458,24 +432,17 @@ static int check_rasterize_inputs(const dm2_layers_desc* d) {
     return 0;
 }
 
-int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries, void* face_scratch, size_t face_bytes,
-                      void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
-                      int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream) {
-    return dm2_rasterize_run_window(d, nullptr, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes,
-                                    image_scratch, image_bytes, render_layers, render_layers_cnt, bary, t, stream);
-}
-
-// dm2_rasterize_run_window (overlap == false: `inside` is not looked at) and dm2_rasterize_overlap_run_window: the same plan,
-// scratch and tile lists; only the kernel over the lists differs.
-static int rasterize_run(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                         void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                         void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
-                         float* bary, float* t, bool overlap, uint8_t* inside, void* stream) {
+// overlap == 0 (`inside` is not looked at) and overlap != 0: the same plan, scratch and tile lists; only the kernel over the
+// lists differs.
+int dm2_rasterize_run(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                      void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
+                      void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
+                      float* bary, float* t, int32_t overlap, uint8_t* inside, void* stream) {
     if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
     dm2_window w;
     if (resolve_window(win, d->W, d->H, &w)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t BF = (int64_t)d->B * d->F, N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
+    const int64_t N = (int64_t)d->B * d->H * d->W, Tn = tiles_of(d->B, d->W, d->H);
     if (N == 0) return 0;
     if (!render_layers_cnt || (d->L > 0 && (!render_layers || !bary || !t))) return fail("rasterize outputs must not be null");
     if (overlap && d->L > 0 && !inside) return fail("rasterize (overlap): inside must not be null");
@@ -488,63 +455,23 @@ static int rasterize_run(const dm2_layers_desc* d, const dm2_window* win, int64_
     dm2::LayerImageState ls = dm2::LayerImageState::carve(image_scratch, N, Tn);
     dm2::FaceState fs{};
     dm2::BinningState bs{};
-    if (BF != 0) {
-        if (dm2_scratch_bytes(DM2_SCRATCH_FACE, BF, 2 * Tn) > face_bytes) return fail("face scratch too small");
-        if (dm2_scratch_bytes(DM2_SCRATCH_BINNING, num_rendered, Tn) > binning_bytes) return fail("binning scratch too small");
-        fs = dm2::FaceState::carve(face_scratch, BF, Tn, dm2::scan_temp_bytes(BF), false);
-        bs = dm2::BinningState::carve(binning_scratch, num_rendered, dm2::sort_temp_bytes(num_rendered, Tn));
-        DM2_HIP(dm2::launch_bin_sort(d->B, d->F, d->W, d->H, num_rendered, max_tile_entries, (d->flags & DM2_FLAG_LEGACY_KERNELS) != 0,
-                                     fs.min_depths, fs, bs, ls.ranges, false, nullptr, st));
-    } else {
-        DM2_HIP(hipMemsetAsync(ls.ranges, 0, (size_t)Tn * sizeof(uint2), st));
-    }
+    if (layers_bin_sort(d, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes, ls.ranges, &fs, &bs, st))
+        return 1;
     if (overlap) dm2::launch_rasterize_overlap(*d, w, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, inside, st);
     else dm2::launch_rasterize(*d, w, fs, ls.ranges, bs.face_list, render_layers, render_layers_cnt, bary, t, st);
     DM2_HIP(hipGetLastError());
     return 0;
 }
 
-int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                             void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                             void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
-                             float* bary, float* t, void* stream) {
-    return rasterize_run(d, win, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch,
-                         image_bytes, render_layers, render_layers_cnt, bary, t, false, nullptr, stream);
-}
-
-int dm2_rasterize_overlap_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                                     void* face_scratch, size_t face_bytes, void* binning_scratch, size_t binning_bytes,
-                                     void* image_scratch, size_t image_bytes, int32_t* render_layers, int32_t* render_layers_cnt,
-                                     float* bary, float* t, uint8_t* inside, void* stream) {
-    return rasterize_run(d, win, num_rendered, max_tile_entries, face_scratch, face_bytes, binning_scratch, binning_bytes, image_scratch,
-                         image_bytes, render_layers, render_layers_cnt, bary, t, true, inside, stream);
-}
-
-int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
-                           float* dL_dverts, void* stream) {
-    return dm2_rasterize_backward_window(d, nullptr, render_layers, dL_dbary, dL_dt, dL_dverts, stream);
-}
-
-int dm2_rasterize_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
-                                  const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream) {
+int dm2_rasterize_backward(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers, const float* dL_dbary,
+                           const float* dL_dt, float* dL_dverts, int32_t overlap, void* stream) {
     if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
     dm2_window w;
     if (resolve_window(win, d->W, d->H, &w)) return 1;
     if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0 || (!dL_dbary && !dL_dt)) return 0;   // nothing is listed or nothing flows
     if (!render_layers || !dL_dverts) return fail("render_layers / dL_dverts must not be null");
-    dm2::launch_rasterize_backward(*d, w, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
-    DM2_HIP(hipGetLastError());
-    return 0;
-}
-
-int dm2_rasterize_overlap_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
-                                          const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream) {
-    if (check_layers_desc(d) || check_rasterize_inputs(d)) return 1;
-    dm2_window w;
-    if (resolve_window(win, d->W, d->H, &w)) return 1;
-    if ((int64_t)d->B * d->H * d->W == 0 || d->L == 0 || d->F == 0 || (!dL_dbary && !dL_dt)) return 0;   // nothing is listed or nothing flows
-    if (!render_layers || !dL_dverts) return fail("render_layers / dL_dverts must not be null");
-    dm2::launch_rasterize_overlap_backward(*d, w, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
+    if (overlap) dm2::launch_rasterize_overlap_backward(*d, w, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
+    else dm2::launch_rasterize_backward(*d, w, render_layers, dL_dbary, dL_dt, dL_dverts, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
@@ -911,19 +838,9 @@ static int check_coverage_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int3
     return 0;
 }
 
-int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                 const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream) {
-    return dm2_coverage_window(B, H, W, L, P, F, temperature, nullptr, render_layers, verts_image, faces, out_cov, stream);
-}
-
-int dm2_coverage_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature, const dm2_window* win,
-                        const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream) {
-    return dm2_coverage_window_inside(B, H, W, L, P, F, temperature, win, render_layers, nullptr, verts_image, faces, out_cov, stream);
-}
-
-int dm2_coverage_window_inside(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature, const dm2_window* win,
-                               const int32_t* render_layers, const uint8_t* inside, const float* verts_image, const int32_t* faces,
-                               float* out_cov, void* stream) {
+int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature, const dm2_window* win,
+                 const int32_t* render_layers, const uint8_t* inside, const float* verts_image, const int32_t* faces,
+                 float* out_cov, void* stream) {
     if (check_coverage_sizes(B, H, W, L, P, F, temperature)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
     if (!render_layers || !out_cov) return fail("coverage: render_layers and out_cov must not be null");
@@ -936,15 +853,8 @@ int dm2_coverage_window_inside(int32_t B, int32_t H, int32_t W, int32_t L, int32
 }
 
 int dm2_coverage_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                          const int32_t* render_layers, const float* verts_image, const int32_t* faces, const float* dL_dcov,
-                          float* dL_dverts_image, void* stream) {
-    return dm2_coverage_backward_window(B, H, W, L, P, F, temperature, nullptr, render_layers, verts_image, faces, dL_dcov,
-                                        dL_dverts_image, stream);
-}
-
-int dm2_coverage_backward_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                                 const dm2_window* win, const int32_t* render_layers, const float* verts_image,
-                                 const int32_t* faces, const float* dL_dcov, float* dL_dverts_image, void* stream) {
+                          const dm2_window* win, const int32_t* render_layers, const float* verts_image,
+                          const int32_t* faces, const float* dL_dcov, float* dL_dverts_image, void* stream) {
     if (check_coverage_sizes(B, H, W, L, P, F, temperature)) return 1;
     if ((int64_t)B * H * W * L == 0 || F == 0 || P == 0 || temperature == 0.0f || !dL_dcov || !dL_dverts_image) return 0;
     if (!render_layers || !faces || !verts_image) return fail("coverage_backward: render_layers, faces and verts_image must not be null");
@@ -973,18 +883,8 @@ static int check_composite_desc(const dm2_layer_composite_desc* d) {
     return 0;
 }
 
-int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
-                         int32_t* out_n_contrib, void* stream) {
-    return dm2_layers_composite_weights(d, out_color, out_depth, out_final_T, out_n_contrib, nullptr, stream);
-}
-
-int dm2_layers_composite_weights(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
-                                 int32_t* out_n_contrib, float* out_face_weights, void* stream) {
-    return dm2_layers_composite_window(d, nullptr, out_color, out_depth, out_final_T, out_n_contrib, out_face_weights, stream);
-}
-
-int dm2_layers_composite_window(const dm2_layer_composite_desc* d, const dm2_window* win, float* out_color, float* out_depth,
-                                float* out_final_T, int32_t* out_n_contrib, float* out_face_weights, void* stream) {
+int dm2_layers_composite(const dm2_layer_composite_desc* d, const dm2_window* win, float* out_color, float* out_depth,
+                         float* out_final_T, int32_t* out_n_contrib, float* out_face_weights, void* stream) {
     if (check_composite_desc(d)) return 1;
     dm2_window w;
     if (resolve_window(win, d->W, d->H, &w)) return 1;
@@ -995,24 +895,10 @@ int dm2_layers_composite_window(const dm2_layer_composite_desc* d, const dm2_win
     return 0;
 }
 
-int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
-                                  const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
-                                  float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream) {
-    return dm2_layers_composite_backward_alpha(d, dL_dout_color, dL_dout_depth, nullptr, n_contrib, dL_dverts_color,
-                                               dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, stream);
-}
-
-int dm2_layers_composite_backward_alpha(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
-                                        const float* dL_dout_alpha, const int32_t* n_contrib, float* dL_dverts_color,
-                                        float* dL_dfaces_opacity, float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream) {
-    return dm2_layers_composite_backward_window(d, nullptr, dL_dout_color, dL_dout_depth, dL_dout_alpha, n_contrib, dL_dverts_color,
-                                                dL_dfaces_opacity, dL_dverts_ndc, dL_dfaces_intense, stream);
-}
-
-int dm2_layers_composite_backward_window(const dm2_layer_composite_desc* d, const dm2_window* win, const float* dL_dout_color,
-                                         const float* dL_dout_depth, const float* dL_dout_alpha, const int32_t* n_contrib,
-                                         float* dL_dverts_color, float* dL_dfaces_opacity, float* dL_dverts_ndc,
-                                         float* dL_dfaces_intense, void* stream) {
+int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const dm2_window* win, const float* dL_dout_color,
+                                  const float* dL_dout_depth, const float* dL_dout_alpha, const int32_t* n_contrib,
+                                  float* dL_dverts_color, float* dL_dfaces_opacity, float* dL_dverts_ndc,
+                                  float* dL_dfaces_intense, void* stream) {
     if (check_composite_desc(d)) return 1;
     dm2_window w;
     if (resolve_window(win, d->W, d->H, &w)) return 1;

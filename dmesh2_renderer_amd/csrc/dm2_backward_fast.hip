@@ -34,7 +34,7 @@
 //       (third template parameter; launch_render_backward_fast picks it from the tiles a face touches)
 //   flush with (entry,component) global atomics.
 //
-// ALPHA (the second template parameter; dm2_backward_alpha with a non-null dL/d(alpha image)): the alpha image 1 - T_final
+// ALPHA (the second template parameter; dm2_backward with a non-null dL/d(alpha image)): the alpha image 1 - T_final
 // adds g_A T_final / (1 - alpha) to a pair's dL/dalpha, g_A prev_T_final for a last contributor of alpha 1 -- the background
 // term with -g_A in the place of bg.dL/dcolour + dL/ddepth.  Folded into that term: the prologue parks T_final K and
 // prev_T_final K in the two s_pixc rows that held T_final and prev_T_final, K = bg.g_c + g_d - g_A; no LDS and no register

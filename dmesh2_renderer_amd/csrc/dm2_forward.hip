@@ -17,7 +17,7 @@ namespace dm2 {
 
 constexpr int FWD_CHUNK = 128;
 
-// WEIGHTS (dm2_forward_weights): each blend adds its alpha * T into an LDS sum per staged face (ds_add_f32); behind the next
+// WEIGHTS (dm2_forward / dm2_forward_run with out_face_weights): each blend adds its alpha * T into an LDS sum per staged face (ds_add_f32); behind the next
 // barrier one lane per list entry flushes a non-zero sum to face_weights[b, face] with one global atomic.
 template <bool WEIGHTS>
 __global__ void __launch_bounds__(TILE_PIX)

@@ -35,7 +35,7 @@ constexpr float FP_EPS = 1.0e-5f;     // relative bound of |quick dot - exact nu
 // per staged face, for rays from `ro`: A = E2 x T, Bv = T x E1, Nn = E2 x E1 and the same sums with every term's magnitude
 struct __attribute__((aligned(16))) FpQuick { float A[3], ma, Bv[3], mb, Nn[3], md; };    // m*: FP_EPS x the sums' un-cancelled magnitudes for |rd_i| <= 1
 
-// WEIGHTS (dm2_forward_weights): a wave walks one entry at a time, so the alpha * T of its blends is summed across the wave
+// WEIGHTS (dm2_forward / dm2_forward_run with out_face_weights): a wave walks one entry at a time, so the alpha * T of its blends is summed across the wave
 // and added into an LDS sum per staged face (one ds_add_f32 per wave and entry hit); behind the next barrier one lane per
 // list entry flushes a non-zero sum to face_weights[b, face] with one global atomic.
 template <bool WEIGHTS>

@@ -65,7 +65,7 @@ struct __attribute__((aligned(8))) FqPair { float alpha, c0, c1, c2, depth; uint
 // (256 x 256 / 2 k faces: forward -14 %, with depth complexity 60: -17 %), costs 4 % with the 2.5-pixel triangles of the
 // 1080p / 1 M workload (a fifth of whose survivors are fully covered: one wave in eight): the launcher picks by the plan's
 // candidate pairs per list entry.
-// WEIGHTS (dm2_forward_weights): phase C adds each blend's alpha * T into an LDS sum per staged face (ds_add_f32); behind the
+// WEIGHTS (dm2_forward / dm2_forward_run with out_face_weights): phase C adds each blend's alpha * T into an LDS sum per staged face (ds_add_f32); behind the
 // next barrier -- the next chunk's first, or the one after the loop -- one lane per list entry flushes a non-zero sum to
 // face_weights[b, face] with one global atomic.  A face is on a tile's list at most once: at most one atomic per entry.
 template <bool CLASSES, bool WEIGHTS>

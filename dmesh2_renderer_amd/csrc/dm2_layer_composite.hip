@@ -18,7 +18,7 @@
 // with T_l from a front-to-back pass.  The layers [0, n_contrib) are processed in chunks of LC_REG from the back: per chunk
 // a front pass (T at the chunk's start from the layers in front of it, then the chunk's hits kept in registers) and a back
 // pass that carries R.  L <= LC_REG is one chunk; a larger L re-intersects the layers in front of each chunk (correct, not fast).
-// ALPHA (the template parameter; dm2_layers_composite_backward_alpha): the alpha image 1 - T_final is a fourth channel of
+// ALPHA (the template parameter; dm2_layers_composite_backward with dL_dout_alpha): the alpha image 1 - T_final is a fourth channel of
 // colour 1 over background 0, RA_l = alpha_l + (1 - alpha_l) RA_{l+1} (RA = 0 behind the last layer), and adds
 // T_l g_A (1 - RA_{l+1}) to dL/dalpha_l -- still no division.
 //
@@ -118,7 +118,7 @@ __device__ __forceinline__ void lc_composite_pixel(const dm2_layer_composite_des
     if (out_n_contrib) out_n_contrib[pix] = n_contrib;
 }
 
-// WEIGHTS (dm2_layers_composite_weights): every blend adds its alpha * T into a FaceTable of one accumulator per face, flushed
+// WEIGHTS (dm2_layers_composite with out_face_weights): every blend adds its alpha * T into a FaceTable of one accumulator per face, flushed
 // with one global atomic per (block, face).  Without WEIGHTS no table is declared.
 template <int VEC, bool WEIGHTS>
 __global__ void __launch_bounds__(TILE_PIX)

@@ -25,7 +25,7 @@
 // put it into the tile's list at all: its bbox is that of mirrored projections).  The stop relies on a held hit's t lying
 // in its face's depth range: rz_off_plane keeps the noise t of a ray in the face's plane out of the slots.
 //
-// Overlap mode (include/dm2_hip.h, dm2_rasterize_overlap_run_window): the same candidates; a candidate is listed iff (a) its
+// Overlap mode (include/dm2_hip.h, dm2_rasterize_run with overlap != 0): the same candidates; a candidate is listed iff (a) its
 // projected triangle verts_image[b, faces[f]] overlaps the pixel's square [X, X+1] x [Y, Y+1] (frame coordinates) -- the tables
 // of cov_tables_pts, tri_pix_overlap_area_only without error and with area != 0: k_coverage's clip, bit for bit, so coverage of
 // a listed slot is never 0 by the "misses the pixel" rule -- (b) ray_tri_intersection succeeds and rz_off_plane holds, and (c)

@@ -12,6 +12,10 @@
  *   generate_render_layers_cuda(render.h:101-119, render.cu:378-476)
  *       -> dm2_layers_plan() + dm2_layers_run()
  *
+ * One entry point per operation: what an operation can do in addition (a render
+ * window, one more output, one more upstream gradient) is a nullable pointer of
+ * its one symbol, and NULL there costs nothing -- the kernels without that work run.
+ *
  * The plan/run split replaces the reference's resize-callback lambdas
  * (render.cu:20-26, renderer.cu:174-183): the number of (tile,face) pairs is
  * data dependent, so `plan` bins the faces, returns the pair count (and the
@@ -36,7 +40,7 @@
 extern "C" {
 #endif
 
-#define DM2_ABI_VERSION 6
+#define DM2_ABI_VERSION 7
 #define DM2_TILE 16 /* config.h:4-5 BLOCK_X = BLOCK_Y = 16 */
 
 /* Inputs of Renderer's op, same meaning and order as render.h:13-45. */
@@ -93,14 +97,14 @@ typedef struct dm2_render_desc {
                                     that owns the host prep as well (dmesh2_renderer_amd/prep.py).  The flag must be set in the
                                     forward call of the same frame too: that is when the record notes the reorder. */
 
-#define DM2_FLAG_TABLES_FROM_IMAGE 32 /* dm2_forward*: the six aa_* tables are not read (their pointers may be NULL): the plan builds them
+#define DM2_FLAG_TABLES_FROM_IMAGE 32 /* dm2_forward_plan / dm2_forward: the six aa_* tables are not read (their pointers may be NULL): the plan builds them
                                     per (view, face) from verts_image[faces] in registers -- CCW reorder, edges, |e| < 1e-3 flags,
                                     reciprocals, inward normals and their offsets, exactly as pyrenderer.py:6-30 / dm2_prepare_faces
                                     compute them -- straight into its packed face records.  For a caller that owns the host prep
                                     (SURVEY.md 8(f) rank 1): 114 B per face less to write and 114 to read.  The backward's dL/d(aa
                                     corners) then only exists per vertex: combine with DM2_FLAG_AA_GRAD_TO_VERTS. */
 
-#define DM2_FLAG_NO_PAIR_POOL 64   /* dm2_forward*: leave blend masks only (DM2_FWD_MASKS), whatever room the binning scratch has behind
+#define DM2_FLAG_NO_PAIR_POOL 64   /* dm2_forward_run / dm2_forward: leave blend masks only (DM2_FWD_MASKS), whatever room the binning scratch has behind
                                     its fixed part: for a caller that finds the plan's pair_bound too large for its memory budget */
 
 /* Scratch kinds for dm2_scratch_bytes (state.h:18-61). */
@@ -158,12 +162,19 @@ int dm2_forward_plan(const dm2_render_desc* d, void* face_scratch, size_t face_b
  * composite also leaves the coverage ratio (forward.cu:375-378) of every blended pair in the appended part and
  * *forward_mode is DM2_FWD_POOL; otherwise DM2_FWD_MASKS (a caller that finds pair_bound too large for its memory
  * simply appends nothing), DM2_FWD_POINT at aa_temperature 0, or DM2_FWD_NONE under DM2_FLAG_NO_BACKWARD /
- * DM2_FLAG_LEGACY_KERNELS.  forward_mode may be NULL. */
+ * DM2_FLAG_LEGACY_KERNELS.  forward_mode may be NULL.
+ * out_face_weights (B,F) float32 or NULL (not wanted: the composite without that work runs); the caller zero-fills it (as the
+ * gradient outputs of dm2_backward).  The composite adds, for every blend of face f into a pixel of view b's patch,
+ * alpha * T -- the face's alpha there times the transmittance in front of it, the factor its colour gets in C += c alpha T
+ * -- to out_face_weights[b * F + f].  So sum_f out_face_weights[b, f] = sum over the patch of 1 - T_final.  Float atomics:
+ * the last bits may vary from run to run.  A caller that composites twice into the same weights (dm2_forward_run after a
+ * dm2_forward that returned 0) must zero them in between. */
 int dm2_forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound,
                     void* face_scratch, size_t face_bytes,
                     void* binning_scratch, size_t binning_bytes,
                     void* image_scratch, size_t image_bytes,
-                    float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream, int32_t* forward_mode);
+                    float* out_color, float* out_depth, int32_t* out_tri_cnt, float* out_face_weights, void* stream,
+                    int32_t* forward_mode);
 
 /* dm2_forward_plan + dm2_forward_run in ONE call for a caller that already holds a binning scratch of plausible size (a
  * training loop: last frame's size plus headroom): the run step is enqueued straight from the plan's read-back, without
@@ -171,28 +182,12 @@ int dm2_forward_run(const dm2_render_desc* d, int64_t num_rendered, int64_t max_
  * Returns 0 (rendered; *num_rendered / *max_tile_entries / *pair_bound / *forward_mode set), 2 when binning_bytes is
  * smaller than dm2_scratch_bytes(DM2_SCRATCH_BINNING, *num_rendered, B*tiles) + dm2_scratch_bytes(DM2_SCRATCH_PAIR_POOL,
  * *pair_bound, 0) -- the plan is done and nothing else: allocate and call dm2_forward_run -- or 1 on error.  A
- * larger-than-needed binning scratch is fine, also for dm2_backward (which must be given the same size). */
+ * larger-than-needed binning scratch is fine, also for dm2_backward (which must be given the same size).  out_tri_cnt,
+ * out_face_weights and forward_mode may be NULL, as for dm2_forward_run; pair_bound must not. */
 int dm2_forward(const dm2_render_desc* d, void* face_scratch, size_t face_bytes,
                 void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
-                float* out_color, float* out_depth, int32_t* out_tri_cnt, void* stream,
+                float* out_color, float* out_depth, int32_t* out_tri_cnt, float* out_face_weights, void* stream,
                 int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound, int32_t* forward_mode);
-
-/* dm2_forward / dm2_forward_run with one more output: out_face_weights (B,F) float32, which the caller zero-fills (as the
- * gradient outputs of dm2_backward).  The composite adds, for every blend of face f into a pixel of view b's patch,
- * alpha * T -- the face's alpha there times the transmittance in front of it, the factor its colour gets in C += c alpha T
- * -- to out_face_weights[b * F + f].  So sum_f out_face_weights[b, f] = sum over the patch of 1 - T_final.  Float atomics:
- * the last bits may vary from run to run.  A caller that composites twice into the same weights (dm2_forward_run_weights
- * after a dm2_forward_weights that returned 0) must zero them in between.  NULL: exactly dm2_forward / dm2_forward_run. */
-int dm2_forward_weights(const dm2_render_desc* d, void* face_scratch, size_t face_bytes,
-                        void* binning_scratch, size_t binning_bytes, void* image_scratch, size_t image_bytes,
-                        float* out_color, float* out_depth, int32_t* out_tri_cnt, float* out_face_weights, void* stream,
-                        int64_t* num_rendered, int64_t* max_tile_entries, int64_t* pair_bound, int32_t* forward_mode);
-int dm2_forward_run_weights(const dm2_render_desc* d, int64_t num_rendered, int64_t max_tile_entries, int64_t pair_bound,
-                            void* face_scratch, size_t face_bytes,
-                            void* binning_scratch, size_t binning_bytes,
-                            void* image_scratch, size_t image_bytes,
-                            float* out_color, float* out_depth, int32_t* out_tri_cnt, float* out_face_weights, void* stream,
-                            int32_t* forward_mode);
 
 /* Gradients (BACKWARD::renderCUDA backward.cu:17-532).  The six outputs must be
  * zero-filled by the caller (the reference's zeros_like, render.cu:313-318):
@@ -203,9 +198,12 @@ int dm2_forward_run_weights(const dm2_render_desc* d, int64_t num_rendered, int6
  * tie_scratch: needed with DM2_FWD_POOL (and, when the binning scratch has a pool part, with DM2_FWD_UNKNOWN or
  * DM2_FWD_POINT at aa_temperature > 0):
  * dm2_scratch_bytes(DM2_SCRATCH_TIE_QUEUE, pairs of the pool part, 0) bytes, scratch of this call only.  The binning
- * scratch is not const: the pool backward keeps its queue counters there (left as it found them). */
+ * scratch is not const: the pool backward keeps its queue counters there (left as it found them).
+ * dL_dout_alpha (B,H,W) or NULL (zero: the kernels without that term run): the upstream gradient of the alpha image of
+ * dm2_forward_alpha.  It reaches dL_dfaces_opacity and, through the AA coverage, dL_daa_face_verts (or verts_image); nothing
+ * else. */
 int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode,
-                 const float* dL_dout_color, const float* dL_dout_depth,
+                 const float* dL_dout_color, const float* dL_dout_depth, const float* dL_dout_alpha,
                  const void* face_scratch, size_t face_bytes,
                  void* binning_scratch, size_t binning_bytes,
                  const void* image_scratch, size_t image_bytes,
@@ -218,19 +216,6 @@ int dm2_backward(const dm2_render_desc* d, int64_t num_rendered, int32_t forward
  * (0 where no face blended).  image_scratch: the forward's, unmodified.  Call it behind dm2_forward / dm2_forward_run
  * on the same stream; it reads nothing else. */
 int dm2_forward_alpha(const dm2_render_desc* d, const void* image_scratch, size_t image_bytes, float* out_alpha, void* stream);
-
-/* dm2_backward with one more upstream gradient: dL_dout_alpha (B,H,W), of the alpha image of dm2_forward_alpha.  It
- * reaches dL_dfaces_opacity and, through the AA coverage, dL_daa_face_verts (or verts_image); nothing else.  NULL: exactly
- * dm2_backward. */
-int dm2_backward_alpha(const dm2_render_desc* d, int64_t num_rendered, int32_t forward_mode,
-                       const float* dL_dout_color, const float* dL_dout_depth, const float* dL_dout_alpha,
-                       const void* face_scratch, size_t face_bytes,
-                       void* binning_scratch, size_t binning_bytes,
-                       const void* image_scratch, size_t image_bytes,
-                       void* tie_scratch, size_t tie_bytes,
-                       float* dL_dverts, float* dL_dverts_color, float* dL_dfaces_opacity,
-                       float* dL_dverts_ndc, float* dL_dfaces_intense, float* dL_daa_face_verts,
-                       void* stream);
 
 /* LayeredRenderer (render.h:101-119). */
 typedef struct dm2_layers_desc {
@@ -250,45 +235,37 @@ typedef struct dm2_layers_desc {
     const float* ray_cam;         /* DM2_FLAG_ANALYTIC_RAYS: (B,32), see dm2_render_desc */
 } dm2_layers_desc;
 
-int dm2_layers_plan(const dm2_layers_desc* d, void* face_scratch, size_t face_bytes,
-                    void* stream, int64_t* num_rendered, int64_t* max_tile_entries);
-/* render_layers (B,H,W,L) must be pre-filled with -1 and render_layers_cnt (B,H,W)
- * with 0 by the caller (render.cu:437-438).  tet_scratch (DM2_SCRATCH_LAYER_TETS bytes for T tets; scratch of this call
- * only) receives one packed 256-B record per tet -- face vertices, outward normals, neighbours, existence flags -- so
- * that a step of the tet walk (forward.cu:853-996) is one contiguous fetch; NULL (or DM2_FLAG_LEGACY_KERNELS) selects the
- * reference's access pattern.  Same layers either way. */
-int dm2_layers_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries,
-                   void* face_scratch, size_t face_bytes,
-                   void* binning_scratch, size_t binning_bytes,
-                   void* image_scratch, size_t image_bytes,
-                   void* tet_scratch, size_t tet_bytes,
-                   int32_t* render_layers, int32_t* render_layers_cnt, void* stream);
-
-/* A render window on the deferred path (dm2_layers_plan / dm2_layers_run / dm2_rasterize_* / dm2_coverage* /
- * dm2_layers_composite*): the `*_window` entry points below take one next to the op's descriptor, whose W, H (and the H, W of
- * dm2_coverage) are then the WINDOW's size, as in dm2_render_desc, and every (B,H,W,...) array is the window's.  Pixel (x, y)
+/* A render window on the deferred path: dm2_layers_plan / dm2_layers_run / dm2_rasterize_* / dm2_coverage* /
+ * dm2_layers_composite* take one next to the op's descriptor, whose W, H (and the H, W of dm2_coverage) are then the WINDOW's
+ * size, as in dm2_render_desc, and every (B,H,W,...) array is the window's.  Pixel (x, y)
  * of view b's window is pixel (x + patch_min[b][0], y + patch_min[b][1]) of that view's full_W x full_H frame: its ray is that
  * frame pixel's (the ray tensors, when given, are the window's own (B,H,W,3) cut of the frame's; DM2_FLAG_ANALYTIC_RAYS
  * evaluates the absolute pixel with full_W, full_H), its pixel square for the coverage is the frame pixel's, and the 16 x 16
  * tile grid is anchored at the window's origin (patch_min), as dm2_forward_plan anchors it.  verts_image stays in the full
  * frame's pixel units.  The window must lie inside the frame (the caller checks: patch_min is device memory); the views may
- * have different origins.  patch_min NULL: every origin is (0, 0).  A NULL window pointer: the entry point without `_window`,
- * to the bit (that entry point forwards with NULL).  Gradients add into the same outputs as without a window. */
+ * have different origins.  patch_min NULL: every origin is (0, 0).  A NULL window pointer: the full frame of the descriptor's
+ * W x H at origin 0.  Gradients add into the same outputs with and without a window. */
 typedef struct dm2_window {
     const int32_t* patch_min;     /* (B,2) int32 (x, y) per view, DEVICE memory; NULL = zeros */
     int32_t full_W, full_H;       /* the frame the cameras' rays and verts_image belong to (Renderer.width/height) */
 } dm2_window;
 
-/* dm2_layers_plan / dm2_layers_run for a window: the faces are binned into the window's tiles (bbox of verts_image against
- * tiles anchored at patch_min), the first-hit pass and the tet walks run over the window's pixels with the window's rays. */
-int dm2_layers_plan_window(const dm2_layers_desc* d, const dm2_window* win, void* face_scratch, size_t face_bytes,
-                           void* stream, int64_t* num_rendered, int64_t* max_tile_entries);
-int dm2_layers_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                          void* face_scratch, size_t face_bytes,
-                          void* binning_scratch, size_t binning_bytes,
-                          void* image_scratch, size_t image_bytes,
-                          void* tet_scratch, size_t tet_bytes,
-                          int32_t* render_layers, int32_t* render_layers_cnt, void* stream);
+/* Bin the faces into the tiles of the frame, or of the window (win NULL: the full frame; otherwise the bbox of verts_image
+ * against tiles anchored at patch_min); num_rendered / max_tile_entries as for dm2_forward_plan. */
+int dm2_layers_plan(const dm2_layers_desc* d, const dm2_window* win, void* face_scratch, size_t face_bytes,
+                    void* stream, int64_t* num_rendered, int64_t* max_tile_entries);
+/* render_layers (B,H,W,L) must be pre-filled with -1 and render_layers_cnt (B,H,W)
+ * with 0 by the caller (render.cu:437-438).  tet_scratch (DM2_SCRATCH_LAYER_TETS bytes for T tets; scratch of this call
+ * only) receives one packed 256-B record per tet -- face vertices, outward normals, neighbours, existence flags -- so
+ * that a step of the tet walk (forward.cu:853-996) is one contiguous fetch; NULL (or DM2_FLAG_LEGACY_KERNELS) selects the
+ * reference's access pattern.  Same layers either way.  win (NULL: the full frame): the one the plan was given; the first-hit
+ * pass and the tet walks run over the window's pixels with the window's rays. */
+int dm2_layers_run(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                   void* face_scratch, size_t face_bytes,
+                   void* binning_scratch, size_t binning_bytes,
+                   void* image_scratch, size_t image_bytes,
+                   void* tet_scratch, size_t tet_bytes,
+                   int32_t* render_layers, int32_t* render_layers_cnt, void* stream);
 
 /* Renderer.rasterize: the first L faces each pixel's ray hits, on any triangle mesh (no tetrahedra), with barycentrics and
  * ray parameter.  Plan with dm2_layers_plan (T = 0; tets, face_tets, tet_faces unused and may be NULL) and size the face /
@@ -314,66 +291,52 @@ int dm2_layers_run_window(const dm2_layers_desc* d, const dm2_window* win, int64
  * camera plane may also be missing from the lists altogether, not only reordered: its vertices behind the camera project
  * mirrored, and the bbox of those projections, which the plan bins by, need not touch the tiles the face is seen in
  * (tests/tet_scenes.py "inside", 75 x 53, two cameras in the mesh: 1 181 of 6 901 clear float64 hits on such faces are in no
- * list).  dm2_rasterize_backward takes the caller's lists as they are; its only guard is rd . n == 0 exactly. */
-int dm2_rasterize_run(const dm2_layers_desc* d, int64_t num_rendered, int64_t max_tile_entries,
-                      void* face_scratch, size_t face_bytes,
-                      void* binning_scratch, size_t binning_bytes,
-                      void* image_scratch, size_t image_bytes,
-                      int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream);
-/* Gradients of dm2_rasterize_run's bary and t w.r.t. verts: dL_dverts (P,3), zero-filled by the caller.  For every slot of
- * render_layers with 0 <= f < F, upstream g = dL_dbary[slot] (3) and g_t = dL_dt[slot]:
- *   dL/dp_k += (g1 - g0) du/dp_k + (g2 - g0) dv/dp_k + g_t dt/dp_k,   p_k = verts[faces[f][k]],
- * at the pixel's ray.  Either upstream gradient may be NULL (zero; both NULL: nothing to do).  Nothing flows through the ray
- * or through which faces are listed.  Float atomics: the last bits may vary from run to run. */
-int dm2_rasterize_backward(const dm2_layers_desc* d, const int32_t* render_layers, const float* dL_dbary, const float* dL_dt,
-                           float* dL_dverts, void* stream);
-/* dm2_rasterize_run / dm2_rasterize_backward for a window (plan with dm2_layers_plan_window): every array is (B,H,W,...) of
- * the window.  The candidates of a window pixel are the faces whose image bbox touches the pixel's 16 x 16 WINDOW tile (the
- * grid anchored at patch_min) and that the depth cull keeps; the hit rule, the (t, f) order, the early exit and the -1 of
- * empty slots are dm2_rasterize_run's, word for word, at the frame pixel's ray.  A face that reaches a pixel through its bbox
- * alone can therefore be a candidate under one grid and not under another: a window and the crop of the full frame agree
- * wherever the tiles coincide (origin a multiple of 16) and may differ only in hits whose bbox misses one of the two tiles.
- * The backward intersects again with the window's rays. */
-int dm2_rasterize_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                             void* face_scratch, size_t face_bytes,
-                             void* binning_scratch, size_t binning_bytes,
-                             void* image_scratch, size_t image_bytes,
-                             int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, void* stream);
-int dm2_rasterize_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
-                                  const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream);
-/* Renderer.rasterize(overlap=True): the faces that overlap a pixel's SQUARE, not only those its centre ray hits -- the faces
- * dm2_forward blends at a temperature > 0 (forward.cu:325-381), so that the deferred path draws a silhouette as it does.  Plan,
- * scratch, candidates (tile list, existence filter) and window rules are dm2_rasterize_run_window's (win NULL: the full frame);
- * d->verts_image must be given.  A candidate f is listed at pixel (x, y) of view b iff
+ * list).  dm2_rasterize_backward takes the caller's lists as they are; its only guard is rd . n == 0 exactly.
+ * win (NULL: the full frame; plan with the same one): every array is (B,H,W,...) of the window.  The candidates of a window
+ * pixel are the faces whose image bbox touches the pixel's 16 x 16 WINDOW tile (the grid anchored at patch_min) and that the
+ * depth cull keeps; the hit rule, the (t, f) order, the early exit and the -1 of empty slots are as above, word for word, at
+ * the frame pixel's ray.  A face that reaches a pixel through its bbox alone can therefore be a candidate under one grid and
+ * not under another: a window and the crop of the full frame agree wherever the tiles coincide (origin a multiple of 16) and
+ * may differ only in hits whose bbox misses one of the two tiles.
+ * overlap == 0: the above; `inside` is not looked at and may be NULL.
+ * overlap != 0 (Renderer.rasterize(overlap=True)): the faces that overlap a pixel's SQUARE, not only those its centre ray hits
+ * -- the faces dm2_forward blends at a temperature > 0 (forward.cu:325-381), so that the deferred path draws a silhouette as it
+ * does.  Plan, scratch, candidates (tile list, existence filter) and window rules are the same; d->verts_image must be given,
+ * and inside must not be NULL unless L == 0.  A candidate f is listed at pixel (x, y) of view b iff
  *   (a) it overlaps the pixel: for the triangle verts_image[b, faces[f]], CCW-reordered, its tables built as under
  *       DM2_FLAG_TABLES_FROM_IMAGE, and the square [X, X+1] x [Y, Y+1], (X, Y) = (x, y) + patch_min[b], the clipper of dm2_coverage
  *       reports no error and area != 0 (so dm2_coverage of a listed slot is never 0 because the face misses the pixel);
- *   (b) ray_tri_intersection succeeds and the ray is off the face's plane (dm2_rasterize_run's rule);
+ *   (b) ray_tri_intersection succeeds and the ray is off the face's plane (the rule above);
  *   (c) the slot's t (below) is >= 0.
  * Per listed slot, with (u, v) the intersection's and (uc, vc, code) = clamp_bary_uv(u, v) (auxiliary.h:292-329):
  *   bary = (1 - uc - vc, uc, vc);   inside = (code == 0), one byte, 1 or 0;
- *   t = the intersection's t when code == 0 (exactly dm2_rasterize_run's value), otherwise the ray parameter of the clamped
+ *   t = the intersection's t when code == 0 (exactly the value of overlap == 0), otherwise the ray parameter of the clamped
  *       point's projection onto the ray, in fp32 in this order, without contraction (dot = (x x + y y) + z z):
  *         b0 = (1 - uc) - vc;  d_k = dot(p_k - ro, rd);  t = ((b0 * d0 + uc * d1) + vc * d2) / dot(rd, rd)
  *       (continuous across the triangle's edge, where the clamped point is the hit).
  * Order: ascending (t, f); the first L are listed; empty slots hold -1 in render_layers, bary and t and 0 in inside.  A slot
- * with inside == 1 is exactly a hit of dm2_rasterize_run: restricted to those slots, in order, the outputs are that call's
+ * with inside == 1 is exactly a hit of overlap == 0: restricted to those slots, in order, the outputs are that call's
  * wherever neither list is truncated.  The walk over a pixel's list is exhaustive (no depth-bound stop: an off-triangle
  * slot's t is not a point of the ray on the face).  inside (B,H,W,L) uint8; every slot of every output is written. */
-int dm2_rasterize_overlap_run_window(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
-                                     void* face_scratch, size_t face_bytes,
-                                     void* binning_scratch, size_t binning_bytes,
-                                     void* image_scratch, size_t image_bytes,
-                                     int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t, uint8_t* inside,
-                                     void* stream);
-/* Gradients of dm2_rasterize_overlap_run_window's bary and t w.r.t. verts, added into dL_dverts (P,3).  Per slot with
- * 0 <= f < F the intersection and its clamp code are recomputed in fp32 as the forward computed them; with the code held fixed
- * dL/d(uc, vc) = (g1 - g0, g2 - g0) (+ g_t dt/d(uc, vc) where code != 0) goes through clamp_bary_uv_grad(code) to (u, v) and
- * on to the vertices as in dm2_rasterize_backward; g_t goes through the intersection's t (code 0) or through the projection
- * formula, its dependence on bary included.  Nothing flows through the rays, the listing decision or inside.  Either upstream
- * gradient may be NULL.  Float atomics. */
-int dm2_rasterize_overlap_backward_window(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers,
-                                          const float* dL_dbary, const float* dL_dt, float* dL_dverts, void* stream);
+int dm2_rasterize_run(const dm2_layers_desc* d, const dm2_window* win, int64_t num_rendered, int64_t max_tile_entries,
+                      void* face_scratch, size_t face_bytes,
+                      void* binning_scratch, size_t binning_bytes,
+                      void* image_scratch, size_t image_bytes,
+                      int32_t* render_layers, int32_t* render_layers_cnt, float* bary, float* t,
+                      int32_t overlap, uint8_t* inside, void* stream);
+/* Gradients of dm2_rasterize_run's bary and t w.r.t. verts: dL_dverts (P,3), zero-filled by the caller.  For every slot of
+ * render_layers with 0 <= f < F, upstream g = dL_dbary[slot] (3) and g_t = dL_dt[slot]:
+ *   dL/dp_k += (g1 - g0) du/dp_k + (g2 - g0) dv/dp_k + g_t dt/dp_k,   p_k = verts[faces[f][k]],
+ * at the pixel's ray.  Either upstream gradient may be NULL (zero; both NULL: nothing to do).  Nothing flows through the ray
+ * or through which faces are listed.  Float atomics: the last bits may vary from run to run.  win (NULL: the full frame): the
+ * forward's; the backward intersects again with the window's rays.
+ * overlap != 0: render_layers are the lists of dm2_rasterize_run with overlap != 0.  Per slot with 0 <= f < F the intersection
+ * and its clamp code are recomputed in fp32 as the forward computed them; with the code held fixed dL/d(uc, vc) =
+ * (g1 - g0, g2 - g0) (+ g_t dt/d(uc, vc) where code != 0) goes through clamp_bary_uv_grad(code) to (u, v) and on to the
+ * vertices as above; g_t goes through the intersection's t (code 0) or through the projection formula, its dependence on bary
+ * included.  Nothing flows through the rays, the listing decision or inside. */
+int dm2_rasterize_backward(const dm2_layers_desc* d, const dm2_window* win, const int32_t* render_layers, const float* dL_dbary,
+                           const float* dL_dt, float* dL_dverts, int32_t overlap, void* stream);
 
 /* Renderer.interpolate: attribute images from face ids and barycentrics per slot (dm2_rasterize_run's, dm2_layers_run's or
  * hand-built).  render_layers (B,H,W,L) int32, bary (B,H,W,L,3) float32, attr (N,C) float32 shared by the views
@@ -596,34 +559,27 @@ int dm2_composite_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t C
  *   DM2_FLAG_TABLES_FROM_IMAGE; area = its overlap with the pixel [x, x+1] x [y, y+1] by the reference's clipper (aa.h:446-504);
  *   a clipper error or area == 0: cov = 0 (dm2_forward skips such a face); else
  *   cov = (float)(1.0 * (double)(1.0f - temperature) + (double)(area * temperature))   (forward.cu:375-378 for a hit).
- * Whether the pixel's ray hits the face is not looked at.  Every element of out_cov (B,H,W,L) is written: no pre-fill. */
-int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                 const int32_t* render_layers, const float* verts_image, const int32_t* faces, float* out_cov, void* stream);
+ * Whether the pixel's ray hits the face is not looked at.  Every element of out_cov (B,H,W,L) is written: no pre-fill.
+ * win (NULL: the full frame): render_layers and out_cov are (B,H,W,L) of the window, and the pixel of slot (b, y, x, l) is
+ * [x + pmx, x + pmx + 1] x [y + pmy, y + pmy + 1] with (pmx, pmy) = patch_min[b]; verts_image stays in frame units.  Per-pixel:
+ * the result is the crop of the full-frame call on layers embedded in a frame of -1.  Only win->patch_min is read (full_W,
+ * full_H are not needed).
+ * inside (NULL: every slot as above): the inside bytes (B,H,W,L) of dm2_rasterize_run with overlap != 0.  A non-empty slot with
+ * inside == 0 mixes as a face that only grazes the pixel (forward.cu:379-381):
+ * cov = (float)(0.0 * (double)(1.0f - temperature) + (double)(area * temperature)) = area * temperature, and cov = 0 at
+ * temperature 0; a slot with inside != 0 is as above.  The gradient is dm2_coverage_backward's either way (dL_dcov * temperature
+ * * d(area)/d(corner)): the mask is not needed there. */
+int dm2_coverage(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature, const dm2_window* win,
+                 const int32_t* render_layers, const uint8_t* inside, const float* verts_image, const int32_t* faces,
+                 float* out_cov, void* stream);
 /* Gradient of dm2_coverage for upstream dL_dcov (B,H,W,L): every slot with a non-zero cov adds
  * dL_dcov[s] * temperature * d(area)/d(corner k) to dL_dverts_image[b, v] (B,P,2), v the face's vertex that the reorder put at
  * corner k; the Jacobian is the reference clipper's (zero at full cover).  dL_dverts_image is zero-filled by the caller; float
- * atomics: its last bits may vary from run to run.  temperature == 0, dL_dcov NULL or dL_dverts_image NULL: nothing runs. */
+ * atomics: its last bits may vary from run to run.  temperature == 0, dL_dcov NULL or dL_dverts_image NULL: nothing runs.
+ * win (NULL: the full frame): as for dm2_coverage; render_layers and dL_dcov are the window's. */
 int dm2_coverage_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                          const int32_t* render_layers, const float* verts_image, const int32_t* faces, const float* dL_dcov,
-                          float* dL_dverts_image, void* stream);
-/* dm2_coverage / dm2_coverage_backward for a window: render_layers, out_cov and dL_dcov are (B,H,W,L) of the window, and the
- * pixel of slot (b, y, x, l) is [x + pmx, x + pmx + 1] x [y + pmy, y + pmy + 1] with (pmx, pmy) = patch_min[b]; verts_image
- * stays in frame units.  Per-pixel: the result is the crop of the full-frame call on layers embedded in a frame of -1.  Only
- * win->patch_min is read (full_W, full_H are not needed). */
-int dm2_coverage_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                        const dm2_window* win, const int32_t* render_layers, const float* verts_image, const int32_t* faces,
-                        float* out_cov, void* stream);
-int dm2_coverage_backward_window(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                                 const dm2_window* win, const int32_t* render_layers, const float* verts_image,
-                                 const int32_t* faces, const float* dL_dcov, float* dL_dverts_image, void* stream);
-/* dm2_coverage_window with the inside bytes (B,H,W,L) of dm2_rasterize_overlap_run_window (win NULL: the full frame; inside
- * NULL: dm2_coverage_window, to the bit).  A non-empty slot with inside == 0 mixes as a face that only grazes the pixel
- * (forward.cu:379-381): cov = (float)(0.0 * (double)(1.0f - temperature) + (double)(area * temperature)) = area * temperature,
- * and cov = 0 at temperature 0; a slot with inside != 0 is dm2_coverage's.  The gradient is dm2_coverage_backward_window's
- * either way (dL_dcov * temperature * d(area)/d(corner)): the mask is not needed there. */
-int dm2_coverage_window_inside(int32_t B, int32_t H, int32_t W, int32_t L, int32_t P, int32_t F, float temperature,
-                               const dm2_window* win, const int32_t* render_layers, const uint8_t* inside,
-                               const float* verts_image, const int32_t* faces, float* out_cov, void* stream);
+                          const dm2_window* win, const int32_t* render_layers, const float* verts_image,
+                          const int32_t* faces, const float* dL_dcov, float* dL_dverts_image, void* stream);
 
 /* Renderer.vertex_normals: area-weighted smooth vertex normals of a triangle mesh, differentiable w.r.t. the vertices, without
  * float atomics.  verts (P,3) float32, faces (F,3) int32, 3 F < 2^31.  A face is valid when its three ids lie in [0, P).
@@ -700,7 +656,13 @@ int dm2_shading_vectors_backward_window(int32_t B, int32_t H, int32_t W, int32_t
  * out_color = C + T background (B,H,W,3), out_depth = D + T (B,H,W; NDC depth, background 1), out_final_T = T (B,H,W),
  * out_n_contrib (B,H,W) int32 = 1 + the index of the last layer that blended (0: none).  out_final_T may be NULL;
  * out_n_contrib is what the backward takes.  Bit-exact: the same fp32 operations, in the same order, as the
- * point-sampled Renderer forward. */
+ * point-sampled Renderer forward.
+ * win (NULL: the full frame): d->W, d->H and every (B,H,W,...) array are the window's; a window pixel's ray is its frame
+ * pixel's (the window's cut of the ray tensors, or DM2_FLAG_ANALYTIC_RAYS at the absolute pixel with full_W, full_H -- the only
+ * place the origin is used).  Per-pixel: the crop of the full-frame call on layers embedded in a frame of -1.
+ * out_face_weights (B,F) float32 or NULL (not wanted: the kernel without that work runs), zero-filled by the caller; every
+ * blend adds alpha * T (faces_opacity[f] times the transmittance in front of the layer) to out_face_weights[b * F + f] -- a
+ * face listed twice in one pixel's layers counts twice.  Float atomics. */
 typedef struct dm2_layer_composite_desc {
     int32_t B, P, F;
     int32_t W, H, L;              /* full frame (with a dm2_window: the window's) width/height, layers per pixel */
@@ -718,36 +680,18 @@ typedef struct dm2_layer_composite_desc {
     const float* ray_cam;         /* DM2_FLAG_ANALYTIC_RAYS: (B,32), see dm2_render_desc */
 } dm2_layer_composite_desc;
 
-int dm2_layers_composite(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
-                         int32_t* out_n_contrib, void* stream);
-/* dm2_layers_composite with one more output: out_face_weights (B,F) float32, zero-filled by the caller; every blend adds
- * alpha * T (faces_opacity[f] times the transmittance in front of the layer) to out_face_weights[b * F + f] -- a face listed
- * twice in one pixel's layers counts twice.  Float atomics.  NULL: exactly dm2_layers_composite. */
-int dm2_layers_composite_weights(const dm2_layer_composite_desc* d, float* out_color, float* out_depth, float* out_final_T,
-                                 int32_t* out_n_contrib, float* out_face_weights, void* stream);
+int dm2_layers_composite(const dm2_layer_composite_desc* d, const dm2_window* win, float* out_color, float* out_depth,
+                         float* out_final_T, int32_t* out_n_contrib, float* out_face_weights, void* stream);
 /* Gradients of the composite w.r.t. verts_color (P,3), faces_opacity (F), verts_ndc (B,P,3; only z written) and
  * faces_intense (B,F); the four outputs must be zero-filled by the caller.  No gradient reaches verts through the
  * barycentrics (the layers are piecewise constant in the points) and none reaches background.  n_contrib: what the
- * forward of the same inputs wrote.  Division-free in alpha: opacities of exactly 1.0 are fine. */
-int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const float* dL_dout_color, const float* dL_dout_depth,
+ * forward of the same inputs wrote.  Division-free in alpha: opacities of exactly 1.0 are fine.  win (NULL: the full frame):
+ * the forward's.  dL_dout_alpha (B,H,W) or NULL (zero: the kernel without that term runs): the upstream gradient of
+ * alpha = 1 - out_final_T; it reaches dL_dfaces_opacity only. */
+int dm2_layers_composite_backward(const dm2_layer_composite_desc* d, const dm2_window* win, const float* dL_dout_color,
+                                  const float* dL_dout_depth, const float* dL_dout_alpha,
                                   const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
                                   float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
-/* dm2_layers_composite_backward with one more upstream gradient: dL_dout_alpha (B,H,W), of alpha = 1 - out_final_T.  It
- * reaches dL_dfaces_opacity only.  NULL: exactly dm2_layers_composite_backward. */
-int dm2_layers_composite_backward_alpha(const dm2_layer_composite_desc* d, const float* dL_dout_color,
-                                        const float* dL_dout_depth, const float* dL_dout_alpha,
-                                        const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
-                                        float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
-/* dm2_layers_composite_weights / dm2_layers_composite_backward_alpha for a window: d->W, d->H and every (B,H,W,...) array are
- * the window's; a window pixel's ray is its frame pixel's (the window's cut of the ray tensors, or DM2_FLAG_ANALYTIC_RAYS at
- * the absolute pixel with full_W, full_H -- the only place the origin is used).  out_face_weights and dL_dout_alpha may be
- * NULL as there.  Per-pixel: the crop of the full-frame call on layers embedded in a frame of -1. */
-int dm2_layers_composite_window(const dm2_layer_composite_desc* d, const dm2_window* win, float* out_color, float* out_depth,
-                                float* out_final_T, int32_t* out_n_contrib, float* out_face_weights, void* stream);
-int dm2_layers_composite_backward_window(const dm2_layer_composite_desc* d, const dm2_window* win, const float* dL_dout_color,
-                                         const float* dL_dout_depth, const float* dL_dout_alpha,
-                                         const int32_t* n_contrib, float* dL_dverts_color, float* dL_dfaces_opacity,
-                                         float* dL_dverts_ndc, float* dL_dfaces_intense, void* stream);
 
 /* Host prep of Renderer.forward / LayeredRenderer.generate, fused.
  * Replaces the ~20 torch kernels of the reference's Python host layer:
@@ -799,7 +743,7 @@ int dm2_prepare_faces_backward_camera(const dm2_prep_desc* d, const float* g_ver
 /* Device side of the sparse leaf-gradient exchange of a frame sharded by tile rows over N ranks (the
  * collectives themselves belong to the caller: dmesh2_renderer_amd/sharding.py drives torch.distributed / RCCL).  Rows are
  * owned by contiguous id ranges: face f by rank f / ceil(F/N), vertex v by rank v / ceil(P/N).
- *   dm2_exchange_mark    after dm2_forward*: flags (P + F bytes of caller scratch: F face flags, then P vertex flags) mark the
+ *   dm2_exchange_mark    after dm2_forward / dm2_forward_run: flags (P + F bytes of caller scratch: F face flags, then P vertex flags) mark the
  *                        faces this rank's tile lists hold (any view) and their vertices; counts (2 N uint32, device):
  *                        [2 o] faces / [2 o + 1] vertices flagged in owner o's range = the rows this rank will send to o.
  *   dm2_exchange_pack    after the backward: the send buffer, per owner o [counts[2 o] rows of (2 + B) floats: id bits, dopacity,

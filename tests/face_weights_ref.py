@@ -1,4 +1,4 @@
-"""Per-face blend weights of the layer compositor, restated in float64 (the contract of dm2_layers_composite_weights).
+"""Per-face blend weights of the layer compositor, restated in float64 (the contract of dm2_layers_composite's out_face_weights).
 
 face_weights[b, f] = sum over the pixels of view b and the layers that blend (the float32 decisions of
 layer_composite_ref.forward32) of faces_opacity[f] * T, with T the product of (1 - alpha) of the layers that blended in front

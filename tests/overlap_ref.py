@@ -1,5 +1,5 @@
 """Restatement of Renderer.rasterize(overlap=True) and Renderer.coverage(inside=...) for the tests (include/dm2_hip.h:
-dm2_rasterize_overlap_run_window, dm2_coverage_window_inside), in numpy on top of the restatements the tests already have.
+dm2_rasterize_run with overlap != 0, dm2_coverage's inside), in numpy on top of the restatements the tests already have.
 
 Per pixel (x, y) of view b (of a window at patch_min, or the full frame) the candidates are ``window_ref.candidates``: the
 pixel's tile list with the faces of existence 0 taken out.  A candidate f is listed iff

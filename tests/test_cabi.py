@@ -21,6 +21,20 @@ def test_header_symbols_are_bound_and_exported():
     for n in names:
         assert getattr(lib, n) is not None
     assert lib.dm2_abi_version() == _C.ABI_VERSION == int(re.search(r"#define DM2_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "dm2_hip.h")).read()).group(1))
+    assert _C.ABI_VERSION == 7
+
+
+def test_one_symbol_per_operation():
+    """ABI v7: an optional window, output or upstream gradient is a nullable argument of the operation's one symbol, not a
+    symbol of its own.  v6 exported 62 symbols; the 16 that named another symbol plus one pointer are gone: 46."""
+    assert len(_C.EXPORTS) == 46
+    # (these exist in one form only: their `_window` is part of the operation's name, no second symbol stands beside them)
+    one_form = {"dm2_bary_derivatives_window", "dm2_shading_vectors_window", "dm2_shading_vectors_backward_window"}
+    assert one_form <= set(_C.EXPORTS)
+    for n in set(_C.EXPORTS) - one_form:
+        assert not re.search(r"_(weights|inside)$", n), n
+        assert not re.search(r"backward_(alpha|window)$", n), n
+        assert not re.match(r"^dm2_(layers_plan|layers_run|rasterize\w*|coverage\w*|layers_composite\w*)_window$", n), n
 
 
 def header_struct(name):
@@ -44,10 +58,11 @@ def header_struct(name):
 
 
 def test_structs_match_header_layout():
-    """Field ORDER, sizes and offsets of the three descriptor structs: the ctypes mirrors in _C.py against the declarations
+    """Field ORDER, sizes and offsets of the three descriptor structs and of dm2_window: the ctypes mirrors in _C.py against the declarations
     of include/dm2_hip.h (natural alignment, as the C compiler lays them out)."""
     import ctypes
-    for name, cls in (("dm2_render_desc", _C.RenderDesc), ("dm2_layers_desc", _C.LayersDesc), ("dm2_prep_desc", _C.PrepDesc)):
+    for name, cls in (("dm2_render_desc", _C.RenderDesc), ("dm2_layers_desc", _C.LayersDesc), ("dm2_prep_desc", _C.PrepDesc),
+                      ("dm2_window", _C.Window)):
         decl = header_struct(name)
         assert [f[0] for f in decl] == [f[0] for f in cls._fields_], name
         off = 0

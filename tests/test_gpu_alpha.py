@@ -1,5 +1,5 @@
 """The alpha (coverage) image: Renderer.forward(..., return_alpha=True), LayeredRenderer.render(..., return_alpha=True), and
-the C entry points under them (dm2_forward_alpha, dm2_backward_alpha, dm2_layers_composite_backward_alpha).
+the C entry points under them (dm2_forward_alpha, dm2_backward's and dm2_layers_composite_backward's dL_dout_alpha).
 
 The reference for all of it is an ordinary colour render.  With verts_color[:, 2] = 0 and background[2] = -1 the blue channel
 is 0 + T * (-1), so 1 + color[..., 2] is 1 - T bit for bit, and the gradients of <g_A, alpha> are the colour op's gradients

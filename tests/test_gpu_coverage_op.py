@@ -54,7 +54,7 @@ def _raw_forward(c, temperature, put=_cu):
     B, H, W, L = rl.shape
     out = torch.full((B, H, W, L), float("nan"), device="cuda")
     p = _C._ptr
-    rc = lib.dm2_coverage(B, H, W, L, vi.shape[1], fc.shape[0], temperature, p(rl), p(vi), p(fc), p(out),
+    rc = lib.dm2_coverage(B, H, W, L, vi.shape[1], fc.shape[0], temperature, None, p(rl), None, p(vi), p(fc), p(out),
                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert rc == 0, lib.dm2_last_error()
     torch.cuda.synchronize()
@@ -127,8 +127,8 @@ def test_no_launch_where_nothing_flows():
         p = _C._ptr
         B, H, W, L = c["render_layers"].shape
         n = (B, H, W, L, c["verts_image"].shape[1], c["faces"].shape[0])
-        assert real(*n, 0.0, p(rl), p(vi), p(fc), p(_cu(c["g"])), p(d), None) == 0
-        assert real(*n, 1.0, p(rl), p(vi), p(fc), None, p(d), None) == 0
+        assert real(*n, 0.0, None, p(rl), p(vi), p(fc), p(_cu(c["g"])), p(d), None) == 0
+        assert real(*n, 1.0, None, p(rl), p(vi), p(fc), None, p(d), None) == 0
         torch.cuda.synchronize()
         assert torch.isnan(d).all()
 
@@ -340,15 +340,15 @@ def test_argument_checks():
     # the C ABI refuses what the shim would never send
     lib = _C.load_library()
     p = _C._ptr
-    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, p(rl), p(vi), p(fc), p(cov), None) == 0
-    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.5, p(rl), p(vi), p(fc), p(cov), None) == 1
-    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, float("nan"), p(rl), p(vi), p(fc), p(cov), None) == 1
-    assert lib.dm2_coverage(2, 4, 5, 3, -1, 6, 1.0, p(rl), p(vi), p(fc), p(cov), None) == 1
-    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, None, p(vi), p(fc), p(cov), None) == 1
-    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, p(rl), p(vi), None, p(cov), None) == 1
-    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, p(rl), p(vi), p(fc), None, None) == 1
-    assert lib.dm2_coverage_backward(2, 4, 5, 3, 7, 6, -1.0, p(rl), p(vi), p(fc), p(cov), p(vi), None) == 1
-    assert lib.dm2_coverage_backward(2, 4, 5, 3, 7, 6, 1.0, None, p(vi), p(fc), p(cov), p(vi), None) == 1
+    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, None, p(rl), None, p(vi), p(fc), p(cov), None) == 0
+    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.5, None, p(rl), None, p(vi), p(fc), p(cov), None) == 1
+    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, float("nan"), None, p(rl), None, p(vi), p(fc), p(cov), None) == 1
+    assert lib.dm2_coverage(2, 4, 5, 3, -1, 6, 1.0, None, p(rl), None, p(vi), p(fc), p(cov), None) == 1
+    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, None, None, None, p(vi), p(fc), p(cov), None) == 1
+    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, None, p(rl), None, p(vi), None, p(cov), None) == 1
+    assert lib.dm2_coverage(2, 4, 5, 3, 7, 6, 1.0, None, p(rl), None, p(vi), p(fc), None, None) == 1
+    assert lib.dm2_coverage_backward(2, 4, 5, 3, 7, 6, -1.0, None, p(rl), p(vi), p(fc), p(cov), p(vi), None) == 1
+    assert lib.dm2_coverage_backward(2, 4, 5, 3, 7, 6, 1.0, None, None, p(vi), p(fc), p(cov), p(vi), None) == 1
     torch.cuda.synchronize()
 
 

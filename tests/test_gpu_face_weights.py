@@ -1,6 +1,6 @@
 """Per-face blend weights: Renderer.forward(..., return_face_weights=True), LayeredRenderer.render(..., return_face_weights=True),
-the ``_C.face_weights_output`` side channel and the C entry points under them (dm2_forward_weights, dm2_forward_run_weights,
-dm2_layers_composite_weights).
+the ``_C.face_weights_output`` side channel and the C entry points under them (out_face_weights of dm2_forward, dm2_forward_run and
+dm2_layers_composite).
 
 face_weights[b, f] is the sum of alpha * T over the blends of face f in view b.  The reference is the colour op's own gradient
 through an identity: with every vertex colour (1, 1, 1), dL/dcolor = (1, 0, 0) and dL/ddepth = 0, dL/dfaces_intense[b, f] =
@@ -147,7 +147,7 @@ def test_weights_tables_from_image():
 
 def test_weights_over_budget_rerun_not_doubled():
     """The pair pool turns out over budget after the first composite: render_forward_cuda renders again with masks only
-    (dm2_forward rendered with a pool, dm2_forward_run_weights renders again); the weights are those of ONE composite."""
+    (dm2_forward rendered with a pool, dm2_forward_run renders again); the weights are those of ONE composite."""
     args = _soup(96)
     want, _ = oracle_weights(to_numpy_args(args))
     dargs = _dev(args)
@@ -157,7 +157,7 @@ def test_weights_over_budget_rerun_not_doubled():
     modes = []
 
     def fwd(*a):
-        rc = lib.dm2_forward_weights(*a)
+        rc = lib.dm2_forward(*a)
         modes.append((rc, a[-1]._obj.value))
         return rc
 
@@ -165,12 +165,12 @@ def test_weights_over_budget_rerun_not_doubled():
 
     def run(*a):
         runs.append(1)
-        return lib.dm2_forward_run_weights(*a)
+        return lib.dm2_forward_run(*a)
 
     budget = _C._pool_budget
     _C._pool_budget = lambda N, R: 1
     try:
-        with _spy_library(dm2_forward_weights=fwd, dm2_forward_run_weights=run), _C.face_weights_output(True):
+        with _spy_library(dm2_forward=fwd, dm2_forward_run=run), _C.face_weights_output(True):
             out = _C.render_forward_cuda(*dargs)
     finally:
         _C._pool_budget = budget
@@ -295,41 +295,53 @@ def test_early_outs_are_zeros():
     assert len(out) == 12 and out[11].shape == (1, 50) and out[11].dtype == torch.float32 and not out[11].any()
 
 
+def _null(p):
+    """Is this ctypes argument a NULL pointer (None, or a c_void_p of 0)?"""
+    return p is None or getattr(p, "value", p) in (None, 0)
+
+
 def test_null_weights_pointer_is_the_old_call():
-    """dm2_forward_weights / dm2_forward_run_weights / dm2_layers_composite_weights with NULL weights: the results of
-    dm2_forward / dm2_forward_run / dm2_layers_composite, bit for bit."""
+    """A caller that asks for nothing extra gets the plain path: with no side channel set, every optional slot of the C calls
+    (weights, alpha gradient, window) is NULL, on the one-call and on the plan-then-run route; dm2_layers_composite with NULL
+    window and NULL weights is composite_layers_cuda, bit for bit; and asking for the weights does not perturb the image."""
     args = _dev(_soup(100))
-    lib = _C.load_library()
-    calls = {"dm2_forward": 0, "dm2_forward_run": 0}
-
-    def fwd(*a):
-        calls["dm2_forward"] += 1
-        return lib.dm2_forward_weights(*a[:10], None, *a[10:])
-
-    def run(*a):
-        calls["dm2_forward_run"] += 1
-        return lib.dm2_forward_run_weights(*a[:13], None, *a[13:])
-
-    plain = _C.render_forward_cuda(*args)
-    with _spy_library(dm2_forward=fwd, dm2_forward_run=run):
-        _C._bin_hint.clear()                                     # (no binning buffer at hand: the plan-then-run route too)
-        nulled = _C.render_forward_cuda(*args)
-    assert calls["dm2_forward"] == 1 and calls["dm2_forward_run"] == 1
-    for i in (1, 2, 5):
-        assert torch.equal(plain[i], nulled[i]), i
-    # the layered entry point
     sc = lref.ortho_scene(B=2, H=21, W=19, L=4, F=7, seed=3)
     la = _layer_args(sc)
+    lib = _C.load_library()
+    calls = {"dm2_forward": 0, "dm2_forward_run": 0, "dm2_backward": 0, "dm2_layers_composite": 0, "dm2_layers_composite_backward": 0}
+    optional = {"dm2_forward": (10,), "dm2_forward_run": (13,), "dm2_backward": (5,), "dm2_layers_composite": (1, 6),
+                "dm2_layers_composite_backward": (1, 4)}
+
+    def spy(name):
+        def f(*a):
+            calls[name] += 1
+            assert all(_null(a[i]) for i in optional[name]), (name, [a[i] for i in optional[name]])
+            return getattr(lib, name)(*a)
+        return f
+
+    plain = _C.render_forward_cuda(*args)
+    with _spy_library(**{name: spy(name) for name in calls}):
+        _C._bin_hint.clear()                                     # (no binning buffer at hand: the plan-then-run route too)
+        nulled = _C.render_forward_cuda(*args)
+        gc, gd = torch.ones_like(nulled[1]), torch.ones_like(nulled[2])
+        _C.render_backward_cuda(nulled[0], *args, gc, gd, nulled[7], nulled[8], nulled[9], *nulled[3:7])
+        shim = _C.composite_layers_cuda(*la)
+        _C.composite_layers_backward_cuda(*la, shim[3], torch.ones_like(shim[0]), torch.ones_like(shim[1]))
+    assert calls == {"dm2_forward": 1, "dm2_forward_run": 1, "dm2_backward": 1, "dm2_layers_composite": 1,
+                     "dm2_layers_composite_backward": 1}, calls
+    for i in (1, 2, 5):
+        assert torch.equal(plain[i], nulled[i]), i
+    with _C.face_weights_output(True):
+        weighted = _C.render_forward_cuda(*args)
+    for i in (1, 2, 5):                                          # (the WEIGHTS kernels only add work beside the blend)
+        assert torch.equal(plain[i], weighted[i]), i
+    # the layered entry point, called directly
     keep = []
     d, dev = _C._composite_desc(*la, keep)
-    o1 = [torch.empty((2, 21, 19, 3), device="cuda"), torch.empty((2, 21, 19), device="cuda"),
-          torch.empty((2, 21, 19), device="cuda"), torch.empty((2, 21, 19), dtype=torch.int32, device="cuda")]
-    o2 = [torch.empty_like(x) for x in o1]
-    st = _C._stream(dev)
-    assert lib.dm2_layers_composite(ctypes.byref(d), *[_C._ptr(x) for x in o1], st) == 0
-    assert lib.dm2_layers_composite_weights(ctypes.byref(d), *[_C._ptr(x) for x in o2], None, st) == 0
+    direct = [torch.empty_like(x) for x in shim]
+    assert lib.dm2_layers_composite(ctypes.byref(d), None, *[_C._ptr(x) for x in direct], None, _C._stream(dev)) == 0
     torch.cuda.synchronize()
-    for x, y in zip(o1, o2):
+    for x, y in zip(shim, direct):
         assert torch.equal(x, y)
 
 

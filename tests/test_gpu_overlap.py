@@ -357,3 +357,23 @@ def test_arguments():
     with pytest.raises(RuntimeError, match="no CPU path"):
         rc.rasterize([0, 1], t["verts"].cpu(), t["faces"].cpu(), 4, overlap=True)
     assert "RasterizeOverlapFunction" in dm2.__all__
+
+
+def test_c_abi_refuses_overlap_without_inside():
+    """The C ABI refuses what the shim would never send: dm2_rasterize_run in overlap mode with L = 1 and no ``inside``, one
+    view of 8 x 8 pixels and one face -> 1 with a message that names ``inside``, before anything is launched (the scratch
+    pointers are NULL: a launch would not get that far either)."""
+    import ctypes
+    dev = "cuda"
+    verts = torch.tensor([[-0.5, -0.5, 0.0], [0.5, -0.5, 0.0], [0.0, 0.5, 0.0]], device=dev)
+    faces = torch.tensor([[0, 1, 2]], dtype=torch.int32, device=dev)
+    ndc, img = torch.zeros((1, 3, 3), device=dev), torch.zeros((1, 3, 2), device=dev)
+    ro, rd = torch.zeros((1, 8, 8, 3), device=dev), torch.ones((1, 8, 8, 3), device=dev)
+    keep = []
+    d, _ = _C._rasterize_desc(8, 8, 1, verts, faces, ro, rd, 1, keep, verts_ndc=ndc, verts_image=img)
+    layers = torch.empty((1, 8, 8, 1), dtype=torch.int32, device=dev)
+    cnt = torch.empty((1, 8, 8), dtype=torch.int32, device=dev)
+    bary, t = torch.empty((1, 8, 8, 1, 3), device=dev), torch.empty((1, 8, 8, 1), device=dev)
+    lib, p = _C.load_library(), _C._ptr
+    rc = lib.dm2_rasterize_run(ctypes.byref(d), None, 0, 0, None, 0, None, 0, None, 0, p(layers), p(cnt), p(bary), p(t), 1, None, None)
+    assert rc == 1 and b"inside" in lib.dm2_last_error()

@@ -64,9 +64,9 @@ def _upstream(shape_bhw, seed):
 # ---- the spy on the C entry points ------------------------------------------------------------------------------------------
 @contextlib.contextmanager
 def library_calls():
-    """-> a list that receives one dict per call of dm2_forward[_weights] / dm2_forward_run[_weights] (fn, rc, the bytes of
-    binning scratch handed over, the forward mode reported; for the plan-and-run call also R and the pair bound) and of
-    dm2_backward[_alpha] (fn, R, the forward mode told)."""
+    """-> a list that receives one dict per call of dm2_forward / dm2_forward_run (fn, rc, the bytes of binning scratch
+    handed over, the forward mode reported; for the plan-and-run call also R and the pair bound) and of dm2_backward (fn, R,
+    the forward mode told)."""
     lib = _C.load_library()
     log = []
 
@@ -75,7 +75,7 @@ def library_calls():
 
         def f(*a):
             rc = real(*a)
-            e = dict(fn=name.replace("_weights", ""), rc=rc, bin_bytes=int(a[bin_at]), mode=int(a[-1]._obj.value))
+            e = dict(fn=name, rc=rc, bin_bytes=int(a[bin_at]), mode=int(a[-1]._obj.value))
             if bin_at == 4:
                 e.update(R=int(a[-4]._obj.value), pairs=int(a[-2]._obj.value))
             log.append(e)
@@ -90,9 +90,7 @@ def library_calls():
             return real(*a)
         return f
 
-    with spy_library(dm2_forward=fwd("dm2_forward", 4), dm2_forward_weights=fwd("dm2_forward_weights", 4),
-                     dm2_forward_run=fwd("dm2_forward_run", 7), dm2_forward_run_weights=fwd("dm2_forward_run_weights", 7),
-                     dm2_backward=bwd("dm2_backward"), dm2_backward_alpha=bwd("dm2_backward_alpha")):
+    with spy_library(dm2_forward=fwd("dm2_forward", 4), dm2_forward_run=fwd("dm2_forward_run", 7), dm2_backward=bwd("dm2_backward")):
         yield log
 
 

@@ -307,7 +307,7 @@ def _composite_op(inp, pm, W, H, weights=False):
 @pytest.mark.parametrize("name", wref.SCENES)
 @pytest.mark.parametrize("win", WINS)
 def test_render_window_bit_equal_to_restatement(name, win):
-    """dm2_layers_composite_window: colour, raw depth, final T and n_contrib of the window are the crop of forward32 on the
+    """dm2_layers_composite under a window: colour, raw depth, final T and n_contrib of the window are the crop of forward32 on the
     layers embedded in a frame of -1, bit for bit; so with face weights, which sum to the window's blends."""
     from face_weights_ref import layered_face_weights64
     from test_gpu_face_weights import check_weights
@@ -382,7 +382,7 @@ def test_render_module_window():
 
 @pytest.mark.parametrize("name", wref.SCENES)
 def test_render_window_backward_op(name):
-    """dm2_layers_composite_backward_window on window (c): the four gradients within GRAD_TOL of float64 on the embedded layers
+    """dm2_layers_composite_backward on window (c): the four gradients within GRAD_TOL of float64 on the embedded layers
     and of the full-frame op fed upstream gradients embedded in zeros."""
     inp, pm, W, H = _render_inputs(name, "c")
     fwd, _ = wref.composite32(inp, pm, W, H)
