@@ -36,7 +36,7 @@ from __future__ import annotations
 
 import contextlib
 import os
-from typing import List, Sequence
+from typing import List, NamedTuple, Sequence
 
 import torch
 
@@ -72,6 +72,61 @@ class _Entered:
         return self.stack.__exit__(*exc)
 
 
+def _hold_channels(ctx, *channels, read=()):
+    """In a Function's forward: keeps the thread's value of each of ``_C``'s side ``channels`` on ``ctx`` for
+    ``_held_channels`` in the backward; -> the values of the channels in ``read``, which the forward looks at and the backward
+    does not re-enter."""
+    ctx.channels = {ch: getattr(_C._tls, ch._slot, ch._off) for ch in channels}
+    return tuple(getattr(_C._tls, ch._slot, ch._off) for ch in read)
+
+
+def _held_channels(ctx):
+    """In the backward, ``with _held_channels(ctx):`` re-enters the channels as the forward saw them (one that was off is
+    entered as off, whatever the thread holds now)."""
+    entered = []
+    for ch, val in ctx.channels.items():
+        if ch is _C.analytic_rays:
+            entered.append(ch(*(val if val is not None else (None, 0, 0))))
+        elif ch is _C.window:
+            entered.append(ch(*(val if val is not None else (None,))))
+        else:
+            entered.append(ch(val))
+    return _Entered(*entered)
+
+
+def _save_optional(ctx, *tensors):
+    """``ctx.save_for_backward`` for tensors of which some may be None; ``_saved_optional`` gives them back, None included."""
+    ctx.saved_present = [t is not None for t in tensors]
+    ctx.save_for_backward(*(t for t in tensors if t is not None))
+
+
+def _saved_optional(ctx):
+    saved = iter(ctx.saved_tensors)
+    return [next(saved) if present else None for present in ctx.saved_present]
+
+
+def _image_grads(grad_color, grad_depth, shape, device):
+    """Zeros for an unmaterialised colour (B,H,W,3) or depth (B,H,W) gradient, ``shape`` = (B,H,W): what the alpha-carrying
+    backwards hand their kernels for an image left out of the loss."""
+    if grad_color is None:
+        grad_color = torch.zeros(tuple(shape) + (3,), dtype=torch.float32, device=device)
+    if grad_depth is None:
+        grad_depth = torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+    return grad_color, grad_depth
+
+
+class _Window(NamedTuple):
+    """A checked render window (``Renderer._window``)."""
+    patch_min: torch.Tensor     # (B,2) int32 on the op's device: the (x, y) origin of each view's window in the frame
+    origins: list               # the same, read back
+    width: int
+    height: int
+
+    @property
+    def empty(self):
+        return self.width == 0 or self.height == 0
+
+
 class RenderFunction(torch.autograd.Function):
     """Differentiable rasterize-and-composite op (reference __init__.py:11-177).
 
@@ -99,15 +154,11 @@ class RenderFunction(torch.autograd.Function):
     def forward(ctx, *inputs):
         if len(inputs) != RenderFunction.N_INPUTS:
             raise TypeError(f"RenderFunction takes {RenderFunction.N_INPUTS} inputs, got {len(inputs)}")
-        # analytic rays (Renderer(analytic_rays=True)): the camera block rides along in the thread-local side channel and is
-        # kept for the backward
-        ctx.analytic = getattr(_C._tls, "analytic", None)
-        # fused host prep: the AA-corner gradients come back already scattered to the vertices' image coordinates
-        # (input 9, verts_image) instead of as dL/d(aa_face_verts) (input 12) -- see _C.aa_grad_to_verts
-        ctx.aa_to_verts = bool(getattr(_C._tls, "aa_to_verts", False))
-        ctx.tables_from_image = bool(getattr(_C._tls, "tables_from_image", False))
-        ctx.alpha = bool(getattr(_C._tls, "alpha_output", False))
-        ctx.weights = bool(getattr(_C._tls, "face_weights_output", False))
+        # kept for the backward: analytic rays (Renderer(analytic_rays=True): the camera block rides along in the side channel)
+        # and the fused host prep's two -- under aa_grad_to_verts the AA-corner gradients come back already scattered to the
+        # vertices' image coordinates (input 9, verts_image) instead of as dL/d(aa_face_verts) (input 12)
+        ctx.alpha, ctx.weights = _hold_channels(ctx, _C.analytic_rays, _C.aa_grad_to_verts, _C.tables_from_image,
+                                                read=(_C.alpha_output, _C.face_weights_output))
         if ctx.alpha:
             ctx.set_materialize_grads(False)        # an unused alpha arrives as None, and the backward is the two-output one
         try:
@@ -117,7 +168,7 @@ class RenderFunction(torch.autograd.Function):
             print("\nAn error occured in renderer forward.")
             print(ex)
             raise
-        ctx.fwd_mode = _C.last_forward_mode()       # what this forward left for its backward (masks, pair pool): picks the backward's kernel
+        ctx.channels[_C.forward_mode] = _C.last_forward_mode()      # what this forward left for its backward (masks, pair pool): picks the backward's kernel
         num_rendered, color, depth = out[0], out[1], out[2]
         opaque = out[3:10]          # 4 AA-record tensors + face/binning/image byte buffers
         tensors_in = [x for x in inputs if torch.is_tensor(x)]
@@ -143,17 +194,11 @@ class RenderFunction(torch.autograd.Function):
         for slot, v in ctx.scalars.items():
             inputs[slot] = v
         oarea, tri_id, tri_cnt, doarea, face_buf, binning_buf, image_buf = saved[ctx.n_tensor_in:]
-        if ctx.alpha:                               # (grads not materialised: zeros for an unused colour / depth)
-            ref = grad_out_alpha if grad_out_alpha is not None else grad_out_color if grad_out_color is not None else grad_out_depth
-            B, H, W = int(inputs[8].shape[0]), int(inputs[3]), int(inputs[2])
-            if grad_out_color is None:
-                grad_out_color = torch.zeros((B, H, W, 3), dtype=torch.float32, device=ref.device)
-            if grad_out_depth is None:
-                grad_out_depth = torch.zeros((B, H, W), dtype=torch.float32, device=ref.device)
+        if ctx.alpha:                               # (grads not materialised)
+            grad_out_color, grad_out_depth = _image_grads(grad_out_color, grad_out_depth,
+                                                          (int(inputs[8].shape[0]), int(inputs[3]), int(inputs[2])), inputs[8].device)
         try:
-            ana = ctx.analytic
-            with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.aa_grad_to_verts(ctx.aa_to_verts), \
-                    _C.forward_mode(ctx.fwd_mode), _C.tables_from_image(ctx.tables_from_image):
+            with _held_channels(ctx):
                 # (the keyword only when alpha is in the loss: otherwise the very call of the two-output op)
                 extra = {} if grad_out_alpha is None else {"dL_dout_alpha": grad_out_alpha}
                 grads = _C.render_backward_cuda(
@@ -166,7 +211,7 @@ class RenderFunction(torch.autograd.Function):
         result: list = [None] * RenderFunction.N_INPUTS
         for slot, g in zip(RenderFunction._GRAD_SLOTS, grads):
             result[slot] = g
-        if ctx.aa_to_verts:
+        if ctx.channels[_C.aa_grad_to_verts]:
             result[9], result[12] = grads[5], None          # (B,P,2): the gradient of verts_image, not of aa_face_verts
         return tuple(result)
 
@@ -211,7 +256,7 @@ class Renderer(torch.nn.Module):
         # the rays are constants of the op, as in the reference (which returns no gradient for them): built without an autograd
         # graph, so that cameras that require grad do not tie every step's backward to a graph of the constructor
         with torch.no_grad():
-            if getattr(self, "analytic_rays", False):
+            if self._analytic():
                 self.ray_cam = torch.cat((torch.inverse(mv).reshape(-1, 16), torch.inverse(proj).reshape(-1, 16)), dim=1) \
                     .to(device=device, dtype=torch.float32).contiguous()
             else:
@@ -275,9 +320,10 @@ class Renderer(torch.nn.Module):
 
     # -- windows on the deferred path ------------------------------------------------
     def _window(self, batch_mvp_idx, patch_min, patch_width, patch_height, device):
-        """The checks of a window of rasterize / generate / coverage / render -> (patch_min as (B,2) int32 on ``device``, the
-        origins as a list): the origins are read back once, for all checks (and for ``select_rays``).  ValueError for a shape
-        other than (B,2), a negative size or a negative origin; ``select_rays``' two assertions for a window past the frame."""
+        """The checks of a window of rasterize / generate / coverage / render -> ``_Window`` (patch_min as (B,2) int32 on
+        ``device``, the origins as a list, the size): the origins are read back once, for all checks (and for ``select_rays``).
+        ValueError for a shape other than (B,2), a negative size or a negative origin; ``select_rays``' two assertions for a
+        window past the frame."""
         B = len(batch_mvp_idx)
         if patch_min.dim() != 2 or tuple(patch_min.shape) != (B, 2):
             raise ValueError(f"patch_min must have dimensions ({B}, 2), got {tuple(patch_min.shape)}")
@@ -289,19 +335,68 @@ class Renderer(torch.nn.Module):
             raise ValueError("patch_min must not be negative")
         assert all(p[0] + patch_width <= self.width for p in pm), "Some b_patch_max_x exceed self.width"
         assert all(p[1] + patch_height <= self.height for p in pm), "Some b_patch_max_y exceed self.height"
-        return patch_min.to(device=device, dtype=torch.int32).contiguous(), pm
+        return _Window(patch_min.to(device=device, dtype=torch.int32).contiguous(), pm, patch_width, patch_height)
 
-    def _window_rays(self, batch_mvp_idx, pm_dev, pm, patch_width, patch_height):
-        """(ray_o, ray_d, context) of a window call: the window's cut of the ray tensors, or placeholders under analytic rays;
-        the context carries the origins (and the cameras) to the op through ``_C``'s side channels."""
+    def _sized_window(self, batch_mvp_idx, patch_min, patch_width, patch_height, device):
+        """The window of rasterize / generate, which take it as ``patch_min`` with both sizes or not at all -> ``_window``'s, or
+        None: the full frame."""
+        if patch_min is None:
+            if patch_width is not None or patch_height is not None:
+                raise ValueError("patch_width / patch_height need patch_min")
+            return None
+        if patch_width is None or patch_height is None:
+            raise ValueError("patch_min needs patch_width and patch_height")
+        return self._window(batch_mvp_idx, patch_min, patch_width, patch_height, device)
+
+    def _layers_window(self, batch_mvp_idx, render_layers, patch_min, device, check_frame):
+        """The window of the ops that are handed ``render_layers`` (B,H,W,L), a window's with ``patch_min`` (its H, W are the
+        window's size) -> ``_window``'s, or None: the full frame.  ``check_frame``: without ``patch_min``, render_layers must
+        have that rank and the frame's size (bary_derivatives, shading_vectors; coverage and render leave both to the op)."""
+        if patch_min is None and not check_frame:
+            return None
+        if render_layers.dim() != 4:
+            raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
+        if patch_min is not None:
+            return self._window(batch_mvp_idx, patch_min, render_layers.shape[2], render_layers.shape[1], device)
+        if tuple(render_layers.shape[1:3]) != (self.height, self.width):
+            raise ValueError(f"render_layers must cover the {self.width} x {self.height} frame (or come with patch_min), "
+                             f"got {tuple(render_layers.shape)}")
+        return None
+
+    def _entered(self, window):
+        """The context of a call on ``window`` (None: the full frame, no window) that takes no rays."""
+        return _C.window(None if window is None else window.patch_min, self.width, self.height)
+
+    def _analytic(self):
+        return getattr(self, "analytic_rays", False)
+
+    def _ray_cam_rows(self, batch_mvp_idx):
+        """inv(mv), inv(proj) of the selected views, (B,32): rows of the block analytic rays keep, or built here."""
+        if self._analytic():
+            return self.ray_cam[torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)]
+        idx = list(batch_mvp_idx)
+        with torch.no_grad():
+            return torch.cat((torch.inverse(self.mv[idx]).reshape(-1, 16), torch.inverse(self.proj[idx]).reshape(-1, 16)), dim=1)
+
+    def _rays(self, batch_mvp_idx, window=None, patch=None):
+        """(ray_o, ray_d, context) of a call on the selected views: the ray tensors' rows (views, for consecutive cameras), or
+        placeholders that are never read under analytic rays, whose cameras the context carries to the op.  ``window``
+        (``_window``'s): the window's cut, and the context carries the origins too (``_C.window``).  ``patch`` =
+        (batch_patch_min, patch_width, patch_height): ``forward``'s, the reference's route -- the cut, but the origins are
+        an argument of the op, not the context's."""
         f32 = torch.float32
-        win = _C.window(pm_dev, self.width, self.height)
-        if getattr(self, "analytic_rays", False):
-            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
-            ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
-            return ph, ph, _Entered(win, _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height))
-        ray_o, ray_d = self.select_rays(batch_mvp_idx, pm_dev, patch_width, patch_height, _origins=pm)
-        return ray_o.to(f32).contiguous(), ray_d.to(f32).contiguous(), _Entered(win)
+        ctx = [] if window is None else [self._entered(window)]
+        if self._analytic():
+            cam = self._ray_cam_rows(batch_mvp_idx)
+            ph = torch.empty((cam.shape[0], 0, 0, 3), dtype=f32, device=cam.device)
+            return ph, ph, _Entered(*ctx, _C.analytic_rays(cam.contiguous(), self.width, self.height))
+        if window is not None:
+            ray_o, ray_d = self.select_rays(batch_mvp_idx, window.patch_min, window.width, window.height, _origins=window.origins)
+        elif patch is not None:
+            ray_o, ray_d = self.select_rays(batch_mvp_idx, *patch)
+        else:
+            ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
+        return ray_o.to(f32), ray_d.to(f32), _Entered(*ctx) if ctx else contextlib.nullcontext()      # (nothing to enter: the full frame)
 
     # -- projection --------------------------------------------------------------
     def compute_verts_ndc_image(self, verts, mv, proj):
@@ -316,6 +411,19 @@ class Renderer(torch.nn.Module):
         image = torch.stack((half[..., 0] * self.width, half[..., 1] * self.height), dim=-1)
         return ndc, image
 
+    def _project(self, batch_mvp_idx, verts, faces, graph):
+        """verts_ndc (B,P,3), verts_image (B,P,2) of the selected views: the fused projection on GPU tensors, else
+        ``compute_verts_ndc_image``.  ``graph`` False: without an autograd graph -- the plan's bins and depth cull, constants
+        of the op like the rays."""
+        mv = self.mv[batch_mvp_idx]
+        proj = self.proj[batch_mvp_idx]
+        i32, f32 = torch.int32, torch.float32
+        with contextlib.nullcontext() if graph else torch.no_grad():
+            if getattr(self, "fused_prep", False) and verts.is_cuda:
+                from . import prep
+                return prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
+            return self.compute_verts_ndc_image(verts, mv, proj)
+
     # -- forward -----------------------------------------------------------------
     def forward(self, batch_mvp_idx: List[int], batch_patch_min: torch.Tensor, patch_width: int,
                 patch_height: int, verts: torch.Tensor, faces: torch.Tensor, verts_color: torch.Tensor,
@@ -329,26 +437,10 @@ class Renderer(torch.nn.Module):
         patch's pixels of alpha * T of the face's blends, the factor its colour gets in C += c alpha T (sum_f equals the
         alpha image's sum; > 0 marks the faces the view used).  Not differentiable; also under torch.no_grad().  Float
         atomics: the last bits may vary from run to run."""
-        with _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
-            return self._forward(batch_mvp_idx, batch_patch_min, patch_width, patch_height, verts, faces, verts_color,
-                                 faces_opacity, faces_intense, background, aa_temperature)
-
-    def _forward(self, batch_mvp_idx, batch_patch_min, patch_width, patch_height, verts, faces, verts_color, faces_opacity,
-                 faces_intense, background, aa_temperature):
-        B = len(batch_mvp_idx)
-        F = faces.shape[0]
-        mv = self.mv[batch_mvp_idx]
-        proj = self.proj[batch_mvp_idx]
-        f32 = torch.float32
-        if getattr(self, "analytic_rays", False):
-            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
-            ray_o = ray_d = torch.empty((B, 0, 0, 3), dtype=f32, device=self.ray_cam.device)      # placeholders, never read
-            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
-                return self._forward_with_rays(B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
-                                               verts_color, faces_opacity, faces_intense, background, aa_temperature)
-        ray_o, ray_d = self.select_rays(batch_mvp_idx, batch_patch_min, patch_width, patch_height)
-        return self._forward_with_rays(B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
-                                       verts_color, faces_opacity, faces_intense, background, aa_temperature)
+        ray_o, ray_d, ctx = self._rays(batch_mvp_idx, patch=(batch_patch_min, patch_width, patch_height))
+        with ctx, _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
+            return self._forward_with_rays(batch_mvp_idx, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
+                                           verts_color, faces_opacity, faces_intense, background, aa_temperature)
 
     def rasterize(self, batch_mvp_idx: Sequence[int], verts: torch.Tensor, faces: torch.Tensor, num_layers: int,
                   faces_existence: torch.Tensor = None, patch_min: torch.Tensor = None, patch_width: int = None,
@@ -384,58 +476,19 @@ class Renderer(torch.nn.Module):
         id); empty slots hold -1, and False in inside.  Hand ``inside`` to ``coverage`` so that a grazing face mixes as it
         does in ``forward``.  Differentiable in bary and t w.r.t. ``verts`` through the clamp (``RasterizeOverlapFunction``)."""
         fn = RasterizeOverlapFunction if overlap else RasterizeFunction
-        if patch_min is None:
-            if patch_width is not None or patch_height is not None:
-                raise ValueError("patch_width / patch_height need patch_min")
-        else:
-            if patch_width is None or patch_height is None:
-                raise ValueError("patch_min needs patch_width and patch_height")
-            return self._rasterize_window(batch_mvp_idx, verts, faces, int(num_layers), faces_existence, patch_min, int(patch_width),
-                                          int(patch_height), fn)
-        mv = self.mv[batch_mvp_idx]
-        proj = self.proj[batch_mvp_idx]
+        window = self._sized_window(batch_mvp_idx, patch_min, patch_width, patch_height, verts.device)
+        pw, ph = (self.width, self.height) if window is None else (window.width, window.height)
         i32, f32 = torch.int32, torch.float32
-        # the plan's bins and depth cull: constants of the op, like the rays
-        with torch.no_grad():
-            if getattr(self, "fused_prep", False) and verts.is_cuda:
-                from . import prep
-                verts_ndc, verts_image = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
-            else:
-                verts_ndc, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
-        fe = None if faces_existence is None else faces_existence.to(i32)
-        args = (verts.to(f32), faces.to(i32), fe, verts_ndc.to(f32), verts_image.to(f32))
-        if getattr(self, "analytic_rays", False):
-            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
-            ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
-            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
-                return fn.apply(*args, ph, ph, self.width, self.height, int(num_layers))
-        ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
-        return fn.apply(*args, ray_o.to(f32), ray_d.to(f32), self.width, self.height, int(num_layers))
-
-    def _project_constants(self, batch_mvp_idx, verts, faces):
-        """verts_ndc, verts_image of the selected views without a graph: the plan's bins and depth cull, constants of the op."""
-        mv = self.mv[batch_mvp_idx]
-        proj = self.proj[batch_mvp_idx]
-        i32, f32 = torch.int32, torch.float32
-        with torch.no_grad():
-            if getattr(self, "fused_prep", False) and verts.is_cuda:
-                from . import prep
-                return prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
-            return self.compute_verts_ndc_image(verts, mv, proj)
-
-    def _rasterize_window(self, batch_mvp_idx, verts, faces, num_layers, faces_existence, patch_min, pw, ph, fn):
-        i32, f32 = torch.int32, torch.float32
-        B, L, dev = len(batch_mvp_idx), num_layers, verts.device
-        pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
-        if pw == 0 or ph == 0:
+        B, L, dev = len(batch_mvp_idx), int(num_layers), verts.device
+        if window is not None and window.empty:
             out = (torch.empty((B, ph, pw, L), dtype=i32, device=dev), torch.empty((B, ph, pw), dtype=i32, device=dev),
                    torch.empty((B, ph, pw, L, 3), dtype=f32, device=dev), torch.empty((B, ph, pw, L), dtype=f32, device=dev))
-            if fn is RasterizeOverlapFunction:
+            if overlap:
                 out += (torch.empty((B, ph, pw, L), dtype=torch.bool, device=dev),)
             return out
-        verts_ndc, verts_image = self._project_constants(batch_mvp_idx, verts, faces)
+        verts_ndc, verts_image = self._project(batch_mvp_idx, verts, faces, graph=False)
         fe = None if faces_existence is None else faces_existence.to(i32)
-        ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
+        ray_o, ray_d, ctx = self._rays(batch_mvp_idx, window)
         with ctx:
             return fn.apply(verts.to(f32), faces.to(i32), fe, verts_ndc.to(f32), verts_image.to(f32), ray_o, ray_d, pw, ph, L)
 
@@ -530,26 +583,12 @@ class Renderer(torch.nn.Module):
         (x + patch_min[b,0], y + patch_min[b,1]): the crop of the full-frame result.  Checks and errors are ``coverage``'s; an
         empty window launches nothing."""
         i32, f32 = torch.int32, torch.float32
-        if render_layers.dim() != 4:
-            raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
-        pm_dev = None
-        if patch_min is not None:
-            pm_dev, _ = self._window(batch_mvp_idx, patch_min, render_layers.shape[2], render_layers.shape[1], verts.device)
-        elif tuple(render_layers.shape[1:3]) != (self.height, self.width):
-            raise ValueError(f"render_layers must cover the {self.width} x {self.height} frame (or come with patch_min), "
-                             f"got {tuple(render_layers.shape)}")
+        window = self._layers_window(batch_mvp_idx, render_layers, patch_min, verts.device, check_frame=True)
         if render_layers.numel() == 0:
             z = torch.empty(tuple(render_layers.shape) + (3,), dtype=f32, device=verts.device)
             return z, z.clone()
-        with torch.no_grad():
-            if getattr(self, "analytic_rays", False):
-                cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
-                cam = self.ray_cam[cams]
-            else:
-                idx = list(batch_mvp_idx)
-                cam = torch.cat((torch.inverse(self.mv[idx]).reshape(-1, 16), torch.inverse(self.proj[idx]).reshape(-1, 16)), dim=1)
-            cam = cam.to(device=verts.device, dtype=f32).contiguous()
-        with _C.window(pm_dev, self.width, self.height):
+        cam = self._ray_cam_rows(batch_mvp_idx).to(device=verts.device, dtype=f32).contiguous()
+        with self._entered(window):
             return BaryDerivativesFunction.apply(render_layers.to(i32), verts.to(f32), faces.to(i32), cam)
 
     def composite(self, values: torch.Tensor, alpha: torch.Tensor, render_layers: torch.Tensor = None,
@@ -596,22 +635,12 @@ class Renderer(torch.nn.Module):
             raise ValueError("temperature must be in the range [0, 1]")
         if inside is not None and tuple(inside.shape) != tuple(render_layers.shape):
             raise ValueError(f"inside must have dimensions {tuple(render_layers.shape)}, got {tuple(inside.shape)}")
-        pm_dev = None
-        if patch_min is not None:
-            if render_layers.dim() != 4:
-                raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
-            pm_dev, _ = self._window(batch_mvp_idx, patch_min, render_layers.shape[2], render_layers.shape[1], verts.device)
-            if render_layers.numel() == 0:
-                return torch.empty(tuple(render_layers.shape), dtype=torch.float32, device=verts.device)
-        mv = self.mv[batch_mvp_idx]
-        proj = self.proj[batch_mvp_idx]
+        window = self._layers_window(batch_mvp_idx, render_layers, patch_min, verts.device, check_frame=False)
+        if window is not None and render_layers.numel() == 0:
+            return torch.empty(tuple(render_layers.shape), dtype=torch.float32, device=verts.device)
         i32, f32 = torch.int32, torch.float32
-        if getattr(self, "fused_prep", False) and verts.is_cuda:
-            from . import prep
-            _, verts_image = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
-        else:
-            _, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
-        with _C.window(pm_dev, self.width, self.height):
+        _, verts_image = self._project(batch_mvp_idx, verts, faces, graph=True)
+        with self._entered(window):
             return CoverageFunction.apply(render_layers.to(i32), verts_image.to(f32), faces.to(i32), float(temperature), inside)
 
     @staticmethod
@@ -675,32 +704,18 @@ class Renderer(torch.nn.Module):
         (x + patch_min[b,0], y + patch_min[b,1]): the crop of the full-frame result.  Checks and errors are ``coverage``'s; an
         empty window launches nothing."""
         i32, f32 = torch.int32, torch.float32
-        if render_layers.dim() != 4:
-            raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
-        B, ph, pw, L = (int(x) for x in render_layers.shape)
-        dev = render_layers.device
+        window = self._layers_window(batch_mvp_idx, render_layers, patch_min, render_layers.device, check_frame=True)
+        if window is not None and render_layers.numel() == 0:
+            return tuple(torch.empty(tuple(render_layers.shape) + (3,), dtype=f32, device=render_layers.device)
+                         for _ in range(2 if normals is None else 4))
         nrm = None if normals is None else normals.to(f32)
-        if patch_min is not None:
-            pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
-            if render_layers.numel() == 0:
-                return tuple(torch.empty((B, ph, pw, L, 3), dtype=f32, device=dev) for _ in range(2 if normals is None else 4))
-            ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
-            with ctx:
-                return ShadingVectorsFunction.apply(render_layers.to(i32), t.to(f32), nrm, ray_o, ray_d)
-        if (ph, pw) != (self.height, self.width):
-            raise ValueError(f"render_layers must cover the {self.width} x {self.height} frame (or come with patch_min), "
-                             f"got {tuple(render_layers.shape)}")
-        if getattr(self, "analytic_rays", False):
-            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
-            hold = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
-            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
-                return ShadingVectorsFunction.apply(render_layers.to(i32), t.to(f32), nrm, hold, hold)
-        ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
-        return ShadingVectorsFunction.apply(render_layers.to(i32), t.to(f32), nrm, ray_o.to(f32), ray_d.to(f32))
+        ray_o, ray_d, ctx = self._rays(batch_mvp_idx, window)
+        with ctx:
+            return ShadingVectorsFunction.apply(render_layers.to(i32), t.to(f32), nrm, ray_o, ray_d)
 
-    def _forward_with_rays(self, B, F, mv, proj, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
+    def _forward_with_rays(self, batch_mvp_idx, ray_o, ray_d, batch_patch_min, patch_width, patch_height, verts, faces,
                            verts_color, faces_opacity, faces_intense, background, aa_temperature):
-        f32 = torch.float32
+        B, F, f32 = len(batch_mvp_idx), faces.shape[0], torch.float32
         if getattr(self, "fused_prep", False) and verts.is_cuda:
             from . import prep
             tfi = getattr(self, "tables_from_image", None)
@@ -708,7 +723,7 @@ class Renderer(torch.nn.Module):
                 # the fused prep owns the AA tables end to end: they are never materialised -- the op's plan builds them per
                 # face from verts_image straight into its packed records (DM2_FLAG_TABLES_FROM_IMAGE; 114 B per face less to
                 # write and to read back), and the corner gradients come back per vertex, as the gradient of verts_image
-                verts_ndc, verts_image = prep.project(verts.to(f32), faces.to(torch.int32), mv.to(f32), proj.to(f32), self.width, self.height)
+                verts_ndc, verts_image = self._project(batch_mvp_idx, verts, faces, graph=True)
                 ph4 = torch.empty((B, 0, 3, 2), dtype=f32, device=verts.device)
                 with _C.tables_from_image(True), _C.aa_grad_to_verts(True):
                     out = RenderFunction.apply(
@@ -716,10 +731,11 @@ class Renderer(torch.nn.Module):
                         verts.to(f32), faces.to(torch.int32), verts_color.to(f32), faces_opacity.to(f32),
                         verts_ndc, verts_image, faces_intense.to(f32), aa_temperature,
                         ph4, ph4, ph4.to(torch.bool), ph4, ph4, torch.empty((B, 0, 3), dtype=f32, device=verts.device),
-                        self.aa_grad_buffer_size, ray_o.to(f32), ray_d.to(f32))
+                        self.aa_grad_buffer_size, ray_o, ray_d)
                 return _finish(out)
             (verts_ndc, verts_image, aa_v, aa_e, aa_z, aa_r, aa_n, aa_c) = prep.prepare(
-                verts.to(f32), faces.to(torch.int32), mv.to(f32), proj.to(f32), self.width, self.height)
+                verts.to(f32), faces.to(torch.int32), self.mv[batch_mvp_idx].to(f32), self.proj[batch_mvp_idx].to(f32), self.width,
+                self.height)
             # the fused prep owns both ends of aa_face_verts: the op hands its corner gradients back per VERTEX (as the
             # gradient of verts_image) and prepare_faces_backward needs no (B,F,3,2) scatter pass (DM2_FUSED_AA_GRAD=0: the
             # reference's route through dL/d(aa_face_verts))
@@ -728,9 +744,9 @@ class Renderer(torch.nn.Module):
                     background.to(f32), batch_patch_min.to(torch.int32), patch_width, patch_height,
                     verts.to(f32), faces.to(torch.int32), verts_color.to(f32), faces_opacity.to(f32),
                     verts_ndc, verts_image, faces_intense.to(f32), aa_temperature,
-                    aa_v, aa_e, aa_z, aa_r, aa_n, aa_c, self.aa_grad_buffer_size, ray_o.to(f32), ray_d.to(f32))
+                    aa_v, aa_e, aa_z, aa_r, aa_n, aa_c, self.aa_grad_buffer_size, ray_o, ray_d)
             return _finish(out)
-        verts_ndc, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
+        verts_ndc, verts_image = self._project(batch_mvp_idx, verts, faces, graph=True)
 
         corners = verts_image[:, faces.flatten()].view(-1, 3, 2)             # (B*F,3,2)
         tri = Triangles(corners[:, 0], corners[:, 1], corners[:, 2])
@@ -747,7 +763,7 @@ class Renderer(torch.nn.Module):
             tri.edges_normal.reshape(B, F, 3, 2).to(f32),
             tri.edges_normal_c.reshape(B, F, 3).to(f32),
             self.aa_grad_buffer_size,
-            ray_o.to(f32), ray_d.to(f32),
+            ray_o, ray_d,
         )
         return _finish(out)
 
@@ -779,9 +795,7 @@ class LayeredCompositeFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background,
                 image_ray_o, image_ray_d):
-        ctx.analytic = getattr(_C._tls, "analytic", None)
-        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
-        ctx.alpha = bool(getattr(_C._tls, "alpha_output", False))
+        (ctx.alpha,) = _hold_channels(ctx, _C.analytic_rays, _C.window, read=(_C.alpha_output,))
         if ctx.alpha:
             ctx.set_materialize_grads(False)
         out = _C.composite_layers_cuda(
@@ -801,18 +815,37 @@ class LayeredCompositeFunction(torch.autograd.Function):
         grad_alpha = grad_rest[0] if ctx.alpha else None      # (then face_weights', ignored)
         (render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
          n_contrib) = ctx.saved_tensors
-        if ctx.alpha:                                  # (grads not materialised: zeros for an unused colour / depth)
-            if grad_color is None:
-                grad_color = torch.zeros(tuple(n_contrib.shape) + (3,), dtype=torch.float32, device=n_contrib.device)
-            if grad_depth is None:
-                grad_depth = torch.zeros(tuple(n_contrib.shape), dtype=torch.float32, device=n_contrib.device)
-        ana, win = ctx.analytic, ctx.window
-        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
+        if ctx.alpha:                                  # (grads not materialised)
+            grad_color, grad_depth = _image_grads(grad_color, grad_depth, n_contrib.shape, n_contrib.device)
+        with _held_channels(ctx):
             extra = {} if grad_alpha is None else {"dL_dout_alpha": grad_alpha}
             dcolor, dopacity, dndc, dintense = _C.composite_layers_backward_cuda(
                 render_layers, verts, faces, verts_color, faces_opacity, faces_intense, verts_ndc, background, ray_o, ray_d,
                 n_contrib, grad_color, grad_depth, **extra)
         return None, None, None, dcolor, dopacity, dintense, dndc, None, None, None
+
+
+def _rasterize_forward(ctx, overlap, verts, faces, faces_existence, verts_ndc, verts_image, image_ray_o, image_ray_d, width, height,
+                       num_layers):
+    """The forward of RasterizeFunction and RasterizeOverlapFunction (``overlap``: one more output, inside)."""
+    _hold_channels(ctx, _C.analytic_rays, _C.window)
+    ctx.set_materialize_grads(False)            # bary / t left out of the loss arrive as None
+    ctx.mode = {"overlap": True} if overlap else {}     # (the keyword only in overlap mode: otherwise the very call it was)
+    out = _C.rasterize_layers_cuda(width, height, verts.detach(), faces, faces_existence, verts_ndc.detach(), verts_image.detach(),
+                                   image_ray_o, image_ray_d, num_layers, **ctx.mode)
+    layers, cnt = out[:2]
+    ctx.mark_non_differentiable(layers, cnt, *out[4:])
+    ctx.save_for_backward(layers, verts.detach(), faces, image_ray_o, image_ray_d)
+    return out
+
+
+def _rasterize_backward(ctx, grad_bary, grad_t):
+    if (grad_bary is None and grad_t is None) or not ctx.needs_input_grad[0]:
+        return (None,) * 10
+    layers, verts, faces, ray_o, ray_d = ctx.saved_tensors
+    with _held_channels(ctx):
+        dverts = _C.rasterize_layers_backward_cuda(layers, verts, faces, ray_o, ray_d, grad_bary, grad_t, **ctx.mode)
+    return (dverts,) + (None,) * 9
 
 
 class RasterizeFunction(torch.autograd.Function):
@@ -828,25 +861,12 @@ class RasterizeFunction(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, verts, faces, faces_existence, verts_ndc, verts_image, image_ray_o, image_ray_d, width, height, num_layers):
-        ctx.analytic = getattr(_C._tls, "analytic", None)
-        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
-        ctx.set_materialize_grads(False)            # bary / t left out of the loss arrive as None
-        layers, cnt, bary, t = _C.rasterize_layers_cuda(width, height, verts.detach(), faces, faces_existence, verts_ndc.detach(),
-                                                        verts_image.detach(), image_ray_o, image_ray_d, num_layers)
-        ctx.mark_non_differentiable(layers, cnt)
-        ctx.save_for_backward(layers, verts.detach(), faces, image_ray_o, image_ray_d)
-        return layers, cnt, bary, t
+    def forward(ctx, *inputs):
+        return _rasterize_forward(ctx, False, *inputs)
 
     @staticmethod
     def backward(ctx, grad_layers, grad_cnt, grad_bary, grad_t):
-        if (grad_bary is None and grad_t is None) or not ctx.needs_input_grad[0]:
-            return (None,) * 10
-        layers, verts, faces, ray_o, ray_d = ctx.saved_tensors
-        ana, win = ctx.analytic, ctx.window
-        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
-            dverts = _C.rasterize_layers_backward_cuda(layers, verts, faces, ray_o, ray_d, grad_bary, grad_t)
-        return (dverts,) + (None,) * 9
+        return _rasterize_backward(ctx, grad_bary, grad_t)
 
 
 class RasterizeOverlapFunction(torch.autograd.Function):
@@ -859,25 +879,12 @@ class RasterizeOverlapFunction(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, verts, faces, faces_existence, verts_ndc, verts_image, image_ray_o, image_ray_d, width, height, num_layers):
-        ctx.analytic = getattr(_C._tls, "analytic", None)
-        ctx.window = getattr(_C._tls, "window", None)
-        ctx.set_materialize_grads(False)
-        layers, cnt, bary, t, inside = _C.rasterize_layers_cuda(width, height, verts.detach(), faces, faces_existence, verts_ndc.detach(),
-                                                                verts_image.detach(), image_ray_o, image_ray_d, num_layers, overlap=True)
-        ctx.mark_non_differentiable(layers, cnt, inside)
-        ctx.save_for_backward(layers, verts.detach(), faces, image_ray_o, image_ray_d)
-        return layers, cnt, bary, t, inside
+    def forward(ctx, *inputs):
+        return _rasterize_forward(ctx, True, *inputs)
 
     @staticmethod
     def backward(ctx, grad_layers, grad_cnt, grad_bary, grad_t, grad_inside):
-        if (grad_bary is None and grad_t is None) or not ctx.needs_input_grad[0]:
-            return (None,) * 10
-        layers, verts, faces, ray_o, ray_d = ctx.saved_tensors
-        ana, win = ctx.analytic, ctx.window
-        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
-            dverts = _C.rasterize_layers_backward_cuda(layers, verts, faces, ray_o, ray_d, grad_bary, grad_t, overlap=True)
-        return (dverts,) + (None,) * 9
+        return _rasterize_backward(ctx, grad_bary, grad_t)
 
 
 class InterpolateFunction(torch.autograd.Function):
@@ -919,8 +926,7 @@ class TextureFunction(torch.autograd.Function):
     def forward(ctx, uv, tex, render_layers, filter_mode, boundary_mode):
         out = _C.texture_cuda(uv.detach(), tex.detach(), render_layers, filter_mode, boundary_mode)
         ctx.modes = (filter_mode, boundary_mode)
-        ctx.has_layers = render_layers is not None
-        ctx.save_for_backward(uv.detach(), tex.detach(), *((render_layers,) if ctx.has_layers else ()))
+        _save_optional(ctx, uv.detach(), tex.detach(), render_layers)
         return out
 
     @staticmethod
@@ -928,8 +934,7 @@ class TextureFunction(torch.autograd.Function):
         need_uv, need_tex = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if grad_out is None or not (need_uv or need_tex):
             return None, None, None, None, None
-        uv, tex = ctx.saved_tensors[:2]
-        render_layers = ctx.saved_tensors[2] if ctx.has_layers else None
+        uv, tex, render_layers = _saved_optional(ctx)
         dtex, duv = _C.texture_backward_cuda(uv, tex, render_layers, *ctx.modes, grad_out, need_tex, need_uv)
         return duv, dtex, None, None, None
 
@@ -948,8 +953,7 @@ class TextureCubeFunction(torch.autograd.Function):
     def forward(ctx, dirs, tex, render_layers, filter_mode):
         out = _C.texture_cube_cuda(dirs.detach(), tex.detach(), render_layers, filter_mode)
         ctx.filter_mode = filter_mode
-        ctx.has_layers = render_layers is not None
-        ctx.save_for_backward(dirs.detach(), tex.detach(), *((render_layers,) if ctx.has_layers else ()))
+        _save_optional(ctx, dirs.detach(), tex.detach(), render_layers)
         return out
 
     @staticmethod
@@ -957,8 +961,7 @@ class TextureCubeFunction(torch.autograd.Function):
         need_dirs, need_tex = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if grad_out is None or not (need_dirs or need_tex):
             return None, None, None, None
-        dirs, tex = ctx.saved_tensors[:2]
-        render_layers = ctx.saved_tensors[2] if ctx.has_layers else None
+        dirs, tex, render_layers = _saved_optional(ctx)
         dtex, ddir = _C.texture_cube_backward_cuda(dirs, tex, render_layers, ctx.filter_mode, grad_out, need_tex, need_dirs)
         return ddir, dtex, None, None
 
@@ -1018,8 +1021,7 @@ class TextureMipFunction(torch.autograd.Function):
     def forward(ctx, uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level):
         out = _C.texture_mip_cuda(uv.detach(), uv_da.detach(), tex.detach(), mip.detach(), render_layers, boundary_mode, max_mip_level)
         ctx.modes = (boundary_mode, max_mip_level)
-        ctx.has_layers = render_layers is not None
-        ctx.save_for_backward(uv.detach(), uv_da.detach(), tex.detach(), mip.detach(), *((render_layers,) if ctx.has_layers else ()))
+        _save_optional(ctx, uv.detach(), uv_da.detach(), tex.detach(), mip.detach(), render_layers)
         return out
 
     @staticmethod
@@ -1027,8 +1029,7 @@ class TextureMipFunction(torch.autograd.Function):
         need_uv, need_tex, need_mip = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         if grad_out is None or not (need_uv or need_tex or need_mip):
             return (None,) * 7
-        uv, uv_da, tex, mip = ctx.saved_tensors[:4]
-        render_layers = ctx.saved_tensors[4] if ctx.has_layers else None
+        uv, uv_da, tex, mip, render_layers = _saved_optional(ctx)
         dtex, dmip, duv = _C.texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, *ctx.modes, grad_out, need_tex, need_mip,
                                                        need_uv)
         return duv, None, dtex, dmip, None, None, None
@@ -1049,8 +1050,7 @@ class CompositeFunction(torch.autograd.Function):
     def forward(ctx, values, alpha, render_layers, background):
         ctx.set_materialize_grads(False)
         out, acc, _, n_contrib = _C.composite_cuda(values.detach(), alpha.detach(), render_layers, background)
-        ctx.has = (render_layers is not None, background is not None)
-        ctx.save_for_backward(values.detach(), alpha.detach(), n_contrib, *(t for t in (render_layers, background) if t is not None))
+        _save_optional(ctx, values.detach(), alpha.detach(), n_contrib, render_layers, background)
         return out, acc
 
     @staticmethod
@@ -1058,10 +1058,7 @@ class CompositeFunction(torch.autograd.Function):
         need_values, need_alpha = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if (grad_out is None and grad_acc is None) or not (need_values or need_alpha):
             return None, None, None, None
-        values, alpha, n_contrib = ctx.saved_tensors[:3]
-        rest = list(ctx.saved_tensors[3:])
-        render_layers = rest.pop(0) if ctx.has[0] else None
-        background = rest.pop(0) if ctx.has[1] else None
+        values, alpha, n_contrib, render_layers, background = _saved_optional(ctx)
         dvalues, dalpha = _C.composite_backward_cuda(values, alpha, render_layers, background, n_contrib, grad_out, grad_acc,
                                                      need_values, need_alpha)
         return dvalues, dalpha, None, None
@@ -1081,7 +1078,7 @@ class CoverageFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, render_layers, verts_image, faces, temperature, inside=None):
         ctx.set_materialize_grads(False)
-        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
+        _hold_channels(ctx, _C.window)              # (origins, frame size) of a window call: kept for the backward
         cov = _C.coverage_cuda(render_layers, verts_image.detach(), faces, temperature, inside)
         ctx.temperature = float(temperature)
         ctx.save_for_backward(render_layers, verts_image.detach(), faces)
@@ -1092,8 +1089,7 @@ class CoverageFunction(torch.autograd.Function):
         if grad_cov is None or ctx.temperature == 0.0 or not ctx.needs_input_grad[1]:
             return None, None, None, None, None
         render_layers, verts_image, faces = ctx.saved_tensors
-        win = ctx.window
-        with _C.window(*(win if win is not None else (None,))):
+        with _held_channels(ctx):
             return None, _C.coverage_backward_cuda(render_layers, verts_image, faces, ctx.temperature, grad_cov), None, None, None
 
 
@@ -1137,12 +1133,11 @@ class ShadingVectorsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, render_layers, t, normals, image_ray_o, image_ray_d):
         ctx.set_materialize_grads(False)
-        ctx.analytic = getattr(_C._tls, "analytic", None)
-        ctx.window = getattr(_C._tls, "window", None)        # (origins, frame size) of a window call: kept for the backward
+        _hold_channels(ctx, _C.analytic_rays, _C.window)
         ctx.has_normals = normals is not None
         outs = _C.shading_vectors_cuda(render_layers, t.detach(), None if normals is None else normals.detach(), image_ray_o,
                                        image_ray_d)
-        ctx.save_for_backward(render_layers, t.detach(), image_ray_o, image_ray_d, *((normals.detach(),) if ctx.has_normals else ()))
+        _save_optional(ctx, render_layers, t.detach(), image_ray_o, image_ray_d, None if normals is None else normals.detach())
         ctx.mark_non_differentiable(outs[1])
         return outs
 
@@ -1152,10 +1147,8 @@ class ShadingVectorsFunction(torch.autograd.Function):
         need_n = ctx.has_normals and ctx.needs_input_grad[2] and (g_normal is not None or g_reflection is not None)
         if not (need_t or need_n):
             return None, None, None, None, None
-        render_layers, t, ray_o, ray_d = ctx.saved_tensors[:4]
-        normals = ctx.saved_tensors[4] if ctx.has_normals else None
-        ana, win = ctx.analytic, ctx.window
-        with _C.analytic_rays(*(ana if ana is not None else (None, 0, 0))), _C.window(*(win if win is not None else (None,))):
+        render_layers, t, ray_o, ray_d, normals = _saved_optional(ctx)
+        with _held_channels(ctx):
             dt, dn = _C.shading_vectors_backward_cuda(render_layers, t, normals, ray_o, ray_d, g_position, g_normal, g_reflection,
                                                       need_t, need_n)
         return None, dt, dn, None, None
@@ -1184,49 +1177,18 @@ class LayeredRenderer(Renderer):
         generates the layers of that window of each view only (H, W = patch_height, patch_width): window pixel (x, y) is frame
         pixel (x + patch_min[b,0], y + patch_min[b,1]) with that pixel's ray, the first-hit pass's 16x16 tiles anchored at the
         window's origin -- ``Renderer.rasterize``'s window rules and errors."""
-        if patch_min is None:
-            if patch_width is not None or patch_height is not None:
-                raise ValueError("patch_width / patch_height need patch_min")
-        else:
-            if patch_width is None or patch_height is None:
-                raise ValueError("patch_min needs patch_width and patch_height")
-            return self._generate_window(batch_mvp_idx, verts, faces, tets, face_tets, tet_faces, faces_existence, int(num_layers),
-                                         patch_min, int(patch_width), int(patch_height))
-        mv = self.mv[batch_mvp_idx]
-        proj = self.proj[batch_mvp_idx]
-        i32, f32 = torch.int32, torch.float32
-        if getattr(self, "fused_prep", False) and verts.is_cuda:
-            from . import prep
-            with torch.no_grad():
-                verts_ndc, verts_image = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
-        else:
-            verts_ndc, verts_image = self.compute_verts_ndc_image(verts, mv, proj)
-        if getattr(self, "analytic_rays", False):
-            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
-            ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
-            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height):
-                return _C.generate_render_layers_cuda(
-                    self.width, self.height, verts.to(f32), faces.to(i32), tets.to(i32), face_tets.to(i32), tet_faces.to(i32),
-                    faces_existence.to(i32), verts_ndc.to(f32), verts_image.to(f32), ph, ph, num_layers)
-        ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
-        return _C.generate_render_layers_cuda(
-            self.width, self.height,
-            verts.to(f32), faces.to(i32), tets.to(i32), face_tets.to(i32), tet_faces.to(i32),
-            faces_existence.to(i32), verts_ndc.to(f32), verts_image.to(f32),
-            ray_o.to(f32), ray_d.to(f32), num_layers)
-
-    def _generate_window(self, batch_mvp_idx, verts, faces, tets, face_tets, tet_faces, faces_existence, num_layers, patch_min, pw, ph):
+        window = self._sized_window(batch_mvp_idx, patch_min, patch_width, patch_height, verts.device)
+        pw, ph = (self.width, self.height) if window is None else (window.width, window.height)
         i32, f32 = torch.int32, torch.float32
         B, dev = len(batch_mvp_idx), verts.device
-        pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
-        if pw == 0 or ph == 0:
-            return torch.empty((B, ph, pw, num_layers), dtype=i32, device=dev), torch.empty((B, ph, pw), dtype=i32, device=dev)
-        verts_ndc, verts_image = self._project_constants(batch_mvp_idx, verts, faces)
-        ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
+        if window is not None and window.empty:
+            return torch.empty((B, ph, pw, int(num_layers)), dtype=i32, device=dev), torch.empty((B, ph, pw), dtype=i32, device=dev)
+        verts_ndc, verts_image = self._project(batch_mvp_idx, verts, faces, graph=False)
+        ray_o, ray_d, ctx = self._rays(batch_mvp_idx, window)
         with ctx:
             return _C.generate_render_layers_cuda(
                 pw, ph, verts.to(f32), faces.to(i32), tets.to(i32), face_tets.to(i32), tet_faces.to(i32), faces_existence.to(i32),
-                verts_ndc.to(f32), verts_image.to(f32), ray_o, ray_d, num_layers)
+                verts_ndc.to(f32), verts_image.to(f32), ray_o, ray_d, int(num_layers))
 
     def render(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
                verts_color: torch.Tensor, faces_opacity: torch.Tensor, faces_intense: torch.Tensor, background: torch.Tensor,
@@ -1249,56 +1211,21 @@ class LayeredRenderer(Renderer):
         window must lie inside the frame (``select_rays``' assertions; ValueError for a negative origin); an empty window
         returns empty images and launches nothing.
         """
-        if patch_min is not None:
-            return self._render_window(batch_mvp_idx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense,
-                                       background, return_alpha, return_face_weights, patch_min)
-        mv = self.mv[batch_mvp_idx]
-        proj = self.proj[batch_mvp_idx]
+        window = self._layers_window(batch_mvp_idx, render_layers, patch_min, verts.device, check_frame=False)
         i32, f32 = torch.int32, torch.float32
-        if getattr(self, "fused_prep", False) and verts.is_cuda:
-            from . import prep
-            verts_ndc, _ = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
-        else:
-            verts_ndc, _ = self.compute_verts_ndc_image(verts, mv, proj)
-        args = (render_layers.to(i32), verts.to(f32), faces.to(i32), verts_color.to(f32), faces_opacity.to(f32),
-                faces_intense.to(f32), verts_ndc.to(f32), background.to(f32))
-        if getattr(self, "analytic_rays", False):
-            cams = torch.as_tensor(list(batch_mvp_idx), device=self.ray_cam.device, dtype=torch.long)
-            ph = torch.empty((len(cams), 0, 0, 3), dtype=f32, device=self.ray_cam.device)
-            with _C.analytic_rays(self.ray_cam[cams].contiguous(), self.width, self.height), _C.alpha_output(return_alpha), \
-                    _C.face_weights_output(return_face_weights):
-                out = LayeredCompositeFunction.apply(*args, ph, ph)
-        else:
-            ray_o, ray_d = self._camera_rows(self.ray_o, batch_mvp_idx), self._camera_rows(self.ray_d, batch_mvp_idx)
-            with _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
-                out = LayeredCompositeFunction.apply(*args, ray_o.to(f32), ray_d.to(f32))
-        # NDC z in [-1,1] (background +1) -> [0,1] with background 0, as Renderer.forward
-        return _finish(out)
-
-    def _render_window(self, batch_mvp_idx, render_layers, verts, faces, verts_color, faces_opacity, faces_intense, background,
-                       return_alpha, return_face_weights, patch_min):
-        i32, f32 = torch.int32, torch.float32
-        if render_layers.dim() != 4:
-            raise ValueError(f"render_layers must have dimensions (B, H, W, L), got {tuple(render_layers.shape)}")
-        B, ph, pw, dev = len(batch_mvp_idx), int(render_layers.shape[1]), int(render_layers.shape[2]), verts.device
-        pm_dev, pm = self._window(batch_mvp_idx, patch_min, pw, ph, dev)
-        if pw == 0 or ph == 0:
+        if window is not None and window.empty:
+            B, ph, pw, dev = len(batch_mvp_idx), window.height, window.width, verts.device
             out = (torch.empty((B, ph, pw, 3), dtype=f32, device=dev), torch.empty((B, ph, pw), dtype=f32, device=dev))
             if return_alpha:
                 out += (torch.empty((B, ph, pw), dtype=f32, device=dev),)
             if return_face_weights:
                 out += (torch.zeros((B, faces.shape[0]), dtype=f32, device=dev),)
             return out
-        mv = self.mv[batch_mvp_idx]
-        proj = self.proj[batch_mvp_idx]
-        if getattr(self, "fused_prep", False) and verts.is_cuda:
-            from . import prep
-            verts_ndc, _ = prep.project(verts.to(f32), faces.to(i32), mv.to(f32), proj.to(f32), self.width, self.height)
-        else:
-            verts_ndc, _ = self.compute_verts_ndc_image(verts, mv, proj)
-        ray_o, ray_d, ctx = self._window_rays(batch_mvp_idx, pm_dev, pm, pw, ph)
+        verts_ndc, _ = self._project(batch_mvp_idx, verts, faces, graph=True)
+        ray_o, ray_d, ctx = self._rays(batch_mvp_idx, window)
         with ctx, _C.alpha_output(return_alpha), _C.face_weights_output(return_face_weights):
             out = LayeredCompositeFunction.apply(render_layers.to(i32), verts.to(f32), faces.to(i32), verts_color.to(f32),
                                                  faces_opacity.to(f32), faces_intense.to(f32), verts_ndc.to(f32), background.to(f32),
                                                  ray_o, ray_d)
+        # NDC z in [-1,1] (background +1) -> [0,1] with background 0, as Renderer.forward
         return _finish(out)

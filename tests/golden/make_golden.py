@@ -21,6 +21,12 @@ and records
                       11 arguments of ``_C.generate_render_layers_cuda``
                       (__init__.py:432-449).
 
+  frontend_calls.json what the front end (dmesh2_renderer_amd/__init__.py) hands to ``_C`` for every public method, as
+                      tests/frontend_trace.py records it on CPU tensors: names, dtypes, shapes, scalars and the structure
+                      of the side channels, no floating-point tensor values.  Needs neither the reference nor a GPU
+                      (``--only-frontend-calls``, and only that flag writes it: a full run leaves it alone); regenerate only
+                      when that contract is meant to change.
+
 Only arrays are written; no reference source or bytecode is copied.  The GPU
 box never runs this script (no /root/reference there) -- tests read the .npz.
 """
@@ -377,7 +383,20 @@ def make_layers_boundary(ref, stub, scenes):
     print("boundary_layers", {k: getattr(v, "shape", None) for k, v in captured.items()})
 
 
+def make_frontend_calls():
+    import json
+    sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+    import frontend_trace
+    trace = frontend_trace.trace()
+    with open(os.path.join(HERE, "frontend_calls.json"), "w") as f:     # one case per line
+        f.write("{\n" + ",\n".join(json.dumps(k) + ": " + json.dumps(v, sort_keys=True) for k, v in sorted(trace.items())) + "\n}\n")
+    print("frontend_calls.json :", len(trace), "cases,", sum(len(v) for v in trace.values()), "calls")
+
+
 def main():
+    if "--only-frontend-calls" in sys.argv:
+        make_frontend_calls()
+        return
     scenes = load_scenes()
     ref, stub = import_reference()
     if "--only-aa-errors" in sys.argv:

@@ -452,7 +452,7 @@ def test_three_forwards_then_their_backwards():
 
 def test_module_three_losses_one_backward():
     """The same through the module: three Renderer.forward calls that leave different modes, the losses summed, one backward();
-    every RenderFunction.backward tells the kernel the mode of its own forward (ctx.fwd_mode)."""
+    every RenderFunction.backward tells the kernel the mode of its own forward (held on ctx with the forward's side channels)."""
     _C._bin_hint.clear()
     sc0 = seq.scene("S0").to("cuda")
     r = dm2.Renderer(sc0.mv, sc0.proj, W, H, "cuda")
