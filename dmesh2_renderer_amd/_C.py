@@ -39,6 +39,13 @@ and its mip-mapped filter (Renderer.bary_derivatives, Renderer.texture_mipmaps, 
     texture_mip_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level) -> out,
     texture_mip_backward_cuda(...those 7..., grad_out, need_tex, need_mip, need_uv) -> (dL/dtex, dL/dmip, dL/duv)
 
+and the cube's mip chain at a level of detail per slot (texture's "linear-mipmap-linear" with "cube" and mip_level; the same
+two C symbols under DM2_TEX_BOUNDARY_CUBE):
+
+    texture_cube_mip_cuda(dirs, level, tex, mip, render_layers, max_mip_level) -> out,
+    texture_cube_mip_backward_cuda(...those 6..., grad_out, need_tex, need_mip, need_dirs, need_level)
+        -> (dL/dtex, dL/dmip, dL/ddirs, dL/dlevel)
+
 and such per-slot values blended into an image (Renderer.composite; not composite_layers_cuda, which shades by itself):
 
     composite_cuda(values, alpha, render_layers, background) -> (out, acc, final_T, n_contrib),
@@ -1361,6 +1368,70 @@ def texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode,
                                         _ptr(duv), _stream(dev)):
             raise _err(lib, "texture_mip_backward_cuda")
     return dtex, dmip, duv
+
+
+TEX_BOUNDARY_CUBE = 2          # DM2_TEX_BOUNDARY_CUBE: dm2_texture_mip / dm2_texture_mip_backward only
+
+
+def _texture_cube_mip_args(dirs, level, tex, mip, render_layers, max_mip_level, grad_out=None):
+    """Checks of a cube mip chain call -> (sizes (B, H, W, L, N, N, C, view_textures, DM2_TEX_BOUNDARY_CUBE, max level code),
+    contiguous tensors (dirs, level, tex, mip, render_layers, grad_out), device)."""
+    sizes, (dc, tx, rl, go), dev = _texture_cube_args(dirs, tex, render_layers, "linear", grad_out)
+    B, H, W, L, N, C, per_view = sizes[:7]
+    _bad(tuple(level.shape) != (B, H, W, L), f"mip_level must have dimensions {(B, H, W, L)}, got {tuple(level.shape)}")
+    _, _, T = mip_layout(N, N, max_mip_level)
+    _bad(6 * (N * N + T) >= 2 ** 31, "tex: the texels of all levels of the cube must number below 2^31")
+    shape = ((B,) if per_view else ()) + (6, T, C)
+    _bad(tuple(mip.shape) != shape,
+        f"mip must have dimensions {shape} for tex {tuple(tex.shape)} and max_mip_level {max_mip_level}, got {tuple(mip.shape)}")
+    _require_gpu(dirs, level, mip)
+    for name, t in (("mip_level", level), ("mip", mip)):
+        _bad(t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype}")
+    return ((B, H, W, L, N, N, C, per_view, TEX_BOUNDARY_CUBE, _max_level_code(max_mip_level)),
+            (dc, level.contiguous(), tx, mip.contiguous(), rl, go), dev)
+
+
+def texture_cube_mip_cuda(dirs, level, tex, mip, render_layers=None, max_mip_level=None):
+    """A cube map and its mip chain looked up by per-slot directions and levels of detail (include/dm2_hip.h: dm2_texture_mip
+    with DM2_TEX_BOUNDARY_CUBE).
+
+    dirs (B,H,W,L,3), level (B,H,W,L) float32 (level 0 is tex), tex (6,N,N,C) or (B,6,N,N,C), mip (6,T,C) or (B,6,T,C): per face
+    the levels 1 .. nlev-1 in ``mip_layout(N, N, max_mip_level)``'s packing, render_layers (B,H,W,L) int32 or None -> out
+    (B,H,W,L,C) float32; 0 where the id is negative, the direction is not finite or all zero, or the level is not finite."""
+    lib = load_library()
+    sizes, (dc, lv, tx, mp, rl, _), dev = _texture_cube_mip_args(dirs, level, tex, mip, render_layers, max_mip_level)
+    B, H, W, L, C = *sizes[:4], sizes[6]
+    if B * H * W * L == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mip(*sizes, _ptr(rl), _ptr(dc), _ptr(lv), _ptr(tx), _ptr(mp), _ptr(out), _stream(dev)):
+            raise _err(lib, "texture_cube_mip_cuda")
+    return out
+
+
+def texture_cube_mip_backward_cuda(dirs, level, tex, mip, render_layers, max_mip_level, grad_out, need_tex, need_mip, need_dirs,
+                                   need_level):
+    """Gradients of texture_cube_mip_cuda (dm2_texture_mip_backward with DM2_TEX_BOUNDARY_CUBE) -> (dL_dtex of tex's shape,
+    dL_dmip of mip's shape, dL_ddirs (B,H,W,L,3), dL_dlevel (B,H,W,L)), each None unless its ``need_*`` asks for it.  The
+    direction's and the level's gradients come from one kernel as rows of four floats, split here."""
+    lib = load_library()
+    sizes, (dc, lv, tx, mp, rl, go), dev = _texture_cube_mip_args(dirs, level, tex, mip, render_layers, max_mip_level, grad_out)
+    B, H, W, L = sizes[:4]
+    f32 = torch.float32
+    if not (need_tex or need_mip or need_dirs or need_level):
+        return None, None, None, None
+    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None      # (summed into)
+    dmip = torch.zeros(tuple(mip.shape), dtype=f32, device=dev) if need_mip else None
+    if B * H * W * L == 0:
+        return (dtex, dmip, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_dirs else None,
+                torch.zeros((B, H, W, L), dtype=f32, device=dev) if need_level else None)
+    rows = torch.empty((B, H, W, L, 4), dtype=f32, device=dev) if need_dirs or need_level else None    # (every element written)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mip_backward(*sizes, _ptr(rl), _ptr(dc), _ptr(lv), _ptr(tx), _ptr(mp), _ptr(go), _ptr(dtex), _ptr(dmip),
+                                        _ptr(rows), _stream(dev)):
+            raise _err(lib, "texture_cube_mip_backward_cuda")
+    return dtex, dmip, rows[..., :3].contiguous() if need_dirs else None, rows[..., 3].contiguous() if need_level else None
 
 
 COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1     # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*

@@ -20,7 +20,9 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   filtering for ``texture`` (``filter_mode="linear-mipmap-linear"``, ``TextureMipFunction``) with the two ops that feed it:
   ``Renderer.bary_derivatives()``, the pixel's footprint on each listed face (``BaryDerivativesFunction``, a constant of
   the pipeline), and ``Renderer.texture_mipmaps()``, the chain of 2 x 2 means (``MipmapFunction``); and cube-map lookup by
-  direction for ``texture`` (``boundary_mode="cube"``, ``TextureCubeFunction``): filtered across the cube's edges and corners;
+  direction for ``texture`` (``boundary_mode="cube"``, ``TextureCubeFunction``): filtered across the cube's edges and corners,
+  and through the cube's mip chain at a level of detail per slot (``mip_level``, ``TextureCubeMipFunction``), which receives a
+  gradient: a glossy reflection whose roughness can be learned;
   and what produces those directions: ``Renderer.vertex_normals()``, smooth normals that carry a gradient to the vertices
   without float atomics (``VertexNormalsFunction``, over ``Renderer.vertex_adjacency()``'s index), and
   ``Renderer.shading_vectors()``, per-slot position, view, unit normal and reflection vectors from the pixel's own ray
@@ -45,7 +47,8 @@ from .pyrenderer import Triangles
 
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
            "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction", "BaryDerivativesFunction",
-           "MipmapFunction", "TextureMipFunction", "TextureCubeFunction", "VertexNormalsFunction", "ShadingVectorsFunction"]
+           "MipmapFunction", "TextureMipFunction", "TextureCubeFunction", "VertexNormalsFunction", "ShadingVectorsFunction",
+           "TextureCubeMipFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -506,7 +509,8 @@ class Renderer(torch.nn.Module):
         return InterpolateFunction.apply(render_layers.to(i32), bary.to(f32), attr.to(f32), attr_faces.to(i32))
 
     def texture(self, uv: torch.Tensor, tex: torch.Tensor, render_layers: torch.Tensor = None, filter_mode: str = "linear",
-                boundary_mode: str = "wrap", uv_da: torch.Tensor = None, mip: torch.Tensor = None, max_mip_level: int = None):
+                boundary_mode: str = "wrap", uv_da: torch.Tensor = None, mip: torch.Tensor = None, max_mip_level: int = None,
+                mip_level: torch.Tensor = None):
         """A texture sampled at ``interpolate``'s UVs (not in the reference): uv (B,H,W,L,2) float32 = (u, v), u along the
         texture's width (what ``interpolate`` returns for a 2-channel attribute), tex (Ht,Wt,C) float32 shared by the views or
         (B,Ht,Wt,C) one texture per view, channel-last, any C >= 1, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C)
@@ -538,12 +542,37 @@ class Renderer(torch.nn.Module):
         continuous over the whole sphere; "nearest" takes the face's nearest texel.  A slot with a negative id, a non-finite
         component or an all-zero direction is empty.  Differentiable w.r.t. ``tex`` and the direction
         (``TextureCubeFunction``); the direction's gradient is orthogonal to it.  ValueError naming ``boundary_mode`` for
-        "linear-mipmap-linear", ``uv_da``, ``mip`` or ``max_mip_level`` with "cube": cube mip chains are not built."""
+        "linear-mipmap-linear", ``mip`` or ``max_mip_level`` with "cube" and without ``mip_level``, and for ``uv_da`` with
+        "cube" always: a cube has no footprint-driven level.
+
+        ``filter_mode="linear-mipmap-linear"`` with ``boundary_mode="cube"`` and ``mip_level`` (B,H,W,L) float32 samples the
+        cube's mip chain at a level of detail per slot (a glossy reflection: the level from the roughness): level 0 is
+        ``tex``, level k has faces of N >> k texels and exists while N >> (k - 1) is even and k <= ``max_mip_level``.  ``mip``
+        (6,T,C) or (B,6,T,C) holds, per face, levels 1 .. nlev-1 packed as ``_C.mip_layout(N, N, max_mip_level)`` lays them
+        out; None builds the box chain here (``texture_mipmaps``), so that ``tex.grad`` receives both the direct gradient and
+        the chain's; a chain the caller supplies (prefiltered, or learned) gets its own gradient and need not be the box
+        chain.  At or below level 0 the result is "linear"'s to the bit, at or beyond the last level the last level's, in
+        between c_j + f (c_{j+1} - c_j) of the two levels' cube samples (seams and corners at each level's own size).  A
+        slot whose level is not finite is empty as well.  Differentiable w.r.t. ``tex``, ``mip``, the direction and
+        ``mip_level`` (``TextureCubeMipFunction``): dL/dmip_level = g . (c_{j+1} - c_j) between two levels, 0 where the level
+        is clamped.  ValueError naming ``mip_level`` for ``mip_level`` with any other combination of modes."""
         i32, f32 = torch.int32, torch.float32
         rl = None if render_layers is None else render_layers.to(i32)
+        if boundary_mode == "cube" and mip_level is not None:
+            if uv_da is not None:
+                raise ValueError('boundary_mode "cube" takes no uv_da: the level of detail comes in through mip_level')
+            if filter_mode != "linear-mipmap-linear":
+                raise ValueError('mip_level belongs to filter_mode "linear-mipmap-linear" with boundary_mode "cube"')
+            tex = tex.to(f32)
+            if mip is None:
+                mip = self.texture_mipmaps(tex, max_mip_level)
+            return TextureCubeMipFunction.apply(uv.to(f32), mip_level.to(f32), tex, mip.to(f32), rl, max_mip_level)
+        if mip_level is not None:
+            raise ValueError('mip_level belongs to filter_mode "linear-mipmap-linear" with boundary_mode "cube"')
         if boundary_mode == "cube":
             if filter_mode == "linear-mipmap-linear" or uv_da is not None or mip is not None or max_mip_level is not None:
-                raise ValueError('boundary_mode "cube" takes filter_mode "linear" or "nearest" and no uv_da, mip or max_mip_level')
+                raise ValueError('boundary_mode "cube" takes filter_mode "linear" or "nearest" and no uv_da, mip or max_mip_level; '
+                                 '"linear-mipmap-linear" with mip_level samples the cube\'s mip chain')
             return TextureCubeFunction.apply(uv.to(f32), tex.to(f32), rl, filter_mode)
         if filter_mode == "linear-mipmap-linear":
             if uv_da is None:
@@ -562,8 +591,16 @@ class Renderer(torch.nn.Module):
         k < ``max_mip_level`` (None: no limit), has half the extents, and each of its texels is the mean of its 2 x 2 parents,
         ((p00 + p10) + (p01 + p11)) * 0.25.  ``mip`` holds levels 1 .. nlev-1 one after the other, each (H_k, W_k, C)
         row-major (``_C.mip_layout``); T = 0 when no level can be built (an odd extent).  Differentiable w.r.t. ``tex``
-        (``MipmapFunction``): the backward is a gather, deterministic."""
-        return MipmapFunction.apply(tex.to(torch.float32), max_mip_level)
+        (``MipmapFunction``): the backward is a gather, deterministic.
+
+        A cube map (6,N,N,C) is six textures and gives (6,T,C); a cube per view (B,6,N,N,C) gives (B,6,T,C).  The 2 x 2 mean
+        within each face is the cube's box chain (a texel's parents never lie on another face), which is what
+        ``texture(..., "linear-mipmap-linear", "cube", mip_level=...)`` builds when it is given no ``mip``."""
+        tex = tex.to(torch.float32)
+        if tex.dim() == 5:
+            mip = MipmapFunction.apply(tex.reshape((-1,) + tuple(tex.shape[2:])), max_mip_level)
+            return mip.reshape(tuple(tex.shape[:2]) + tuple(mip.shape[1:]))
+        return MipmapFunction.apply(tex, max_mip_level)
 
     def bary_derivatives(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
                          patch_min: torch.Tensor = None):
@@ -1033,6 +1070,35 @@ class TextureMipFunction(torch.autograd.Function):
         dtex, dmip, duv = _C.texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, *ctx.modes, grad_out, need_tex, need_mip,
                                                        need_uv)
         return duv, None, dtex, dmip, None, None, None
+
+
+class TextureCubeMipFunction(torch.autograd.Function):
+    """out = the cube map and its mip chain in each slot's direction at the slot's level of detail
+    (``_C.texture_cube_mip_cuda``): c_j + f (c_{j+1} - c_j) of the cube samples of the two levels round the level; one level
+    at or below level 0 and at or beyond the last.
+
+    Inputs: dirs (B,H,W,L,3)*, mip_level (B,H,W,L)*, tex (6,N,N,C)* or (B,6,N,N,C)*, mip (6,T,C)* or (B,6,T,C)*, render_layers
+    (B,H,W,L) int32 or None, max_mip_level.  Output: out (B,H,W,L,C).  (* = receives a gradient.)  A non-empty slot sends
+    (1 - f) w g and f w g to the texels of its two levels (level 0's in tex, the others in mip), the blend of the two levels'
+    direction gradients to dirs, and g . (c_{j+1} - c_j) to its level (0 where the level is clamped).  Only the gradients
+    ``needs_input_grad`` asks for are computed."""
+
+    @staticmethod
+    def forward(ctx, dirs, mip_level, tex, mip, render_layers, max_mip_level):
+        out = _C.texture_cube_mip_cuda(dirs.detach(), mip_level.detach(), tex.detach(), mip.detach(), render_layers, max_mip_level)
+        ctx.max_mip_level = max_mip_level
+        _save_optional(ctx, dirs.detach(), mip_level.detach(), tex.detach(), mip.detach(), render_layers)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_dirs, need_level, need_tex, need_mip = ctx.needs_input_grad[:4]
+        if grad_out is None or not (need_dirs or need_level or need_tex or need_mip):
+            return (None,) * 6
+        dirs, mip_level, tex, mip, render_layers = _saved_optional(ctx)
+        dtex, dmip, ddir, dlevel = _C.texture_cube_mip_backward_cuda(dirs, mip_level, tex, mip, render_layers, ctx.max_mip_level, grad_out,
+                                                                     need_tex, need_mip, need_dirs, need_level)
+        return ddir, dlevel, dtex, dmip, None, None
 
 
 class CompositeFunction(torch.autograd.Function):

@@ -756,10 +756,30 @@ static int check_texture_mip_sizes(int32_t B, int32_t H, int32_t W, int32_t L, i
     return check_mip_sizes(B, Ht, Wt, C, max_mip_level, T);
 }
 
+// DM2_TEX_BOUNDARY_CUBE: Ht == Wt == N, a chain per face (*T: its texels), every level's texels in one 32-bit key space
+static int check_texture_cube_mip_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C,
+                                        int32_t max_mip_level, int64_t* T) {
+    if (Ht != Wt) return fail("texture_mip: a cube's faces must be square (Ht == Wt)");
+    if (check_texture_cube_sizes(B, H, W, L, Ht, C, DM2_TEX_FILTER_LINEAR)) return 1;
+    dm2::mip_levels(Ht, Wt, max_mip_level, T);
+    if (6 * ((int64_t)Ht * Wt + *T) > 0x7FFFFFFF) return fail("texture_mip: the texels of all levels of the cube must number below 2^31");
+    return 0;
+}
+
 int dm2_texture_mip(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
                     int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv, const float* uv_da,
                     const float* tex, const float* mip, float* out, void* stream) {
     int64_t T;
+    if (boundary == DM2_TEX_BOUNDARY_CUBE) {                             // uv: directions, uv_da: the level of detail
+        if (check_texture_cube_mip_sizes(B, H, W, L, Ht, Wt, C, max_mip_level, &T)) return 1;
+        if ((int64_t)B * H * W * L == 0) return 0;
+        if (!uv || !uv_da || !tex || !out) return fail("texture_mip: dirs, the level, tex and out must not be null");
+        if (T > 0 && !mip) return fail("texture_mip: mip must not be null");
+        dm2::launch_texture_cube_mip(B, H, W, L, Ht, C, view_textures, max_mip_level, render_layers, uv, uv_da, tex, mip, out,
+                                     (hipStream_t)stream);
+        DM2_HIP(hipGetLastError());
+        return 0;
+    }
     if (check_texture_mip_sizes(B, H, W, L, Ht, Wt, C, boundary, max_mip_level, &T)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
     if (!uv || !uv_da || !tex || !out) return fail("texture_mip: uv, uv_da, tex and out must not be null");
@@ -775,6 +795,18 @@ int dm2_texture_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
                              const float* uv_da, const float* tex, const float* mip, const float* dL_dout, float* dL_dtex,
                              float* dL_dmip, float* dL_duv, void* stream) {
     int64_t T;
+    if (boundary == DM2_TEX_BOUNDARY_CUBE) {                             // dL_duv: (B,H,W,L,4) rows (dL/ddir, dL/dlevel)
+        if (check_texture_cube_mip_sizes(B, H, W, L, Ht, Wt, C, max_mip_level, &T)) return 1;
+        if (T == 0) dL_dmip = nullptr;
+        if ((int64_t)B * H * W * L == 0 || (!dL_dtex && !dL_dmip && !dL_duv)) return 0;
+        if (!uv || !uv_da || !dL_dout) return fail("texture_mip_backward: dirs, the level and dL_dout must not be null");
+        if (dL_duv && (!tex || (T > 0 && !mip))) return fail("texture_mip_backward: tex and mip must not be null");
+        if ((uintptr_t)dL_duv % 16) return fail("texture_mip_backward: the cube's dL_duv rows must be 16-byte aligned");
+        dm2::launch_texture_cube_mip_backward(B, H, W, L, Ht, C, view_textures, max_mip_level, render_layers, uv, uv_da, tex, mip,
+                                              dL_dout, dL_dtex, dL_dmip, dL_duv, (hipStream_t)stream);
+        DM2_HIP(hipGetLastError());
+        return 0;
+    }
     if (check_texture_mip_sizes(B, H, W, L, Ht, Wt, C, boundary, max_mip_level, &T)) return 1;
     if (T == 0) dL_dmip = nullptr;                                       // an empty chain: nothing to add into
     if ((int64_t)B * H * W * L == 0 || (!dL_dtex && !dL_dmip && !dL_duv)) return 0;

@@ -153,6 +153,56 @@ __device__ __forceinline__ void tex_scatter_layer(TexTable<CH>& tab, int tid, bo
     }
 }
 
+// tex_scatter_layer for a caller whose list has holes: pair k takes part when bit k of ``mask`` is set (the cube's mip chain: a
+// corner's missing tap, one per level at the most, so a single ``skip`` does not say it).  The same body otherwise; written
+// out a second time because tex_scatter_layer's callers are pinned to their instruction streams.
+// ``first``: the pairs (bits of mask) whose keys claim their table slots before any other key does.  A tile of unrelated
+// directions holds up to 8 * 256 keys, four times the table; the keys of the coarse levels are the few that every tile of the
+// frame shares, and one of them that finds the table full would go to global memory once per lane, all on the same addresses.
+template <int CH, int NT, bool MAY_BE_ABSENT, typename Row>
+__device__ __forceinline__ void tex_scatter_layer_masked(TexTable<CH>& tab, int tid, bool live, const int* key, const float* w, unsigned mask,
+                                                         unsigned first, const float* __restrict__ g, int64_t s, int C, Row&& row) {
+    tab.clear_keys(tid);
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < NT; k++) {
+            if (!((mask & first) >> k & 1u)) continue;
+            if (MAY_BE_ABSENT && !row(key[k])) continue;
+            tab.slot(key[k]);
+        }
+    }
+    for (int c0 = 0; c0 < C; c0 += CH) {
+        const int nc = min(CH, C - c0);
+        tab.clear_acc(tid);
+        __syncthreads();
+        if (live) {
+            float gv[CH];
+#pragma unroll
+            for (int c = 0; c < CH; c++) gv[c] = c < nc ? g[s * C + c0 + c] : 0.0f;
+#pragma unroll
+            for (int k = 0; k < NT; k++) {
+                if (!((mask >> k) & 1u)) continue;
+                float* dst = row(key[k]);
+                if (MAY_BE_ABSENT && !dst) continue;
+                const int slot = tab.slot(key[k]);
+#pragma unroll
+                for (int c = 0; c < CH; c++) {
+                    if (c >= nc) continue;
+                    const float v = w[k] * gv[c];
+                    if (slot >= 0) tab.add(slot, c, v);
+                    else atomicAdd(dst + c0 + c, v);
+                }
+            }
+        }
+        __syncthreads();
+        tab.flush_by_slot(tid, [&](int k, int c, float v) {
+            if (c < nc) atomicAdd(row(k) + c0 + c, v);
+        });
+        __syncthreads();
+    }
+}
+
 // ---- host side ----
 
 // the fields every op's sizes struct has

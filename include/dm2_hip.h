@@ -375,6 +375,7 @@ int dm2_interpolate_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
 #define DM2_TEX_FILTER_LINEAR 1
 #define DM2_TEX_BOUNDARY_WRAP 0
 #define DM2_TEX_BOUNDARY_CLAMP 1
+#define DM2_TEX_BOUNDARY_CUBE 2 /* dm2_texture_mip and dm2_texture_mip_backward only: the cube's mip chain, see there */
 int dm2_texture(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
                 int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex, float* out,
                 void* stream);
@@ -512,6 +513,33 @@ int dm2_texture_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
                              int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv,
                              const float* uv_da, const float* tex, const float* mip, const float* dL_dout, float* dL_dtex,
                              float* dL_dmip, float* dL_duv, void* stream);
+/* boundary == DM2_TEX_BOUNDARY_CUBE: Renderer.texture(filter_mode="linear-mipmap-linear", boundary_mode="cube", mip_level=...),
+ * a cube map and its mip chain looked up by a direction and a level of detail per slot.  The arguments of the two entry
+ * points above then mean (a variant of the operation, so a value code and no symbol of its own):
+ *   Ht == Wt == N (anything else is refused); uv = dirs (B,H,W,L,3) as for dm2_texture_cube; uv_da = the level of detail
+ *   (B,H,W,L), one float per slot, level 0 being tex; tex (6,N,N,C) or, with view_textures, (B,6,N,N,C); mip (6,T,C) or
+ *   (B,6,T,C): per face the levels 1 .. nlev-1 in dm2_texture_mipmaps' layout for (N, N, max_mip_level), level k with faces of
+ *   N_k = N >> k (dm2_texture_mipmaps of the six faces as six textures gives the box chain; any chain of that shape is
+ *   accepted); 6 * (N * N + T) < 2^31; mip may be NULL when T == 0.
+ *   empty: the slot is empty by dm2_texture_cube's rules, or its level is not finite: out[s,:] = 0, nothing is read through it,
+ *     no gradient;
+ *   forward, lod = the slot's level, all fp32 in the written order: lod <= 0: level 0 alone (bit-equal to dm2_texture_cube
+ *     with DM2_TEX_FILTER_LINEAR); lod >= nlev - 1: the last level alone; otherwise j = (int)floorf(lod), f = lod - (float)j,
+ *       out[s,c] = c_j + f * (c_{j+1} - c_j)
+ *     c_k = dm2_texture_cube's linear sample of level k with N_k in place of N: the face and (sc, tc, ma), and with them
+ *     sn, tn, are computed once; X_k = sn * (float)N_k - 0.5f, Y_k alike; the seam rule and the three-tap corner blend apply at
+ *     that level's size.
+ *   backward, the derivative of that fp32 function at its own j, f, fractions, faces and addresses, with (m_j, m_{j+1}) =
+ *     (1 - f, f) (one level: weight 1 on it):
+ *     dL_dtex / dL_dmip[t_k of level k, c] += m_k * w * g[s,c], w as in dm2_texture_cube_backward (w / W at a corner; a missing
+ *       tap adds nothing): level 0's texels in dL_dtex, the others in dL_dmip; zero-filled by the caller; float atomics;
+ *     dL_duv is (B,H,W,L,4) = (dL/ddir.x, .y, .z, dL/dlevel), one 16-byte row per slot (16-byte aligned), every element written:
+ *       dL/ddir = m_j * ddir_j + m_{j+1} * ddir_{j+1}, ddir_k = dm2_texture_cube_backward's dL_ddir of level k with its N_k
+ *         factor; orthogonal to the direction;
+ *       dL/dlevel = sum_c g[s,c] * (c_{j+1,c} - c_{j,c}), the channels in order, where 0 < lod < nlev - 1 (at an integer lod
+ *         inside the range the right-hand derivative, j = lod); 0 where the level is clamped or the slot is empty;
+ *       a pure function of the inputs.
+ *   Any output pointer may be NULL, as above; dL_duv is produced when either the direction's or the level's gradient is wanted. */
 
 /* Renderer.composite: per-slot values (dm2_interpolate's or dm2_texture's output, or anything shaded from them) blended front
  * to back into an image: LayeredRenderer.render's blend with the colour supplied by the caller.
