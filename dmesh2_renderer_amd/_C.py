@@ -46,6 +46,11 @@ two C symbols under DM2_TEX_BOUNDARY_CUBE):
     texture_cube_mip_backward_cuda(...those 6..., grad_out, need_tex, need_mip, need_dirs, need_level)
         -> (dL/dtex, dL/dmip, dL/ddirs, dL/dlevel)
 
+and the GGX prefilter that turns a cube's box chain into a roughness chain (Renderer.cube_prefilter; dm2_texture_mipmaps and
+its backward under DM2_MIP_FILTER_CUBE_GGX):
+
+    cube_prefilter_cuda(chain, N, max_mip_level) -> filtered chain,  cube_prefilter_transpose_cuda(grad, N, max_mip_level) -> xbar
+
 and such per-slot values blended into an image (Renderer.composite; not composite_layers_cuda, which shades by itself):
 
     composite_cuda(values, alpha, render_layers, background) -> (out, acc, final_T, n_contrib),
@@ -1434,7 +1439,61 @@ def texture_cube_mip_backward_cuda(dirs, level, tex, mip, render_layers, max_mip
     return dtex, dmip, rows[..., :3].contiguous() if need_dirs else None, rows[..., 3].contiguous() if need_level else None
 
 
-COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1     # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*
+MIP_FILTER_CUBE_GGX = 0x40000000    # DM2_MIP_FILTER_CUBE_GGX: dm2_texture_mipmaps / dm2_texture_mipmaps_backward only
+
+
+def _cube_prefilter_args(chain, N, max_mip_level, what="chain"):
+    """Checks of a cube prefilter call -> (sizes (NB, N, N, C, the filter's code with the level limit), contiguous chain, device)."""
+    N = int(N)
+    _bad(N < 1, "N must be at least 1")
+    _bad(chain.dim() not in (3, 4), f"{what} must have dimensions (6, T, C) or (B, 6, T, C)")
+    _bad(int(chain.shape[-3]) != 6, f"{what}: a cube has six faces, got {int(chain.shape[-3])}")
+    _, _, T = mip_layout(N, N, max_mip_level)
+    _bad(6 * (N * N + T) >= 2 ** 31, "the texels of all levels of the cube must number below 2^31")
+    C = int(chain.shape[-1])
+    shape = tuple(chain.shape[:-3]) + (6, T, C)
+    _bad(tuple(chain.shape) != shape,
+        f"{what} must have dimensions {shape} for N {N} and max_mip_level {max_mip_level}, got {tuple(chain.shape)}")
+    _bad(C < 1, f"{what} must have at least one channel")
+    dev = _require_gpu(chain)
+    _bad(chain.dtype != torch.float32, f"{what}: expected dtype {torch.float32}, got {chain.dtype}")
+    limit = 0xFFFF if max_mip_level is None else min(int(max_mip_level), 0xFFFE)
+    NB = 6 * (int(chain.size(0)) if chain.dim() == 4 else 1)
+    _bad(NB > 65535, f"{what}: at most 10922 cubes in one call")
+    return (NB, N, N, C, MIP_FILTER_CUBE_GGX | limit), chain.contiguous(), dev
+
+
+def cube_prefilter_cuda(chain, N, max_mip_level=None):
+    """The GGX prefilter of a cube's mip chain, un-normalised (include/dm2_hip.h: dm2_texture_mipmaps with
+    DM2_MIP_FILTER_CUBE_GGX): chain (6,T,C) or (B,6,T,C) float32, per face the levels 1 .. nlev-1 in ``mip_layout(N, N,
+    max_mip_level)``'s packing -> the same shape: level k filtered from level k with the lobe of roughness k / (nlev - 1),
+    y[o] = sum_s K(o,s) Om_s x[s].  A gather: deterministic; T = 0 launches nothing."""
+    lib = load_library()
+    sizes, x, dev = _cube_prefilter_args(chain, N, max_mip_level)
+    y = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)        # (every element written by the kernel)
+    if y.numel() == 0:
+        return y
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mipmaps(*sizes, _ptr(x), _ptr(y), _stream(dev)):
+            raise _err(lib, "cube_prefilter_cuda")
+    return y
+
+
+def cube_prefilter_transpose_cuda(grad, N, max_mip_level=None):
+    """The transpose of cube_prefilter_cuda (dm2_texture_mipmaps_backward with DM2_MIP_FILTER_CUBE_GGX): grad of the chain's
+    shape -> xbar[s] = Om_s sum_o K(o,s) grad[o], the same shape.  A gather as well: deterministic."""
+    lib = load_library()
+    sizes, g, dev = _cube_prefilter_args(grad, N, max_mip_level, "grad")
+    xbar = torch.empty(tuple(g.shape), dtype=torch.float32, device=dev)     # (every element written by the kernel)
+    if xbar.numel() == 0:
+        return xbar
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_mipmaps_backward(*sizes, _ptr(g), _ptr(xbar), _stream(dev)):
+            raise _err(lib, "cube_prefilter_transpose_cuda")
+    return xbar
+
+
+COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1    # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*
 
 
 def _composite_args(values, alpha, render_layers, background, n_contrib=None, grad_out=None, grad_acc=None):

@@ -22,7 +22,8 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   the pipeline), and ``Renderer.texture_mipmaps()``, the chain of 2 x 2 means (``MipmapFunction``); and cube-map lookup by
   direction for ``texture`` (``boundary_mode="cube"``, ``TextureCubeFunction``): filtered across the cube's edges and corners,
   and through the cube's mip chain at a level of detail per slot (``mip_level``, ``TextureCubeMipFunction``), which receives a
-  gradient: a glossy reflection whose roughness can be learned;
+  gradient: a glossy reflection whose roughness can be learned; with ``Renderer.cube_prefilter()``, the GGX prefilter that
+  makes that chain a roughness chain whose last level is the diffuse irradiance (``CubePrefilterFunction``, a gather both ways);
   and what produces those directions: ``Renderer.vertex_normals()``, smooth normals that carry a gradient to the vertices
   without float atomics (``VertexNormalsFunction``, over ``Renderer.vertex_adjacency()``'s index), and
   ``Renderer.shading_vectors()``, per-slot position, view, unit normal and reflection vectors from the pixel's own ray
@@ -48,7 +49,7 @@ from .pyrenderer import Triangles
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
            "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction", "BaryDerivativesFunction",
            "MipmapFunction", "TextureMipFunction", "TextureCubeFunction", "VertexNormalsFunction", "ShadingVectorsFunction",
-           "TextureCubeMipFunction"]
+           "TextureCubeMipFunction", "CubePrefilterFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -602,6 +603,44 @@ class Renderer(torch.nn.Module):
             return mip.reshape(tuple(tex.shape[:2]) + tuple(mip.shape[1:]))
         return MipmapFunction.apply(tex, max_mip_level)
 
+    @staticmethod
+    def cube_prefilter_norm(N: int, max_mip_level: int = None, device=None):
+        """The normalisation of ``cube_prefilter`` for cubes with faces of N x N under ``max_mip_level`` -> norm (6,T) float32:
+        per chain texel the lobe's weight sum W[o] = sum_s K(o,s) Om_s (the filter applied to a chain of ones).  It depends on
+        (N, max_mip_level) alone: build it once per cube size and pass it as ``cube_prefilter(..., norm=norm)``.  Nothing is
+        cached here."""
+        T = _C.mip_layout(N, N, max_mip_level)[2]
+        ones = torch.ones((6, T, 1), dtype=torch.float32, device=torch.device("cuda") if device is None else device)
+        return _C.cube_prefilter_cuda(ones, N, max_mip_level).reshape(6, T)
+
+    def cube_prefilter(self, tex: torch.Tensor, max_mip_level: int = None, norm: torch.Tensor = None):
+        """A cube map's roughness chain (not in the reference): tex (6,N,N,C) float32 or (B,6,N,N,C) -> mip (6,T,C) or
+        (B,6,T,C) float32 in ``_C.mip_layout(N, N, max_mip_level)``'s packing, ready for ``texture(dirs, tex, rl,
+        "linear-mipmap-linear", "cube", mip=mip, max_mip_level=max_mip_level, mip_level=roughness * (nlev - 1))``.
+
+        Level k >= 1 of nlev levels is level k of the box chain (``texture_mipmaps``) convolved over the whole sphere, across
+        the faces, with the GGX lobe of roughness r = k / (nlev - 1) (a = r^2; the split-sum lobe D(n.h) (n.l) with n = v = r,
+        weighted by each texel's solid angle) and divided by the lobe's weight sum ``norm``: a constant cube stays constant.
+        Level 0, the mirror, is ``tex`` itself.  The lobe is cut where it has fallen below 1/4096 of its peak (at most 1/64 of
+        its mass; only below r = 0.298); at r = 1 it is the cosine lobe, so the last level of a full chain is the diffuse
+        irradiance map over pi.  The contract is in include/dm2_hip.h under DM2_MIP_FILTER_CUBE_GGX.
+
+        ``norm``: ``cube_prefilter_norm(N, max_mip_level)``, (6,T); None builds it in this call.  An odd N gives T = 0 and an
+        empty chain.  Differentiable w.r.t. ``tex`` (``CubePrefilterFunction`` on top of ``MipmapFunction``): the backward is
+        the filter's transpose, a gather like the forward, so both are deterministic and free of float atomics."""
+        tex = tex.to(torch.float32)
+        if tex.dim() not in (4, 5) or tex.shape[-4] != 6 or tex.shape[-3] != tex.shape[-2]:
+            raise RuntimeError(f"cube_prefilter: tex must have dimensions (6, N, N, C) or (B, 6, N, N, C), got {tuple(tex.shape)}")
+        N = int(tex.shape[-2])
+        T = _C.mip_layout(N, N, max_mip_level)[2]
+        if norm is None:
+            norm = Renderer.cube_prefilter_norm(N, max_mip_level, tex.device)
+        elif tuple(norm.shape) != (6, T):
+            raise RuntimeError(f"cube_prefilter: norm must have dimensions {(6, T)} for N {N} and max_mip_level {max_mip_level}, "
+                               f"got {tuple(norm.shape)}")
+        chain = Renderer.texture_mipmaps(self, tex, max_mip_level)
+        return CubePrefilterFunction.apply(chain, N, max_mip_level) / norm.to(torch.float32).unsqueeze(-1)
+
     def bary_derivatives(self, batch_mvp_idx: Sequence[int], render_layers: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor,
                          patch_min: torch.Tensor = None):
         """The footprint of a pixel on each listed face (not in the reference): render_layers (B,H,W,L) int32 face ids (as
@@ -1041,6 +1080,26 @@ class MipmapFunction(torch.autograd.Function):
             return None, None
         (tex,) = ctx.saved_tensors
         return _C.texture_mipmaps_backward_cuda(tex, ctx.max_mip_level, grad_mip), None
+
+
+class CubePrefilterFunction(torch.autograd.Function):
+    """out = the GGX prefilter of a cube's mip chain, un-normalised (``_C.cube_prefilter_cuda``): level k convolved with the
+    lobe of roughness k / (nlev - 1), out[o] = sum_s K(o,s) Om_s chain[s].
+
+    Inputs: chain (6,T,C)* or (B,6,T,C)*, N, max_mip_level (int or None).  Output: the same shape.  (* = receives a gradient.)
+    The filter is linear and K symmetric: dL/dchain[s] = Om_s sum_o K(o,s) g[o] (``_C.cube_prefilter_transpose_cuda``), a
+    gather like the forward, deterministic."""
+
+    @staticmethod
+    def forward(ctx, chain, N, max_mip_level):
+        ctx.sizes = (N, max_mip_level)
+        return _C.cube_prefilter_cuda(chain.detach(), N, max_mip_level)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if grad_out is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        return _C.cube_prefilter_transpose_cuda(grad_out, *ctx.sizes), None, None
 
 
 class TextureMipFunction(torch.autograd.Function):

@@ -723,9 +723,40 @@ static int check_mip_sizes(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_
     return 0;
 }
 
+// max_mip_level carries DM2_MIP_FILTER_CUBE_GGX: the GGX prefilter of NB / 6 cubes' chains (*cubes), each (6,T,C); *max_level:
+// the level limit the code holds (-1: none)
+static int check_cube_prefilter(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t code, int* cubes, int* max_level, int64_t* T) {
+    if (code & ~(DM2_MIP_FILTER_CUBE_GGX | 0xFFFF)) return fail("texture_mipmaps: unknown bits in max_mip_level's filter code");
+    if (NB < 0 || NB > 65535) return fail("texture_mipmaps: the number of textures must lie in [0, 65535]");
+    if (NB % 6) return fail("texture_mipmaps: the cube filter takes six faces per cube (NB must be a multiple of 6)");
+    if (Ht < 1 || Wt < 1) return fail("texture_mipmaps: Ht and Wt must be at least 1");
+    if (Ht != Wt) return fail("texture_mipmaps: a cube's faces must be square (Ht == Wt)");
+    if (C < 1 || C > dm2::cube_prefilter_max_channels()) return fail("texture_mipmaps: the cube filter takes 1 to 262140 channels");
+    *cubes = NB / 6;
+    *max_level = (code & 0xFFFF) == 0xFFFF ? -1 : (code & 0xFFFF);
+    dm2::mip_levels(Ht, Wt, *max_level, T);
+    if (6 * ((int64_t)Ht * Wt + *T) > 0x7FFFFFFF) return fail("texture_mipmaps: the texels of all levels of the cube must number below 2^31");
+    return 0;
+}
+
+// both directions of the filter: x (NB,T,C) -> y (NB,T,C)
+static int cube_prefilter(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t code, int transpose, const float* x, float* y,
+                          void* stream) {
+    int cubes, max_level;
+    int64_t T;
+    if (check_cube_prefilter(NB, Ht, Wt, C, code, &cubes, &max_level, &T)) return 1;
+    if (cubes == 0 || T == 0) return 0;
+    if (!x || !y) return fail("texture_mipmaps: the cube filter's input and output chains must not be null");
+    dm2::launch_cube_prefilter(cubes, Ht, C, max_level, transpose, x, y, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* tex, float* mip,
                         void* stream) {
     int64_t T;
+    if (max_mip_level >= 0 && (max_mip_level & DM2_MIP_FILTER_CUBE_GGX))
+        return cube_prefilter(NB, Ht, Wt, C, max_mip_level, 0, tex, mip, stream);
     if (check_mip_sizes(NB, Ht, Wt, C, max_mip_level, &T)) return 1;
     if (NB == 0 || T == 0) return 0;
     if (!tex || !mip) return fail("texture_mipmaps: tex and mip must not be null");
@@ -737,6 +768,8 @@ int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t m
 int dm2_texture_mipmaps_backward(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* dL_dmip,
                                  float* dL_dtex, void* stream) {
     int64_t T;
+    if (max_mip_level >= 0 && (max_mip_level & DM2_MIP_FILTER_CUBE_GGX))
+        return cube_prefilter(NB, Ht, Wt, C, max_mip_level, 1, dL_dmip, dL_dtex, stream);
     if (check_mip_sizes(NB, Ht, Wt, C, max_mip_level, &T)) return 1;
     if (NB == 0) return 0;
     if (!dL_dtex) return fail("texture_mipmaps_backward: dL_dtex must not be null");

@@ -326,6 +326,11 @@ void launch_texture_cube_mip_backward(int B, int H, int W, int L, int N, int C, 
                                       const int32_t* render_layers, const float* dirs, const float* level, const float* tex,
                                       const float* mip, const float* dL_dout, float* dL_dtex, float* dL_dmip, float* dL_ddir_level,
                                       hipStream_t st);
+// Renderer.cube_prefilter (dm2_cube_prefilter.hip): the GGX prefilter of ``cubes`` chains x (cubes, 6, T, C) of mip_levels(N, N,
+// max_level) into y of the same shape, level by level (transpose != 0: its transpose); every element of y is written, no
+// atomics.  cubes > 0, T > 0, C in [1, cube_prefilter_max_channels()], 6 (N N + T) < 2^31.
+int cube_prefilter_max_channels();
+void launch_cube_prefilter(int cubes, int N, int C, int max_level, int transpose, const float* x, float* y, hipStream_t st);
 
 }  // namespace dm2
 

@@ -479,6 +479,28 @@ int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t m
  * a gather: no atomics, a pure function of the inputs (zeros when nlev == 1). */
 int dm2_texture_mipmaps_backward(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* dL_dmip,
                                  float* dL_dtex, void* stream);
+/* max_mip_level >= 0 with DM2_MIP_FILTER_CUBE_GGX set: Renderer.cube_prefilter, the GGX prefilter of cube mip chains (a variant
+ * of building a chain, so a value code and no symbol of its own; every other max_mip_level keeps its meaning).  The arguments of
+ * the two entry points above then mean:
+ *   the level limit is max_mip_level & 0xFFFF (0xFFFF: none), any other bit is refused; Ht == Wt == N (anything else is refused);
+ *   NB is a multiple of 6 and six consecutive textures are one cube's faces (+x, -x, +y, -y, +z, -z, dm2_texture_cube's face
+ *   coordinates); forward: tex = the input chain x (NB,T,C), mip = y (NB,T,C); backward: dL_dmip = ybar (NB,T,C), dL_dtex =
+ *   xbar (NB,T,C); T, nlev and the packing as above for (N, N, limit); T == 0: nothing runs; 6 * (N * N + T) < 2^31; C <= 262140.
+ * Texel (face, j, i) of a level with faces of n x n, all fp32, separate multiplies and adds in the written order:
+ *   sc = (2 (i + 0.5)) / n - 1,  tc = (2 (j + 0.5)) / n - 1,  p = the cube point of (face, sc, tc) (the inverse of the lookup's table)
+ *   q = (1 + sc sc) + tc tc,  rq = sqrtf(q),  d = p / rq per component,  Om = 1 / (q rq)   (the solid angle up to 4 / n^2)
+ * Level k >= 1 (n = N >> k) has roughness r = (float)k / (float)(nlev - 1), a = r r, a2 = a a.  For texels o, s of that level:
+ *   m = ((d_o.x - d_s.x)^2 + (d_o.y - d_s.y)^2) + (d_o.z - d_s.z)^2          (= 2 (1 - cos))
+ *   c = 1 - 0.5 m,   e = a2 + (1 - a2) (0.25 m)                               (0.25 m = sin^2 of the half angle)
+ *   member: c > 0 and e <= 64 a2;   K(o,s) = ((a2 / e) (a2 / e)) c for a member, 0 otherwise
+ * K = D(n.h) (n.l) of the split-sum GGX lobe with n = v = r, scaled to peak 1; symmetric in (o, s) to the bit; a texel is its
+ * own member.  The cut drops the lobe below 1/4096 of its peak, at most 1/64 of the distribution's mass (its CDF is
+ * a2 cos^2 / e); for a2 >= 1/127 it never bites, and at r = 1 K = c on the open hemisphere: the cosine lobe.  Each level is
+ * filtered from the same level of the input, un-normalised:
+ *   forward:   y[o,ch] = sum_s (K(o,s) Om_s) x[s,ch]          backward (the transpose): xbar[s,ch] = Om_s sum_o K(o,s) ybar[o,ch]
+ * Both are gathers: every element is written, no atomics, a pure function of the inputs.  The order of the sums is the
+ * kernel's own: against the sums in float64 an element with mem members is held to (mem + 4) 2^-24 sum |K Om x|. */
+#define DM2_MIP_FILTER_CUBE_GGX 0x40000000
 
 /* Renderer.texture(filter_mode="linear-mipmap-linear"): trilinear sampling.  uv, tex, render_layers, out, view_textures and
  * boundary as for dm2_texture; uv_da (B,H,W,L,4) float32 = (du/dX, dv/dX, du/dY, dv/dY), the UV footprint of the slot's pixel
