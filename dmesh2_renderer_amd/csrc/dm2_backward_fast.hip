@@ -301,8 +301,9 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
         float i0 = 0.f, i1 = 0.f, i2 = 0.f, ratio = 0.f, alpha = 0.f;
         int code = 0;
         bool blend = false;
-        // carried from B2 into phase D in registers (phase C in between needs few): ray, world corners, colours, NDC z
-        f3 k_ro = {0, 0, 0}, k_rd = {0, 0, 0}, k_p0 = {0, 0, 0}, k_p1 = {0, 0, 0}, k_p2 = {0, 0, 0};
+        // carried from B2 into phase D in registers (phase C in between needs few): ray direction and the edge vectors B2's
+        // intersection formed (T = ro - p0, E1 = p1 - p0, E2 = p2 - p0: all the chain rule reads of ray and corners), colours, NDC z
+        f3 k_rd = {0, 0, 0}, k_T = {0, 0, 0}, k_E1 = {0, 0, 0}, k_E2 = {0, 0, 0};
         float k_col[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, k_dep[3] = {0, 0, 0}, k_int = 0.f, k_opa = 0.f;
         if (have) {
             const int lo = (int)(mk >> 9) - 1;                                    // the slot of pair tid, first pair mk & 511
@@ -335,11 +336,11 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
             const f3 rd = {s_ray[q * 6 + 3], s_ray[q * 6 + 4], s_ray[q * 6 + 5]};
             const f3 p0 = {fc.v[0], fc.v[1], fc.v[2]}, p1 = {fc.v[3], fc.v[4], fc.v[5]}, p2 = {fc.v[6], fc.v[7], fc.v[8]};
             f3 tuv = {0, 0, 0};
-            k_ro = ro; k_rd = rd; k_p0 = p0; k_p1 = p1; k_p2 = p2;
+            k_rd = rd; k_T = ro - p0; k_E1 = p1 - p0; k_E2 = p2 - p0;
 #pragma unroll
             for (int c = 0; c < 9; c++) k_col[c] = fc.col[c];
             k_dep[0] = fc.dep[0]; k_dep[1] = fc.dep[1]; k_dep[2] = fc.dep[2]; k_int = fc.intense; k_opa = fc.opacity;
-            if (ray_tri_intersection(ro, rd, p0, p1, p2, tuv)) {
+            if (ray_tri_intersection_edges(rd, k_T, k_E1, k_E2, tuv)) {
                 float iuc, ivc;
                 clamp_bary_uv_chain(tuv.y, tuv.z, iuc, ivc, code);             // (the chain: see dm2_device_math.h)
                 i0 = 1 - iuc - ivc; i1 = iuc; i2 = ivc;
@@ -462,7 +463,7 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                 } else {
                     float bg_dot = 0.f;
                     bg_dot += bg0 * qc0; bg_dot += bg1 * qc1; bg_dot += bg2 * qc2;
-                    const float bd_dot = (float)(0.0 + 1.0 * (double)qd);          // backward.cu:394
+                    const float bd_dot = qd;                                       // backward.cu:394: 0.0 + 1.0 * dL/ddepth
                     if (alpha_is_one) {
                         dL_dalpha += (-prev_T_final) * bg_dot;
                         dL_dalpha += (-prev_T_final) * bd_dot;
@@ -498,26 +499,30 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
                     const float dL_dratio = (dL_dalpha * opacity) * temp;
                     dL_doarea = dL_dratio / pix_area;
                     float dL_di0 = 0.f, dL_di1 = 0.f, dL_di2 = 0.f, dL_dfint = 0.f;
-#pragma unroll
-                    for (int ch = 0; ch < 3; ch++) {
-                        dL_di0 += colD[ch] * dics[ch] * intense;
-                        dL_di1 += colD[3 + ch] * dics[ch] * intense;
-                        dL_di2 += colD[6 + ch] * dics[ch] * intense;
-                        g1[ch] = 0.f + i0 * dics[ch] * intense;
-                        g1[3 + ch] = 0.f + i1 * dics[ch] * intense;
-                        g1[6 + ch] = 0.f + i2 * dics[ch] * intense;
-                        dL_dfint += (i0 * colD[ch] + i1 * colD[3 + ch] + i2 * colD[6 + ch]) * dics[ch];
-                    }
+                    // (backward.cu:408-488 with the factors that are 0 or 1 taken out and dL/dcolour * intensity formed once
+                    // per channel: the same sums in another order, for gradients that owe the reference 1e-5.  The intensity
+                    // gradient first, the twelve outputs last: dics dies into dci and the colours into dL/di before the outputs
+                    // take their registers -- outputs first costs the POOL instantiations two spilled VGPRs)
+                    auto fint = [&](int ch) { return (i0 * colD[ch] + i1 * colD[3 + ch] + i2 * colD[6 + ch]) * dics[ch]; };
+                    dL_dfint = (fint(0) + fint(1)) + fint(2);
                     g1[13] = dL_dfint;
-                    dL_di0 += depD[0] * did; dL_di1 += depD[1] * did; dL_di2 += depD[2] * did;
-                    g1[9] = 0.f + i0 * did; g1[10] = 0.f + i1 * did; g1[11] = 0.f + i2 * did;
+                    const float dci[3] = {dics[0] * intense, dics[1] * intense, dics[2] * intense};
+                    dL_di0 = ((colD[0] * dci[0] + colD[1] * dci[1]) + colD[2] * dci[2]) + depD[0] * did;
+                    dL_di1 = ((colD[3] * dci[0] + colD[4] * dci[1]) + colD[5] * dci[2]) + depD[1] * did;
+                    dL_di2 = ((colD[6] * dci[0] + colD[7] * dci[1]) + colD[8] * dci[2]) + depD[2] * did;
                     float diuc_diu, diuc_div, divc_diu, divc_div;
                     clamp_bary_uv_grad(code, diuc_diu, diuc_div, divc_diu, divc_div);
-                    const float di0_diu = -1.f * diuc_diu + -1.f * divc_diu, di0_div = -1.f * diuc_div + -1.f * divc_div;
-                    const float di1_diu = 1.f * diuc_diu + 0.f * divc_diu, di1_div = 1.f * diuc_div + 0.f * divc_div;
-                    const float di2_diu = 0.f * diuc_diu + 1.f * divc_diu, di2_div = 0.f * diuc_div + 1.f * divc_div;
-                    dL_diu = dL_di0 * di0_diu + dL_di1 * di1_diu + dL_di2 * di2_diu;
-                    dL_div = dL_di0 * di0_div + dL_di1 * di1_div + dL_di2 * di2_div;
+                    // i0 = 1 - iuc - ivc, i1 = iuc, i2 = ivc
+                    const float d10 = dL_di1 - dL_di0, d20 = dL_di2 - dL_di0;
+                    dL_diu = diuc_diu * d10 + divc_diu * d20;
+                    dL_div = diuc_div * d10 + divc_div * d20;
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) {
+                        g1[ch] = i0 * dci[ch];
+                        g1[3 + ch] = i1 * dci[ch];
+                        g1[6 + ch] = i2 * dci[ch];
+                    }
+                    g1[9] = i0 * did; g1[10] = i1 * did; g1[11] = i2 * did;
                 }
                 run_sums(g1);
                 if (emit_add) {
@@ -599,9 +604,8 @@ k_render_backward_fast(dm2_render_desc d, const uint2* __restrict__ ranges, cons
 #pragma unroll
                 for (int c = 0; c < 9; c++) g3[c] = 0.f;
                 if (active) {
-                    const f3 ro = k_ro, rd = k_rd, p0 = k_p0, p1 = k_p1, p2 = k_p2;
                     f3 du0, du1, du2, dv0, dv1, dv2;
-                    ray_tri_intersection_grad<true>(ro, rd, p0, p1, p2, corrected, du0, du1, du2, dv0, dv1, dv2);
+                    ray_tri_intersection_grad_edges<true>(k_rd, k_T, k_E1, k_E2, corrected, du0, du1, du2, dv0, dv1, dv2);
                     const f3 dp0 = dL_diu * du0 + dL_div * dv0;
                     const f3 dp1 = dL_diu * du1 + dL_div * dv1;
                     const f3 dp2 = dL_diu * du2 + dL_div * dv2;

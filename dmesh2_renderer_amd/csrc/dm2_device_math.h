@@ -57,6 +57,19 @@ __device__ __forceinline__ void analytic_ray(const float* __restrict__ cam, floa
 }
 
 // ---- Moeller-Trumbore without inside test (auxiliary.h:212-243) -------------
+// From the edge vectors T = ro - p0, E1 = p1 - p0, E2 = p2 - p0, for a caller that keeps them (k_render_backward_fast hands
+// them to its chain rule): the operations of ray_tri_intersection below, in its order.
+__device__ __forceinline__ bool ray_tri_intersection_edges(f3 rd, f3 T, f3 E1, f3 E2, f3& tuv) {
+    f3 P = cross(rd, E2), Q = cross(T, E1);
+    float denom = dot(P, E1);
+    if (denom == 0.0f) return false;
+    float inv_denom = 1.0f / denom;
+    tuv.x = dot(Q, E2) * inv_denom;
+    tuv.y = dot(P, T) * inv_denom;
+    tuv.z = dot(Q, rd) * inv_denom;
+    return true;
+}
+
 __device__ __forceinline__ bool ray_tri_intersection(f3 ro, f3 rd, f3 p0, f3 p1, f3 p2, f3& tuv) {
     f3 T = ro - p0, E1 = p1 - p0, E2 = p2 - p0;
     f3 P = cross(rd, E2), Q = cross(T, E1);
@@ -91,11 +104,11 @@ __device__ __forceinline__ float rcp_refined(float x) {
     return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
 }
 
+// (from the edge vectors T = ro - p0, E1 = p1 - p0, E2 = p2 - p0; the corner form below forms them and calls this)
 template <bool FAST_RCP = false>
-__device__ __forceinline__ void ray_tri_intersection_grad(f3 ro, f3 rd, f3 p0, f3 p1, f3 p2, bool corrected,
-                                                          f3& du_dp0, f3& du_dp1, f3& du_dp2,
-                                                          f3& dv_dp0, f3& dv_dp1, f3& dv_dp2) {
-    f3 T = ro - p0, E1 = p1 - p0, E2 = p2 - p0;
+__device__ __forceinline__ void ray_tri_intersection_grad_edges(f3 rd, f3 T, f3 E1, f3 E2, bool corrected,
+                                                                f3& du_dp0, f3& du_dp1, f3& du_dp2,
+                                                                f3& dv_dp0, f3& dv_dp1, f3& dv_dp2) {
     f3 dxE2 = cross(rd, E2);
     float denom_sqrt = dot(dxE2, E1);
     float denom = denom_sqrt * denom_sqrt;
@@ -122,6 +135,13 @@ __device__ __forceinline__ void ray_tri_intersection_grad(f3 ro, f3 rd, f3 p0, f
     dv_dp0 = -dv_dE1 - dv_dE2 - dv_dT;
     du_dp1 = du_dE1; dv_dp1 = dv_dE1;
     du_dp2 = du_dE2; dv_dp2 = dv_dE2;
+}
+
+template <bool FAST_RCP = false>
+__device__ __forceinline__ void ray_tri_intersection_grad(f3 ro, f3 rd, f3 p0, f3 p1, f3 p2, bool corrected,
+                                                          f3& du_dp0, f3& du_dp1, f3& du_dp2,
+                                                          f3& dv_dp0, f3& dv_dp1, f3& dv_dp2) {
+    ray_tri_intersection_grad_edges<FAST_RCP>(rd, ro - p0, p1 - p0, p2 - p0, corrected, du_dp0, du_dp1, du_dp2, dv_dp0, dv_dp1, dv_dp2);
 }
 
 // ---- auxiliary.h:292-329 ------------------------------------------------------
