@@ -32,6 +32,11 @@ and a cube map looked up by such an image of directions (Renderer.texture's boun
     texture_cube_cuda(dirs, tex, render_layers, filter_mode) -> out,
     texture_cube_backward_cuda(...those 4..., grad_out, need_tex, need_dirs) -> (dL/dtex, dL/ddirs)
 
+and a voxel grid looked up by such an image of positions (Renderer.texture3d; the same two C symbols under DM2_TEX_VOLUME_*):
+
+    texture_volume_cuda(xyz, grid, render_layers, filter_mode, boundary_mode) -> out,
+    texture_volume_backward_cuda(...those 5..., grad_out, need_grid, need_xyz) -> (dL/dgrid, dL/dxyz)
+
 and its mip-mapped filter (Renderer.bary_derivatives, Renderer.texture_mipmaps, texture's "linear-mipmap-linear"):
 
     bary_derivatives_cuda(render_layers, verts, faces, ray_cam) -> (dbary_dx, dbary_dy),
@@ -1075,6 +1080,75 @@ def texture_cube_backward_cuda(dirs, tex, render_layers, filter_mode, grad_out, 
         if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(dc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(ddir), _stream(dev)):
             raise _err(lib, "texture_cube_backward_cuda")
     return dtex, ddir
+
+
+TEX_VOLUME_BOUNDARIES = {"clamp": 0x100, "wrap": 0x200}      # DM2_TEX_VOLUME_*: OR-ed into dm2_texture_cube's filter
+
+
+def _texture_volume_args(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out=None):
+    """Checks of a volume call -> (sizes (B, H, W, L, N, C, view_textures, filter | volume bit), contiguous tensors, device)."""
+    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
+    _bad(boundary_mode not in TEX_VOLUME_BOUNDARIES,
+         f"boundary_mode must be one of {sorted(TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
+    _bad(xyz.dim() != 5 or xyz.size(4) != 3, f"xyz must have dimensions (B, H, W, L, 3), got {tuple(xyz.shape)}")
+    B, H, W, L = (int(x) for x in xyz.shape[:4])
+    _bad(grid.dim() not in (4, 5), "grid must have dimensions (N, N, N, C) or (B, N, N, N, C)")
+    _bad(grid.dim() == 5 and grid.size(0) != B, f"grid must have dimensions (N, N, N, C) or ({B}, N, N, N, C), got {tuple(grid.shape)}")
+    Nk, Nj, N, C = (int(x) for x in grid.shape[-4:])
+    _bad(Nk != N or Nj != N, f"grid must be a cube, (N, N, N, C) or ({B}, N, N, N, C), got {tuple(grid.shape)}")
+    _bad(N < 1, "grid must have at least one voxel")
+    _bad(C < 1, "grid must have at least one channel")
+    _bad(N * N * N >= 2 ** 31, "grid: N * N * N must be below 2^31")
+    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
+    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
+        f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
+    dev = _require_gpu(*[t for t in (xyz, grid, render_layers, grad_out) if t is not None])
+    f32, i32 = torch.float32, torch.int32
+    named = (("xyz", xyz, f32), ("grid", grid, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
+    ts = []
+    for name, t, dt in named:
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    code = TEX_FILTERS[filter_mode] | TEX_VOLUME_BOUNDARIES[boundary_mode]
+    return (B, H, W, L, N, C, 1 if grid.dim() == 5 else 0, code), ts, dev
+
+
+def texture_volume_cuda(xyz, grid, render_layers=None, filter_mode="linear", boundary_mode="clamp"):
+    """A voxel grid looked up by per-slot positions (include/dm2_hip.h: dm2_texture_cube with DM2_TEX_VOLUME_*).
+
+    xyz (B,H,W,L,3) float32 in the grid's unit cube (x along the grid's last spatial axis), grid (N,N,N,C) or (B,N,N,N,C)
+    float32 channel-last, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is negative or a
+    coordinate is not finite (or beyond 2^24 voxels)."""
+    lib = load_library()
+    sizes, (pc, gr, rl, _), dev = _texture_volume_args(xyz, grid, render_layers, filter_mode, boundary_mode)
+    B, H, W, L, C = *sizes[:4], sizes[5]
+    if B * H * W * L == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_cube(*sizes, _ptr(rl), _ptr(pc), _ptr(gr), _ptr(out), _stream(dev)):
+            raise _err(lib, "texture_volume_cuda")
+    return out
+
+
+def texture_volume_backward_cuda(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out, need_grid, need_xyz):
+    """Gradients of texture_volume_cuda (dm2_texture_cube_backward with DM2_TEX_VOLUME_*) -> (dL_dgrid of grid's shape or None,
+    dL_dxyz (B,H,W,L,3) or None): only what ``need_grid`` / ``need_xyz`` ask for is computed."""
+    lib = load_library()
+    sizes, (pc, gr, rl, go), dev = _texture_volume_args(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out)
+    B, H, W, L = sizes[:4]
+    f32 = torch.float32
+    if not (need_grid or need_xyz):
+        return None, None
+    dgrid = torch.zeros(tuple(grid.shape), dtype=f32, device=dev) if need_grid else None
+    if B * H * W * L == 0:
+        return dgrid, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None
+    dxyz = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None      # (every element written)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(pc), _ptr(gr), _ptr(go), _ptr(dgrid), _ptr(dxyz), _stream(dev)):
+            raise _err(lib, "texture_volume_backward_cuda")
+    return dgrid, dxyz
 
 
 def _vertex_normals_args(verts, faces, offsets, corners, normals=None, lens=None, grad_normals=None):

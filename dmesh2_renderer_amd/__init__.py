@@ -27,7 +27,9 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   and what produces those directions: ``Renderer.vertex_normals()``, smooth normals that carry a gradient to the vertices
   without float atomics (``VertexNormalsFunction``, over ``Renderer.vertex_adjacency()``'s index), and
   ``Renderer.shading_vectors()``, per-slot position, view, unit normal and reflection vectors from the pixel's own ray
-  (``ShadingVectorsFunction``)
+  (``ShadingVectorsFunction``); and ``Renderer.texture3d()``: a voxel grid of colours or features looked up at that position
+  (trilinear or nearest, clamp or wrap), differentiable w.r.t. the grid and the position (``TextureVolumeFunction``): the
+  appearance model that needs no UV table
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -49,7 +51,7 @@ from .pyrenderer import Triangles
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
            "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction", "BaryDerivativesFunction",
            "MipmapFunction", "TextureMipFunction", "TextureCubeFunction", "VertexNormalsFunction", "ShadingVectorsFunction",
-           "TextureCubeMipFunction", "CubePrefilterFunction"]
+           "TextureCubeMipFunction", "CubePrefilterFunction", "TextureVolumeFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -586,6 +588,29 @@ class Renderer(torch.nn.Module):
             raise ValueError('uv_da and mip belong to filter_mode "linear-mipmap-linear"')
         return TextureFunction.apply(uv.to(f32), tex.to(f32), rl, filter_mode, boundary_mode)
 
+    def texture3d(self, xyz: torch.Tensor, grid: torch.Tensor, render_layers: torch.Tensor = None, filter_mode: str = "linear",
+                  boundary_mode: str = "clamp"):
+        """A voxel grid looked up at per-slot positions (not in the reference): an appearance field over space, which needs no
+        UV table and so follows a mesh whose connectivity changes.  xyz (B,H,W,L,3) float32 = the position in the grid's unit
+        cube, x along the grid's last spatial axis and z along its first (``(position - lo) / (hi - lo)`` of
+        ``shading_vectors``' position for a grid over the box [lo, hi]), grid (N,N,N,C) float32 shared by the views or
+        (B,N,N,N,C) one grid per view, channel-last, indexed [k][j][i], any C >= 1, render_layers (B,H,W,L) int32 or None
+        -> out (B,H,W,L,C) float32.  Voxel centres sit at ((i + 0.5) / N, (j + 0.5) / N, (k + 0.5) / N); ``filter_mode``
+        "linear" (trilinear) or "nearest", ``boundary_mode`` "clamp" or "wrap" (repeat).
+
+        A slot with ``render_layers`` < 0 (None: no slot, by id), or with a coordinate that is not finite, is empty: zeros
+        out, nothing read from the grid through it (the zeros ``shading_vectors`` writes into its empty slots never reach voxel
+        (0, 0, 0)), no gradient.  Differentiable w.r.t. ``grid`` and ``xyz`` (``TextureVolumeFunction``); through ``xyz``,
+        ``shading_vectors``' and ``rasterize``'s backwards carry the gradient on to ``verts``.  ValueError for an unknown
+        mode."""
+        if filter_mode not in _C.TEX_FILTERS:
+            raise ValueError(f"filter_mode must be one of {sorted(_C.TEX_FILTERS)}, got {filter_mode!r}")
+        if boundary_mode not in _C.TEX_VOLUME_BOUNDARIES:
+            raise ValueError(f"boundary_mode must be one of {sorted(_C.TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
+        i32, f32 = torch.int32, torch.float32
+        rl = None if render_layers is None else render_layers.to(i32)
+        return TextureVolumeFunction.apply(xyz.to(f32), grid.to(f32), rl, filter_mode, boundary_mode)
+
     def texture_mipmaps(self, tex: torch.Tensor, max_mip_level: int = None):
         """The mip chain of a texture (not in the reference): tex (Ht,Wt,C) float32 or (B,Ht,Wt,C) -> mip (T,C) or (B,T,C)
         float32.  Level 0 is ``tex`` itself and is not copied; level k+1 exists while both extents of level k are even and
@@ -1040,6 +1065,33 @@ class TextureCubeFunction(torch.autograd.Function):
         dirs, tex, render_layers = _saved_optional(ctx)
         dtex, ddir = _C.texture_cube_backward_cuda(dirs, tex, render_layers, ctx.filter_mode, grad_out, need_tex, need_dirs)
         return ddir, dtex, None, None
+
+
+class TextureVolumeFunction(torch.autograd.Function):
+    """out = the voxel grid at each slot's position (``_C.texture_volume_cuda``): trilinear a0 + fz (a1 - a0) over the bilinear
+    blends of the two planes round (x N - 0.5, y N - 0.5, z N - 0.5), or the nearest voxel; clamp or wrap addressing.
+
+    Inputs: xyz (B,H,W,L,3)*, grid (N,N,N,C)* or (B,N,N,N,C)*, render_layers (B,H,W,L) int32 or None, filter_mode,
+    boundary_mode.  Output: out (B,H,W,L,C).  (* = receives a gradient.)  A non-empty slot sends w_pqr g to its eight voxels and
+    the grid's finite differences . g to (x, y, z) (zeros for nearest); empty slots send nothing and get zero.  Only the
+    gradients ``needs_input_grad`` asks for are computed: no voxel scatter when only xyz requires grad, and the reverse.
+    """
+
+    @staticmethod
+    def forward(ctx, xyz, grid, render_layers, filter_mode, boundary_mode):
+        out = _C.texture_volume_cuda(xyz.detach(), grid.detach(), render_layers, filter_mode, boundary_mode)
+        ctx.modes = (filter_mode, boundary_mode)
+        _save_optional(ctx, xyz.detach(), grid.detach(), render_layers)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_xyz, need_grid = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_out is None or not (need_xyz or need_grid):
+            return None, None, None, None, None
+        xyz, grid, render_layers = _saved_optional(ctx)
+        dgrid, dxyz = _C.texture_volume_backward_cuda(xyz, grid, render_layers, *ctx.modes, grad_out, need_grid, need_xyz)
+        return dxyz, dgrid, None, None, None
 
 
 class BaryDerivativesFunction(torch.autograd.Function):

@@ -574,8 +574,53 @@ static int check_texture_cube_sizes(int32_t B, int32_t H, int32_t W, int32_t L, 
     return 0;
 }
 
+// filter carries DM2_TEX_VOLUME_CLAMP or DM2_TEX_VOLUME_WRAP: Renderer.texture3d, a voxel grid looked up by positions.
+// *vfilter, *vboundary: the DM2_TEX_FILTER_* and DM2_TEX_BOUNDARY_* of the call.
+static int check_texture_volume_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t filter, int* vfilter,
+                                      int* vboundary) {
+    const int32_t vol = filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP);
+    if (vol == (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP)) return fail("texture_cube: a volume takes one boundary, clamp or wrap");
+    *vfilter = filter & ~vol;
+    *vboundary = vol == DM2_TEX_VOLUME_WRAP ? DM2_TEX_BOUNDARY_WRAP : DM2_TEX_BOUNDARY_CLAMP;
+    if (N > 1290) return fail("texture_cube: a volume's N * N * N must be below 2^31");      // 1290^3 < 2^31 < 1291^3
+    return check_texture_cube_sizes(B, H, W, L, N, C, *vfilter);          // (its own bound on N lies above this one)
+}
+
+static int texture_volume(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                          const int32_t* render_layers, const float* xyz, const float* grid, float* out, void* stream) {
+    int vfilter, vboundary;
+    if (check_texture_volume_sizes(B, H, W, L, N, C, filter, &vfilter, &vboundary)) return 1;
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!xyz || !grid || !out) return fail("texture_cube: a volume's xyz, grid and out must not be null");
+    dm2::launch_texture_volume(B, H, W, L, N, C, view_textures, vfilter, vboundary, render_layers, xyz, grid, out, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+static int texture_volume_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
+                                   int32_t filter, const int32_t* render_layers, const float* xyz, const float* grid,
+                                   const float* dL_dout, float* dL_dgrid, float* dL_dxyz, void* stream) {
+    int vfilter, vboundary;
+    if (check_texture_volume_sizes(B, H, W, L, N, C, filter, &vfilter, &vboundary)) return 1;
+    const int64_t S = (int64_t)B * H * W * L;
+    if (S == 0 || (!dL_dgrid && !dL_dxyz)) return 0;
+    if (!xyz || !dL_dout) return fail("texture_cube_backward: a volume's xyz and dL_dout must not be null");
+    if (dL_dxyz && vfilter == DM2_TEX_FILTER_NEAREST) {                   // piecewise constant in the position
+        DM2_HIP(hipMemsetAsync(dL_dxyz, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
+        dL_dxyz = nullptr;
+    }
+    if (dL_dxyz && !grid) return fail("texture_cube_backward: a volume's grid must not be null");
+    if (dL_dgrid || dL_dxyz)
+        dm2::launch_texture_volume_backward(B, H, W, L, N, C, view_textures, vfilter, vboundary, render_layers, xyz, grid, dL_dout,
+                                            dL_dgrid, dL_dxyz, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
                      const int32_t* render_layers, const float* dirs, const float* tex, float* out, void* stream) {
+    if (filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP))
+        return texture_volume(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, out, stream);
     if (check_texture_cube_sizes(B, H, W, L, N, C, filter)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
     if (!dirs || !tex || !out) return fail("texture_cube: dirs, tex and out must not be null");
@@ -587,6 +632,9 @@ int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int3
 int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
                               int32_t filter, const int32_t* render_layers, const float* dirs, const float* tex,
                               const float* dL_dout, float* dL_dtex, float* dL_ddir, void* stream) {
+    if (filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP))
+        return texture_volume_backward(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, dL_dout, dL_dtex, dL_ddir,
+                                       stream);
     if (check_texture_cube_sizes(B, H, W, L, N, C, filter)) return 1;
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dtex && !dL_ddir)) return 0;

@@ -261,6 +261,13 @@ void launch_texture_cube(int B, int H, int W, int L, int N, int C, int view_text
 void launch_texture_cube_backward(int B, int H, int W, int L, int N, int C, int view_textures, int filter,
                                   const int32_t* render_layers, const float* dirs, const float* tex, const float* dL_dout,
                                   float* dL_dtex, float* dL_ddir, hipStream_t st);
+// Renderer.texture3d (dm2_texture_volume.hip): as launch_texture / launch_texture_backward, for a voxel grid (N, N, N, C)
+// looked up by positions (B, H, W, L, 3) in its unit cube; N * N * N < 2^31; dL_dxyz: linear only.
+void launch_texture_volume(int B, int H, int W, int L, int N, int C, int view_textures, int filter, int boundary,
+                           const int32_t* render_layers, const float* xyz, const float* grid, float* out, hipStream_t st);
+void launch_texture_volume_backward(int B, int H, int W, int L, int N, int C, int view_textures, int filter, int boundary,
+                                    const int32_t* render_layers, const float* xyz, const float* grid, const float* dL_dout,
+                                    float* dL_dgrid, float* dL_dxyz, hipStream_t st);
 // Renderer.composite (dm2_composite.hip): every element of out / out_acc / out_final_T / out_n_contrib / dL_dvalues and of the
 // per-slot dL_dalpha is written; the backward adds into the per-face dL_dalpha (per_face != 0).  B * H * W > 0, C >= 1; NULL:
 // render_layers (per-slot alpha only), background, any output but out, either upstream gradient, either output gradient.

@@ -439,6 +439,37 @@ int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int3
 int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
                               int32_t filter, const int32_t* render_layers, const float* dirs, const float* tex,
                               const float* dL_dout, float* dL_dtex, float* dL_ddir, void* stream);
+/* filter with DM2_TEX_VOLUME_CLAMP or DM2_TEX_VOLUME_WRAP set (OR-ed with DM2_TEX_FILTER_NEAREST or _LINEAR): Renderer.texture3d,
+ * a voxel grid looked up by a position per slot (a variant of "a texture looked up by three coordinates": no symbol of its own).
+ * Both functions above then read their arguments as: dirs = xyz (B,H,W,L,3) float32, the position in the grid's unit cube, x
+ * along the grid's last spatial axis and z along its first; tex = the grid (N,N,N,C) float32 shared by the views
+ * (view_textures == 0) or (B,N,N,N,C), channel-last, indexed [k][j][i]; dL_dtex = dL_dgrid; dL_ddir = dL_dxyz.  N, C >= 1;
+ * N * N * N < 2^31 takes the place of 6 * N * N < 2^31.  Both bits set, or any other bit beside DM2_TEX_FILTER_*, is refused.
+ * Voxel centres sit at ((i + 0.5) / N, (j + 0.5) / N, (k + 0.5) / N).  Per slot s, all fp32, separate multiplies and adds in
+ * the written order, without contraction (bit-exact):
+ *   X  = x * (float)N - 0.5f      Y = y * (float)N - 0.5f      Z = z * (float)N - 0.5f
+ *   X0 = floorf(X)   fx = X - X0   i0 = (int)X0                 (Y0, fy, j0 and Z0, fz, k0 alike)
+ * A slot is empty when render_layers[s] < 0 (render_layers NULL: never by id), or a coordinate is not finite, or |X|, |Y| or |Z|
+ * is not below 2^24 (dm2_texture's rule, per axis): out[s,:] = 0, and nothing is read from the grid through it.  Otherwise the
+ * eight taps are t_pqr = grid[addr(k0 + r)][addr(j0 + q)][addr(i0 + p)] with dm2_texture's addr of the boundary, n = N
+ * (DM2_TEX_VOLUME_CLAMP: DM2_TEX_BOUNDARY_CLAMP's, DM2_TEX_VOLUME_WRAP: DM2_TEX_BOUNDARY_WRAP's):
+ *   DM2_TEX_FILTER_LINEAR   a_r = b0 + fy * (b1 - b0), b_q = t_0qr + fx * (t_1qr - t_0qr)   (dm2_texture's blend in plane k0 + r),
+ *                           out[s,c] = a_0 + fz * (a_1 - a_0)
+ *   DM2_TEX_FILTER_NEAREST  out[s,c] = grid[addr((int)floorf(Z + 0.5f))][addr((int)floorf(Y + 0.5f))][addr((int)floorf(X + 0.5f))]
+ * Every element of out is written: no pre-fill.
+ * Gradients for upstream g = dL_dout (B,H,W,L,C): the derivative of that fp32 function at its fp32 fractions and addresses.
+ * Per non-empty slot s:
+ *   dL_dgrid[t_pqr,c] += w_pqr * g[s,c], w_pqr = (wx_p * wy_q) * wz_r with (w_0, w_1) = (1 - f, f) per axis (nearest: weight 1
+ *     on the one voxel); the view's own grid when view_textures != 0, summed over the views otherwise; taps that meet in one
+ *     voxel (N = 1, clamp at a border) all add; dL_dgrid is zero-filled by the caller and summed with float atomics: its last
+ *     bits may vary from run to run;
+ *   dL_dxyz[s,a] = (float)N * sum_c g[s,c] * d out / d f_a, with u_r = (t_10r - t_00r) + fy * ((t_11r - t_01r) - (t_10r - t_00r))
+ *     and v_r = b1 - b0 of plane r:  d out / d fx = U_0 + fz * (U_1 - U_0),  d out / d fy = V_0 + fz * (V_1 - V_0) over the sums
+ *     U_r = sum_c g * u_r, V_r = sum_c g * v_r, and d out / d fz = a_1 - a_0; used as it stands where clamp has a kink; zeros
+ *     for nearest and in an empty slot; every element is written; a pure function of the inputs.
+ * Either output pointer may be NULL (not wanted; its kernel is not launched; tex may then be NULL for dL_dgrid alone). */
+#define DM2_TEX_VOLUME_CLAMP 0x100
+#define DM2_TEX_VOLUME_WRAP 0x200
 
 /* Renderer.bary_derivatives: the footprint of a pixel on each listed face.  render_layers (B,H,W,L) int32, verts (P,3) float32,
  * faces (F,3) int32, ray_cam (B,32) float32 = inv(mv) (16, row-major) then inv(proj) (16) of each view, the camera block of
