@@ -37,6 +37,14 @@ and a voxel grid looked up by such an image of positions (Renderer.texture3d; th
     texture_volume_cuda(xyz, grid, render_layers, filter_mode, boundary_mode) -> out,
     texture_volume_backward_cuda(...those 5..., grad_out, need_grid, need_xyz) -> (dL/dgrid, dL/dxyz)
 
+and a multiresolution hash encoding looked up by such positions (Renderer.hash_grid; the same two C symbols under
+DM2_TEX_HASH_GRID_CODE):
+
+    hash_grid_resolutions(num_levels, base_resolution, growth) -> [R_0, ..., R_{NL-1}],
+    hash_grid_code(log2_rows, num_levels, growth, filter_mode, boundary_mode) -> the filter word,
+    hash_grid_cuda(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode) -> out,
+    hash_grid_backward_cuda(...those 7..., grad_out, need_table, need_xyz) -> (dL/dtable, dL/dxyz)
+
 and its mip-mapped filter (Renderer.bary_derivatives, Renderer.texture_mipmaps, texture's "linear-mipmap-linear"):
 
     bary_derivatives_cuda(render_layers, verts, faces, ray_cam) -> (dbary_dx, dbary_dy),
@@ -1149,6 +1157,119 @@ def texture_volume_backward_cuda(xyz, grid, render_layers, filter_mode, boundary
         if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(pc), _ptr(gr), _ptr(go), _ptr(dgrid), _ptr(dxyz), _stream(dev)):
             raise _err(lib, "texture_volume_backward_cuda")
     return dgrid, dxyz
+
+
+TEX_HASH_GRID = 0x800                                        # DM2_TEX_HASH_GRID
+HASH_GRID_FEATURES = (1, 2, 4, 8)
+HASH_GRID_MAX_LEVELS, HASH_GRID_MAX_RESOLUTION = 32, 2 ** 20
+HASH_GRID_LOG2_ROWS = (4, 24)
+
+
+def _hash_grid_q(growth):
+    """growth -> q = 16 growth, an integer in 17..32 (ValueError otherwise)."""
+    q = float(growth) * 16.0
+    if not (17.0 <= q <= 32.0 and q == int(q)):                          # (NaN fails the first test)
+        raise ValueError(f"growth must be a multiple of 1/16 from 1.0625 to 2, got {growth!r}")
+    return int(q)
+
+
+def hash_grid_resolutions(num_levels, base_resolution=16, growth=1.5):
+    """The level resolutions of a hash grid (include/dm2_hip.h, DM2_TEX_HASH_GRID_CODE): R_0 = base_resolution,
+    R_{l+1} = (R_l * q) >> 4 with q = 16 growth.  ValueError for a growth that is no multiple of 1/16 in [1.0625, 2], fewer than
+    1 or more than 32 levels, a base resolution below 1 or a finest level above 2^20."""
+    q = _hash_grid_q(growth)
+    num_levels, base_resolution = int(num_levels), int(base_resolution)
+    if not 1 <= num_levels <= HASH_GRID_MAX_LEVELS:
+        raise ValueError(f"num_levels must be in 1..{HASH_GRID_MAX_LEVELS}, got {num_levels}")
+    if base_resolution < 1:
+        raise ValueError(f"base_resolution must be at least 1, got {base_resolution}")
+    res = [base_resolution]
+    while len(res) < num_levels:
+        res.append((res[-1] * q) >> 4)
+    if res[-1] > HASH_GRID_MAX_RESOLUTION:
+        raise ValueError(f"the finest level's resolution must not exceed 2^20, got {res[-1]}")
+    return res
+
+
+def hash_grid_code(log2_rows, num_levels, growth=1.5, filter_mode="linear", boundary_mode="clamp"):
+    """dm2_texture_cube's filter word of a hash grid call: DM2_TEX_HASH_GRID_CODE(log2_rows, num_levels, 16 growth) | the filter |
+    the volume's boundary bit."""
+    return (TEX_HASH_GRID | (int(log2_rows) << 12) | ((int(num_levels) - 1) << 17) | ((_hash_grid_q(growth) - 17) << 22)
+            | TEX_FILTERS[filter_mode] | TEX_VOLUME_BOUNDARIES[boundary_mode])
+
+
+def _hash_grid_args(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode, grad_out=None):
+    """Checks of a hash grid call -> (sizes (B, H, W, L, N, NL * F, 0, code), contiguous tensors, device)."""
+    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
+    _bad(boundary_mode not in TEX_VOLUME_BOUNDARIES,
+         f"boundary_mode must be one of {sorted(TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
+    _bad(xyz.dim() != 5 or xyz.size(4) != 3, f"xyz must have dimensions (B, H, W, L, 3), got {tuple(xyz.shape)}")
+    B, H, W, L = (int(x) for x in xyz.shape[:4])
+    _bad(table.dim() != 3, f"table must have dimensions (NL, T, F), got {tuple(table.shape)}")
+    NL, T, F = (int(x) for x in table.shape)
+    _bad(not 1 <= NL <= HASH_GRID_MAX_LEVELS, f"table must have 1..{HASH_GRID_MAX_LEVELS} levels, got {NL}")
+    log2T = T.bit_length() - 1
+    _bad(T < 1 or (1 << log2T) != T or not HASH_GRID_LOG2_ROWS[0] <= log2T <= HASH_GRID_LOG2_ROWS[1],
+         f"table must have a power of two from 2^4 to 2^24 rows per level, got {T}")
+    _bad(F not in HASH_GRID_FEATURES, f"table must have 1, 2, 4 or 8 features per row, got {F}")
+    _bad(NL * T * F >= 2 ** 31, "table: NL * T * F must be below 2^31")
+    try:
+        hash_grid_resolutions(NL, base_resolution, growth)
+        code = hash_grid_code(log2T, NL, growth, filter_mode, boundary_mode)
+    except ValueError as e:
+        raise RuntimeError(str(e)) from None
+    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
+        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
+    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, NL * F),
+        f"grad_out must have dimensions {(B, H, W, L, NL * F)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
+    dev = _require_gpu(*[t for t in (xyz, table, render_layers, grad_out) if t is not None])
+    f32, i32 = torch.float32, torch.int32
+    named = (("xyz", xyz, f32), ("table", table, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
+    ts = []
+    for name, t, dt in named:
+        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
+        ts.append(None if t is None else t.contiguous())
+    return (B, H, W, L, int(base_resolution), NL * F, 0, code), ts, dev
+
+
+def hash_grid_cuda(xyz, table, render_layers=None, base_resolution=16, growth=1.5, filter_mode="linear", boundary_mode="clamp"):
+    """A multiresolution hash encoding looked up by per-slot positions (include/dm2_hip.h: dm2_texture_cube with
+    DM2_TEX_HASH_GRID_CODE).
+
+    xyz (B,H,W,L,3) float32 in the field's unit cube, table (NL,T,F) float32, render_layers (B,H,W,L) int32 or None -> out
+    (B,H,W,L,NL*F) float32, channel l * F + f; 0 where the id is negative or a coordinate is not finite (or beyond 2^24 voxels
+    of the finest level)."""
+    lib = load_library()
+    sizes, (pc, tb, rl, _), dev = _hash_grid_args(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode)
+    B, H, W, L, C = *sizes[:4], sizes[5]
+    if B * H * W * L == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_cube(*sizes, _ptr(rl), _ptr(pc), _ptr(tb), _ptr(out), _stream(dev)):
+            raise _err(lib, "hash_grid_cuda")
+    return out
+
+
+def hash_grid_backward_cuda(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode, grad_out, need_table,
+                            need_xyz):
+    """Gradients of hash_grid_cuda (dm2_texture_cube_backward with DM2_TEX_HASH_GRID_CODE) -> (dL_dtable (NL,T,F) or None,
+    dL_dxyz (B,H,W,L,3) or None): only what ``need_table`` / ``need_xyz`` ask for is computed."""
+    lib = load_library()
+    sizes, (pc, tb, rl, go), dev = _hash_grid_args(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode,
+                                                   grad_out)
+    B, H, W, L = sizes[:4]
+    f32 = torch.float32
+    if not (need_table or need_xyz):
+        return None, None
+    dtable = torch.zeros(tuple(table.shape), dtype=f32, device=dev) if need_table else None
+    if B * H * W * L == 0:
+        return dtable, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None
+    dxyz = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None      # (every element written)
+    with torch.cuda.device(dev):
+        if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(pc), _ptr(tb), _ptr(go), _ptr(dtable), _ptr(dxyz), _stream(dev)):
+            raise _err(lib, "hash_grid_backward_cuda")
+    return dtable, dxyz
 
 
 def _vertex_normals_args(verts, faces, offsets, corners, normals=None, lens=None, grad_normals=None):

@@ -29,7 +29,8 @@ Same module surface as the reference's ``dmesh2_renderer/__init__.py``:
   ``Renderer.shading_vectors()``, per-slot position, view, unit normal and reflection vectors from the pixel's own ray
   (``ShadingVectorsFunction``); and ``Renderer.texture3d()``: a voxel grid of colours or features looked up at that position
   (trilinear or nearest, clamp or wrap), differentiable w.r.t. the grid and the position (``TextureVolumeFunction``): the
-  appearance model that needs no UV table
+  appearance model that needs no UV table; and ``Renderer.hash_grid()``: the multiresolution hash encoding of that position
+  (``HashGridFunction``), for fields finer than a dense grid can hold
 
 The native work goes through ``dmesh2_renderer_amd._C`` -- a ctypes shim over
 the C-ABI library ``libdm2_hip.so`` (include/dm2_hip.h) whose three functions
@@ -51,7 +52,7 @@ from .pyrenderer import Triangles
 __all__ = ["RenderFunction", "Renderer", "LayeredRenderer", "LayeredCompositeFunction", "RasterizeFunction", "InterpolateFunction",
            "TextureFunction", "CoverageFunction", "Triangles", "RasterizeOverlapFunction", "BaryDerivativesFunction",
            "MipmapFunction", "TextureMipFunction", "TextureCubeFunction", "VertexNormalsFunction", "ShadingVectorsFunction",
-           "TextureCubeMipFunction", "CubePrefilterFunction", "TextureVolumeFunction"]
+           "TextureCubeMipFunction", "CubePrefilterFunction", "TextureVolumeFunction", "HashGridFunction"]
 
 # Host prep of Renderer.forward (projection + the six AA tables): the fused HIP kernels of dmesh2_renderer_amd/prep.py by
 # default on GPU tensors (two kernels each way instead of ~20 torch kernels each way; verts_image differs from the torch
@@ -611,6 +612,46 @@ class Renderer(torch.nn.Module):
         rl = None if render_layers is None else render_layers.to(i32)
         return TextureVolumeFunction.apply(xyz.to(f32), grid.to(f32), rl, filter_mode, boundary_mode)
 
+    def hash_grid(self, xyz: torch.Tensor, table: torch.Tensor, render_layers: torch.Tensor = None, base_resolution: int = 16,
+                  growth: float = 1.5, filter_mode: str = "linear", boundary_mode: str = "clamp"):
+        """A multiresolution hash encoding looked up at per-slot positions (not in the reference): the input of a small MLP
+        that models appearance over space at a detail no dense grid can hold.  xyz (B,H,W,L,3) float32 = the position in the
+        field's unit cube, axes and meaning as for ``texture3d``; table (NL,T,F) float32 shared by the views: NL = 1..32
+        levels, T = 2^4..2^24 rows per level, F = 1, 2, 4 or 8 features per row; render_layers (B,H,W,L) int32 or None
+        -> out (B,H,W,L,NL*F) float32, the levels' samples concatenated, channel l * F + f.
+
+        Level l is ``texture3d``'s lookup (``filter_mode`` "linear" or "nearest", ``boundary_mode`` "clamp" or "wrap") of a
+        virtual R_l^3 grid, ``hash_grid_resolutions(NL, base_resolution, growth)``: R_0 = base_resolution,
+        R_{l+1} = (R_l * 16 growth) >> 4, ``growth`` a multiple of 1/16 from 1.0625 to 2.  Its voxel (k, j, i) is row
+        (k R_l + j) R_l + i of table[l] while R_l^3 <= T and row (i ^ j * 2654435761 ^ k * 805459861) mod T after that.
+
+        A slot with ``render_layers`` < 0 (None: no slot, by id), or with a coordinate that is not finite, is empty: zeros
+        out, nothing read from the table through it, no gradient.  Differentiable w.r.t. ``table`` and ``xyz``
+        (``HashGridFunction``); through ``xyz``, ``shading_vectors``' and ``rasterize``'s backwards carry the gradient on to
+        ``verts``.  ValueError for an unknown mode, a bad ``growth`` or ``base_resolution``, or a table whose T or F the op
+        does not take."""
+        if filter_mode not in _C.TEX_FILTERS:
+            raise ValueError(f"filter_mode must be one of {sorted(_C.TEX_FILTERS)}, got {filter_mode!r}")
+        if boundary_mode not in _C.TEX_VOLUME_BOUNDARIES:
+            raise ValueError(f"boundary_mode must be one of {sorted(_C.TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
+        if table.dim() != 3:
+            raise ValueError(f"table must have dimensions (NL, T, F), got {tuple(table.shape)}")
+        NL, T, F = (int(x) for x in table.shape)
+        lo, hi = _C.HASH_GRID_LOG2_ROWS
+        if T < 1 or T & (T - 1) or not lo <= T.bit_length() - 1 <= hi:
+            raise ValueError(f"table: T must be a power of two from 2^{lo} to 2^{hi} rows per level, got {T}")
+        if F not in _C.HASH_GRID_FEATURES:
+            raise ValueError(f"table: F must be 1, 2, 4 or 8 features per row, got {F}")
+        _C.hash_grid_resolutions(NL, base_resolution, growth)            # (ValueError for growth, NL, base_resolution, R_{NL-1})
+        i32, f32 = torch.int32, torch.float32
+        rl = None if render_layers is None else render_layers.to(i32)
+        return HashGridFunction.apply(xyz.to(f32), table.to(f32), rl, int(base_resolution), float(growth), filter_mode, boundary_mode)
+
+    @staticmethod
+    def hash_grid_resolutions(num_levels: int, base_resolution: int = 16, growth: float = 1.5):
+        """[R_0, ..., R_{NL-1}] of ``hash_grid``: R_0 = base_resolution, R_{l+1} = (R_l * 16 growth) >> 4."""
+        return _C.hash_grid_resolutions(num_levels, base_resolution, growth)
+
     def texture_mipmaps(self, tex: torch.Tensor, max_mip_level: int = None):
         """The mip chain of a texture (not in the reference): tex (Ht,Wt,C) float32 or (B,Ht,Wt,C) -> mip (T,C) or (B,T,C)
         float32.  Level 0 is ``tex`` itself and is not copied; level k+1 exists while both extents of level k are even and
@@ -1092,6 +1133,33 @@ class TextureVolumeFunction(torch.autograd.Function):
         xyz, grid, render_layers = _saved_optional(ctx)
         dgrid, dxyz = _C.texture_volume_backward_cuda(xyz, grid, render_layers, *ctx.modes, grad_out, need_grid, need_xyz)
         return dxyz, dgrid, None, None, None
+
+
+class HashGridFunction(torch.autograd.Function):
+    """out = the hash grid's levels at each slot's position (``_C.hash_grid_cuda``): per level ``TextureVolumeFunction``'s lookup
+    of a virtual R_l^3 grid whose voxels live in rows of table[l], by position while the level fits and by hash after that.
+
+    Inputs: xyz (B,H,W,L,3)*, table (NL,T,F)*, render_layers (B,H,W,L) int32 or None, base_resolution, growth, filter_mode,
+    boundary_mode.  Output: out (B,H,W,L,NL*F).  (* = receives a gradient.)  A non-empty slot sends w_pqr g to its eight rows of
+    every level and the levels' finite differences . g, scaled by R_l, to (x, y, z) (zeros for nearest); empty slots send nothing
+    and get zero.  Only the gradients ``needs_input_grad`` asks for are computed.
+    """
+
+    @staticmethod
+    def forward(ctx, xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode):
+        ctx.modes = (base_resolution, growth, filter_mode, boundary_mode)
+        out = _C.hash_grid_cuda(xyz.detach(), table.detach(), render_layers, *ctx.modes)
+        _save_optional(ctx, xyz.detach(), table.detach(), render_layers)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_xyz, need_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if grad_out is None or not (need_xyz or need_table):
+            return (None,) * 7
+        xyz, table, render_layers = _saved_optional(ctx)
+        dtable, dxyz = _C.hash_grid_backward_cuda(xyz, table, render_layers, *ctx.modes, grad_out, need_table, need_xyz)
+        return dxyz, dtable, None, None, None, None, None
 
 
 class BaryDerivativesFunction(torch.autograd.Function):

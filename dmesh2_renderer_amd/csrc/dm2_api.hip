@@ -617,8 +617,81 @@ static int texture_volume_backward(int32_t B, int32_t H, int32_t W, int32_t L, i
     return 0;
 }
 
+// filter carries DM2_TEX_HASH_GRID: Renderer.hash_grid, a multiresolution hash encoding looked up by positions.
+struct HashGridCall {
+    int filter, boundary;   // DM2_TEX_FILTER_*, DM2_TEX_BOUNDARY_*
+    int NL, T, F;
+    int R[32];              // R_0 = N, R_{l+1} = (R_l * q) >> 4
+};
+
+static int check_hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                           HashGridCall* h) {
+    const int32_t fields = DM2_TEX_HASH_GRID_CODE(31, 32, 32);            // every bit of the code's three fields, and the hash bit
+    const int32_t vol = filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP);
+    if (filter & ~(fields | DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP | DM2_TEX_FILTER_LINEAR))
+        return fail("texture_cube: unknown bits beside a hash grid's code");
+    if (vol != DM2_TEX_VOLUME_CLAMP && vol != DM2_TEX_VOLUME_WRAP) return fail("texture_cube: a hash grid takes one boundary, clamp or wrap");
+    if (view_textures) return fail("texture_cube: a hash grid's table is shared by the views");
+    h->filter = filter & DM2_TEX_FILTER_LINEAR;
+    h->boundary = vol == DM2_TEX_VOLUME_WRAP ? DM2_TEX_BOUNDARY_WRAP : DM2_TEX_BOUNDARY_CLAMP;
+    const int log2T = (filter >> 12) & 31, q = ((filter >> 22) & 15) + 17;
+    h->NL = ((filter >> 17) & 31) + 1;
+    if (log2T < 4 || log2T > 24) return fail("texture_cube: a hash grid's log2(T) must be in 4..24");
+    h->T = 1 << log2T;
+    if (B < 0 || H < 0 || W < 0 || L < 0) return fail("texture_cube: negative size");
+    if (N < 1) return fail("texture_cube: a hash grid's base resolution must be at least 1");
+    if (C < 1 || C % h->NL != 0) return fail("texture_cube: a hash grid's C must be NL * F");
+    h->F = C / h->NL;
+    if (h->F != 1 && h->F != 2 && h->F != 4 && h->F != 8) return fail("texture_cube: a hash grid's F must be 1, 2, 4 or 8");
+    if ((int64_t)h->NL * h->T * h->F > 0x7FFFFFFF) return fail("texture_cube: a hash grid's NL * T * F must be below 2^31");
+    int64_t r = N;
+    for (int l = 0; l < h->NL; l++) {
+        if (r > (1 << 20)) return fail("texture_cube: a hash grid's finest resolution must not exceed 2^20");
+        h->R[l] = (int)r;
+        r = (r * q) >> 4;
+    }
+    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || (int64_t)B * h->NL > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
+        return fail("texture_cube: too many slots, rows or views");
+    return 0;
+}
+
+static int hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                     const int32_t* render_layers, const float* xyz, const float* table, float* out, void* stream) {
+    HashGridCall h;
+    if (check_hash_grid(B, H, W, L, N, C, view_textures, filter, &h)) return 1;
+    if (!xyz) return fail("texture_cube: a hash grid's xyz must not be null");
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!table || !out) return fail("texture_cube: a hash grid's table and out must not be null");
+    dm2::launch_hash_grid(B, H, W, L, h.NL, h.T, h.F, h.R, h.filter, h.boundary, render_layers, xyz, table, out, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+static int hash_grid_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                              const int32_t* render_layers, const float* xyz, const float* table, const float* dL_dout,
+                              float* dL_dtable, float* dL_dxyz, void* stream) {
+    HashGridCall h;
+    if (check_hash_grid(B, H, W, L, N, C, view_textures, filter, &h)) return 1;
+    if (!xyz) return fail("texture_cube_backward: a hash grid's xyz must not be null");
+    const int64_t S = (int64_t)B * H * W * L;
+    if (S == 0 || (!dL_dtable && !dL_dxyz)) return 0;
+    if (!dL_dout) return fail("texture_cube_backward: a hash grid's dL_dout must not be null");
+    if (dL_dxyz && h.filter == DM2_TEX_FILTER_NEAREST) {                  // piecewise constant in the position
+        DM2_HIP(hipMemsetAsync(dL_dxyz, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
+        dL_dxyz = nullptr;
+    }
+    if (dL_dxyz && !table) return fail("texture_cube_backward: a hash grid's table must not be null");
+    if (dL_dtable || dL_dxyz)
+        dm2::launch_hash_grid_backward(B, H, W, L, h.NL, h.T, h.F, h.R, h.filter, h.boundary, render_layers, xyz, table, dL_dout,
+                                       dL_dtable, dL_dxyz, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
 int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
                      const int32_t* render_layers, const float* dirs, const float* tex, float* out, void* stream) {
+    if (filter & DM2_TEX_HASH_GRID)
+        return hash_grid(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, out, stream);
     if (filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP))
         return texture_volume(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, out, stream);
     if (check_texture_cube_sizes(B, H, W, L, N, C, filter)) return 1;
@@ -632,6 +705,8 @@ int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int3
 int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
                               int32_t filter, const int32_t* render_layers, const float* dirs, const float* tex,
                               const float* dL_dout, float* dL_dtex, float* dL_ddir, void* stream) {
+    if (filter & DM2_TEX_HASH_GRID)
+        return hash_grid_backward(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, dL_dout, dL_dtex, dL_ddir, stream);
     if (filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP))
         return texture_volume_backward(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, dL_dout, dL_dtex, dL_ddir,
                                        stream);

@@ -268,6 +268,14 @@ void launch_texture_volume(int B, int H, int W, int L, int N, int C, int view_te
 void launch_texture_volume_backward(int B, int H, int W, int L, int N, int C, int view_textures, int filter, int boundary,
                                     const int32_t* render_layers, const float* xyz, const float* grid, const float* dL_dout,
                                     float* dL_dgrid, float* dL_dxyz, hipStream_t st);
+// Renderer.hash_grid (dm2_hash_grid.hip): a table (NL, T, F) looked up by positions (B, H, W, L, 3), level v the lookup of a
+// virtual R[v]^3 grid (R: the NL resolutions, worked out by the caller); T a power of two, F in {1, 2, 4, 8}, NL <= 32,
+// NL * T * F < 2^31, B * NL <= 65535; out / dL_dout (B, H, W, L, NL * F); dL_dxyz: linear only.
+void launch_hash_grid(int B, int H, int W, int L, int NL, int T, int F, const int* R, int filter, int boundary,
+                      const int32_t* render_layers, const float* xyz, const float* table, float* out, hipStream_t st);
+void launch_hash_grid_backward(int B, int H, int W, int L, int NL, int T, int F, const int* R, int filter, int boundary,
+                               const int32_t* render_layers, const float* xyz, const float* table, const float* dL_dout,
+                               float* dL_dtable, float* dL_dxyz, hipStream_t st);
 // Renderer.composite (dm2_composite.hip): every element of out / out_acc / out_final_T / out_n_contrib / dL_dvalues and of the
 // per-slot dL_dalpha is written; the backward adds into the per-face dL_dalpha (per_face != 0).  B * H * W > 0, C >= 1; NULL:
 // render_layers (per-slot alpha only), background, any output but out, either upstream gradient, either output gradient.

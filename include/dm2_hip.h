@@ -470,6 +470,38 @@ int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_
  * Either output pointer may be NULL (not wanted; its kernel is not launched; tex may then be NULL for dL_dgrid alone). */
 #define DM2_TEX_VOLUME_CLAMP 0x100
 #define DM2_TEX_VOLUME_WRAP 0x200
+/* filter with DM2_TEX_HASH_GRID_CODE(log2T, NL, q) set, OR-ed with DM2_TEX_FILTER_NEAREST or _LINEAR and exactly one of
+ * DM2_TEX_VOLUME_CLAMP / DM2_TEX_VOLUME_WRAP: Renderer.hash_grid, a multiresolution hash encoding looked up by a position per slot
+ * (no symbol of its own either).  Both functions above then read their arguments as: N = the base resolution; C = NL * F;
+ * dirs = xyz (B,H,W,L,3) float32, the position in the field's unit cube, axes as for the volume; tex = the table (NL, T, F)
+ * float32, T = 2^log2T rows per level, shared by the views; dL_dtex = dL_dtable; dL_ddir = dL_dxyz; out and dL_dout are
+ * (B,H,W,L,NL*F), level-major: channel l * F + f.
+ * Refused: view_textures != 0; the hash bit without a boundary bit or with both; NL outside 1..32 (by the code: never); C % NL
+ * != 0; F = C / NL not in {1, 2, 4, 8}; log2T outside 4..24; N < 1; R_{NL-1} > 2^20; NL * T * F >= 2^31; B * NL > 65535; NULL
+ * xyz; bits 26..31 and every bit that is no field of the code.  Without the hash bit the fields of the code are unknown bits.
+ * Level resolutions, integers:  R_0 = N,  R_{l+1} = (R_l * q) >> 4,  q in 17..32 (growth q / 16).
+ * One level l is the volume's lookup above of a virtual R_l^3 grid, n = R_l, whose voxel (k, j, i) is row row_l(k, j, i) of
+ * table[l]; all fp32, separate multiplies and adds in the written order, without contraction (bit-exact):
+ *   X  = x * (float)R_l - 0.5f   X0 = floorf(X)   fx = X - X0   i0 = (int)X0        (Y0, fy, j0 and Z0, fz, k0 alike)
+ *   t_pqr = table[l][row_l(addr(k0 + r), addr(j0 + q), addr(i0 + p))]               (addr: the volume's, of the boundary bit)
+ *   DM2_TEX_FILTER_LINEAR   out[s, l*F + f] = a_0 + fz * (a_1 - a_0), a_r the volume's blend of plane k0 + r
+ *   DM2_TEX_FILTER_NEAREST  out[s, l*F + f] = table[l][row_l(addr((int)floorf(Z + 0.5f)), addr(.. Y ..), addr(.. X ..))]
+ * Row addressing, on the addresses after addr:
+ *   (int64)R_l^3 <= T (a dense level):  row = (k * R_l + j) * R_l + i
+ *   otherwise, in uint32_t arithmetic that wraps:  row = (i ^ (j * 2654435761u) ^ (k * 805459861u)) & (T - 1)
+ * Taps that land in one row (collisions, R_l = 1, clamp at a border) all read it, and all add to it in the backward.
+ * A slot is empty when render_layers[s] < 0 (render_layers NULL: never by id), or |X|, |Y| or |Z| at the finest level l = NL - 1
+ * is not below 2^24 (NaN and infinities included; the R_l do not decrease, so no coarser level is out of range when the finest
+ * is not): zeros in all NL * F channels, nothing read from the table through it, no gradient.  Every element of out is written.
+ * Gradients for upstream g = dL_dout: the derivative of that fp32 function at its fp32 fractions and addresses.
+ *   dL_dtable[l, row_pqr, f] += ((wx_p * wy_q) * wz_r) * g[s, l*F + f], (w_0, w_1) = (1 - f, f) per axis (nearest: weight 1 on
+ *     the one row); zero-filled by the caller, summed with float atomics: its last bits may vary from run to run;
+ *   dL_dxyz[s, a] = sum over l = 0 .. NL - 1, in that order from 0.0f, of (float)R_l * the level's volume term:
+ *     U_0 + fz * (U_1 - U_0), V_0 + fz * (V_1 - V_0) and sum_f g * (a_1 - a_0), the sums over the level's F features in order
+ *     (the volume's U_r, V_r); zeros for nearest and in an empty slot; every element is written; a pure function of the inputs.
+ * Either output pointer may be NULL (not wanted; its kernel is not launched; tex may then be NULL for dL_dtable alone). */
+#define DM2_TEX_HASH_GRID 0x800
+#define DM2_TEX_HASH_GRID_CODE(log2T, NL, q) (DM2_TEX_HASH_GRID | ((log2T) << 12) | (((NL) - 1) << 17) | (((q) - 17) << 22))
 
 /* Renderer.bary_derivatives: the footprint of a pixel on each listed face.  render_layers (B,H,W,L) int32, verts (P,3) float32,
  * faces (F,3) int32, ray_cam (B,32) float32 = inv(mv) (16, row-major) then inv(proj) (16) of each view, the camera block of
