@@ -95,6 +95,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -960,205 +961,13 @@ def interpolate_backward_cuda(render_layers, bary, attr, attr_faces, grad_out, n
     return dattr, dbary
 
 
+# -- the per-slot lookup ops: a coordinate per slot (B,H,W,L,k), a table and optional render_layers -> out (B,H,W,L,C); the
+#    backward returns the table's gradient (summed into) and the coordinate's (fully written).  Each op is one ``_Lookup``
+#    record and two thin wrappers; ``_lookup_args`` / ``_lookup_forward`` / ``_lookup_backward`` do the rest. -------------------
 TEX_FILTERS = {"nearest": 0, "linear": 1}        # include/dm2_hip.h DM2_TEX_FILTER_*
 TEX_BOUNDARIES = {"wrap": 0, "clamp": 1}         # DM2_TEX_BOUNDARY_*
-
-
-def _texture_args(uv, tex, render_layers, filter_mode, boundary_mode, grad_out=None):
-    """Checks of a texture call -> (sizes (B, H, W, L, Ht, Wt, C, view_textures, filter, boundary), contiguous tensors, device)."""
-    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
-    _bad(boundary_mode not in TEX_BOUNDARIES, f"boundary_mode must be one of {sorted(TEX_BOUNDARIES)}, got {boundary_mode!r}")
-    _bad(uv.dim() != 5 or uv.size(4) != 2, f"uv must have dimensions (B, H, W, L, 2), got {tuple(uv.shape)}")
-    B, H, W, L = (int(x) for x in uv.shape[:4])
-    _bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
-    _bad(tex.dim() == 4 and tex.size(0) != B, f"tex must have dimensions (Ht, Wt, C) or ({B}, Ht, Wt, C), got {tuple(tex.shape)}")
-    Ht, Wt, C = (int(x) for x in tex.shape[-3:])
-    _bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
-    _bad(C < 1, "tex must have at least one channel")
-    _bad(Ht * Wt >= 2 ** 31, "tex: Ht * Wt must be below 2^31")
-    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
-        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
-    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
-        f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
-    dev = _require_gpu(*[t for t in (uv, tex, render_layers, grad_out) if t is not None])
-    f32, i32 = torch.float32, torch.int32
-    named = (("uv", uv, f32), ("tex", tex, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
-    ts = []
-    for name, t, dt in named:
-        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
-        ts.append(None if t is None else t.contiguous())
-    return (B, H, W, L, Ht, Wt, C, 1 if tex.dim() == 4 else 0, TEX_FILTERS[filter_mode], TEX_BOUNDARIES[boundary_mode]), ts, dev
-
-
-def texture_cuda(uv, tex, render_layers=None, filter_mode="linear", boundary_mode="wrap"):
-    """A texture sampled at per-slot UVs (include/dm2_hip.h: dm2_texture).
-
-    uv (B,H,W,L,2) float32, tex (Ht,Wt,C) or (B,Ht,Wt,C) float32 channel-last, render_layers (B,H,W,L) int32 or None
-    -> out (B,H,W,L,C) float32; 0 where the id is negative or uv is not finite (or beyond 2^24 texels)."""
-    lib = load_library()
-    sizes, (uvc, tx, rl, _), dev = _texture_args(uv, tex, render_layers, filter_mode, boundary_mode)
-    B, H, W, L, C = *sizes[:4], sizes[6]
-    if B * H * W * L == 0:
-        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
-    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture(*sizes, _ptr(rl), _ptr(uvc), _ptr(tx), _ptr(out), _stream(dev)):
-            raise _err(lib, "texture_cuda")
-    return out
-
-
-def texture_backward_cuda(uv, tex, render_layers, filter_mode, boundary_mode, grad_out, need_tex, need_uv):
-    """Gradients of texture_cuda (dm2_texture_backward) -> (dL_dtex of tex's shape or None, dL_duv (B,H,W,L,2) or None): only
-    what ``need_tex`` / ``need_uv`` ask for is computed."""
-    lib = load_library()
-    sizes, (uvc, tx, rl, go), dev = _texture_args(uv, tex, render_layers, filter_mode, boundary_mode, grad_out)
-    B, H, W, L = sizes[:4]
-    f32 = torch.float32
-    if not (need_tex or need_uv):
-        return None, None
-    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None
-    if B * H * W * L == 0:
-        return dtex, torch.zeros((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None
-    duv = torch.empty((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None      # (every element written)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_backward(*sizes, _ptr(rl), _ptr(uvc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(duv), _stream(dev)):
-            raise _err(lib, "texture_backward_cuda")
-    return dtex, duv
-
-
-def _texture_cube_args(dirs, tex, render_layers, filter_mode, grad_out=None):
-    """Checks of a cube-map call -> (sizes (B, H, W, L, N, C, view_textures, filter), contiguous tensors, device)."""
-    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
-    _bad(dirs.dim() != 5 or dirs.size(4) != 3, f"dirs must have dimensions (B, H, W, L, 3), got {tuple(dirs.shape)}")
-    B, H, W, L = (int(x) for x in dirs.shape[:4])
-    _bad(tex.dim() not in (4, 5), "tex must have dimensions (6, N, N, C) or (B, 6, N, N, C)")
-    _bad(tex.dim() == 5 and tex.size(0) != B, f"tex must have dimensions (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
-    six, Nr, N, C = (int(x) for x in tex.shape[-4:])
-    _bad(six != 6, f"tex must have six faces, (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
-    _bad(Nr != N, f"tex must have square faces, got {tuple(tex.shape)}")
-    _bad(N < 1, "tex must have at least one row and one column per face")
-    _bad(C < 1, "tex must have at least one channel")
-    _bad(6 * N * N >= 2 ** 31, "tex: 6 * N * N must be below 2^31")
-    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
-        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
-    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
-        f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
-    dev = _require_gpu(*[t for t in (dirs, tex, render_layers, grad_out) if t is not None])
-    f32, i32 = torch.float32, torch.int32
-    named = (("dirs", dirs, f32), ("tex", tex, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
-    ts = []
-    for name, t, dt in named:
-        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
-        ts.append(None if t is None else t.contiguous())
-    return (B, H, W, L, N, C, 1 if tex.dim() == 5 else 0, TEX_FILTERS[filter_mode]), ts, dev
-
-
-def texture_cube_cuda(dirs, tex, render_layers=None, filter_mode="linear"):
-    """A cube map looked up by per-slot directions (include/dm2_hip.h: dm2_texture_cube).
-
-    dirs (B,H,W,L,3) float32 of any non-zero length, tex (6,N,N,C) or (B,6,N,N,C) float32 channel-last (+x, -x, +y, -y, +z,
-    -z), render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is negative or the direction is
-    not finite or all zero."""
-    lib = load_library()
-    sizes, (dc, tx, rl, _), dev = _texture_cube_args(dirs, tex, render_layers, filter_mode)
-    B, H, W, L, C = *sizes[:4], sizes[5]
-    if B * H * W * L == 0:
-        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
-    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_cube(*sizes, _ptr(rl), _ptr(dc), _ptr(tx), _ptr(out), _stream(dev)):
-            raise _err(lib, "texture_cube_cuda")
-    return out
-
-
-def texture_cube_backward_cuda(dirs, tex, render_layers, filter_mode, grad_out, need_tex, need_dirs):
-    """Gradients of texture_cube_cuda (dm2_texture_cube_backward) -> (dL_dtex of tex's shape or None, dL_ddirs (B,H,W,L,3) or
-    None): only what ``need_tex`` / ``need_dirs`` ask for is computed."""
-    lib = load_library()
-    sizes, (dc, tx, rl, go), dev = _texture_cube_args(dirs, tex, render_layers, filter_mode, grad_out)
-    B, H, W, L = sizes[:4]
-    f32 = torch.float32
-    if not (need_tex or need_dirs):
-        return None, None
-    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None
-    if B * H * W * L == 0:
-        return dtex, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_dirs else None
-    ddir = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_dirs else None     # (every element written)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(dc), _ptr(tx), _ptr(go), _ptr(dtex), _ptr(ddir), _stream(dev)):
-            raise _err(lib, "texture_cube_backward_cuda")
-    return dtex, ddir
-
-
 TEX_VOLUME_BOUNDARIES = {"clamp": 0x100, "wrap": 0x200}      # DM2_TEX_VOLUME_*: OR-ed into dm2_texture_cube's filter
-
-
-def _texture_volume_args(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out=None):
-    """Checks of a volume call -> (sizes (B, H, W, L, N, C, view_textures, filter | volume bit), contiguous tensors, device)."""
-    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
-    _bad(boundary_mode not in TEX_VOLUME_BOUNDARIES,
-         f"boundary_mode must be one of {sorted(TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
-    _bad(xyz.dim() != 5 or xyz.size(4) != 3, f"xyz must have dimensions (B, H, W, L, 3), got {tuple(xyz.shape)}")
-    B, H, W, L = (int(x) for x in xyz.shape[:4])
-    _bad(grid.dim() not in (4, 5), "grid must have dimensions (N, N, N, C) or (B, N, N, N, C)")
-    _bad(grid.dim() == 5 and grid.size(0) != B, f"grid must have dimensions (N, N, N, C) or ({B}, N, N, N, C), got {tuple(grid.shape)}")
-    Nk, Nj, N, C = (int(x) for x in grid.shape[-4:])
-    _bad(Nk != N or Nj != N, f"grid must be a cube, (N, N, N, C) or ({B}, N, N, N, C), got {tuple(grid.shape)}")
-    _bad(N < 1, "grid must have at least one voxel")
-    _bad(C < 1, "grid must have at least one channel")
-    _bad(N * N * N >= 2 ** 31, "grid: N * N * N must be below 2^31")
-    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
-        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
-    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C),
-        f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
-    dev = _require_gpu(*[t for t in (xyz, grid, render_layers, grad_out) if t is not None])
-    f32, i32 = torch.float32, torch.int32
-    named = (("xyz", xyz, f32), ("grid", grid, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
-    ts = []
-    for name, t, dt in named:
-        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
-        ts.append(None if t is None else t.contiguous())
-    code = TEX_FILTERS[filter_mode] | TEX_VOLUME_BOUNDARIES[boundary_mode]
-    return (B, H, W, L, N, C, 1 if grid.dim() == 5 else 0, code), ts, dev
-
-
-def texture_volume_cuda(xyz, grid, render_layers=None, filter_mode="linear", boundary_mode="clamp"):
-    """A voxel grid looked up by per-slot positions (include/dm2_hip.h: dm2_texture_cube with DM2_TEX_VOLUME_*).
-
-    xyz (B,H,W,L,3) float32 in the grid's unit cube (x along the grid's last spatial axis), grid (N,N,N,C) or (B,N,N,N,C)
-    float32 channel-last, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is negative or a
-    coordinate is not finite (or beyond 2^24 voxels)."""
-    lib = load_library()
-    sizes, (pc, gr, rl, _), dev = _texture_volume_args(xyz, grid, render_layers, filter_mode, boundary_mode)
-    B, H, W, L, C = *sizes[:4], sizes[5]
-    if B * H * W * L == 0:
-        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
-    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_cube(*sizes, _ptr(rl), _ptr(pc), _ptr(gr), _ptr(out), _stream(dev)):
-            raise _err(lib, "texture_volume_cuda")
-    return out
-
-
-def texture_volume_backward_cuda(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out, need_grid, need_xyz):
-    """Gradients of texture_volume_cuda (dm2_texture_cube_backward with DM2_TEX_VOLUME_*) -> (dL_dgrid of grid's shape or None,
-    dL_dxyz (B,H,W,L,3) or None): only what ``need_grid`` / ``need_xyz`` ask for is computed."""
-    lib = load_library()
-    sizes, (pc, gr, rl, go), dev = _texture_volume_args(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out)
-    B, H, W, L = sizes[:4]
-    f32 = torch.float32
-    if not (need_grid or need_xyz):
-        return None, None
-    dgrid = torch.zeros(tuple(grid.shape), dtype=f32, device=dev) if need_grid else None
-    if B * H * W * L == 0:
-        return dgrid, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None
-    dxyz = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None      # (every element written)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(pc), _ptr(gr), _ptr(go), _ptr(dgrid), _ptr(dxyz), _stream(dev)):
-            raise _err(lib, "texture_volume_backward_cuda")
-    return dgrid, dxyz
-
-
+TEX_BOUNDARY_CUBE = 2          # DM2_TEX_BOUNDARY_CUBE: dm2_texture_mip / dm2_texture_mip_backward only
 TEX_HASH_GRID = 0x800                                        # DM2_TEX_HASH_GRID
 HASH_GRID_FEATURES = (1, 2, 4, 8)
 HASH_GRID_MAX_LEVELS, HASH_GRID_MAX_RESOLUTION = 32, 2 ** 20
@@ -1198,13 +1007,41 @@ def hash_grid_code(log2_rows, num_levels, growth=1.5, filter_mode="linear", boun
             | TEX_FILTERS[filter_mode] | TEX_VOLUME_BOUNDARIES[boundary_mode])
 
 
-def _hash_grid_args(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode, grad_out=None):
-    """Checks of a hash grid call -> (sizes (B, H, W, L, N, NL * F, 0, code), contiguous tensors, device)."""
-    _bad(filter_mode not in TEX_FILTERS, f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {filter_mode!r}")
-    _bad(boundary_mode not in TEX_VOLUME_BOUNDARIES,
-         f"boundary_mode must be one of {sorted(TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
-    _bad(xyz.dim() != 5 or xyz.size(4) != 3, f"xyz must have dimensions (B, H, W, L, 3), got {tuple(xyz.shape)}")
-    B, H, W, L = (int(x) for x in xyz.shape[:4])
+# The table checks of each op: (table, B, filter_mode, boundary_mode, ...) -> (the ABI words behind (B, H, W, L), C).
+def _texture_table(tex, B, filter_mode, boundary_mode):
+    _bad(tex.dim() not in (3, 4), "tex must have dimensions (Ht, Wt, C) or (B, Ht, Wt, C)")
+    _bad(tex.dim() == 4 and tex.size(0) != B, f"tex must have dimensions (Ht, Wt, C) or ({B}, Ht, Wt, C), got {tuple(tex.shape)}")
+    Ht, Wt, C = (int(x) for x in tex.shape[-3:])
+    _bad(Ht < 1 or Wt < 1, "tex must have at least one row and one column")
+    _bad(C < 1, "tex must have at least one channel")
+    _bad(Ht * Wt >= 2 ** 31, "tex: Ht * Wt must be below 2^31")
+    return (Ht, Wt, C, 1 if tex.dim() == 4 else 0, TEX_FILTERS[filter_mode], TEX_BOUNDARIES[boundary_mode]), C
+
+
+def _cube_table(tex, B, filter_mode, boundary_mode):
+    _bad(tex.dim() not in (4, 5), "tex must have dimensions (6, N, N, C) or (B, 6, N, N, C)")
+    _bad(tex.dim() == 5 and tex.size(0) != B, f"tex must have dimensions (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
+    six, Nr, N, C = (int(x) for x in tex.shape[-4:])
+    _bad(six != 6, f"tex must have six faces, (6, N, N, C) or ({B}, 6, N, N, C), got {tuple(tex.shape)}")
+    _bad(Nr != N, f"tex must have square faces, got {tuple(tex.shape)}")
+    _bad(N < 1, "tex must have at least one row and one column per face")
+    _bad(C < 1, "tex must have at least one channel")
+    _bad(6 * N * N >= 2 ** 31, "tex: 6 * N * N must be below 2^31")
+    return (N, C, 1 if tex.dim() == 5 else 0, TEX_FILTERS[filter_mode]), C
+
+
+def _volume_table(grid, B, filter_mode, boundary_mode):
+    _bad(grid.dim() not in (4, 5), "grid must have dimensions (N, N, N, C) or (B, N, N, N, C)")
+    _bad(grid.dim() == 5 and grid.size(0) != B, f"grid must have dimensions (N, N, N, C) or ({B}, N, N, N, C), got {tuple(grid.shape)}")
+    Nk, Nj, N, C = (int(x) for x in grid.shape[-4:])
+    _bad(Nk != N or Nj != N, f"grid must be a cube, (N, N, N, C) or ({B}, N, N, N, C), got {tuple(grid.shape)}")
+    _bad(N < 1, "grid must have at least one voxel")
+    _bad(C < 1, "grid must have at least one channel")
+    _bad(N * N * N >= 2 ** 31, "grid: N * N * N must be below 2^31")
+    return (N, C, 1 if grid.dim() == 5 else 0, TEX_FILTERS[filter_mode] | TEX_VOLUME_BOUNDARIES[boundary_mode]), C
+
+
+def _hash_grid_table(table, B, filter_mode, boundary_mode, base_resolution, growth):
     _bad(table.dim() != 3, f"table must have dimensions (NL, T, F), got {tuple(table.shape)}")
     NL, T, F = (int(x) for x in table.shape)
     _bad(not 1 <= NL <= HASH_GRID_MAX_LEVELS, f"table must have 1..{HASH_GRID_MAX_LEVELS} levels, got {NL}")
@@ -1218,18 +1055,172 @@ def _hash_grid_args(xyz, table, render_layers, base_resolution, growth, filter_m
         code = hash_grid_code(log2T, NL, growth, filter_mode, boundary_mode)
     except ValueError as e:
         raise RuntimeError(str(e)) from None
-    _bad(render_layers is not None and tuple(render_layers.shape) != (B, H, W, L),
-        f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape) if render_layers is not None else None}")
-    _bad(grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, NL * F),
-        f"grad_out must have dimensions {(B, H, W, L, NL * F)}, got {tuple(grad_out.shape) if grad_out is not None else None}")
-    dev = _require_gpu(*[t for t in (xyz, table, render_layers, grad_out) if t is not None])
+    return (int(base_resolution), NL * F, 0, code), NL * F
+
+
+# The chain checks of the two mip-mapped ops: (the table's words, B, max_mip_level) -> (the ABI words, mip's shape).
+def _texture_chain(words, B, max_mip_level):
+    Ht, Wt, C, per_view, _, boundary = words
+    _, _, T = mip_layout(Ht, Wt, max_mip_level)
+    _bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
+    return (Ht, Wt, C, per_view, boundary, _max_level_code(max_mip_level)), ((B,) if per_view else ()) + (T, C)
+
+
+def _cube_chain(words, B, max_mip_level):
+    N, C, per_view, _ = words
+    _, _, T = mip_layout(N, N, max_mip_level)
+    _bad(6 * (N * N + T) >= 2 ** 31, "tex: the texels of all levels of the cube must number below 2^31")
+    return (N, N, C, per_view, TEX_BOUNDARY_CUBE, _max_level_code(max_mip_level)), ((B,) if per_view else ()) + (6, T, C)
+
+
+class _Lookup(NamedTuple):
+    """What tells one lookup op from another."""
+    name: str                       # the wrappers are <name>_cuda and <name>_backward_cuda
+    coord: str                      # the coordinate's name in messages, and its width k
+    width: int
+    table: str                      # the table's name in messages
+    boundaries: Optional[dict]      # what boundary_mode may be (None: the op has none)
+    check_table: Callable           # one of the _*_table above
+    forward: str                    # the two exports
+    backward: str
+    slot_input: Optional[tuple] = None      # mip-mapped ops: (name, trailing shape) of the second per-slot input ...
+    check_chain: Optional[Callable] = None  # ... and one of the _*_chain above
+    row: Optional[int] = None               # floats per slot of the raw coordinate gradient (None: width) and how it is cut
+    split: tuple = (slice(None),)           # into what the backward returns, one index of the last axis each
+
+
+_TEXTURE = _Lookup("texture", "uv", 2, "tex", TEX_BOUNDARIES, _texture_table, "dm2_texture", "dm2_texture_backward")
+_TEXTURE_CUBE = _Lookup("texture_cube", "dirs", 3, "tex", None, _cube_table, "dm2_texture_cube", "dm2_texture_cube_backward")
+_TEXTURE_VOLUME = _Lookup("texture_volume", "xyz", 3, "grid", TEX_VOLUME_BOUNDARIES, _volume_table, "dm2_texture_cube",
+                          "dm2_texture_cube_backward")
+_HASH_GRID = _TEXTURE_VOLUME._replace(name="hash_grid", table="table", check_table=_hash_grid_table)
+_TEXTURE_MIP = _TEXTURE._replace(name="texture_mip", forward="dm2_texture_mip", backward="dm2_texture_mip_backward",
+                                 slot_input=("uv_da", (4,)), check_chain=_texture_chain)
+_TEXTURE_CUBE_MIP = _TEXTURE_CUBE._replace(name="texture_cube_mip", forward="dm2_texture_mip", backward="dm2_texture_mip_backward",
+                                           slot_input=("mip_level", ()), check_chain=_cube_chain, row=4, split=(slice(0, 3), 3))
+
+
+def _lookup_args(op, coord, table, render_layers, modes, grad_out=None, chain=None):
+    """Checks of a lookup call.  modes = (filter_mode, boundary_mode, ...whatever else ``op.check_table`` takes); chain = (the
+    second per-slot input, mip, max_mip_level) of a mip-mapped op -> (the ABI words (B, H, W, L, ...), C, the contiguous inputs
+    in the library's order: (render_layers, coord[, slot input], table[, mip][, grad_out]), device).  Training calls this
+    several times a step: a message is put together only where its check fails."""
+    if modes[0] not in TEX_FILTERS:
+        raise RuntimeError(f"filter_mode must be one of {sorted(TEX_FILTERS)}, got {modes[0]!r}")
+    if op.boundaries is not None and modes[1] not in op.boundaries:
+        raise RuntimeError(f"boundary_mode must be one of {sorted(op.boundaries)}, got {modes[1]!r}")
+    if coord.dim() != 5 or coord.size(4) != op.width:
+        raise RuntimeError(f"{op.coord} must have dimensions (B, H, W, L, {op.width}), got {tuple(coord.shape)}")
+    B, H, W, L = coord.shape[:4]
+    words, C = op.check_table(table, B, *modes)
+    if render_layers is not None and tuple(render_layers.shape) != (B, H, W, L):
+        raise RuntimeError(f"render_layers must have dimensions {(B, H, W, L)}, got {tuple(render_layers.shape)}")
+    if grad_out is not None and tuple(grad_out.shape) != (B, H, W, L, C):
+        raise RuntimeError(f"grad_out must have dimensions {(B, H, W, L, C)}, got {tuple(grad_out.shape)}")
+    dev = _require_gpu(*[t for t in (coord, table, render_layers, grad_out) if t is not None])
     f32, i32 = torch.float32, torch.int32
-    named = (("xyz", xyz, f32), ("table", table, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32))
-    ts = []
-    for name, t, dt in named:
-        _bad(t is not None and t.dtype != dt, f"{name}: expected dtype {dt}, got {t.dtype if t is not None else None}")
-        ts.append(None if t is None else t.contiguous())
-    return (B, H, W, L, int(base_resolution), NL * F, 0, code), ts, dev
+    for name, t, dt in ((op.coord, coord, f32), (op.table, table, f32), ("render_layers", render_layers, i32), ("grad_out", grad_out, f32)):
+        if t is not None and t.dtype != dt:
+            raise RuntimeError(f"{name}: expected dtype {dt}, got {t.dtype}")
+    ins = (None if render_layers is None else render_layers.contiguous(), coord.contiguous(), table.contiguous())
+    if chain is not None:
+        (name, tail), (slot, mip, max_mip_level) = op.slot_input, chain
+        if tuple(slot.shape) != (B, H, W, L) + tail:
+            raise RuntimeError(f"{name} must have dimensions {(B, H, W, L) + tail}, got {tuple(slot.shape)}")
+        words, shape = op.check_chain(words, B, max_mip_level)
+        if tuple(mip.shape) != shape:
+            raise RuntimeError(f"mip must have dimensions {shape} for tex {tuple(table.shape)} and max_mip_level {max_mip_level}, "
+                               f"got {tuple(mip.shape)}")
+        _require_gpu(coord, slot, mip)
+        for name, t in ((name, slot), ("mip", mip)):
+            if t.dtype != f32:
+                raise RuntimeError(f"{name}: expected dtype {f32}, got {t.dtype}")
+        ins = (ins[0], ins[1], slot.contiguous(), ins[2], mip.contiguous())
+    if grad_out is not None:
+        ins += (grad_out.contiguous(),)
+    return (B, H, W, L) + words, C, ins, dev
+
+
+def _lookup_forward(op, coord, table, render_layers, modes, chain=None):
+    lib = load_library()
+    sizes, C, ins, dev = _lookup_args(op, coord, table, render_layers, modes, None, chain)
+    B, H, W, L = sizes[:4]
+    if B * H * W * L == 0:
+        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
+    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
+    with torch.cuda.device(dev):
+        if getattr(lib, op.forward)(*sizes, *map(_ptr, ins), _ptr(out), _stream(dev)):
+            raise _err(lib, op.name + "_cuda")
+    return out
+
+
+def _lookup_backward(op, coord, table, render_layers, modes, grad_out, need_tables, need_coords, chain=None):
+    """need_tables: a flag per table (the table[, mip]), need_coords: a flag per entry of ``op.split`` -> their gradients in that
+    order, None where not asked for."""
+    lib = load_library()
+    sizes, _, ins, dev = _lookup_args(op, coord, table, render_layers, modes, grad_out, chain)
+    B, H, W, L = sizes[:4]
+    f32 = torch.float32
+    if not (any(need_tables) or any(need_coords)):
+        return (None,) * (len(need_tables) + len(need_coords))
+    dtables = (torch.zeros(tuple(table.shape), dtype=f32, device=dev) if need_tables[0] else None,)         # (summed into)
+    if chain is not None:
+        dtables += (torch.zeros(tuple(chain[1].shape), dtype=f32, device=dev) if need_tables[1] else None,)
+    rows = None
+    if any(need_coords):                                                  # (every element written; an empty grid launches nothing)
+        rows = (torch.zeros if B * H * W * L == 0 else torch.empty)((B, H, W, L, op.row or op.width), dtype=f32, device=dev)
+    if B * H * W * L != 0:
+        with torch.cuda.device(dev):
+            if getattr(lib, op.backward)(*sizes, *map(_ptr, ins), *map(_ptr, dtables), _ptr(rows), _stream(dev)):
+                raise _err(lib, op.name + "_backward_cuda")
+    if op.row is None:
+        return dtables + (rows,)
+    return dtables + tuple(rows[..., s].contiguous() if need else None for s, need in zip(op.split, need_coords))
+
+
+def texture_cuda(uv, tex, render_layers=None, filter_mode="linear", boundary_mode="wrap"):
+    """A texture sampled at per-slot UVs (include/dm2_hip.h: dm2_texture).
+
+    uv (B,H,W,L,2) float32, tex (Ht,Wt,C) or (B,Ht,Wt,C) float32 channel-last, render_layers (B,H,W,L) int32 or None
+    -> out (B,H,W,L,C) float32; 0 where the id is negative or uv is not finite (or beyond 2^24 texels)."""
+    return _lookup_forward(_TEXTURE, uv, tex, render_layers, (filter_mode, boundary_mode))
+
+
+def texture_backward_cuda(uv, tex, render_layers, filter_mode, boundary_mode, grad_out, need_tex, need_uv):
+    """Gradients of texture_cuda (dm2_texture_backward) -> (dL_dtex of tex's shape or None, dL_duv (B,H,W,L,2) or None): only
+    what ``need_tex`` / ``need_uv`` ask for is computed."""
+    return _lookup_backward(_TEXTURE, uv, tex, render_layers, (filter_mode, boundary_mode), grad_out, (need_tex,), (need_uv,))
+
+
+def texture_cube_cuda(dirs, tex, render_layers=None, filter_mode="linear"):
+    """A cube map looked up by per-slot directions (include/dm2_hip.h: dm2_texture_cube).
+
+    dirs (B,H,W,L,3) float32 of any non-zero length, tex (6,N,N,C) or (B,6,N,N,C) float32 channel-last (+x, -x, +y, -y, +z,
+    -z), render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is negative or the direction is
+    not finite or all zero."""
+    return _lookup_forward(_TEXTURE_CUBE, dirs, tex, render_layers, (filter_mode, None))
+
+
+def texture_cube_backward_cuda(dirs, tex, render_layers, filter_mode, grad_out, need_tex, need_dirs):
+    """Gradients of texture_cube_cuda (dm2_texture_cube_backward) -> (dL_dtex of tex's shape or None, dL_ddirs (B,H,W,L,3) or
+    None): only what ``need_tex`` / ``need_dirs`` ask for is computed."""
+    return _lookup_backward(_TEXTURE_CUBE, dirs, tex, render_layers, (filter_mode, None), grad_out, (need_tex,), (need_dirs,))
+
+
+def texture_volume_cuda(xyz, grid, render_layers=None, filter_mode="linear", boundary_mode="clamp"):
+    """A voxel grid looked up by per-slot positions (include/dm2_hip.h: dm2_texture_cube with DM2_TEX_VOLUME_*).
+
+    xyz (B,H,W,L,3) float32 in the grid's unit cube (x along the grid's last spatial axis), grid (N,N,N,C) or (B,N,N,N,C)
+    float32 channel-last, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is negative or a
+    coordinate is not finite (or beyond 2^24 voxels)."""
+    return _lookup_forward(_TEXTURE_VOLUME, xyz, grid, render_layers, (filter_mode, boundary_mode))
+
+
+def texture_volume_backward_cuda(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out, need_grid, need_xyz):
+    """Gradients of texture_volume_cuda (dm2_texture_cube_backward with DM2_TEX_VOLUME_*) -> (dL_dgrid of grid's shape or None,
+    dL_dxyz (B,H,W,L,3) or None): only what ``need_grid`` / ``need_xyz`` ask for is computed."""
+    return _lookup_backward(_TEXTURE_VOLUME, xyz, grid, render_layers, (filter_mode, boundary_mode), grad_out, (need_grid,),
+                            (need_xyz,))
 
 
 def hash_grid_cuda(xyz, table, render_layers=None, base_resolution=16, growth=1.5, filter_mode="linear", boundary_mode="clamp"):
@@ -1239,37 +1230,50 @@ def hash_grid_cuda(xyz, table, render_layers=None, base_resolution=16, growth=1.
     xyz (B,H,W,L,3) float32 in the field's unit cube, table (NL,T,F) float32, render_layers (B,H,W,L) int32 or None -> out
     (B,H,W,L,NL*F) float32, channel l * F + f; 0 where the id is negative or a coordinate is not finite (or beyond 2^24 voxels
     of the finest level)."""
-    lib = load_library()
-    sizes, (pc, tb, rl, _), dev = _hash_grid_args(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode)
-    B, H, W, L, C = *sizes[:4], sizes[5]
-    if B * H * W * L == 0:
-        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
-    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_cube(*sizes, _ptr(rl), _ptr(pc), _ptr(tb), _ptr(out), _stream(dev)):
-            raise _err(lib, "hash_grid_cuda")
-    return out
+    return _lookup_forward(_HASH_GRID, xyz, table, render_layers, (filter_mode, boundary_mode, base_resolution, growth))
 
 
 def hash_grid_backward_cuda(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode, grad_out, need_table,
                             need_xyz):
     """Gradients of hash_grid_cuda (dm2_texture_cube_backward with DM2_TEX_HASH_GRID_CODE) -> (dL_dtable (NL,T,F) or None,
     dL_dxyz (B,H,W,L,3) or None): only what ``need_table`` / ``need_xyz`` ask for is computed."""
-    lib = load_library()
-    sizes, (pc, tb, rl, go), dev = _hash_grid_args(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode,
-                                                   grad_out)
-    B, H, W, L = sizes[:4]
-    f32 = torch.float32
-    if not (need_table or need_xyz):
-        return None, None
-    dtable = torch.zeros(tuple(table.shape), dtype=f32, device=dev) if need_table else None
-    if B * H * W * L == 0:
-        return dtable, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None
-    dxyz = torch.empty((B, H, W, L, 3), dtype=f32, device=dev) if need_xyz else None      # (every element written)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_cube_backward(*sizes, _ptr(rl), _ptr(pc), _ptr(tb), _ptr(go), _ptr(dtable), _ptr(dxyz), _stream(dev)):
-            raise _err(lib, "hash_grid_backward_cuda")
-    return dtable, dxyz
+    return _lookup_backward(_HASH_GRID, xyz, table, render_layers, (filter_mode, boundary_mode, base_resolution, growth), grad_out,
+                            (need_table,), (need_xyz,))
+
+
+def texture_mip_cuda(uv, uv_da, tex, mip, render_layers=None, boundary_mode="wrap", max_mip_level=None):
+    """Trilinear sampling of a texture and its mip chain (include/dm2_hip.h: dm2_texture_mip).
+
+    uv (B,H,W,L,2), uv_da (B,H,W,L,4) = (du/dX, dv/dX, du/dY, dv/dY), tex (Ht,Wt,C) or (B,Ht,Wt,C), mip = texture_mipmaps_cuda's
+    chain of tex under the same max_mip_level, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is
+    negative or uv / uv_da is not finite."""
+    return _lookup_forward(_TEXTURE_MIP, uv, tex, render_layers, ("linear", boundary_mode), (uv_da, mip, max_mip_level))
+
+
+def texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out, need_tex, need_mip, need_uv):
+    """Gradients of texture_mip_cuda (dm2_texture_mip_backward) -> (dL_dtex of tex's shape, dL_dmip of mip's shape, dL_duv
+    (B,H,W,L,2)), each None unless its ``need_*`` asks for it; uv_da gets none (the level of detail is a constant of the op)."""
+    return _lookup_backward(_TEXTURE_MIP, uv, tex, render_layers, ("linear", boundary_mode), grad_out, (need_tex, need_mip),
+                            (need_uv,), (uv_da, mip, max_mip_level))
+
+
+def texture_cube_mip_cuda(dirs, level, tex, mip, render_layers=None, max_mip_level=None):
+    """A cube map and its mip chain looked up by per-slot directions and levels of detail (include/dm2_hip.h: dm2_texture_mip
+    with DM2_TEX_BOUNDARY_CUBE).
+
+    dirs (B,H,W,L,3), level (B,H,W,L) float32 (level 0 is tex), tex (6,N,N,C) or (B,6,N,N,C), mip (6,T,C) or (B,6,T,C): per face
+    the levels 1 .. nlev-1 in ``mip_layout(N, N, max_mip_level)``'s packing, render_layers (B,H,W,L) int32 or None -> out
+    (B,H,W,L,C) float32; 0 where the id is negative, the direction is not finite or all zero, or the level is not finite."""
+    return _lookup_forward(_TEXTURE_CUBE_MIP, dirs, tex, render_layers, ("linear", None), (level, mip, max_mip_level))
+
+
+def texture_cube_mip_backward_cuda(dirs, level, tex, mip, render_layers, max_mip_level, grad_out, need_tex, need_mip, need_dirs,
+                                   need_level):
+    """Gradients of texture_cube_mip_cuda (dm2_texture_mip_backward with DM2_TEX_BOUNDARY_CUBE) -> (dL_dtex of tex's shape,
+    dL_dmip of mip's shape, dL_ddirs (B,H,W,L,3), dL_dlevel (B,H,W,L)), each None unless its ``need_*`` asks for it.  The
+    direction's and the level's gradients come from one kernel as rows of four floats, split here."""
+    return _lookup_backward(_TEXTURE_CUBE_MIP, dirs, tex, render_layers, ("linear", None), grad_out, (need_tex, need_mip),
+                            (need_dirs, need_level), (level, mip, max_mip_level))
 
 
 def _vertex_normals_args(verts, faces, offsets, corners, normals=None, lens=None, grad_normals=None):
@@ -1486,18 +1490,22 @@ def _mipmap_args(tex, max_mip_level, grad_mip=None):
     return (NB, Ht, Wt, C, _max_level_code(max_mip_level)), shape, ts, dev
 
 
+def _chain_run(lib, export, what, sizes, src, shape, dev):
+    """dst of ``shape`` = one of the two chain exports of src; an empty dst launches nothing."""
+    dst = torch.empty(shape, dtype=torch.float32, device=dev)               # (every element written by the kernels)
+    if dst.numel() != 0:
+        with torch.cuda.device(dev):
+            if getattr(lib, export)(*sizes, _ptr(src), _ptr(dst), _stream(dev)):
+                raise _err(lib, what)
+    return dst
+
+
 def texture_mipmaps_cuda(tex, max_mip_level=None):
     """The mip chain of a texture (include/dm2_hip.h: dm2_texture_mipmaps): tex (Ht,Wt,C) or (B,Ht,Wt,C) float32 -> mip (T,C)
     or (B,T,C) float32, levels 1 .. nlev-1 concatenated (``mip_layout``); T = 0 (and no launch) when no level can be built."""
     lib = load_library()
     sizes, shape, (tx, _), dev = _mipmap_args(tex, max_mip_level)
-    mip = torch.empty(shape, dtype=torch.float32, device=dev)               # (every element written by the kernels)
-    if mip.numel() == 0:
-        return mip
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mipmaps(*sizes, _ptr(tx), _ptr(mip), _stream(dev)):
-            raise _err(lib, "texture_mipmaps_cuda")
-    return mip
+    return _chain_run(lib, "dm2_texture_mipmaps", "texture_mipmaps_cuda", sizes, tx, shape, dev)
 
 
 def texture_mipmaps_backward_cuda(tex, max_mip_level, grad_mip):
@@ -1507,131 +1515,7 @@ def texture_mipmaps_backward_cuda(tex, max_mip_level, grad_mip):
     sizes, shape, (tx, gm), dev = _mipmap_args(tex, max_mip_level, grad_mip)
     if gm.numel() == 0:
         return torch.zeros(tuple(tex.shape), dtype=torch.float32, device=dev)
-    dtex = torch.empty(tuple(tex.shape), dtype=torch.float32, device=dev)  # (every element written)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mipmaps_backward(*sizes, _ptr(gm), _ptr(dtex), _stream(dev)):
-            raise _err(lib, "texture_mipmaps_backward_cuda")
-    return dtex
-
-
-def _texture_mip_args(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out=None):
-    """Checks of a trilinear texture call -> (sizes (B, H, W, L, Ht, Wt, C, view_textures, boundary, max level code),
-    contiguous tensors (uv, uv_da, tex, mip, render_layers, grad_out), device)."""
-    sizes, (uvc, tx, rl, go), dev = _texture_args(uv, tex, render_layers, "linear", boundary_mode, grad_out)
-    B, H, W, L, Ht, Wt, C, per_view = sizes[:8]
-    _bad(tuple(uv_da.shape) != (B, H, W, L, 4), f"uv_da must have dimensions {(B, H, W, L, 4)}, got {tuple(uv_da.shape)}")
-    _, _, T = mip_layout(Ht, Wt, max_mip_level)
-    _bad(Ht * Wt + T >= 2 ** 31, "tex: the texels of all levels must number below 2^31")
-    shape = ((B,) if per_view else ()) + (T, C)
-    _bad(tuple(mip.shape) != shape,
-        f"mip must have dimensions {shape} for tex {tuple(tex.shape)} and max_mip_level {max_mip_level}, got {tuple(mip.shape)}")
-    _require_gpu(uv, uv_da, mip)
-    for name, t in (("uv_da", uv_da), ("mip", mip)):
-        _bad(t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype}")
-    return sizes[:8] + (sizes[9], _max_level_code(max_mip_level)), (uvc, uv_da.contiguous(), tx, mip.contiguous(), rl, go), dev
-
-
-def texture_mip_cuda(uv, uv_da, tex, mip, render_layers=None, boundary_mode="wrap", max_mip_level=None):
-    """Trilinear sampling of a texture and its mip chain (include/dm2_hip.h: dm2_texture_mip).
-
-    uv (B,H,W,L,2), uv_da (B,H,W,L,4) = (du/dX, dv/dX, du/dY, dv/dY), tex (Ht,Wt,C) or (B,Ht,Wt,C), mip = texture_mipmaps_cuda's
-    chain of tex under the same max_mip_level, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is
-    negative or uv / uv_da is not finite."""
-    lib = load_library()
-    sizes, (uvc, da, tx, mp, rl, _), dev = _texture_mip_args(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level)
-    B, H, W, L, C = *sizes[:4], sizes[6]
-    if B * H * W * L == 0:
-        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
-    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mip(*sizes, _ptr(rl), _ptr(uvc), _ptr(da), _ptr(tx), _ptr(mp), _ptr(out), _stream(dev)):
-            raise _err(lib, "texture_mip_cuda")
-    return out
-
-
-def texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out, need_tex, need_mip, need_uv):
-    """Gradients of texture_mip_cuda (dm2_texture_mip_backward) -> (dL_dtex of tex's shape, dL_dmip of mip's shape, dL_duv
-    (B,H,W,L,2)), each None unless its ``need_*`` asks for it; uv_da gets none (the level of detail is a constant of the op)."""
-    lib = load_library()
-    sizes, (uvc, da, tx, mp, rl, go), dev = _texture_mip_args(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level, grad_out)
-    B, H, W, L = sizes[:4]
-    f32 = torch.float32
-    if not (need_tex or need_mip or need_uv):
-        return None, None, None
-    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None      # (summed into)
-    dmip = torch.zeros(tuple(mip.shape), dtype=f32, device=dev) if need_mip else None
-    if B * H * W * L == 0:
-        return dtex, dmip, torch.zeros((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None
-    duv = torch.empty((B, H, W, L, 2), dtype=f32, device=dev) if need_uv else None        # (every element written)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mip_backward(*sizes, _ptr(rl), _ptr(uvc), _ptr(da), _ptr(tx), _ptr(mp), _ptr(go), _ptr(dtex), _ptr(dmip),
-                                        _ptr(duv), _stream(dev)):
-            raise _err(lib, "texture_mip_backward_cuda")
-    return dtex, dmip, duv
-
-
-TEX_BOUNDARY_CUBE = 2          # DM2_TEX_BOUNDARY_CUBE: dm2_texture_mip / dm2_texture_mip_backward only
-
-
-def _texture_cube_mip_args(dirs, level, tex, mip, render_layers, max_mip_level, grad_out=None):
-    """Checks of a cube mip chain call -> (sizes (B, H, W, L, N, N, C, view_textures, DM2_TEX_BOUNDARY_CUBE, max level code),
-    contiguous tensors (dirs, level, tex, mip, render_layers, grad_out), device)."""
-    sizes, (dc, tx, rl, go), dev = _texture_cube_args(dirs, tex, render_layers, "linear", grad_out)
-    B, H, W, L, N, C, per_view = sizes[:7]
-    _bad(tuple(level.shape) != (B, H, W, L), f"mip_level must have dimensions {(B, H, W, L)}, got {tuple(level.shape)}")
-    _, _, T = mip_layout(N, N, max_mip_level)
-    _bad(6 * (N * N + T) >= 2 ** 31, "tex: the texels of all levels of the cube must number below 2^31")
-    shape = ((B,) if per_view else ()) + (6, T, C)
-    _bad(tuple(mip.shape) != shape,
-        f"mip must have dimensions {shape} for tex {tuple(tex.shape)} and max_mip_level {max_mip_level}, got {tuple(mip.shape)}")
-    _require_gpu(dirs, level, mip)
-    for name, t in (("mip_level", level), ("mip", mip)):
-        _bad(t.dtype != torch.float32, f"{name}: expected dtype {torch.float32}, got {t.dtype}")
-    return ((B, H, W, L, N, N, C, per_view, TEX_BOUNDARY_CUBE, _max_level_code(max_mip_level)),
-            (dc, level.contiguous(), tx, mip.contiguous(), rl, go), dev)
-
-
-def texture_cube_mip_cuda(dirs, level, tex, mip, render_layers=None, max_mip_level=None):
-    """A cube map and its mip chain looked up by per-slot directions and levels of detail (include/dm2_hip.h: dm2_texture_mip
-    with DM2_TEX_BOUNDARY_CUBE).
-
-    dirs (B,H,W,L,3), level (B,H,W,L) float32 (level 0 is tex), tex (6,N,N,C) or (B,6,N,N,C), mip (6,T,C) or (B,6,T,C): per face
-    the levels 1 .. nlev-1 in ``mip_layout(N, N, max_mip_level)``'s packing, render_layers (B,H,W,L) int32 or None -> out
-    (B,H,W,L,C) float32; 0 where the id is negative, the direction is not finite or all zero, or the level is not finite."""
-    lib = load_library()
-    sizes, (dc, lv, tx, mp, rl, _), dev = _texture_cube_mip_args(dirs, level, tex, mip, render_layers, max_mip_level)
-    B, H, W, L, C = *sizes[:4], sizes[6]
-    if B * H * W * L == 0:
-        return torch.zeros((B, H, W, L, C), dtype=torch.float32, device=dev)      # no launch
-    out = torch.empty((B, H, W, L, C), dtype=torch.float32, device=dev)         # (every element written by the kernel)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mip(*sizes, _ptr(rl), _ptr(dc), _ptr(lv), _ptr(tx), _ptr(mp), _ptr(out), _stream(dev)):
-            raise _err(lib, "texture_cube_mip_cuda")
-    return out
-
-
-def texture_cube_mip_backward_cuda(dirs, level, tex, mip, render_layers, max_mip_level, grad_out, need_tex, need_mip, need_dirs,
-                                   need_level):
-    """Gradients of texture_cube_mip_cuda (dm2_texture_mip_backward with DM2_TEX_BOUNDARY_CUBE) -> (dL_dtex of tex's shape,
-    dL_dmip of mip's shape, dL_ddirs (B,H,W,L,3), dL_dlevel (B,H,W,L)), each None unless its ``need_*`` asks for it.  The
-    direction's and the level's gradients come from one kernel as rows of four floats, split here."""
-    lib = load_library()
-    sizes, (dc, lv, tx, mp, rl, go), dev = _texture_cube_mip_args(dirs, level, tex, mip, render_layers, max_mip_level, grad_out)
-    B, H, W, L = sizes[:4]
-    f32 = torch.float32
-    if not (need_tex or need_mip or need_dirs or need_level):
-        return None, None, None, None
-    dtex = torch.zeros(tuple(tex.shape), dtype=f32, device=dev) if need_tex else None      # (summed into)
-    dmip = torch.zeros(tuple(mip.shape), dtype=f32, device=dev) if need_mip else None
-    if B * H * W * L == 0:
-        return (dtex, dmip, torch.zeros((B, H, W, L, 3), dtype=f32, device=dev) if need_dirs else None,
-                torch.zeros((B, H, W, L), dtype=f32, device=dev) if need_level else None)
-    rows = torch.empty((B, H, W, L, 4), dtype=f32, device=dev) if need_dirs or need_level else None    # (every element written)
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mip_backward(*sizes, _ptr(rl), _ptr(dc), _ptr(lv), _ptr(tx), _ptr(mp), _ptr(go), _ptr(dtex), _ptr(dmip),
-                                        _ptr(rows), _stream(dev)):
-            raise _err(lib, "texture_cube_mip_backward_cuda")
-    return dtex, dmip, rows[..., :3].contiguous() if need_dirs else None, rows[..., 3].contiguous() if need_level else None
+    return _chain_run(lib, "dm2_texture_mipmaps_backward", "texture_mipmaps_backward_cuda", sizes, gm, tuple(tex.shape), dev)
 
 
 MIP_FILTER_CUBE_GGX = 0x40000000    # DM2_MIP_FILTER_CUBE_GGX: dm2_texture_mipmaps / dm2_texture_mipmaps_backward only
@@ -1665,13 +1549,7 @@ def cube_prefilter_cuda(chain, N, max_mip_level=None):
     y[o] = sum_s K(o,s) Om_s x[s].  A gather: deterministic; T = 0 launches nothing."""
     lib = load_library()
     sizes, x, dev = _cube_prefilter_args(chain, N, max_mip_level)
-    y = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)        # (every element written by the kernel)
-    if y.numel() == 0:
-        return y
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mipmaps(*sizes, _ptr(x), _ptr(y), _stream(dev)):
-            raise _err(lib, "cube_prefilter_cuda")
-    return y
+    return _chain_run(lib, "dm2_texture_mipmaps", "cube_prefilter_cuda", sizes, x, tuple(x.shape), dev)
 
 
 def cube_prefilter_transpose_cuda(grad, N, max_mip_level=None):
@@ -1679,13 +1557,7 @@ def cube_prefilter_transpose_cuda(grad, N, max_mip_level=None):
     shape -> xbar[s] = Om_s sum_o K(o,s) grad[o], the same shape.  A gather as well: deterministic."""
     lib = load_library()
     sizes, g, dev = _cube_prefilter_args(grad, N, max_mip_level, "grad")
-    xbar = torch.empty(tuple(g.shape), dtype=torch.float32, device=dev)     # (every element written by the kernel)
-    if xbar.numel() == 0:
-        return xbar
-    with torch.cuda.device(dev):
-        if lib.dm2_texture_mipmaps_backward(*sizes, _ptr(g), _ptr(xbar), _stream(dev)):
-            raise _err(lib, "cube_prefilter_transpose_cuda")
-    return xbar
+    return _chain_run(lib, "dm2_texture_mipmaps_backward", "cube_prefilter_transpose_cuda", sizes, g, tuple(g.shape), dev)
 
 
 COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1    # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*

@@ -1054,7 +1054,33 @@ class InterpolateFunction(torch.autograd.Function):
         return None, dbary, dattr, None
 
 
-class TextureFunction(torch.autograd.Function):
+class _LookupFunction(torch.autograd.Function):
+    """The body of the per-slot lookup Functions.  Their inputs are ``tensors`` leading tensors (detached and saved), render_layers
+    (saved, may be None) and the modes; a subclass names its ``_C`` entry pair (``<entry>_cuda``, ``<entry>_backward_cuda``, looked
+    up on ``_C`` at call time) and, in ``grads``, the input positions that receive a gradient, in the order in which the backward
+    entry takes their ``need_*`` flags and returns their gradients."""
+    entry, tensors, grads = None, 0, ()
+
+    @classmethod
+    def forward(cls, ctx, *inputs):
+        detached = [t.detach() for t in inputs[:cls.tensors]]
+        ctx.modes = inputs[cls.tensors + 1:]
+        out = getattr(_C, cls.entry + "_cuda")(*detached, *inputs[cls.tensors:])
+        _save_optional(ctx, *detached, inputs[cls.tensors])
+        return out
+
+    @classmethod
+    def backward(cls, ctx, grad_out):
+        needs = [ctx.needs_input_grad[i] for i in cls.grads]
+        grads = [None] * (cls.tensors + 1 + len(ctx.modes))
+        if grad_out is not None and any(needs):
+            got = getattr(_C, cls.entry + "_backward_cuda")(*_saved_optional(ctx), *ctx.modes, grad_out, *needs)
+            for i, g in zip(cls.grads, got):
+                grads[i] = g
+        return tuple(grads)
+
+
+class TextureFunction(_LookupFunction):
     """out = the texture at each slot's uv (``_C.texture_cuda``): bilinear a + fy (b - a) over the four texels round
     (u Wt - 0.5, v Ht - 0.5), or the nearest texel; wrap or clamp addressing.
 
@@ -1064,24 +1090,10 @@ class TextureFunction(torch.autograd.Function):
     ``needs_input_grad`` asks for are computed: no texel scatter when only uv requires grad, and the reverse.
     """
 
-    @staticmethod
-    def forward(ctx, uv, tex, render_layers, filter_mode, boundary_mode):
-        out = _C.texture_cuda(uv.detach(), tex.detach(), render_layers, filter_mode, boundary_mode)
-        ctx.modes = (filter_mode, boundary_mode)
-        _save_optional(ctx, uv.detach(), tex.detach(), render_layers)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        need_uv, need_tex = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if grad_out is None or not (need_uv or need_tex):
-            return None, None, None, None, None
-        uv, tex, render_layers = _saved_optional(ctx)
-        dtex, duv = _C.texture_backward_cuda(uv, tex, render_layers, *ctx.modes, grad_out, need_tex, need_uv)
-        return duv, dtex, None, None, None
+    entry, tensors, grads = "texture", 2, (1, 0)
 
 
-class TextureCubeFunction(torch.autograd.Function):
+class TextureCubeFunction(_LookupFunction):
     """out = the cube map in each slot's direction (``_C.texture_cube_cuda``): the major axis picks the face, bilinear over four
     taps that continue onto the adjacent face across an edge (three renormalised taps at a cube corner), or the nearest texel.
 
@@ -1091,24 +1103,10 @@ class TextureCubeFunction(torch.autograd.Function):
     get zero.  Only the gradients ``needs_input_grad`` asks for are computed.
     """
 
-    @staticmethod
-    def forward(ctx, dirs, tex, render_layers, filter_mode):
-        out = _C.texture_cube_cuda(dirs.detach(), tex.detach(), render_layers, filter_mode)
-        ctx.filter_mode = filter_mode
-        _save_optional(ctx, dirs.detach(), tex.detach(), render_layers)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        need_dirs, need_tex = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if grad_out is None or not (need_dirs or need_tex):
-            return None, None, None, None
-        dirs, tex, render_layers = _saved_optional(ctx)
-        dtex, ddir = _C.texture_cube_backward_cuda(dirs, tex, render_layers, ctx.filter_mode, grad_out, need_tex, need_dirs)
-        return ddir, dtex, None, None
+    entry, tensors, grads = "texture_cube", 2, (1, 0)
 
 
-class TextureVolumeFunction(torch.autograd.Function):
+class TextureVolumeFunction(_LookupFunction):
     """out = the voxel grid at each slot's position (``_C.texture_volume_cuda``): trilinear a0 + fz (a1 - a0) over the bilinear
     blends of the two planes round (x N - 0.5, y N - 0.5, z N - 0.5), or the nearest voxel; clamp or wrap addressing.
 
@@ -1118,24 +1116,10 @@ class TextureVolumeFunction(torch.autograd.Function):
     gradients ``needs_input_grad`` asks for are computed: no voxel scatter when only xyz requires grad, and the reverse.
     """
 
-    @staticmethod
-    def forward(ctx, xyz, grid, render_layers, filter_mode, boundary_mode):
-        out = _C.texture_volume_cuda(xyz.detach(), grid.detach(), render_layers, filter_mode, boundary_mode)
-        ctx.modes = (filter_mode, boundary_mode)
-        _save_optional(ctx, xyz.detach(), grid.detach(), render_layers)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        need_xyz, need_grid = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if grad_out is None or not (need_xyz or need_grid):
-            return None, None, None, None, None
-        xyz, grid, render_layers = _saved_optional(ctx)
-        dgrid, dxyz = _C.texture_volume_backward_cuda(xyz, grid, render_layers, *ctx.modes, grad_out, need_grid, need_xyz)
-        return dxyz, dgrid, None, None, None
+    entry, tensors, grads = "texture_volume", 2, (1, 0)
 
 
-class HashGridFunction(torch.autograd.Function):
+class HashGridFunction(_LookupFunction):
     """out = the hash grid's levels at each slot's position (``_C.hash_grid_cuda``): per level ``TextureVolumeFunction``'s lookup
     of a virtual R_l^3 grid whose voxels live in rows of table[l], by position while the level fits and by hash after that.
 
@@ -1145,21 +1129,7 @@ class HashGridFunction(torch.autograd.Function):
     and get zero.  Only the gradients ``needs_input_grad`` asks for are computed.
     """
 
-    @staticmethod
-    def forward(ctx, xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode):
-        ctx.modes = (base_resolution, growth, filter_mode, boundary_mode)
-        out = _C.hash_grid_cuda(xyz.detach(), table.detach(), render_layers, *ctx.modes)
-        _save_optional(ctx, xyz.detach(), table.detach(), render_layers)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        need_xyz, need_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if grad_out is None or not (need_xyz or need_table):
-            return (None,) * 7
-        xyz, table, render_layers = _saved_optional(ctx)
-        dtable, dxyz = _C.hash_grid_backward_cuda(xyz, table, render_layers, *ctx.modes, grad_out, need_table, need_xyz)
-        return dxyz, dtable, None, None, None, None, None
+    entry, tensors, grads = "hash_grid", 2, (1, 0)
 
 
 class BaryDerivativesFunction(torch.autograd.Function):
@@ -1222,7 +1192,7 @@ class CubePrefilterFunction(torch.autograd.Function):
         return _C.cube_prefilter_transpose_cuda(grad_out, *ctx.sizes), None, None
 
 
-class TextureMipFunction(torch.autograd.Function):
+class TextureMipFunction(_LookupFunction):
     """out = the trilinear sample of a texture and its mip chain at each slot's uv (``_C.texture_mip_cuda``): the bilinear
     samples c_j, c_{j+1} of the two levels round the slot's level of detail, c_j + f (c_{j+1} - c_j); one level at or below
     level 0 and beyond the last.
@@ -1233,25 +1203,10 @@ class TextureMipFunction(torch.autograd.Function):
     levels' finite differences . g to (u, v); uv_da gets none: the level of detail is a constant of the op.  Only the gradients
     ``needs_input_grad`` asks for are computed."""
 
-    @staticmethod
-    def forward(ctx, uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level):
-        out = _C.texture_mip_cuda(uv.detach(), uv_da.detach(), tex.detach(), mip.detach(), render_layers, boundary_mode, max_mip_level)
-        ctx.modes = (boundary_mode, max_mip_level)
-        _save_optional(ctx, uv.detach(), uv_da.detach(), tex.detach(), mip.detach(), render_layers)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        need_uv, need_tex, need_mip = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        if grad_out is None or not (need_uv or need_tex or need_mip):
-            return (None,) * 7
-        uv, uv_da, tex, mip, render_layers = _saved_optional(ctx)
-        dtex, dmip, duv = _C.texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, *ctx.modes, grad_out, need_tex, need_mip,
-                                                       need_uv)
-        return duv, None, dtex, dmip, None, None, None
+    entry, tensors, grads = "texture_mip", 4, (2, 3, 0)
 
 
-class TextureCubeMipFunction(torch.autograd.Function):
+class TextureCubeMipFunction(_LookupFunction):
     """out = the cube map and its mip chain in each slot's direction at the slot's level of detail
     (``_C.texture_cube_mip_cuda``): c_j + f (c_{j+1} - c_j) of the cube samples of the two levels round the level; one level
     at or below level 0 and at or beyond the last.
@@ -1262,22 +1217,7 @@ class TextureCubeMipFunction(torch.autograd.Function):
     direction gradients to dirs, and g . (c_{j+1} - c_j) to its level (0 where the level is clamped).  Only the gradients
     ``needs_input_grad`` asks for are computed."""
 
-    @staticmethod
-    def forward(ctx, dirs, mip_level, tex, mip, render_layers, max_mip_level):
-        out = _C.texture_cube_mip_cuda(dirs.detach(), mip_level.detach(), tex.detach(), mip.detach(), render_layers, max_mip_level)
-        ctx.max_mip_level = max_mip_level
-        _save_optional(ctx, dirs.detach(), mip_level.detach(), tex.detach(), mip.detach(), render_layers)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        need_dirs, need_level, need_tex, need_mip = ctx.needs_input_grad[:4]
-        if grad_out is None or not (need_dirs or need_level or need_tex or need_mip):
-            return (None,) * 6
-        dirs, mip_level, tex, mip, render_layers = _saved_optional(ctx)
-        dtex, dmip, ddir, dlevel = _C.texture_cube_mip_backward_cuda(dirs, mip_level, tex, mip, render_layers, ctx.max_mip_level, grad_out,
-                                                                     need_tex, need_mip, need_dirs, need_level)
-        return ddir, dlevel, dtex, dmip, None, None
+    entry, tensors, grads = "texture_cube_mip", 4, (2, 3, 0, 1)
 
 
 class CompositeFunction(torch.autograd.Function):

@@ -520,6 +520,21 @@ int dm2_interpolate_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
     return 0;
 }
 
+// The launch bound the lookup ops share: 256 slots per block, one grid row per view (hash grid: per view and level).
+static int check_slot_grid(const char* op, int64_t S, int64_t views, int64_t H) {
+    if ((S + 255) / 256 > 0x7FFFFFFF || views > 65535 || (H + dm2::TILE - 1) / dm2::TILE > 65535)
+        return fail(std::string(op) + ": too many slots, rows or views");
+    return 0;
+}
+
+// A nearest filter is piecewise constant in the coordinate: its gradient, S * k floats, is zeroed on the stream and dropped.
+static int zero_nearest_grad(int filter, float** grad, int64_t S, int k, void* stream) {
+    if (!*grad || filter != DM2_TEX_FILTER_NEAREST) return 0;
+    DM2_HIP(hipMemsetAsync(*grad, 0, (size_t)S * k * sizeof(float), (hipStream_t)stream));
+    *grad = nullptr;
+    return 0;
+}
+
 static int check_texture_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t filter,
                                int32_t boundary) {
     if (B < 0 || H < 0 || W < 0 || L < 0) return fail("texture: negative size");
@@ -528,9 +543,7 @@ static int check_texture_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32
     if (C < 1) return fail("texture: C must be at least 1");
     if (filter != DM2_TEX_FILTER_NEAREST && filter != DM2_TEX_FILTER_LINEAR) return fail("texture: unknown filter");
     if (boundary != DM2_TEX_BOUNDARY_WRAP && boundary != DM2_TEX_BOUNDARY_CLAMP) return fail("texture: unknown boundary");
-    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || B > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
-        return fail("texture: too many slots, rows or views");
-    return 0;
+    return check_slot_grid("texture", (int64_t)B * H * W * L, B, H);
 }
 
 int dm2_texture(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
@@ -551,10 +564,7 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dtex && !dL_duv)) return 0;
     if (!uv || !dL_dout) return fail("texture_backward: uv and dL_dout must not be null");
-    if (dL_duv && filter == DM2_TEX_FILTER_NEAREST) {                     // piecewise constant in uv
-        DM2_HIP(hipMemsetAsync(dL_duv, 0, (size_t)S * 2 * sizeof(float), (hipStream_t)stream));
-        dL_duv = nullptr;
-    }
+    if (zero_nearest_grad(filter, &dL_duv, S, 2, stream)) return 1;
     if (dL_duv && !tex) return fail("texture_backward: tex must not be null");
     if (dL_dtex || dL_duv)
         dm2::launch_texture_backward(B, H, W, L, Ht, Wt, C, view_textures, filter, boundary, render_layers, uv, tex, dL_dout,
@@ -569,9 +579,7 @@ static int check_texture_cube_sizes(int32_t B, int32_t H, int32_t W, int32_t L, 
     if ((int64_t)6 * N * N > 0x7FFFFFFF) return fail("texture_cube: 6 * N * N must be below 2^31");
     if (C < 1) return fail("texture_cube: C must be at least 1");
     if (filter != DM2_TEX_FILTER_NEAREST && filter != DM2_TEX_FILTER_LINEAR) return fail("texture_cube: unknown filter");
-    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || B > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
-        return fail("texture_cube: too many slots, rows or views");
-    return 0;
+    return check_slot_grid("texture_cube", (int64_t)B * H * W * L, B, H);
 }
 
 // filter carries DM2_TEX_VOLUME_CLAMP or DM2_TEX_VOLUME_WRAP: Renderer.texture3d, a voxel grid looked up by positions.
@@ -605,10 +613,7 @@ static int texture_volume_backward(int32_t B, int32_t H, int32_t W, int32_t L, i
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dgrid && !dL_dxyz)) return 0;
     if (!xyz || !dL_dout) return fail("texture_cube_backward: a volume's xyz and dL_dout must not be null");
-    if (dL_dxyz && vfilter == DM2_TEX_FILTER_NEAREST) {                   // piecewise constant in the position
-        DM2_HIP(hipMemsetAsync(dL_dxyz, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
-        dL_dxyz = nullptr;
-    }
+    if (zero_nearest_grad(vfilter, &dL_dxyz, S, 3, stream)) return 1;
     if (dL_dxyz && !grid) return fail("texture_cube_backward: a volume's grid must not be null");
     if (dL_dgrid || dL_dxyz)
         dm2::launch_texture_volume_backward(B, H, W, L, N, C, view_textures, vfilter, vboundary, render_layers, xyz, grid, dL_dout,
@@ -650,9 +655,7 @@ static int check_hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N
         h->R[l] = (int)r;
         r = (r * q) >> 4;
     }
-    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || (int64_t)B * h->NL > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
-        return fail("texture_cube: too many slots, rows or views");
-    return 0;
+    return check_slot_grid("texture_cube", (int64_t)B * H * W * L, (int64_t)B * h->NL, H);
 }
 
 static int hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
@@ -676,10 +679,7 @@ static int hash_grid_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dtable && !dL_dxyz)) return 0;
     if (!dL_dout) return fail("texture_cube_backward: a hash grid's dL_dout must not be null");
-    if (dL_dxyz && h.filter == DM2_TEX_FILTER_NEAREST) {                  // piecewise constant in the position
-        DM2_HIP(hipMemsetAsync(dL_dxyz, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
-        dL_dxyz = nullptr;
-    }
+    if (zero_nearest_grad(h.filter, &dL_dxyz, S, 3, stream)) return 1;
     if (dL_dxyz && !table) return fail("texture_cube_backward: a hash grid's table must not be null");
     if (dL_dtable || dL_dxyz)
         dm2::launch_hash_grid_backward(B, H, W, L, h.NL, h.T, h.F, h.R, h.filter, h.boundary, render_layers, xyz, table, dL_dout,
@@ -714,10 +714,7 @@ int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dtex && !dL_ddir)) return 0;
     if (!dirs || !dL_dout) return fail("texture_cube_backward: dirs and dL_dout must not be null");
-    if (dL_ddir && filter == DM2_TEX_FILTER_NEAREST) {                    // piecewise constant in the direction
-        DM2_HIP(hipMemsetAsync(dL_ddir, 0, (size_t)S * 3 * sizeof(float), (hipStream_t)stream));
-        dL_ddir = nullptr;
-    }
+    if (zero_nearest_grad(filter, &dL_ddir, S, 3, stream)) return 1;
     if (dL_ddir && !tex) return fail("texture_cube_backward: tex must not be null");
     if (dL_dtex || dL_ddir)
         dm2::launch_texture_cube_backward(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, dL_dout, dL_dtex,

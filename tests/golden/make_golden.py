@@ -27,6 +27,12 @@ and records
                       (``--only-frontend-calls``, and only that flag writes it: a full run leaves it alone); regenerate only
                       when that contract is meant to change.
 
+  lookup_shim_errors.json, lookup_shim_calls.json
+                      what the shim (dmesh2_renderer_amd/_C.py) raises on malformed arguments of the per-slot lookup ops
+                      and what it hands to the library for well-formed ones, as tests/shim_trace.py records both on CPU
+                      tensors.  Need neither the reference nor a GPU (``--only-shim-errors``, ``--only-shim-calls``, and
+                      only those flags write them); regenerate only when that contract is meant to change.
+
 Only arrays are written; no reference source or bytecode is copied.  The GPU
 box never runs this script (no /root/reference there) -- tests read the .npz.
 """
@@ -393,9 +399,25 @@ def make_frontend_calls():
     print("frontend_calls.json :", len(trace), "cases,", sum(len(v) for v in trace.values()), "calls")
 
 
+def make_shim(name, what):
+    import json
+    sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+    import shim_trace
+    table = getattr(shim_trace, what)()
+    with open(os.path.join(HERE, name), "w") as f:                      # one case per line
+        f.write("{\n" + ",\n".join(json.dumps(k) + ": " + json.dumps(v, sort_keys=True) for k, v in sorted(table.items())) + "\n}\n")
+    print(name, ":", len(table), "cases")
+
+
 def main():
     if "--only-frontend-calls" in sys.argv:
         make_frontend_calls()
+        return
+    if "--only-shim-errors" in sys.argv or "--only-shim-calls" in sys.argv:
+        if "--only-shim-errors" in sys.argv:
+            make_shim("lookup_shim_errors.json", "errors")
+        if "--only-shim-calls" in sys.argv:
+            make_shim("lookup_shim_calls.json", "calls")
         return
     scenes = load_scenes()
     ref, stub = import_reference()
