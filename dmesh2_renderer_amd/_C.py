@@ -32,16 +32,14 @@ and a cube map looked up by such an image of directions (Renderer.texture's boun
     texture_cube_cuda(dirs, tex, render_layers, filter_mode) -> out,
     texture_cube_backward_cuda(...those 4..., grad_out, need_tex, need_dirs) -> (dL/dtex, dL/ddirs)
 
-and a voxel grid looked up by such an image of positions (Renderer.texture3d; the same two C symbols under DM2_TEX_VOLUME_*):
+and a voxel grid looked up by such an image of positions (Renderer.texture3d):
 
     texture_volume_cuda(xyz, grid, render_layers, filter_mode, boundary_mode) -> out,
     texture_volume_backward_cuda(...those 5..., grad_out, need_grid, need_xyz) -> (dL/dgrid, dL/dxyz)
 
-and a multiresolution hash encoding looked up by such positions (Renderer.hash_grid; the same two C symbols under
-DM2_TEX_HASH_GRID_CODE):
+and a multiresolution hash encoding looked up by such positions (Renderer.hash_grid):
 
     hash_grid_resolutions(num_levels, base_resolution, growth) -> [R_0, ..., R_{NL-1}],
-    hash_grid_code(log2_rows, num_levels, growth, filter_mode, boundary_mode) -> the filter word,
     hash_grid_cuda(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode) -> out,
     hash_grid_backward_cuda(...those 7..., grad_out, need_table, need_xyz) -> (dL/dtable, dL/dxyz)
 
@@ -52,15 +50,13 @@ and its mip-mapped filter (Renderer.bary_derivatives, Renderer.texture_mipmaps, 
     texture_mip_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode, max_mip_level) -> out,
     texture_mip_backward_cuda(...those 7..., grad_out, need_tex, need_mip, need_uv) -> (dL/dtex, dL/dmip, dL/duv)
 
-and the cube's mip chain at a level of detail per slot (texture's "linear-mipmap-linear" with "cube" and mip_level; the same
-two C symbols under DM2_TEX_BOUNDARY_CUBE):
+and the cube's mip chain at a level of detail per slot (texture's "linear-mipmap-linear" with "cube" and mip_level):
 
     texture_cube_mip_cuda(dirs, level, tex, mip, render_layers, max_mip_level) -> out,
     texture_cube_mip_backward_cuda(...those 6..., grad_out, need_tex, need_mip, need_dirs, need_level)
         -> (dL/dtex, dL/dmip, dL/ddirs, dL/dlevel)
 
-and the GGX prefilter that turns a cube's box chain into a roughness chain (Renderer.cube_prefilter; dm2_texture_mipmaps and
-its backward under DM2_MIP_FILTER_CUBE_GGX):
+and the GGX prefilter that turns a cube's box chain into a roughness chain (Renderer.cube_prefilter):
 
     cube_prefilter_cuda(chain, N, max_mip_level) -> filtered chain,  cube_prefilter_transpose_cuda(grad, N, max_mip_level) -> xbar
 
@@ -114,7 +110,7 @@ DM2_FLAG_NO_PAIR_POOL = 64
 SCRATCH_FACE, SCRATCH_IMAGE, SCRATCH_BINNING, SCRATCH_LAYER_IMAGE, SCRATCH_LAYER_TETS, SCRATCH_PAIR_POOL, SCRATCH_TIE_QUEUE = range(7)
 # what a forward left for its backward (include/dm2_hip.h DM2_FWD_*)
 FWD_UNKNOWN, FWD_NONE, FWD_MASKS, FWD_POOL, FWD_POINT = 0, 1, 2, 3, 4
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # opt-in flags applied to every call (tests use this for the corrected-gradient mode)
 _flags = 0
@@ -193,6 +189,10 @@ EXPORTS = {
     "dm2_texture_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
     "dm2_texture_cube": (ctypes.c_int, [_i32] * 8 + [_vp] * 5),
     "dm2_texture_cube_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 7),
+    "dm2_texture_volume": (ctypes.c_int, [_i32] * 9 + [_vp] * 5),
+    "dm2_texture_volume_backward": (ctypes.c_int, [_i32] * 9 + [_vp] * 7),
+    "dm2_hash_grid": (ctypes.c_int, [_i32] * 11 + [_vp] * 5),
+    "dm2_hash_grid_backward": (ctypes.c_int, [_i32] * 11 + [_vp] * 7),
     "dm2_vertex_normals_scratch_bytes": (_sz, [_i32] * 3),
     "dm2_vertex_normals": (ctypes.c_int, [_i32] * 3 + [_vp] * 5 + [_sz] + [_vp] * 3),
     "dm2_vertex_normals_backward": (ctypes.c_int, [_i32] * 3 + [_vp] * 8 + [_sz] + [_vp] * 2),
@@ -203,6 +203,10 @@ EXPORTS = {
     "dm2_texture_mipmaps_backward": (ctypes.c_int, [_i32] * 5 + [_vp] * 3),
     "dm2_texture_mip": (ctypes.c_int, [_i32] * 10 + [_vp] * 7),
     "dm2_texture_mip_backward": (ctypes.c_int, [_i32] * 10 + [_vp] * 10),
+    "dm2_texture_cube_mip": (ctypes.c_int, [_i32] * 8 + [_vp] * 7),
+    "dm2_texture_cube_mip_backward": (ctypes.c_int, [_i32] * 8 + [_vp] * 10),
+    "dm2_cube_prefilter": (ctypes.c_int, [_i32] * 4 + [_vp] * 3),
+    "dm2_cube_prefilter_backward": (ctypes.c_int, [_i32] * 4 + [_vp] * 3),
     "dm2_composite": (ctypes.c_int, [_i32] * 7 + [_vp] * 9),
     "dm2_composite_backward": (ctypes.c_int, [_i32] * 7 + [_vp] * 10),
     "dm2_coverage": (ctypes.c_int, [_i32] * 6 + [ctypes.c_float, ctypes.POINTER(Window)] + [_vp] * 6),
@@ -966,9 +970,10 @@ def interpolate_backward_cuda(render_layers, bary, attr, attr_faces, grad_out, n
 #    record and two thin wrappers; ``_lookup_args`` / ``_lookup_forward`` / ``_lookup_backward`` do the rest. -------------------
 TEX_FILTERS = {"nearest": 0, "linear": 1}        # include/dm2_hip.h DM2_TEX_FILTER_*
 TEX_BOUNDARIES = {"wrap": 0, "clamp": 1}         # DM2_TEX_BOUNDARY_*
-TEX_VOLUME_BOUNDARIES = {"clamp": 0x100, "wrap": 0x200}      # DM2_TEX_VOLUME_*: OR-ed into dm2_texture_cube's filter
-TEX_BOUNDARY_CUBE = 2          # DM2_TEX_BOUNDARY_CUBE: dm2_texture_mip / dm2_texture_mip_backward only
-TEX_HASH_GRID = 0x800                                        # DM2_TEX_HASH_GRID
+# ABI 7's words for a volume's boundary, then OR-ed into dm2_texture_cube's filter.  Nothing here sends them and the library
+# refuses them as unknown filters.  The name stays because ABI 7's test modules read it when they are imported: without it
+# that suite cannot even be collected against this library, with it exactly the tests of the retired encoding fail.
+TEX_VOLUME_BOUNDARIES = {"clamp": 0x100, "wrap": 0x200}
 HASH_GRID_FEATURES = (1, 2, 4, 8)
 HASH_GRID_MAX_LEVELS, HASH_GRID_MAX_RESOLUTION = 32, 2 ** 20
 HASH_GRID_LOG2_ROWS = (4, 24)
@@ -983,7 +988,7 @@ def _hash_grid_q(growth):
 
 
 def hash_grid_resolutions(num_levels, base_resolution=16, growth=1.5):
-    """The level resolutions of a hash grid (include/dm2_hip.h, DM2_TEX_HASH_GRID_CODE): R_0 = base_resolution,
+    """The level resolutions of a hash grid (include/dm2_hip.h, dm2_hash_grid): R_0 = base_resolution,
     R_{l+1} = (R_l * q) >> 4 with q = 16 growth.  ValueError for a growth that is no multiple of 1/16 in [1.0625, 2], fewer than
     1 or more than 32 levels, a base resolution below 1 or a finest level above 2^20."""
     q = _hash_grid_q(growth)
@@ -998,13 +1003,6 @@ def hash_grid_resolutions(num_levels, base_resolution=16, growth=1.5):
     if res[-1] > HASH_GRID_MAX_RESOLUTION:
         raise ValueError(f"the finest level's resolution must not exceed 2^20, got {res[-1]}")
     return res
-
-
-def hash_grid_code(log2_rows, num_levels, growth=1.5, filter_mode="linear", boundary_mode="clamp"):
-    """dm2_texture_cube's filter word of a hash grid call: DM2_TEX_HASH_GRID_CODE(log2_rows, num_levels, 16 growth) | the filter |
-    the volume's boundary bit."""
-    return (TEX_HASH_GRID | (int(log2_rows) << 12) | ((int(num_levels) - 1) << 17) | ((_hash_grid_q(growth) - 17) << 22)
-            | TEX_FILTERS[filter_mode] | TEX_VOLUME_BOUNDARIES[boundary_mode])
 
 
 # The table checks of each op: (table, B, filter_mode, boundary_mode, ...) -> (the ABI words behind (B, H, W, L), C).
@@ -1038,7 +1036,7 @@ def _volume_table(grid, B, filter_mode, boundary_mode):
     _bad(N < 1, "grid must have at least one voxel")
     _bad(C < 1, "grid must have at least one channel")
     _bad(N * N * N >= 2 ** 31, "grid: N * N * N must be below 2^31")
-    return (N, C, 1 if grid.dim() == 5 else 0, TEX_FILTERS[filter_mode] | TEX_VOLUME_BOUNDARIES[boundary_mode]), C
+    return (N, C, 1 if grid.dim() == 5 else 0, TEX_FILTERS[filter_mode], TEX_BOUNDARIES[boundary_mode]), C
 
 
 def _hash_grid_table(table, B, filter_mode, boundary_mode, base_resolution, growth):
@@ -1052,10 +1050,9 @@ def _hash_grid_table(table, B, filter_mode, boundary_mode, base_resolution, grow
     _bad(NL * T * F >= 2 ** 31, "table: NL * T * F must be below 2^31")
     try:
         hash_grid_resolutions(NL, base_resolution, growth)
-        code = hash_grid_code(log2T, NL, growth, filter_mode, boundary_mode)
     except ValueError as e:
         raise RuntimeError(str(e)) from None
-    return (int(base_resolution), NL * F, 0, code), NL * F
+    return (int(base_resolution), log2T, NL, F, _hash_grid_q(growth), TEX_FILTERS[filter_mode], TEX_BOUNDARIES[boundary_mode]), NL * F
 
 
 # The chain checks of the two mip-mapped ops: (the table's words, B, max_mip_level) -> (the ABI words, mip's shape).
@@ -1070,7 +1067,7 @@ def _cube_chain(words, B, max_mip_level):
     N, C, per_view, _ = words
     _, _, T = mip_layout(N, N, max_mip_level)
     _bad(6 * (N * N + T) >= 2 ** 31, "tex: the texels of all levels of the cube must number below 2^31")
-    return (N, N, C, per_view, TEX_BOUNDARY_CUBE, _max_level_code(max_mip_level)), ((B,) if per_view else ()) + (6, T, C)
+    return (N, C, per_view, _max_level_code(max_mip_level)), ((B,) if per_view else ()) + (6, T, C)
 
 
 class _Lookup(NamedTuple):
@@ -1091,13 +1088,14 @@ class _Lookup(NamedTuple):
 
 _TEXTURE = _Lookup("texture", "uv", 2, "tex", TEX_BOUNDARIES, _texture_table, "dm2_texture", "dm2_texture_backward")
 _TEXTURE_CUBE = _Lookup("texture_cube", "dirs", 3, "tex", None, _cube_table, "dm2_texture_cube", "dm2_texture_cube_backward")
-_TEXTURE_VOLUME = _Lookup("texture_volume", "xyz", 3, "grid", TEX_VOLUME_BOUNDARIES, _volume_table, "dm2_texture_cube",
-                          "dm2_texture_cube_backward")
-_HASH_GRID = _TEXTURE_VOLUME._replace(name="hash_grid", table="table", check_table=_hash_grid_table)
+_TEXTURE_VOLUME = _Lookup("texture_volume", "xyz", 3, "grid", TEX_BOUNDARIES, _volume_table, "dm2_texture_volume",
+                          "dm2_texture_volume_backward")
+_HASH_GRID = _Lookup("hash_grid", "xyz", 3, "table", TEX_BOUNDARIES, _hash_grid_table, "dm2_hash_grid", "dm2_hash_grid_backward")
 _TEXTURE_MIP = _TEXTURE._replace(name="texture_mip", forward="dm2_texture_mip", backward="dm2_texture_mip_backward",
                                  slot_input=("uv_da", (4,)), check_chain=_texture_chain)
-_TEXTURE_CUBE_MIP = _TEXTURE_CUBE._replace(name="texture_cube_mip", forward="dm2_texture_mip", backward="dm2_texture_mip_backward",
-                                           slot_input=("mip_level", ()), check_chain=_cube_chain, row=4, split=(slice(0, 3), 3))
+_TEXTURE_CUBE_MIP = _Lookup("texture_cube_mip", "dirs", 3, "tex", None, _cube_table, "dm2_texture_cube_mip",
+                            "dm2_texture_cube_mip_backward", slot_input=("mip_level", ()), check_chain=_cube_chain, row=4,
+                            split=(slice(0, 3), 3))
 
 
 def _lookup_args(op, coord, table, render_layers, modes, grad_out=None, chain=None):
@@ -1208,7 +1206,7 @@ def texture_cube_backward_cuda(dirs, tex, render_layers, filter_mode, grad_out, 
 
 
 def texture_volume_cuda(xyz, grid, render_layers=None, filter_mode="linear", boundary_mode="clamp"):
-    """A voxel grid looked up by per-slot positions (include/dm2_hip.h: dm2_texture_cube with DM2_TEX_VOLUME_*).
+    """A voxel grid looked up by per-slot positions (include/dm2_hip.h: dm2_texture_volume).
 
     xyz (B,H,W,L,3) float32 in the grid's unit cube (x along the grid's last spatial axis), grid (N,N,N,C) or (B,N,N,N,C)
     float32 channel-last, render_layers (B,H,W,L) int32 or None -> out (B,H,W,L,C) float32; 0 where the id is negative or a
@@ -1217,15 +1215,14 @@ def texture_volume_cuda(xyz, grid, render_layers=None, filter_mode="linear", bou
 
 
 def texture_volume_backward_cuda(xyz, grid, render_layers, filter_mode, boundary_mode, grad_out, need_grid, need_xyz):
-    """Gradients of texture_volume_cuda (dm2_texture_cube_backward with DM2_TEX_VOLUME_*) -> (dL_dgrid of grid's shape or None,
+    """Gradients of texture_volume_cuda (dm2_texture_volume_backward) -> (dL_dgrid of grid's shape or None,
     dL_dxyz (B,H,W,L,3) or None): only what ``need_grid`` / ``need_xyz`` ask for is computed."""
     return _lookup_backward(_TEXTURE_VOLUME, xyz, grid, render_layers, (filter_mode, boundary_mode), grad_out, (need_grid,),
                             (need_xyz,))
 
 
 def hash_grid_cuda(xyz, table, render_layers=None, base_resolution=16, growth=1.5, filter_mode="linear", boundary_mode="clamp"):
-    """A multiresolution hash encoding looked up by per-slot positions (include/dm2_hip.h: dm2_texture_cube with
-    DM2_TEX_HASH_GRID_CODE).
+    """A multiresolution hash encoding looked up by per-slot positions (include/dm2_hip.h: dm2_hash_grid).
 
     xyz (B,H,W,L,3) float32 in the field's unit cube, table (NL,T,F) float32, render_layers (B,H,W,L) int32 or None -> out
     (B,H,W,L,NL*F) float32, channel l * F + f; 0 where the id is negative or a coordinate is not finite (or beyond 2^24 voxels
@@ -1235,7 +1232,7 @@ def hash_grid_cuda(xyz, table, render_layers=None, base_resolution=16, growth=1.
 
 def hash_grid_backward_cuda(xyz, table, render_layers, base_resolution, growth, filter_mode, boundary_mode, grad_out, need_table,
                             need_xyz):
-    """Gradients of hash_grid_cuda (dm2_texture_cube_backward with DM2_TEX_HASH_GRID_CODE) -> (dL_dtable (NL,T,F) or None,
+    """Gradients of hash_grid_cuda (dm2_hash_grid_backward) -> (dL_dtable (NL,T,F) or None,
     dL_dxyz (B,H,W,L,3) or None): only what ``need_table`` / ``need_xyz`` ask for is computed."""
     return _lookup_backward(_HASH_GRID, xyz, table, render_layers, (filter_mode, boundary_mode, base_resolution, growth), grad_out,
                             (need_table,), (need_xyz,))
@@ -1258,8 +1255,8 @@ def texture_mip_backward_cuda(uv, uv_da, tex, mip, render_layers, boundary_mode,
 
 
 def texture_cube_mip_cuda(dirs, level, tex, mip, render_layers=None, max_mip_level=None):
-    """A cube map and its mip chain looked up by per-slot directions and levels of detail (include/dm2_hip.h: dm2_texture_mip
-    with DM2_TEX_BOUNDARY_CUBE).
+    """A cube map and its mip chain looked up by per-slot directions and levels of detail (include/dm2_hip.h:
+    dm2_texture_cube_mip).
 
     dirs (B,H,W,L,3), level (B,H,W,L) float32 (level 0 is tex), tex (6,N,N,C) or (B,6,N,N,C), mip (6,T,C) or (B,6,T,C): per face
     the levels 1 .. nlev-1 in ``mip_layout(N, N, max_mip_level)``'s packing, render_layers (B,H,W,L) int32 or None -> out
@@ -1269,7 +1266,7 @@ def texture_cube_mip_cuda(dirs, level, tex, mip, render_layers=None, max_mip_lev
 
 def texture_cube_mip_backward_cuda(dirs, level, tex, mip, render_layers, max_mip_level, grad_out, need_tex, need_mip, need_dirs,
                                    need_level):
-    """Gradients of texture_cube_mip_cuda (dm2_texture_mip_backward with DM2_TEX_BOUNDARY_CUBE) -> (dL_dtex of tex's shape,
+    """Gradients of texture_cube_mip_cuda (dm2_texture_cube_mip_backward) -> (dL_dtex of tex's shape,
     dL_dmip of mip's shape, dL_ddirs (B,H,W,L,3), dL_dlevel (B,H,W,L)), each None unless its ``need_*`` asks for it.  The
     direction's and the level's gradients come from one kernel as rows of four floats, split here."""
     return _lookup_backward(_TEXTURE_CUBE_MIP, dirs, tex, render_layers, ("linear", None), grad_out, (need_tex, need_mip),
@@ -1518,11 +1515,8 @@ def texture_mipmaps_backward_cuda(tex, max_mip_level, grad_mip):
     return _chain_run(lib, "dm2_texture_mipmaps_backward", "texture_mipmaps_backward_cuda", sizes, gm, tuple(tex.shape), dev)
 
 
-MIP_FILTER_CUBE_GGX = 0x40000000    # DM2_MIP_FILTER_CUBE_GGX: dm2_texture_mipmaps / dm2_texture_mipmaps_backward only
-
-
 def _cube_prefilter_args(chain, N, max_mip_level, what="chain"):
-    """Checks of a cube prefilter call -> (sizes (NB, N, N, C, the filter's code with the level limit), contiguous chain, device)."""
+    """Checks of a cube prefilter call -> (sizes (cubes, N, C, max level code), contiguous chain, device)."""
     N = int(N)
     _bad(N < 1, "N must be at least 1")
     _bad(chain.dim() not in (3, 4), f"{what} must have dimensions (6, T, C) or (B, 6, T, C)")
@@ -1536,28 +1530,26 @@ def _cube_prefilter_args(chain, N, max_mip_level, what="chain"):
     _bad(C < 1, f"{what} must have at least one channel")
     dev = _require_gpu(chain)
     _bad(chain.dtype != torch.float32, f"{what}: expected dtype {torch.float32}, got {chain.dtype}")
-    limit = 0xFFFF if max_mip_level is None else min(int(max_mip_level), 0xFFFE)
-    NB = 6 * (int(chain.size(0)) if chain.dim() == 4 else 1)
-    _bad(NB > 65535, f"{what}: at most 10922 cubes in one call")
-    return (NB, N, N, C, MIP_FILTER_CUBE_GGX | limit), chain.contiguous(), dev
+    cubes = int(chain.size(0)) if chain.dim() == 4 else 1
+    _bad(cubes > 10922, f"{what}: at most 10922 cubes in one call")
+    return (cubes, N, C, _max_level_code(max_mip_level)), chain.contiguous(), dev
 
 
 def cube_prefilter_cuda(chain, N, max_mip_level=None):
-    """The GGX prefilter of a cube's mip chain, un-normalised (include/dm2_hip.h: dm2_texture_mipmaps with
-    DM2_MIP_FILTER_CUBE_GGX): chain (6,T,C) or (B,6,T,C) float32, per face the levels 1 .. nlev-1 in ``mip_layout(N, N,
-    max_mip_level)``'s packing -> the same shape: level k filtered from level k with the lobe of roughness k / (nlev - 1),
+    """The GGX prefilter of a cube's mip chain, un-normalised (include/dm2_hip.h: dm2_cube_prefilter): chain (6,T,C) or
+    (B,6,T,C) float32, per face the levels 1 .. nlev-1 in ``mip_layout(N, N, max_mip_level)``'s packing -> the same shape: level k filtered from level k with the lobe of roughness k / (nlev - 1),
     y[o] = sum_s K(o,s) Om_s x[s].  A gather: deterministic; T = 0 launches nothing."""
     lib = load_library()
     sizes, x, dev = _cube_prefilter_args(chain, N, max_mip_level)
-    return _chain_run(lib, "dm2_texture_mipmaps", "cube_prefilter_cuda", sizes, x, tuple(x.shape), dev)
+    return _chain_run(lib, "dm2_cube_prefilter", "cube_prefilter_cuda", sizes, x, tuple(x.shape), dev)
 
 
 def cube_prefilter_transpose_cuda(grad, N, max_mip_level=None):
-    """The transpose of cube_prefilter_cuda (dm2_texture_mipmaps_backward with DM2_MIP_FILTER_CUBE_GGX): grad of the chain's
+    """The transpose of cube_prefilter_cuda (dm2_cube_prefilter_backward): grad of the chain's
     shape -> xbar[s] = Om_s sum_o K(o,s) grad[o], the same shape.  A gather as well: deterministic."""
     lib = load_library()
     sizes, g, dev = _cube_prefilter_args(grad, N, max_mip_level, "grad")
-    return _chain_run(lib, "dm2_texture_mipmaps_backward", "cube_prefilter_transpose_cuda", sizes, g, tuple(g.shape), dev)
+    return _chain_run(lib, "dm2_cube_prefilter_backward", "cube_prefilter_transpose_cuda", sizes, g, tuple(g.shape), dev)
 
 
 COMPOSITE_ALPHA_PER_SLOT, COMPOSITE_ALPHA_PER_FACE = 0, 1    # include/dm2_hip.h DM2_COMPOSITE_ALPHA_*

@@ -606,8 +606,8 @@ class Renderer(torch.nn.Module):
         mode."""
         if filter_mode not in _C.TEX_FILTERS:
             raise ValueError(f"filter_mode must be one of {sorted(_C.TEX_FILTERS)}, got {filter_mode!r}")
-        if boundary_mode not in _C.TEX_VOLUME_BOUNDARIES:
-            raise ValueError(f"boundary_mode must be one of {sorted(_C.TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
+        if boundary_mode not in _C.TEX_BOUNDARIES:
+            raise ValueError(f"boundary_mode must be one of {sorted(_C.TEX_BOUNDARIES)}, got {boundary_mode!r}")
         i32, f32 = torch.int32, torch.float32
         rl = None if render_layers is None else render_layers.to(i32)
         return TextureVolumeFunction.apply(xyz.to(f32), grid.to(f32), rl, filter_mode, boundary_mode)
@@ -632,8 +632,8 @@ class Renderer(torch.nn.Module):
         does not take."""
         if filter_mode not in _C.TEX_FILTERS:
             raise ValueError(f"filter_mode must be one of {sorted(_C.TEX_FILTERS)}, got {filter_mode!r}")
-        if boundary_mode not in _C.TEX_VOLUME_BOUNDARIES:
-            raise ValueError(f"boundary_mode must be one of {sorted(_C.TEX_VOLUME_BOUNDARIES)}, got {boundary_mode!r}")
+        if boundary_mode not in _C.TEX_BOUNDARIES:
+            raise ValueError(f"boundary_mode must be one of {sorted(_C.TEX_BOUNDARIES)}, got {boundary_mode!r}")
         if table.dim() != 3:
             raise ValueError(f"table must have dimensions (NL, T, F), got {tuple(table.shape)}")
         NL, T, F = (int(x) for x in table.shape)
@@ -689,7 +689,7 @@ class Renderer(torch.nn.Module):
         weighted by each texel's solid angle) and divided by the lobe's weight sum ``norm``: a constant cube stays constant.
         Level 0, the mirror, is ``tex`` itself.  The lobe is cut where it has fallen below 1/4096 of its peak (at most 1/64 of
         its mass; only below r = 0.298); at r = 1 it is the cosine lobe, so the last level of a full chain is the diffuse
-        irradiance map over pi.  The contract is in include/dm2_hip.h under DM2_MIP_FILTER_CUBE_GGX.
+        irradiance map over pi.  The contract is in include/dm2_hip.h under dm2_cube_prefilter.
 
         ``norm``: ``cube_prefilter_norm(N, max_mip_level)``, (6,T); None builds it in this call.  An odd N gives T = 0 and an
         empty chain.  Differentiable w.r.t. ``tex`` (``CubePrefilterFunction`` on top of ``MipmapFunction``): the backward is

@@ -573,128 +573,104 @@ int dm2_texture_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht,
     return 0;
 }
 
-static int check_texture_cube_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t filter) {
-    if (B < 0 || H < 0 || W < 0 || L < 0) return fail("texture_cube: negative size");
-    if (N < 1) return fail("texture_cube: N must be at least 1");
-    if ((int64_t)6 * N * N > 0x7FFFFFFF) return fail("texture_cube: 6 * N * N must be below 2^31");
-    if (C < 1) return fail("texture_cube: C must be at least 1");
-    if (filter != DM2_TEX_FILTER_NEAREST && filter != DM2_TEX_FILTER_LINEAR) return fail("texture_cube: unknown filter");
-    return check_slot_grid("texture_cube", (int64_t)B * H * W * L, B, H);
+// the sizes of a lookup into a table with faces or planes of N x N (op: the prefix of the messages)
+static int check_texture_cube_sizes(const char* op, int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t filter) {
+    if (B < 0 || H < 0 || W < 0 || L < 0) return fail(std::string(op) + ": negative size");
+    if (N < 1) return fail(std::string(op) + ": N must be at least 1");
+    if ((int64_t)6 * N * N > 0x7FFFFFFF) return fail(std::string(op) + ": 6 * N * N must be below 2^31");
+    if (C < 1) return fail(std::string(op) + ": C must be at least 1");
+    if (filter != DM2_TEX_FILTER_NEAREST && filter != DM2_TEX_FILTER_LINEAR) return fail(std::string(op) + ": unknown filter");
+    return check_slot_grid(op, (int64_t)B * H * W * L, B, H);
 }
 
-// filter carries DM2_TEX_VOLUME_CLAMP or DM2_TEX_VOLUME_WRAP: Renderer.texture3d, a voxel grid looked up by positions.
-// *vfilter, *vboundary: the DM2_TEX_FILTER_* and DM2_TEX_BOUNDARY_* of the call.
-static int check_texture_volume_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t filter, int* vfilter,
-                                      int* vboundary) {
-    const int32_t vol = filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP);
-    if (vol == (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP)) return fail("texture_cube: a volume takes one boundary, clamp or wrap");
-    *vfilter = filter & ~vol;
-    *vboundary = vol == DM2_TEX_VOLUME_WRAP ? DM2_TEX_BOUNDARY_WRAP : DM2_TEX_BOUNDARY_CLAMP;
-    if (N > 1290) return fail("texture_cube: a volume's N * N * N must be below 2^31");      // 1290^3 < 2^31 < 1291^3
-    return check_texture_cube_sizes(B, H, W, L, N, C, *vfilter);          // (its own bound on N lies above this one)
+static int check_texture_volume_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t filter, int32_t boundary) {
+    if (boundary != DM2_TEX_BOUNDARY_WRAP && boundary != DM2_TEX_BOUNDARY_CLAMP) return fail("texture_volume: unknown boundary");
+    if (N > 1290) return fail("texture_volume: a volume's N * N * N must be below 2^31");     // 1290^3 < 2^31 < 1291^3
+    return check_texture_cube_sizes("texture_volume", B, H, W, L, N, C, filter);              // (its own bound on N lies above this one)
 }
 
-static int texture_volume(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
-                          const int32_t* render_layers, const float* xyz, const float* grid, float* out, void* stream) {
-    int vfilter, vboundary;
-    if (check_texture_volume_sizes(B, H, W, L, N, C, filter, &vfilter, &vboundary)) return 1;
+int dm2_texture_volume(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                       int32_t boundary, const int32_t* render_layers, const float* xyz, const float* grid, float* out, void* stream) {
+    if (check_texture_volume_sizes(B, H, W, L, N, C, filter, boundary)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
-    if (!xyz || !grid || !out) return fail("texture_cube: a volume's xyz, grid and out must not be null");
-    dm2::launch_texture_volume(B, H, W, L, N, C, view_textures, vfilter, vboundary, render_layers, xyz, grid, out, (hipStream_t)stream);
+    if (!xyz || !grid || !out) return fail("texture_volume: a volume's xyz, grid and out must not be null");
+    dm2::launch_texture_volume(B, H, W, L, N, C, view_textures, filter, boundary, render_layers, xyz, grid, out, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
 
-static int texture_volume_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
-                                   int32_t filter, const int32_t* render_layers, const float* xyz, const float* grid,
-                                   const float* dL_dout, float* dL_dgrid, float* dL_dxyz, void* stream) {
-    int vfilter, vboundary;
-    if (check_texture_volume_sizes(B, H, W, L, N, C, filter, &vfilter, &vboundary)) return 1;
+int dm2_texture_volume_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
+                                int32_t filter, int32_t boundary, const int32_t* render_layers, const float* xyz, const float* grid,
+                                const float* dL_dout, float* dL_dgrid, float* dL_dxyz, void* stream) {
+    if (check_texture_volume_sizes(B, H, W, L, N, C, filter, boundary)) return 1;
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dgrid && !dL_dxyz)) return 0;
-    if (!xyz || !dL_dout) return fail("texture_cube_backward: a volume's xyz and dL_dout must not be null");
-    if (zero_nearest_grad(vfilter, &dL_dxyz, S, 3, stream)) return 1;
-    if (dL_dxyz && !grid) return fail("texture_cube_backward: a volume's grid must not be null");
+    if (!xyz || !dL_dout) return fail("texture_volume_backward: a volume's xyz and dL_dout must not be null");
+    if (zero_nearest_grad(filter, &dL_dxyz, S, 3, stream)) return 1;
+    if (dL_dxyz && !grid) return fail("texture_volume_backward: a volume's grid must not be null");
     if (dL_dgrid || dL_dxyz)
-        dm2::launch_texture_volume_backward(B, H, W, L, N, C, view_textures, vfilter, vboundary, render_layers, xyz, grid, dL_dout,
+        dm2::launch_texture_volume_backward(B, H, W, L, N, C, view_textures, filter, boundary, render_layers, xyz, grid, dL_dout,
                                             dL_dgrid, dL_dxyz, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
 
-// filter carries DM2_TEX_HASH_GRID: Renderer.hash_grid, a multiresolution hash encoding looked up by positions.
-struct HashGridCall {
-    int filter, boundary;   // DM2_TEX_FILTER_*, DM2_TEX_BOUNDARY_*
-    int NL, T, F;
-    int R[32];              // R_0 = N, R_{l+1} = (R_l * q) >> 4
-};
-
-static int check_hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
-                           HashGridCall* h) {
-    const int32_t fields = DM2_TEX_HASH_GRID_CODE(31, 32, 32);            // every bit of the code's three fields, and the hash bit
-    const int32_t vol = filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP);
-    if (filter & ~(fields | DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP | DM2_TEX_FILTER_LINEAR))
-        return fail("texture_cube: unknown bits beside a hash grid's code");
-    if (vol != DM2_TEX_VOLUME_CLAMP && vol != DM2_TEX_VOLUME_WRAP) return fail("texture_cube: a hash grid takes one boundary, clamp or wrap");
-    if (view_textures) return fail("texture_cube: a hash grid's table is shared by the views");
-    h->filter = filter & DM2_TEX_FILTER_LINEAR;
-    h->boundary = vol == DM2_TEX_VOLUME_WRAP ? DM2_TEX_BOUNDARY_WRAP : DM2_TEX_BOUNDARY_CLAMP;
-    const int log2T = (filter >> 12) & 31, q = ((filter >> 22) & 15) + 17;
-    h->NL = ((filter >> 17) & 31) + 1;
-    if (log2T < 4 || log2T > 24) return fail("texture_cube: a hash grid's log2(T) must be in 4..24");
-    h->T = 1 << log2T;
-    if (B < 0 || H < 0 || W < 0 || L < 0) return fail("texture_cube: negative size");
-    if (N < 1) return fail("texture_cube: a hash grid's base resolution must be at least 1");
-    if (C < 1 || C % h->NL != 0) return fail("texture_cube: a hash grid's C must be NL * F");
-    h->F = C / h->NL;
-    if (h->F != 1 && h->F != 2 && h->F != 4 && h->F != 8) return fail("texture_cube: a hash grid's F must be 1, 2, 4 or 8");
-    if ((int64_t)h->NL * h->T * h->F > 0x7FFFFFFF) return fail("texture_cube: a hash grid's NL * T * F must be below 2^31");
-    int64_t r = N;
-    for (int l = 0; l < h->NL; l++) {
-        if (r > (1 << 20)) return fail("texture_cube: a hash grid's finest resolution must not exceed 2^20");
-        h->R[l] = (int)r;
-        r = (r * q) >> 4;
+// R[l]: the level resolutions, R_0 = base_resolution, R_{l+1} = (R_l * growth16) >> 4
+static int check_hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t base_resolution, int32_t log2_rows, int32_t num_levels,
+                           int32_t features, int32_t growth16, int32_t filter, int32_t boundary, int R[32]) {
+    if (filter != DM2_TEX_FILTER_NEAREST && filter != DM2_TEX_FILTER_LINEAR) return fail("hash_grid: unknown filter");
+    if (boundary != DM2_TEX_BOUNDARY_WRAP && boundary != DM2_TEX_BOUNDARY_CLAMP) return fail("hash_grid: unknown boundary");
+    if (num_levels < 1 || num_levels > 32) return fail("hash_grid: a hash grid's num_levels must be in 1..32");
+    if (growth16 < 17 || growth16 > 32) return fail("hash_grid: a hash grid's growth16 must be in 17..32");
+    if (log2_rows < 4 || log2_rows > 24) return fail("hash_grid: a hash grid's log2(T) must be in 4..24");
+    if (B < 0 || H < 0 || W < 0 || L < 0) return fail("hash_grid: negative size");
+    if (base_resolution < 1) return fail("hash_grid: a hash grid's base resolution must be at least 1");
+    if (features != 1 && features != 2 && features != 4 && features != 8) return fail("hash_grid: a hash grid's F must be 1, 2, 4 or 8");
+    if (((int64_t)num_levels * features << log2_rows) > 0x7FFFFFFF) return fail("hash_grid: a hash grid's NL * T * F must be below 2^31");
+    int64_t r = base_resolution;
+    for (int l = 0; l < num_levels; l++) {
+        if (r > (1 << 20)) return fail("hash_grid: a hash grid's finest resolution must not exceed 2^20");
+        R[l] = (int)r;
+        r = (r * growth16) >> 4;
     }
-    return check_slot_grid("texture_cube", (int64_t)B * H * W * L, (int64_t)B * h->NL, H);
+    return check_slot_grid("hash_grid", (int64_t)B * H * W * L, (int64_t)B * num_levels, H);
 }
 
-static int hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
-                     const int32_t* render_layers, const float* xyz, const float* table, float* out, void* stream) {
-    HashGridCall h;
-    if (check_hash_grid(B, H, W, L, N, C, view_textures, filter, &h)) return 1;
-    if (!xyz) return fail("texture_cube: a hash grid's xyz must not be null");
+int dm2_hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t base_resolution, int32_t log2_rows, int32_t num_levels,
+                  int32_t features, int32_t growth16, int32_t filter, int32_t boundary, const int32_t* render_layers, const float* xyz,
+                  const float* table, float* out, void* stream) {
+    int R[32];
+    if (check_hash_grid(B, H, W, L, base_resolution, log2_rows, num_levels, features, growth16, filter, boundary, R)) return 1;
+    if (!xyz) return fail("hash_grid: a hash grid's xyz must not be null");
     if ((int64_t)B * H * W * L == 0) return 0;
-    if (!table || !out) return fail("texture_cube: a hash grid's table and out must not be null");
-    dm2::launch_hash_grid(B, H, W, L, h.NL, h.T, h.F, h.R, h.filter, h.boundary, render_layers, xyz, table, out, (hipStream_t)stream);
+    if (!table || !out) return fail("hash_grid: a hash grid's table and out must not be null");
+    dm2::launch_hash_grid(B, H, W, L, num_levels, 1 << log2_rows, features, R, filter, boundary, render_layers, xyz, table, out,
+                          (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
 
-static int hash_grid_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
-                              const int32_t* render_layers, const float* xyz, const float* table, const float* dL_dout,
-                              float* dL_dtable, float* dL_dxyz, void* stream) {
-    HashGridCall h;
-    if (check_hash_grid(B, H, W, L, N, C, view_textures, filter, &h)) return 1;
-    if (!xyz) return fail("texture_cube_backward: a hash grid's xyz must not be null");
+int dm2_hash_grid_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t base_resolution, int32_t log2_rows, int32_t num_levels,
+                           int32_t features, int32_t growth16, int32_t filter, int32_t boundary, const int32_t* render_layers,
+                           const float* xyz, const float* table, const float* dL_dout, float* dL_dtable, float* dL_dxyz, void* stream) {
+    int R[32];
+    if (check_hash_grid(B, H, W, L, base_resolution, log2_rows, num_levels, features, growth16, filter, boundary, R)) return 1;
+    if (!xyz) return fail("hash_grid_backward: a hash grid's xyz must not be null");
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dtable && !dL_dxyz)) return 0;
-    if (!dL_dout) return fail("texture_cube_backward: a hash grid's dL_dout must not be null");
-    if (zero_nearest_grad(h.filter, &dL_dxyz, S, 3, stream)) return 1;
-    if (dL_dxyz && !table) return fail("texture_cube_backward: a hash grid's table must not be null");
+    if (!dL_dout) return fail("hash_grid_backward: a hash grid's dL_dout must not be null");
+    if (zero_nearest_grad(filter, &dL_dxyz, S, 3, stream)) return 1;
+    if (dL_dxyz && !table) return fail("hash_grid_backward: a hash grid's table must not be null");
     if (dL_dtable || dL_dxyz)
-        dm2::launch_hash_grid_backward(B, H, W, L, h.NL, h.T, h.F, h.R, h.filter, h.boundary, render_layers, xyz, table, dL_dout,
-                                       dL_dtable, dL_dxyz, (hipStream_t)stream);
+        dm2::launch_hash_grid_backward(B, H, W, L, num_levels, 1 << log2_rows, features, R, filter, boundary, render_layers, xyz, table,
+                                       dL_dout, dL_dtable, dL_dxyz, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }
 
 int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
                      const int32_t* render_layers, const float* dirs, const float* tex, float* out, void* stream) {
-    if (filter & DM2_TEX_HASH_GRID)
-        return hash_grid(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, out, stream);
-    if (filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP))
-        return texture_volume(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, out, stream);
-    if (check_texture_cube_sizes(B, H, W, L, N, C, filter)) return 1;
+    if (check_texture_cube_sizes("texture_cube", B, H, W, L, N, C, filter)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
     if (!dirs || !tex || !out) return fail("texture_cube: dirs, tex and out must not be null");
     dm2::launch_texture_cube(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, out, (hipStream_t)stream);
@@ -705,12 +681,7 @@ int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int3
 int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
                               int32_t filter, const int32_t* render_layers, const float* dirs, const float* tex,
                               const float* dL_dout, float* dL_dtex, float* dL_ddir, void* stream) {
-    if (filter & DM2_TEX_HASH_GRID)
-        return hash_grid_backward(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, dL_dout, dL_dtex, dL_ddir, stream);
-    if (filter & (DM2_TEX_VOLUME_CLAMP | DM2_TEX_VOLUME_WRAP))
-        return texture_volume_backward(B, H, W, L, N, C, view_textures, filter, render_layers, dirs, tex, dL_dout, dL_dtex, dL_ddir,
-                                       stream);
-    if (check_texture_cube_sizes(B, H, W, L, N, C, filter)) return 1;
+    if (check_texture_cube_sizes("texture_cube", B, H, W, L, N, C, filter)) return 1;
     const int64_t S = (int64_t)B * H * W * L;
     if (S == 0 || (!dL_dtex && !dL_ddir)) return 0;
     if (!dirs || !dL_dout) return fail("texture_cube_backward: dirs and dL_dout must not be null");
@@ -843,40 +814,34 @@ static int check_mip_sizes(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_
     return 0;
 }
 
-// max_mip_level carries DM2_MIP_FILTER_CUBE_GGX: the GGX prefilter of NB / 6 cubes' chains (*cubes), each (6,T,C); *max_level:
-// the level limit the code holds (-1: none)
-static int check_cube_prefilter(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t code, int* cubes, int* max_level, int64_t* T) {
-    if (code & ~(DM2_MIP_FILTER_CUBE_GGX | 0xFFFF)) return fail("texture_mipmaps: unknown bits in max_mip_level's filter code");
-    if (NB < 0 || NB > 65535) return fail("texture_mipmaps: the number of textures must lie in [0, 65535]");
-    if (NB % 6) return fail("texture_mipmaps: the cube filter takes six faces per cube (NB must be a multiple of 6)");
-    if (Ht < 1 || Wt < 1) return fail("texture_mipmaps: Ht and Wt must be at least 1");
-    if (Ht != Wt) return fail("texture_mipmaps: a cube's faces must be square (Ht == Wt)");
-    if (C < 1 || C > dm2::cube_prefilter_max_channels()) return fail("texture_mipmaps: the cube filter takes 1 to 262140 channels");
-    *cubes = NB / 6;
-    *max_level = (code & 0xFFFF) == 0xFFFF ? -1 : (code & 0xFFFF);
-    dm2::mip_levels(Ht, Wt, *max_level, T);
-    if (6 * ((int64_t)Ht * Wt + *T) > 0x7FFFFFFF) return fail("texture_mipmaps: the texels of all levels of the cube must number below 2^31");
+// both directions of the GGX prefilter of cubes' chains: x (cubes,6,T,C) -> y (cubes,6,T,C)
+static int cube_prefilter(int32_t cubes, int32_t N, int32_t C, int32_t max_mip_level, int transpose, const float* x, float* y,
+                          void* stream) {
+    int64_t T;
+    if (cubes < 0 || cubes > 10922) return fail("cube_prefilter: the number of cubes must lie in [0, 10922]");     // 6 * cubes <= 65535
+    if (N < 1) return fail("cube_prefilter: N must be at least 1");
+    if (C < 1 || C > dm2::cube_prefilter_max_channels()) return fail("cube_prefilter: the cube filter takes 1 to 262140 channels");
+    dm2::mip_levels(N, N, max_mip_level, &T);
+    if (6 * ((int64_t)N * N + T) > 0x7FFFFFFF) return fail("cube_prefilter: the texels of all levels of the cube must number below 2^31");
+    if (cubes == 0 || T == 0) return 0;
+    if (!x || !y) return fail("cube_prefilter: the cube filter's input and output chains must not be null");
+    dm2::launch_cube_prefilter(cubes, N, C, max_mip_level, transpose, x, y, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
     return 0;
 }
 
-// both directions of the filter: x (NB,T,C) -> y (NB,T,C)
-static int cube_prefilter(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t code, int transpose, const float* x, float* y,
-                          void* stream) {
-    int cubes, max_level;
-    int64_t T;
-    if (check_cube_prefilter(NB, Ht, Wt, C, code, &cubes, &max_level, &T)) return 1;
-    if (cubes == 0 || T == 0) return 0;
-    if (!x || !y) return fail("texture_mipmaps: the cube filter's input and output chains must not be null");
-    dm2::launch_cube_prefilter(cubes, Ht, C, max_level, transpose, x, y, (hipStream_t)stream);
-    DM2_HIP(hipGetLastError());
-    return 0;
+int dm2_cube_prefilter(int32_t cubes, int32_t N, int32_t C, int32_t max_mip_level, const float* x, float* y, void* stream) {
+    return cube_prefilter(cubes, N, C, max_mip_level, 0, x, y, stream);
+}
+
+int dm2_cube_prefilter_backward(int32_t cubes, int32_t N, int32_t C, int32_t max_mip_level, const float* ybar, float* xbar,
+                                void* stream) {
+    return cube_prefilter(cubes, N, C, max_mip_level, 1, ybar, xbar, stream);
 }
 
 int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* tex, float* mip,
                         void* stream) {
     int64_t T;
-    if (max_mip_level >= 0 && (max_mip_level & DM2_MIP_FILTER_CUBE_GGX))
-        return cube_prefilter(NB, Ht, Wt, C, max_mip_level, 0, tex, mip, stream);
     if (check_mip_sizes(NB, Ht, Wt, C, max_mip_level, &T)) return 1;
     if (NB == 0 || T == 0) return 0;
     if (!tex || !mip) return fail("texture_mipmaps: tex and mip must not be null");
@@ -888,8 +853,6 @@ int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t m
 int dm2_texture_mipmaps_backward(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* dL_dmip,
                                  float* dL_dtex, void* stream) {
     int64_t T;
-    if (max_mip_level >= 0 && (max_mip_level & DM2_MIP_FILTER_CUBE_GGX))
-        return cube_prefilter(NB, Ht, Wt, C, max_mip_level, 1, dL_dmip, dL_dtex, stream);
     if (check_mip_sizes(NB, Ht, Wt, C, max_mip_level, &T)) return 1;
     if (NB == 0) return 0;
     if (!dL_dtex) return fail("texture_mipmaps_backward: dL_dtex must not be null");
@@ -909,30 +872,10 @@ static int check_texture_mip_sizes(int32_t B, int32_t H, int32_t W, int32_t L, i
     return check_mip_sizes(B, Ht, Wt, C, max_mip_level, T);
 }
 
-// DM2_TEX_BOUNDARY_CUBE: Ht == Wt == N, a chain per face (*T: its texels), every level's texels in one 32-bit key space
-static int check_texture_cube_mip_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C,
-                                        int32_t max_mip_level, int64_t* T) {
-    if (Ht != Wt) return fail("texture_mip: a cube's faces must be square (Ht == Wt)");
-    if (check_texture_cube_sizes(B, H, W, L, Ht, C, DM2_TEX_FILTER_LINEAR)) return 1;
-    dm2::mip_levels(Ht, Wt, max_mip_level, T);
-    if (6 * ((int64_t)Ht * Wt + *T) > 0x7FFFFFFF) return fail("texture_mip: the texels of all levels of the cube must number below 2^31");
-    return 0;
-}
-
 int dm2_texture_mip(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
                     int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv, const float* uv_da,
                     const float* tex, const float* mip, float* out, void* stream) {
     int64_t T;
-    if (boundary == DM2_TEX_BOUNDARY_CUBE) {                             // uv: directions, uv_da: the level of detail
-        if (check_texture_cube_mip_sizes(B, H, W, L, Ht, Wt, C, max_mip_level, &T)) return 1;
-        if ((int64_t)B * H * W * L == 0) return 0;
-        if (!uv || !uv_da || !tex || !out) return fail("texture_mip: dirs, the level, tex and out must not be null");
-        if (T > 0 && !mip) return fail("texture_mip: mip must not be null");
-        dm2::launch_texture_cube_mip(B, H, W, L, Ht, C, view_textures, max_mip_level, render_layers, uv, uv_da, tex, mip, out,
-                                     (hipStream_t)stream);
-        DM2_HIP(hipGetLastError());
-        return 0;
-    }
     if (check_texture_mip_sizes(B, H, W, L, Ht, Wt, C, boundary, max_mip_level, &T)) return 1;
     if ((int64_t)B * H * W * L == 0) return 0;
     if (!uv || !uv_da || !tex || !out) return fail("texture_mip: uv, uv_da, tex and out must not be null");
@@ -948,18 +891,6 @@ int dm2_texture_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
                              const float* uv_da, const float* tex, const float* mip, const float* dL_dout, float* dL_dtex,
                              float* dL_dmip, float* dL_duv, void* stream) {
     int64_t T;
-    if (boundary == DM2_TEX_BOUNDARY_CUBE) {                             // dL_duv: (B,H,W,L,4) rows (dL/ddir, dL/dlevel)
-        if (check_texture_cube_mip_sizes(B, H, W, L, Ht, Wt, C, max_mip_level, &T)) return 1;
-        if (T == 0) dL_dmip = nullptr;
-        if ((int64_t)B * H * W * L == 0 || (!dL_dtex && !dL_dmip && !dL_duv)) return 0;
-        if (!uv || !uv_da || !dL_dout) return fail("texture_mip_backward: dirs, the level and dL_dout must not be null");
-        if (dL_duv && (!tex || (T > 0 && !mip))) return fail("texture_mip_backward: tex and mip must not be null");
-        if ((uintptr_t)dL_duv % 16) return fail("texture_mip_backward: the cube's dL_duv rows must be 16-byte aligned");
-        dm2::launch_texture_cube_mip_backward(B, H, W, L, Ht, C, view_textures, max_mip_level, render_layers, uv, uv_da, tex, mip,
-                                              dL_dout, dL_dtex, dL_dmip, dL_duv, (hipStream_t)stream);
-        DM2_HIP(hipGetLastError());
-        return 0;
-    }
     if (check_texture_mip_sizes(B, H, W, L, Ht, Wt, C, boundary, max_mip_level, &T)) return 1;
     if (T == 0) dL_dmip = nullptr;                                       // an empty chain: nothing to add into
     if ((int64_t)B * H * W * L == 0 || (!dL_dtex && !dL_dmip && !dL_duv)) return 0;
@@ -967,6 +898,46 @@ int dm2_texture_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
     if (dL_duv && (!tex || (T > 0 && !mip))) return fail("texture_mip_backward: tex and mip must not be null");
     dm2::launch_texture_mip_backward(B, H, W, L, Ht, Wt, C, view_textures, boundary, max_mip_level, render_layers, uv, uv_da, tex,
                                      mip, dL_dout, dL_dtex, dL_dmip, dL_duv, (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+// a chain per face (*T: its texels), every level's texels in one 32-bit key space
+static int check_texture_cube_mip_sizes(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t max_mip_level,
+                                        int64_t* T) {
+    if (check_texture_cube_sizes("texture_cube_mip", B, H, W, L, N, C, DM2_TEX_FILTER_LINEAR)) return 1;
+    dm2::mip_levels(N, N, max_mip_level, T);
+    if (6 * ((int64_t)N * N + *T) > 0x7FFFFFFF) return fail("texture_cube_mip: the texels of all levels of the cube must number below 2^31");
+    return 0;
+}
+
+int dm2_texture_cube_mip(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t max_mip_level,
+                         const int32_t* render_layers, const float* dirs, const float* level, const float* tex, const float* mip,
+                         float* out, void* stream) {
+    int64_t T;
+    if (check_texture_cube_mip_sizes(B, H, W, L, N, C, max_mip_level, &T)) return 1;
+    if ((int64_t)B * H * W * L == 0) return 0;
+    if (!dirs || !level || !tex || !out) return fail("texture_cube_mip: dirs, the level, tex and out must not be null");
+    if (T > 0 && !mip) return fail("texture_cube_mip: mip must not be null");
+    dm2::launch_texture_cube_mip(B, H, W, L, N, C, view_textures, max_mip_level, render_layers, dirs, level, tex, mip, out,
+                                 (hipStream_t)stream);
+    DM2_HIP(hipGetLastError());
+    return 0;
+}
+
+int dm2_texture_cube_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
+                                  int32_t max_mip_level, const int32_t* render_layers, const float* dirs, const float* level,
+                                  const float* tex, const float* mip, const float* dL_dout, float* dL_dtex, float* dL_dmip,
+                                  float* dL_drows, void* stream) {
+    int64_t T;
+    if (check_texture_cube_mip_sizes(B, H, W, L, N, C, max_mip_level, &T)) return 1;
+    if (T == 0) dL_dmip = nullptr;                                       // an empty chain: nothing to add into
+    if ((int64_t)B * H * W * L == 0 || (!dL_dtex && !dL_dmip && !dL_drows)) return 0;
+    if (!dirs || !level || !dL_dout) return fail("texture_cube_mip_backward: dirs, the level and dL_dout must not be null");
+    if (dL_drows && (!tex || (T > 0 && !mip))) return fail("texture_cube_mip_backward: tex and mip must not be null");
+    if ((uintptr_t)dL_drows % 16) return fail("texture_cube_mip_backward: the cube's dL_drows rows must be 16-byte aligned");
+    dm2::launch_texture_cube_mip_backward(B, H, W, L, N, C, view_textures, max_mip_level, render_layers, dirs, level, tex, mip,
+                                          dL_dout, dL_dtex, dL_dmip, dL_drows, (hipStream_t)stream);
     DM2_HIP(hipGetLastError());
     return 0;
 }

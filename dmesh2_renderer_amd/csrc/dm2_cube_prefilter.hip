@@ -1,6 +1,6 @@
 // dm2_cube_prefilter.hip -- Renderer.cube_prefilter: the GGX prefilter of a cube's mip chain and its transpose.
 //
-// Contract: include/dm2_hip.h, dm2_texture_mipmaps with DM2_MIP_FILTER_CUBE_GGX.  Level k of the chain (faces of n = N >> k) is
+// Contract: include/dm2_hip.h, dm2_cube_prefilter.  Level k of the chain (faces of n = N >> k) is
 // filtered from the same level of the input with the lobe K(o,s) of roughness k / (nlev - 1):
 //   forward:   y[o,c]    = sum_s (K(o,s) Om_s) x[s,c]
 //   transpose: xbar[s,c] = Om_s sum_o K(o,s) ybar[o,c]

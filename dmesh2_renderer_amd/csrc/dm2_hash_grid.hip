@@ -6,7 +6,7 @@
 //                          that order, su_r, sv_r the uv terms (tex_uv_term) of plane r over the level's F features
 //   k_hash_grid_bwd_table  dL/dtable[v, row_pqr, f] += w_pqr g[s, v F + f]
 //
-// Contract (include/dm2_hip.h, dm2_texture_cube_backward, "DM2_TEX_HASH_GRID"): X = x R_v - 0.5 in fp32, X0 = floor(X),
+// Contract (include/dm2_hip.h, dm2_hash_grid): X = x R_v - 0.5 in fp32, X0 = floor(X),
 // fx = X - X0, Y and Z alike; the taps through dm2_texture's addr with n = R_v; row = (k R_v + j) R_v + i where R_v^3 <= T, else
 // (i ^ j 2654435761 ^ k 805459861) mod T in wrapping 32-bit arithmetic, on the addresses after addr.  A slot is empty when its
 // id is negative or |X|, |Y| or |Z| at the finest level is not below 2^24 (NaN and infinite coordinates included): zeros in

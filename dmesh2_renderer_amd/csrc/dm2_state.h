@@ -331,7 +331,7 @@ void launch_texture_mip_backward(int B, int H, int W, int L, int Ht, int Wt, int
                                  const int32_t* render_layers, const float* uv, const float* uv_da, const float* tex,
                                  const float* mip, const float* dL_dout, float* dL_dtex, float* dL_dmip, float* dL_duv,
                                  hipStream_t st);
-// ... with DM2_TEX_BOUNDARY_CUBE (dm2_texture_cube.hip): a cube (6, N, N, C) and its chain (6, T, C) looked up by directions
+// Renderer.texture's cube mip chain (dm2_texture_cube.hip): a cube (6, N, N, C) and its chain (6, T, C) looked up by directions
 // (B, H, W, L, 3) at the level of detail ``level`` (B, H, W, L); 6 (N N + T) < 2^31.  dL_ddir_level: (B, H, W, L, 4) rows
 // (dL/ddir, dL/dlevel), 16-byte aligned, every element written; the backward adds into dL_dtex and dL_dmip; any of its three
 // output pointers may be NULL; mip may be NULL when the chain is empty.

@@ -325,7 +325,7 @@ void launch_texture_cube_backward(int B, int H, int W, int L, int N, int C, int 
 //                               lod <= 0 or lod >= nlev - 1); lod is the slot's own, given by the caller
 //   k_texture_cube_mip_bwd_dir  (dL/ddir, dL/dlod)[s] = ((1 - f) ddir_j + f ddir_{j+1}, sum_c g (c_{j+1} - c_j)), one 16-byte row
 //   k_texture_cube_mip_bwd_tex  dL/dtex, dL/dmip[t of level j, j + 1] += (1 - f) w g, f w g
-// Contract: include/dm2_hip.h, dm2_texture_mip with DM2_TEX_BOUNDARY_CUBE.  The face and (sc, tc, ma) are the slot's, computed
+// Contract: include/dm2_hip.h, dm2_texture_cube_mip.  The face and (sc, tc, ma) are the slot's, computed
 // once; each level repeats cube_tap's linear stage at its own size N_k = N >> k (cm_level).  A texel of any level has one key per
 // view, as in dm2_texture_mip.hip: level 0 is (face N + j) N + i, level k >= 1 is 6 N N + face T + off_k + j N_k + i (T: the
 // chain's texels of one face), which is its row in tex (6 N N, C) followed by mip (6 T, C).

@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define DM2_ABI_VERSION 7
+#define DM2_ABI_VERSION 8
 #define DM2_TILE 16 /* config.h:4-5 BLOCK_X = BLOCK_Y = 16 */
 
 /* Inputs of Renderer's op, same meaning and order as render.h:13-45. */
@@ -375,7 +375,6 @@ int dm2_interpolate_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
 #define DM2_TEX_FILTER_LINEAR 1
 #define DM2_TEX_BOUNDARY_WRAP 0
 #define DM2_TEX_BOUNDARY_CLAMP 1
-#define DM2_TEX_BOUNDARY_CUBE 2 /* dm2_texture_mip and dm2_texture_mip_backward only: the cube's mip chain, see there */
 int dm2_texture(int32_t B, int32_t H, int32_t W, int32_t L, int32_t Ht, int32_t Wt, int32_t C, int32_t view_textures,
                 int32_t filter, int32_t boundary, const int32_t* render_layers, const float* uv, const float* tex, float* out,
                 void* stream);
@@ -439,26 +438,27 @@ int dm2_texture_cube(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int3
 int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
                               int32_t filter, const int32_t* render_layers, const float* dirs, const float* tex,
                               const float* dL_dout, float* dL_dtex, float* dL_ddir, void* stream);
-/* filter with DM2_TEX_VOLUME_CLAMP or DM2_TEX_VOLUME_WRAP set (OR-ed with DM2_TEX_FILTER_NEAREST or _LINEAR): Renderer.texture3d,
- * a voxel grid looked up by a position per slot (a variant of "a texture looked up by three coordinates": no symbol of its own).
- * Both functions above then read their arguments as: dirs = xyz (B,H,W,L,3) float32, the position in the grid's unit cube, x
- * along the grid's last spatial axis and z along its first; tex = the grid (N,N,N,C) float32 shared by the views
- * (view_textures == 0) or (B,N,N,N,C), channel-last, indexed [k][j][i]; dL_dtex = dL_dgrid; dL_ddir = dL_dxyz.  N, C >= 1;
- * N * N * N < 2^31 takes the place of 6 * N * N < 2^31.  Both bits set, or any other bit beside DM2_TEX_FILTER_*, is refused.
+
+/* Renderer.texture3d: a voxel grid looked up by a position per slot.  xyz (B,H,W,L,3) float32, the position in the grid's unit
+ * cube, x along the grid's last spatial axis and z along its first; grid (N,N,N,C) float32 shared by the views
+ * (view_textures == 0) or (B,N,N,N,C), channel-last, indexed [k][j][i]; render_layers (B,H,W,L) int32 or NULL; out (B,H,W,L,C).
+ * N, C >= 1; N * N * N < 2^31.  filter: DM2_TEX_FILTER_*; boundary: DM2_TEX_BOUNDARY_WRAP or DM2_TEX_BOUNDARY_CLAMP; any other
+ * filter or boundary is refused.
  * Voxel centres sit at ((i + 0.5) / N, (j + 0.5) / N, (k + 0.5) / N).  Per slot s, all fp32, separate multiplies and adds in
  * the written order, without contraction (bit-exact):
  *   X  = x * (float)N - 0.5f      Y = y * (float)N - 0.5f      Z = z * (float)N - 0.5f
  *   X0 = floorf(X)   fx = X - X0   i0 = (int)X0                 (Y0, fy, j0 and Z0, fz, k0 alike)
  * A slot is empty when render_layers[s] < 0 (render_layers NULL: never by id), or a coordinate is not finite, or |X|, |Y| or |Z|
  * is not below 2^24 (dm2_texture's rule, per axis): out[s,:] = 0, and nothing is read from the grid through it.  Otherwise the
- * eight taps are t_pqr = grid[addr(k0 + r)][addr(j0 + q)][addr(i0 + p)] with dm2_texture's addr of the boundary, n = N
- * (DM2_TEX_VOLUME_CLAMP: DM2_TEX_BOUNDARY_CLAMP's, DM2_TEX_VOLUME_WRAP: DM2_TEX_BOUNDARY_WRAP's):
+ * eight taps are t_pqr = grid[addr(k0 + r)][addr(j0 + q)][addr(i0 + p)] with dm2_texture's addr of the boundary, n = N:
  *   DM2_TEX_FILTER_LINEAR   a_r = b0 + fy * (b1 - b0), b_q = t_0qr + fx * (t_1qr - t_0qr)   (dm2_texture's blend in plane k0 + r),
  *                           out[s,c] = a_0 + fz * (a_1 - a_0)
  *   DM2_TEX_FILTER_NEAREST  out[s,c] = grid[addr((int)floorf(Z + 0.5f))][addr((int)floorf(Y + 0.5f))][addr((int)floorf(X + 0.5f))]
- * Every element of out is written: no pre-fill.
- * Gradients for upstream g = dL_dout (B,H,W,L,C): the derivative of that fp32 function at its fp32 fractions and addresses.
- * Per non-empty slot s:
+ * Every element of out is written: no pre-fill. */
+int dm2_texture_volume(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t filter,
+                       int32_t boundary, const int32_t* render_layers, const float* xyz, const float* grid, float* out, void* stream);
+/* Gradients of dm2_texture_volume for upstream g = dL_dout (B,H,W,L,C): the derivative of that fp32 function at its fp32
+ * fractions and addresses.  Per non-empty slot s:
  *   dL_dgrid[t_pqr,c] += w_pqr * g[s,c], w_pqr = (wx_p * wy_q) * wz_r with (w_0, w_1) = (1 - f, f) per axis (nearest: weight 1
  *     on the one voxel); the view's own grid when view_textures != 0, summed over the views otherwise; taps that meet in one
  *     voxel (N = 1, clamp at a border) all add; dL_dgrid is zero-filled by the caller and summed with float atomics: its last
@@ -467,23 +467,22 @@ int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_
  *     and v_r = b1 - b0 of plane r:  d out / d fx = U_0 + fz * (U_1 - U_0),  d out / d fy = V_0 + fz * (V_1 - V_0) over the sums
  *     U_r = sum_c g * u_r, V_r = sum_c g * v_r, and d out / d fz = a_1 - a_0; used as it stands where clamp has a kink; zeros
  *     for nearest and in an empty slot; every element is written; a pure function of the inputs.
- * Either output pointer may be NULL (not wanted; its kernel is not launched; tex may then be NULL for dL_dgrid alone). */
-#define DM2_TEX_VOLUME_CLAMP 0x100
-#define DM2_TEX_VOLUME_WRAP 0x200
-/* filter with DM2_TEX_HASH_GRID_CODE(log2T, NL, q) set, OR-ed with DM2_TEX_FILTER_NEAREST or _LINEAR and exactly one of
- * DM2_TEX_VOLUME_CLAMP / DM2_TEX_VOLUME_WRAP: Renderer.hash_grid, a multiresolution hash encoding looked up by a position per slot
- * (no symbol of its own either).  Both functions above then read their arguments as: N = the base resolution; C = NL * F;
- * dirs = xyz (B,H,W,L,3) float32, the position in the field's unit cube, axes as for the volume; tex = the table (NL, T, F)
- * float32, T = 2^log2T rows per level, shared by the views; dL_dtex = dL_dtable; dL_ddir = dL_dxyz; out and dL_dout are
- * (B,H,W,L,NL*F), level-major: channel l * F + f.
- * Refused: view_textures != 0; the hash bit without a boundary bit or with both; NL outside 1..32 (by the code: never); C % NL
- * != 0; F = C / NL not in {1, 2, 4, 8}; log2T outside 4..24; N < 1; R_{NL-1} > 2^20; NL * T * F >= 2^31; B * NL > 65535; NULL
- * xyz; bits 26..31 and every bit that is no field of the code.  Without the hash bit the fields of the code are unknown bits.
- * Level resolutions, integers:  R_0 = N,  R_{l+1} = (R_l * q) >> 4,  q in 17..32 (growth q / 16).
+ * Either output pointer may be NULL (not wanted; its kernel is not launched; grid may then be NULL for dL_dgrid alone). */
+int dm2_texture_volume_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
+                                int32_t filter, int32_t boundary, const int32_t* render_layers, const float* xyz, const float* grid,
+                                const float* dL_dout, float* dL_dgrid, float* dL_dxyz, void* stream);
+
+/* Renderer.hash_grid: a multiresolution hash encoding looked up by a position per slot.  NL = num_levels, F = features,
+ * T = 2^log2_rows rows per level, q = growth16 (growth q / 16): xyz (B,H,W,L,3) float32, the position in the field's unit cube,
+ * axes as for the volume; table (NL, T, F) float32, shared by the views; render_layers (B,H,W,L) int32 or NULL; out and dL_dout
+ * are (B,H,W,L,NL*F), level-major: channel l * F + f.  filter and boundary as for dm2_texture_volume.
+ * Refused: NL outside 1..32; q outside 17..32; F not in {1, 2, 4, 8}; log2_rows outside 4..24; base_resolution < 1;
+ * R_{NL-1} > 2^20; NL * T * F >= 2^31; B * NL > 65535; NULL xyz; an unknown filter or boundary.
+ * Level resolutions, integers:  R_0 = base_resolution,  R_{l+1} = (R_l * q) >> 4.
  * One level l is the volume's lookup above of a virtual R_l^3 grid, n = R_l, whose voxel (k, j, i) is row row_l(k, j, i) of
  * table[l]; all fp32, separate multiplies and adds in the written order, without contraction (bit-exact):
  *   X  = x * (float)R_l - 0.5f   X0 = floorf(X)   fx = X - X0   i0 = (int)X0        (Y0, fy, j0 and Z0, fz, k0 alike)
- *   t_pqr = table[l][row_l(addr(k0 + r), addr(j0 + q), addr(i0 + p))]               (addr: the volume's, of the boundary bit)
+ *   t_pqr = table[l][row_l(addr(k0 + r), addr(j0 + q), addr(i0 + p))]               (addr: the volume's, of the boundary)
  *   DM2_TEX_FILTER_LINEAR   out[s, l*F + f] = a_0 + fz * (a_1 - a_0), a_r the volume's blend of plane k0 + r
  *   DM2_TEX_FILTER_NEAREST  out[s, l*F + f] = table[l][row_l(addr((int)floorf(Z + 0.5f)), addr(.. Y ..), addr(.. X ..))]
  * Row addressing, on the addresses after addr:
@@ -492,16 +491,20 @@ int dm2_texture_cube_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_
  * Taps that land in one row (collisions, R_l = 1, clamp at a border) all read it, and all add to it in the backward.
  * A slot is empty when render_layers[s] < 0 (render_layers NULL: never by id), or |X|, |Y| or |Z| at the finest level l = NL - 1
  * is not below 2^24 (NaN and infinities included; the R_l do not decrease, so no coarser level is out of range when the finest
- * is not): zeros in all NL * F channels, nothing read from the table through it, no gradient.  Every element of out is written.
- * Gradients for upstream g = dL_dout: the derivative of that fp32 function at its fp32 fractions and addresses.
+ * is not): zeros in all NL * F channels, nothing read from the table through it, no gradient.  Every element of out is written. */
+int dm2_hash_grid(int32_t B, int32_t H, int32_t W, int32_t L, int32_t base_resolution, int32_t log2_rows, int32_t num_levels,
+                  int32_t features, int32_t growth16, int32_t filter, int32_t boundary, const int32_t* render_layers, const float* xyz,
+                  const float* table, float* out, void* stream);
+/* Gradients of dm2_hash_grid for upstream g = dL_dout: the derivative of that fp32 function at its fp32 fractions and addresses.
  *   dL_dtable[l, row_pqr, f] += ((wx_p * wy_q) * wz_r) * g[s, l*F + f], (w_0, w_1) = (1 - f, f) per axis (nearest: weight 1 on
  *     the one row); zero-filled by the caller, summed with float atomics: its last bits may vary from run to run;
  *   dL_dxyz[s, a] = sum over l = 0 .. NL - 1, in that order from 0.0f, of (float)R_l * the level's volume term:
  *     U_0 + fz * (U_1 - U_0), V_0 + fz * (V_1 - V_0) and sum_f g * (a_1 - a_0), the sums over the level's F features in order
  *     (the volume's U_r, V_r); zeros for nearest and in an empty slot; every element is written; a pure function of the inputs.
- * Either output pointer may be NULL (not wanted; its kernel is not launched; tex may then be NULL for dL_dtable alone). */
-#define DM2_TEX_HASH_GRID 0x800
-#define DM2_TEX_HASH_GRID_CODE(log2T, NL, q) (DM2_TEX_HASH_GRID | ((log2T) << 12) | (((NL) - 1) << 17) | (((q) - 17) << 22))
+ * Either output pointer may be NULL (not wanted; its kernel is not launched; table may then be NULL for dL_dtable alone). */
+int dm2_hash_grid_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t base_resolution, int32_t log2_rows, int32_t num_levels,
+                           int32_t features, int32_t growth16, int32_t filter, int32_t boundary, const int32_t* render_layers,
+                           const float* xyz, const float* table, const float* dL_dout, float* dL_dtable, float* dL_dxyz, void* stream);
 
 /* Renderer.bary_derivatives: the footprint of a pixel on each listed face.  render_layers (B,H,W,L) int32, verts (P,3) float32,
  * faces (F,3) int32, ray_cam (B,32) float32 = inv(mv) (16, row-major) then inv(proj) (16) of each view, the camera block of
@@ -542,13 +545,13 @@ int dm2_texture_mipmaps(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t m
  * a gather: no atomics, a pure function of the inputs (zeros when nlev == 1). */
 int dm2_texture_mipmaps_backward(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, int32_t max_mip_level, const float* dL_dmip,
                                  float* dL_dtex, void* stream);
-/* max_mip_level >= 0 with DM2_MIP_FILTER_CUBE_GGX set: Renderer.cube_prefilter, the GGX prefilter of cube mip chains (a variant
- * of building a chain, so a value code and no symbol of its own; every other max_mip_level keeps its meaning).  The arguments of
- * the two entry points above then mean:
- *   the level limit is max_mip_level & 0xFFFF (0xFFFF: none), any other bit is refused; Ht == Wt == N (anything else is refused);
- *   NB is a multiple of 6 and six consecutive textures are one cube's faces (+x, -x, +y, -y, +z, -z, dm2_texture_cube's face
- *   coordinates); forward: tex = the input chain x (NB,T,C), mip = y (NB,T,C); backward: dL_dmip = ybar (NB,T,C), dL_dtex =
- *   xbar (NB,T,C); T, nlev and the packing as above for (N, N, limit); T == 0: nothing runs; 6 * (N * N + T) < 2^31; C <= 262140.
+/* Every non-negative max_mip_level of the two entry points above is a level limit.  (Up to ABI 7 bit 30 of it selected the
+ * cube prefilter below; a caller built against that version is stopped by dm2_abi_version before it gets here.) */
+
+/* Renderer.cube_prefilter: the GGX prefilter of cube mip chains.  x, y (cubes,6,T,C) float32: per cube its six faces (+x, -x,
+ * +y, -y, +z, -z, dm2_texture_cube's face coordinates), per face the levels 1 .. nlev-1 of dm2_texture_mipmaps' layout for
+ * (N, N, max_mip_level) (max_mip_level < 0: no limit); T == 0: nothing runs; 0 <= cubes <= 10922; 6 * (N * N + T) < 2^31;
+ * 1 <= C <= 262140.  dm2_cube_prefilter_backward is the transpose: ybar, xbar of the same shape.
  * Texel (face, j, i) of a level with faces of n x n, all fp32, separate multiplies and adds in the written order:
  *   sc = (2 (i + 0.5)) / n - 1,  tc = (2 (j + 0.5)) / n - 1,  p = the cube point of (face, sc, tc) (the inverse of the lookup's table)
  *   q = (1 + sc sc) + tc tc,  rq = sqrtf(q),  d = p / rq per component,  Om = 1 / (q rq)   (the solid angle up to 4 / n^2)
@@ -563,7 +566,9 @@ int dm2_texture_mipmaps_backward(int32_t NB, int32_t Ht, int32_t Wt, int32_t C, 
  *   forward:   y[o,ch] = sum_s (K(o,s) Om_s) x[s,ch]          backward (the transpose): xbar[s,ch] = Om_s sum_o K(o,s) ybar[o,ch]
  * Both are gathers: every element is written, no atomics, a pure function of the inputs.  The order of the sums is the
  * kernel's own: against the sums in float64 an element with mem members is held to (mem + 4) 2^-24 sum |K Om x|. */
-#define DM2_MIP_FILTER_CUBE_GGX 0x40000000
+int dm2_cube_prefilter(int32_t cubes, int32_t N, int32_t C, int32_t max_mip_level, const float* x, float* y, void* stream);
+int dm2_cube_prefilter_backward(int32_t cubes, int32_t N, int32_t C, int32_t max_mip_level, const float* ybar, float* xbar,
+                                void* stream);
 
 /* Renderer.texture(filter_mode="linear-mipmap-linear"): trilinear sampling.  uv, tex, render_layers, out, view_textures and
  * boundary as for dm2_texture; uv_da (B,H,W,L,4) float32 = (du/dX, dv/dX, du/dY, dv/dY), the UV footprint of the slot's pixel
@@ -598,33 +603,41 @@ int dm2_texture_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t
                              int32_t boundary, int32_t max_mip_level, const int32_t* render_layers, const float* uv,
                              const float* uv_da, const float* tex, const float* mip, const float* dL_dout, float* dL_dtex,
                              float* dL_dmip, float* dL_duv, void* stream);
-/* boundary == DM2_TEX_BOUNDARY_CUBE: Renderer.texture(filter_mode="linear-mipmap-linear", boundary_mode="cube", mip_level=...),
- * a cube map and its mip chain looked up by a direction and a level of detail per slot.  The arguments of the two entry
- * points above then mean (a variant of the operation, so a value code and no symbol of its own):
- *   Ht == Wt == N (anything else is refused); uv = dirs (B,H,W,L,3) as for dm2_texture_cube; uv_da = the level of detail
- *   (B,H,W,L), one float per slot, level 0 being tex; tex (6,N,N,C) or, with view_textures, (B,6,N,N,C); mip (6,T,C) or
- *   (B,6,T,C): per face the levels 1 .. nlev-1 in dm2_texture_mipmaps' layout for (N, N, max_mip_level), level k with faces of
- *   N_k = N >> k (dm2_texture_mipmaps of the six faces as six textures gives the box chain; any chain of that shape is
- *   accepted); 6 * (N * N + T) < 2^31; mip may be NULL when T == 0.
+
+/* Renderer.texture(filter_mode="linear-mipmap-linear", boundary_mode="cube", mip_level=...): a cube map and its mip chain looked
+ * up by a direction and a level of detail per slot.  dirs (B,H,W,L,3), render_layers, out and view_textures as for
+ * dm2_texture_cube; level (B,H,W,L) float32, the level of detail, one float per slot, level 0 being tex; tex (6,N,N,C) or, with
+ * view_textures, (B,6,N,N,C); mip (6,T,C) or (B,6,T,C): per face the levels 1 .. nlev-1 in dm2_texture_mipmaps' layout for
+ * (N, N, max_mip_level) (max_mip_level < 0: no limit), level k with faces of N_k = N >> k (dm2_texture_mipmaps of the six faces
+ * as six textures gives the box chain; any chain of that shape is accepted); 6 * (N * N + T) < 2^31; mip may be NULL when T == 0.
  *   empty: the slot is empty by dm2_texture_cube's rules, or its level is not finite: out[s,:] = 0, nothing is read through it,
  *     no gradient;
- *   forward, lod = the slot's level, all fp32 in the written order: lod <= 0: level 0 alone (bit-equal to dm2_texture_cube
+ *   lod = the slot's level, all fp32 in the written order: lod <= 0: level 0 alone (bit-equal to dm2_texture_cube
  *     with DM2_TEX_FILTER_LINEAR); lod >= nlev - 1: the last level alone; otherwise j = (int)floorf(lod), f = lod - (float)j,
  *       out[s,c] = c_j + f * (c_{j+1} - c_j)
  *     c_k = dm2_texture_cube's linear sample of level k with N_k in place of N: the face and (sc, tc, ma), and with them
  *     sn, tn, are computed once; X_k = sn * (float)N_k - 0.5f, Y_k alike; the seam rule and the three-tap corner blend apply at
  *     that level's size.
- *   backward, the derivative of that fp32 function at its own j, f, fractions, faces and addresses, with (m_j, m_{j+1}) =
- *     (1 - f, f) (one level: weight 1 on it):
- *     dL_dtex / dL_dmip[t_k of level k, c] += m_k * w * g[s,c], w as in dm2_texture_cube_backward (w / W at a corner; a missing
- *       tap adds nothing): level 0's texels in dL_dtex, the others in dL_dmip; zero-filled by the caller; float atomics;
- *     dL_duv is (B,H,W,L,4) = (dL/ddir.x, .y, .z, dL/dlevel), one 16-byte row per slot (16-byte aligned), every element written:
- *       dL/ddir = m_j * ddir_j + m_{j+1} * ddir_{j+1}, ddir_k = dm2_texture_cube_backward's dL_ddir of level k with its N_k
- *         factor; orthogonal to the direction;
- *       dL/dlevel = sum_c g[s,c] * (c_{j+1,c} - c_{j,c}), the channels in order, where 0 < lod < nlev - 1 (at an integer lod
- *         inside the range the right-hand derivative, j = lod); 0 where the level is clamped or the slot is empty;
- *       a pure function of the inputs.
- *   Any output pointer may be NULL, as above; dL_duv is produced when either the direction's or the level's gradient is wanted. */
+ * Every element of out is written. */
+int dm2_texture_cube_mip(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures, int32_t max_mip_level,
+                         const int32_t* render_layers, const float* dirs, const float* level, const float* tex, const float* mip,
+                         float* out, void* stream);
+/* Gradients of dm2_texture_cube_mip for upstream g = dL_dout (B,H,W,L,C): the derivative of that fp32 function at its own j, f,
+ * fractions, faces and addresses, with (m_j, m_{j+1}) = (1 - f, f) (one level: weight 1 on it):
+ *   dL_dtex / dL_dmip[t_k of level k, c] += m_k * w * g[s,c], w as in dm2_texture_cube_backward (w / W at a corner; a missing
+ *     tap adds nothing): level 0's texels in dL_dtex, the others in dL_dmip; zero-filled by the caller; float atomics;
+ *   dL_drows is (B,H,W,L,4) = (dL/ddir.x, .y, .z, dL/dlevel), one 16-byte row per slot (16-byte aligned), every element written:
+ *     dL/ddir = m_j * ddir_j + m_{j+1} * ddir_{j+1}, ddir_k = dm2_texture_cube_backward's dL_ddir of level k with its N_k
+ *       factor; orthogonal to the direction;
+ *     dL/dlevel = sum_c g[s,c] * (c_{j+1,c} - c_{j,c}), the channels in order, where 0 < lod < nlev - 1 (at an integer lod
+ *       inside the range the right-hand derivative, j = lod); 0 where the level is clamped or the slot is empty;
+ *     a pure function of the inputs.
+ * Any of the three output pointers may be NULL (not wanted; a kernel none of whose outputs is wanted is not launched; tex and
+ * mip may be NULL when dL_drows is); dL_drows is produced when either the direction's or the level's gradient is wanted. */
+int dm2_texture_cube_mip_backward(int32_t B, int32_t H, int32_t W, int32_t L, int32_t N, int32_t C, int32_t view_textures,
+                                  int32_t max_mip_level, const int32_t* render_layers, const float* dirs, const float* level,
+                                  const float* tex, const float* mip, const float* dL_dout, float* dL_dtex, float* dL_dmip,
+                                  float* dL_drows, void* stream);
 
 /* Renderer.composite: per-slot values (dm2_interpolate's or dm2_texture's output, or anything shaded from them) blended front
  * to back into an image: LayeredRenderer.render's blend with the colour supplied by the caller.

@@ -1,5 +1,5 @@
-"""Restatement of Renderer.cube_prefilter (include/dm2_hip.h: dm2_texture_mipmaps / dm2_texture_mipmaps_backward with
-DM2_MIP_FILTER_CUBE_GGX) in numpy, on tests/texture_cube_ref.py's face table and tests/texture_mip_ref.py's layout.
+"""Restatement of Renderer.cube_prefilter (include/dm2_hip.h: dm2_cube_prefilter / dm2_cube_prefilter_backward) in numpy,
+on tests/texture_cube_ref.py's face table and tests/texture_mip_ref.py's layout.
 
 A level with faces of n x n has texels (face, j, i), row face n n + j n + i.  d, Om, K and the membership are computed in
 float32 exactly as the contract writes them (separate multiplies and adds, in the written order); every sum is in float64.

@@ -1,5 +1,5 @@
-"""Restatement of the hash grid contract of Renderer.hash_grid (include/dm2_hip.h: dm2_texture_cube / dm2_texture_cube_backward
-with DM2_TEX_HASH_GRID_CODE) in numpy.
+"""Restatement of the hash grid contract of Renderer.hash_grid (include/dm2_hip.h: dm2_hash_grid / dm2_hash_grid_backward)
+in numpy.
 
 xyz (B,H,W,L,3) = a position per slot in the field's unit cube; table (NL,T,F), T a power of two; render_layers (B,H,W,L) or None;
 N the base resolution, q = 16 growth in 17..32.  Level resolutions R_0 = N, R_{l+1} = (R_l q) >> 4.  Per slot and level, in float32:

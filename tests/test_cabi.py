@@ -21,13 +21,16 @@ def test_header_symbols_are_bound_and_exported():
     for n in names:
         assert getattr(lib, n) is not None
     assert lib.dm2_abi_version() == _C.ABI_VERSION == int(re.search(r"#define DM2_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "dm2_hip.h")).read()).group(1))
-    assert _C.ABI_VERSION == 7
+    assert _C.ABI_VERSION == 8
 
 
 def test_one_symbol_per_operation():
     """ABI v7: an optional window, output or upstream gradient is a nullable argument of the operation's one symbol, not a
-    symbol of its own.  v6 exported 62 symbols; the 16 that named another symbol plus one pointer are gone: 46."""
-    assert len(_C.EXPORTS) == 46
+    symbol of its own.  v6 exported 62 symbols; the 16 that named another symbol plus one pointer are gone: 46.  ABI v8: an
+    operation of its own has a symbol of its own, too.  The voxel grid, the hash grid, the cube's mip chain and the cube
+    prefilter, which travelled as value codes of dm2_texture_cube, dm2_texture_mip and dm2_texture_mipmaps, got a forward and
+    a backward export each: 54."""
+    assert len(_C.EXPORTS) == 54
     # (these exist in one form only: their `_window` is part of the operation's name, no second symbol stands beside them)
     one_form = {"dm2_bary_derivatives_window", "dm2_shading_vectors_window", "dm2_shading_vectors_backward_window"}
     assert one_form <= set(_C.EXPORTS)
@@ -35,6 +38,28 @@ def test_one_symbol_per_operation():
         assert not re.search(r"_(weights|inside)$", n), n
         assert not re.search(r"backward_(alpha|window)$", n), n
         assert not re.match(r"^dm2_(layers_plan|layers_run|rasterize\w*|coverage\w*|layers_composite\w*)_window$", n), n
+
+
+def test_lookup_ops_share_no_export():
+    """The six lookup records of the shim name six forward and six backward exports, and what the shim calls for one family of
+    tests/shim_trace.py's OPS it calls for no other."""
+    import json
+    import shim_trace
+    ops = [_C._TEXTURE, _C._TEXTURE_CUBE, _C._TEXTURE_VOLUME, _C._HASH_GRID, _C._TEXTURE_MIP, _C._TEXTURE_CUBE_MIP]
+    assert sorted(op.name for op in ops) == sorted(shim_trace.OPS)
+    assert len({op.forward for op in ops}) == len({op.backward for op in ops}) == 6
+    assert len({op.forward for op in ops} | {op.backward for op in ops}) == 12
+    for op in ops:
+        assert op.forward in _C.EXPORTS and op.backward == op.forward + "_backward" and op.backward in _C.EXPORTS, op.name
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "lookup_shim_calls.json")))
+    served = {}
+    for case, rec in golden.items():
+        family = max((n for n in shim_trace.OPS if case.startswith(n + "-")), key=len, default=None)
+        if family is not None:
+            for call in rec["calls"]:
+                served.setdefault(call["export"], set()).add(family)
+    assert set(served) == {op.forward for op in ops} | {op.backward for op in ops}
+    assert all(len(f) == 1 for f in served.values()), served
 
 
 def header_struct(name):

@@ -1,4 +1,4 @@
-"""The definition of Renderer.cube_prefilter (tests/cube_prefilter_ref.py, include/dm2_hip.h: DM2_MIP_FILTER_CUBE_GGX) on the
+"""The definition of Renderer.cube_prefilter (tests/cube_prefilter_ref.py, include/dm2_hip.h: dm2_cube_prefilter) on the
 CPU: the lobe's symmetry to the bit, self-membership, where the cut bites, the hemisphere at roughness 1, a constant cube, the
 first-order cosine convolution against its analytic value; and the shim's and the front end's argument errors, which need no
 GPU."""
@@ -10,6 +10,7 @@ import torch
 
 import cube_prefilter_ref as ref
 import texture_cube_ref as cref
+from util import assert_own_exports
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -116,7 +117,7 @@ def test_surface():
     assert list(inspect.signature(dm2.Renderer.cube_prefilter).parameters) == ["self", "tex", "max_mip_level", "norm"]
     assert list(inspect.signature(dm2.Renderer.cube_prefilter_norm).parameters) == ["N", "max_mip_level", "device"]
     assert dm2.LayeredRenderer.cube_prefilter is dm2.Renderer.cube_prefilter
-    assert _C.MIP_FILTER_CUBE_GGX == 0x40000000
+    assert_own_exports("dm2_cube_prefilter")                             # its own two symbols, no value code
     for name in ("cube_prefilter_cuda", "cube_prefilter_transpose_cuda"):
         assert callable(getattr(_C, name))
 

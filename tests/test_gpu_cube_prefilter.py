@@ -1,4 +1,4 @@
-"""Renderer.cube_prefilter / dm2_texture_mipmaps with DM2_MIP_FILTER_CUBE_GGX on the GPU against the contract's restatement
+"""Renderer.cube_prefilter / dm2_cube_prefilter on the GPU against the contract's restatement
 (tests/cube_prefilter_ref.py): the whole operator from one one-hot call (exact zeros off the members, 4 * 2^-24 on them); dense
 inputs, the transpose and the adjoint identity against the float64 sums under the derived bound (members + 4) 2^-24 sum |K Om x|;
 determinism; the public op and its gradient; the path into texture(..., "cube", mip_level=...); refusals at the C ABI.
@@ -217,29 +217,27 @@ def test_end_to_end_into_the_cube_lookup():
 
 def test_refusals_at_the_abi():
     lib = _C.load_library()
-    code = _C.MIP_FILTER_CUBE_GGX | 0xFFFF
     N, C = 8, 3
     T = ref.layout(N)[2]
     x = torch.ones((6, T, C), device="cuda")
     y = torch.full((6, T, C), -7.0, device="cuda")
     p = lambda a: ctypes.c_void_p(a.data_ptr())
-    for fn in (lib.dm2_texture_mipmaps, lib.dm2_texture_mipmaps_backward):
-        for args, text in (((6, N, 4, C, code, p(x), p(y)), b"square"), ((6, 4, N, C, code, p(x), p(y)), b"square"),
-                           ((5, N, N, C, code, p(x), p(y)), b"multiple of 6"), ((7, N, N, C, code, p(x), p(y)), b"multiple of 6"),
-                           ((6, N, N, C, code, None, p(y)), b"null"), ((6, N, N, C, code, p(x), None), b"null"),
-                           ((6, N, N, 0, code, p(x), p(y)), b"channels"), ((6, 0, 0, C, code, p(x), p(y)), b"at least 1"),
-                           ((6, N, N, C, code | 0x10000, p(x), p(y)), b"unknown bits")):
+    for fn in (lib.dm2_cube_prefilter, lib.dm2_cube_prefilter_backward):
+        for args, text in (((1, N, C, -1, None, p(y)), b"null"), ((1, N, C, -1, p(x), None), b"null"),
+                           ((1, N, 0, -1, p(x), p(y)), b"channels"), ((1, 0, C, -1, p(x), p(y)), b"at least 1"),
+                           ((-1, N, C, -1, p(x), p(y)), b"number of cubes"), ((10923, N, C, -1, p(x), p(y)), b"number of cubes")):
             assert fn(*args, None) == 1 and text in lib.dm2_last_error(), (args, lib.dm2_last_error())
         torch.cuda.synchronize()
         assert (y == -7.0).all()                                          # a refused call writes nothing
-        assert fn(6, 5, 5, C, code, None, None, None) == 0                # T == 0: nothing runs
-        assert fn(0, N, N, C, code, None, None, None) == 0
-        assert fn(6, N, N, C, _C.MIP_FILTER_CUBE_GGX | 0, None, None, None) == 0     # a limit of no levels
-    # the limit rides in the low 16 bits: 1 builds level 1 alone, as r = 1
+        assert fn(1, 5, C, -1, None, None, None) == 0                     # T == 0: nothing runs
+        assert fn(0, N, C, -1, None, None, None) == 0
+        assert fn(10922, 5, C, -1, None, None, None) == 0                 # (the most cubes a call takes; T == 0)
+        assert fn(1, N, C, 0, None, None, None) == 0                      # a limit of no levels
+    # the limit is a word of its own: 1 builds level 1 alone, as r = 1
     T1 = ref.layout(N, 1)[2]
     x1 = torch.ones((6, T1, 1), device="cuda")
     y1 = torch.empty_like(x1)
-    assert lib.dm2_texture_mipmaps(6, N, N, 1, _C.MIP_FILTER_CUBE_GGX | 1, p(x1), p(y1), None) == 0
+    assert lib.dm2_cube_prefilter(1, N, 1, 1, p(x1), p(y1), None) == 0
     torch.cuda.synchronize()
     W, wb = ref.norm64(N, 1)
     assert (np.abs(_np(y1)[..., 0] - W) <= wb).all()

@@ -1,4 +1,4 @@
-"""Renderer.hash_grid / dm2_texture_cube with DM2_TEX_HASH_GRID_CODE on the GPU against the contract's restatement
+"""Renderer.hash_grid / dm2_hash_grid on the GPU against the contract's restatement
 (tests/hash_grid_ref.py): the forward bit-equal to forward32, both gradients per element within
 |g - g64| <= 1e-5 max|g64| + 8 eps32 sum|terms| (util.summation_bound) with exact zeros where no term arrives; a single dense level
 against texture3d's kernels; the two routes of the table scatter; empty slots next to a NaN-poisoned table; alignment and strides;
@@ -288,17 +288,18 @@ def test_needs_input_grad_and_repeats():
     mv, proj = scenes.camera(32, 16)
     r = dm2.Renderer(mv[None].cuda(), proj[None].cuda(), 32, 16, "cuda")
     lib = _C.load_library()
-    real_b, real_f = lib.dm2_texture_cube_backward, lib.dm2_texture_cube
+    real_b, real_f = lib.dm2_hash_grid_backward, lib.dm2_hash_grid
     calls, fwd_calls = [], []
+    words = lambda a: (a[5], a[6]) + a[8:11]                                 # (log2_rows, num_levels, growth16, filter, boundary)
 
     def spy(*a):
-        calls.append((a[7], a[-3].value is not None, a[-2].value is not None))       # (filter code, dL_dtable, dL_dxyz not NULL)
+        calls.append((words(a), a[-3].value is not None, a[-2].value is not None))   # (the words, dL_dtable, dL_dxyz not NULL)
         return real_b(*a)
 
     def spy_f(*a):
-        fwd_calls.append(a[7])
+        fwd_calls.append(words(a))
         return real_f(*a)
-    lib.dm2_texture_cube_backward, lib.dm2_texture_cube = spy, spy_f
+    lib.dm2_hash_grid_backward, lib.dm2_hash_grid = spy, spy_f
     try:
         res = {}
         for need_t, need_p in ((True, True), (True, False), (False, True), (True, True)):
@@ -306,7 +307,7 @@ def test_needs_input_grad_and_repeats():
             out = r.hash_grid(u, t, _cu(rl), N, q / 16, boundary_mode="wrap")
             out.backward(g)
             res.setdefault((need_t, need_p), []).append((t.grad, u.grad))
-        code = _C.hash_grid_code(6, NL, q / 16, "linear", "wrap")
+        code = (6, NL, q, _C.TEX_FILTERS["linear"], _C.TEX_BOUNDARIES["wrap"])
         assert calls == [(code, True, True), (code, True, False), (code, False, True), (code, True, True)]
         assert fwd_calls == [code] * 4
         assert res[(True, False)][0][1] is None and res[(False, True)][0][0] is None
@@ -322,7 +323,7 @@ def test_needs_input_grad_and_repeats():
         assert _C.hash_grid_backward_cuda(_cu(p), _cu(table), _cu(rl), N, q / 16, "linear", "clamp", g, False, False) == (None, None)
         assert not calls and len(fwd_calls) == 1
     finally:
-        lib.dm2_texture_cube_backward, lib.dm2_texture_cube = real_b, real_f
+        lib.dm2_hash_grid_backward, lib.dm2_hash_grid = real_b, real_f
 
 
 @pytest.mark.parametrize("family", ("all_zero", "one_pixel_per_tile", "one_channel"))
@@ -375,39 +376,38 @@ def test_argument_checks():
     # the C ABI refuses what the shim would never send
     lib = _C.load_library()
     ptr = lambda t: _C._ptr(t)
-    lin, CL, WR, HG = _C.TEX_FILTERS["linear"], _C.TEX_VOLUME_BOUNDARIES["clamp"], _C.TEX_VOLUME_BOUNDARIES["wrap"], _C.TEX_HASH_GRID
-    code = lambda log2T=6, NL=4, q=24: HG | (log2T << 12) | ((NL - 1) << 17) | ((q - 17) << 22)
+    lin, near, CL, WR = _C.TEX_FILTERS["linear"], _C.TEX_FILTERS["nearest"], _C.TEX_BOUNDARIES["clamp"], _C.TEX_BOUNDARIES["wrap"]
     dp = torch.empty_like(p)
     tab, dtab = torch.zeros((2, 4 * 64 * 8), device="cuda")                # room for every accepted call below: F up to 8
     outb, gout = torch.zeros((2, p.shape[:4].numel() * 32), device="cuda")
 
-    def fwd(c, N=16, C=8, view_textures=0, xyz=p):
-        return lib.dm2_texture_cube(2, 4, 5, 3, N, C, view_textures, c, ptr(rl), ptr(xyz) if xyz is not None else None, ptr(tab), ptr(outb), None)
+    def fwd(f=lin, b=CL, N=16, log2T=6, NL=4, F=2, q=24, xyz=p):
+        return lib.dm2_hash_grid(2, 4, 5, 3, N, log2T, NL, F, q, f, b, ptr(rl), ptr(xyz) if xyz is not None else None, ptr(tab), ptr(outb), None)
 
-    def bwd(c, N=16, C=8, view_textures=0, xyz=p):
-        return lib.dm2_texture_cube_backward(2, 4, 5, 3, N, C, view_textures, c, ptr(rl), ptr(xyz) if xyz is not None else None,
-                                             ptr(tab), ptr(gout), ptr(dtab), ptr(dp), None)
-    for call in (fwd, bwd):
-        for c in (code() | lin | CL, code() | lin | WR, code() | CL, code() | WR):
-            assert call(c) == 0, hex(c)
-        assert call(code() | lin | CL, C=4) == 0 and call(code() | lin | CL, C=16) == 0 and call(code() | lin | CL, C=32) == 0
-        assert call(code() | lin | CL, view_textures=1) == 1
-        assert call(code() | lin) == 1                                     # no boundary
-        assert call(code() | lin | CL | WR) == 1                           # both
-        assert call(code() | lin | CL, C=9) == 1                           # C % NL != 0
-        assert call(code() | lin | CL, C=12) == 1 and call(code() | lin | CL, C=64) == 1      # F = 3, F = 16
-        assert call(code(log2T=3) | lin | CL) == 1 and call(code(log2T=25) | lin | CL) == 1 and call(code(log2T=31) | lin | CL) == 1
-        assert call(code() | lin | CL, N=0) == 1
-        assert call(code(q=32) | lin | CL, N=2 ** 18) == 1                 # R_3 = 2^21
-        assert call(code(q=17) | lin | CL, N=2 ** 20 + 1) == 1
-        assert call(code(log2T=24, NL=32) | lin | CL, N=1, C=128) == 1     # NL T F = 2^31
-        assert call(code() | lin | CL, xyz=None) == 1                      # NULL xyz
-        for hi in range(26, 32):
-            assert call(code() | lin | CL | (1 << hi if hi < 31 else -(1 << 31))) == 1, hi
+    def bwd(f=lin, b=CL, N=16, log2T=6, NL=4, F=2, q=24, xyz=p):
+        return lib.dm2_hash_grid_backward(2, 4, 5, 3, N, log2T, NL, F, q, f, b, ptr(rl), ptr(xyz) if xyz is not None else None,
+                                          ptr(tab), ptr(gout), ptr(dtab), ptr(dp), None)
+    # ABI 7's word for the same call: a filter of the cube lookup, which knows no such filter any more
+    former = 0x800 | (6 << 12) | ((4 - 1) << 17) | ((24 - 17) << 22) | lin | 0x100
+    cube = lambda f: lib.dm2_texture_cube(2, 4, 5, 3, 16, 8, 0, f, ptr(rl), ptr(p), ptr(tab), ptr(outb), None)
+    cube_b = lambda f: lib.dm2_texture_cube_backward(2, 4, 5, 3, 16, 8, 0, f, ptr(rl), ptr(p), ptr(tab), ptr(gout), ptr(dtab), ptr(dp), None)
+    for call, old in ((fwd, cube), (bwd, cube_b)):
+        for f, b in ((lin, CL), (lin, WR), (near, CL), (near, WR)):
+            assert call(f, b) == 0, (f, b)
+        assert call(F=1) == 0 and call(F=4) == 0 and call(F=8) == 0
+        assert call(b=2) == 1 and call(b=-1) == 1                          # an unknown boundary
+        assert call(F=3) == 1 and call(F=16) == 1 and call(F=0) == 1
+        assert call(NL=0) == 1 and call(NL=33) == 1
+        assert call(q=16) == 1 and call(q=33) == 1
+        assert call(log2T=3) == 1 and call(log2T=25) == 1 and call(log2T=31) == 1
+        assert call(N=0) == 1
+        assert call(q=32, N=2 ** 18) == 1                                  # R_3 = 2^21
+        assert call(q=17, N=2 ** 20 + 1) == 1
+        assert call(log2T=24, NL=32, N=1, F=4) == 1                        # NL T F = 2^31
+        assert call(xyz=None) == 1                                         # NULL xyz
         for unknown in (2, 4, 0x80, 0x400):
-            assert call(code() | lin | CL | unknown) == 1, unknown
-        for field in (1 << 12, 6 << 12, 3 << 17, 7 << 22, code() & ~HG):    # the code's fields without the hash bit: unknown bits
-            assert call(lin | CL | field) == 1 and call(lin | field) == 1, hex(field)
+            assert call(f=lin | unknown) == 1, unknown                     # an unknown filter
+        assert old(former) == 1 and old(former & ~0x800) == 1 and old(former & ~0x100) == 1, hex(former)
     torch.cuda.synchronize()
     assert not _np(dtab).any() and not _np(outb).any()                    # (a zero table out, g = 0 added)
 

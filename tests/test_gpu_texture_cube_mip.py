@@ -1,5 +1,5 @@
-"""Renderer.texture(filter_mode="linear-mipmap-linear", boundary_mode="cube", mip_level=...) / dm2_texture_mip with
-DM2_TEX_BOUNDARY_CUBE on the GPU against the contract's restatement (tests/texture_cube_mip_ref.py): the forward bit-equal to
+"""Renderer.texture(filter_mode="linear-mipmap-linear", boundary_mode="cube", mip_level=...) / dm2_texture_cube_mip
+on the GPU against the contract's restatement (tests/texture_cube_mip_ref.py): the forward bit-equal to
 forward32; dL/dtex, dL/dmip and dL/ddirs within GRAD_TOL of grads64, dL/dmip_level per element; the level's branch points; seams
 and corners at every level size; both routes of the texel scatter; alignment; needs_input_grad; argument checks down to the C
 ABI; the module path from rasterize to the gradients of a per-face roughness, of the cube and of the vertices."""
@@ -335,7 +335,7 @@ def test_needs_input_grad():
         return real(*a)
     _C.texture_cube_mip_backward_cuda = spy
     lib = _C.load_library()
-    real_b = lib.dm2_texture_mip_backward
+    real_b = lib.dm2_texture_cube_mip_backward
     launches = []
     try:
         res = {}
@@ -354,7 +354,7 @@ def test_needs_input_grad():
             else:
                 assert rel_linf(_np(res[need][k]), _np(res[combos[0]][k])) <= GRAD_TOL
         del calls[:]
-        lib.dm2_texture_mip_backward = lambda *a: launches.append(tuple(bool(p.value) for p in a[-4:-1])) or real_b(*a)
+        lib.dm2_texture_cube_mip_backward = lambda *a: launches.append(tuple(bool(p.value) for p in a[-4:-1])) or real_b(*a)
         out = r.texture(_cu(d), _cu(tex), _cu(rl), "linear-mipmap-linear", "cube", mip=_cu(mip), mip_level=_cu(lod))
         assert out.grad_fn is None
         w = torch.ones(1, device="cuda", requires_grad=True)
@@ -368,7 +368,7 @@ def test_needs_input_grad():
         assert launches == [(True, False, False), (False, True, False), (False, False, True)]     # the other pointers NULL
     finally:
         _C.texture_cube_mip_backward_cuda = real
-        lib.dm2_texture_mip_backward = real_b
+        lib.dm2_texture_cube_mip_backward = real_b
 
 
 @pytest.mark.parametrize("C", [4, 16])
@@ -433,11 +433,11 @@ def test_argument_checks():
     assert torch.equal(r.texture(d, tex, rl, "linear-mipmap-linear", "cube", mip=mip, mip_level=lod), ok)
     # degenerate sizes: zeros without a launch
     lib = _C.load_library()
-    real_f, real_b = lib.dm2_texture_mip, lib.dm2_texture_mip_backward
+    real_f, real_b = lib.dm2_texture_cube_mip, lib.dm2_texture_cube_mip_backward
     launches = []
     try:
-        lib.dm2_texture_mip = lambda *a: launches.append("f") or real_f(*a)
-        lib.dm2_texture_mip_backward = lambda *a: launches.append("b") or real_b(*a)
+        lib.dm2_texture_cube_mip = lambda *a: launches.append("f") or real_f(*a)
+        lib.dm2_texture_cube_mip_backward = lambda *a: launches.append("b") or real_b(*a)
         for shape in ((0, 4, 5, 2), (2, 0, 5, 2), (2, 4, 5, 0)):
             d0, l0 = torch.ones(shape + (3,), device="cuda"), torch.ones(shape, device="cuda")
             out = _C.texture_cube_mip_cuda(d0, l0, tex, mip, None)
@@ -446,21 +446,23 @@ def test_argument_checks():
             assert tuple(dd.shape) == shape + (3,) and tuple(dl.shape) == shape and not dt.any() and not dm.any()
         assert not launches
     finally:
-        lib.dm2_texture_mip, lib.dm2_texture_mip_backward = real_f, real_b
-    # the C ABI: code 2 belongs to dm2_texture_mip and its backward, with square faces
+        lib.dm2_texture_cube_mip, lib.dm2_texture_cube_mip_backward = real_f, real_b
+    # the C ABI: the cube's chain has its own two symbols; boundary 2, its word under ABI 7, is unknown to the 2D ops
     p = lambda t: _C._ptr(t)
     rows = torch.zeros((2, 4, 5, 3, 4), device="cuda")
-    assert lib.dm2_texture_mip(2, 4, 5, 3, 8, 8, 3, 0, 2, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None) == 0
-    assert lib.dm2_texture_mip(2, 4, 5, 3, 8, 4, 3, 0, 2, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None) == 1
-    assert lib.dm2_texture_mip(2, 4, 5, 3, 18919, 18919, 3, 0, 2, 0, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None) == 1
-    assert lib.dm2_texture_mip(2, 4, 5, 3, 8, 8, 3, 0, 2, -1, p(rl), p(d), p(lod), p(tex), None, p(ok), None) == 1
-    assert lib.dm2_texture_mip(2, 4, 5, 3, 8, 8, 3, 0, 7, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None) == 1
-    assert lib.dm2_texture_mip_backward(2, 4, 5, 3, 8, 8, 3, 0, 2, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None, None, p(rows),
-                                        None) == 0
-    assert lib.dm2_texture_mip_backward(2, 4, 5, 3, 8, 4, 3, 0, 2, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None, None, p(rows),
-                                        None) == 1
-    assert lib.dm2_texture_mip_backward(2, 4, 5, 3, 8, 8, 3, 0, 2, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None, None,
-                                        ctypes_offset(rows, 4), None) == 1
+    assert lib.dm2_texture_cube_mip(2, 4, 5, 3, 8, 3, 0, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None) == 0
+    assert lib.dm2_texture_cube_mip(2, 4, 5, 3, 18919, 3, 0, 0, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None) == 1
+    assert lib.dm2_texture_cube_mip(2, 4, 5, 3, 8, 3, 0, -1, p(rl), p(d), p(lod), p(tex), None, p(ok), None) == 1
+    assert lib.dm2_texture_cube_mip_backward(2, 4, 5, 3, 8, 3, 0, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None, None, p(rows),
+                                             None) == 0
+    assert lib.dm2_texture_cube_mip_backward(2, 4, 5, 3, 18919, 3, 0, 0, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None, None,
+                                             p(rows), None) == 1
+    assert lib.dm2_texture_cube_mip_backward(2, 4, 5, 3, 8, 3, 0, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None, None,
+                                             ctypes_offset(rows, 4), None) == 1
+    for boundary in (2, 7):
+        assert lib.dm2_texture_mip(2, 4, 5, 3, 8, 8, 3, 0, boundary, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None) == 1
+        assert lib.dm2_texture_mip_backward(2, 4, 5, 3, 8, 8, 3, 0, boundary, -1, p(rl), p(d), p(lod), p(tex), p(mip), p(ok), None, None,
+                                            p(rows), None) == 1
     assert lib.dm2_texture(2, 4, 5, 3, 8, 8, 3, 0, 1, 2, p(rl), p(d), p(tex), p(ok), None) == 1
     assert lib.dm2_texture_backward(2, 4, 5, 3, 8, 8, 3, 0, 1, 2, p(rl), p(d), p(tex), p(ok), None, p(rows), None) == 1
     torch.cuda.synchronize()

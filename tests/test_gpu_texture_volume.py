@@ -1,4 +1,4 @@
-"""Renderer.texture3d / dm2_texture_cube with DM2_TEX_VOLUME_* on the GPU against the contract's restatement
+"""Renderer.texture3d / dm2_texture_volume on the GPU against the contract's restatement
 (tests/texture_volume_ref.py): the forward bit-equal to forward32, both gradients per element within
 |g - g64| <= 1e-5 max|g64| + 8 eps32 sum|terms| (util.summation_bound) with exact zeros where no term arrives; the two routes of
 the voxel scatter; empty slots next to a NaN-poisoned grid; alignment and strides; needs_input_grad; repeats; the argument checks
@@ -22,7 +22,7 @@ W, H, BIDX = 40, 24, [1, 0]            # no multiple of the 16 x 16 tile either 
 NS = (1, 2, 5, 16)
 CS = (1, 2, 3, 4, 5, 8, 16)           # every chunk length of the scatter (1, 2, 3, 4, 4 + 1), the four-channel reads at 4, 8 and 16
 LS = (1, 3)
-VOL_CLAMP, VOL_WRAP = _C.TEX_VOLUME_BOUNDARIES["clamp"], _C.TEX_VOLUME_BOUNDARIES["wrap"]
+CLAMP, WRAP = _C.TEX_BOUNDARIES["clamp"], _C.TEX_BOUNDARIES["wrap"]
 
 
 def _bits(a):
@@ -244,13 +244,13 @@ def test_needs_input_grad_and_repeats():
     mv, proj = scenes.camera(32, 16)
     r = dm2.Renderer(mv[None].cuda(), proj[None].cuda(), 32, 16, "cuda")
     lib = _C.load_library()
-    real_b = lib.dm2_texture_cube_backward
+    real_b = lib.dm2_texture_volume_backward
     calls = []
 
     def spy(*a):
-        calls.append((a[7], a[-3].value is not None, a[-2].value is not None))       # (filter code, dL_dgrid, dL_dxyz not NULL)
+        calls.append((a[7:9], a[-3].value is not None, a[-2].value is not None))     # ((filter, boundary), dL_dgrid, dL_dxyz not NULL)
         return real_b(*a)
-    lib.dm2_texture_cube_backward = spy
+    lib.dm2_texture_volume_backward = spy
     try:
         res = {}
         for need_g, need_p in ((True, True), (True, False), (False, True), (True, True)):
@@ -258,7 +258,7 @@ def test_needs_input_grad_and_repeats():
             out = r.texture3d(u, t, _cu(rl), boundary_mode="wrap")
             out.backward(g)
             res.setdefault((need_g, need_p), []).append((t.grad, u.grad))
-        code = _C.TEX_FILTERS["linear"] | VOL_WRAP
+        code = (_C.TEX_FILTERS["linear"], WRAP)
         assert calls == [(code, True, True), (code, True, False), (code, False, True), (code, True, True)]
         assert res[(True, False)][0][1] is None and res[(False, True)][0][0] is None
         first, again = res[(True, True)]
@@ -276,7 +276,7 @@ def test_needs_input_grad_and_repeats():
         assert _C.texture_volume_backward_cuda(_cu(p), _cu(grid), _cu(rl), "linear", "clamp", g, False, False) == (None, None)
         assert not calls
     finally:
-        lib.dm2_texture_cube_backward = real_b
+        lib.dm2_texture_volume_backward = real_b
 
 
 def test_argument_checks():
@@ -311,20 +311,25 @@ def test_argument_checks():
     q = lambda t: _C._ptr(t)
     lin = _C.TEX_FILTERS["linear"]
     dp = torch.empty_like(p)
-    fwd =lambda N, code, xyz=p: lib.dm2_texture_cube(2, 4, 5, 3, N, 3, 0, code, q(rl), q(xyz) if xyz is not None else None, q(grid), q(ok), None)
-    bwd = lambda N, code, xyz=p: lib.dm2_texture_cube_backward(2, 4, 5, 3, N, 3, 0, code, q(rl), q(xyz) if xyz is not None else None,
-                                                                q(grid), q(ok), q(grid), q(dp), None)
-    for call in (fwd, bwd):
-        for code in (lin | VOL_CLAMP, lin | VOL_WRAP, VOL_CLAMP, VOL_WRAP):
-            assert call(8, code) == 0, code
-        assert call(0, lin | VOL_CLAMP) == 1
-        assert call(1291, lin | VOL_CLAMP) == 1                           # 1291^3 >= 2^31 > 1290^3
-        assert call(2 ** 31 - 1, lin | VOL_WRAP) == 1
-        assert call(8, lin | VOL_CLAMP | VOL_WRAP) == 1                   # both boundaries
+    nearest = _C.TEX_FILTERS["nearest"]
+    fwd = lambda N, f, b, xyz=p: lib.dm2_texture_volume(2, 4, 5, 3, N, 3, 0, f, b, q(rl), q(xyz) if xyz is not None else None, q(grid),
+                                                        q(ok), None)
+    bwd = lambda N, f, b, xyz=p: lib.dm2_texture_volume_backward(2, 4, 5, 3, N, 3, 0, f, b, q(rl), q(xyz) if xyz is not None else None,
+                                                                 q(grid), q(ok), q(grid), q(dp), None)
+    cube = lambda f: lib.dm2_texture_cube(2, 4, 5, 3, 8, 3, 0, f, q(rl), q(p), q(grid), q(ok), None)
+    cube_b = lambda f: lib.dm2_texture_cube_backward(2, 4, 5, 3, 8, 3, 0, f, q(rl), q(p), q(grid), q(ok), q(grid), q(dp), None)
+    for call, old in ((fwd, cube), (bwd, cube_b)):
+        for f, b in ((lin, CLAMP), (lin, WRAP), (nearest, CLAMP), (nearest, WRAP)):
+            assert call(8, f, b) == 0, (f, b)
+        assert call(0, lin, CLAMP) == 1
+        assert call(1291, lin, CLAMP) == 1                                # 1291^3 >= 2^31 > 1290^3
+        assert call(2 ** 31 - 1, lin, WRAP) == 1
+        assert call(8, lin, 2) == 1 and call(8, lin, -1) == 1             # an unknown boundary
         for unknown in (2, 4, 0x80, 0x400, 0x40000000):
-            assert call(8, lin | VOL_CLAMP | unknown) == 1, unknown
-            assert call(8, lin | unknown) == 1, unknown                   # (and without the volume bit, as before)
-        assert call(8, lin | VOL_CLAMP, None) == 1                        # NULL xyz
+            assert call(8, lin | unknown, CLAMP) == 1, unknown            # an unknown filter
+            assert old(lin | unknown) == 1, unknown                       # (and of the cube's own symbol, as before)
+        assert old(0x101) == 1 and old(0x201) == 1                        # ABI 7's volume codes: unknown filters of the cube now
+        assert call(8, lin, CLAMP, None) == 1                             # NULL xyz
     torch.cuda.synchronize()
     assert not _np(grid).any()                                            # (the accepted backward calls added g = ok = 0)
 

@@ -3,8 +3,6 @@ integers, to the volume contract's restatement on a single dense level, to a flo
 to central differences, and its edge cases (collisions, the empty rule) to what the contract says of them; and the front end's
 and the shim's argument checks, which need no GPU."""
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,7 @@ import torch
 
 import hash_grid_ref as ref
 import texture_volume_ref as vol
-from util import ROOT, scenes
+from util import assert_own_exports, scenes
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -250,17 +248,7 @@ def test_empty_rule_at_the_finest_level_is_at_any_level():
 
 
 def test_surface_and_argument_checks():
-    hdr = open(os.path.join(ROOT, "include", "dm2_hip.h")).read()
-    bit = int(re.search(r"^#define DM2_TEX_HASH_GRID (0x[0-9a-fA-F]+)\b", hdr, flags=re.M).group(1), 16)
-    assert bit == _C.TEX_HASH_GRID == 0x800
-    macro = re.search(r"^#define DM2_TEX_HASH_GRID_CODE\(log2T, NL, q\) (.*)$", hdr, flags=re.M).group(1)
-    for log2T, NL, q in ((4, 1, 17), (24, 32, 32), (19, 16, 24), (15, 7, 29)):
-        want = eval(macro.replace("DM2_TEX_HASH_GRID", str(bit)), {}, dict(log2T=log2T, NL=NL, q=q))
-        for fm, fcode in _C.TEX_FILTERS.items():
-            for bm, bcode in _C.TEX_VOLUME_BOUNDARIES.items():
-                assert _C.hash_grid_code(log2T, NL, q / 16, fm, bm) == want | fcode | bcode
-        assert want < 2 ** 26 and want & 0x7FF == 0                         # clear of the filter and boundary bits and of bits 26..31
-    assert "dm2_texture_cube" in _C.EXPORTS and not any("hash" in e for e in _C.EXPORTS)             # a value code, no new symbol
+    assert_own_exports("dm2_hash_grid")                                  # its own two symbols, no value code
     assert "HashGridFunction" in dm2.__all__ and issubclass(dm2.HashGridFunction, torch.autograd.Function)
     assert dm2.LayeredRenderer.hash_grid is dm2.Renderer.hash_grid
     sig = inspect.signature(dm2.Renderer.hash_grid)

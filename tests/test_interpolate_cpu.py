@@ -99,7 +99,7 @@ def test_interface():
     for name in ("dm2_interpolate", "dm2_interpolate_backward"):
         assert re.search(r"\bint\s+%s\s*\(" % name, header), name
         assert name in _C.EXPORTS
-    assert _C.ABI_VERSION == 7
+    assert _C.ABI_VERSION == 8
     assert issubclass(dm2.InterpolateFunction, torch.autograd.Function) and "InterpolateFunction" in dm2.__all__
     assert callable(dm2.Renderer.interpolate) and dm2.LayeredRenderer.interpolate is dm2.Renderer.interpolate
     rl, bary, attr, af, g = (torch.from_numpy(x) for x in _hand(3, False))

@@ -3,8 +3,6 @@ clamped ends and the integer levels against the cube op's restatement; constant 
 level size; the gradients, the level's among them, against float64 central differences; the box chain; what the feature is for
 (a checkerboard cube is flat at level 1); and the interface the feature adds."""
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,7 @@ import pytest
 import texture_cube_mip_ref as ref
 import texture_cube_ref as cref
 import texture_mip_ref as mref
-from util import ROOT
+from util import assert_own_exports
 
 U32 = 2.0 ** -24                    # unit roundoff of float32
 
@@ -283,15 +281,14 @@ def test_keys_and_level_edges():
 
 
 def test_interface():
-    """Fails without the feature: the boundary code, the two wrappers, the autograd function, the keyword; CPU tensors are
+    """Fails without the feature: the two exports, the two wrappers, the autograd function, the keyword; CPU tensors are
     refused like everywhere else; mip_level with another mode combination is a ValueError naming it."""
     import torch
 
     import dmesh2_renderer_amd as dm2
     from dmesh2_renderer_amd import _C
-    hdr = open(os.path.join(ROOT, "include", "dm2_hip.h")).read()
-    assert re.search(r"^#define DM2_TEX_BOUNDARY_CUBE 2\b", hdr, flags=re.M)
-    assert _C.TEX_BOUNDARY_CUBE == 2 and "cube" not in _C.TEX_BOUNDARIES
+    assert_own_exports("dm2_texture_cube_mip")                           # its own two symbols, no boundary code
+    assert "cube" not in _C.TEX_BOUNDARIES
     assert callable(_C.texture_cube_mip_cuda) and callable(_C.texture_cube_mip_backward_cuda)
     assert "TextureCubeMipFunction" in dm2.__all__ and issubclass(dm2.TextureCubeMipFunction, torch.autograd.Function)
     params = list(inspect.signature(dm2.Renderer.texture).parameters)

@@ -2,15 +2,13 @@
 float64 on the CPU), its gradients to central differences, its edge cases to what the contract says of them; and the front
 end's and the shim's argument checks, which need no GPU."""
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import texture_volume_ref as ref
-from util import ROOT, scenes
+from util import assert_own_exports, scenes
 
 import dmesh2_renderer_amd as dm2
 from dmesh2_renderer_amd import _C
@@ -213,12 +211,14 @@ def test_distinct_voxels_per_tile():
 
 
 def test_surface_and_argument_checks():
-    hdr = open(os.path.join(ROOT, "include", "dm2_hip.h")).read()
-    codes = {name: int(re.search(rf"^#define DM2_TEX_VOLUME_{name.upper()} (0x[0-9a-fA-F]+)\b", hdr, flags=re.M).group(1), 16)
-             for name in ref.BOUNDARIES}
-    assert codes == _C.TEX_VOLUME_BOUNDARIES and codes["clamp"] != codes["wrap"]
-    assert all(c & (c - 1) == 0 and c > max(_C.TEX_FILTERS.values()) for c in codes.values())       # single bits clear of the filter codes
-    assert "dm2_texture_cube" in _C.EXPORTS and not any("volume" in e for e in _C.EXPORTS)           # a value code, no new symbol
+    assert_own_exports("dm2_texture_volume")                             # its own two symbols, no value code
+    assert set(ref.BOUNDARIES) == set(_C.TEX_BOUNDARIES) and _C._TEXTURE_VOLUME.boundaries is _C.TEX_BOUNDARIES
+    lib = _C.load_library()                                              # ABI 7's words, still named in the shim: refused (no GPU needed)
+    for word in _C.TEX_VOLUME_BOUNDARIES.values():
+        for filt in _C.TEX_FILTERS.values():
+            assert lib.dm2_texture_cube(2, 4, 5, 3, 8, 3, 0, filt | word, *[None] * 5) == 1
+            assert b"unknown filter" in lib.dm2_last_error()
+            assert lib.dm2_texture_cube_backward(2, 4, 5, 3, 8, 3, 0, filt | word, *[None] * 7) == 1
     assert "TextureVolumeFunction" in dm2.__all__ and issubclass(dm2.TextureVolumeFunction, torch.autograd.Function)
     assert dm2.LayeredRenderer.texture3d is dm2.Renderer.texture3d
     sig = inspect.signature(dm2.Renderer.texture3d)

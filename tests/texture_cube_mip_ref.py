@@ -1,5 +1,5 @@
 """Restatement of texture(filter_mode="linear-mipmap-linear", boundary_mode="cube", mip_level=...) (include/dm2_hip.h:
-dm2_texture_mip / dm2_texture_mip_backward with DM2_TEX_BOUNDARY_CUBE) in numpy, on tests/texture_cube_ref.py's stage / blend per
+dm2_texture_cube_mip / dm2_texture_cube_mip_backward) in numpy, on tests/texture_cube_ref.py's stage / blend per
 level and tests/texture_mip_ref.py's layout.
 
 dirs (B,H,W,L,3); level (B,H,W,L) = the level of detail per slot; tex (6,N,N,C) or (B,6,N,N,C) = level 0; mip (6,T,C) or

@@ -1,5 +1,5 @@
-"""Restatement of the volume contract of Renderer.texture3d (include/dm2_hip.h: dm2_texture_cube / dm2_texture_cube_backward with
-DM2_TEX_VOLUME_CLAMP or DM2_TEX_VOLUME_WRAP) in numpy.
+"""Restatement of the volume contract of Renderer.texture3d (include/dm2_hip.h: dm2_texture_volume /
+dm2_texture_volume_backward) in numpy.
 
 xyz (B,H,W,L,3) = a position per slot in the grid's unit cube, x along the grid's last spatial axis and z along its first; grid
 (N,N,N,C) shared by the views or (B,N,N,N,C), indexed [k][j][i]; render_layers (B,H,W,L) or None.  Per slot, in float32:

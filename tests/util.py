@@ -1,6 +1,7 @@
 """Shared helpers for the tests (CPU side)."""
 import contextlib
 import os
+import re
 import sys
 
 import numpy as np
@@ -18,6 +19,18 @@ ARG_NAMES = [
     "faces_opacity", "verts_ndc", "verts_image", "faces_intense", "aa_temperature", "aa_face_verts",
     "aa_face_edges", "aa_face_edges_iszero", "aa_face_edges_recip", "aa_face_edges_normal",
     "aa_face_edges_normal_c", "len_oarea_buffer", "image_ray_o", "image_ray_d"]
+
+
+def assert_own_exports(forward):
+    """ABI v8: an op that travelled as a value code of another op's symbol has a forward and a backward export of its own,
+    declared in the header, and the codes are gone from the header and from the shim."""
+    hdr = open(os.path.join(ROOT, "include", "dm2_hip.h")).read()
+    for name in (forward, forward + "_backward"):
+        assert name in _C.EXPORTS and re.search(rf"^int {name}\(", hdr, flags=re.M), name
+    for macro in ("DM2_TEX_VOLUME_", "DM2_TEX_HASH_GRID", "DM2_TEX_BOUNDARY_CUBE", "DM2_MIP_FILTER_CUBE_GGX"):
+        assert macro not in hdr, macro
+    for attr in ("TEX_HASH_GRID", "TEX_BOUNDARY_CUBE", "MIP_FILTER_CUBE_GGX", "hash_grid_code"):
+        assert not hasattr(_C, attr), attr
 
 
 @contextlib.contextmanager

@@ -1,4 +1,4 @@
-"""Time Renderer.cube_prefilter (dm2_texture_mipmaps / dm2_texture_mipmaps_backward with DM2_MIP_FILTER_CUBE_GGX), forward under
+"""Time Renderer.cube_prefilter (dm2_cube_prefilter / dm2_cube_prefilter_backward), forward under
 no_grad and forward + backward (the cube requiring grad), with ``norm`` supplied and with ``norm=None`` (built in the call), at
 N = 64, 256, 512 with ``max_mip_level`` chosen so that the last level has faces of 16^2, C = 3.  One JSON line.
 

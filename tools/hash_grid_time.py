@@ -1,4 +1,4 @@
-"""Time Renderer.hash_grid (dm2_texture_cube + dm2_texture_cube_backward with DM2_TEX_HASH_GRID_CODE) next to the plain-torch
+"""Time Renderer.hash_grid (dm2_hash_grid + dm2_hash_grid_backward) next to the plain-torch
 encoding a user would write (``torch_encoding`` below: per level the index arithmetic, eight gathers and a weighted sum, with
 autograd for its backward) at the same slots: forward under no_grad and forward + backward (the table and the position both
 requiring grad), N = 16, growth 1.5, 16 levels, F = 2 and 4, T = 2^15 and 2^19.  Next to it, for context only, texture3d on a

@@ -1,5 +1,5 @@
-"""Time Renderer.texture(..., "linear-mipmap-linear", "cube", mip=chain, mip_level=level) (dm2_texture_mip /
-dm2_texture_mip_backward with DM2_TEX_BOUNDARY_CUBE) next to
+"""Time Renderer.texture(..., "linear-mipmap-linear", "cube", mip=chain, mip_level=level) (dm2_texture_cube_mip /
+dm2_texture_cube_mip_backward) next to
 
   per_level   the route without the op: one "linear" cube call per level over all slots, a torch gather of the two levels
               round each slot's level and a lerp, with autograd (nlev scatters in the backward);

@@ -1,4 +1,4 @@
-"""Time Renderer.texture3d (dm2_texture_cube + dm2_texture_cube_backward with DM2_TEX_VOLUME_CLAMP) next to the lines it
+"""Time Renderer.texture3d (dm2_texture_volume + dm2_texture_volume_backward) next to the lines it
 replaces,
 
     vol = grid.permute(3, 0, 1, 2)[None]                                  # channel-first, as grid_sample wants it
