@@ -480,7 +480,9 @@ static int check_interpolate_sizes(int32_t B, int32_t H, int32_t W, int32_t L, i
     if (B < 0 || H < 0 || W < 0 || L < 0 || F < 0 || N < 0) return fail("interpolate: negative size");
     if (C < 1) return fail("interpolate: C must be at least 1");
     if (view_tables && (int64_t)B * N > 0x7FFFFFFF) return fail("interpolate: B * N must be below 2^31");
-    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || B > 65535) return fail("interpolate: too many slots or views");
+    // (the attr backward's grid is one block per tile and view: tile rows and views are grid dimensions of 16 bits)
+    if (((int64_t)B * H * W * L + 255) / 256 > 0x7FFFFFFF || B > 65535 || ((int64_t)H + dm2::TILE - 1) / dm2::TILE > 65535)
+        return fail("interpolate: too many slots, rows or views");
     return 0;
 }
 

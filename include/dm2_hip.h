@@ -344,7 +344,9 @@ int dm2_rasterize_backward(const dm2_layers_desc* d, const dm2_window* win, cons
  * A slot s is filled when f = render_layers[s] lies in [0, F) and v_k = attr_faces[f][k], k = 0..2, all lie in [0, N):
  *   out[s,c] = (bary[s,0] * attr[v_0,c] + bary[s,1] * attr[v_1,c]) + bary[s,2] * attr[v_2,c]
  * in fp32, in this order, without contraction (bit-exact).  Every other slot is empty: out[s,:] = 0, and neither its bary
- * nor any attr row is read through it.  Every element of out is written: no pre-fill.  C >= 1; B * N < 2^31. */
+ * nor any attr row is read through it.  Every element of out is written: no pre-fill.  C >= 1; B * N < 2^31.
+ * Launch bounds, forward and backward alike (refused with "interpolate: too many slots, rows or views", nothing launched):
+ * B <= 65535; H <= 16 * 65535 (the tile rows of the attr backward's grid); ceil(B * H * W * L / 256) < 2^31. */
 int dm2_interpolate(int32_t B, int32_t H, int32_t W, int32_t L, int32_t F, int32_t N, int32_t C, int32_t view_tables,
                     const int32_t* render_layers, const float* bary, const float* attr, const int32_t* attr_faces,
                     float* out, void* stream);
